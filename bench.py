@@ -4,6 +4,7 @@ SynthesizerTrn.infer on the BASELINE.json headline workload (C3: a 64-utterance 
 batch of ~5 s utterances, phoneme/duration/F0/energy/noise supplied), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--controls all|duration|none]
+                    [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 launches itself: the parent process (which never touches a GPU) starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same args>`
@@ -17,15 +18,23 @@ rank.  Workloads:
 all pad to the GLOBAL frame count (one int all-reduce MAX, SURVEY gotcha G6), broadcast the packed weights from
 rank 0 over RCCL once before timing, and end every step with the gather of the waveforms on rank 0 -- the
 exchange the north star names.  value = valid samples of all ranks / max-over-ranks time; the line also carries the
-per-rank step times (min / max) and the gather's share of a step (a second timed pass without the gather).
+per-rank step times (min / max) and, with --full, the gather's share of a step (a second timed pass without the gather).
 
 A step = one full infer() of one batch with all inputs resident in HBM.  By default TWO batches are in flight per GPU
 (--in-flight 2: two contexts on two HIP streams, step k on context k % 2 -- the frame-rate half of batch k + 1, ~120 short
 launches that leave most of the chip idle, overlaps the generator of batch k); `value` is the throughput of the K timed
-steps, `single_batch` the same K steps with one batch in flight (a step = one batch start to end: the latency figure).  The headline is timed with profiling OFF; the
-per-kernel-class event timing behind `roofline` comes from a second, untimed pass of `--profile-steps` steps.
-At N = 1 rank 0 then times the parity-pinned CPU oracle on a bounded sample of the same batch (`cpu_baseline`)
-and checks the GPU waveform of those utterances against it (`parity`).
+steps.  The headline is timed with profiling OFF.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the secondary measurements, each
+after the timed steps: `single_batch` (the same K steps with one batch in flight, a step = one batch start to end: the
+latency figure), the gather's share of a step (the K steps once more without the exchange), the per-kernel-class event
+timing behind `roofline` (an untimed pass of `--profile-steps` steps), and at N = 1 the parity-pinned CPU oracle timed on
+a bounded sample of the same batch (`cpu_baseline`) with the GPU waveform of those utterances checked against it (`parity`).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- o, x_mask, z, z_p, m_p, logs_p, duration,
+f0, energy (rank 0's utterances under a process group) -- as DIR/<name>.npy in float32 (float64 for integer outputs).  When
+they exceed 64 MiB, every array keeps the same fixed, seeded sample of utterances.  Inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -64,7 +73,7 @@ def parse(argv=None):
     p.add_argument("--controls", default="all", choices=["all", "duration", "none"],
                    help="which control tensors are supplied: all (headline), duration only (F0 / energy predicted), "
                         "none (every predictor of reference models.py:681-708 runs)")
-    p.add_argument("--profile-steps", type=int, default=2, help="untimed steps with per-launch events (roofline)")
+    p.add_argument("--profile-steps", type=int, default=2, help="--full: untimed steps with per-launch events (roofline)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample", type=int, default=16, help="utterances of the batch timed on the CPU oracle")
     p.add_argument("--cpu-runs", type=int, default=3, help="timed CPU-oracle runs (the median is reported) after one warm-up run")
@@ -88,7 +97,43 @@ def parse(argv=None):
     p.add_argument("--dist", action="store_true",
                    help="initialise torch.distributed (RCCL) even at --gpus 1: the weight broadcast, the frame-count "
                         "all-reduce and the waveform gather run through the collectives with one rank")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure single_batch, the gather's share of a step, the roofline "
+                        "(--profile-steps) and, at N = 1, cpu_baseline + parity (unless --no-cpu-baseline)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MiB in all: "
+                        "a fixed, seeded sample of utterances when the batch's outputs are larger)")
     return p.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """Write batch-first numpy arrays as dirname/<name>.npy: floating outputs as float32, integer ones as float64 (exact).
+    If they exceed DUMP_BUDGET_BYTES, every array keeps the same seeded sample of rows (utterances), in index order: the
+    sample depends only on the batch size and the per-utterance size, so runs with the same arguments pick the same rows."""
+    import numpy as np
+    out = {}
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        out[k] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) and a.dtype.itemsize <= 4 else np.float64)
+    B = min(a.shape[0] for a in out.values())
+    if any(a.shape[0] != B for a in out.values()):
+        raise ValueError({k: a.shape for k, a in out.items()})
+    per_row = sum(a.nbytes for a in out.values()) // max(B, 1)
+    rows = np.arange(B)
+    if per_row * B > DUMP_BUDGET_BYTES:
+        n = DUMP_BUDGET_BYTES // per_row
+        if n < 1:
+            raise SystemExit(f"--dump-outputs: one utterance's outputs ({per_row} bytes) exceed {DUMP_BUDGET_BYTES} bytes")
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=n, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), np.ascontiguousarray(a[rows]))
+    return {"dir": dirname, "names": sorted(out), "utterances": int(rows.size), "of": int(B),
+            "bytes": int(per_row * rows.size)}
 
 
 def self_launch(args) -> int:
@@ -360,7 +405,7 @@ def main():
         (o, x_mask, (z, z_p, m_p, logs_p), duration, f0, energy), _ = pool[0].infer(
             ph, ln, sid=sid, noise_scale=0.667, noise=noise, t_f=tf_global,
             after=(lambda res: g.start(res[0])) if g is not None else None, **ctl)
-        last.update(o=o, z=z, duration=duration)
+        last.update(o=o, x_mask=x_mask, z=z, z_p=z_p, m_p=m_p, logs_p=logs_p, duration=duration, f0=f0, energy=energy)
         return o
 
     def drain():
@@ -386,10 +431,15 @@ def main():
     dt = time.perf_counter() - t0
     arm(extra=4.0 * per_step_guess * args.steps)
     dt_rank = dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned, copied to the host before any later step can reuse its context's buffers
+        dumped = dump_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in last.items()
+                                                  if torch.is_tensor(v)})
     # ONE batch in flight (a step = one batch start to end: the latency figure, and the headline of rounds 1-5): the same K
     # steps once more on context 0 alone (untimed for `value`)
     dt_single = None
-    if len(pool_all) > 1:
+    if args.full and len(pool_all) > 1:
         pool[0] = pool_all.restrict(1)
         for _ in range(2):
             step()
@@ -404,7 +454,7 @@ def main():
         arm(extra=4.0 * per_step_guess * args.steps)
     # the gather's share of a step: the same K steps once more WITHOUT the exchange (untimed for `value`)
     dt_nogather = None
-    if gatherer is not None:
+    if args.full and gatherer is not None:
         keep, gatherer = gatherer, None
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -415,7 +465,7 @@ def main():
 
     # ---- second, untimed pass: HIP events around every launch of the profiled classes (rank 0's numbers are reported)
     prof = {}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         arm()
         pool[0] = pool_all.restrict(1)                 # (the per-launch event pass runs one batch at a time on context 0)
         torch.cuda.synchronize()
@@ -485,7 +535,8 @@ def main():
         dist.all_reduce(mn, op=dist.ReduceOp.MIN)
         dt, total_valid = float(mx[0].item()), float(sm[1].item())
         rank_ms = [float(mn[0].item()) / args.steps * 1e3, float(mx[0].item()) / args.steps * 1e3]
-        dt_nogather = float(mx[2].item())
+        if dt_nogather is not None:
+            dt_nogather = float(mx[2].item())
         if dt_single is not None:
             dt_single = float(mx[3].item())
     else:
@@ -509,7 +560,8 @@ def main():
                                    f"{split_text}, 44.1 kHz, hop 512, "
                                    f"{ {'all': 'phoneme/duration/F0/energy/noise supplied', 'duration': 'phoneme/duration/noise supplied, F0 and energy PREDICTED', 'none': 'phonemes + noise supplied, duration / F0 / energy PREDICTED'}[args.controls] }"
                                    ", random-init (synthetic) weights of configs/config.json"
-                                   + (f"; {args.in_flight} batches in flight per GPU (single_batch = one)" if args.in_flight > 1 else ""),
+                                   + (f"; {args.in_flight} batches in flight per GPU" + (" (single_batch = one)" if args.full else "")
+                                      if args.in_flight > 1 else ""),
                        "utterances_per_gpu": B, "global_batch": B_all * (1 if sharded_global else world),
                        "padded_frames": tf_global, "valid_samples_per_step": int(total_valid),
                        "frames_padded": int(B * tf_global), "frames_computed": frames_computed,
@@ -522,11 +574,16 @@ def main():
             "n_ranks_seen": n_ranks_seen,
             "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
             "gather": ({"bytes_into_rank0_per_step": int(4 * 512 * tf_global * (B_all * (1 if sharded_global else world) - B)),
-                        "ms_per_step_without_gather": dt_nogather / args.steps * 1e3,
-                        "share_of_step": max(0.0, 1.0 - dt_nogather / dt)} if use_dist else None),
+                        **({"ms_per_step_without_gather": dt_nogather / args.steps * 1e3,
+                            "share_of_step": max(0.0, 1.0 - dt_nogather / dt)} if dt_nogather is not None else {})}
+                       if use_dist else None),
             "collectives": (f"torch.distributed backend {dist.get_backend()}: weight-arena broadcast, frame-count all-reduce MAX, "
                             "waveform gather on rank 0 (side stream, persistent buffers)") if use_dist else "none (one process, no process group)",
         }
+        if not args.full:
+            del out["single_batch"]                      # (measured by --full only)
+        if dumped:
+            out["outputs"] = dumped
         if gen_mode == "f32":
             out["dtype"] = "f32"
         elif gen_mode == "f16":      # opt-in reduced precision: NOT the headline configuration
@@ -612,9 +669,10 @@ def main():
                 except Exception:
                     pass
             out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline and args.workload == "C5":
+        cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
+        if cpu_leg and args.workload == "C5":
             out["parity"] = c5_prefix_parity(sd, dims, batch, last, tf_global)
-        elif world == 1 and not args.no_cpu_baseline:
+        elif cpu_leg:
             frames_all = frames_local
             gpu_out = dict(o=last["o"], z=last["z"], duration=last["duration"] if torch.is_tensor(last["duration"]) else ctl["duration_control"],
                            frames=frames_all)

@@ -38,7 +38,7 @@ def run_bench(*extra, gpus=2, backend="gloo"):
 def test_two_rank_bench_self_launches_on_one_gpu():
     """The default line answers BASELINE.json's metric literally: ONE batch (here 6 utterances instead of 64) split
     shard_range-wise over the ranks -- global_batch is the single batch, not batch x ranks."""
-    d = run_bench("--batch", "6")
+    d = run_bench("--batch", "6", "--full")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     assert d["n_ranks_seen"] == 2 and "gloo" in d["collectives"]
     assert d["config"]["global_batch"] == 6 and d["config"]["utterances_per_gpu"] == 3 and d["config"]["parallelism"] == "shard2"
@@ -76,7 +76,7 @@ def test_rccl_path_runs_on_hardware_with_one_rank():
     of the packed weight arena, the frame-count all-reduce, the side-stream waveform gather with persistent buffers,
     the barriers -- executed on the MI355X.  One rank (this box has one GPU; RCCL refuses two ranks per device),
     launched through the self-launch path: the parent never touches the GPU, the rank is a fresh child process."""
-    d = run_bench("--dist", "--batch", "4", "--no-cpu-baseline", gpus=1, backend="nccl")
+    d = run_bench("--dist", "--batch", "4", "--no-cpu-baseline", "--full", gpus=1, backend="nccl")
     assert d["n_gpus"] == 1 and d["n_ranks_seen"] == 1 and "nccl" in d["collectives"]
     assert d["value"] > 0 and d["config"]["utterances_per_gpu"] == 4 and d["config"]["global_batch"] == 4
     assert "per GPU" in d["config"]["workload"]               # (one GPU: the headline line reads as before)
@@ -146,10 +146,33 @@ def test_batches_in_flight_are_disclosed_and_the_single_batch_figure_rides_along
     k + 1 overlaps the generator of batch k).  The line says so, carries the one-batch-in-flight figure of the same K
     steps beside it, and --in-flight 1 is rounds 1-5's headline form; both deliver the same waveforms."""
     a, b = tmp_path / "two.npy", tmp_path / "one.npy"
-    d2 = run_bench("--batch", "4", "--no-cpu-baseline", "--dump-wave", str(a), gpus=1, backend="nccl")
-    d1 = run_bench("--batch", "4", "--no-cpu-baseline", "--in-flight", "1", "--dump-wave", str(b), gpus=1, backend="nccl")
+    d2 = run_bench("--batch", "4", "--no-cpu-baseline", "--full", "--dump-wave", str(a), gpus=1, backend="nccl")
+    d1 = run_bench("--batch", "4", "--no-cpu-baseline", "--full", "--in-flight", "1", "--dump-wave", str(b), gpus=1, backend="nccl")
     assert d2["config"]["batches_in_flight"] == 2 and d1["config"]["batches_in_flight"] == 1
     sb = d2["single_batch"]
     assert sb and sb["ms_per_step"] > 0 and sb["value"] > 0 and d1["single_batch"] is None
     assert d2["roofline"]["launches"] == 51 == d1["roofline"]["launches"]          # the profiled pass runs one batch at a time
     assert np.array_equal(np.load(a), np.load(b))                                  # same kernels on the same inputs: same bits
+
+
+def test_plain_run_is_lean_and_dumps_what_the_last_timed_step_returned(tmp_path):
+    """A plain run times the K steps and prints the line; the secondary measurements come with --full only.
+    --dump-outputs writes what infer() returned in the last timed step, and two runs with the same arguments see the
+    same inputs: the files agree bit for bit, and the waveform is the one --dump-wave's extra step delivers."""
+    a, b, w = tmp_path / "a", tmp_path / "b", tmp_path / "wave.npy"
+    d = run_bench("--batch", "4", "--dump-outputs", str(a), "--dump-wave", str(w), gpus=1, backend="nccl")
+    for key in ("single_batch", "roofline", "cpu_baseline", "parity"):
+        assert key not in d, key
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    names = {"o", "x_mask", "z", "z_p", "m_p", "logs_p", "duration", "f0", "energy"}
+    assert set(d["outputs"]["names"]) == names and d["outputs"]["utterances"] == 4
+    assert {p.name for p in a.iterdir()} == {f"{n}.npy" for n in names}
+    run_bench("--batch", "4", "--dump-outputs", str(b), gpus=1, backend="nccl")
+    T = d["config"]["padded_frames"]
+    for n in names:
+        x, y = np.load(a / f"{n}.npy"), np.load(b / f"{n}.npy")
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 4 and np.isfinite(x).all(), n
+        assert np.array_equal(x, y), n
+    o = np.load(a / "o.npy")
+    assert o.shape == (4, 1, 512 * T) and np.abs(o).max() > 0
+    assert np.array_equal(o.reshape(4, -1), np.load(w))

@@ -8,7 +8,7 @@ for i in $(seq 1 "$N"); do
   for E in "$@"; do
     if [ "$E" = "-" ]; then E=""; fi
     # shellcheck disable=SC2086
-    env $E python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline 2> /dev/null | python3 -c "
+    env $E python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline 2> /dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('== [%s] #%s: %.2f ms/step  generator %.2f ms in %d launches  frame-rate convs %.2f ms  attention %.2f ms' % (sys.argv[1], sys.argv[2], d['ms_per_step'], r['kernel_ms_per_step'], r['launches'], r['frame_rate_convs']['ms_per_step'], r['attention']['ms_per_step']))" "$E" "$i"

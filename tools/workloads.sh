@@ -8,7 +8,7 @@ for D in "$@"; do
   python - "$D" <<'PY'
 import json, subprocess, sys
 def run(*a):
-    o = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", *a], capture_output=True, text=True).stdout.strip().splitlines()
+    o = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", *a], capture_output=True, text=True).stdout.strip().splitlines()
     return json.loads(o[-1])
 one = run("--workload", "C2", "--batch", "1", "--steps", "40", "--warmup", "8")
 c5 = run("--workload", "C5", "--steps", "10", "--warmup", "3")
