@@ -95,6 +95,14 @@ typedef struct vsp_ctx vsp_ctx;
 int vsp_abi_version(void);
 /* Replaces SynthesizerTrn.__init__ (reference models.py:537-622) for the infer path. */
 int vsp_create(const vsp_config* cfg, int device, vsp_ctx** out);
+/* vsp_create_ex (round 7, ABI 7, additive): the same with the generator's ResBlock kind, the reference's `resblock`
+ * constructor argument (models.py:251): 1 = ResBlock1 (modules.py:187-229), 2 = ResBlock2 (modules.py:232-256: two
+ * convolutions per block, dilation[0] and dilation[1] of each resblock_dilation_sizes row; state_dict keys
+ * dec.resblocks.N.convs.{0,1}.*).  vsp_create(cfg, ...) is vsp_create_ex(cfg, 1, ...); any other kind returns
+ * VSP_ERR_ARG, and so does kind 2 with n_resblock_dilations < 2.  The packed arena's configuration hash covers kind 2:
+ * a context of one kind refuses the other kind's arena in vsp_commit_adopted_weights.  VSP_RB2_FUSE=0 (read here) runs
+ * every ResBlock2 convolution as a launch of its own (second implementation, bit-identical). */
+int vsp_create_ex(const vsp_config* cfg, int32_t resblock, int device, vsp_ctx** out);
 int vsp_destroy(vsp_ctx* ctx);
 const char* vsp_last_error(const vsp_ctx* ctx);
 
@@ -382,6 +390,14 @@ int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilatio
  * n_pairs <= 3.  The three modes return identical bits.  x != out. */
 int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const int* dilations, const float* x,
                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
+/* vsp_cl_resblock2 (round 7, ABI 7, additive): ResBlock2.forward without the mask (reference modules.py:245-249):
+ *   for c < 2:  x = x + conv_c(lrelu(x), dilations[c]), slope 0.1
+ * w_host[c] dense [C][C][K], bias_host[c] [C]; x, out [B][T][C] channels-last, x != out.
+ * mode 0: one launch per convolution (g16_conv, in_act + res), any C % 32 == 0;  mode 1: ONE launch (g16_rb2),
+ * C = 32 or 64, (K - 1) / 2 * dilations[c] <= 32.  The two modes return identical bits.  Outside the kernels' cover:
+ * VSP_ERR_UNSUPPORTED. */
+int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
+                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
@@ -420,6 +436,7 @@ int vsp_profile_read_class(vsp_ctx* ctx, int cls, int64_t* launches, double* tot
  *   VSP_FAM_CONV   one launch per convolution (g16_conv / g16_convp)      VSP_FAM_UPS    a transposed up-convolution
  *   VSP_FAM_PAIR   one launch per ResBlock conv pair (g16_pp at 128 channels, g16_pair at 64, g16_rw at 32)
  *   VSP_FAM_CHAIN  one launch per ResBlock (g16_rc / g16_chain)           VSP_FAM_PRE    conv_pre (+ cond)
+ *   VSP_FAM_RB2    one launch per ResBlock2 block (g16_rb2; round 7)
  * Fills up to `max_families` slots (families that saw no launch since the last reset are skipped) and returns the
  * number filled (>= 0) or a negative error code.  Call it BEFORE the vsp_profile_read_class(..., reset = 1) of the
  * same class; it never resets. */
@@ -429,6 +446,7 @@ int vsp_profile_read_class(vsp_ctx* ctx, int cls, int64_t* launches, double* tot
 #define VSP_FAM_PAIR 3
 #define VSP_FAM_CHAIN 4
 #define VSP_FAM_PRE 5
+#define VSP_FAM_RB2 6
 int vsp_profile_read_families(vsp_ctx* ctx, int cls, int max_families, int* family, int64_t* launches, double* total_ms,
                               double* total_flops, double* total_bytes, double* total_bytes_moved /* ABI 7, may be NULL */);
 

@@ -50,6 +50,7 @@ _U64 = C.c_uint64
 SIGNATURES = {
     "vsp_abi_version": (_I, []),
     "vsp_create": (_I, [C.POINTER(VspConfig), _I, C.POINTER(_P)]),
+    "vsp_create_ex": (_I, [C.POINTER(VspConfig), C.c_int32, _I, C.POINTER(_P)]),
     "vsp_destroy": (_I, [_P]),
     "vsp_last_error": (C.c_char_p, [_P]),
     "vsp_status": (_I, [_P, C.POINTER(C.c_uint), _I]),
@@ -103,6 +104,7 @@ SIGNATURES = {
     "vsp_cl_conv1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),
     "vsp_conv1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _I, _P]),
     "vsp_cl_resblock": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "vsp_cl_resblock2": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -14,7 +14,7 @@ using namespace vsp;
 
 namespace {
 
-void generator_frame_dependence(const vsp_config& c, int pre_k, int post_k, int& back, int& fwd);   // (defined below)
+void generator_frame_dependence(const vsp_config& c, int resblock, int pre_k, int post_k, int& back, int& fwd);   // (defined below)
 long total_upsample(const vsp_config& c);
 
 struct T3 {
@@ -230,6 +230,32 @@ struct Run {
       const double el = (double)T * L1.Cout;
       prof_end(VSP_PROF_GENERATOR, 2.0 * 2.0 * L1.Cout * L1.Cin * L1.K * (double)T * B, 4.0 * B * el * 4.0,
                4.0 * B * el * (5.0 + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
+    }
+  }
+  // fused ResBlock2 (g16_rb2, gen16_rb2.hip): y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y)) [+ out] [/ div]
+  void clrb2(const ResBlockW& rb, int ch, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B) {
+    if (dry() || !ok()) return;
+    ClRb2Args a;
+    std::memset(&a, 0, sizeof a);
+    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
+    for (int c = 0; c < 2; ++c) {
+      a.w[c] = reinterpret_cast<const uint16_t*>(A(rb.h1[c].wg));
+      a.b[c] = A((size_t)rb.h1[c].b);
+      a.dil[c] = rb.dil[c];
+    }
+    a.C = ch; a.K = rb.k; a.T = T;
+    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
+    a.acc_prev = acc_prev ? 1 : 0; a.div = div;
+    a.terms = ctx->gen_mode == 2 ? 1 : 3;
+    a.glen = glen; a.grate = grate_out;
+    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(VSP_FAM_RB2, ch));
+    chk(launch_g16_rb2(a, B, s), "g16_rb2");
+    if (prof) {
+      // the two convolutions this launch replaces, each charged its input and its output; both residual
+      // reads (and the accumulate read of a stage's later blocks) -> bytes_ext
+      const double el = (double)T * ch;
+      prof_end(VSP_PROF_GENERATOR, 2.0 * 2.0 * ch * ch * rb.k * (double)T * B, 4.0 * B * el * 4.0,
+               4.0 * B * el * (6.0 + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
     }
   }
   // cond(g): 1x1 conv on g [B][gin] (T = 1) -> out [B][M]
@@ -469,6 +495,23 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
     for (int j = 0; j < nk; ++j) {
       const ResBlockW& rb = m.rbs[i * nk + j];
       const int nd = (int)rb.dil.size();
+      if (rb.kind == 2) {
+        // ResBlock2 (reference modules.py:245-249): x = x + conv_d(lrelu(x)) per convolution, ping-pong XU -> YA -> XS
+        for (int d = 0; d < nd; ++d) {
+          const bool last = d == nd - 1;
+          const T3 yin = d == 0 ? XU : ((d & 1) ? YA : T1);
+          const T3 yout = last ? XS : ((d & 1) ? T1 : YA);
+          a = r.args(rb.c1[d], yin, yout, (int)Tout, (int)Tout);
+          a.in_act = 1; a.in_slope = 0.1f;
+          a.res = yin.p; a.r_bs = yin.bs; a.r_cs = yin.cs;
+          if (last) {
+            a.acc_prev = j > 0;
+            if (j == nk - 1) a.div = (float)nk;
+          }
+          r.conv(a, B, true);
+        }
+        continue;
+      }
       for (int d = 0; d < nd; ++d) {
         const T3 yin = d == 0 ? XU : YA;
         a = r.args(rb.c1[d], yin, T1, (int)Tout, (int)Tout);
@@ -549,7 +592,7 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
       if (chi >= 128 && chi % 32 == 0) mx_img = std::max(mx_img, cl_img_halfs(chi, (int)t) / 2);
     }
   }
-  const bool want_img = r.ctx->t_img && mx_img && r.ctx->gen_mode == 1;
+  const bool want_img = r.ctx->t_img && mx_img && r.ctx->gen_mode == 1 && r.ctx->resblock == 1;   // (ResBlock2: fp32 tensors)
   uint16_t* timg = want_img ? reinterpret_cast<uint16_t*>(r.ws.f((size_t)B * mx_img)) : nullptr;
   std::vector<uint16_t*> side_img;
   if (want_img && r.ctx->rb_streams)
@@ -563,7 +606,7 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   // (back / fwd: output frame F depends on input frames [F - back, F + fwd], sample-exact: 13 / 13 for configs/config.json.
   // A tensor that ends after E frames is exact up to frame E - 1 - fwd; frame len + back is the first steady one.)
   int back = 0, fwd = 0;
-  generator_frame_dependence(c, m.g_pre.K, m.post_k, back, fwd);
+  generator_frame_dependence(c, r.ctx->resblock, m.g_pre.K, m.post_k, back, fwd);
   int* glen_all = r.ctx->trim_tails ? reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int))) : nullptr;
   // (gen_tail_fill keeps the computed tensor end -- fwd frames of the waveform -- in 64 KB of LDS: other configurations run untrimmed)
   bool trim = glen_all && in_lengths && T > back + fwd + 1 && (size_t)fwd * total_upsample(c) * sizeof(float) <= 64 * 1024;
@@ -673,6 +716,27 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
         uint16_t* const ti = chain_img(j);
         auto before_last = [&]() { if (conc && j > 0) r.chk(hipStreamWaitEvent(r.s, ev[j], 0), "sum order wait"); };
         auto after_last = [&]() { if (conc) r.chk(hipEventRecord(ev[1 + j], r.s), "chain end event"); r.s = main_s; };
+        if (rb.kind == 2) {
+          // ResBlock2 (reference modules.py:245-249): one fused launch on the 32/64-channel stages (g16_rb2), else one
+          // g16_conv per convolution with in_act + res, the running x ping-ponging xu -> ya -> xs; the last launch of the
+          // stage's last block divides by nk (the reference's order of the sum).  VSP_RB2_FUSE=0: per convolution everywhere.
+          if (r.ctx->rb2_fuse && nd == 2 && g16_rb2_supported(ch, rb.k, rb.dil.data())) {
+            before_last();
+            r.clrb2(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
+            after_last();
+            continue;
+          }
+          for (int d = 0; d < nd; ++d) {
+            const bool last = d == nd - 1;
+            const float* yin = d == 0 ? xu : ((d & 1) ? ya : t1);
+            float* yout = last ? xs : ((d & 1) ? t1 : ya);
+            if (last) before_last();
+            r.clconv(rb.h1[d], yin, bs, yout, bs, yin, bs, (int)Tout, (int)Tout, (int)Tout, 0.1f, last && j > 0,
+                     (last && j == nk - 1) ? (float)nk : 1.f, nb);
+          }
+          after_last();
+          continue;
+        }
         bool fuse = r.ctx->fuse_pairs;
         const int terms = r.ctx->gen_mode == 2 ? 1 : 3;
         for (int d = 0; d < nd; ++d)
@@ -739,23 +803,32 @@ int check_ready(vsp_ctx* ctx) {
   return VSP_OK;
 }
 
+// One-sided support of ResBlock j of a stage, in samples at the stage's rate: ResBlock1 (reference modules.py:210-223)
+// sum over its dilations of (k - 1) d / 2 + (k - 1) / 2 (a dilated and an undilated convolution per step); ResBlock2
+// (modules.py:245-249) (k - 1) d / 2 for dilation[0] and dilation[1] only (one convolution per step, the rest unused).
+long resblock_support(const vsp_config& c, int resblock, int j) {
+  const long kk = c.resblock_kernel_sizes[j];
+  long acc = 0;
+  if (resblock == 2) {
+    for (int d = 0; d < 2 && d < c.n_resblock_dilations; ++d) acc += (kk - 1) * c.resblock_dilation_sizes[j][d] / 2;
+    return acc;
+  }
+  for (int d = 0; d < c.n_resblock_dilations; ++d) acc += (kk - 1) * c.resblock_dilation_sizes[j][d] / 2 + (kk - 1) / 2;
+  return acc;
+}
+
 // Exact dependence of the generator's output FRAMES on its input frames, from the configuration (sample-exact supports;
 // vsp_generator_halo_frames below is the coarser per-stage bound the streamed vocoder uses): output frame F depends on
 // input frames [F - back, F + fwd].  An impulse at input position 0 reaches output samples [lo, hi]: conv_pre widens the
 // support by its padding, a transposed convolution (k, s, p) maps [lo, hi] to [lo s - p, hi s - p + k - 1], a stage's
-// ResBlocks widen it by max_k sum_d ((k - 1) d / 2 + (k - 1) / 2), conv_post by its padding.
-void generator_frame_dependence(const vsp_config& c, int pre_k, int post_k, int& back, int& fwd) {
+// ResBlocks widen it by max_k of the block's support (resblock_support), conv_post by its padding.
+void generator_frame_dependence(const vsp_config& c, int resblock, int pre_k, int post_k, int& back, int& fwd) {
   long lo = -(pre_k - 1) / 2, hi = (pre_k - 1) / 2, up = 1;
   for (int i = 0; i < c.n_upsamples; ++i) {
     const long s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i], p = (k - s) / 2;
     lo = lo * s - p; hi = hi * s - p + k - 1; up *= s;
     long rb = 0;
-    for (int j = 0; j < c.n_resblock_kernels; ++j) {
-      long acc = 0;
-      const long kk = c.resblock_kernel_sizes[j];
-      for (int d = 0; d < c.n_resblock_dilations; ++d) acc += (kk - 1) * c.resblock_dilation_sizes[j][d] / 2 + (kk - 1) / 2;
-      rb = std::max(rb, acc);
-    }
+    for (int j = 0; j < c.n_resblock_kernels; ++j) rb = std::max(rb, resblock_support(c, resblock, j));
     lo -= rb; hi += rb;
   }
   lo -= (post_k - 1) / 2; hi += (post_k - 1) / 2;
@@ -777,11 +850,14 @@ extern "C" {
 
 int vsp_abi_version(void) { return VSP_ABI_VERSION; }
 
-int vsp_create(const vsp_config* cfg, int device, vsp_ctx** out) {
-  if (!cfg || !out) return VSP_ERR_ARG;
+int vsp_create(const vsp_config* cfg, int device, vsp_ctx** out) { return vsp_create_ex(cfg, 1, device, out); }
+
+int vsp_create_ex(const vsp_config* cfg, int32_t resblock, int device, vsp_ctx** out) {
+  if (!cfg || !out || (resblock != 1 && resblock != 2)) return VSP_ERR_ARG;
   vsp_ctx* ctx = new (std::nothrow) vsp_ctx();
   if (!ctx) return VSP_ERR_ARG;
   ctx->cfg = *cfg;
+  ctx->resblock = resblock;
   ctx->device = device;
   // Second implementations kept under test (tests/test_hip_parity.py): VSP_FRAME=f32 / VSP_ATT=f32 / VSP_GENERATOR=f32
   // (f32 matrix core), VSP_FUSE_PAIRS=0 (one launch per convolution), VSP_CHAIN=<mask> (whole-ResBlock launches:
@@ -796,6 +872,7 @@ int vsp_create(const vsp_config* cfg, int device, vsp_ctx** out) {
     want_f16 = !strcmp(e, "f16");
   }
   if (const char* e = getenv("VSP_FUSE_PAIRS")) ctx->fuse_pairs = atoi(e) != 0;
+  if (const char* e = getenv("VSP_RB2_FUSE")) ctx->rb2_fuse = atoi(e) != 0;      // 0: ResBlock2 one launch per convolution (second implementation)
   if (const char* e = getenv("VSP_TIMG")) ctx->t_img = atoi(e) != 0;   // 0: ResBlock intermediates as fp32 tensors (second implementation)
   if (const char* e = getenv("VSP_PP")) ctx->pp_pairs = atoi(e) != 0;  // 0: the 128-channel stage's k3 / k7 pairs as two launches
   if (const char* e = getenv("VSP_PAIR")) ctx->pair_ring = !strcmp(e, "ring");
@@ -818,7 +895,7 @@ int vsp_create(const vsp_config* cfg, int device, vsp_ctx** out) {
   if (const char* e = getenv("VSP_CHAIN_CH")) ctx->chain_ch = atoi(e);
   if (const char* e = getenv("VSP_CHAIN128")) ctx->chain128_mask = atoi(e);
 #endif
-  build_schema(ctx->cfg, ctx->schema);
+  build_schema(ctx->cfg, ctx->schema, ctx->resblock);
   const int rc = plan_model(ctx);            // (falls back to gen_mode 0 when the channels-last kernels do not cover the config)
   if (want_f16 && ctx->gen_mode == 1) ctx->gen_mode = 2;   // opt-in reduced precision: same packing as mode 1
   *out = ctx;  // returned even on failure so that vsp_last_error can be read; caller destroys it
@@ -1012,6 +1089,7 @@ static uint32_t config_hash(const vsp_ctx* ctx) {
   const int sw[3] = {ctx->frame_f16s ? 1 : 0, ctx->model.has_cl ? 1 : 0, ctx->gen_mode != 0 ? 1 : 0};
   mix(sw, sizeof sw);
   mix(&ctx->act_scale, sizeof ctx->act_scale);   // (the packed generator biases carry it)
+  if (ctx->resblock == 2) mix(&ctx->resblock, sizeof ctx->resblock);   // (ResBlock1 arenas hash as they always did)
   return h;
 }
 
@@ -1723,7 +1801,7 @@ int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, cons
 }
 
 // Receptive field of the generator in input frames (one side), from the configuration: walking back from conv_post,
-// every ResBlock1 stage adds max_k sum_d ((k-1) d / 2 + (k-1) / 2) positions at its rate, every transposed conv maps
+// every stage adds the largest ResBlock support (resblock_support) in positions at its rate, every transposed conv maps
 // w positions to ceil((w + (k + s) / 2 - 1) / s), conv_pre adds 3.  (14 for configs/config.json; measured 12.33.)
 int vsp_generator_halo_frames(const vsp_ctx* ctx) {
   if (!ctx) return VSP_ERR_ARG;
@@ -1731,12 +1809,7 @@ int vsp_generator_halo_frames(const vsp_ctx* ctx) {
   long w = 3;   // conv_post k7
   for (int i = c.n_upsamples - 1; i >= 0; --i) {
     long rb = 0;
-    for (int j = 0; j < c.n_resblock_kernels; ++j) {
-      long acc = 0;
-      const int k = c.resblock_kernel_sizes[j];
-      for (int d = 0; d < c.n_resblock_dilations; ++d) acc += (long)(k - 1) * c.resblock_dilation_sizes[j][d] / 2 + (k - 1) / 2;
-      rb = std::max(rb, acc);
-    }
+    for (int j = 0; j < c.n_resblock_kernels; ++j) rb = std::max(rb, resblock_support(c, ctx->resblock, j));
     w += rb;
     const int s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i];
     w = (w + (k + s) / 2 - 1 + s - 1) / s;
@@ -1746,7 +1819,8 @@ int vsp_generator_halo_frames(const vsp_ctx* ctx) {
 
 int vsp_generator_frame_dependence(const vsp_ctx* ctx, int* back, int* fwd) {
   if (!ctx || !back || !fwd) return VSP_ERR_ARG;
-  generator_frame_dependence(ctx->cfg, ctx->model.g_pre.K > 0 ? ctx->model.g_pre.K : 7, ctx->model.post_k, *back, *fwd);
+  generator_frame_dependence(ctx->cfg, ctx->resblock, ctx->model.g_pre.K > 0 ? ctx->model.g_pre.K : 7, ctx->model.post_k,
+                             *back, *fwd);
   return VSP_OK;
 }
 
@@ -2048,6 +2122,42 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
       }
       yin = yout;
     }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
+                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
+  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || mode < 0 || mode > 1 ||
+      (terms != 1 && terms != 3) || !w_host[0] || !w_host[1])
+    return VSP_ERR_ARG;
+  if (C <= 0 || C % 32 || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  for (int c = 0; c < 2; ++c)
+    if (dilations[c] < 1 || (K - 1) * dilations[c] > 64) return VSP_ERR_UNSUPPORTED;
+  if (mode == 1 && !g16_rb2_supported(C, K, dilations)) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w[2], bias[2];
+  hipError_t e = hipSuccess;
+  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = upload_cl_conv(w_host[c], bias_host[c], C, C, K, w[c], bias[c], s);
+  DevBuf y;
+  if (e == hipSuccess && mode == 0) e = y.alloc((size_t)B * T * C * 4);
+  if (e != hipSuccess) return op_rc(e);
+  if (mode == 1) {
+    ClRb2Args a;
+    std::memset(&a, 0, sizeof a);
+    a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
+    for (int c = 0; c < 2; ++c) {
+      a.w[c] = static_cast<const uint16_t*>(w[c].p); a.b[c] = static_cast<const float*>(bias[c].p); a.dil[c] = dilations[c];
+    }
+    a.C = C; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
+    e = launch_g16_rb2(a, B, s);
+  } else {
+    // one g16_conv per convolution: y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y))
+    float* yp = static_cast<float*>(y.p);
+    e = launch_g16_conv(cl_conv_args(x, T, C, C, K, dilations[0], w[0], bias[0], 0.1f, x, terms, yp), B, s);
+    if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(yp, T, C, C, K, dilations[1], w[1], bias[1], 0.1f, yp, terms, out), B, s);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return op_rc(e);

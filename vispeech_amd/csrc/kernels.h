@@ -203,6 +203,22 @@ bool g16_rc_supported(int C, int K, const int* dil, int np, int terms, int acc_p
 hipError_t launch_g16_rc(const ClChainArgs& a, int B, hipStream_t s);
 bool g16_chain_supported(int C, int K, const int* dil, int np);
 hipError_t launch_g16_chain(const ClChainArgs& a, int B, hipStream_t s);
+// Fused ResBlock2 on channels-last activations (gen16_rb2.hip, round 7): both convolutions of the block in one launch,
+//   y = x + conv_a(lrelu(x), dil[0]) + b_a,   out = y + conv_b(lrelu(y), dil[1]) + b_b  [+ out] [/ div];  x != out.
+struct ClRb2Args {
+  const float* x; long x_bs;
+  float* out; long o_bs;
+  const uint16_t* w[2]; const float* b[2];  // conv_a, conv_b: packed f16 fragment images, biases (* G16_WSCALE)
+  int dil[2];
+  int C, K, T;
+  float slope;
+  int acc_prev; float div;
+  int terms;
+  int tiles, halo;                          // set by the launcher: tiles per utterance, columns recomputed per side
+  const int* glen; int grate;               // ragged batch (see ClConvArgs): utterance b's T = glen[b] * grate; NULL = uniform
+};
+bool g16_rb2_supported(int C, int K, const int* dil);
+hipError_t launch_g16_rb2(const ClRb2Args& a, int B, hipStream_t s);
 hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s);
 // image-input convolutions on the 128-row tile as persistent blocks pipelined across tiles (gen16_pipe.hip):
 // launch_g16_conv routes tiles of at most 28 steps there (VSP_G16_PIPE=0: never, =1: always -- bit-identical)

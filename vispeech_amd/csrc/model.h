@@ -58,10 +58,11 @@ struct PosteriorW {
   std::vector<Conv> in, res, skip;
 };
 struct ResBlockW {
+  int kind = 1;                    // 1: ResBlock1 (convs1 / convs2 pairs), 2: ResBlock2 (reference modules.py:232-249)
   int k = 0;
-  std::vector<int> dil;
-  std::vector<Conv> c1, c2;        // f32-MFMA packing (generator mode 0)
-  std::vector<ClConv> h1, h2;      // split-f16 packing (generator mode 1)
+  std::vector<int> dil;            // kind 2: the two dilations the reference uses (dilation[0], dilation[1])
+  std::vector<Conv> c1, c2;        // f32-MFMA packing (generator mode 0); kind 2: c1 = convs.0, convs.1, c2 empty
+  std::vector<ClConv> h1, h2;      // split-f16 packing (generator mode 1); kind 2: h1 = convs.0, convs.1, h2 empty
 };
 
 struct Model {
@@ -109,6 +110,7 @@ struct SchemaEntry {
 
 struct vsp_ctx {
   vsp_config cfg;
+  int resblock = 1;               // generator ResBlock kind (vsp_create_ex): 1 = ResBlock1, 2 = ResBlock2
   int device = 0;
   std::string err;
   std::map<std::string, vsp::SchemaEntry> schema;
@@ -169,6 +171,7 @@ struct vsp_ctx {
   int chain_mask = 0x1;    // ResBlock chains (all dilation pairs of a ResBlock in one launch): bit 0 = k3, 1 = k7, 2 = k11 (VSP_CHAIN=<mask>; measured: only k3 pays)
   int chain128_mask = 0;   // conv PAIRS of the 128-channel stage as one launch each (g16_chain, one pair): bit 0 = k3, 1 = k7, 2 = k11 (VSP_CHAIN128)
   int chain_ch = 32;       // widest stage that runs chains (VSP_CHAIN_CH)
+  bool rb2_fuse = true;    // ResBlock2 blocks of the 32/64-channel stages as one launch (g16_rb2; VSP_RB2_FUSE=0: one per convolution)
   bool fuse_pairs = true;  // ResBlock conv pairs of the 32/64-channel stages as one launch (VSP_FUSE_PAIRS=0: two launches)
   double chunk_mb = 0.0;   // generator batch chunk in MiB per activation tensor (VSP_CHUNK_MB; 0 = whole batch: measured faster)
   // profiling: HIP event pairs around the launches of a class (VSP_PROF_* in vispeech_hip.h)
@@ -197,7 +200,7 @@ struct vsp_ctx {
 };
 
 namespace vsp {
-void build_schema(const vsp_config& c, std::map<std::string, SchemaEntry>& out);
+void build_schema(const vsp_config& c, std::map<std::string, SchemaEntry>& out, int resblock = 1);
 int plan_model(vsp_ctx* ctx);                         // fills ctx->model offsets from cfg
 int fill_model(vsp_ctx* ctx, std::vector<float>& host_arena);  // folds + packs ctx->raw
 }  // namespace vsp

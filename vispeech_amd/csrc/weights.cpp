@@ -63,7 +63,7 @@ static void schema_wn(std::map<std::string, SchemaEntry>& s, const std::string& 
   }
 }
 
-void build_schema(const vsp_config& c, std::map<std::string, SchemaEntry>& s) {
+void build_schema(const vsp_config& c, std::map<std::string, SchemaEntry>& s, int resblock) {
   s.clear();
   const int64_t h = c.hidden_channels, gin = c.gin_channels, inter = c.inter_channels;
   add(s, "enc_p.symbol_emb.weight", {c.n_vocab, h});
@@ -83,6 +83,15 @@ void build_schema(const vsp_config& c, std::map<std::string, SchemaEntry>& s) {
     ch = cout;
     for (int j = 0; j < c.n_resblock_kernels; ++j) {
       const std::string rb = "dec.resblocks." + std::to_string(i * c.n_resblock_kernels + j);
+      if (resblock == 2) {          // ResBlock2 (reference modules.py:232-243): convs.0 / convs.1
+        for (int m = 0; m < 2; ++m) {
+          const std::string q = rb + ".convs." + std::to_string(m);
+          add(s, q + ".bias", {ch});
+          add(s, q + ".weight_g", {ch, 1, 1});
+          add(s, q + ".weight_v", {ch, ch, c.resblock_kernel_sizes[j]});
+        }
+        continue;
+      }
       for (const char* grp : {".convs1.", ".convs2."})
         for (int m = 0; m < c.n_resblock_dilations; ++m) {
           const std::string q = rb + grp + std::to_string(m);
@@ -227,6 +236,10 @@ int plan_model(vsp_ctx* ctx) {
   if (c.n_upsamples < 1 || c.n_upsamples > VSP_MAX_LIST || c.n_resblock_kernels < 1 ||
       c.n_resblock_kernels > VSP_MAX_LIST || c.n_resblock_dilations < 1 || c.n_resblock_dilations > VSP_MAX_LIST)
     return ctx->fail(VSP_ERR_ARG, "list sizes out of range");
+  if (ctx->resblock != 1 && ctx->resblock != 2) return ctx->fail(VSP_ERR_ARG, "resblock kind %d (1 or 2)", ctx->resblock);
+  // ResBlock2 reads dilation[0] and dilation[1] only (reference modules.py:234-239; fewer raise IndexError there)
+  if (ctx->resblock == 2 && c.n_resblock_dilations < 2)
+    return ctx->fail(VSP_ERR_ARG, "resblock \"2\" needs two dilations per kernel size (got %d)", c.n_resblock_dilations);
   Planner p;
   p.raw(ARENA_HEADER_FLOATS);  // arena header (model.h): magic, ABI, size, flags, config hash
   p.f16s = ctx->frame_f16s;   // everything up to the generator: encoders, predictors, projection, flows, posterior
@@ -325,7 +338,21 @@ int plan_model(vsp_ctx* ctx) {
     ch = cout;
     for (int j = 0; j < c.n_resblock_kernels; ++j) {
       ResBlockW rb;
+      rb.kind = ctx->resblock;
       rb.k = c.resblock_kernel_sizes[j];
+      if (rb.kind == 2) {
+        // two convolutions, each with its input's leaky-relu and a residual; the halo check covers the used dilations
+        for (int q = 0; q < 2; ++q) {
+          const int d = c.resblock_dilation_sizes[j][q];
+          if (d < 1) return ctx->fail(VSP_ERR_ARG, "resblock dilation %d", d);
+          if ((rb.k - 1) * d + 3 > CONV_HALO) return ctx->fail(VSP_ERR_UNSUPPORTED, "resblock halo (k-1)*d > %d", CONV_HALO);
+          rb.dil.push_back(d);
+          rb.c1.push_back(p.conv(ch, ch, rb.k, d, (rb.k * d - d) / 2, true));
+          if (cl_ok) rb.h1.push_back(p.clconv(ch, ch, rb.k, d, (rb.k * d - d) / 2, 1, 0));
+        }
+        m.rbs.push_back(rb);
+        continue;
+      }
       for (int q = 0; q < c.n_resblock_dilations; ++q) {
         const int d = c.resblock_dilation_sizes[j][q];
         if ((rb.k - 1) * d + 3 > CONV_HALO) return ctx->fail(VSP_ERR_UNSUPPORTED, "resblock halo (k-1)*d > %d", CONV_HALO);
@@ -643,6 +670,14 @@ int fill_model(vsp_ctx* ctx, std::vector<float>& arena) {
     for (int j = 0; j < nk && f.ok; ++j) {
       const ResBlockW& rb = m.rbs[i * nk + j];
       const std::string q = "dec.resblocks." + std::to_string(i * nk + j);
+      if (rb.kind == 2) {
+        for (size_t d = 0; d < rb.dil.size(); ++d) {
+          const std::string n = q + ".convs." + std::to_string(d);
+          f.conv_plain(rb.c1[d], n + ".weight", n + ".bias");
+          if (m.has_cl) f.clconv_plain(rb.h1[d], n + ".weight", n + ".bias");
+        }
+        continue;
+      }
       for (size_t d = 0; d < rb.dil.size(); ++d) {
         f.conv_plain(rb.c1[d], q + ".convs1." + std::to_string(d) + ".weight", q + ".convs1." + std::to_string(d) + ".bias");
         f.conv_plain(rb.c2[d], q + ".convs2." + std::to_string(d) + ".weight", q + ".convs2." + std::to_string(d) + ".bias");

@@ -35,7 +35,10 @@ class Engine:
             raise RuntimeError("vispeech_amd runs on an MI355X (torch device 'cuda'); there is no CPU path")
         self.cfg = _lib.make_config(dims)
         ctx = C.c_void_p()
-        rc = self.lib.vsp_create(C.byref(self.cfg), self.device.index or 0, C.byref(ctx))
+        if dims.resblock_kind == 2:                 # (ResBlock1 contexts keep the plain vsp_create)
+            rc = self.lib.vsp_create_ex(C.byref(self.cfg), 2, self.device.index or 0, C.byref(ctx))
+        else:
+            rc = self.lib.vsp_create(C.byref(self.cfg), self.device.index or 0, C.byref(ctx))
         self.ctx = ctx
         _lib.check(rc, ctx, "vsp_create")
         self._arena: Optional[torch.Tensor] = None
@@ -517,7 +520,7 @@ class Engine:
         return int(n.value), float(ms.value), float(fl.value), float(by.value), float(bx.value), float(bm.value)
 
 
-    _FAMILY_KINDS = {0: "other", 1: "conv", 2: "ups", 3: "pair", 4: "chain", 5: "pre"}
+    _FAMILY_KINDS = {0: "other", 1: "conv", 2: "ups", 3: "pair", 4: "chain", 5: "pre", 6: "rb2"}
 
     def profile_read_families(self, cls: int = _lib.PROF_GENERATOR, max_families: int = 64):
         """Per kernel family of one class since the last reset (call BEFORE profile_read(reset=True)):

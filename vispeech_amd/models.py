@@ -3,7 +3,8 @@
 Mirrors the reference's class surface for ``infer`` and nothing else:
 the constructor signature (reference models.py:537-561), ``infer`` with the same arguments and the
 same 6-tuple result (reference models.py:672-722), ``load_state_dict`` accepting reference
-checkpoints unchanged (753-tensor schema, weight_g/weight_v pairs included), ``eval()``, ``to()``.
+checkpoints unchanged (753-tensor schema, weight_g/weight_v pairs included; 609 tensors for ``resblock`` "2", the
+ResBlock2 generator), ``eval()``, ``to()``.
 ``voice_conversion`` (reference models.py:724-732) is served as well when the checkpoint carries the
 ``enc_q.*`` tensors.  Training-time members (``forward``, discriminators) are out of scope and raise.  All arithmetic runs in libvispeech_hip on the MI355X; if the extension is not
 built, constructing the model raises ImportError.
@@ -27,8 +28,6 @@ class SynthesizerTrn:
                  resblock_kernel_sizes, resblock_dilation_sizes, upsample_rates, upsample_initial_channel,
                  upsample_kernel_sizes, n_speakers=0, gin_channels=0, use_sdp=False, freeze_textencoder=False,
                  freeze_decoder=False, device="cuda:0", **kwargs):
-        if str(resblock) != "1":
-            raise NotImplementedError("only resblock '1' (ResBlock1) is on the reference's configured path")
         self.dims: ModelDims = dims_from_ctor(
             n_vocab, spec_channels, hop_length, sampling_rate, segment_size, inter_channels, hidden_channels,
             filter_channels, n_heads, n_layers, kernel_size, p_dropout, resblock, resblock_kernel_sizes,

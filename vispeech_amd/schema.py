@@ -51,6 +51,12 @@ class ModelDims:
     posterior_layers: int = 16      # models.py:595
 
     @property
+    def resblock_kind(self) -> int:
+        """1 = ResBlock1, 2 = ResBlock2.  The reference picks ResBlock1 only for ``resblock == '1'`` (models.py:251); here
+        ``str(resblock) == "1"`` does, so an int 1 also means ResBlock1."""
+        return 1 if str(self.resblock) == "1" else 2
+
+    @property
     def total_upsample(self) -> int:
         p = 1
         for u in self.upsample_rates:
@@ -112,7 +118,7 @@ def state_dict_schema(d: ModelDims) -> "OrderedDict[str, Shape]":
     out["enc_p.proj.weight"] = (2 * d.inter_channels, h, 1)
     out["enc_p.proj.bias"] = (2 * d.inter_channels,)
 
-    # dec: Generator (models.py:244-269), ResBlock1 (modules.py:187-206)
+    # dec: Generator (models.py:244-269), ResBlock1 (modules.py:187-206) or ResBlock2 (modules.py:232-243)
     c0 = d.upsample_initial_channel
     out["dec.conv_pre.weight"] = (c0, d.inter_channels, 7)
     out["dec.conv_pre.bias"] = (c0,)
@@ -127,6 +133,12 @@ def state_dict_schema(d: ModelDims) -> "OrderedDict[str, Shape]":
         ch = c0 // (2 ** (i + 1))
         for j, (k, dil) in enumerate(zip(d.resblock_kernel_sizes, d.resblock_dilation_sizes)):
             p = f"dec.resblocks.{i * nk + j}"
+            if d.resblock_kind == 2:                          # convs.0 / convs.1: dilation[0], dilation[1]
+                for m in range(2):
+                    out[f"{p}.convs.{m}.bias"] = (ch,)
+                    out[f"{p}.convs.{m}.weight_g"] = (ch, 1, 1)
+                    out[f"{p}.convs.{m}.weight_v"] = (ch, ch, k)
+                continue
             for grp in ("convs1", "convs2"):
                 for m in range(len(dil)):
                     out[f"{p}.{grp}.{m}.bias"] = (ch,)
