@@ -398,6 +398,28 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
  * VSP_ERR_UNSUPPORTED. */
 int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
                      const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
+/* vsp_cl_conv_transpose1d (ABI 7, additive): HiFi-GAN's up-convolution as the channels-last generator runs it
+ * (reference models.py:253-256, 277-278: F.leaky_relu + ConvTranspose1d),
+ *   out = conv_transpose1d(lrelu(x, in_slope), w, bias, stride, padding = (K - stride) / 2)
+ * x [B][T][Cin], out [B][T stride][Cout] channels-last; in_slope = 1 applies no activation.  w_host is torch's
+ * ConvTranspose1d weight [Cin][Cout][K] (weight-norm folded), bias_host [Cout] or NULL.  They are packed as the model packs
+ * dec.ups.* and the launch goes through the generator's launcher, so a shape and grid run the kernel the generator would
+ * run (the streaming g16_ups or the polyphase g16_conv tile).  lengths: NULL or a DEVICE int32 [B], 0 <= lengths[b] <= T:
+ * utterance b's tensor then ends after lengths[b] input rows (the generator's ragged batch) -- out rows [0, lengths[b]
+ * stride) are those of x[b, :lengths[b]], the rows behind them are not written.  Cin % 32 == 0, Cout % 16 == 0, stride Cout
+ * a multiple of 32, K % stride == 0, K - stride even, K / stride - 1 <= 64, an utterance's input and output below 2 GiB:
+ * VSP_ERR_UNSUPPORTED otherwise; x == out, a bad terms or a length outside [0, T]: VSP_ERR_ARG. */
+int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                            const float* w_host, const float* bias_host, float in_slope, const int32_t* lengths,
+                            int terms, float* out);
+/* vsp_conv_transpose1d (ABI 7, additive): the same up-convolution on the f32 MFMA kernel (conv1d_f32_mfma's transposed
+ * epilogue), as the f32 generator runs it: VSP_GENERATOR=f32, and the configurations whose channel counts the split-f16
+ * kernels do not cover.  Channel-major x [B][Cin][T] -> out [B][Cout][T stride] (device, fp32, T contiguous); any Cin and
+ * Cout; w_host / bias_host as above.  The generator pads its time rows to a multiple of 64 columns: the call stages x and
+ * out through such buffers itself (any T >= 1).  K % stride == 0, K - stride even, K / stride + 2 <= 64:
+ * VSP_ERR_UNSUPPORTED otherwise; x == out: VSP_ERR_ARG. */
+int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                         const float* w_host, const float* bias_host, float in_slope, float* out);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch

@@ -253,7 +253,9 @@ def posterior_encoder(w, y, mask_f, g, noise, dims):
 
 
 def generator(w, x, g, dims):
-    """Generator.forward (reference models.py:271-290) with ResBlock1 (modules.py:210-223)."""
+    """Generator.forward (reference models.py:271-290) with ResBlock1 (modules.py:210-223) or, for resblock "2",
+    ResBlock2 (modules.py:245-249: one convolution per dilation, dilation[0] and dilation[1] only)."""
+    kind = getattr(dims, "resblock_kind", 1)
     x = F.conv1d(x, w["dec.conv_pre.weight"], w["dec.conv_pre.bias"], padding=3)
     x = x + F.conv1d(g, w["dec.cond.weight"], w["dec.cond.bias"])
     nk = len(dims.resblock_kernel_sizes)
@@ -265,6 +267,14 @@ def generator(w, x, g, dims):
         for j, (rk, dil) in enumerate(zip(dims.resblock_kernel_sizes, dims.resblock_dilation_sizes)):
             p = f"dec.resblocks.{i * nk + j}"
             y = x
+            if kind == 2:
+                for mth, dd in enumerate(dil[:2]):
+                    t = F.leaky_relu(y, LRELU_SLOPE)
+                    t = F.conv1d(t, w[f"{p}.convs.{mth}.weight"], w[f"{p}.convs.{mth}.bias"],
+                                 dilation=dd, padding=(rk * dd - dd) // 2)
+                    y = t + y
+                xs = y if xs is None else xs + y
+                continue
             for mth, dd in enumerate(dil):
                 t = F.leaky_relu(y, LRELU_SLOPE)
                 t = F.conv1d(t, w[f"{p}.convs1.{mth}.weight"], w[f"{p}.convs1.{mth}.bias"],

@@ -1942,11 +1942,11 @@ struct DevBuf {           // hipMalloc'd scratch of one stand-alone call
   ~DevBuf() { if (p) (void)hipFree(p); }
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
 };
-// dense [Cout][Cin][K] host weights -> packed fragment image on the device; bias -> device
+// dense [phases * Cout][Cin][K] host weights -> packed fragment image on the device; bias [Cout] -> device
 hipError_t upload_cl_conv(const float* w_host, const float* bias_host, int Cout, int Cin, int K, DevBuf& w, DevBuf& bias,
-                          hipStream_t s) {
-  std::vector<uint16_t> packed(packed_g16_halfs(Cout, Cin, K));
-  pack_g16_weights(packed.data(), Cout, Cin, K, w_host);
+                          hipStream_t s, int phases = 1) {
+  std::vector<uint16_t> packed(packed_g16_halfs(phases * Cout, Cin, K));
+  pack_g16_weights(packed.data(), phases * Cout, Cin, K, w_host);
   hipError_t e = w.alloc(packed.size() * 2);
   if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
   if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, s);
@@ -1972,6 +1972,10 @@ ClConvArgs cl_conv_args(const float* x, int T, int Cin, int Cout, int K, int dil
   return a;
 }
 int op_rc(hipError_t e) { return e == hipSuccess ? VSP_OK : (e == hipErrorInvalidValue ? VSP_ERR_UNSUPPORTED : VSP_ERR_HIP); }
+// HiFi-GAN's up-convolutions as the generator runs them (kernels.h ups_weight_offset): kt = K / stride taps per phase over
+// the input padded by kt - 1, Nq = T + 1 input times, output rows n = stride q + r - (K - stride) / 2 kept in [0, stride T)
+// -- the shapes plan_model accepts
+bool ups_shape_ok(int K, int stride) { return stride >= 1 && K >= stride && K % stride == 0 && (K - stride) % 2 == 0; }
 }  // namespace
 
 int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
@@ -2159,6 +2163,93 @@ int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilati
     e = launch_g16_conv(cl_conv_args(x, T, C, C, K, dilations[0], w[0], bias[0], 0.1f, x, terms, yp), B, s);
     if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(yp, T, C, C, K, dilations[1], w[1], bias[1], 0.1f, yp, terms, out), B, s);
   }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                            const float* w_host, const float* bias_host, float in_slope, const int32_t* lengths,
+                            int terms, float* out) {
+  if (!x || !w_host || !out || x == out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 16 || !ups_shape_ok(K, stride) || K / stride - 1 > 64 ||
+      (size_t)T * std::max<size_t>(Cin, (size_t)stride * Cout) * 4 >= (size_t)1 << 31)
+    return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int kt = K / stride;
+  if (lengths) {                                         // (the kernels read rows [0, len) of an utterance: len > T overruns x)
+    std::vector<int32_t> len(B);
+    hipError_t e = hipMemcpyAsync(len.data(), lengths, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    for (int32_t l : len)
+      if (l < 0 || l > T) return VSP_ERR_ARG;
+  }
+  // the model's channels-last packing (weights.cpp, Filler::clconv of dec.ups.*): row = phase * Cout + co
+  std::vector<float> dense((size_t)stride * Cout * Cin * kt);
+  for (int r = 0; r < stride; ++r)
+    for (int co = 0; co < Cout; ++co)
+      for (int ci = 0; ci < Cin; ++ci)
+        for (int tap = 0; tap < kt; ++tap)
+          dense[(((size_t)r * Cout + co) * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, co, r, tap, Cout, stride, kt)];
+  DevBuf w, bias;
+  hipError_t e = upload_cl_conv(dense.data(), bias_host, Cout, Cin, kt, w, bias, s, stride);
+  if (e != hipSuccess) return op_rc(e);
+  ClConvArgs a = cl_conv_args(x, T, Cin, Cout, kt, 1, w, bias, in_slope, nullptr, terms, out);
+  a.o_bs = (long)T * stride * Cout;
+  a.pad = kt - 1;
+  a.Nq = T + 1; a.T_store = T * stride;
+  a.phases = stride; a.ups_p = (K - stride) / 2;
+  a.glen = lengths; a.g_in = 1; a.g_store = stride;
+  e = launch_g16_conv(a, B, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                         const float* w_host, const float* bias_host, float in_slope, float* out) {
+  if (!x || !w_host || !out || x == out || B < 0 || T < 0) return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || !ups_shape_ok(K, stride) || K / stride - 1 + 3 > CONV_HALO) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int kt = K / stride, M = Cout * stride;
+  // the model's f32 packing (weights.cpp, Filler::conv of dec.ups.*): row = co * stride + phase
+  std::vector<float> dense((size_t)M * Cin * kt), bd(M, 0.f);
+  for (int row = 0; row < M; ++row) {
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int tap = 0; tap < kt; ++tap)
+        dense[((size_t)row * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, row / stride, row % stride, tap, Cout, stride, kt)];
+    if (bias_host) bd[row] = bias_host[row / stride];
+  }
+  std::vector<float> packed(packed_conv_floats(M, Cin, kt));
+  pack_conv_weights(packed.data(), M, Cin, kt, dense.data());
+  // run_generator's tensors: time rows padded to a multiple of 64 columns; staged here from / to the caller's dense ones
+  const long tp_in = ((long)T + 63) / 64 * 64, T_out = (long)T * stride, tp_out = (T_out + 63) / 64 * 64;
+  DevBuf w, bias, xs, os;
+  hipError_t e = w.alloc(packed.size() * 4);
+  if (e == hipSuccess) e = bias.alloc((size_t)M * 4);
+  if (e == hipSuccess) e = xs.alloc((size_t)B * Cin * tp_in * 4);
+  if (e == hipSuccess) e = os.alloc((size_t)B * Cout * tp_out * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(xs.p, 0, (size_t)B * Cin * tp_in * 4, s);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(xs.p, (size_t)tp_in * 4, x, (size_t)T * 4, (size_t)T * 4, (size_t)B * Cin, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return op_rc(e);
+  ConvArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = static_cast<const float*>(xs.p); a.x_bs = (long)Cin * tp_in; a.x_cs = tp_in;
+  a.wp = static_cast<const float*>(w.p); a.bias = static_cast<const float*>(bias.p);
+  a.out = static_cast<float*>(os.p); a.o_bs = (long)Cout * tp_out; a.o_cs = tp_out;
+  a.Cin = Cin; a.M = M; a.K = kt; a.dil = 1; a.pad = kt - 1;
+  a.T_in = T; a.Nq = T + 1; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
+  a.in_act = 1; a.in_slope = in_slope;
+  a.alpha = 1.f; a.div = 1.f;
+  a.ups_s = stride; a.ups_p = (K - stride) / 2; a.T_store = (int)T_out;
+  e = launch_conv(a, B, s);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(out, (size_t)T_out * 4, os.p, (size_t)tp_out * 4, (size_t)T_out * 4, (size_t)B * Cout,
+                         hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return op_rc(e);
 }

@@ -238,6 +238,14 @@ bool g16_pp_supported(int C, int K, int dil, int terms);
 hipError_t launch_g16_pp(const ClPairArgs& a, int B, hipStream_t s);
 size_t packed_g16_halfs(int rows, int Cin, int K);
 void pack_g16_weights(uint16_t* dst, int rows, int Cin, int K, const float* dense /* [rows][Cin][K] */);
+// HiFi-GAN's up-convolution (torch ConvTranspose1d, weight w[Cin][Cout][k], stride s, k = kt s, padding p = (k - s) / 2,
+// reference models.py:253-256) in polyphase form: one kt-tap convolution per phase r < s over the input padded by kt - 1,
+//   out[s q + r - p][co] = bias[co] + sum_{tap < kt} sum_ci x[q - (kt - 1) + tap][ci] * w[ci][co][s (kt - 1 - tap) + r]
+// for q <= T (output rows outside [0, s T) dropped).  The offset of that weight in w: the ONE mapping behind the model's
+// packing (weights.cpp: dec.ups.*) and the stand-alone operators (api.hip: vsp_cl_conv_transpose1d, vsp_conv_transpose1d).
+inline size_t ups_weight_offset(int ci, int co, int r, int tap, int Cout, int s, int kt) {
+  return ((size_t)ci * Cout + co) * ((size_t)kt * s) + (size_t)s * (kt - 1 - tap) + r;
+}
 // mel[b][m][t] = log(max(sum_{f in [lo[m], hi[m])} basis[m][f] * spec[b][f][t], 1e-5))  (reference mel_processing.py:16-22, 73-82)
 hipError_t launch_spec_to_mel(const float* spec, const float* basis, const int* lo, const int* hi, float* mel, int B,
                               int n_freq, int n_mels, int T, hipStream_t s);

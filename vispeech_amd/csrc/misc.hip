@@ -505,7 +505,8 @@ __global__ void __launch_bounds__(128) conv_post_kernel(const float* __restrict_
 }
 hipError_t launch_conv_post(const float* x, long x_bs, long x_cs, const float* w, int C, int K, float slope,
                             float* o, long o_bs, int B, int T, hipStream_t s, unsigned* flags) {
-  if (K > CP_MAXK || C > 32) return hipErrorInvalidValue;
+  // (C <= 64: the staged tile + weights, (64 * 520 + 64 * 8) * 4 = 135168 B, fit the 140 KiB requested below)
+  if (K > CP_MAXK || C < 1 || C > 64) return hipErrorInvalidValue;
   const size_t lds = ((size_t)C * (CP_TILE + 8) + (size_t)C * CP_MAXK) * sizeof(float);
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(conv_post_kernel), 140 * 1024, attr_done); e != hipSuccess) return e;

@@ -316,7 +316,10 @@ int plan_model(vsp_ctx* ctx) {
     const int cin = c0 >> i, cout = c0 >> (i + 1);
     if (cin % 32 || cout % 32 || (cin != 32 && cin % 64) || (cout != 32 && cout % 64)) m.has_cl = false;
   }
-  if ((c0 >> c.n_upsamples) > 64) m.has_cl = false;  // conv_post_cl covers <= 64 channels
+  // conv_post: both of its kernels (launch_conv_post of the f32 generator, launch_conv_post_cl) cover <= 64 channels, so
+  // every configuration the split-f16 generator serves also runs on the f32 one (VSP_GENERATOR=f32, the fallback above)
+  if ((c0 >> c.n_upsamples) > 64)
+    return ctx->fail(VSP_ERR_UNSUPPORTED, "conv_post kernels cover <= 64 input channels (got %d)", c0 >> c.n_upsamples);
   if (!m.has_cl) ctx->gen_mode = 0;
   // (conv_pre and the speaker conditioning run on the split-f16 path whenever the vocoder does)
   p.f16s = ctx->frame_f16s && ctx->gen_mode != 0;
@@ -367,7 +370,6 @@ int plan_model(vsp_ctx* ctx) {
       m.rbs.push_back(rb);
     }
   }
-  if (ch > 32) return ctx->fail(VSP_ERR_UNSUPPORTED, "conv_post kernel covers <= 32 input channels (got %d)", ch);
   m.post_c = ch;
   m.post_k = 7;
   m.post_w = p.raw((size_t)ch * 7);
@@ -655,17 +657,14 @@ int fill_model(vsp_ctx* ctx, std::vector<float>& arena) {
     if (!f.ok) break;
     const float* wd = W->data.data();
     const float* bd = B->data.data();
-    const int s = U.ups_s, kt = U.K, cout = U.M / s, k = kt * s;
-    // out[co][s*q + r - p] = sum_ci sum_m x[ci][q - m] * w[ci][co][s*m + r]; tap = kt-1-m
-    f.conv(U, [=](int row, int ci, int tap) {
-      const int co = row / s, r = row % s, mm = kt - 1 - tap;
-      return wd[((size_t)ci * cout + co) * k + s * mm + r];
-    }, [=](int row) { return bd[row / s]; });
+    const int s = U.ups_s, kt = U.K, cout = U.M / s;
+    // polyphase (kernels.h ups_weight_offset); the f32 form stacks the phases channel-major: row = co * s + r
+    f.conv(U, [=](int row, int ci, int tap) { return wd[ups_weight_offset(ci, row / s, row % s, tap, cout, s, kt)]; },
+           [=](int row) { return bd[row / s]; });
     if (m.has_cl) {
-      // polyphase: out[s*q + r - p][co] = sum_m sum_ci x[q - m][ci] * w[ci][co][s*m + r], tap = kt-1-m
-      f.clconv(m.ups_h[i], [=](int r, int co, int ci, int tap) {
-        return wd[((size_t)ci * cout + co) * k + s * (kt - 1 - tap) + r];
-      }, [=](int co) { return bd[co]; });
+      // ... and the channels-last form phase-major: row = r * cout + co (Filler::clconv)
+      f.clconv(m.ups_h[i], [=](int r, int co, int ci, int tap) { return wd[ups_weight_offset(ci, co, r, tap, cout, s, kt)]; },
+               [=](int co) { return bd[co]; });
     }
     for (int j = 0; j < nk && f.ok; ++j) {
       const ResBlockW& rb = m.rbs[i * nk + j];
