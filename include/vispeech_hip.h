@@ -421,6 +421,49 @@ int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K
 int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
                          const float* w_host, const float* bias_host, float in_slope, float* out);
 
+/* ---- output stage (round 8, ABI 7, additive) ------------------------------------------------ */
+/* The last hop of the reference's /tts handler: it writes the 44.1 kHz waveform and runs `ffmpeg -i c.wav -ar 22050`
+ * (inference_api.py:50-52); clients receive 22.05 kHz PCM16.  Here: waveform float32 at the model's rate -> polyphase FIR
+ * resampling by L / M -> float32 or PCM16 at the output rate, one launch, on the caller's stream, one-shot or chunked.
+ *
+ * The filter is specified, not copied, so that anybody can recompute it.  g = gcd(in_rate, out_rate), L = out_rate / g,
+ * M = in_rate / g, Q = max(L, M); a Kaiser-windowed sinc at rate in_rate * L:
+ *   H    = zeros * Q                                  (half length; 2 H + 1 taps)
+ *   fc   = rolloff / Q
+ *   h[n] = L fc sinc(fc n) kaiser(2 H + 1, beta)[n + H],  n = -H .. H        (numpy's sinc / kaiser conventions)
+ *   y[m] = sum_k h[m M - k L] x[k],  k in [0, n_valid) with |m M - k L| <= H,  m = 0 .. ceil(n_valid L / M) - 1
+ * x is zero outside [0, n_valid): y is scipy.signal.resample_poly(x, L, M, window = h / L).  Defaults: zeros 32,
+ * beta 9.62 (Kaiser's formula for 96 dB, the floor of a 16-bit output), rolloff 1 - 3.065 / zeros (stop-band edge on the
+ * narrower Nyquist frequency).  Supported: L <= 320, M <= 441, 1 <= zeros <= 64 (VSP_ERR_UNSUPPORTED beyond; other bad
+ * arguments VSP_ERR_ARG).  L = M = 1 is the pass-through: H = 0, one unit tap -- quantisation only.
+ *
+ * vsp_resample_plan / vsp_resample_filter / vsp_resample_out_len are host-only (no device, like vsp_mel_filterbank): the
+ * plan, the 2 H + 1 taps (computed in double precision, rounded to fp32 once; rolloff <= 0 selects the default) and
+ * ceil(n L / M). */
+int vsp_resample_plan(int in_rate, int out_rate, int zeros, int* L, int* M, int* half_len);
+int vsp_resample_filter(int in_rate, int out_rate, int zeros, double beta, double rolloff, float* taps_host);
+int64_t vsp_resample_out_len(int64_t n, int L, int M);
+/* Builds the filter of (in_rate -> out_rate) and uploads its table to the context's device; replaces an earlier one.  May
+ * allocate and synchronise (like vsp_finalize_weights; needs no weights).  out_rate == in_rate configures the pass-through,
+ * out_rate == 0 turns the stage off and frees the table.  zeros == 0: 32; rolloff <= 0: 1 - 3.065 / zeros. */
+int vsp_output_configure(vsp_ctx* ctx, int in_rate, int out_rate, int zeros, double beta, double rolloff);
+/* No allocation, no synchronisation, caller's stream.  x [B][x_stride] holds input samples [x_first, x_first + x_len) of
+ * each utterance; n_valid [B] (DEVICE int64, NULL = n_max for all) is each utterance's TOTAL valid length, n_max (host) an
+ * upper bound of them (the padded length: the host cannot read n_valid without a synchronisation, so the shape checks and
+ * the grid use n_max; n_valid is clamped to [0, n_max]).  Writes output samples [m0, m1) to out[b][0 .. m1 - m0)
+ * (out [B][out_stride]; float32 if pcm == 0, int16 if pcm == 1: clip(rint(y * 32767.0f), -32768, 32767), round half to
+ * even, product in fp32 -- the rule of vispeech_amd.service.pcm16).  Samples at and behind ceil(n_valid[b] L / M) are
+ * written as 0.  Input positions outside [0, n_valid[b]) are never read: what a padded batch holds there cannot reach
+ * the output.  Every input sample of [0, n_max) that a requested output depends on must lie in the passed window, and
+ * x_first + x_len <= n_max, x_len <= x_stride, m1 <= ceil(n_max L / M), m1 - m0 <= out_stride: VSP_ERR_SHAPE otherwise,
+ * decided on the host before anything is launched.  The one-shot call is x_first = 0, x_len = n_max, m0 = 0,
+ * m1 = ceil(n_max L / M).  An output sample's value depends on (x, m) alone -- one thread per sample, fp32 FMAs in ascending
+ * k -- not on the window, the tile or the batch layout: outputs computed window by window are the bytes of the one-shot call
+ * (which outputs a window completes: vispeech_amd.output_stage.complete_outputs).  Not configured: VSP_ERR_STATE. */
+int vsp_output_chunk(vsp_ctx* ctx, void* stream, int B, const float* x, int64_t x_stride, int64_t x_first, int64_t x_len,
+                     const int64_t* n_valid, int64_t n_max, int64_t m0, int64_t m1, void* out, int64_t out_stride,
+                     int pcm);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

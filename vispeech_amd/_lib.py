@@ -107,6 +107,11 @@ SIGNATURES = {
     "vsp_cl_resblock2": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_cl_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),
     "vsp_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P]),
+    "vsp_resample_plan": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "vsp_resample_filter": (_I, [_I, _I, _I, C.c_double, C.c_double, _P]),
+    "vsp_resample_out_len": (_I64, [_I64, _I, _I]),
+    "vsp_output_configure": (_I, [_P, _I, _I, _I, C.c_double, C.c_double]),
+    "vsp_output_chunk": (_I, [_P, _P, _I, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -911,6 +911,7 @@ int vsp_destroy(vsp_ctx* ctx) {
   if (ctx->flags_host) (void)hipHostFree(ctx->flags_host);
   for (auto st : ctx->side) if (st) (void)hipStreamDestroy(st);
   if (ctx->arena && ctx->arena_owned) (void)hipFree(ctx->arena);
+  if (ctx->out_tab) (void)hipFree(ctx->out_tab);
   delete ctx;
   return VSP_OK;
 }

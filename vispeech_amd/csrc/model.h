@@ -161,6 +161,10 @@ struct vsp_ctx {
   const int64_t* fl_known_src = nullptr;
   hipStream_t side[2] = {nullptr, nullptr};
   std::vector<hipEvent_t> sync_ev;
+  // output stage (resample.hip, vsp_output_configure): the polyphase table [P][L] on the device and its plan -- resampling
+  // by L / M with 2 H + 1 prototype taps, P taps per output starting J = H / L input samples before the output's own
+  float* out_tab = nullptr;
+  int out_L = 0, out_M = 0, out_H = 0, out_J = 0, out_P = 0;
   int64_t noise_first = 0;        // stream index of element 0 of a library-drawn noise tensor (vsp_set_noise_offset)
   bool adopted_pending = false;   // an adopted arena whose header has not been checked yet (vsp_commit_adopted_weights)
   int gen_mode = 1;  // 0: f32 MFMA channel-major generator, 1: split-f16 (fp32-accurate) channels-last generator,

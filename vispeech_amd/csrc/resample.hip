@@ -1,0 +1,347 @@
+// Output stage of the service path (include/vispeech_hip.h, "output stage"): waveform float32 at the model's rate ->
+// rational polyphase FIR resampling by L / M -> float32 or PCM16 at the output rate.  What the reference does with
+// `ffmpeg -i c.wav -ar 22050` after synthesis (inference_api.py:50-52), on the GPU and chunk by chunk.
+//
+//   y[m] = sum_k h[m M - k L] x[k],  |m M - k L| <= H,  k in [0, n_valid)        h: Kaiser-windowed sinc, 2 H + 1 taps
+//
+// With m M = k0 L + p (p = the sample's phase) the taps of one output are h[p + j L]; the table holds them per phase in
+// ASCENDING k, all phases padded with zeros to the same count P and aligned to the same first input sample k0 - J
+// (J = H / L):   tab[i][m mod L] = h[p(m) + (J - i) L],  i = 0 .. P - 1,  input sample k = k0 - J + i.
+// The column index is m mod L, not p: m -> p is a bijection of [0, L) (gcd(L, M) = 1), and neighbouring lanes (consecutive
+// m) then read neighbouring words of a table row -- a coalesced read of an L2-resident table (113 KB at most for the
+// default filters) where a phase-major table would cost one cache line per lane.
+//
+// One thread per output sample, fp32 FMAs in ascending k: a sample's value is a function of (x, m) alone -- not of the tile,
+// the window a streaming caller passes or the batch layout -- which is what makes the streamed output byte-identical to
+// the one-shot one.  Samples outside [0, n_valid[b]) and outside the passed window are never read (selected to zero while
+// the tile is staged), so whatever a padded batch holds behind an utterance's end cannot reach the output.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "model.h"
+
+namespace {
+
+constexpr int RS_TILE = 256;            // output samples (= threads) per block
+constexpr int RS_X_LDS_FLOATS = 12288;  // input staging area per block (48 KiB)
+constexpr int RS_TAB_LDS_FLOATS = 4096; // a one-phase table (L = 1) up to this size is held in LDS (16 KiB)
+constexpr int RS_MIN_PASS = 32;         // fewer taps per staging pass than this: read x from global memory instead
+
+struct ResampleArgs {
+  const float* x;
+  int64_t x_stride, x_first, x_len;
+  const int64_t* n_valid;
+  int64_t n_max, m0, m1;
+  void* out;
+  int64_t out_stride;
+  const float* tab;       // [P][L]
+  int L, M, J, P;
+  int pass;               // taps per staging pass (multiple of 4, or P)
+  int xs_words;           // LDS words of the input tile (the one-phase table follows it)
+  int seg;                // L = 1 staging: words per polyphase segment of the de-interleaved tile (0: linear tile)
+  int mode;               // 0: x tile in LDS, table from global / L2;  1: L = 1, de-interleaved x tile + table in LDS;
+                          // 2: x and table from global memory (spans too long for LDS)
+  int pcm;                // 0: float32 out, 1: int16 out
+  int pair_ok;            // int16 rows are 4-byte aligned: even lanes store packed pairs
+  int vec_ok;             // x rows are 16-byte aligned: the tile is staged with 16-byte loads
+};
+
+__device__ __forceinline__ int rs_pcm16(float y) {
+  // service.pcm16: clip(rint(y * 32767.0f), -32768, 32767), product in fp32, round half to even
+  const float r = rintf(y * 32767.0f);
+  return (int)fminf(fmaxf(r, -32768.f), 32767.f);
+}
+
+__global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a) {
+  extern __shared__ float smem[];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int64_t m_first = a.m0 + (int64_t)blockIdx.x * RS_TILE;
+  const int64_t m_last = min(m_first + RS_TILE, a.m1) - 1;         // (the grid covers [m0, m1): m_first <= m_last)
+  const int64_t m = m_first + tid;
+  const bool active = m <= m_last;
+  const int64_t mm = active ? m : m_last;                            // idle lanes shadow the last sample: offsets stay in the tile
+  int64_t nv = a.n_valid ? a.n_valid[b] : a.n_max;
+  nv = min(max(nv, (int64_t)0), a.n_max);
+  const int64_t lo = max(a.x_first, (int64_t)0), hi = min(nv, a.x_first + a.x_len);   // readable samples [lo, hi)
+  const int64_t out_len = (nv * a.L + a.M - 1) / a.M;
+  const float* __restrict__ xb = a.x + (int64_t)b * a.x_stride - a.x_first;             // xb[k] = sample k of utterance b
+  const int64_t ks = (mm * a.M) / a.L - a.J;                                             // first input sample of this output
+  const int col = (int)(mm % a.L);
+  const float* __restrict__ tcol = a.tab + col;
+  float acc = 0.f;
+
+  if (a.mode == 2) {
+    for (int i = 0; i < a.P; ++i) {
+      const int64_t k = ks + i;
+      const float xv = (k >= lo && k < hi) ? xb[k] : 0.f;
+      acc = fmaf(tcol[(size_t)i * a.L], xv, acc);
+    }
+  } else {
+    float* xs = smem;
+    float* ts = smem + a.xs_words;
+    if (a.mode == 1) {
+      for (int i = tid; i < a.P; i += RS_TILE) ts[i] = a.tab[i];
+    }
+    int64_t kb = (m_first * a.M) / a.L - a.J;                        // first input sample of the tile
+    if (a.vec_ok) kb -= (((int64_t)b * a.x_stride - a.x_first + kb) & 3);   // ... moved down to a 16-byte boundary of x
+    const int off = (int)(ks - kb);
+    const int span = (int)((m_last * a.M) / a.L - a.J - kb) + 1;    // tile words before the pass's taps are added
+    for (int i0 = 0; i0 < a.P; i0 += a.pass) {
+      const int n_i = min(a.pass, a.P - i0);
+      const int need = span + n_i - 1;
+      const int64_t k_base = kb + i0;
+      if (i0) __syncthreads();
+      if (a.vec_ok) {
+        for (int o = tid * 4; o < need; o += RS_TILE * 4) {
+          const int64_t k = k_base + o;
+          float4 v;
+          if (k >= lo && k + 3 < hi) {
+            v = *reinterpret_cast<const float4*>(xb + k);
+          } else {
+            v.x = (k >= lo && k < hi) ? xb[k] : 0.f;
+            v.y = (k + 1 >= lo && k + 1 < hi) ? xb[k + 1] : 0.f;
+            v.z = (k + 2 >= lo && k + 2 < hi) ? xb[k + 2] : 0.f;
+            v.w = (k + 3 >= lo && k + 3 < hi) ? xb[k + 3] : 0.f;
+          }
+          if (a.seg) {
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) xs[((o + q) % a.M) * a.seg + (o + q) / a.M] = e[q];
+          } else {
+            *reinterpret_cast<float4*>(xs + o) = v;
+          }
+        }
+      } else {
+        for (int o = tid; o < need; o += RS_TILE) {
+          const int64_t k = k_base + o;
+          const float v = (k >= lo && k < hi) ? xb[k] : 0.f;
+          xs[a.seg ? (o % a.M) * a.seg + o / a.M : o] = v;
+        }
+      }
+      __syncthreads();
+      if (a.mode == 1) {
+        // L = 1: lane t reads tile word off + i = (off0 + t M) + i.  In the de-interleaved tile (word o at
+        // (o mod M) seg + o / M) the lanes of a wave read consecutive words of one segment: no bank conflict where the
+        // linear tile would be read at stride M; the tap is the same for all lanes (a broadcast LDS read).
+        // Taps are fetched four at a time (one 16-byte broadcast read): 1.25 LDS reads per FMA instead of 2.
+        int r = off % a.M;
+        const float* xp = xs + r * a.seg + off / a.M;
+        const int wrap = a.M * a.seg - 1;
+        auto step = [&]() { xp += a.seg; if (++r == a.M) { r = 0; xp -= wrap; } };
+        int i = 0;
+        for (; i + 4 <= n_i; i += 4) {
+          const float4 t = *reinterpret_cast<const float4*>(ts + i0 + i);
+          acc = fmaf(t.x, *xp, acc); step();
+          acc = fmaf(t.y, *xp, acc); step();
+          acc = fmaf(t.z, *xp, acc); step();
+          acc = fmaf(t.w, *xp, acc); step();
+        }
+        for (; i < n_i; ++i) { acc = fmaf(ts[i0 + i], *xp, acc); step(); }
+      } else {
+        const float* __restrict__ tp = tcol + (size_t)i0 * a.L;
+        const float* xo = xs + off;
+        int i = 0;
+        for (; i + 4 <= n_i; i += 4) {                               // (four table loads in flight; the FMA order stays ascending)
+          const float t0 = tp[(size_t)i * a.L], t1 = tp[(size_t)(i + 1) * a.L], t2 = tp[(size_t)(i + 2) * a.L],
+                      t3 = tp[(size_t)(i + 3) * a.L];
+          acc = fmaf(t0, xo[i], acc);
+          acc = fmaf(t1, xo[i + 1], acc);
+          acc = fmaf(t2, xo[i + 2], acc);
+          acc = fmaf(t3, xo[i + 3], acc);
+        }
+        for (; i < n_i; ++i) acc = fmaf(tp[(size_t)i * a.L], xo[i], acc);
+      }
+    }
+  }
+
+  const float y = m < out_len ? acc : 0.f;                           // behind the utterance's own output: silence
+  const int64_t j = m - a.m0;
+  if (!a.pcm) {
+    if (active) static_cast<float*>(a.out)[(int64_t)b * a.out_stride + j] = y;
+    return;
+  }
+  const int q = rs_pcm16(y);
+  const int q_next = __shfl_down(q, 1);                              // (all lanes take part; idle lanes hold a valid shadow)
+  int16_t* o16 = static_cast<int16_t*>(a.out) + (int64_t)b * a.out_stride + j;
+  if (a.pair_ok) {
+    if (!(tid & 1) && active) {
+      if (m + 1 <= m_last) *reinterpret_cast<uint32_t*>(o16) = (uint32_t)(q & 0xffff) | ((uint32_t)q_next << 16);
+      else *o16 = (int16_t)q;
+    }
+  } else if (active) {
+    *o16 = (int16_t)q;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- host: plan and filter
+double bessel_i0(double x) {
+  const double q = x * x / 4.0;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < sum * 1e-18) break;
+  }
+  return sum;
+}
+
+struct Plan { int L = 0, M = 0, H = 0; };
+
+int make_plan(int in_rate, int out_rate, int zeros, Plan& p) {
+  if (in_rate <= 0 || out_rate <= 0 || zeros < 1) return VSP_ERR_ARG;
+  const int g = std::gcd(in_rate, out_rate);
+  p.L = out_rate / g;
+  p.M = in_rate / g;
+  if (p.L > 320 || p.M > 441 || zeros > 64) return VSP_ERR_UNSUPPORTED;
+  p.H = (p.L == 1 && p.M == 1) ? 0 : zeros * std::max(p.L, p.M);    // L = M = 1: the pass-through, one unit tap
+  return VSP_OK;
+}
+
+// h[n], n = -H .. H, in double precision (numpy's sinc and kaiser conventions)
+void make_filter(const Plan& p, int zeros, double beta, double rolloff, std::vector<double>& h) {
+  const int H = p.H;
+  h.assign((size_t)2 * H + 1, 0.0);
+  if (H == 0) { h[0] = 1.0; return; }
+  const double fc = rolloff / std::max(p.L, p.M);
+  const double i0b = bessel_i0(beta);
+  const double pi = 3.14159265358979323846;
+  for (int n = -H; n <= H; ++n) {
+    const double r = (double)n / H;
+    const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    const double a = pi * fc * n;
+    const double s = n == 0 ? 1.0 : std::sin(a) / a;
+    h[(size_t)(n + H)] = p.L * fc * s * w;
+  }
+}
+
+double default_rolloff(int zeros) { return 1.0 - 3.065 / zeros; }
+
+inline int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+
+}  // namespace
+
+int vsp_resample_plan(int in_rate, int out_rate, int zeros, int* L, int* M, int* half_len) {
+  Plan p;
+  if (!L || !M || !half_len) return VSP_ERR_ARG;
+  if (int rc = make_plan(in_rate, out_rate, zeros, p)) return rc;
+  *L = p.L; *M = p.M; *half_len = p.H;
+  return VSP_OK;
+}
+
+int vsp_resample_filter(int in_rate, int out_rate, int zeros, double beta, double rolloff, float* taps_host) {
+  Plan p;
+  if (!taps_host || !(beta >= 0.0) || !(rolloff <= 1.0)) return VSP_ERR_ARG;
+  if (int rc = make_plan(in_rate, out_rate, zeros, p)) return rc;
+  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
+  std::vector<double> h;
+  make_filter(p, zeros, beta, rolloff, h);
+  for (size_t i = 0; i < h.size(); ++i) taps_host[i] = (float)h[i];
+  return VSP_OK;
+}
+
+int64_t vsp_resample_out_len(int64_t n, int L, int M) {
+  if (n < 0 || L < 1 || M < 1) return VSP_ERR_ARG;
+  return (n * L + M - 1) / M;
+}
+
+int vsp_output_configure(vsp_ctx* ctx, int in_rate, int out_rate, int zeros, double beta, double rolloff) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (out_rate == 0) {                                   // off
+    if (ctx->out_tab) (void)hipFree(ctx->out_tab);
+    ctx->out_tab = nullptr;
+    ctx->out_L = ctx->out_M = ctx->out_H = ctx->out_J = ctx->out_P = 0;
+    return VSP_OK;
+  }
+  if (zeros == 0) zeros = 32;
+  if (!(beta >= 0.0)) return ctx->fail(VSP_ERR_ARG, "output stage: beta must be >= 0");
+  if (!(rolloff <= 1.0)) return ctx->fail(VSP_ERR_ARG, "output stage: rolloff must be in (0, 1] (<= 0: 1 - 3.065 / zeros)");
+  Plan p;
+  if (int rc = make_plan(in_rate, out_rate, zeros, p))
+    return ctx->fail(rc, "output stage %d -> %d Hz, %d zeros: rates must be positive, L <= 320, M <= 441, 1 <= zeros <= 64",
+                     in_rate, out_rate, zeros);
+  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
+  std::vector<double> h;
+  make_filter(p, zeros, beta, rolloff, h);
+  const int L = p.L, M = p.M, H = p.H;
+  const int J = H / L;
+  const int P = J + (H + L - 1) / L + 1;
+  std::vector<float> tab((size_t)P * L, 0.f);
+  for (int c = 0; c < L; ++c) {
+    const int64_t ph = ((int64_t)c * M) % L;
+    for (int i = 0; i < P; ++i) {
+      const int64_t t = ph + (int64_t)(J - i) * L;
+      if (t >= -H && t <= H) tab[(size_t)i * L + c] = (float)h[(size_t)(t + H)];
+    }
+  }
+  void* d = nullptr;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipMalloc(&d, tab.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (d) (void)hipFree(d);
+    return ctx->fail(VSP_ERR_HIP, "output stage table: %s", hipGetErrorString(e));
+  }
+  if (ctx->out_tab) (void)hipFree(ctx->out_tab);
+  ctx->out_tab = static_cast<float*>(d);
+  ctx->out_L = L; ctx->out_M = M; ctx->out_H = H; ctx->out_J = J; ctx->out_P = P;
+  return VSP_OK;
+}
+
+int vsp_output_chunk(vsp_ctx* ctx, void* stream, int B, const float* x, int64_t x_stride, int64_t x_first, int64_t x_len,
+                     const int64_t* n_valid, int64_t n_max, int64_t m0, int64_t m1, void* out, int64_t out_stride,
+                     int pcm) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (!ctx->out_tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
+  if (B < 0 || B > 65535 || !x || !out || (pcm != 0 && pcm != 1)) return ctx->fail(VSP_ERR_ARG, "vsp_output_chunk: null or bad argument");
+  const int64_t L = ctx->out_L, M = ctx->out_M, H = ctx->out_H;
+  if (n_max < 0 || n_max > ((int64_t)1 << 40) || x_first < 0 || x_len < 0 || x_first + x_len > n_max || x_len > x_stride)
+    return ctx->fail(VSP_ERR_SHAPE, "vsp_output_chunk: window [%lld, +%lld) outside [0, n_max = %lld) or longer than its row",
+                     (long long)x_first, (long long)x_len, (long long)n_max);
+  if (m0 < 0 || m1 < m0 || m1 > (n_max * L + M - 1) / M || m1 - m0 > out_stride)
+    return ctx->fail(VSP_ERR_SHAPE, "vsp_output_chunk: outputs [%lld, %lld) outside [0, ceil(n_max L / M)) or longer than their row",
+                     (long long)m0, (long long)m1);
+  if (B == 0 || m1 == m0) return VSP_OK;
+  // every input sample of [0, n_max) that a requested output depends on must be in the window
+  const int64_t k_lo = std::max<int64_t>(0, ceil_div(m0 * M - H, L));
+  const int64_t k_hi = std::min<int64_t>(n_max - 1, floor_div((m1 - 1) * M + H, L));
+  if (k_lo <= k_hi && (k_lo < x_first || k_hi >= x_first + x_len))
+    return ctx->fail(VSP_ERR_SHAPE, "vsp_output_chunk: outputs [%lld, %lld) need input samples [%lld, %lld], the window holds [%lld, %lld)",
+                     (long long)m0, (long long)m1, (long long)k_lo, (long long)k_hi, (long long)x_first,
+                     (long long)(x_first + x_len));
+  ResampleArgs a;
+  a.x = x; a.x_stride = x_stride; a.x_first = x_first; a.x_len = x_len;
+  a.n_valid = n_valid; a.n_max = n_max; a.m0 = m0; a.m1 = m1;
+  a.out = out; a.out_stride = out_stride;
+  a.tab = ctx->out_tab;
+  a.L = (int)L; a.M = (int)M; a.J = ctx->out_J; a.P = ctx->out_P;
+  a.pcm = pcm;
+  a.pair_ok = pcm && ((uintptr_t)out % 4 == 0) && (out_stride % 2 == 0);
+  a.vec_ok = ((uintptr_t)x % 16 == 0) && (x_stride % 4 == 0);
+  // tile words: the outputs of a tile start within (TILE - 1) M / L + 1 samples of each other, + 3 for the alignment
+  const int64_t span = ((int64_t)(RS_TILE - 1) * M) / L + 2 + 3;
+  const bool one_phase = L == 1 && a.P <= RS_TAB_LDS_FLOATS;
+  const int64_t room = one_phase ? RS_X_LDS_FLOATS - span - 2 * M - 8 : RS_X_LDS_FLOATS - span - 8;
+  a.seg = 0;
+  if (room >= std::min<int64_t>(a.P, RS_MIN_PASS)) {
+    a.pass = room >= a.P ? a.P : (int)(room & ~(int64_t)3);
+    a.mode = one_phase ? 1 : 0;
+    if (one_phase) a.seg = (int)((span + a.pass + 3) / M + 2);          // (every tile word, the 16-byte loads' overhang included)
+    a.xs_words = one_phase ? (int)(M * a.seg) : (int)(span + a.pass + 8);
+    a.xs_words = (a.xs_words + 3) & ~3;
+  } else {
+    a.pass = a.P;
+    a.mode = 2;
+    a.xs_words = 0;
+  }
+  const size_t lds = (size_t)(a.xs_words + (a.mode == 1 ? a.P : 0)) * sizeof(float);   // <= 48 KiB + 16 KiB
+  const dim3 grid((unsigned)((m1 - m0 + RS_TILE - 1) / RS_TILE), (unsigned)B);
+  hipLaunchKernelGGL(resample_kernel, grid, dim3(RS_TILE), lds, (hipStream_t)stream, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "resample_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}

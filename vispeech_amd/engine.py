@@ -508,6 +508,74 @@ class Engine:
             _lib.check(rc, self.ctx, "vsp_generator_stream_chunk")
             yield o
 
+    # ------------------------------------------------------------------ output stage
+    def configure_output(self, out_rate: Optional[int], zeros: int = 32, beta: float = 9.62,
+                         rolloff: Optional[float] = None, in_rate: Optional[int] = None) -> None:
+        """``vsp_output_configure``: build and upload the filter that takes the waveform from ``in_rate`` (the model's
+        sampling rate) to ``out_rate`` -- what the reference's service does with ffmpeg after synthesis
+        (inference_api.py:51).  ``out_rate`` equal to ``in_rate`` is the pass-through (quantisation only), None turns the
+        stage off.  Allocates: call it once, outside the request path."""
+        from . import output_stage
+        in_rate = int(self.dims.sampling_rate if in_rate is None else in_rate)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_output_configure(self.ctx, in_rate, 0 if out_rate is None else int(out_rate), int(zeros),
+                                               float(beta), 0.0 if rolloff is None else float(rolloff))
+        _lib.check(rc, self.ctx, "vsp_output_configure")
+        self.output_plan = None if out_rate is None else output_stage.plan(in_rate, int(out_rate), int(zeros))
+        self.output_rate = None if out_rate is None else int(out_rate)
+
+    output_plan = None        # (L, M, H) of the configured output stage
+    output_rate = None
+
+    def output_chunk(self, x: torch.Tensor, x_first: int, n_max: int, m0: int, m1: int, n_valid=None,
+                     pcm: bool = True) -> torch.Tensor:
+        """``vsp_output_chunk``: output samples [m0, m1) of every utterance from the window ``x`` [B, n] (float32 on the
+        device, rows may be strided), which holds input samples [x_first, x_first + n).  ``n_valid``: None or the
+        utterances' total valid lengths (int64 on the device).  Returns [B, m1 - m0], int16 if ``pcm`` else float32."""
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise ValueError("x must be a float32 [B, n] tensor on the engine's device with contiguous rows")
+        B, n = x.shape
+        nv = None if n_valid is None else _dev_i64(n_valid, self.device)
+        if nv is not None and nv.numel() != B:
+            raise ValueError(f"n_valid must have {B} entries")
+        out = torch.empty((B, max(int(m1 - m0), 0)), dtype=torch.int16 if pcm else torch.float32, device=self.device)
+        if out.numel() == 0:
+            return out
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_output_chunk(self.ctx, self._stream(), B, _ptr(x), x.stride(0) if B > 1 else max(n, 1),
+                                           int(x_first), n, _ptr(nv), int(n_max), int(m0), int(m1), _ptr(out),
+                                           out.shape[1], int(bool(pcm)))
+        _lib.check(rc, self.ctx, "vsp_output_chunk")
+        return out
+
+    def output(self, o: torch.Tensor, sample_lengths=None, pcm: bool = True):
+        """One-shot output stage of a whole batch: ``o`` [B, 1, n] or [B, n] as ``infer`` returns it, ``sample_lengths``
+        the valid samples per utterance (None: all n) -> (tensor [B, ceil(n L / M)], out_lengths).  What ``o`` holds
+        behind an utterance's valid length is never read; the output behind ``out_lengths[b]`` is 0."""
+        from . import output_stage
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        x = o.reshape(o.shape[0], -1) if o.dim() == 3 else o
+        L, M, _ = self.output_plan
+        nv = None if sample_lengths is None else _dev_i64(sample_lengths, self.device).clamp(0, x.shape[1])
+        y = output_stage.one_shot(self, x, nv, pcm)
+        lens = torch.full((x.shape[0],), y.shape[1], dtype=torch.int64, device=self.device) if nv is None \
+            else (nv * L + (M - 1)) // M
+        return y, lens
+
+    def output_stream(self, chunks, n_valid=None, pcm: bool = True):
+        """Streamed output stage: consumes the [B, 1, n] chunks of ``generator_stream`` (or any consecutive windows of a
+        waveform), keeps the history the filter still needs between chunks on the device, yields the output samples
+        each chunk completes ([B, m] tensors) and flushes the tail when the chunks end.  The concatenation equals
+        ``output`` of the concatenated waveform bit for bit (``vispeech_amd.output_stage.stream``)."""
+        from . import output_stage
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        nv = None if n_valid is None else _dev_i64(n_valid, self.device)
+        return output_stage.stream(self, chunks, nv, pcm)
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

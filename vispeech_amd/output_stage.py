@@ -1,0 +1,101 @@
+"""Host logic of the output stage (include/vispeech_hip.h, "output stage"): the plan and taps of the resampling filter,
+and the one place that decides which output samples a streamed window completes and which input samples the next window
+still needs.  All arithmetic on audio runs in ``vsp_output_chunk``; the functions here drive an *engine* -- any object with
+
+    output_plan                                                  (L, M, H) of the configured stage
+    output_chunk(x, x_first, n_max, m0, m1, n_valid, pcm)        output samples [m0, m1) from the window x [B, n]
+                                                                 that holds input samples [x_first, x_first + n)
+
+-- which is ``vispeech_amd.engine.Engine`` in production and a double-precision stand-in in the host tests.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Iterable, Iterator, Optional, Tuple
+
+import numpy as np
+
+DEFAULT_ZEROS = 32
+DEFAULT_BETA = 9.62          # Kaiser's formula for 96 dB, the floor of a 16-bit output
+
+
+def default_rolloff(zeros: int = DEFAULT_ZEROS) -> float:
+    """Puts the stop-band edge on the narrower Nyquist frequency."""
+    return 1.0 - 3.065 / zeros
+
+
+def plan(in_rate: int, out_rate: int, zeros: int = DEFAULT_ZEROS) -> Tuple[int, int, int]:
+    """``vsp_resample_plan``: (L, M, H) -- resampling by L / M with a prototype of 2 H + 1 taps."""
+    from . import _lib
+    L, M, H = C.c_int(), C.c_int(), C.c_int()
+    rc = _lib.lib().vsp_resample_plan(int(in_rate), int(out_rate), int(zeros), C.byref(L), C.byref(M), C.byref(H))
+    _lib.check(rc, None, f"vsp_resample_plan({in_rate} -> {out_rate}, zeros = {zeros})")
+    return L.value, M.value, H.value
+
+
+def taps(in_rate: int, out_rate: int, zeros: int = DEFAULT_ZEROS, beta: float = DEFAULT_BETA,
+         rolloff: Optional[float] = None) -> np.ndarray:
+    """``vsp_resample_filter``: the library's own fp32 prototype h[-H .. H]."""
+    from . import _lib
+    _, _, H = plan(in_rate, out_rate, zeros)
+    h = np.zeros(2 * H + 1, dtype=np.float32)
+    rc = _lib.lib().vsp_resample_filter(int(in_rate), int(out_rate), int(zeros), float(beta),
+                                        0.0 if rolloff is None else float(rolloff), h.ctypes.data_as(C.c_void_p))
+    _lib.check(rc, None, "vsp_resample_filter")
+    return h
+
+
+def out_len(n: int, L: int, M: int) -> int:
+    """ceil(n L / M): output samples of an utterance of n input samples."""
+    return -((-int(n) * L) // M)
+
+
+def complete_outputs(n_seen: int, L: int, M: int, H: int, ended: bool = False) -> int:
+    """How many leading output samples are final once input samples [0, n_seen) are known: sample m is complete when its
+    last tap lies inside them, m M + H < L n_seen, or when the input has ended."""
+    total = out_len(n_seen, L, M)
+    if ended:
+        return total
+    return min(total, max(0, -((H - L * int(n_seen)) // M)))          # ceil((L n_seen - H) / M)
+
+
+def history_start(m_next: int, L: int, M: int, H: int) -> int:
+    """First input sample that output sample ``m_next`` (the first incomplete one) depends on: ceil((m M - H) / L)."""
+    return max(0, -((H - int(m_next) * M) // L))
+
+
+def _cat(a, b):
+    if isinstance(a, np.ndarray):
+        return np.concatenate([a, b], axis=1)
+    import torch
+    return torch.cat([a, b], dim=1)
+
+
+def one_shot(eng, x, n_valid=None, pcm: bool = True):
+    """The whole of x [B, n] in one ``output_chunk`` call -> [B, ceil(n L / M)]."""
+    L, M, _ = eng.output_plan
+    n = int(x.shape[1])
+    return eng.output_chunk(x, 0, n, 0, out_len(n, L, M), n_valid, pcm)
+
+
+def stream(eng, chunks: Iterable, n_valid=None, pcm: bool = True) -> Iterator:
+    """Consumes consecutive windows [B, n_i] of the input and yields, per window, the output samples it completes
+    ([B, m_i], possibly nothing for a short window), then the tail once the input has ended.  Between windows only the
+    input samples that incomplete outputs still need are kept (about 2 H / L of them, on the device for device chunks).
+    The concatenation equals ``one_shot`` of the concatenated input exactly: the same samples go through the same
+    ``output_chunk`` arithmetic, whose result depends on (x, m) alone."""
+    L, M, H = eng.output_plan
+    hist, first, seen, m_next = None, 0, 0, 0
+    for c in chunks:
+        x = c.reshape(c.shape[0], -1)
+        win = x if hist is None or hist.shape[1] == 0 else _cat(hist, x)
+        seen += int(x.shape[1])
+        m_done = complete_outputs(seen, L, M, H)
+        if m_done > m_next:
+            yield eng.output_chunk(win, first, seen, m_next, m_done, n_valid, pcm)
+            m_next = m_done
+        k = min(seen, history_start(m_next, L, M, H))
+        hist, first = win[:, k - first:], k
+    m_end = out_len(seen, L, M)
+    if hist is not None and m_end > m_next:
+        yield eng.output_chunk(hist, first, seen, m_next, m_end, n_valid, pcm)

@@ -25,6 +25,12 @@ def pcm16(audio) -> np.ndarray:
     return np.clip(np.rint(np.asarray(a, dtype=np.float32).reshape(-1) * 32767.0), -32768, 32767).astype("<i2")
 
 
+def _host_i16(y) -> np.ndarray:
+    """int16 output of the engine's output stage -> little-endian int16 on the host."""
+    a = y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)
+    return np.ascontiguousarray(a.reshape(-1), dtype="<i2")
+
+
 class Busy(RuntimeError):
     """Another synthesis is in flight (the reference answers such a request with a 'server busy' text)."""
 
@@ -74,13 +80,38 @@ class _LockedStream:
 class SynthesisService:
     """One model, one synthesis at a time, never queueing (reference inference_api.py:13, 37)."""
 
-    def __init__(self, net, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667, stream=None):
+    def __init__(self, net, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667, stream=None,
+                 *, output_rate: Optional[int] = None, device_pcm: bool = False):
+        """``output_rate``: deliver PCM16 at this rate instead of the model's -- the reference's service sends the
+        22.05 kHz file that ``ffmpeg -ar 22050`` makes of the waveform (inference_api.py:51); here the engine's output
+        stage resamples and quantises on the GPU, one-shot and per streamed chunk, and int16 is what crosses to the
+        host.  ``device_pcm=True`` without a rate: the same stage as a pass-through (GPU quantisation at the model's
+        rate).  Neither: the float32 copy and the host quantiser, exactly as before."""
         self.net = net
         self.sampling_rate = int(sampling_rate)
         self.chunk_frames = int(chunk_frames)
         self.noise_scale = float(noise_scale)
         self._lock = threading.Lock()
         self._stream = stream          # a torch.cuda.Stream all of this service's GPU work runs on (None: the caller's)
+        self.output_rate = None if output_rate is None else int(output_rate)
+        self._output_stage = output_rate is not None or bool(device_pcm)
+        if self._output_stage:
+            with self._scope():
+                net._engine.configure_output(self.delivered_rate, in_rate=self.sampling_rate)
+
+    @property
+    def delivered_rate(self) -> int:
+        """Sampling rate of the PCM16 this service returns."""
+        return self.sampling_rate if self.output_rate is None else self.output_rate
+
+    def _output_engine(self):
+        """The engine, checked: the output stage is state of the ENGINE, and another service on the same model may have
+        configured another rate since this one was built."""
+        eng = self.net._engine
+        if eng.output_rate != self.delivered_rate:
+            raise RuntimeError(f"the engine's output stage delivers {eng.output_rate} Hz, this service {self.delivered_rate} Hz: "
+                               "one output rate per model context")
+        return eng
 
     def _scope(self):
         """The stream scope of this service's GPU work (``PooledSynthesisService`` gives every slot its own stream)."""
@@ -112,14 +143,19 @@ class SynthesisService:
             with self._scope():
                 o, frames = self._infer(batch, noise)
                 hop = self.net.dims.total_upsample
-                pcm = pcm16(o[utterance, 0, : int(frames[utterance]) * hop])      # (device -> host: the stream has drained)
+                if self._output_stage:
+                    y, _ = self._output_engine().output(o[utterance:utterance + 1, 0, : int(frames[utterance]) * hop], pcm=True)
+                    pcm = _host_i16(y)                                            # (device -> host: int16 at the output rate)
+                else:
+                    pcm = pcm16(o[utterance, 0, : int(frames[utterance]) * hop])  # (device -> host: the stream has drained)
             self._check_numerics()
             return pcm
         finally:
             self.release()
 
     def wav_bytes(self, batch, utterance: int = 0, noise=None) -> Optional[bytes]:
-        """The reference's response body: a mono PCM16 WAV at the model's sampling rate (inference_api.py:50, 64)."""
+        """The reference's response body: a mono PCM16 WAV (inference_api.py:50-52, 64) at the model's sampling rate or, with
+        ``output_rate``, at that rate."""
         pcm = self.synthesize(batch, utterance, noise)
         if pcm is None:
             return None
@@ -127,7 +163,7 @@ class SynthesisService:
         with wave.open(buf, "wb") as w:
             w.setnchannels(1)
             w.setsampwidth(2)
-            w.setframerate(self.sampling_rate)
+            w.setframerate(self.delivered_rate)
             w.writeframes(pcm.tobytes())
         return buf.getvalue()
 
@@ -152,6 +188,9 @@ class SynthesisService:
             dec = eng.decode(enc, tf, z_noise, self.noise_scale, max_len=0)     # everything but the vocoder
             chunks = eng.generator_stream(dec["z"], enc["g"], self.chunk_frames)
         left = int(frames[utterance]) * net.dims.total_upsample
+        if self._output_stage:
+            yield from self._stream_output_stage(chunks, utterance, left)
+            return
         while left > 0:
             # (the stream scope is entered per chunk, never held across a yield: the consumer's thread keeps its own stream)
             with self._scope():
@@ -161,6 +200,27 @@ class SynthesisService:
                 piece = pcm16(o[utterance, 0, : min(left, o.shape[2])])
             self._check_numerics()
             left -= piece.size
+            yield piece.tobytes()
+
+    def _stream_output_stage(self, chunks, utterance: int, left: int) -> Iterator[bytes]:
+        """The streamed path through the output stage: each vocoder chunk's valid samples go through
+        ``Engine.output_stream``, which returns the output samples that chunk completes; the tail follows the last one."""
+        def valid_part():
+            n = left
+            for o in chunks:
+                if n <= 0:
+                    break
+                take = min(n, o.shape[2])
+                n -= take
+                yield o[utterance:utterance + 1, 0, :take]
+        pieces = self._output_engine().output_stream(valid_part(), None, pcm=True)
+        while True:
+            with self._scope():                      # (per chunk, as above: never held across a yield)
+                y = next(pieces, None)
+                if y is None:
+                    break
+                piece = _host_i16(y)
+            self._check_numerics()
             yield piece.tobytes()
 
     # ------------------------------------------------------------------ helpers
@@ -204,8 +264,10 @@ class PooledSynthesisService:
     N locks instead of one).  The frame-rate half of one request overlaps the vocoder of another: 3.1 -> 2.1 -> 1.7 ms per
     single-utterance request at 1 / 2 / 3 slots (profiles/r06_batches_in_flight.txt)."""
 
-    def __init__(self, pool, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667):
-        self.slots = [SynthesisService(net, sampling_rate, chunk_frames, noise_scale, stream=st)
+    def __init__(self, pool, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667, *,
+                 output_rate: Optional[int] = None, device_pcm: bool = False):
+        self.slots = [SynthesisService(net, sampling_rate, chunk_frames, noise_scale, stream=st, output_rate=output_rate,
+                                       device_pcm=device_pcm)
                       for net, st in zip(pool.nets, pool.streams if pool.streams[0] is not None else [None] * len(pool.nets))]
 
     @property
