@@ -259,6 +259,11 @@ int vsp_wn_layer(vsp_ctx* ctx, void* stream, int which, int layer, int B, int T,
                  const int64_t* lengths, float* skip, int accumulate, void* workspace, int64_t workspace_bytes);
 /* Generator.forward (reference models.py:271-290). z [B][inter][T] (already masked/truncated). */
 int64_t vsp_generator_workspace_bytes(const vsp_ctx* ctx, int B, int T);
+/* Which generator this context runs (ABI 7, additive): 0 the channel-major f32 kernels -- asked for with
+ * VSP_GENERATOR=f32, or because a stage's channel count is outside the channels-last kernels' cover (32, multiples of
+ * 64, and a last stage of 16 reached from 32); 1 the split-f16 channels-last kernels; 2 the same with plain f16 operands
+ * (VSP_GENERATOR=f16).  Valid once the context exists. */
+int vsp_generator_kind(const vsp_ctx* ctx);
 int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g,
                   float* o, void* workspace, int64_t workspace_bytes);
 
@@ -364,7 +369,8 @@ int vsp_spec_to_mel(void* stream, int B, int T, int n_fft, int n_mels, int sampl
  *
  * vsp_cl_conv1d: out = conv1d(lrelu(x, in_slope), w, dilation, padding = dilation (K - 1) / 2) + bias
  * [+ res]; in_slope = 1 applies no activation (reference modules.py:214-221: F.leaky_relu + Conv1d).
- * Cin % 32 == 0, Cout % 32 == 0, K odd, (K - 1) * dilation <= 64. */
+ * Cin % 32 == 0, Cout % 32 == 0, K odd, (K - 1) * dilation <= 64.  Also Cin == Cout == 16 (additive: the last stage
+ * of a five-stage generator, g16_c16; x != out there); 16 mixed with another count is VSP_ERR_UNSUPPORTED. */
 int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x,
                   const float* w_host, const float* bias_host, float in_slope, const float* res, int terms,
                   float* out);
@@ -387,7 +393,9 @@ int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilatio
  * w_host[2 p], w_host[2 p + 1] = conv1_p, conv2_p dense [C][C][K]; bias_host likewise [C].
  * mode 0: one launch per convolution (g16_conv), any C % 32 == 0;
  * mode 1: one launch per pair (g16_pair), C = 32 or 64;  mode 2: ONE launch (g16_chain), C = 32 or 64,
- * n_pairs <= 3.  The three modes return identical bits.  x != out. */
+ * n_pairs <= 3.  The three modes return identical bits.  x != out.
+ * C = 16 (additive: g16_c16): mode 0 one launch per convolution, mode 1 a pair's two
+ * convolutions per launch, mode 2 the whole block (n_pairs <= 3) -- one kernel, identical bits. */
 int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const int* dilations, const float* x,
                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
 /* vsp_cl_resblock2 (round 7, ABI 7, additive): ResBlock2.forward without the mask (reference modules.py:245-249):
@@ -395,7 +403,7 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
  * w_host[c] dense [C][C][K], bias_host[c] [C]; x, out [B][T][C] channels-last, x != out.
  * mode 0: one launch per convolution (g16_conv, in_act + res), any C % 32 == 0;  mode 1: ONE launch (g16_rb2),
  * C = 32 or 64, (K - 1) / 2 * dilations[c] <= 32.  The two modes return identical bits.  Outside the kernels' cover:
- * VSP_ERR_UNSUPPORTED. */
+ * VSP_ERR_UNSUPPORTED.  C = 16 (additive): both modes on g16_c16. */
 int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
                      const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
 /* vsp_cl_conv_transpose1d (ABI 7, additive): HiFi-GAN's up-convolution as the channels-last generator runs it
@@ -502,6 +510,8 @@ int vsp_profile_read_class(vsp_ctx* ctx, int cls, int64_t* launches, double* tot
  *   VSP_FAM_PAIR   one launch per ResBlock conv pair (g16_pp at 128 channels, g16_pair at 64, g16_rw at 32)
  *   VSP_FAM_CHAIN  one launch per ResBlock (g16_rc / g16_chain)           VSP_FAM_PRE    conv_pre (+ cond)
  *   VSP_FAM_RB2    one launch per ResBlock2 block (g16_rb2; round 7)
+ * Launches of at most 16 output channels (the last stage of a five-stage generator, g16_c16) carry level 7 in place of
+ * log2(channels / 32).
  * Fills up to `max_families` slots (families that saw no launch since the last reset are skipped) and returns the
  * number filled (>= 0) or a negative error code.  Call it BEFORE the vsp_profile_read_class(..., reset = 1) of the
  * same class; it never resets. */

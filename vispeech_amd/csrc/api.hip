@@ -72,6 +72,7 @@ struct Run {
   }
 
   static int fam(int kind, int channels) {
+    if (channels <= 16) return kind | (7 << 3);   // (the 16-channel last stage of a five-stage generator: level 7)
     int l = 0;
     while ((32 << l) < channels && l < 7) ++l;
     return kind | (l << 3);
@@ -129,14 +130,51 @@ struct Run {
     ctx->prof_bytes_ext[cls] += bytes_ext * f;
     ctx->prof_bytes_moved[cls] += bytes_moved * f;
   }
+  // the 16-channel last stage (g16_c16, gen16_c16.hip): pairs [p0, p0 + np) of a ResBlock1, or a whole ResBlock2, as one
+  // launch of 2 np (2) convolution steps; charged to the family of the wrapper that routes here
+  void clc16(const ResBlockW& rb, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B, int p0, int np,
+             int family) {
+    ClC16Args a;
+    std::memset(&a, 0, sizeof a);
+    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
+    if (rb.kind == 2) {
+      for (int c = 0; c < 2; ++c) {
+        a.w[c] = reinterpret_cast<const uint16_t*>(A(rb.h1[c].wg)); a.b[c] = A((size_t)rb.h1[c].b);
+        a.dil[c] = rb.dil[c]; a.add[c] = 1;
+      }
+      a.nsteps = 2;
+    } else {
+      for (int p = 0; p < np; ++p) {
+        a.w[2 * p] = reinterpret_cast<const uint16_t*>(A(rb.h1[p0 + p].wg)); a.b[2 * p] = A((size_t)rb.h1[p0 + p].b);
+        a.w[2 * p + 1] = reinterpret_cast<const uint16_t*>(A(rb.h2[p0 + p].wg)); a.b[2 * p + 1] = A((size_t)rb.h2[p0 + p].b);
+        a.dil[2 * p] = rb.dil[p0 + p]; a.dil[2 * p + 1] = 1; a.add[2 * p + 1] = 1;
+      }
+      a.nsteps = 2 * np;
+    }
+    a.K = rb.k; a.T = T;
+    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
+    a.acc_prev = acc_prev ? 1 : 0; a.div = div;
+    a.terms = ctx->gen_mode == 2 ? 1 : 3;
+    a.glen = glen; a.grate = grate_out;
+    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(family, 16));
+    chk(launch_g16_c16(a, B, s), "g16_c16");
+    if (prof) {
+      // the convolutions this launch replaces, each charged its input and its output; residual reads (one per
+      // pair, one per ResBlock2 convolution) and the accumulate read -> bytes_ext
+      const double el = (double)T * 16, n = a.nsteps, nres = rb.kind == 2 ? 2.0 : np;
+      prof_end(VSP_PROF_GENERATOR, n * 2.0 * 16 * 16 * rb.k * (double)T * B, 4.0 * B * el * 2.0 * n,
+               4.0 * B * el * (2.0 * n + nres + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
+    }
+  }
   // fused ResBlock1 chain (g16_chain, gen16.hip): all dilation pairs of one ResBlock in one launch
   // (pairs [p0, p0 + np) of the ResBlock: the whole block by default)
   void clchain(const ResBlockW& rb, int ch, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B,
                int p0 = 0, int np = -1) {
     if (dry() || !ok()) return;
+    if (np < 0) np = (int)rb.dil.size();
+    if (ch == 16) return clc16(rb, x, out, bs, T, acc_prev, div, B, p0, np, VSP_FAM_CHAIN);
     ClChainArgs a;
     std::memset(&a, 0, sizeof a);
-    if (np < 0) np = (int)rb.dil.size();
     a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
     for (int p = 0; p < np; ++p) {
       a.w[2 * p] = reinterpret_cast<const uint16_t*>(A(rb.h1[p0 + p].wg));
@@ -235,6 +273,7 @@ struct Run {
   // fused ResBlock2 (g16_rb2, gen16_rb2.hip): y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y)) [+ out] [/ div]
   void clrb2(const ResBlockW& rb, int ch, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B) {
     if (dry() || !ok()) return;
+    if (ch == 16) return clc16(rb, x, out, bs, T, acc_prev, div, B, 0, 2, VSP_FAM_RB2);
     ClRb2Args a;
     std::memset(&a, 0, sizeof a);
     a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
@@ -720,7 +759,8 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
           // ResBlock2 (reference modules.py:245-249): one fused launch on the 32/64-channel stages (g16_rb2), else one
           // g16_conv per convolution with in_act + res, the running x ping-ponging xu -> ya -> xs; the last launch of the
           // stage's last block divides by nk (the reference's order of the sum).  VSP_RB2_FUSE=0: per convolution everywhere.
-          if (r.ctx->rb2_fuse && nd == 2 && g16_rb2_supported(ch, rb.k, rb.dil.data())) {
+          if (r.ctx->rb2_fuse && nd == 2 &&
+              (ch == 16 ? g16_c16_rb2_supported(rb.k, rb.dil.data()) : g16_rb2_supported(ch, rb.k, rb.dil.data()))) {
             before_last();
             r.clrb2(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
             after_last();
@@ -734,6 +774,15 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
             r.clconv(rb.h1[d], yin, bs, yout, bs, yin, bs, (int)Tout, (int)Tout, (int)Tout, 0.1f, last && j > 0,
                      (last && j == nk - 1) ? (float)nk : 1.f, nb);
           }
+          after_last();
+          continue;
+        }
+        // the 16-channel last stage (gen16_c16.hip): the whole ResBlock as one launch for every kernel size -- its cost is
+        // traffic, not arithmetic; VSP_CHAIN=0 / VSP_FUSE_PAIRS=0, or a halo the block cannot hold: one launch per
+        // convolution below (launch_g16_conv routes 16 -> 16 to the same kernel: bit-identical)
+        if (ch == 16 && r.ctx->fuse_pairs && r.ctx->chain_mask && g16_c16_rb1_supported(rb.k, rb.dil.data(), nd)) {
+          before_last();
+          r.clchain(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
           after_last();
           continue;
         }
@@ -1804,6 +1853,11 @@ int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, cons
 // Receptive field of the generator in input frames (one side), from the configuration: walking back from conv_post,
 // every stage adds the largest ResBlock support (resblock_support) in positions at its rate, every transposed conv maps
 // w positions to ceil((w + (k + s) / 2 - 1) / s), conv_pre adds 3.  (14 for configs/config.json; measured 12.33.)
+int vsp_generator_kind(const vsp_ctx* ctx) {
+  if (!ctx) return VSP_ERR_ARG;
+  return ctx->model.has_cl ? ctx->gen_mode : 0;
+}
+
 int vsp_generator_halo_frames(const vsp_ctx* ctx) {
   if (!ctx) return VSP_ERR_ARG;
   const vsp_config& c = ctx->cfg;
@@ -1946,8 +2000,10 @@ struct DevBuf {           // hipMalloc'd scratch of one stand-alone call
 // dense [phases * Cout][Cin][K] host weights -> packed fragment image on the device; bias [Cout] -> device
 hipError_t upload_cl_conv(const float* w_host, const float* bias_host, int Cout, int Cin, int K, DevBuf& w, DevBuf& bias,
                           hipStream_t s, int phases = 1) {
-  std::vector<uint16_t> packed(packed_g16_halfs(phases * Cout, Cin, K));
-  pack_g16_weights(packed.data(), phases * Cout, Cin, K, w_host);
+  const bool c16 = cl_is_c16(Cout, Cin, phases);         // (gen16_c16.hip's image)
+  std::vector<uint16_t> packed(c16 ? packed_g16c16_halfs(K) : packed_g16_halfs(phases * Cout, Cin, K));
+  if (c16) pack_g16c16_weights(packed.data(), K, w_host);
+  else pack_g16_weights(packed.data(), phases * Cout, Cin, K, w_host);
   hipError_t e = w.alloc(packed.size() * 2);
   if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
   if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, s);
@@ -1982,9 +2038,11 @@ bool ups_shape_ok(int K, int stride) { return stride >= 1 && K >= stride && K % 
 int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
                   const float* bias_host, float in_slope, const float* res, int terms, float* out) {
   if (!x || !w_host || !out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
-  if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 32 || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation > 64 ||
+  const bool c16 = Cin == 16 && Cout == 16;              // (g16_c16; mixed 16 / 32 has no kernel)
+  if (Cin <= 0 || Cout <= 0 || (!c16 && (Cin % 32 || Cout % 32)) || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation > 64 ||
       (size_t)T * std::max(Cin, Cout) * 4 >= (size_t)1 << 31)
     return VSP_ERR_UNSUPPORTED;
+  if (c16 && x == out) return VSP_ERR_ARG;
   if (B == 0 || T == 0) return VSP_OK;
   hipStream_t s = (hipStream_t)stream;
   DevBuf w, bias;
@@ -2063,13 +2121,17 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
   if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || n_pairs < 1 || n_pairs > 8 ||
       mode < 0 || mode > 2 || (terms != 1 && terms != 3))
     return VSP_ERR_ARG;
-  if (C <= 0 || C % 32 || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  const bool c16 = C == 16;                              // (g16_c16: mode 1 = a pair's two steps, mode 2 = the whole block)
+  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
   for (int p = 0; p < n_pairs; ++p) {
     if (dilations[p] < 1 || (K - 1) * dilations[p] > 64) return VSP_ERR_UNSUPPORTED;
-    if (mode == 1 && !g16_pair_supported(C, K, dilations[p]) && !g16_pp_supported(C, K, dilations[p], terms)) return VSP_ERR_UNSUPPORTED;
+    if (mode == 1 && (c16 ? !g16_c16_rb1_supported(K, dilations + p, 1)
+                          : !g16_pair_supported(C, K, dilations[p]) && !g16_pp_supported(C, K, dilations[p], terms)))
+      return VSP_ERR_UNSUPPORTED;
     if (!w_host[2 * p] || !w_host[2 * p + 1]) return VSP_ERR_ARG;
   }
-  if (mode == 2 && (n_pairs > 3 || !g16_chain_supported(C, K, dilations, n_pairs))) return VSP_ERR_UNSUPPORTED;
+  if (mode == 2 && (n_pairs > 3 || (c16 ? !g16_c16_rb1_supported(K, dilations, n_pairs) : !g16_chain_supported(C, K, dilations, n_pairs))))
+    return VSP_ERR_UNSUPPORTED;
   if (B == 0 || T == 0) return VSP_OK;
   hipStream_t s = (hipStream_t)stream;
   std::vector<DevBuf> w(2 * n_pairs), bias(2 * n_pairs);
@@ -2081,12 +2143,26 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
   if (e == hipSuccess && mode != 2) e = ya.alloc(el * 4);
   if (e == hipSuccess && mode != 2) e = yb.alloc(el * 4);
   DevBuf timg;
-  if (e == hipSuccess && mode == 0 && terms == 3 && K >= 3) {
+  if (e == hipSuccess && mode == 0 && terms == 3 && K >= 3 && !c16) {
     e = timg.alloc((size_t)B * cl_img_halfs(C, T) * 2);
     if (e == hipSuccess) e = launch_cl_img_zero_pads(static_cast<uint16_t*>(timg.p), B, C, T, s);
   }
   if (e != hipSuccess) return op_rc(e);
-  if (mode == 2) {
+  // 16 channels: pairs [p0, p0 + np) as one g16_c16 launch
+  auto c16_pairs = [&](const float* xin, float* yout, int p0, int np) {
+    ClC16Args a;
+    std::memset(&a, 0, sizeof a);
+    a.x = xin; a.x_bs = (long)T * C; a.out = yout; a.o_bs = (long)T * C;
+    for (int i = 0; i < 2 * np; ++i) {
+      a.w[i] = static_cast<const uint16_t*>(w[2 * p0 + i].p); a.b[i] = static_cast<const float*>(bias[2 * p0 + i].p);
+      a.dil[i] = (i & 1) ? 1 : dilations[p0 + i / 2]; a.add[i] = i & 1;
+    }
+    a.nsteps = 2 * np; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
+    return launch_g16_c16(a, B, s);
+  };
+  if (mode == 2 && c16) {
+    e = c16_pairs(x, out, 0, n_pairs);
+  } else if (mode == 2) {
     ClChainArgs a;
     std::memset(&a, 0, sizeof a);
     a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
@@ -2100,7 +2176,9 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
     const float* yin = x;
     for (int p = 0; p < n_pairs && e == hipSuccess; ++p) {
       float* yout = p == n_pairs - 1 ? out : static_cast<float*>((p & 1) ? yb.p : ya.p);
-      if (mode == 1) {
+      if (mode == 1 && c16) {
+        e = c16_pairs(yin, yout, p, 1);
+      } else if (mode == 1) {
         ClPairArgs a;
         std::memset(&a, 0, sizeof a);
         a.x = yin; a.x_bs = (long)T * C; a.out = yout; a.o_bs = (long)T * C;
@@ -2137,10 +2215,11 @@ int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilati
   if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || mode < 0 || mode > 1 ||
       (terms != 1 && terms != 3) || !w_host[0] || !w_host[1])
     return VSP_ERR_ARG;
-  if (C <= 0 || C % 32 || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  const bool c16 = C == 16;                              // (g16_c16: two steps with a residual each)
+  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
   for (int c = 0; c < 2; ++c)
     if (dilations[c] < 1 || (K - 1) * dilations[c] > 64) return VSP_ERR_UNSUPPORTED;
-  if (mode == 1 && !g16_rb2_supported(C, K, dilations)) return VSP_ERR_UNSUPPORTED;
+  if (mode == 1 && (c16 ? !g16_c16_rb2_supported(K, dilations) : !g16_rb2_supported(C, K, dilations))) return VSP_ERR_UNSUPPORTED;
   if (B == 0 || T == 0) return VSP_OK;
   hipStream_t s = (hipStream_t)stream;
   DevBuf w[2], bias[2];
@@ -2149,7 +2228,17 @@ int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilati
   DevBuf y;
   if (e == hipSuccess && mode == 0) e = y.alloc((size_t)B * T * C * 4);
   if (e != hipSuccess) return op_rc(e);
-  if (mode == 1) {
+  if (mode == 1 && c16) {
+    ClC16Args a;
+    std::memset(&a, 0, sizeof a);
+    a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
+    for (int c = 0; c < 2; ++c) {
+      a.w[c] = static_cast<const uint16_t*>(w[c].p); a.b[c] = static_cast<const float*>(bias[c].p); a.dil[c] = dilations[c];
+      a.add[c] = 1;
+    }
+    a.nsteps = 2; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
+    e = launch_g16_c16(a, B, s);
+  } else if (mode == 1) {
     ClRb2Args a;
     std::memset(&a, 0, sizeof a);
     a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;

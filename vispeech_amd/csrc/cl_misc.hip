@@ -95,9 +95,11 @@ __global__ void __launch_bounds__(256) conv_post_cl_kernel(const float* __restri
 hipError_t launch_conv_post_cl(const float* x, long x_bs, int x_ts, const float* w, int C, int K, float slope,
                                float* o, long o_bs, int B, int T, hipStream_t s, const int* glen, int grate, float unscale,
                                unsigned* flags) {
-  if (K > 8 || x_ts != C || (C != 32 && C != 64)) return hipErrorInvalidValue;
+  if (K > 8 || x_ts != C || (C != 16 && C != 32 && C != 64)) return hipErrorInvalidValue;
   dim3 grid((T + CPL_TILE - 1) / CPL_TILE, B);
-  if (C == 32)
+  if (C == 16)      // (the last stage of a five-stage generator)
+    hipLaunchKernelGGL(conv_post_cl_kernel<16>, grid, dim3(256), 0, s, x, x_bs, w, K, slope, o, o_bs, T, glen, grate, unscale, flags);
+  else if (C == 32)
     hipLaunchKernelGGL(conv_post_cl_kernel<32>, grid, dim3(256), 0, s, x, x_bs, w, K, slope, o, o_bs, T, glen, grate, unscale, flags);
   else
     hipLaunchKernelGGL(conv_post_cl_kernel<64>, grid, dim3(256), 0, s, x, x_bs, w, K, slope, o, o_bs, T, glen, grate, unscale, flags);

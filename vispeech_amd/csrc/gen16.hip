@@ -715,6 +715,22 @@ static hipError_t launch_g16_ups(const ClConvArgs& a, int B, hipStream_t s) {
 }
 
 hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s) {
+  // 16 -> 16 channels (the last stage of a five-stage generator): one step of g16_c16 (gen16_c16.hip), whose weight
+  // image is pack_g16c16_weights'.  fp32 tensors only, "same" padding, one extent for input and output.
+  if (cl_is_c16(a.Cout, a.Cin, a.phases)) {
+    if (a.x_img || a.o_img || !a.x || !a.out || a.x_ts != 16 || a.o_ts != 16 || (a.res && a.r_ts != 16) || a.K < 1 || !(a.K & 1) ||
+        a.pad != a.dil * (a.K - 1) / 2 || a.T_in != a.Nq || a.T_store != a.Nq || (a.glen && a.g_in != a.g_store) || a.ups_p)
+      return hipErrorInvalidValue;
+    ClC16Args c;
+    std::memset(&c, 0, sizeof c);
+    c.x = a.x; c.x_bs = a.x_bs; c.res = a.res; c.r_bs = a.r_bs; c.out = a.out; c.o_bs = a.o_bs;
+    c.w[0] = a.wh; c.b[0] = a.bias; c.dil[0] = a.dil; c.add[0] = a.res ? 1 : 0;
+    c.nsteps = 1; c.K = a.K; c.T = a.Nq;
+    c.slope = a.in_act ? a.in_slope : 1.f;                // (leaky-relu with slope 1 is the identity)
+    c.acc_prev = a.acc_prev; c.div = a.div; c.terms = a.terms;
+    c.glen = a.glen; c.grate = a.g_store;
+    return launch_g16_c16(c, B, s);
+  }
   if ((a.K - 1) * a.dil > G16_HALO || a.K < 1 || a.Nq <= 0 || B <= 0 || a.Cout % 16 || a.Cin % 32 || a.phases < 1 ||
       (a.x_ts & 3) || (a.x_bs & 3) || (reinterpret_cast<uintptr_t>(a.x) & 15) || (a.o_ts & 3) || (a.o_bs & 3) ||
       (reinterpret_cast<uintptr_t>(a.out) & 15) || (!a.out && !a.o_img) || (!a.x && !a.x_img))

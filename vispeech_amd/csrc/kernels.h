@@ -220,6 +220,36 @@ struct ClRb2Args {
 bool g16_rb2_supported(int C, int K, const int* dil);
 hipError_t launch_g16_rb2(const ClRb2Args& a, int B, hipStream_t s);
 hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s);
+// The 16-channel last stage of a five-stage generator (gen16_c16.hip): a SEQUENCE of 1 .. 6 convolutions 16 -> 16 of one
+// channels-last tensor in one launch.  Step i convolves the leaky-relu of its input with w[i] at dilation dil[i]; its result
+// (+ the running tensor when add[i], which it then replaces) is the next step's input.  The running tensor starts as res
+// (NULL: x).  The last step's result [+ out] [/ div] is stored.  x != out.
+//   ResBlock1:  steps [conv(d_p), conv(1) + add] per pair;  ResBlock2:  [conv(d) + add] x 2;  one convolution:  one step.
+struct ClC16Args {
+  const float* x; long x_bs;
+  const float* res; long r_bs;
+  float* out; long o_bs;
+  const uint16_t* w[6]; const float* b[6];  // pack_g16c16_weights images, biases (* G16_WSCALE)
+  int dil[6]; int add[6];
+  int nsteps, K, T;
+  float slope;
+  int acc_prev; float div;
+  int terms;
+  int tiles, halo;                          // set by the launcher: tiles per utterance, columns recomputed per side
+  const int* glen; int grate;               // ragged batch (see ClConvArgs): utterance b's T = glen[b] * grate; NULL = uniform
+};
+constexpr int G16_C16_BT = 512;             // columns per block; a launch stores G16_C16_BT - 2 * sum_i (K - 1) dil[i] / 2 of them
+bool g16_c16_supported(int K, const int* dil, int nsteps);
+hipError_t launch_g16_c16(const ClC16Args& a, int B, hipStream_t s);
+// the step lists of a ResBlock1 (pairs [p0, p0 + np): dilations dil[p], then 1) and of a ResBlock2 (two dilations)
+bool g16_c16_rb1_supported(int K, const int* dil, int np);
+bool g16_c16_rb2_supported(int K, const int* dil);
+// 16 -> 16 weights [16][16][K] in 16x16x32 A-fragment order, one K-step = TWO TAPS x 16 channels: [step][hi | lo][lane][8 halfs],
+// lane l: output channel l & 15, tap 2 step + (l >> 5), input channels 8 ((l >> 4) & 1) .. + 7; an odd K's last step has a
+// zero second tap.  * G16_WSCALE like pack_g16_weights.
+size_t packed_g16c16_halfs(int K);
+void pack_g16c16_weights(uint16_t* dst, int K, const float* dense /* [16][16][K] */);
+inline bool cl_is_c16(int Cout, int Cin, int phases) { return Cout == 16 && Cin == 16 && phases == 1; }
 // image-input convolutions on the 128-row tile as persistent blocks pipelined across tiles (gen16_pipe.hip):
 // launch_g16_conv routes tiles of at most 28 steps there (VSP_G16_PIPE=0: never, =1: always -- bit-identical)
 bool g16_pipe_supported(const ClConvArgs& a);

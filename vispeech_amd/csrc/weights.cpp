@@ -194,7 +194,8 @@ struct Planner {
   ClConv clconv(int Cout, int Cin, int K, int dil, int pad, int phases, int ups_p) {
     ClConv c;
     c.Cout = Cout; c.Cin = Cin; c.K = K; c.dil = dil; c.pad = pad; c.phases = phases; c.ups_p = ups_p;
-    c.wg = raw(packed_g16_halfs(phases * Cout, Cin, K) / 2);
+    // (16 -> 16, the last stage of a five-stage generator: the two-taps-per-step image of gen16_c16.hip)
+    c.wg = raw((cl_is_c16(Cout, Cin, phases) ? packed_g16c16_halfs(K) : packed_g16_halfs(phases * Cout, Cin, K)) / 2);
     c.b = (long)raw((size_t)Cout);
     return c;
   }
@@ -310,10 +311,16 @@ int plan_model(vsp_ctx* ctx) {
   // when the split-f16 channels-last kernels do not cover the configuration, BEFORE conv_pre / cond are planned.
   const int c0 = c.upsample_initial_channel;
   int ch = c0;
-  // the split-f16 channels-last generator covers channel counts of 32 or multiples of 64
+  // the split-f16 channels-last generator covers channel counts of 32 or multiples of 64, and a LAST stage of 16 channels
+  // (gen16_c16.hip: a five-stage generator, 512 initial channels) reached from 32 by an up-convolution whose stacked phases
+  // fill whole 32-row tiles (g16_conv: stride * 16 a multiple of 32).  Anything else -- 24 / 48 / 96 / 192 channels, 16
+  // channels anywhere but last -- runs the channel-major f32 generator (vsp_generator_kind reports which).
   m.has_cl = true;
   for (int i = 0; i < c.n_upsamples; ++i) {
     const int cin = c0 >> i, cout = c0 >> (i + 1);
+    const bool last16 = i == c.n_upsamples - 1 && cin == 32 && cout == 16 && c.upsample_rates[i] > 0 &&
+                        (c.upsample_rates[i] * 16) % 32 == 0;
+    if (last16) continue;
     if (cin % 32 || cout % 32 || (cin != 32 && cin % 64) || (cout != 32 && cout % 64)) m.has_cl = false;
   }
   // conv_post: both of its kernels (launch_conv_post of the f32 generator, launch_conv_post_cl) cover <= 64 channels, so
@@ -449,7 +456,8 @@ struct Filler {
           for (int t = 0; t < c.K; ++t) dense[(((size_t)ph * c.Cout + co) * c.Cin + ci) * c.K + t] = w(ph, co, ci, t);
     if (ctx->gen_mode != 0) check_f16_range(dense);       // (VSP_GENERATOR=f32 never multiplies this image)
     // [phase][co][ci][tap] is [row = phase * Cout + co][ci][tap]: the stacked-phase form gen16.hip multiplies
-    pack_g16_weights(reinterpret_cast<uint16_t*>(arena.data() + c.wg), c.phases * c.Cout, c.Cin, c.K, dense.data());
+    if (cl_is_c16(c.Cout, c.Cin, c.phases)) pack_g16c16_weights(reinterpret_cast<uint16_t*>(arena.data() + c.wg), c.K, dense.data());
+    else pack_g16_weights(reinterpret_cast<uint16_t*>(arena.data() + c.wg), c.phases * c.Cout, c.Cin, c.K, dense.data());
     // (kernels.h: the bias rides in the scaled accumulator; model.h: ... of activations that are carried * act_scale)
     for (int co = 0; co < c.Cout; ++co) arena[c.b + co] = b(co) * G16_WSCALE * ctx->act_scale;
   }

@@ -475,6 +475,12 @@ class Engine:
         return o
 
     @property
+    def generator_kind(self) -> int:
+        """Which generator the context runs (``vsp_generator_kind``): 0 the channel-major f32 kernels (``VSP_GENERATOR=f32``
+        or a configuration the channels-last kernels do not cover), 1 split-f16 channels-last, 2 the opt-in plain f16."""
+        return int(self.lib.vsp_generator_kind(self.ctx))
+
+    @property
     def generator_halo(self) -> int:
         """Frames of context the streamed vocoder adds on each side (``vsp_generator_halo_frames``)."""
         return int(self.lib.vsp_generator_halo_frames(self.ctx))
@@ -598,7 +604,7 @@ class Engine:
         ms, fl, by, bm = (C.c_double * m)(), (C.c_double * m)(), (C.c_double * m)(), (C.c_double * m)()
         k = self.lib.vsp_profile_read_families(self.ctx, int(cls), m, fam, n, ms, fl, by, bm)
         _lib.check(min(k, 0), self.ctx, "vsp_profile_read_families")
-        out = [dict(kind=self._FAMILY_KINDS.get(fam[i] & 7, "other"), channels=32 << (fam[i] >> 3), launches=int(n[i]),
+        out = [dict(kind=self._FAMILY_KINDS.get(fam[i] & 7, "other"), channels=16 if (fam[i] >> 3) == 7 else 32 << (fam[i] >> 3), launches=int(n[i]),
                     ms=float(ms[i]), flops=float(fl[i]), bytes=float(by[i]), moved=float(bm[i])) for i in range(k)]
         return sorted(out, key=lambda d: -d["ms"])
 
