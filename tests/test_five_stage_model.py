@@ -193,6 +193,26 @@ def test_per_convolution_forms_are_bit_identical(net, net2, ctor1, ctor2, w1, w2
     assert m2._engine.status() == 0
 
 
+def test_generator_schedule(net, ctor1, w1):
+    """the four wide stages as in configs/config.json, each ResBlock of the 16-channel stage one
+    g16_c16 launch charged to the chain family; VSP_CHAIN=0: pairs on the 32-channel stage, one launch per convolution on
+    the 16-channel one (3 blocks x 3 pairs x 2 convolutions)."""
+    common = {("pre", 512): 1, ("ups", 256): 1, ("ups", 128): 1, ("ups", 64): 1, ("ups", 32): 1, ("ups", 16): 1,
+              ("conv", 256): 18, ("conv", 128): 6, ("pair", 128): 6, ("pair", 64): 9}
+    gen = torch.Generator().manual_seed(3)
+    z = torch.randn(2, net.dims.inter_channels, 37, generator=gen)
+    gv = torch.randn(2, net.dims.gin_channels, generator=gen)
+    for m, launches in ((net, {("pair", 32): 6, ("chain", 32): 1, ("chain", 16): 3}),
+                        (make_net(ctor1, w1, VSP_CHAIN="0"), {("pair", 32): 9, ("conv", 16): 18})):
+        e = m._engine
+        e.profile(True)
+        e.generator(z, gv)
+        fam = e.profile_read_families()
+        e.profile_read(reset=True)
+        e.profile(False)
+        assert {(f["kind"], f["channels"]): f["launches"] for f in fam} == {**common, **launches}
+
+
 @pytest.mark.parametrize("kind", ["1", "2"])
 @pytest.mark.parametrize("chunk", [5, 64])
 def test_streamed_vocoder_is_bit_identical(kind, chunk, net, net2):

@@ -489,6 +489,53 @@ def test_fused_resblock_paths_are_bit_identical(net, dims, weights, monkeypatch,
         assert torch.equal(a, b), (B, T, float((a - b).abs().max()))
 
 
+def generator_schedule(m, z, g):
+    """One profiled generator call: ({(kind, channels): launches}, sum of flops, sum of bytes) over the kernel families."""
+    e = m._engine
+    e.profile(True)
+    e.generator(z, g)
+    fam = e.profile_read_families()
+    e.profile_read(reset=True)
+    e.profile(False)
+    return ({(f["kind"], f["channels"]): f["launches"] for f in fam}, sum(f["flops"] for f in fam),
+            sum(f["bytes"] for f in fam))
+
+
+# configs/config.json: conv_pre and the four up-convolutions are common to every schedule
+COMMON_LAUNCHES = {("pre", 512): 1, ("ups", 256): 1, ("ups", 128): 1, ("ups", 64): 1, ("ups", 32): 1}
+DEFAULT_SCHEDULE = {("conv", 256): 18, ("conv", 128): 6, ("pair", 128): 6, ("pair", 64): 9, ("pair", 32): 6, ("chain", 32): 1}
+
+
+@pytest.mark.parametrize("env, launches, total", [
+    ({}, DEFAULT_SCHEDULE, 51),
+    ({"VSP_FUSE_PAIRS": "0"}, {("conv", 256): 18, ("conv", 128): 18, ("conv", 64): 18, ("conv", 32): 18}, 77),
+    ({"VSP_CHAIN": "0"}, {("conv", 256): 18, ("conv", 128): 6, ("pair", 128): 6, ("pair", 64): 9, ("pair", 32): 9}, 53),
+    ({"VSP_CHAIN": "7"}, {("conv", 256): 18, ("conv", 128): 6, ("pair", 128): 6, ("pair", 64): 9, ("chain", 32): 3}, 47),
+    ({"VSP_PP": "0"}, {("conv", 256): 18, ("conv", 128): 18, ("pair", 64): 9, ("pair", 32): 6, ("chain", 32): 1}, 57),
+], ids=["default", "two_launches", "pair_launches", "chains_for_every_kernel_size", "no_128_channel_pair_kernel"])
+def test_generator_schedule(net, dims, weights, monkeypatch, env, launches, total):
+    """Which kernel family serves which ResBlock (51 launches by default).  Every schedule computes
+    the same bits, so only the family counters of a profiled call can tell that a switch still selects its schedule and
+    that the default did not fall back to one launch per convolution.  Every schedule replaces the same 72 ResBlock
+    convolutions, 4 up-convolutions and conv_pre: the booked flops and layer-boundary bytes are the default's, exactly."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    from vispeech_amd import config as vcfg
+    from vispeech_amd.models import SynthesizerTrn
+    args, kwargs = vcfg.synthesizer_args(vcfg.default_hparams())
+    m = SynthesizerTrn(*args, **kwargs).eval()             # (the VSP_* switches are read when the context is created)
+    m.load_state_dict(weights, strict=True)
+    r = np.random.Generator(np.random.PCG64(7))
+    z = torch.from_numpy(r.standard_normal((2, dims.inter_channels, 37)).astype(np.float32))
+    g = torch.from_numpy(r.standard_normal((2, dims.gin_channels)).astype(np.float32))
+    got, flops, nbytes = generator_schedule(m, z, g)
+    print(env, got, flops, nbytes)
+    assert got == {**COMMON_LAUNCHES, **launches}
+    assert sum(got.values()) == total
+    _, flops0, nbytes0 = generator_schedule(net, z, g)
+    assert flops == flops0 and nbytes == nbytes0, (flops, flops0, nbytes, nbytes0)
+
+
 def test_alternative_kernel_paths_match_golden(dims, weights, golden_dir, monkeypatch):
     """Switchable second implementations stay correct: frame-rate convs on the f32 matrix core
     (VSP_FRAME=f32) and the two-pass f32 attention kernel (VSP_ATT=f32)."""

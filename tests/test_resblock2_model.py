@@ -129,6 +129,24 @@ def test_per_convolution_form_is_bit_identical(net, ctor, weights, g):
     assert m._engine.status() == 0
 
 
+def test_generator_schedule(net, ctor, weights, dims):
+    """one g16_rb2 launch per block on the 32 / 64-channel stages, two g16_conv launches per block
+    on the 128 / 256-channel ones and, under VSP_RB2_FUSE=0, everywhere (3 blocks per stage; conv_pre, 4 up-convolutions)."""
+    common = {("pre", 512): 1, ("ups", 256): 1, ("ups", 128): 1, ("ups", 64): 1, ("ups", 32): 1}
+    gen = torch.Generator().manual_seed(3)
+    z = torch.randn(2, dims.inter_channels, 37, generator=gen)
+    gv = torch.randn(2, dims.gin_channels, generator=gen)
+    for m, launches in ((net, {("conv", 256): 6, ("conv", 128): 6, ("rb2", 64): 3, ("rb2", 32): 3}),
+                        (make_net(ctor, weights, VSP_RB2_FUSE="0"), {("conv", c): 6 for c in (256, 128, 64, 32)})):
+        e = m._engine
+        e.profile(True)
+        e.generator(z, gv)
+        fam = e.profile_read_families()
+        e.profile_read(reset=True)
+        e.profile(False)
+        assert {(f["kind"], f["channels"]): f["launches"] for f in fam} == {**common, **launches}
+
+
 def test_trimmed_tails_are_bit_identical(net, ctor, weights, g):
     m = make_net(ctor, weights, VSP_TRIM_TAILS="0")
     back, fwd = net._engine.generator_frame_dependence()

@@ -130,71 +130,56 @@ struct Run {
     ctx->prof_bytes_ext[cls] += bytes_ext * f;
     ctx->prof_bytes_moved[cls] += bytes_moved * f;
   }
-  // the 16-channel last stage (g16_c16, gen16_c16.hip): pairs [p0, p0 + np) of a ResBlock1, or a whole ResBlock2, as one
-  // launch of 2 np (2) convolution steps; charged to the family of the wrapper that routes here
-  void clc16(const ResBlockW& rb, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B, int p0, int np,
-             int family) {
-    ClC16Args a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
-    if (rb.kind == 2) {
-      for (int c = 0; c < 2; ++c) {
-        a.w[c] = reinterpret_cast<const uint16_t*>(A(rb.h1[c].wg)); a.b[c] = A((size_t)rb.h1[c].b);
-        a.dil[c] = rb.dil[c]; a.add[c] = 1;
-      }
-      a.nsteps = 2;
-    } else {
-      for (int p = 0; p < np; ++p) {
-        a.w[2 * p] = reinterpret_cast<const uint16_t*>(A(rb.h1[p0 + p].wg)); a.b[2 * p] = A((size_t)rb.h1[p0 + p].b);
-        a.w[2 * p + 1] = reinterpret_cast<const uint16_t*>(A(rb.h2[p0 + p].wg)); a.b[2 * p + 1] = A((size_t)rb.h2[p0 + p].b);
-        a.dil[2 * p] = rb.dil[p0 + p]; a.dil[2 * p + 1] = 1; a.add[2 * p + 1] = 1;
-      }
-      a.nsteps = 2 * np;
-    }
-    a.K = rb.k; a.T = T;
-    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
-    a.acc_prev = acc_prev ? 1 : 0; a.div = div;
-    a.terms = ctx->gen_mode == 2 ? 1 : 3;
-    a.glen = glen; a.grate = grate_out;
-    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(family, 16));
-    chk(launch_g16_c16(a, B, s), "g16_c16");
-    if (prof) {
-      // the convolutions this launch replaces, each charged its input and its output; residual reads (one per
-      // pair, one per ResBlock2 convolution) and the accumulate read -> bytes_ext
-      const double el = (double)T * 16, n = a.nsteps, nres = rb.kind == 2 ? 2.0 : np;
-      prof_end(VSP_PROF_GENERATOR, n * 2.0 * 16 * 16 * rb.k * (double)T * B, 4.0 * B * el * 2.0 * n,
-               4.0 * B * el * (2.0 * n + nres + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
-    }
+  int terms() const { return ctx->gen_mode == 2 ? 1 : 3; }
+  ClW cw(const ClConv& L) const { return ClW{reinterpret_cast<const uint16_t*>(A(L.wg)), A((size_t)L.b)}; }
+  // convolution i of a ResBlock in execution order (cl_args.h): ResBlock1 conv1, conv2 of pair 0, 1, ..; ResBlock2 conv_a, conv_b
+  ClW cw(const ResBlockW& rb, int i) const { return cw(rb.kind == 2 ? rb.h1[i] : ((i & 1) ? rb.h2 : rb.h1)[i / 2]); }
+  // Books a fused launch that replaces n convolutions C -> C (kernel K) on B x T columns and reads r residuals: each
+  // convolution is charged its input and its output -> bytes; the residual reads and the accumulate read
+  // (acc_prev) -> bytes_ext; as fused the launch moves input, output and the previous sum once each -> bytes_moved.
+  // (pair: n 2, r 1; chain of np pairs: n 2 np, r np; ResBlock2: n 2, r 2)
+  void prof_end_fused(int n, int r, int C, int K, int T, int B, bool acc_prev) {
+    const double el = (double)T * C, acc = acc_prev ? 1.0 : 0.0;
+    prof_end(VSP_PROF_GENERATOR, n * 2.0 * C * C * K * (double)T * B, 4.0 * B * el * (2.0 * n), 4.0 * B * el * (2.0 * n + r + acc),
+             4.0 * B * el * (2.0 + acc));
   }
-  // fused ResBlock1 chain (g16_chain, gen16.hip): all dilation pairs of one ResBlock in one launch
-  // (pairs [p0, p0 + np) of the ResBlock: the whole block by default)
-  void clchain(const ResBlockW& rb, int ch, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B,
-               int p0 = 0, int np = -1) {
-    if (dry() || !ok()) return;
-    if (np < 0) np = (int)rb.dil.size();
-    if (ch == 16) return clc16(rb, x, out, bs, T, acc_prev, div, B, p0, np, VSP_FAM_CHAIN);
-    ClChainArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
-    for (int p = 0; p < np; ++p) {
-      a.w[2 * p] = reinterpret_cast<const uint16_t*>(A(rb.h1[p0 + p].wg));
-      a.w[2 * p + 1] = reinterpret_cast<const uint16_t*>(A(rb.h2[p0 + p].wg));
-      a.b[2 * p] = A((size_t)rb.h1[p0 + p].b); a.b[2 * p + 1] = A((size_t)rb.h2[p0 + p].b);
-      a.dil[p] = rb.dil[p0 + p];
-    }
-    a.np = np; a.C = ch; a.K = rb.k; a.T = T;
-    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
+  // the tail every fused launch shares: what the schedule alone knows, the launch, the booking
+  template <class Args>
+  void launch_fused(Args a, hipError_t (*launch)(const Args&, int, hipStream_t), const char* what, int family, int n, int r, int C,
+                    int K, bool acc_prev, float div, int B) {
     a.acc_prev = acc_prev ? 1 : 0; a.div = div;
-    a.terms = ctx->gen_mode == 2 ? 1 : 3;
-    a.ring = ctx->chain_ring ? 1 : 0;
     a.glen = glen; a.grate = grate_out;
-    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(VSP_FAM_CHAIN, ch));
-    chk(launch_g16_chain(a, B, s), "g16_chain");
-    if (prof) {
-      // the 2 np convolutions this launch replaces, each charged its input and its output
-      const double el = (double)T * ch;
-      prof_end(VSP_PROF_GENERATOR, np * 2.0 * 2.0 * ch * ch * rb.k * (double)T * B, 4.0 * B * el * 4.0 * np,
-               4.0 * B * el * (5.0 * np + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
+    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(family, C));
+    chk(launch(a, B, s), what);
+    if (prof) prof_end_fused(n, r, C, K, a.T, B, acc_prev);
+  }
+  // Pairs [p0, p0 + np) of a ResBlock1, or a whole ResBlock2, as ONE launch: out = block(x) [+ out] [/ div], x != out.
+  //   as_pair: g16_pair (gen16.hip; np = 1), which routes to g16_rw / g16_rw64 / g16_pp itself;
+  //   else 16 channels: g16_c16 (gen16_c16.hip), charged to the family of the kernel it stands in for;
+  //        ResBlock2: g16_rb2 (gen16_rb2.hip);  ResBlock1: g16_chain (gen16.hip), which routes to g16_rc itself.
+  void clfused(const ResBlockW& rb, int ch, int p0, int np, bool as_pair, const float* x, float* out, int T, bool acc_prev,
+               float div, int B) {
+    if (dry() || !ok()) return;
+    const int n = rb.kind == 2 ? 2 : 2 * np, nres = rb.kind == 2 ? 2 : np;   // convolutions replaced, residual reads
+    ClW w[6];
+    for (int i = 0; i < n; ++i) w[i] = cw(rb, 2 * p0 + i);
+    const int* dil = rb.dil.data() + p0;
+    const int family = rb.kind == 2 ? VSP_FAM_RB2 : as_pair ? VSP_FAM_PAIR : VSP_FAM_CHAIN;
+    if (as_pair) {
+      ClPairArgs a = cl_pair_args(w, ch, rb.k, dil[0], x, out, T, terms());
+      a.ring = ctx->pair_ring ? 1 : 0;
+      a.rw64 = ctx->rw64 ? 1 : 0;
+      launch_fused(a, launch_g16_pair, "g16_pair", family, n, nres, ch, rb.k, acc_prev, div, B);
+    } else if (ch == 16) {
+      launch_fused(cl_c16_args(rb.kind, w, rb.k, dil, np, x, out, T, terms()), launch_g16_c16, "g16_c16", family, n, nres, ch, rb.k,
+                   acc_prev, div, B);
+    } else if (rb.kind == 2) {
+      launch_fused(cl_rb2_args(w, ch, rb.k, dil, x, out, T, terms()), launch_g16_rb2, "g16_rb2", family, n, nres, ch, rb.k, acc_prev,
+                   div, B);
+    } else {
+      ClChainArgs a = cl_chain_args(w, ch, rb.k, dil, np, x, out, T, terms());
+      a.ring = ctx->chain_ring ? 1 : 0;
+      launch_fused(a, launch_g16_chain, "g16_chain", family, n, nres, ch, rb.k, acc_prev, div, B);
     }
   }
   void conv(const ConvArgs& a, int B, bool generator = false) {
@@ -208,93 +193,27 @@ struct Run {
       prof_end(cls, 2.0 * a.M * a.Cin * a.K * (double)a.Nq * B, 4.0 * B * (in_el + out_el), ext, ext);
     }
   }
-  // channels-last split-f16 conv: x [B][T_in][Cin] -> out rows of Cout
+  // One channels-last split-f16 convolution of the generator (g16_conv): a ResBlock convolution x [B][T][C] -> out [+ res],
+  // or an up-convolution (L.phases > 1) x [B][T][Cin] -> out [B][T phases][Cout].
   // x_img / o_img (round 4): the input read from / the result (also, or with out == NULL only) written as an OPERAND
   // IMAGE (kernels.h ClConvArgs): a ResBlock's intermediate lives in HBM as the next convolution's split, activated
   // window planes and reaches its LDS by LDS-DMA, without conversion arithmetic in the consumer.
-  void clconv(const ClConv& L, const float* x, long x_bs, float* out, long o_bs, const float* res, long r_bs, int T_in,
-              int Nq, int T_store, float in_slope, bool acc_prev, float div, int B, const uint16_t* x_img = nullptr,
-              uint16_t* o_img = nullptr) {
+  void clconv(const ClConv& L, const float* x, float* out, const float* res, int T, bool acc_prev, float div, int B,
+              const uint16_t* x_img = nullptr, uint16_t* o_img = nullptr) {
     if (dry() || !ok()) return;
-    ClConvArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.x_img = x_img; a.xi_bs = (long)cl_img_halfs(L.Cin, T_in); a.xi_tpad = cl_img_tpad(T_in);
-    a.o_img = o_img; a.oi_bs = (long)cl_img_halfs(L.Cout, T_store); a.oi_tpad = cl_img_tpad(T_store);
-    a.oi_slope = 0.1f;                                 // modules.LRELU_SLOPE: what every ResBlock convolution applies to its input
-    a.x = x; a.x_bs = x_bs; a.x_ts = L.Cin;
-    a.wh = reinterpret_cast<const uint16_t*>(A(L.wg));
-    a.bias = A((size_t)L.b);
-    a.out = out; a.o_bs = o_bs; a.o_ts = L.Cout;
-    a.res = res; a.r_bs = r_bs; a.r_ts = L.Cout;
-    a.Cin = L.Cin; a.Cout = L.Cout; a.K = L.K; a.dil = L.dil; a.pad = L.pad;
-    a.T_in = T_in; a.Nq = Nq;
-    a.in_act = 1; a.in_slope = in_slope;
+    ClConvArgs a = L.phases > 1 ? cl_ups_args(cw(L), L.Cin, L.Cout, L.K, L.phases, x, T, CL_LRELU_SLOPE, out, terms())
+                                : cl_conv_args(cw(L), L.Cin, L.Cout, L.K, L.dil, x, T, CL_LRELU_SLOPE, res, out, terms());
+    a.x_img = x_img; a.o_img = o_img;
     a.acc_prev = acc_prev ? 1 : 0; a.div = div;
-    a.phases = L.phases; a.ups_p = L.ups_p; a.T_store = T_store;
-    a.terms = ctx->gen_mode == 2 ? 1 : 3;
     a.glen = glen; a.g_in = L.phases > 1 ? grate_in : grate_out; a.g_store = grate_out;
     const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(L.phases > 1 ? VSP_FAM_UPS : VSP_FAM_CONV, L.Cout));
     chk(launch_g16_conv(a, B, s), "g16_conv");
     if (prof) {
       // input once + output once; the residual / accumulate reads go to bytes_ext
-      const double in_el = (double)T_in * L.Cin, out_el = (double)T_store * L.Cout;
+      const double in_el = (double)a.T_in * L.Cin, out_el = (double)a.T_store * L.Cout;
       const double ext = 4.0 * B * (in_el + out_el * (1.0 + (res ? 1.0 : 0.0) + (acc_prev ? 1.0 : 0.0)));
-      prof_end(VSP_PROF_GENERATOR, 2.0 * L.Cout * L.Cin * L.K * L.phases * (double)Nq * B, 4.0 * B * (in_el + out_el), ext,
+      prof_end(VSP_PROF_GENERATOR, 2.0 * L.Cout * L.Cin * L.K * L.phases * (double)a.Nq * B, 4.0 * B * (in_el + out_el), ext,
                ext + (out && o_img ? 4.0 * B * out_el : 0.0));
-    }
-  }
-  // fused ResBlock1 pair (g16_pair, gen16.hip): out = x + conv2(lrelu(conv1(lrelu(x)))) [+ out] [/ div]
-  void clpair(const ClConv& L1, const ClConv& L2, const float* x, float* out, long bs, int T, bool acc_prev, float div,
-              int B) {
-    if (dry() || !ok()) return;
-    ClPairArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
-    a.w1h = reinterpret_cast<const uint16_t*>(A(L1.wg));
-    a.w2h = reinterpret_cast<const uint16_t*>(A(L2.wg));
-    a.b1 = A((size_t)L1.b); a.b2 = A((size_t)L2.b);
-    a.C = L1.Cout; a.K = L1.K; a.dil = L1.dil; a.T = T;
-    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
-    a.acc_prev = acc_prev ? 1 : 0; a.div = div;
-    a.terms = ctx->gen_mode == 2 ? 1 : 3;
-    a.ring = ctx->pair_ring ? 1 : 0;
-    a.rw64 = ctx->rw64 ? 1 : 0;
-    a.glen = glen; a.grate = grate_out;
-    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(VSP_FAM_PAIR, L1.Cout));
-    chk(launch_g16_pair(a, B, s), "g16_pair");
-    if (prof) {
-      // the two convolutions this launch replaces: SURVEY.md 8d charges each its input and its output (4 passes of
-      // T x C); with conv2's residual read (and the accumulate read of a ResBlock's last pair): 5 (6) -> bytes_ext
-      const double el = (double)T * L1.Cout;
-      prof_end(VSP_PROF_GENERATOR, 2.0 * 2.0 * L1.Cout * L1.Cin * L1.K * (double)T * B, 4.0 * B * el * 4.0,
-               4.0 * B * el * (5.0 + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
-    }
-  }
-  // fused ResBlock2 (g16_rb2, gen16_rb2.hip): y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y)) [+ out] [/ div]
-  void clrb2(const ResBlockW& rb, int ch, const float* x, float* out, long bs, int T, bool acc_prev, float div, int B) {
-    if (dry() || !ok()) return;
-    if (ch == 16) return clc16(rb, x, out, bs, T, acc_prev, div, B, 0, 2, VSP_FAM_RB2);
-    ClRb2Args a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = bs; a.out = out; a.o_bs = bs;
-    for (int c = 0; c < 2; ++c) {
-      a.w[c] = reinterpret_cast<const uint16_t*>(A(rb.h1[c].wg));
-      a.b[c] = A((size_t)rb.h1[c].b);
-      a.dil[c] = rb.dil[c];
-    }
-    a.C = ch; a.K = rb.k; a.T = T;
-    a.slope = 0.1f;                                    // modules.LRELU_SLOPE (reference modules.py:17)
-    a.acc_prev = acc_prev ? 1 : 0; a.div = div;
-    a.terms = ctx->gen_mode == 2 ? 1 : 3;
-    a.glen = glen; a.grate = grate_out;
-    const bool prof = prof_begin(VSP_PROF_GENERATOR, fam(VSP_FAM_RB2, ch));
-    chk(launch_g16_rb2(a, B, s), "g16_rb2");
-    if (prof) {
-      // the two convolutions this launch replaces, each charged its input and its output; both residual
-      // reads (and the accumulate read of a stage's later blocks) -> bytes_ext
-      const double el = (double)T * ch;
-      prof_end(VSP_PROF_GENERATOR, 2.0 * 2.0 * ch * ch * rb.k * (double)T * B, 4.0 * B * el * 4.0,
-               4.0 * B * el * (6.0 + (acc_prev ? 1.0 : 0.0)), 4.0 * B * el * (2.0 + (acc_prev ? 1.0 : 0.0)));
     }
   }
   // cond(g): 1x1 conv on g [B][gin] (T = 1) -> out [B][M]
@@ -488,6 +407,18 @@ void run_posterior(Run& r, int B, int T, T3 y, const int64_t* lengths, const flo
   }
 }
 
+// max over the generator's stages of f(channels, columns): stage i has upsample_initial_channel >> (i + 1) channels and
+// T * upsample_rates[0] * .. * upsample_rates[i] columns per utterance
+template <class F>
+size_t max_over_stages(const vsp_config& c, int T, size_t mx, F f) {
+  long t = T;
+  for (int i = 0; i < c.n_upsamples; ++i) {
+    t *= c.upsample_rates[i];
+    mx = std::max(mx, (size_t)f(c.upsample_initial_channel >> (i + 1), t));
+  }
+  return mx;
+}
+
 // Generator.forward (reference models.py:271-290).  z [B][inter][T]; in_lengths != null applies
 // the (z * x_mask) of models.py:720 while staging conv_pre's input.
 void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const float* g, float* o) {
@@ -497,14 +428,8 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
   float* gc = r.ws.f((size_t)B * c0);
   r.cond(m.g_cond, g, gc, B);
   // buffer sizes: max over stages of C * T
-  size_t mx = (size_t)c0 * ((T + 63) / 64 * 64);
-  {
-    long t = T;
-    for (int i = 0; i < c.n_upsamples; ++i) {
-      t *= c.upsample_rates[i];
-      mx = std::max(mx, (size_t)(c0 >> (i + 1)) * (size_t)((t + 63) / 64 * 64));
-    }
-  }
+  const size_t mx = max_over_stages(c, T, (size_t)c0 * ((T + 63) / 64 * 64),
+                                    [](int ch, long t) { return (size_t)ch * (size_t)((t + 63) / 64 * 64); });
   float* buf[5];
   for (auto& b : buf) b = r.ws.f((size_t)B * mx);
   auto view = [&](int k, int C, long Tn) {
@@ -576,8 +501,6 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
           "conv_post");
 }
 
-// Generator.forward on the split-f16 channels-last kernels (gen16.hip): conv_pre stays on the
-// f32 kernel (input z is channel-major and tiny), its output is transposed once to [B][T][C].
 // The context's two side streams and n fork / join events (created on first use, on the device the caller's stream
 // belongs to; destroyed with the context).
 bool ensure_side_streams(Run& r, size_t n_events) {
@@ -599,6 +522,69 @@ bool ensure_side_streams(Run& r, size_t n_events) {
   return true;
 }
 
+// stages that run one launch per convolution (>= 128 channels) hand a ResBlock1 pair's intermediate over as an operand image
+// (VSP_TIMG=0, the plain-f16 generator and ResBlock2: fp32 tensors)
+bool cl_stage_img(const vsp_ctx& c, int ch) {
+  return c.t_img && c.gen_mode == 1 && c.resblock == 1 && ch >= 128 && ch % 32 == 0;
+}
+
+// The launches that serve one ResBlock of a channels-last stage, decided from the context's switches (model.h) and the
+// kernels' predicates before anything runs.  Every choice computes the same bits (tests/test_hip_parity.py:
+// test_fused_resblock_paths_are_bit_identical); what each one launches is pinned by test_generator_schedule.
+enum class RbLaunch {
+  Fused,          // pairs [p0, p0 + np) of a ResBlock1, or a whole ResBlock2, in one launch: g16_chain / g16_rc, g16_rb2, g16_c16
+  Pair,           // one ResBlock1 pair: g16_pair, which routes to g16_rw / g16_rw64 / g16_pp
+  TwoConvs,       // one ResBlock1 pair as two g16_conv launches, fp32 intermediate
+  TwoConvsImage,  // ... the intermediate as an operand image
+  Conv            // one ResBlock2 convolution: g16_conv with the residual
+};
+struct RbUnit {
+  RbLaunch kind;
+  int p0, np;
+};
+struct RbPlan {
+  int n = 0;
+  RbUnit u[VSP_MAX_LIST];           // (a block has at most VSP_MAX_LIST dilations: vsp_config)
+  void add(RbLaunch kind, int p0, int np) { u[n++] = RbUnit{kind, p0, np}; }
+};
+RbPlan plan_resblock(const vsp_ctx& c, const ResBlockW& rb, int ch) {
+  RbPlan p;
+  const int nd = (int)rb.dil.size(), terms = c.gen_mode == 2 ? 1 : 3;
+  const int* dil = rb.dil.data();
+  if (rb.kind == 2) {
+    // ResBlock2 (reference modules.py:245-249): one fused launch on the 16/32/64-channel stages, else one g16_conv per
+    // convolution with in_act + res.  VSP_RB2_FUSE=0: per convolution everywhere.
+    const bool fused = c.rb2_fuse && nd == 2 && (ch == 16 ? g16_c16_rb2_supported(rb.k, dil) : g16_rb2_supported(ch, rb.k, dil));
+    if (fused) p.add(RbLaunch::Fused, 0, 2);
+    for (int d = 0; d < nd && !fused; ++d) p.add(RbLaunch::Conv, d, 1);
+    return p;
+  }
+  // the 16-channel last stage (gen16_c16.hip): the whole ResBlock as one launch for every kernel size -- its cost is
+  // traffic, not arithmetic; VSP_CHAIN=0 / VSP_FUSE_PAIRS=0, or a halo the block cannot hold: one launch per
+  // convolution below (launch_g16_conv routes 16 -> 16 to the same kernel: bit-identical)
+  if (ch == 16 && c.fuse_pairs && c.chain_mask && g16_c16_rb1_supported(rb.k, dil, nd)) {
+    p.add(RbLaunch::Fused, 0, nd);
+    return p;
+  }
+  bool fuse = c.fuse_pairs;
+  for (int d = 0; d < nd; ++d)
+    fuse = fuse && (g16_pair_supported(ch, rb.k, dil[d]) || (c.pp_pairs && g16_pp_supported(ch, rb.k, dil[d], terms)));
+  const int kbit = rb.k <= 3 ? 1 : rb.k <= 7 ? 2 : 4;
+  if (fuse && (c.chain_mask & kbit) && ch <= c.chain_ch && nd <= 3 && g16_chain_supported(ch, rb.k, dil, nd)) {
+    p.add(RbLaunch::Fused, 0, nd);
+    return p;
+  }
+  for (int d = 0; d < nd; ++d) {
+    if (fuse) p.add(RbLaunch::Pair, d, 1);
+    // 128-channel pair as ONE launch (g16_chain, 128-column blocks; VSP_CHAIN128): the intermediate never reaches HBM
+    else if (ch == 128 && (c.chain128_mask & kbit) && g16_chain_supported(ch, rb.k, dil + d, 1)) p.add(RbLaunch::Fused, d, 1);
+    else p.add(cl_stage_img(c, ch) && rb.k >= 3 ? RbLaunch::TwoConvsImage : RbLaunch::TwoConvs, d, 1);
+  }
+  return p;
+}
+
+// Generator.forward on the split-f16 channels-last kernels (gen16.hip): conv_pre stays on the
+// f32 kernel (input z is channel-major and tiny), its output is transposed once to [B][T][C].
 void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const float* g, float* o) {
   const vsp_config& c = r.ctx->cfg;
   const Model& m = r.ctx->model;
@@ -606,14 +592,7 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   float* gc = r.ws.f((size_t)B * c0);
   r.cond(m.g_cond, g, gc, B);
   T3 X0 = r.ws.t3(B, c0, T);
-  size_t mx = (size_t)c0 * T;
-  {
-    long t = T;
-    for (int i = 0; i < c.n_upsamples; ++i) {
-      t *= c.upsample_rates[i];
-      mx = std::max(mx, (size_t)(c0 >> (i + 1)) * (size_t)t);
-    }
-  }
+  const size_t mx = max_over_stages(c, T, (size_t)c0 * T, [](int ch, long t) { return (size_t)ch * (size_t)t; });
   float* buf[5];
   for (auto& bptr : buf) bptr = r.ws.f((size_t)B * mx);
   // ResBlocks 1 .. nk-1 of a stage on side streams (vsp_ctx::rb_streams): their own ping-pong tensors (and operand image)
@@ -621,17 +600,10 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   if (r.ctx->rb_streams)
     for (int j = 1; j < nk; ++j)
       for (int u = 0; u < 2; ++u) side_buf.push_back(r.ws.f((size_t)B * mx));
-  // the operand image of a ResBlock intermediate on the stages that run one launch per convolution (>= 128 channels)
-  size_t mx_img = 0;
-  {
-    long t = T;
-    for (int i = 0; i < c.n_upsamples; ++i) {
-      t *= c.upsample_rates[i];
-      const int chi = c0 >> (i + 1);
-      if (chi >= 128 && chi % 32 == 0) mx_img = std::max(mx_img, cl_img_halfs(chi, (int)t) / 2);
-    }
-  }
-  const bool want_img = r.ctx->t_img && mx_img && r.ctx->gen_mode == 1 && r.ctx->resblock == 1;   // (ResBlock2: fp32 tensors)
+  // the operand image of a ResBlock intermediate on the stages that hand one over (cl_stage_img)
+  const size_t mx_img = max_over_stages(
+      c, T, 0, [&](int ch, long t) { return cl_stage_img(*r.ctx, ch) ? cl_img_halfs(ch, (int)t) / 2 : (size_t)0; });
+  const bool want_img = mx_img != 0;
   uint16_t* timg = want_img ? reinterpret_cast<uint16_t*>(r.ws.f((size_t)B * mx_img)) : nullptr;
   std::vector<uint16_t*> side_img;
   if (want_img && r.ctx->rb_streams)
@@ -717,7 +689,7 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
       }
       const float* xin = buf[cur] + (size_t)b0 * xbs;
       float *xu = XU + (size_t)b0 * bs, *xs = XS + (size_t)b0 * bs;
-      r.clconv(U, xin, xbs, xu, bs, nullptr, 0, (int)Tn, (int)Tn + 1, (int)Tout, 0.1f, false, 1.f, nb);
+      r.clconv(U, xin, xu, nullptr, (int)Tn, false, 1.f, nb);
       // The stage's ResBlocks are independent chains until their sum (reference models.py:276-285): chain 0 runs on the
       // caller's stream, chains 1 .. on the context's side streams with their own intermediates, forked after the
       // up-convolution; a chain's LAST launch accumulates into xs and therefore waits for the previous chain's last
@@ -726,8 +698,7 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
                         (int)side_buf.size() == 2 * (nk - 1) && ensure_side_streams(r, (size_t)c.n_upsamples * (nk + 1));
       hipStream_t const main_s = r.s;
       hipEvent_t* const ev = conc ? r.ctx->sync_ev.data() + (size_t)i * (nk + 1) : nullptr;   // [0] fork, [1 + j] chain j's last launch
-      // stages that run one launch per convolution hand the pair's intermediate over as an operand image
-      const bool use_img = timg && ch >= 128 && ch % 32 == 0;
+      const bool use_img = timg && cl_stage_img(*r.ctx, ch);
       auto chain_img = [&](int j) -> uint16_t* {
         if (!use_img) return nullptr;
         uint16_t* base = (conc && j != 1 && (int)side_img.size() == nk - 1) ? side_img[j == 0 ? 0 : j - 1] : timg;
@@ -739,7 +710,6 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
       if (conc) r.chk(hipEventRecord(ev[0], main_s), "fork event");
       for (int j = 0; j < nk; ++j) {
         const ResBlockW& rb = m.rbs[i * nk + j];
-        const int nd = (int)rb.dil.size();
         // chain j's stream and intermediates: chain 0 on the high-priority side stream, chain 1 on the caller's, the rest
         // on the low-priority one -- the hardware then dispatches a chain's blocks into the slots the chains before it
         // leave free (ramps, partial last rounds) instead of sharing the CUs launch by launch in lockstep, and a chain's
@@ -753,80 +723,31 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
           r.chk(hipStreamWaitEvent(r.s, ev[0], 0), "fork wait");
         }
         uint16_t* const ti = chain_img(j);
-        auto before_last = [&]() { if (conc && j > 0) r.chk(hipStreamWaitEvent(r.s, ev[j], 0), "sum order wait"); };
-        auto after_last = [&]() { if (conc) r.chk(hipEventRecord(ev[1 + j], r.s), "chain end event"); r.s = main_s; };
-        if (rb.kind == 2) {
-          // ResBlock2 (reference modules.py:245-249): one fused launch on the 32/64-channel stages (g16_rb2), else one
-          // g16_conv per convolution with in_act + res, the running x ping-ponging xu -> ya -> xs; the last launch of the
-          // stage's last block divides by nk (the reference's order of the sum).  VSP_RB2_FUSE=0: per convolution everywhere.
-          if (r.ctx->rb2_fuse && nd == 2 &&
-              (ch == 16 ? g16_c16_rb2_supported(rb.k, rb.dil.data()) : g16_rb2_supported(ch, rb.k, rb.dil.data()))) {
-            before_last();
-            r.clrb2(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
-            after_last();
-            continue;
-          }
-          for (int d = 0; d < nd; ++d) {
-            const bool last = d == nd - 1;
-            const float* yin = d == 0 ? xu : ((d & 1) ? ya : t1);
-            float* yout = last ? xs : ((d & 1) ? t1 : ya);
-            if (last) before_last();
-            r.clconv(rb.h1[d], yin, bs, yout, bs, yin, bs, (int)Tout, (int)Tout, (int)Tout, 0.1f, last && j > 0,
-                     (last && j == nk - 1) ? (float)nk : 1.f, nb);
-          }
-          after_last();
-          continue;
-        }
-        // the 16-channel last stage (gen16_c16.hip): the whole ResBlock as one launch for every kernel size -- its cost is
-        // traffic, not arithmetic; VSP_CHAIN=0 / VSP_FUSE_PAIRS=0, or a halo the block cannot hold: one launch per
-        // convolution below (launch_g16_conv routes 16 -> 16 to the same kernel: bit-identical)
-        if (ch == 16 && r.ctx->fuse_pairs && r.ctx->chain_mask && g16_c16_rb1_supported(rb.k, rb.dil.data(), nd)) {
-          before_last();
-          r.clchain(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
-          after_last();
-          continue;
-        }
-        bool fuse = r.ctx->fuse_pairs;
-        const int terms = r.ctx->gen_mode == 2 ? 1 : 3;
-        for (int d = 0; d < nd; ++d)
-          fuse = fuse && (g16_pair_supported(ch, rb.k, rb.dil[d]) || (r.ctx->pp_pairs && g16_pp_supported(ch, rb.k, rb.dil[d], terms)));
-        const int kbit = rb.k <= 3 ? 1 : rb.k <= 7 ? 2 : 4;
-        if (fuse && (r.ctx->chain_mask & kbit) && ch <= r.ctx->chain_ch && nd <= 3 &&
-            g16_chain_supported(ch, rb.k, rb.dil.data(), nd)) {
-          before_last();
-          r.clchain(rb, ch, xu, xs, bs, (int)Tout, j > 0, j == nk - 1 ? (float)nk : 1.f, nb);
-          after_last();
-          continue;
-        }
-        for (int d = 0; d < nd; ++d) {
-          const bool last = d == nd - 1;
+        // The block's launches in order (plan_resblock).  A launch reads the running tensor from `yin` and writes it to
+        // another buffer (a tile reads halo rows that a neighbour writes) -- ping-pong between ya and t1; the two-launch
+        // pair updates it in place (in ya from the first pair on), with the other of the two or the image as its intermediate.
+        // The block's last launch adds its result to the stage's sum in xs (and the stage's last block divides by nk: the
+        // reference's order of the sum).
+        const RbPlan plan = plan_resblock(*r.ctx, rb, ch);
+        const float* yin = xu;
+        for (int k = 0; k < plan.n; ++k) {
+          const RbUnit& u = plan.u[k];
+          const bool last = k == plan.n - 1, acc = last && j > 0;
+          const bool two = u.kind == RbLaunch::TwoConvs || u.kind == RbLaunch::TwoConvsImage;
           const float div = (last && j == nk - 1) ? (float)nk : 1.f;
-          if (fuse) {
-            // one launch per pair; the running y ping-pongs between ya and t1 (a block reads halo rows
-            // that a neighbour writes, so a pair cannot run in place)
-            const float* yin = d == 0 ? xu : ((d & 1) ? ya : t1);
-            float* yout = last ? xs : ((d & 1) ? t1 : ya);
-            if (last) before_last();
-            r.clpair(rb.h1[d], rb.h2[d], yin, yout, bs, (int)Tout, last && j > 0, div, nb);
-          } else if (ch == 128 && (r.ctx->chain128_mask & kbit) && g16_chain_supported(ch, rb.k, &rb.dil[d], 1)) {
-            // 128-channel pair as ONE launch (g16_chain, 128-column blocks): the intermediate never reaches HBM
-            const float* yin = d == 0 ? xu : ((d & 1) ? ya : t1);
-            float* yout = last ? xs : ((d & 1) ? t1 : ya);
-            if (last) before_last();
-            r.clchain(rb, ch, yin, yout, bs, (int)Tout, last && j > 0, div, nb, d, 1);
-          } else {
-            const float* yin = d == 0 ? xu : ya;
-            const bool img = ti != nullptr && rb.k >= 3;
-            r.clconv(rb.h1[d], yin, bs, img ? nullptr : t1, bs, nullptr, 0, (int)Tout, (int)Tout, (int)Tout, 0.1f, false, 1.f,
-                     nb, nullptr, img ? ti : nullptr);
-            if (last) before_last();
-            r.clconv(rb.h2[d], t1, bs, last ? xs : ya, bs, yin, bs, (int)Tout, (int)Tout, (int)Tout, 0.1f,
-                     last && j > 0, div, nb, img ? ti : nullptr, nullptr);
-          }
+          float* const mid = yin == t1 ? ya : t1;
+          float* const yout = last ? xs : two ? (yin == xu ? ya : const_cast<float*>(yin)) : (yin == ya ? t1 : ya);
+          uint16_t* const img = u.kind == RbLaunch::TwoConvsImage ? ti : nullptr;
+          if (two) r.clconv(rb.h1[u.p0], yin, img ? nullptr : mid, nullptr, (int)Tout, false, 1.f, nb, nullptr, img);
+          if (last && conc && j > 0) r.chk(hipStreamWaitEvent(r.s, ev[j], 0), "sum order wait");
+          if (two) r.clconv(rb.h2[u.p0], mid, yout, yin, (int)Tout, acc, div, nb, img, nullptr);
+          else if (u.kind == RbLaunch::Conv) r.clconv(rb.h1[u.p0], yin, yout, yin, (int)Tout, acc, div, nb);
+          else r.clfused(rb, ch, u.p0, u.np, u.kind == RbLaunch::Pair, yin, yout, (int)Tout, acc, div, nb);
+          yin = yout;
         }
-        after_last();
+        if (conc) r.chk(hipEventRecord(ev[1 + j], r.s), "chain end event");
+        r.s = main_s;
       }
-      r.s = main_s;
       if (conc) r.chk(hipStreamWaitEvent(main_s, ev[nk], 0), "join wait");
     }
     cur = fb[3];
@@ -1850,14 +1771,14 @@ int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, cons
   return r.rc;
 }
 
-// Receptive field of the generator in input frames (one side), from the configuration: walking back from conv_post,
-// every stage adds the largest ResBlock support (resblock_support) in positions at its rate, every transposed conv maps
-// w positions to ceil((w + (k + s) / 2 - 1) / s), conv_pre adds 3.  (14 for configs/config.json; measured 12.33.)
 int vsp_generator_kind(const vsp_ctx* ctx) {
   if (!ctx) return VSP_ERR_ARG;
   return ctx->model.has_cl ? ctx->gen_mode : 0;
 }
 
+// Receptive field of the generator in input frames (one side), from the configuration: walking back from conv_post,
+// every stage adds the largest ResBlock support (resblock_support) in positions at its rate, every transposed conv maps
+// w positions to ceil((w + (k + s) / 2 - 1) / s), conv_pre adds 3.  (14 for configs/config.json; measured 12.33.)
 int vsp_generator_halo_frames(const vsp_ctx* ctx) {
   if (!ctx) return VSP_ERR_ARG;
   const vsp_config& c = ctx->cfg;
@@ -1988,360 +1909,6 @@ int vsp_spec_to_mel(void* stream, int B, int T, int n_fft, int n_mels, int sampl
   if (dw) (void)hipFree(dw);
   if (dr) (void)hipFree(dr);
   return e == hipSuccess ? VSP_OK : VSP_ERR_HIP;
-}
-
-// -------------------------------------------------------------------------------------------- stand-alone vocoder operators
-namespace {
-struct DevBuf {           // hipMalloc'd scratch of one stand-alone call
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-// dense [phases * Cout][Cin][K] host weights -> packed fragment image on the device; bias [Cout] -> device
-hipError_t upload_cl_conv(const float* w_host, const float* bias_host, int Cout, int Cin, int K, DevBuf& w, DevBuf& bias,
-                          hipStream_t s, int phases = 1) {
-  const bool c16 = cl_is_c16(Cout, Cin, phases);         // (gen16_c16.hip's image)
-  std::vector<uint16_t> packed(c16 ? packed_g16c16_halfs(K) : packed_g16_halfs(phases * Cout, Cin, K));
-  if (c16) pack_g16c16_weights(packed.data(), K, w_host);
-  else pack_g16_weights(packed.data(), phases * Cout, Cin, K, w_host);
-  hipError_t e = w.alloc(packed.size() * 2);
-  if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, s);
-  std::vector<float> scaled(Cout, 0.f);                  // (kernels.h: these kernels take the bias * G16_WSCALE)
-  if (bias_host) for (int i = 0; i < Cout; ++i) scaled[i] = bias_host[i] * G16_WSCALE;
-  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, scaled.data(), (size_t)Cout * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);     // the host vectors die with this frame
-  return e;
-}
-ClConvArgs cl_conv_args(const float* x, int T, int Cin, int Cout, int K, int dil, const DevBuf& w, const DevBuf& bias,
-                        float in_slope, const float* res, int terms, float* out) {
-  ClConvArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x = x; a.x_bs = (long)T * Cin; a.x_ts = Cin;
-  a.wh = static_cast<const uint16_t*>(w.p); a.bias = static_cast<const float*>(bias.p);
-  a.out = out; a.o_bs = (long)T * Cout; a.o_ts = Cout;
-  a.res = res; a.r_bs = (long)T * Cout; a.r_ts = Cout;
-  a.Cin = Cin; a.Cout = Cout; a.K = K; a.dil = dil; a.pad = dil * (K - 1) / 2;
-  a.T_in = T; a.Nq = T; a.T_store = T;
-  a.in_act = 1; a.in_slope = in_slope;
-  a.acc_prev = 0; a.div = 1.f; a.phases = 1; a.ups_p = 0;
-  a.terms = terms;
-  return a;
-}
-int op_rc(hipError_t e) { return e == hipSuccess ? VSP_OK : (e == hipErrorInvalidValue ? VSP_ERR_UNSUPPORTED : VSP_ERR_HIP); }
-// HiFi-GAN's up-convolutions as the generator runs them (kernels.h ups_weight_offset): kt = K / stride taps per phase over
-// the input padded by kt - 1, Nq = T + 1 input times, output rows n = stride q + r - (K - stride) / 2 kept in [0, stride T)
-// -- the shapes plan_model accepts
-bool ups_shape_ok(int K, int stride) { return stride >= 1 && K >= stride && K % stride == 0 && (K - stride) % 2 == 0; }
-}  // namespace
-
-int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
-                  const float* bias_host, float in_slope, const float* res, int terms, float* out) {
-  if (!x || !w_host || !out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
-  const bool c16 = Cin == 16 && Cout == 16;              // (g16_c16; mixed 16 / 32 has no kernel)
-  if (Cin <= 0 || Cout <= 0 || (!c16 && (Cin % 32 || Cout % 32)) || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation > 64 ||
-      (size_t)T * std::max(Cin, Cout) * 4 >= (size_t)1 << 31)
-    return VSP_ERR_UNSUPPORTED;
-  if (c16 && x == out) return VSP_ERR_ARG;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  DevBuf w, bias;
-  hipError_t e = upload_cl_conv(w_host, bias_host, Cout, Cin, K, w, bias, s);
-  if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(x, T, Cin, Cout, K, dilation, w, bias, in_slope, res, terms, out), B, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
-}
-
-int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
-               const float* bias_host, const int64_t* lengths, int mask_in, int in_act, float in_slope, int act,
-               const float* res, int mask_out, int split_f16, float* out) {
-  if (!x || !w_host || !out || B < 0 || T < 0 || act < 0 || act > 2 || ((mask_in || mask_out) && !lengths) || (act == 2 && res))
-    return VSP_ERR_ARG;
-  if (Cin <= 0 || Cout <= 0 || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation + 3 > CONV_HALO ||
-      (act == 2 && Cout % 64) || ((T & 3) && T != 1))   // (rows of T floats must stay 16-byte aligned for the vector staging;
-                                                        //  T = 1: the one-time-step projections, conv_t1_gemv)
-    return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  // the gate reads its tanh / sigmoid halves from interleaved 32-row tiles (weights.cpp packs WN in_layers the same way)
-  std::vector<float> wd((size_t)Cout * Cin * K), bd(Cout, 0.f);
-  for (int r = 0; r < Cout; ++r) {
-    int src = r;
-    if (act == 2) { const int tile = r / 32, in = r % 32; src = (tile & 1) * (Cout / 2) + (tile >> 1) * 32 + in; }
-    std::memcpy(&wd[(size_t)r * Cin * K], w_host + (size_t)src * Cin * K, (size_t)Cin * K * sizeof(float));
-    if (bias_host) bd[r] = bias_host[src];
-  }
-  std::vector<float> packed(packed_conv_floats(Cout, Cin, K));
-  if (split_f16) pack_conv_weights_f16s(packed.data(), Cout, Cin, K, wd.data());
-  else pack_conv_weights(packed.data(), Cout, Cin, K, wd.data());
-  DevBuf w, bias;
-  hipError_t e = w.alloc(packed.size() * 4);
-  if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)Cout * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return op_rc(e);
-  const int rows_out = act == 2 ? Cout / 2 : Cout;
-  ConvArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x = x; a.x_bs = (long)Cin * T; a.x_cs = T;
-  a.wp = static_cast<const float*>(w.p); a.bias = static_cast<const float*>(bias.p);
-  a.out = out; a.o_bs = (long)rows_out * T; a.o_cs = T;
-  a.res = res; a.r_bs = (long)rows_out * T; a.r_cs = T;
-  a.lengths = lengths;
-  a.Cin = Cin; a.M = Cout; a.K = K; a.dil = dilation; a.pad = dilation * (K - 1) / 2;
-  a.T_in = T; a.Nq = T; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
-  a.in_mask = mask_in ? 1 : 0; a.in_act = in_act ? 1 : 0; a.in_slope = in_slope;
-  a.act = act; a.alpha = 1.f; a.div = 1.f; a.mask_post = mask_out ? 1 : 0;
-  a.f16s = split_f16 ? 1 : 0;
-  if (split_f16 == 2) {
-    // the column-tile form (conv_cols.hip: every output row of a 64-column tile in one block) as a stand-alone operator:
-    // the same weights in 16x16x32 A-fragment order; refused where that kernel does not apply
-    std::vector<uint16_t> wgh(packed_g16_halfs(Cout, Cin, 1));
-    DevBuf wgd;
-    if (K != 1 || Cin % 32 || Cout % 16) return VSP_ERR_UNSUPPORTED;
-    pack_g16_weights(wgh.data(), Cout, Cin, 1, wd.data());
-    e = wgd.alloc(wgh.size() * 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(wgd.p, wgh.data(), wgh.size() * 2, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    a.wg = static_cast<const uint16_t*>(wgd.p);
-    if (!conv_cols_supported(a)) return VSP_ERR_UNSUPPORTED;
-    e = launch_conv_cols(a, B, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return op_rc(e);
-  }
-  e = launch_conv(a, B, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
-}
-
-int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const int* dilations, const float* x,
-                    const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
-  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || n_pairs < 1 || n_pairs > 8 ||
-      mode < 0 || mode > 2 || (terms != 1 && terms != 3))
-    return VSP_ERR_ARG;
-  const bool c16 = C == 16;                              // (g16_c16: mode 1 = a pair's two steps, mode 2 = the whole block)
-  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
-  for (int p = 0; p < n_pairs; ++p) {
-    if (dilations[p] < 1 || (K - 1) * dilations[p] > 64) return VSP_ERR_UNSUPPORTED;
-    if (mode == 1 && (c16 ? !g16_c16_rb1_supported(K, dilations + p, 1)
-                          : !g16_pair_supported(C, K, dilations[p]) && !g16_pp_supported(C, K, dilations[p], terms)))
-      return VSP_ERR_UNSUPPORTED;
-    if (!w_host[2 * p] || !w_host[2 * p + 1]) return VSP_ERR_ARG;
-  }
-  if (mode == 2 && (n_pairs > 3 || (c16 ? !g16_c16_rb1_supported(K, dilations, n_pairs) : !g16_chain_supported(C, K, dilations, n_pairs))))
-    return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<DevBuf> w(2 * n_pairs), bias(2 * n_pairs);
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 * n_pairs && e == hipSuccess; ++i) e = upload_cl_conv(w_host[i], bias_host[i], C, C, K, w[i], bias[i], s);
-  const size_t el = (size_t)B * T * C;
-  DevBuf t1, ya, yb;
-  if (e == hipSuccess && mode != 2) e = t1.alloc(el * 4);
-  if (e == hipSuccess && mode != 2) e = ya.alloc(el * 4);
-  if (e == hipSuccess && mode != 2) e = yb.alloc(el * 4);
-  DevBuf timg;
-  if (e == hipSuccess && mode == 0 && terms == 3 && K >= 3 && !c16) {
-    e = timg.alloc((size_t)B * cl_img_halfs(C, T) * 2);
-    if (e == hipSuccess) e = launch_cl_img_zero_pads(static_cast<uint16_t*>(timg.p), B, C, T, s);
-  }
-  if (e != hipSuccess) return op_rc(e);
-  // 16 channels: pairs [p0, p0 + np) as one g16_c16 launch
-  auto c16_pairs = [&](const float* xin, float* yout, int p0, int np) {
-    ClC16Args a;
-    std::memset(&a, 0, sizeof a);
-    a.x = xin; a.x_bs = (long)T * C; a.out = yout; a.o_bs = (long)T * C;
-    for (int i = 0; i < 2 * np; ++i) {
-      a.w[i] = static_cast<const uint16_t*>(w[2 * p0 + i].p); a.b[i] = static_cast<const float*>(bias[2 * p0 + i].p);
-      a.dil[i] = (i & 1) ? 1 : dilations[p0 + i / 2]; a.add[i] = i & 1;
-    }
-    a.nsteps = 2 * np; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
-    return launch_g16_c16(a, B, s);
-  };
-  if (mode == 2 && c16) {
-    e = c16_pairs(x, out, 0, n_pairs);
-  } else if (mode == 2) {
-    ClChainArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
-    for (int i = 0; i < 2 * n_pairs; ++i) { a.w[i] = static_cast<const uint16_t*>(w[i].p); a.b[i] = static_cast<const float*>(bias[i].p); }
-    for (int p = 0; p < n_pairs; ++p) a.dil[p] = dilations[p];
-    a.np = n_pairs; a.C = C; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
-    if (const char* ev = getenv("VSP_CHAIN_RING")) a.ring = atoi(ev) != 0;   // (read per call: the test API has no context)
-    e = launch_g16_chain(a, B, s);
-  } else {
-    // the running y ping-pongs between two buffers (a tile reads halo rows its neighbour writes)
-    const float* yin = x;
-    for (int p = 0; p < n_pairs && e == hipSuccess; ++p) {
-      float* yout = p == n_pairs - 1 ? out : static_cast<float*>((p & 1) ? yb.p : ya.p);
-      if (mode == 1 && c16) {
-        e = c16_pairs(yin, yout, p, 1);
-      } else if (mode == 1) {
-        ClPairArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.x = yin; a.x_bs = (long)T * C; a.out = yout; a.o_bs = (long)T * C;
-        a.w1h = static_cast<const uint16_t*>(w[2 * p].p); a.w2h = static_cast<const uint16_t*>(w[2 * p + 1].p);
-        a.b1 = static_cast<const float*>(bias[2 * p].p); a.b2 = static_cast<const float*>(bias[2 * p + 1].p);
-        a.C = C; a.K = K; a.dil = dilations[p]; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
-        if (const char* ev = getenv("VSP_PAIR")) a.ring = !strcmp(ev, "ring");     // (read per call: the test API has no context)
-        if (const char* ev = getenv("VSP_RW64")) a.rw64 = atoi(ev) != 0;
-        e = launch_g16_pair(a, B, s);
-      } else {
-        // one launch per convolution; the intermediate as an operand image where the kernels take one (terms 3, K >= 3):
-        // the path the >= 128-channel stages of the generator run
-        const bool img = terms == 3 && K >= 3 && timg.p;
-        ClConvArgs a1 = cl_conv_args(yin, T, C, C, K, dilations[p], w[2 * p], bias[2 * p], 0.1f, nullptr, terms,
-                                     img ? nullptr : static_cast<float*>(t1.p));
-        ClConvArgs a2 = cl_conv_args(static_cast<const float*>(t1.p), T, C, C, K, 1, w[2 * p + 1], bias[2 * p + 1], 0.1f, yin,
-                                     terms, yout);
-        if (img) {
-          a1.o_img = static_cast<uint16_t*>(timg.p); a1.oi_bs = (long)cl_img_halfs(C, T); a1.oi_tpad = cl_img_tpad(T); a1.oi_slope = 0.1f;
-          a2.x_img = a1.o_img; a2.xi_bs = a1.oi_bs; a2.xi_tpad = a1.oi_tpad;
-        }
-        e = launch_g16_conv(a1, B, s);
-        if (e == hipSuccess) e = launch_g16_conv(a2, B, s);
-      }
-      yin = yout;
-    }
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
-}
-
-int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
-                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
-  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || mode < 0 || mode > 1 ||
-      (terms != 1 && terms != 3) || !w_host[0] || !w_host[1])
-    return VSP_ERR_ARG;
-  const bool c16 = C == 16;                              // (g16_c16: two steps with a residual each)
-  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
-  for (int c = 0; c < 2; ++c)
-    if (dilations[c] < 1 || (K - 1) * dilations[c] > 64) return VSP_ERR_UNSUPPORTED;
-  if (mode == 1 && (c16 ? !g16_c16_rb2_supported(K, dilations) : !g16_rb2_supported(C, K, dilations))) return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  DevBuf w[2], bias[2];
-  hipError_t e = hipSuccess;
-  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = upload_cl_conv(w_host[c], bias_host[c], C, C, K, w[c], bias[c], s);
-  DevBuf y;
-  if (e == hipSuccess && mode == 0) e = y.alloc((size_t)B * T * C * 4);
-  if (e != hipSuccess) return op_rc(e);
-  if (mode == 1 && c16) {
-    ClC16Args a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
-    for (int c = 0; c < 2; ++c) {
-      a.w[c] = static_cast<const uint16_t*>(w[c].p); a.b[c] = static_cast<const float*>(bias[c].p); a.dil[c] = dilations[c];
-      a.add[c] = 1;
-    }
-    a.nsteps = 2; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
-    e = launch_g16_c16(a, B, s);
-  } else if (mode == 1) {
-    ClRb2Args a;
-    std::memset(&a, 0, sizeof a);
-    a.x = x; a.x_bs = (long)T * C; a.out = out; a.o_bs = (long)T * C;
-    for (int c = 0; c < 2; ++c) {
-      a.w[c] = static_cast<const uint16_t*>(w[c].p); a.b[c] = static_cast<const float*>(bias[c].p); a.dil[c] = dilations[c];
-    }
-    a.C = C; a.K = K; a.T = T; a.slope = 0.1f; a.acc_prev = 0; a.div = 1.f; a.terms = terms;
-    e = launch_g16_rb2(a, B, s);
-  } else {
-    // one g16_conv per convolution: y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y))
-    float* yp = static_cast<float*>(y.p);
-    e = launch_g16_conv(cl_conv_args(x, T, C, C, K, dilations[0], w[0], bias[0], 0.1f, x, terms, yp), B, s);
-    if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(yp, T, C, C, K, dilations[1], w[1], bias[1], 0.1f, yp, terms, out), B, s);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
-}
-
-int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
-                            const float* w_host, const float* bias_host, float in_slope, const int32_t* lengths,
-                            int terms, float* out) {
-  if (!x || !w_host || !out || x == out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
-  if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 16 || !ups_shape_ok(K, stride) || K / stride - 1 > 64 ||
-      (size_t)T * std::max<size_t>(Cin, (size_t)stride * Cout) * 4 >= (size_t)1 << 31)
-    return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int kt = K / stride;
-  if (lengths) {                                         // (the kernels read rows [0, len) of an utterance: len > T overruns x)
-    std::vector<int32_t> len(B);
-    hipError_t e = hipMemcpyAsync(len.data(), lengths, (size_t)B * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return op_rc(e);
-    for (int32_t l : len)
-      if (l < 0 || l > T) return VSP_ERR_ARG;
-  }
-  // the model's channels-last packing (weights.cpp, Filler::clconv of dec.ups.*): row = phase * Cout + co
-  std::vector<float> dense((size_t)stride * Cout * Cin * kt);
-  for (int r = 0; r < stride; ++r)
-    for (int co = 0; co < Cout; ++co)
-      for (int ci = 0; ci < Cin; ++ci)
-        for (int tap = 0; tap < kt; ++tap)
-          dense[(((size_t)r * Cout + co) * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, co, r, tap, Cout, stride, kt)];
-  DevBuf w, bias;
-  hipError_t e = upload_cl_conv(dense.data(), bias_host, Cout, Cin, kt, w, bias, s, stride);
-  if (e != hipSuccess) return op_rc(e);
-  ClConvArgs a = cl_conv_args(x, T, Cin, Cout, kt, 1, w, bias, in_slope, nullptr, terms, out);
-  a.o_bs = (long)T * stride * Cout;
-  a.pad = kt - 1;
-  a.Nq = T + 1; a.T_store = T * stride;
-  a.phases = stride; a.ups_p = (K - stride) / 2;
-  a.glen = lengths; a.g_in = 1; a.g_store = stride;
-  e = launch_g16_conv(a, B, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
-}
-
-int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
-                         const float* w_host, const float* bias_host, float in_slope, float* out) {
-  if (!x || !w_host || !out || x == out || B < 0 || T < 0) return VSP_ERR_ARG;
-  if (Cin <= 0 || Cout <= 0 || !ups_shape_ok(K, stride) || K / stride - 1 + 3 > CONV_HALO) return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int kt = K / stride, M = Cout * stride;
-  // the model's f32 packing (weights.cpp, Filler::conv of dec.ups.*): row = co * stride + phase
-  std::vector<float> dense((size_t)M * Cin * kt), bd(M, 0.f);
-  for (int row = 0; row < M; ++row) {
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int tap = 0; tap < kt; ++tap)
-        dense[((size_t)row * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, row / stride, row % stride, tap, Cout, stride, kt)];
-    if (bias_host) bd[row] = bias_host[row / stride];
-  }
-  std::vector<float> packed(packed_conv_floats(M, Cin, kt));
-  pack_conv_weights(packed.data(), M, Cin, kt, dense.data());
-  // run_generator's tensors: time rows padded to a multiple of 64 columns; staged here from / to the caller's dense ones
-  const long tp_in = ((long)T + 63) / 64 * 64, T_out = (long)T * stride, tp_out = (T_out + 63) / 64 * 64;
-  DevBuf w, bias, xs, os;
-  hipError_t e = w.alloc(packed.size() * 4);
-  if (e == hipSuccess) e = bias.alloc((size_t)M * 4);
-  if (e == hipSuccess) e = xs.alloc((size_t)B * Cin * tp_in * 4);
-  if (e == hipSuccess) e = os.alloc((size_t)B * Cout * tp_out * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemsetAsync(xs.p, 0, (size_t)B * Cin * tp_in * 4, s);
-  if (e == hipSuccess)
-    e = hipMemcpy2DAsync(xs.p, (size_t)tp_in * 4, x, (size_t)T * 4, (size_t)T * 4, (size_t)B * Cin, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return op_rc(e);
-  ConvArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x = static_cast<const float*>(xs.p); a.x_bs = (long)Cin * tp_in; a.x_cs = tp_in;
-  a.wp = static_cast<const float*>(w.p); a.bias = static_cast<const float*>(bias.p);
-  a.out = static_cast<float*>(os.p); a.o_bs = (long)Cout * tp_out; a.o_cs = tp_out;
-  a.Cin = Cin; a.M = M; a.K = kt; a.dil = 1; a.pad = kt - 1;
-  a.T_in = T; a.Nq = T + 1; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
-  a.in_act = 1; a.in_slope = in_slope;
-  a.alpha = 1.f; a.div = 1.f;
-  a.ups_s = stride; a.ups_p = (K - stride) / 2; a.T_store = (int)T_out;
-  e = launch_conv(a, B, s);
-  if (e == hipSuccess)
-    e = hipMemcpy2DAsync(out, (size_t)T_out * 4, os.p, (size_t)tp_out * 4, (size_t)T_out * 4, (size_t)B * Cout,
-                         hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
 }
 
 // -------------------------------------------------------------------------------------------- profiling

@@ -194,12 +194,13 @@ bool g16_c16_supported(int K, const int* dil, int nsteps) {
   return C16_BT - 2 * g16_c16_halo(K, dil, nsteps) >= C16_BT / 8 && g16_c16_lds(K, nsteps) <= 160 * 1024;
 }
 bool g16_c16_rb1_supported(int K, const int* dil, int np) {
-  if (np < 1 || np > 3) return false;
-  int d[6];
-  for (int p = 0; p < np; ++p) { d[2 * p] = dil[p]; d[2 * p + 1] = 1; }
-  return g16_c16_supported(K, d, 2 * np);
+  int d[6], add[6];
+  return np >= 1 && np <= 3 && g16_c16_supported(K, d, cl_c16_steps(1, dil, np, d, add));
 }
-bool g16_c16_rb2_supported(int K, const int* dil) { return g16_c16_supported(K, dil, 2); }
+bool g16_c16_rb2_supported(int K, const int* dil) {
+  int d[6], add[6];
+  return g16_c16_supported(K, d, cl_c16_steps(2, dil, 2, d, add));
+}
 
 template <int TERMS>
 static hipError_t launch_g16_c16_terms(const ClC16Args& a, int B, hipStream_t s) {

@@ -79,7 +79,7 @@ void pack_conv_weights_f16s(float* dst, int M, int Cin, int K, const float* dens
 
 // The channels-last split-f16 kernels take their weights AND biases * G16_WSCALE and unscale every result by G16_UNSCALE
 // (powers of two: exact; g16_common.h "ONE accumulator per tile"): pack_g16_weights scales the weights itself, whoever
-// fills a bias array for these kernels (weights.cpp, upload_cl_conv in api.hip) scales the bias.
+// fills a bias array for these kernels (weights.cpp, upload_cl_conv in ops.hip) scales the bias.
 #ifndef G16_WSCALE_V          // (timing experiments only: -DG16_WSCALE_V=1.f -DG16_UNSCALE_V=1.f is the unscaled form)
 #define G16_WSCALE_V 256.f
 #define G16_UNSCALE_V (1.f / 256.f)
@@ -241,7 +241,7 @@ struct ClC16Args {
 constexpr int G16_C16_BT = 512;             // columns per block; a launch stores G16_C16_BT - 2 * sum_i (K - 1) dil[i] / 2 of them
 bool g16_c16_supported(int K, const int* dil, int nsteps);
 hipError_t launch_g16_c16(const ClC16Args& a, int B, hipStream_t s);
-// the step lists of a ResBlock1 (pairs [p0, p0 + np): dilations dil[p], then 1) and of a ResBlock2 (two dilations)
+// the step lists (cl_args.h, cl_c16_steps) of np pairs of a ResBlock1 and of a ResBlock2
 bool g16_c16_rb1_supported(int K, const int* dil, int np);
 bool g16_c16_rb2_supported(int K, const int* dil);
 // 16 -> 16 weights [16][16][K] in 16x16x32 A-fragment order, one K-step = TWO TAPS x 16 channels: [step][hi | lo][lane][8 halfs],
@@ -272,7 +272,7 @@ void pack_g16_weights(uint16_t* dst, int rows, int Cin, int K, const float* dens
 // reference models.py:253-256) in polyphase form: one kt-tap convolution per phase r < s over the input padded by kt - 1,
 //   out[s q + r - p][co] = bias[co] + sum_{tap < kt} sum_ci x[q - (kt - 1) + tap][ci] * w[ci][co][s (kt - 1 - tap) + r]
 // for q <= T (output rows outside [0, s T) dropped).  The offset of that weight in w: the ONE mapping behind the model's
-// packing (weights.cpp: dec.ups.*) and the stand-alone operators (api.hip: vsp_cl_conv_transpose1d, vsp_conv_transpose1d).
+// packing (weights.cpp: dec.ups.*) and the stand-alone operators (ops.hip: vsp_cl_conv_transpose1d, vsp_conv_transpose1d).
 inline size_t ups_weight_offset(int ci, int co, int r, int tap, int Cout, int s, int kt) {
   return ((size_t)ci * Cout + co) * ((size_t)kt * s) + (size_t)s * (kt - 1 - tap) + r;
 }
@@ -374,3 +374,5 @@ hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* s
                                  hipStream_t s);
 
 }  // namespace vsp
+
+#include "cl_args.h"   // (builders of the Cl*Args above)

@@ -1,0 +1,317 @@
+// Stand-alone vocoder operators of the C-ABI (include/vispeech_hip.h): one convolution, ResBlock or up-convolution on the
+// caller's tensors with host weights, no context -- what tests/test_cl_ops.py, test_c16_ops.py, test_resblock2_ops.py and
+// test_upsample_ops.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
+// uses (cl_args.h).  Every call allocates, uploads and synchronises: test and measurement entry points, not a hot path.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "kernels.h"
+
+using namespace vsp;
+
+namespace {
+struct DevBuf {           // hipMalloc'd scratch of one stand-alone call
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+// dense [phases * Cout][Cin][K] host weights -> packed fragment image on the device; bias [Cout] -> device
+hipError_t upload_cl_conv(const float* w_host, const float* bias_host, int Cout, int Cin, int K, DevBuf& w, DevBuf& bias,
+                          hipStream_t s, int phases = 1) {
+  const bool c16 = cl_is_c16(Cout, Cin, phases);         // (gen16_c16.hip's image)
+  std::vector<uint16_t> packed(c16 ? packed_g16c16_halfs(K) : packed_g16_halfs(phases * Cout, Cin, K));
+  if (c16) pack_g16c16_weights(packed.data(), K, w_host);
+  else pack_g16_weights(packed.data(), phases * Cout, Cin, K, w_host);
+  hipError_t e = w.alloc(packed.size() * 2);
+  if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, s);
+  std::vector<float> scaled(Cout, 0.f);                  // (kernels.h: these kernels take the bias * G16_WSCALE)
+  if (bias_host) for (int i = 0; i < Cout; ++i) scaled[i] = bias_host[i] * G16_WSCALE;
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, scaled.data(), (size_t)Cout * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);     // the host vectors die with this frame
+  return e;
+}
+ClW cw(const DevBuf& w, const DevBuf& bias) { return ClW{static_cast<const uint16_t*>(w.p), static_cast<const float*>(bias.p)}; }
+int op_rc(hipError_t e) { return e == hipSuccess ? VSP_OK : (e == hipErrorInvalidValue ? VSP_ERR_UNSUPPORTED : VSP_ERR_HIP); }
+// HiFi-GAN's up-convolutions as the generator runs them (kernels.h ups_weight_offset): kt = K / stride taps per phase over
+// the input padded by kt - 1, Nq = T + 1 input times, output rows n = stride q + r - (K - stride) / 2 kept in [0, stride T)
+// -- the shapes plan_model accepts
+bool ups_shape_ok(int K, int stride) { return stride >= 1 && K >= stride && K % stride == 0 && (K - stride) % 2 == 0; }
+}  // namespace
+
+extern "C" {
+
+int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
+                  const float* bias_host, float in_slope, const float* res, int terms, float* out) {
+  if (!x || !w_host || !out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
+  const bool c16 = Cin == 16 && Cout == 16;              // (g16_c16; mixed 16 / 32 has no kernel)
+  if (Cin <= 0 || Cout <= 0 || (!c16 && (Cin % 32 || Cout % 32)) || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation > 64 ||
+      (size_t)T * std::max(Cin, Cout) * 4 >= (size_t)1 << 31)
+    return VSP_ERR_UNSUPPORTED;
+  if (c16 && x == out) return VSP_ERR_ARG;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w, bias;
+  hipError_t e = upload_cl_conv(w_host, bias_host, Cout, Cin, K, w, bias, s);
+  if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(cw(w, bias), Cin, Cout, K, dilation, x, T, in_slope, res, out, terms), B, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
+               const float* bias_host, const int64_t* lengths, int mask_in, int in_act, float in_slope, int act,
+               const float* res, int mask_out, int split_f16, float* out) {
+  if (!x || !w_host || !out || B < 0 || T < 0 || act < 0 || act > 2 || ((mask_in || mask_out) && !lengths) || (act == 2 && res))
+    return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || K < 1 || !(K & 1) || dilation < 1 || (K - 1) * dilation + 3 > CONV_HALO ||
+      (act == 2 && Cout % 64) || ((T & 3) && T != 1))   // (rows of T floats must stay 16-byte aligned for the vector staging;
+                                                        //  T = 1: the one-time-step projections, conv_t1_gemv)
+    return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // the gate reads its tanh / sigmoid halves from interleaved 32-row tiles (weights.cpp packs WN in_layers the same way)
+  std::vector<float> wd((size_t)Cout * Cin * K), bd(Cout, 0.f);
+  for (int r = 0; r < Cout; ++r) {
+    int src = r;
+    if (act == 2) { const int tile = r / 32, in = r % 32; src = (tile & 1) * (Cout / 2) + (tile >> 1) * 32 + in; }
+    std::memcpy(&wd[(size_t)r * Cin * K], w_host + (size_t)src * Cin * K, (size_t)Cin * K * sizeof(float));
+    if (bias_host) bd[r] = bias_host[src];
+  }
+  std::vector<float> packed(packed_conv_floats(Cout, Cin, K));
+  if (split_f16) pack_conv_weights_f16s(packed.data(), Cout, Cin, K, wd.data());
+  else pack_conv_weights(packed.data(), Cout, Cin, K, wd.data());
+  DevBuf w, bias;
+  hipError_t e = w.alloc(packed.size() * 4);
+  if (e == hipSuccess) e = bias.alloc((size_t)Cout * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)Cout * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return op_rc(e);
+  const int rows_out = act == 2 ? Cout / 2 : Cout;
+  ConvArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = x; a.x_bs = (long)Cin * T; a.x_cs = T;
+  a.wp = static_cast<const float*>(w.p); a.bias = static_cast<const float*>(bias.p);
+  a.out = out; a.o_bs = (long)rows_out * T; a.o_cs = T;
+  a.res = res; a.r_bs = (long)rows_out * T; a.r_cs = T;
+  a.lengths = lengths;
+  a.Cin = Cin; a.M = Cout; a.K = K; a.dil = dilation; a.pad = dilation * (K - 1) / 2;
+  a.T_in = T; a.Nq = T; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
+  a.in_mask = mask_in ? 1 : 0; a.in_act = in_act ? 1 : 0; a.in_slope = in_slope;
+  a.act = act; a.alpha = 1.f; a.div = 1.f; a.mask_post = mask_out ? 1 : 0;
+  a.f16s = split_f16 ? 1 : 0;
+  if (split_f16 == 2) {
+    // the column-tile form (conv_cols.hip: every output row of a 64-column tile in one block) as a stand-alone operator:
+    // the same weights in 16x16x32 A-fragment order; refused where that kernel does not apply
+    std::vector<uint16_t> wgh(packed_g16_halfs(Cout, Cin, 1));
+    DevBuf wgd;
+    if (K != 1 || Cin % 32 || Cout % 16) return VSP_ERR_UNSUPPORTED;
+    pack_g16_weights(wgh.data(), Cout, Cin, 1, wd.data());
+    e = wgd.alloc(wgh.size() * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(wgd.p, wgh.data(), wgh.size() * 2, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    a.wg = static_cast<const uint16_t*>(wgd.p);
+    if (!conv_cols_supported(a)) return VSP_ERR_UNSUPPORTED;
+    e = launch_conv_cols(a, B, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return op_rc(e);
+  }
+  e = launch_conv(a, B, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const int* dilations, const float* x,
+                    const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
+  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || n_pairs < 1 || n_pairs > 8 ||
+      mode < 0 || mode > 2 || (terms != 1 && terms != 3))
+    return VSP_ERR_ARG;
+  const bool c16 = C == 16;                              // (g16_c16: mode 1 = a pair's two steps, mode 2 = the whole block)
+  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (dilations[p] < 1 || (K - 1) * dilations[p] > 64) return VSP_ERR_UNSUPPORTED;
+    if (mode == 1 && (c16 ? !g16_c16_rb1_supported(K, dilations + p, 1)
+                          : !g16_pair_supported(C, K, dilations[p]) && !g16_pp_supported(C, K, dilations[p], terms)))
+      return VSP_ERR_UNSUPPORTED;
+    if (!w_host[2 * p] || !w_host[2 * p + 1]) return VSP_ERR_ARG;
+  }
+  if (mode == 2 && (n_pairs > 3 || (c16 ? !g16_c16_rb1_supported(K, dilations, n_pairs) : !g16_chain_supported(C, K, dilations, n_pairs))))
+    return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<DevBuf> w(2 * n_pairs), bias(2 * n_pairs);
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 2 * n_pairs && e == hipSuccess; ++i) e = upload_cl_conv(w_host[i], bias_host[i], C, C, K, w[i], bias[i], s);
+  const size_t el = (size_t)B * T * C;
+  DevBuf t1, ya, yb;
+  if (e == hipSuccess && mode != 2) e = t1.alloc(el * 4);
+  if (e == hipSuccess && mode != 2) e = ya.alloc(el * 4);
+  if (e == hipSuccess && mode != 2) e = yb.alloc(el * 4);
+  DevBuf timg;
+  if (e == hipSuccess && mode == 0 && terms == 3 && K >= 3 && !c16) {
+    e = timg.alloc((size_t)B * cl_img_halfs(C, T) * 2);
+    if (e == hipSuccess) e = launch_cl_img_zero_pads(static_cast<uint16_t*>(timg.p), B, C, T, s);
+  }
+  if (e != hipSuccess) return op_rc(e);
+  std::vector<ClW> conv(2 * n_pairs);                   // (execution order: conv1, conv2 of pair 0, 1, ..)
+  for (int i = 0; i < 2 * n_pairs; ++i) conv[i] = cw(w[i], bias[i]);
+  // pairs [p0, p0 + np) as one launch: g16_c16 at 16 channels, else g16_pair (as_pair) or g16_chain
+  auto fused = [&](const float* xin, float* yout, int p0, int np, bool as_pair) {
+    if (c16) return launch_g16_c16(cl_c16_args(1, &conv[2 * p0], K, dilations + p0, np, xin, yout, T, terms), B, s);
+    if (as_pair) {
+      ClPairArgs a = cl_pair_args(&conv[2 * p0], C, K, dilations[p0], xin, yout, T, terms);
+      if (const char* ev = getenv("VSP_PAIR")) a.ring = !strcmp(ev, "ring");     // (read per call: the test API has no context)
+      if (const char* ev = getenv("VSP_RW64")) a.rw64 = atoi(ev) != 0;
+      return launch_g16_pair(a, B, s);
+    }
+    ClChainArgs a = cl_chain_args(&conv[2 * p0], C, K, dilations + p0, np, xin, yout, T, terms);
+    if (const char* ev = getenv("VSP_CHAIN_RING")) a.ring = atoi(ev) != 0;
+    return launch_g16_chain(a, B, s);
+  };
+  if (mode == 2) {
+    e = fused(x, out, 0, n_pairs, false);
+  } else {
+    // the running y ping-pongs between two buffers (a tile reads halo rows its neighbour writes)
+    const float* yin = x;
+    for (int p = 0; p < n_pairs && e == hipSuccess; ++p) {
+      float* yout = p == n_pairs - 1 ? out : static_cast<float*>((p & 1) ? yb.p : ya.p);
+      if (mode == 1) {
+        e = fused(yin, yout, p, 1, true);
+      } else {
+        // one launch per convolution; the intermediate as an operand image where the kernels take one (terms 3, K >= 3):
+        // the path the >= 128-channel stages of the generator run
+        uint16_t* const img = static_cast<uint16_t*>(timg.p);   // (NULL where none was allocated above)
+        ClConvArgs a1 = cl_conv_args(conv[2 * p], C, C, K, dilations[p], yin, T, CL_LRELU_SLOPE, nullptr,
+                                     img ? nullptr : static_cast<float*>(t1.p), terms);
+        ClConvArgs a2 = cl_conv_args(conv[2 * p + 1], C, C, K, 1, static_cast<const float*>(t1.p), T, CL_LRELU_SLOPE, yin, yout, terms);
+        a1.o_img = img; a2.x_img = img;
+        e = launch_g16_conv(a1, B, s);
+        if (e == hipSuccess) e = launch_g16_conv(a2, B, s);
+      }
+      yin = yout;
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
+                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
+  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || mode < 0 || mode > 1 ||
+      (terms != 1 && terms != 3) || !w_host[0] || !w_host[1])
+    return VSP_ERR_ARG;
+  const bool c16 = C == 16;                              // (g16_c16: two steps with a residual each)
+  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  for (int c = 0; c < 2; ++c)
+    if (dilations[c] < 1 || (K - 1) * dilations[c] > 64) return VSP_ERR_UNSUPPORTED;
+  if (mode == 1 && (c16 ? !g16_c16_rb2_supported(K, dilations) : !g16_rb2_supported(C, K, dilations))) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w[2], bias[2];
+  hipError_t e = hipSuccess;
+  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = upload_cl_conv(w_host[c], bias_host[c], C, C, K, w[c], bias[c], s);
+  DevBuf y;
+  if (e == hipSuccess && mode == 0) e = y.alloc((size_t)B * T * C * 4);
+  if (e != hipSuccess) return op_rc(e);
+  const ClW conv[2] = {cw(w[0], bias[0]), cw(w[1], bias[1])};
+  if (mode == 1 && c16) {
+    e = launch_g16_c16(cl_c16_args(2, conv, K, dilations, 2, x, out, T, terms), B, s);
+  } else if (mode == 1) {
+    e = launch_g16_rb2(cl_rb2_args(conv, C, K, dilations, x, out, T, terms), B, s);
+  } else {
+    // one g16_conv per convolution: y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y))
+    float* yp = static_cast<float*>(y.p);
+    e = launch_g16_conv(cl_conv_args(conv[0], C, C, K, dilations[0], x, T, CL_LRELU_SLOPE, x, yp, terms), B, s);
+    if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(conv[1], C, C, K, dilations[1], yp, T, CL_LRELU_SLOPE, yp, out, terms), B, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                            const float* w_host, const float* bias_host, float in_slope, const int32_t* lengths,
+                            int terms, float* out) {
+  if (!x || !w_host || !out || x == out || B < 0 || T < 0 || (terms != 1 && terms != 3)) return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 16 || !ups_shape_ok(K, stride) || K / stride - 1 > 64 ||
+      (size_t)T * std::max<size_t>(Cin, (size_t)stride * Cout) * 4 >= (size_t)1 << 31)
+    return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int kt = K / stride;
+  if (lengths) {                                         // (the kernels read rows [0, len) of an utterance: len > T overruns x)
+    std::vector<int32_t> len(B);
+    hipError_t e = hipMemcpyAsync(len.data(), lengths, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return op_rc(e);
+    for (int32_t l : len)
+      if (l < 0 || l > T) return VSP_ERR_ARG;
+  }
+  // the model's channels-last packing (weights.cpp, Filler::clconv of dec.ups.*): row = phase * Cout + co
+  std::vector<float> dense((size_t)stride * Cout * Cin * kt);
+  for (int r = 0; r < stride; ++r)
+    for (int co = 0; co < Cout; ++co)
+      for (int ci = 0; ci < Cin; ++ci)
+        for (int tap = 0; tap < kt; ++tap)
+          dense[(((size_t)r * Cout + co) * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, co, r, tap, Cout, stride, kt)];
+  DevBuf w, bias;
+  hipError_t e = upload_cl_conv(dense.data(), bias_host, Cout, Cin, kt, w, bias, s, stride);
+  if (e != hipSuccess) return op_rc(e);
+  ClConvArgs a = cl_ups_args(cw(w, bias), Cin, Cout, kt, stride, x, T, in_slope, out, terms);
+  a.glen = lengths; a.g_in = 1; a.g_store = stride;
+  e = launch_g16_conv(a, B, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
+                         const float* w_host, const float* bias_host, float in_slope, float* out) {
+  if (!x || !w_host || !out || x == out || B < 0 || T < 0) return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || !ups_shape_ok(K, stride) || K / stride - 1 + 3 > CONV_HALO) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int kt = K / stride, M = Cout * stride;
+  // the model's f32 packing (weights.cpp, Filler::conv of dec.ups.*): row = co * stride + phase
+  std::vector<float> dense((size_t)M * Cin * kt), bd(M, 0.f);
+  for (int row = 0; row < M; ++row) {
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int tap = 0; tap < kt; ++tap)
+        dense[((size_t)row * Cin + ci) * kt + tap] = w_host[ups_weight_offset(ci, row / stride, row % stride, tap, Cout, stride, kt)];
+    if (bias_host) bd[row] = bias_host[row / stride];
+  }
+  std::vector<float> packed(packed_conv_floats(M, Cin, kt));
+  pack_conv_weights(packed.data(), M, Cin, kt, dense.data());
+  // run_generator's tensors: time rows padded to a multiple of 64 columns; staged here from / to the caller's dense ones
+  const long tp_in = ((long)T + 63) / 64 * 64, T_out = (long)T * stride, tp_out = (T_out + 63) / 64 * 64;
+  DevBuf w, bias, xs, os;
+  hipError_t e = w.alloc(packed.size() * 4);
+  if (e == hipSuccess) e = bias.alloc((size_t)M * 4);
+  if (e == hipSuccess) e = xs.alloc((size_t)B * Cin * tp_in * 4);
+  if (e == hipSuccess) e = os.alloc((size_t)B * Cout * tp_out * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)M * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(xs.p, 0, (size_t)B * Cin * tp_in * 4, s);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(xs.p, (size_t)tp_in * 4, x, (size_t)T * 4, (size_t)T * 4, (size_t)B * Cin, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return op_rc(e);
+  ConvArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = static_cast<const float*>(xs.p); a.x_bs = (long)Cin * tp_in; a.x_cs = tp_in;
+  a.wp = static_cast<const float*>(w.p); a.bias = static_cast<const float*>(bias.p);
+  a.out = static_cast<float*>(os.p); a.o_bs = (long)Cout * tp_out; a.o_cs = tp_out;
+  a.Cin = Cin; a.M = M; a.K = kt; a.dil = 1; a.pad = kt - 1;
+  a.T_in = T; a.Nq = T + 1; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
+  a.in_act = 1; a.in_slope = in_slope;
+  a.alpha = 1.f; a.div = 1.f;
+  a.ups_s = stride; a.ups_p = (K - stride) / 2; a.T_store = (int)T_out;
+  e = launch_conv(a, B, s);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(out, (size_t)T_out * 4, os.p, (size_t)tp_out * 4, (size_t)T_out * 4, (size_t)B * Cout,
+                         hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+}  // extern "C"
