@@ -266,6 +266,14 @@ int64_t vsp_generator_workspace_bytes(const vsp_ctx* ctx, int B, int T);
 int vsp_generator_kind(const vsp_ctx* ctx);
 int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g,
                   float* o, void* workspace, int64_t workspace_bytes);
+/* The generator with per-utterance ends (ABI 7, additive; round 10): utterance b's waveform samples [0, L_b * up),
+ * L_b = min(lengths[b], T), up = prod(upsample_rates), are what vsp_generator returns for a B = 1 call on z[b][:, :L_b] -- its
+ * tensors END at L_b in every stage, whatever z holds behind L_b and whoever shares the batch -- and o is exactly 0.0 behind
+ * them.  lengths [B] int64 on the device (< 1: the whole row is zero).  Workspace: vsp_generator_workspace_bytes + B *
+ * sizeof(int) bytes (an upper bound kept for callers' arithmetic: vsp_generator_workspace_bytes itself holds the per-utterance
+ * plan, so the extra ints are not touched).  It is the generator call vsp_decode / vsp_infer / vsp_voice_conversion make in isolated mode. */
+int vsp_generator_ragged(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g,
+                         const int64_t* lengths, float* o, void* workspace, int64_t workspace_bytes);
 
 /* Streamed vocoder (BASELINE config 5; the chunked output loop of reference inference_api.py:50-60 applied to the
  * vocoder itself): the waveform samples of frames [f0, f1) of z [B][inter][T], computed from those frames plus
@@ -337,6 +345,26 @@ int vsp_randn_at(void* stream, uint64_t seed, int64_t first, int64_t n, float* o
  * global batch sets lo * inter * Tf (Tf = the GLOBAL padded frame count): the result no longer depends on the shard
  * layout.  Sticky until changed; 0 restores the default.  (Added in round 4; callers that never set it are unaffected.) */
 int vsp_set_noise_offset(vsp_ctx* ctx, int64_t first_element);
+
+/* ---- isolated mode (ABI 7, additive; round 10): batch-invariant synthesis ------------------ */
+/* In a padded batch the reference applies no mask in dec, pitch_prenet, energy_prenet and EnergyPredictor (SURVEY gotcha
+ * G5): a shorter utterance's audio depends on what it was batched with, and the default mode reproduces that padded call.
+ * With the mode ON, every tensor vsp_encode / vsp_decode / vsp_infer / vsp_voice_conversion return, restricted to
+ * utterance b's own extent (lengths[b] phonemes, L_b frames, min(L_b, max_len) frames of waveform), is what the reference
+ * returns for a B = 1 call on that utterance's unpadded inputs -- independent of B, Tp, Tf, the other utterances and the
+ * position in the batch; the controls are read at t < lengths[b] only; every float output is exactly 0.0 behind its extent
+ * (x_mask as before).  The guarantee is the usual tolerance against the reference, not bit-identity with a B = 1 call of this
+ * library (kernels are chosen by launch size).  Sticky context state, default OFF: nothing changes for callers that never
+ * set it.  vsp_get_isolated: 0 / 1. */
+int vsp_set_isolated(vsp_ctx* ctx, int on);
+int vsp_get_isolated(const vsp_ctx* ctx);
+/* Noise in isolated mode.  A caller's noise tensor [B][inter][Tf]: utterance b uses noise[b][:, :L_b].  noise == NULL: the
+ * library draws utterance b's tensor as the first inter * L_b elements of the Philox stream keyed seeds[b], laid out
+ * [inter][L_b] (element (c, t) = stream element c * L_b + t) -- exactly what a B = 1, Tf = L_b, noise_seed = seeds[b] call
+ * draws -- so the sample does not depend on the batch either.  seeds_host [B] (host memory, copied; B = 0 forgets them);
+ * a drawing call whose B differs from the seeds set fails with VSP_ERR_STATE.  The noise_seed argument and
+ * vsp_set_noise_offset are not read in isolated mode. */
+int vsp_set_noise_seeds(vsp_ctx* ctx, const uint64_t* seeds_host, int B);
 
 /* ---- mel spectrogram (reference mel_processing.py:73-112) --------------------------------- */
 /* The mel basis the reference takes from librosa.filters.mel(sampling_rate, n_fft, n_mels, fmin, fmax) with that

@@ -78,6 +78,9 @@ SIGNATURES = {
     "vsp_randn": (_I, [_P, _U64, _I64, _P]),
     "vsp_randn_at": (_I, [_P, _U64, _I64, _I64, _P]),
     "vsp_set_noise_offset": (_I, [_P, _I64]),
+    "vsp_set_isolated": (_I, [_P, _I]),
+    "vsp_get_isolated": (_I, [_P]),
+    "vsp_set_noise_seeds": (_I, [_P, C.POINTER(_U64), _I]),
     "vsp_encoder_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_encoder": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I64]),
     "vsp_length_regulate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -85,6 +88,7 @@ SIGNATURES = {
     "vsp_flow_reverse": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I64]),
     "vsp_generator_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_generator": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I64]),
+    "vsp_generator_ragged": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I64]),
     "vsp_generator_kind": (_I, [_P]),
     "vsp_generator_halo_frames": (_I, [_P]),
     "vsp_generator_frame_dependence": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),

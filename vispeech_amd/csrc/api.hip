@@ -61,6 +61,7 @@ struct Run {
   const int64_t* host_lengths = nullptr;   // the batch's frame counts where the host knows them (vsp_ctx::fl_known), else NULL
   const int* glen = nullptr;
   int grate_in = 0, grate_out = 0;
+  bool iso = false;                        // isolated mode (model.h): the generator ends utterance b's tensors at in_lengths[b]
   // share of the padded frames the launches of the current generator chunk compute (trimmed tails): the profiled work
   // of a launch is charged for the frames it processes, not for the padded tensor (set while profiling only)
   double work_frac = 1.0;
@@ -438,6 +439,20 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
   };
   int cur = 0;  // buffer holding the stage input
   T3 X = view(cur, c0, T);
+  // Isolated mode: these kernels have no per-utterance extent, but every convolution can mask its staged input
+  // (ConvArgs::lengths + in_mask): with utterance b's length at every stage's rate, whatever a launch writes behind an
+  // utterance's end is never read by the next one -- each convolution sees the zero padding of a tensor that ends there.
+  // (the array is part of the workspace in either mode: its size does not depend on the context's state)
+  int64_t* const stage_len = reinterpret_cast<int64_t*>(r.ws.bytes((size_t)(VSP_MAX_LIST + 1) * B * sizeof(int64_t)));
+  const bool iso = r.iso && in_lengths;
+  if (iso && !r.dry() && r.ok()) {
+    long rate[VSP_MAX_LIST + 1] = {1};
+    for (int i = 0; i < c.n_upsamples; ++i) rate[i + 1] = rate[i] * m.ups[i].ups_s;
+    r.chk(launch_stage_lengths(in_lengths, B, rate, c.n_upsamples + 1, stage_len, r.s), "stage_lengths");
+  }
+  auto own_end = [&](ConvArgs& ca, int stage) {
+    if (iso) { ca.lengths = stage_len + (size_t)stage * B; ca.in_mask = 1; }
+  };
   ConvArgs a = r.args(m.g_pre, z, X, T, T);
   a.lengths = in_lengths; a.in_mask = in_lengths ? 1 : 0;
   a.cond = gc; a.cond_bs = c0;
@@ -455,6 +470,7 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
     a = r.args(U, X, XU, (int)Tn, (int)Tn + 1);
     a.in_act = 1; a.in_slope = 0.1f;
     a.T_store = (int)Tout;
+    own_end(a, i);
     r.conv(a, B, true);
     for (int j = 0; j < nk; ++j) {
       const ResBlockW& rb = m.rbs[i * nk + j];
@@ -472,6 +488,7 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
             a.acc_prev = j > 0;
             if (j == nk - 1) a.div = (float)nk;
           }
+          own_end(a, i + 1);
           r.conv(a, B, true);
         }
         continue;
@@ -480,6 +497,7 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
         const T3 yin = d == 0 ? XU : YA;
         a = r.args(rb.c1[d], yin, T1, (int)Tout, (int)Tout);
         a.in_act = 1; a.in_slope = 0.1f;
+        own_end(a, i + 1);
         r.conv(a, B, true);
         const bool last = d == nd - 1;
         a = r.args(rb.c2[d], T1, last ? XS : YA, (int)Tout, (int)Tout);
@@ -489,6 +507,7 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
           a.acc_prev = j > 0;
           if (j == nk - 1) a.div = (float)nk;
         }
+        own_end(a, i + 1);
         r.conv(a, B, true);
       }
     }
@@ -496,9 +515,11 @@ void run_generator(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const 
     X = XS;
     Tn = Tout;
   }
-  if (!r.dry() && r.ok())
-    r.chk(launch_conv_post(X.p, X.bs, X.cs, r.A(m.post_w), m.post_c, m.post_k, 0.01f, o, Tn, B, (int)Tn, r.s, r.ctx->flags_dev),
-          "conv_post");
+  if (!r.dry() && r.ok()) {
+    r.chk(launch_conv_post(X.p, X.bs, X.cs, r.A(m.post_w), m.post_c, m.post_k, 0.01f, o, Tn, B, (int)Tn, r.s, r.ctx->flags_dev,
+                           iso ? stage_len + (size_t)c.n_upsamples * B : nullptr), "conv_post");
+    if (iso) r.chk(launch_gen_tail_zero(o, Tn, in_lengths, B, T, (int)(Tn / T), r.s), "gen_tail_zero");
+  }
 }
 
 // The context's two side streams and n fork / join events (created on first use, on the device the caller's stream
@@ -618,18 +639,26 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   // A tensor that ends after E frames is exact up to frame E - 1 - fwd; frame len + back is the first steady one.)
   int back = 0, fwd = 0;
   generator_frame_dependence(c, r.ctx->resblock, m.g_pre.K, m.post_k, back, fwd);
-  int* glen_all = r.ctx->trim_tails ? reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int))) : nullptr;
+  // Isolated mode (model.h): the same per-utterance extent with glen[b] = the utterance's own length -- its tensors END where
+  // a B = 1 call's would, nothing behind the end is computed, and gen_tail_zero writes the padded rest of the waveform.
+  // Neither of the tail fill's preconditions below applies to it.
+  const bool iso = r.iso && in_lengths;
+  // (the plan is part of the workspace whatever the context's switches: its size does not depend on the context's state)
+  int* glen_all = reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int)));
   // (gen_tail_fill keeps the computed tensor end -- fwd frames of the waveform -- in 64 KB of LDS: other configurations run untrimmed)
-  bool trim = glen_all && in_lengths && T > back + fwd + 1 && (size_t)fwd * total_upsample(c) * sizeof(float) <= 64 * 1024;
+  bool trim = in_lengths && (iso || (r.ctx->trim_tails && T > back + fwd + 1 &&
+                                                 (size_t)fwd * total_upsample(c) * sizeof(float) <= 64 * 1024));
   if (trim && r.host_lengths) {
     // the host knows the frame counts (vsp_frame_lengths_host of this batch): when no utterance ends early enough to be
     // trimmed (a uniform batch, one long utterance) the kernels run WITHOUT per-utterance extents -- same output, and
     // the persistent pipelined g16_convp serves the uniform tiles again
     bool any = false;
-    for (int b = 0; b < B; ++b) any = any || std::max<int64_t>(r.host_lengths[b], 0) + back + 1 + fwd < T;
+    for (int b = 0; b < B; ++b) any = any || std::max<int64_t>(r.host_lengths[b], 0) + (iso ? 0 : back + 1 + fwd) < T;
     trim = any;
   }
-  if (trim && !r.dry() && r.ok()) r.chk(launch_gen_plan(in_lengths, B, T, back, fwd, glen_all, r.s), "gen_plan");
+  if (trim && !r.dry() && r.ok())
+    r.chk(iso ? launch_gen_plan_isolated(in_lengths, B, T, glen_all, r.s) : launch_gen_plan(in_lengths, B, T, back, fwd, glen_all, r.s),
+          "gen_plan");
   // profiled (untimed) passes charge every launch the frames it COMPUTES: read the plan back (a host wait -- profiling only)
   std::vector<int> glen_host;
   if (trim && r.ctx->prof_on && !r.dry() && r.ok()) {
@@ -758,7 +787,8 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   if (!r.dry() && r.ok()) {
     r.chk(launch_conv_post_cl(buf[cur], Tn * ch, ch, r.A(m.post_wt), m.post_c, m.post_k, 0.01f, o, Tn, B, (int)Tn, r.s,
                               trim ? glen_all : nullptr, (int)(Tn / T), 1.f / r.ctx->act_scale, r.ctx->flags_dev), "conv_post_cl");
-    if (trim) r.chk(launch_gen_tail_fill(o, Tn, in_lengths, glen_all, B, T, back, fwd, (int)(Tn / T), r.s), "gen_tail_fill");
+    if (trim && iso) r.chk(launch_gen_tail_zero(o, Tn, in_lengths, B, T, (int)(Tn / T), r.s), "gen_tail_zero");
+    else if (trim) r.chk(launch_gen_tail_fill(o, Tn, in_lengths, glen_all, B, T, back, fwd, (int)(Tn / T), r.s), "gen_tail_fill");
   }
 }
 
@@ -1158,6 +1188,10 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   const Model& m = ctx->model;
   const int h = c.hidden_channels, gin = c.gin_channels;
   Run r{ctx, s, ws};
+  // Isolated mode (model.h): the controls are read at t < lengths[b] only, the signals the two prenets convolve are zero
+  // behind an utterance's end (what a B = 1 call's zero padding is), the EnergyPredictor masks like the duration
+  // predictor, and every output is zero behind its extent.
+  const bool iso = ctx->isolated;
   const T3 XV = ext(x_var, h, Tp);
   T3 XE = ws.t3(B, h, Tp), TMP = ws.t3(B, h, Tp);
   float* cvec = ws.f((size_t)B * h);
@@ -1178,6 +1212,8 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   if (live) { ctx->fl_src = nullptr; ctx->fl_known_src = nullptr; }
   if (dctl && live) {
     r.chk(hipMemcpyAsync(duration, dctl, (size_t)B * Tp * sizeof(float), hipMemcpyDeviceToDevice, s), "dur copy");
+    // (a caller's pad values would count as frames: the reference's regulator loops over all Tp)
+    if (iso) r.chk(launch_mask_rows(lengths, B, Tp, duration, nullptr, nullptr, nullptr, s), "duration mask");
     r.chk(launch_duration_cumsum(duration, cum_dur, frame_lengths, B, Tp, s, ctx->flags_dev), "duration cumsum");
     // (early_copy == false: the one-call form vsp_infer never reads the counts back -- nothing would consume the copy)
     if (r.ok() && early_copy && ctx->early_fl && early_frame_lengths_ready(ctx, B)) {
@@ -1205,6 +1241,7 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
     if (live) {
       r.chk(launch_chan_dot(A2.p, A2.bs, A2.cs, r.A(m.dur_pw), r.A(m.dur_pb), lengths, 1, 1, pred, B, f, Tp, s), "dur proj");
       r.chk(launch_duration_from_logw(pred, lengths, dscale, duration, B, Tp, s), "duration");
+      if (iso) r.chk(launch_mask_rows(lengths, B, Tp, duration, nullptr, nullptr, nullptr, s), "duration mask");   // (ceil(-scale) at the pad)
     }
   }
   // ---- pitch (models.py:691-698, 505-514)
@@ -1218,6 +1255,8 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   }
   if (live) {
     r.chk(launch_pitch(pctl, pred, pscale, lf0, f0, B * Tp, s), "pitch");
+    // (the predicted lf0 carries proj_f0's bias at the pad, a control whatever the caller left there)
+    if (iso) r.chk(launch_mask_rows(lengths, B, Tp, lf0, f0, nullptr, nullptr, s), "pitch mask");
     r.chk(launch_prenet_add(XV.p, XV.bs, XV.cs, r.A(m.ppre_w), r.A(m.ppre_b), lf0, B, h, Tp, s), "pitch_prenet");
   }
   // ---- energy (models.py:701-708; frame_prior_network.py:104-124: no mask anywhere)
@@ -1228,17 +1267,23 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
     if (live) r.chk(launch_add_cond(XV.p, XV.bs, XV.cs, cvec, h, TMP.p, TMP.bs, TMP.cs, B, h, Tp, s), "add_cond");
     ConvArgs a = r.args(m.en_c1, TMP, A1, Tp, Tp);
     a.act = 1;
+    if (iso) { a.lengths = lengths; a.in_mask = 1; }   // x + cond(g) is not zero at the pad
     r.conv(a, B);
     r.ln(A1, T3{}, m.en_g1, m.en_b1, A1, B, e, Tp);
     a = r.args(m.en_c2, A1, A2, Tp, Tp);
     a.act = 1;
+    if (iso) { a.lengths = lengths; a.in_mask = 1; }   // ... nor what conv 1 + LayerNorm put there
     r.conv(a, B);
     r.ln(A2, T3{}, m.en_g2, m.en_b2, A2, B, e, Tp);
     if (live) r.chk(launch_chan_dot(A2.p, A2.bs, A2.cs, r.A(m.en_lw), r.A(m.en_lb), nullptr, 0, 0, pred, B, e, Tp, s), "energy linear");
   }
   if (live) {
     r.chk(launch_energy(ectl, pred, escale, norm_e, energy, B * Tp, s), "energy");
+    // (norm_energy, not the control: a zero energy control is norm_energy = -60 / 36 at the pad)
+    if (iso) r.chk(launch_mask_rows(lengths, B, Tp, norm_e, energy, nullptr, nullptr, s), "energy mask");
     r.chk(launch_prenet_add(XV.p, XV.bs, XV.cs, r.A(m.epre_w), r.A(m.epre_b), norm_e, B, h, Tp, s), "energy_prenet");
+    // (the regulator never reads x_var behind an utterance's end; zero all the same: the stage's output contract)
+    if (iso) r.chk(launch_mask3(XV.p, XV.bs, XV.cs, lengths, B, h, Tp, s), "x_var mask");
     if (!dctl) r.chk(launch_duration_cumsum(duration, cum_dur, frame_lengths, B, Tp, s, ctx->flags_dev), "duration cumsum");
   }
   if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "encode workspace too small (need %zu bytes)", ws.cur);
@@ -1304,12 +1349,26 @@ static int decode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, int T
   const Model& m = ctx->model;
   const int h = c.hidden_channels, inter = c.inter_channels;
   Run r{ctx, s, ws};
+  r.iso = ctx->isolated;
   if (frame_lengths && ctx->fl_known_src == frame_lengths && (int)ctx->fl_known.size() == B) r.host_lengths = ctx->fl_known.data();
   T3 XF = ws.t3(B, h, Tf), HF = ws.t3(B, h, Tf);
   // noise == NULL: the library draws it (Philox4x32-10 keyed by noise_seed) -- the torch.randn_like of models.py:718
   float* drawn = ws.f((size_t)B * inter * Tf);
+  uint64_t* seeds_dev = reinterpret_cast<uint64_t*>(ws.bytes((size_t)B * sizeof(uint64_t)));
   const bool live = !ws.dry && !ws.overflow;
-  if (live && !noise && noise_scale != 0.f) {
+  if (live && !noise && noise_scale != 0.f && r.iso) {
+    // isolated mode: utterance b's own draw, keyed seeds[b], laid out [inter][L_b] -- what a B = 1 call with Tf = L_b and
+    // noise_seed = seeds[b] draws (vsp_set_noise_seeds; noise_seed and the noise offset are not read)
+    if ((int)ctx->noise_seeds.size() != B)
+      return ctx->fail(VSP_ERR_STATE, "isolated mode draws per-utterance noise: vsp_set_noise_seeds for B = %d first (%d set)",
+                       B, (int)ctx->noise_seeds.size());
+    // (pageable source: the runtime reads it into its own staging memory before this call returns -- hipMemcpyAsync is
+    // asynchronous only for pinned host memory -- so a later vsp_set_noise_seeds may replace the vector while the copy is
+    // still queued on the stream; the seeds land in THIS call's workspace, not in context memory the next call overwrites)
+    r.chk(hipMemcpyAsync(seeds_dev, ctx->noise_seeds.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, s), "noise seeds");
+    if (r.ok()) r.chk(launch_randn_ragged(seeds_dev, frame_lengths, B, inter, Tf, drawn, s), "randn_ragged");
+    noise = drawn;
+  } else if (live && !noise && noise_scale != 0.f) {
     r.chk(launch_randn(noise_seed, (long)ctx->noise_first, (long)B * inter * Tf, drawn, s), "randn");
     noise = drawn;
   }
@@ -1327,6 +1386,10 @@ static int decode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, int T
   if (live) {
     const long n = (long)B * inter * Tf;
     r.chk(launch_reparam(m_p, logs_p, noise, noise_scale, z_p, n, s, z, ctx->flags_dev), "reparam");   // (z = z_p: the flow transforms z in place)
+    if (r.iso) {   // m_p = logs_p = 0 at the pad: z_p is noise * noise_scale there
+      r.chk(launch_mask3(z_p, (long)inter * Tf, Tf, frame_lengths, B, inter, Tf, s), "z_p mask");
+      r.chk(launch_mask3(z, (long)inter * Tf, Tf, frame_lengths, B, inter, Tf, s), "z mask");
+    }
   }
   run_flow(r, B, Tf, Z, g, frame_lengths);
   const int Tdec = max_len < 0 ? Tf : std::min(Tf, max_len);
@@ -1600,6 +1663,21 @@ int vsp_set_noise_offset(vsp_ctx* ctx, int64_t first_element) {
   return VSP_OK;
 }
 
+int vsp_set_isolated(vsp_ctx* ctx, int on) {
+  if (!ctx) return VSP_ERR_ARG;
+  ctx->isolated = on != 0;
+  return VSP_OK;
+}
+
+int vsp_get_isolated(const vsp_ctx* ctx) { return ctx ? (ctx->isolated ? 1 : 0) : VSP_ERR_ARG; }
+
+int vsp_set_noise_seeds(vsp_ctx* ctx, const uint64_t* seeds_host, int B) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (B < 0 || (B > 0 && !seeds_host)) return ctx->fail(VSP_ERR_ARG, "vsp_set_noise_seeds: B < 0 or null seeds");
+  ctx->noise_seeds.assign(seeds_host, seeds_host + B);     // (B = 0 forgets them)
+  return VSP_OK;
+}
+
 // ---------------------------------------------------------------------------------- spectrogram
 int vsp_spectrogram_frames(const vsp_ctx* ctx, int L, int hop) {
   if (!ctx || ctx->cfg.spec_channels <= 1 || hop <= 0) return VSP_ERR_ARG;
@@ -1688,6 +1766,7 @@ static int vc_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int T, const floa
   const Model& m = ctx->model;
   const int inter = c.inter_channels, gin = c.gin_channels;
   Run r{ctx, s, ws};
+  r.iso = ctx->isolated;     // (the posterior encoder and both flows mask already: the generator call is the difference)
   float* g_src = ws.f((size_t)B * gin);
   float* g_tgt = ws.f((size_t)B * gin);
   T3 MQ = m_q ? ext(m_q, inter, T) : ws.t3(B, inter, T);
@@ -1768,6 +1847,22 @@ int vsp_generator(vsp_ctx* ctx, void* stream, int B, int T, const float* z, cons
   Run r{ctx, (hipStream_t)stream, ws};
   run_gen(r, B, T, ext(z, ctx->cfg.inter_channels, T), nullptr, g, o);
   if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "generator workspace too small (need %zu bytes)", ws.cur);
+  return r.rc;
+}
+
+int vsp_generator_ragged(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g, const int64_t* lengths,
+                         float* o, void* workspace, int64_t workspace_bytes) {
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  if (B <= 0 || T <= 0 || !z || !g || !lengths || !o || !workspace) return ctx->fail(VSP_ERR_ARG, "vsp_generator_ragged: bad argument");
+  const int64_t need = vsp_generator_workspace_bytes(ctx, B, T) + (int64_t)B * (int64_t)sizeof(int);
+  if (workspace_bytes < need)
+    return ctx->fail(VSP_ERR_WORKSPACE, "ragged generator workspace too small (need %lld bytes)", (long long)need);
+  Ws ws(workspace, (size_t)workspace_bytes, false);
+  Run r{ctx, (hipStream_t)stream, ws};
+  r.iso = true;
+  run_gen(r, B, T, ext(z, ctx->cfg.inter_channels, T), lengths, g, o);
+  if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "ragged generator workspace too small (need %zu bytes)", ws.cur);
   return r.rc;
 }
 

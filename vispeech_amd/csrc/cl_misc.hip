@@ -177,4 +177,43 @@ hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, con
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Isolated mode (kernels.h): the per-utterance extent is the utterance's own length, and the padded rest of the
+// waveform is zero.
+__global__ void gen_plan_isolated_kernel(const int64_t* __restrict__ lengths, int B, int T, int* __restrict__ glen) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long len = lengths[b];
+  glen[b] = len < 1 ? 1 : (len < T ? (int)len : T);
+}
+hipError_t launch_gen_plan_isolated(const int64_t* lengths, int B, int T, int* glen, hipStream_t s) {
+  if (!lengths || !glen || B <= 0 || T <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gen_plan_isolated_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lengths, B, T, glen);
+  return hipGetLastError();
+}
+// One 16-byte store per thread over the padded waveform (grid.x covers n = T * up samples, grid.y = utterance); a piece
+// that straddles the utterance's end, the tensor's end, or sits on an unaligned row goes sample by sample.
+__global__ void __launch_bounds__(256) gen_tail_zero_kernel(float* __restrict__ o, long o_bs, const int64_t* __restrict__ lengths,
+                                                            int T, int up) {
+  const int b = blockIdx.y;
+  long len = lengths[b];
+  len = len < 0 ? 0 : (len < T ? len : T);
+  const long start = len * up, n = (long)T * up;
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i + 4 <= start || i >= n) return;
+  float* ob = o + (size_t)b * o_bs;
+  if (i >= start && i + 4 <= n && (reinterpret_cast<uintptr_t>(ob + i) & 15) == 0) {
+    *reinterpret_cast<float4*>(ob + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const long lo = i > start ? i : start, hi = i + 4 < n ? i + 4 : n;
+  for (long k = lo; k < hi; ++k) ob[k] = 0.f;
+}
+hipError_t launch_gen_tail_zero(float* o, long o_bs, const int64_t* lengths, int B, int T, int up, hipStream_t s) {
+  if (!o || !lengths || B <= 0 || T <= 0 || up <= 0) return hipErrorInvalidValue;
+  const long quads = ((long)T * up + 3) / 4;
+  hipLaunchKernelGGL(gen_tail_zero_kernel, dim3((unsigned)((quads + 255) / 256), B), dim3(256), 0, s, o, o_bs, lengths, T, up);
+  return hipGetLastError();
+}
+
 }  // namespace vsp

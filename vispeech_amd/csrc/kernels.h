@@ -296,6 +296,13 @@ hipError_t launch_conv_post_cl(const float* x, long x_bs, int x_ts, const float*
 hipError_t launch_gen_plan(const int64_t* lengths, int B, int T, int back, int fwd, int* glen, hipStream_t s);
 hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, const int* glen, int B, int T, int back, int fwd,
                                 int up, hipStream_t s);
+// Isolated mode (round 10; include/vispeech_hip.h, vsp_set_isolated): every utterance of a batch as a B = 1 call on its
+// own unpadded tensors computes it.  The generator then ENDS utterance b's tensor at its own length -- the same per-utterance
+// extent as above with no frames behind the utterance -- and the padded rest of the waveform is zero.
+//   gen_plan_isolated:  glen[b] = clamp(lengths[b], 1, T) (an empty utterance computes one frame, which gen_tail_zero erases);
+//   gen_tail_zero:      o[b][clamp(lengths[b], 0, T) * up .. T * up) = 0.
+hipError_t launch_gen_plan_isolated(const int64_t* lengths, int B, int T, int* glen, hipStream_t s);
+hipError_t launch_gen_tail_zero(float* o, long o_bs, const int64_t* lengths, int B, int T, int up, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // attention with windowed relative position (reference attentions.py:148-179), f32 MFMA.
@@ -357,9 +364,18 @@ hipError_t launch_reparam(const float* m_p, const float* logs_p, const float* no
 // out[i] = standard normal draw first + i of the Philox4x32-10 stream keyed by `seed` (misc.hip)
 hipError_t launch_randn(uint64_t seed, long first, long n, float* out, hipStream_t s);
 hipError_t launch_mask_u8(const int64_t* lengths, uint8_t* mask, int B, int T, hipStream_t s);
-// o[b][t] = tanh( sum_c sum_j w[c][j] * lrelu(x[b][c][t+j-pad], slope) )  (conv_post, no bias)
+// isolated mode: out[b][c][t] = t < L ? element c * L + t of the Philox stream keyed seeds[b] : 0, L = max(row_len[b], 0) --
+// the [C][L] tensor launch_randn(seeds[b], 0, C * L) draws for utterance b alone, inside a [B][C][T] batch tensor
+hipError_t launch_randn_ragged(const uint64_t* seeds, const int64_t* row_len, int B, int C, int T, float* out, hipStream_t s);
+// p_k[b][t] = 0 for t >= lengths[b], k < 4 ([B][T] tensors; NULL entries skipped): the phoneme-rate signals of isolated mode
+hipError_t launch_mask_rows(const int64_t* lengths, int B, int T, float* p0, float* p1, float* p2, float* p3, hipStream_t s);
+// out[i][b] = max(lengths[b], 0) * rate[i], i < n <= 9: an utterance's extent at every stage rate of the channel-major generator
+hipError_t launch_stage_lengths(const int64_t* lengths, int B, const long* rate, int n, int64_t* out, hipStream_t s);
+// o[b][t] = tanh( sum_c sum_j w[c][j] * lrelu(x[b][c][t+j-pad], slope) )  (conv_post, no bias); tlen != NULL: utterance b's
+// tensor ends at min(T, tlen[b]) -- nothing behind it is read or written
 hipError_t launch_conv_post(const float* x, long x_bs, long x_cs, const float* w, int C, int K, float slope,
-                            float* o, long o_bs, int B, int T, hipStream_t s, unsigned* flags = nullptr);
+                            float* o, long o_bs, int B, int T, hipStream_t s, unsigned* flags = nullptr,
+                            const int64_t* tlen = nullptr);
 hipError_t launch_copy3(const float* x, long x_bs, long x_cs, float* y, long y_bs, long y_cs, int B, int C,
                         int T, hipStream_t s);
 // x[b][c][t] = 0 for t >= lengths[b]

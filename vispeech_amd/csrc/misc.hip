@@ -437,6 +437,72 @@ hipError_t launch_randn(uint64_t seed, long first, long n, float* out, hipStream
   return hipGetLastError();
 }
 
+// Isolated mode (kernels.h): utterance b's own [C][L_b] draw inside the padded [B][C][T] tensor.  One element per thread
+// (the four words of a counter are computed by up to four threads: a row of L_b elements does not start on a counter
+// boundary); same Philox / Box-Muller arithmetic as randn_kernel.
+__global__ void __launch_bounds__(256) randn_ragged_kernel(const uint64_t* __restrict__ seeds, const int64_t* __restrict__ row_len,
+                                                           int C, int T, long n, float* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long ct = (long)C * T;
+  const int b = (int)(i / ct);
+  const long r = i - (long)b * ct;
+  const int c = (int)(r / T), t = (int)(r - (long)c * T);
+  long L = row_len[b];
+  L = L < 0 ? 0 : L;
+  if (t >= L) { out[i] = 0.f; return; }
+  const long e = (long)c * L + t, q = e >> 2;
+  const int j = (int)(e & 3), p = j >> 1;
+  const uint64_t seed = seeds[b];
+  uint32_t w[4];
+  philox4x32_10((uint32_t)(q & 0xffffffffu), (uint32_t)((unsigned long)q >> 32), 0u, 0u, (uint32_t)(seed & 0xffffffffu),
+                (uint32_t)(seed >> 32), w);
+  const float u1 = ((float)(w[2 * p] >> 9) + 0.5f) * (1.f / 8388608.f);
+  const float u2 = ((float)(w[2 * p + 1] >> 9) + 0.5f) * (1.f / 8388608.f);
+  const float rad = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  out[i] = (j & 1) ? rad * sn : rad * cs;
+}
+hipError_t launch_randn_ragged(const uint64_t* seeds, const int64_t* row_len, int B, int C, int T, float* out, hipStream_t s) {
+  if (!seeds || !row_len || !out || B <= 0 || C <= 0 || T <= 0) return hipErrorInvalidValue;
+  const long n = (long)B * C * T;
+  hipLaunchKernelGGL(randn_ragged_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, seeds, row_len, C, T, n, out);
+  return hipGetLastError();
+}
+
+__global__ void mask_rows_kernel(const int64_t* __restrict__ lengths, int T, float* __restrict__ p0, float* __restrict__ p1,
+                                 float* __restrict__ p2, float* __restrict__ p3) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (t >= T || t < lengths[b]) return;
+  const size_t i = (size_t)b * T + t;
+  if (p0) p0[i] = 0.f;
+  if (p1) p1[i] = 0.f;
+  if (p2) p2[i] = 0.f;
+  if (p3) p3[i] = 0.f;
+}
+hipError_t launch_mask_rows(const int64_t* lengths, int B, int T, float* p0, float* p1, float* p2, float* p3, hipStream_t s) {
+  if (!lengths || B <= 0 || T <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_rows_kernel, dim3(cdiv(T, 64), B), dim3(64), 0, s, lengths, T, p0, p1, p2, p3);
+  return hipGetLastError();
+}
+
+struct StageRates { long r[9]; };
+__global__ void stage_lengths_kernel(const int64_t* __restrict__ lengths, int B, StageRates rates, int n, int64_t* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  long len = lengths[b];
+  len = len < 0 ? 0 : len;
+  for (int i = 0; i < n; ++i) out[(size_t)i * B + b] = len * rates.r[i];
+}
+hipError_t launch_stage_lengths(const int64_t* lengths, int B, const long* rate, int n, int64_t* out, hipStream_t s) {
+  if (!lengths || !rate || !out || B <= 0 || n < 1 || n > 9) return hipErrorInvalidValue;
+  StageRates r{};
+  for (int i = 0; i < n; ++i) r.r[i] = rate[i];
+  hipLaunchKernelGGL(stage_lengths_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, lengths, B, r, n, out);
+  return hipGetLastError();
+}
+
 __global__ void mask_u8_kernel(const int64_t* __restrict__ lengths, uint8_t* __restrict__ mask, int T) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
   if (t >= T) return;
@@ -457,12 +523,17 @@ constexpr int CP_MAXK = 8;
 __global__ void __launch_bounds__(128) conv_post_kernel(const float* __restrict__ x, long x_bs, long x_cs,
                                                         const float* __restrict__ w, int C, int K, float slope,
                                                         float* __restrict__ o, long o_bs, int T,
-                                                        unsigned* __restrict__ flags) {
+                                                        unsigned* __restrict__ flags, const int64_t* __restrict__ tlen) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int LW = CP_TILE + 8;
   float* xs = sm;            // [C][LW]
   float* ws = sm + C * LW;   // [C][CP_MAXK]
   const int b = blockIdx.y, t0 = blockIdx.x * CP_TILE, pad = (K - 1) / 2;
+  if (tlen) {                // isolated mode: this utterance's tensor ends at its own length
+    const long l = tlen[b];
+    T = l < T ? (l < 0 ? 0 : (int)l) : T;
+    if (t0 >= T) return;     // (uniform: before the barrier)
+  }
   const float* xb = x + (size_t)b * x_bs;
   for (int idx = threadIdx.x; idx < C * CP_MAXK; idx += 128) {
     const int c = idx / CP_MAXK, j = idx % CP_MAXK;
@@ -504,14 +575,14 @@ __global__ void __launch_bounds__(128) conv_post_kernel(const float* __restrict_
   }
 }
 hipError_t launch_conv_post(const float* x, long x_bs, long x_cs, const float* w, int C, int K, float slope,
-                            float* o, long o_bs, int B, int T, hipStream_t s, unsigned* flags) {
+                            float* o, long o_bs, int B, int T, hipStream_t s, unsigned* flags, const int64_t* tlen) {
   // (C <= 64: the staged tile + weights, (64 * 520 + 64 * 8) * 4 = 135168 B, fit the 140 KiB requested below)
   if (K > CP_MAXK || C < 1 || C > 64) return hipErrorInvalidValue;
   const size_t lds = ((size_t)C * (CP_TILE + 8) + (size_t)C * CP_MAXK) * sizeof(float);
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(conv_post_kernel), 140 * 1024, attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL(conv_post_kernel, dim3(cdiv(T, CP_TILE), B), dim3(128), lds, s, x, x_bs, x_cs, w, C, K, slope,
-                     o, o_bs, T, flags);
+                     o, o_bs, T, flags, tlen);
   return hipGetLastError();
 }
 

@@ -166,6 +166,11 @@ struct vsp_ctx {
   float* out_tab = nullptr;
   int out_L = 0, out_M = 0, out_H = 0, out_J = 0, out_P = 0;
   int64_t noise_first = 0;        // stream index of element 0 of a library-drawn noise tensor (vsp_set_noise_offset)
+  // Isolated mode (vsp_set_isolated, round 10): every utterance of a batch as a B = 1 call on its own unpadded inputs
+  // computes it -- masks where the reference applies none, the generator's tensors ending at the utterance's own length,
+  // and per-utterance noise keys (vsp_set_noise_seeds; noise_first is then ignored).  Off: the reference's padded batch.
+  bool isolated = false;
+  std::vector<uint64_t> noise_seeds;
   bool adopted_pending = false;   // an adopted arena whose header has not been checked yet (vsp_commit_adopted_weights)
   int gen_mode = 1;  // 0: f32 MFMA channel-major generator, 1: split-f16 (fp32-accurate) channels-last generator,
                      // 2: same kernels with plain f16 operands (VSP_GENERATOR=f16, opt-in reduced precision)

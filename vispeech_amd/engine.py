@@ -5,7 +5,7 @@ the current HIP stream); every arithmetic step runs in the library's kernels.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Mapping, Optional
+from typing import Dict, Mapping, Optional, Sequence
 
 import numpy as np
 import torch
@@ -143,9 +143,45 @@ class Engine:
     def _f(self, *shape) -> torch.Tensor:
         return torch.empty(shape, dtype=torch.float32, device=self.device)
 
+    # ------------------------------------------------------------------ isolated mode (vsp_set_isolated)
+    def set_isolated(self, on: bool) -> None:
+        """Sticky context state: every utterance of a batch as the reference computes it ALONE (include/vispeech_hip.h).
+        ``encode`` / ``decode`` / ``infer_padded`` / ``voice_conversion`` set it from their ``isolated`` argument on every
+        call, so a default call on a shared engine is never isolated by accident."""
+        _lib.check(self.lib.vsp_set_isolated(self.ctx, int(bool(on))), self.ctx, "vsp_set_isolated")
+
+    @property
+    def isolated(self) -> bool:
+        return bool(self.lib.vsp_get_isolated(self.ctx))
+
+    def set_noise_seeds(self, seeds: Optional[Sequence[int]]) -> None:
+        """``vsp_set_noise_seeds``: the Philox key of every utterance's own noise in isolated mode (None: forget them)."""
+        seeds = [] if seeds is None else [int(x) & (2**64 - 1) for x in seeds]
+        arr = (C.c_uint64 * max(len(seeds), 1))(*seeds)
+        _lib.check(self.lib.vsp_set_noise_seeds(self.ctx, arr, len(seeds)), self.ctx, "vsp_set_noise_seeds")
+
+    @staticmethod
+    def _isolated_seeds(isolated: bool, noise, noise_scale, noise_seed, B: int):
+        """(scalar seed for the C call, per-utterance seeds or None).  Isolated mode keys the noise per utterance: a plain
+        int would hand every utterance of the batch the same draw."""
+        if not isolated:
+            if noise_seed is not None and not isinstance(noise_seed, (int, np.integer)):
+                raise ValueError("a sequence of noise seeds needs isolated=True")
+            return noise_seed, None
+        if noise_seed is None:
+            if noise is None and float(noise_scale) != 0.0:
+                raise ValueError("isolated=True: pass noise or one noise_seed per utterance (noise_scale != 0)")
+            return 0, None
+        if isinstance(noise_seed, (int, np.integer)):
+            raise ValueError("isolated=True takes one noise_seed per utterance (a sequence of B ints), not a plain int")
+        seeds = [int(x) for x in noise_seed]
+        if len(seeds) != B:
+            raise ValueError(f"noise_seed must have {B} entries, got {len(seeds)}")
+        return 0, seeds
+
     # ------------------------------------------------------------------ the path
     def encode(self, phonemes, lengths, sid, duration_ctl=None, pitch_ctl=None, energy_ctl=None,
-               duration_scale=1.0, pitch_scale=1.0, energy_scale=1.0) -> Dict[str, torch.Tensor]:
+               duration_scale=1.0, pitch_scale=1.0, energy_scale=1.0, isolated: bool = False) -> Dict[str, torch.Tensor]:
         d = self.dims
         ph = _dev_i64(phonemes, self.device)
         ln = _dev_i64(lengths, self.device)
@@ -162,6 +198,7 @@ class Engine:
                    frame_lengths=torch.empty(B, dtype=torch.int64, device=self.device),
                    cum_dur=torch.empty(B, Tp, dtype=torch.int32, device=self.device))
         ws = self._workspace("encode", self.lib.vsp_encode_workspace_bytes(self.ctx, B, Tp))
+        self.set_isolated(isolated)
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_encode(self.ctx, self._stream(), B, Tp, _ptr(ph), _ptr(ln), _ptr(sd), _ptr(dc), _ptr(pc),
                                      _ptr(ec), float(duration_scale), float(pitch_scale), float(energy_scale),
@@ -221,18 +258,21 @@ class Engine:
         return dict(Tf=int(Tf), Tdec=Tdec, o_buf=o_buf, out=out, ws=ws, max_len=max_len)
 
     def decode(self, enc: Mapping[str, torch.Tensor], Tf: int, noise: Optional[torch.Tensor], noise_scale: float,
-               max_len: Optional[int] = None, noise_seed: Optional[int] = None, bufs=None,
-               noise_offset: int = 0) -> Dict[str, torch.Tensor]:
+               max_len: Optional[int] = None, noise_seed=None, bufs=None,
+               noise_offset: int = 0, isolated: bool = False) -> Dict[str, torch.Tensor]:
         """``noise`` None with ``noise_scale`` != 0: the library draws it on the device -- elements ``noise_offset`` ..
         of ``vsp_randn(noise_seed)``; the caller must then name the seed (a silent default would hand out the same
         "random" sample on every call).  ``noise_offset``: a shard [lo, hi) of a global batch passes lo * inter * Tf so
         that its utterances get the noise they would get unsharded.
-        ``bufs``: a ``decode_buffers`` result for the same ``Tf`` / ``max_len`` (else allocated here)."""
+        ``bufs``: a ``decode_buffers`` result for the same ``Tf`` / ``max_len`` (else allocated here).
+        ``isolated``: every utterance as the reference computes it alone; ``noise_seed`` is then a sequence of B ints, one
+        key per utterance (``vsp_set_noise_seeds``), and ``noise_offset`` is not read."""
+        B, _, Tp = enc["x_var"].shape
+        noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
         if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
             raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
         noise_seed = 0 if noise_seed is None else noise_seed
         d = self.dims
-        B, _, Tp = enc["x_var"].shape
         inter = d.inter_channels
         if bufs is None or bufs["Tf"] != int(Tf) or bufs["max_len"] != max_len:
             bufs = self.decode_buffers(B, Tp, Tf, max_len)
@@ -241,6 +281,9 @@ class Engine:
             noise = _dev_f32(noise, self.device)
             if tuple(noise.shape) != (B, inter, Tf):
                 raise ValueError(f"noise must be [{B},{inter},{Tf}], got {tuple(noise.shape)}")
+        self.set_isolated(isolated)
+        if isolated:
+            self.set_noise_seeds(seeds)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_decode(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,
@@ -256,16 +299,17 @@ class Engine:
     # ------------------------------------------------------------------ per-stage entry points
     def infer_padded(self, phonemes, lengths, sid, tf_pad: int, noise, noise_scale: float = 1.0, max_len=None,
                      duration_ctl=None, pitch_ctl=None, energy_ctl=None, duration_scale: float = 1.0,
-                     pitch_scale: float = 1.0, energy_scale: float = 1.0, noise_seed: Optional[int] = None,
-                     noise_offset: int = 0) -> Dict[str, torch.Tensor]:
+                     pitch_scale: float = 1.0, energy_scale: float = 1.0, noise_seed=None,
+                     noise_offset: int = 0, isolated: bool = False) -> Dict[str, torch.Tensor]:
         """``vsp_infer``: the whole path in ONE call and without the host read of the frame counts, for
         callers that know an upper bound ``tf_pad`` of the frame count (supplied durations / fixed max_len).
-        ``noise`` None with ``noise_scale`` != 0 needs an explicit ``noise_seed`` (see ``decode``)."""
+        ``noise`` None with ``noise_scale`` != 0 needs an explicit ``noise_seed`` (see ``decode``, also for ``isolated``)."""
+        ph = _dev_i64(phonemes, self.device)
+        B, Tp = ph.shape
+        noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
         if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
             raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
         noise_seed = 0 if noise_seed is None else noise_seed
-        ph = _dev_i64(phonemes, self.device)
-        B, Tp = ph.shape
         ln, sd = _dev_i64(lengths, self.device), _dev_i64(sid, self.device)
         ctl = [None if t is None else _dev_f32(t, self.device).reshape(B, Tp) for t in (duration_ctl, pitch_ctl, energy_ctl)]
         Tf = int(tf_pad)
@@ -283,6 +327,9 @@ class Engine:
         dur, f0, en = (self._f(B, Tp) for _ in range(3))
         fl = torch.empty(B, dtype=torch.int64, device=self.device)
         ws = self._workspace("infer", self.lib.vsp_infer_workspace_bytes(self.ctx, B, Tp, Tf))
+        self.set_isolated(isolated)
+        if isolated:
+            self.set_noise_seeds(seeds)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_infer(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,
@@ -440,7 +487,7 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_posterior_encoder")
         return z, m, logs
 
-    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, noise) -> Dict[str, torch.Tensor]:
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, noise, isolated: bool = False) -> Dict[str, torch.Tensor]:
         """SynthesizerTrn.voice_conversion (reference models.py:724-732); ``noise`` [B,inter,T] is the
         ``torch.randn_like`` of the posterior encoder (models.py:240)."""
         y = _dev_f32(y, self.device)
@@ -456,6 +503,7 @@ class Engine:
         z, z_p, z_hat, m_q, logs_q = (self._f(B, inter, T) for _ in range(5))
         y_mask = torch.empty((B, 1, T), dtype=torch.uint8, device=self.device)
         ws = self._workspace("vc", self.lib.vsp_voice_conversion_workspace_bytes(self.ctx, B, T))
+        self.set_isolated(isolated)
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_voice_conversion(self.ctx, self._stream(), B, T, _ptr(y), _ptr(yl), _ptr(ss), _ptr(st),
                                                _ptr(noise), _ptr(o), _ptr(y_mask), _ptr(z), _ptr(z_p), _ptr(z_hat),
@@ -472,6 +520,23 @@ class Engine:
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_generator(self.ctx, self._stream(), B, T, _ptr(z), _ptr(g), _ptr(o), _ptr(ws), ws.numel())
         _lib.check(rc, self.ctx, "vsp_generator")
+        return o
+
+    def generator_ragged(self, z, g, lengths) -> torch.Tensor:
+        """``vsp_generator_ragged``: the generator with per-utterance ends -- utterance b's first ``lengths[b]`` frames of
+        waveform are what ``generator(z[b:b+1, :, :lengths[b]], g[b:b+1])`` returns, the rest of its row is 0."""
+        z = _dev_f32(z, self.device)
+        g = _dev_f32(g, self.device).reshape(z.shape[0], -1)
+        ln = _dev_i64(lengths, self.device)
+        B, _, T = z.shape
+        if ln.numel() != B:
+            raise ValueError(f"lengths must have {B} entries")
+        o = self._f(B, 1, T * self.dims.total_upsample)
+        ws = self._workspace("generator", self.lib.vsp_generator_workspace_bytes(self.ctx, B, T) + 4 * B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_generator_ragged(self.ctx, self._stream(), B, T, _ptr(z), _ptr(g), _ptr(ln), _ptr(o), _ptr(ws),
+                                               ws.numel())
+        _lib.check(rc, self.ctx, "vsp_generator_ragged")
         return o
 
     @property

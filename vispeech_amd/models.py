@@ -105,11 +105,13 @@ class SynthesizerTrn:
         raise NotImplementedError("SynthesizerTrn.forward is the training path (reference models.py:624-670): out of scope")
 
     @torch.no_grad()
-    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, *, noise: Optional[torch.Tensor] = None):
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, *, noise: Optional[torch.Tensor] = None,
+                         isolated: bool = False):
         """Reference models.py:724-732: posterior encoder on the linear spectrogram ``y``
         [B, spec_channels, T] with the source speaker, flow forward (source), flow reverse (target),
         generator (target).  ``noise`` (keyword-only, optional) replaces the ``torch.randn_like`` of
-        the posterior encoder (models.py:240).  Returns ``(o_hat, y_mask, (z, z_p, z_hat))``; needs the
+        the posterior encoder (models.py:240).  ``isolated``: as in ``infer`` -- the vocoder ends every utterance's tensors at
+        its own length.  Returns ``(o_hat, y_mask, (z, z_p, z_hat))``; needs the
         ``enc_q.*`` tensors in the loaded state_dict."""
         eng = self._engine
         if not eng.ready:
@@ -120,7 +122,8 @@ class SynthesizerTrn:
         B, _, T = y.shape
         if noise is None:
             noise = torch.randn(B, self.dims.inter_channels, T, dtype=torch.float32, device=eng.device)
-        r = eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, noise)
+        # (the keyword is passed only when set: engine stand-ins of older callers and tests need not know it)
+        r = eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, noise, **({"isolated": True} if isolated else {}))
         return r["o_hat"], r["y_mask"].to(torch.float32), (r["z"], r["z_p"], r["z_hat"])
 
     def __call__(self, *a, **k):
@@ -130,13 +133,18 @@ class SynthesizerTrn:
     @torch.no_grad()
     def infer(self, phonemes, phonemes_lengths, sid=None, noise_scale=1, max_len=None, energy_control=None,
               pitch_control=None, duration_control=None, *, noise: Optional[torch.Tensor] = None,
-              t_f: Optional[int] = None, noise_seed: Optional[int] = None, noise_offset: int = 0):
+              t_f: Optional[int] = None, noise_seed=None, noise_offset: int = 0, isolated: bool = False):
         """Reference models.py:672-722.  ``noise`` (keyword-only, optional) replaces the
         ``torch.randn_like`` draw of models.py:718 so runs can be reproduced; without it the draw is
         ``torch.randn`` on the GPU (torch's generator, as in the reference) unless ``noise_seed`` is given: then the
         library draws it itself (``vsp_randn``, what a C caller gets) from stream element ``noise_offset`` on (a shard
         [lo, hi) of a global batch passes lo * inter_channels * t_f: same noise as unsharded).  ``t_f`` pads the frame
-        axis to a global maximum for sharded batches (SURVEY gotcha G6).  Returns
+        axis to a global maximum for sharded batches (SURVEY gotcha G6).
+        ``isolated`` (off by default: the reference's padded call, bit-compatible): every returned tensor, restricted to
+        utterance b's own extent, is what the reference returns for a B = 1 call on that utterance's unpadded inputs --
+        independent of the batch it shares -- and exactly 0 behind the extent.  ``noise_seed`` is then a sequence of B
+        ints, one Philox key per utterance (a plain int raises: it would hand every utterance the same draw), and
+        ``noise_offset`` is not read.  Returns
         ``(o, x_mask, (z, z_p, m_p, logs_p), duration, F0, energy)``."""
         eng = self._engine
         if not eng.ready:
@@ -153,7 +161,11 @@ class SynthesizerTrn:
         d_t, d_s = split(duration_control)
         p_t, p_s = split(pitch_control)
         e_t, e_s = split(energy_control)
-        enc = eng.encode(phonemes, phonemes_lengths, sid, d_t, p_t, e_t, d_s, p_s, e_s)
+        # (the keyword is passed only when set: engine stand-ins of older callers and tests need not know it)
+        iso = {"isolated": True} if isolated else {}
+        no_seed = noise_seed is None                     # the caller named no seed: torch draws the noise, in either mode
+        noise_seed, seeds = eng._isolated_seeds(bool(isolated), noise, 0.0, noise_seed, B)
+        enc = eng.encode(phonemes, phonemes_lengths, sid, d_t, p_t, e_t, d_s, p_s, e_s, **iso)
         # (a known padding: the second half's tensors are allocated while the GPU is still busy with the first)
         bufs = eng.decode_buffers(B, Tp, int(t_f), max_len) if t_f is not None and int(t_f) > 0 else None
         _, tf_local = eng.frame_lengths_host(enc["frame_lengths"])
@@ -161,10 +173,10 @@ class SynthesizerTrn:
         if Tf <= 0:
             raise ValueError("all durations are zero: nothing to synthesise")
         ns = float(noise_scale)
-        if noise is None and ns != 0.0 and noise_seed is None:
+        if noise is None and ns != 0.0 and no_seed:
             noise = torch.randn(B, self.dims.inter_channels, Tf, dtype=torch.float32, device=eng.device)
-        dec = eng.decode(enc, Tf, noise, ns, max_len, noise_seed=0 if noise_seed is None else int(noise_seed), bufs=bufs,
-                         noise_offset=int(noise_offset))
+        dec = eng.decode(enc, Tf, noise, ns, max_len, noise_seed=seeds if isolated else (0 if noise_seed is None else int(noise_seed)),
+                         bufs=bufs, noise_offset=int(noise_offset), **iso)
         duration = duration_control if d_t is not None else enc["duration"].view(B, 1, Tp)
         return (dec["o"], dec["x_mask"], (dec["z"], dec["z_p"], dec["m_p"], dec["logs_p"]), duration, enc["F0"],
                 enc["energy"])

@@ -14,6 +14,9 @@ from __future__ import annotations
 import io
 import threading
 import wave
+import concurrent.futures
+import queue
+import time
 from typing import Dict, Iterator, Optional, Sequence
 
 import numpy as np
@@ -81,8 +84,10 @@ class SynthesisService:
     """One model, one synthesis at a time, never queueing (reference inference_api.py:13, 37)."""
 
     def __init__(self, net, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667, stream=None,
-                 *, output_rate: Optional[int] = None, device_pcm: bool = False):
-        """``output_rate``: deliver PCM16 at this rate instead of the model's -- the reference's service sends the
+                 *, output_rate: Optional[int] = None, device_pcm: bool = False, isolated: bool = False):
+        """``isolated``: run every batch in isolated mode (``SynthesizerTrn.infer(isolated=True)``): an utterance's audio is
+        what the reference returns for it alone, whatever it is batched with.
+        ``output_rate``: deliver PCM16 at this rate instead of the model's -- the reference's service sends the
         22.05 kHz file that ``ffmpeg -ar 22050`` makes of the waveform (inference_api.py:51); here the engine's output
         stage resamples and quantises on the GPU, one-shot and per streamed chunk, and int16 is what crosses to the
         host.  ``device_pcm=True`` without a rate: the same stage as a pass-through (GPU quantisation at the model's
@@ -91,6 +96,9 @@ class SynthesisService:
         self.sampling_rate = int(sampling_rate)
         self.chunk_frames = int(chunk_frames)
         self.noise_scale = float(noise_scale)
+        self.isolated = bool(isolated)
+        # (passed only when set: engine / net stand-ins of older callers and tests need not know the keyword)
+        self._iso = {"isolated": True} if self.isolated else {}
         self._lock = threading.Lock()
         self._stream = stream          # a torch.cuda.Stream all of this service's GPU work runs on (None: the caller's)
         self.output_rate = None if output_rate is None else int(output_rate)
@@ -185,9 +193,14 @@ class SynthesisService:
             enc, frames, tf = self._encode(batch)
             z_noise = noise if noise is not None else torch.randn(
                 enc["x_var"].shape[0], net.dims.inter_channels, tf, dtype=torch.float32, device=eng.device)
-            dec = eng.decode(enc, tf, z_noise, self.noise_scale, max_len=0)     # everything but the vocoder
-            chunks = eng.generator_stream(dec["z"], enc["g"], self.chunk_frames)
-        left = int(frames[utterance]) * net.dims.total_upsample
+            dec = eng.decode(enc, tf, z_noise, self.noise_scale, max_len=0, **self._iso)     # everything but the vocoder
+            left = int(frames[utterance]) * net.dims.total_upsample
+            if self.isolated:
+                # the utterance's own frames: a tensor that really ends where the isolated batch's ended artificially
+                u, utterance = utterance, 0
+                chunks = eng.generator_stream(dec["z"][u:u + 1, :, :int(frames[u])], enc["g"][u:u + 1], self.chunk_frames)
+            else:
+                chunks = eng.generator_stream(dec["z"], enc["g"], self.chunk_frames)
         if self._output_stage:
             yield from self._stream_output_stage(chunks, utterance, left)
             return
@@ -240,7 +253,7 @@ class SynthesisService:
         c = self._controls(batch)
         t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
         enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(c["duration"]), t(c["f0"]),
-                         t(c["energy"]))
+                         t(c["energy"]), **self._iso)
         frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
         if tf <= 0:
             raise ValueError("all durations are zero: nothing to synthesise")
@@ -253,7 +266,7 @@ class SynthesisService:
         t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
         o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]),
                                   noise_scale=self.noise_scale, duration_control=t(c["duration"]),
-                                  pitch_control=t(c["f0"]), energy_control=t(c["energy"]), noise=noise)
+                                  pitch_control=t(c["f0"]), energy_control=t(c["energy"]), noise=noise, **self._iso)
         return o, x_mask.sum(dim=(1, 2)).cpu().tolist()
 
 
@@ -265,9 +278,9 @@ class PooledSynthesisService:
     single-utterance request at 1 / 2 / 3 slots (profiles/r06_batches_in_flight.txt)."""
 
     def __init__(self, pool, sampling_rate: int = 44100, chunk_frames: int = 64, noise_scale: float = 0.667, *,
-                 output_rate: Optional[int] = None, device_pcm: bool = False):
+                 output_rate: Optional[int] = None, device_pcm: bool = False, isolated: bool = False):
         self.slots = [SynthesisService(net, sampling_rate, chunk_frames, noise_scale, stream=st, output_rate=output_rate,
-                                       device_pcm=device_pcm)
+                                       device_pcm=device_pcm, isolated=isolated)
                       for net, st in zip(pool.nets, pool.streams if pool.streams[0] is not None else [None] * len(pool.nets))]
 
     @property
@@ -295,3 +308,94 @@ class PooledSynthesisService:
             except Busy:
                 continue
         raise Busy("every synthesis slot is taken")
+
+
+class BatchingSynthesisService:
+    """Requests from many callers, synthesised together (round 10).  The services above refuse a request while another is in
+    flight, because in the reference's padded batch an utterance's audio depends on its batch-mates; in ISOLATED mode it
+    does not, so requests can share a batch: ``submit`` queues one ``collate_rows`` row with its own noise seed and
+    returns a future of its PCM16; one worker thread collects up to ``max_batch`` requests -- waiting at most
+    ``max_wait_s`` after the first -- collates them and runs ONE ``net.infer(..., isolated=True)`` with the requests' seeds.
+    A failing batch fails its own futures and nothing else.  No retry, no priority.
+    ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays)."""
+
+    def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
+                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100):
+        if max_batch < 1 or max_wait_s < 0:
+            raise ValueError("max_batch >= 1 and max_wait_s >= 0")
+        if collate is None:
+            if table is None or spk2id is None:
+                raise ValueError("pass table and spk2id (for collate_rows) or a collate callable")
+            from .text import collate_rows
+            collate = lambda rows: collate_rows(rows, table, spk2id)
+        self._collate = collate
+        self.net, self.max_batch, self.max_wait_s = net, int(max_batch), float(max_wait_s)
+        self.noise_scale = float(noise_scale)
+        self.output_rate = None if output_rate is None else int(output_rate)
+        if self.output_rate is not None:
+            net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
+        self._q: "queue.Queue" = queue.Queue()
+        self._closed = False
+        self._gate = threading.Lock()        # orders submit's check + put against close's sentinel: nothing queues behind it
+        self._worker = threading.Thread(target=self._run, name="vispeech-batching", daemon=True)
+        self._worker.start()
+
+    def submit(self, row, noise_seed: int) -> "concurrent.futures.Future":
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The future's
+        result is the request's PCM16 samples (numpy int16, valid part only)."""
+        fut: "concurrent.futures.Future" = concurrent.futures.Future()
+        with self._gate:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            self._q.put((row, int(noise_seed), fut))
+        return fut
+
+    def close(self) -> None:
+        """Serve what is queued, then stop the worker and join it."""
+        with self._gate:
+            if not self._closed:
+                self._closed = True
+                self._q.put(None)
+        self._worker.join()
+
+    def _run(self) -> None:
+        stop = False
+        while not stop:
+            first = self._q.get()
+            if first is None:
+                break
+            reqs, deadline = [first], time.monotonic() + self.max_wait_s
+            while len(reqs) < self.max_batch:
+                try:
+                    nxt = self._q.get(timeout=max(deadline - time.monotonic(), 0.0))
+                except queue.Empty:
+                    break
+                if nxt is None:
+                    stop = True
+                    break
+                reqs.append(nxt)
+            reqs = [r for r in reqs if r[2].set_running_or_notify_cancel()]
+            if not reqs:
+                continue
+            try:
+                for (_, _, fut), pcm in zip(reqs, self._synthesize([r[0] for r in reqs], [r[1] for r in reqs])):
+                    fut.set_result(pcm)
+            except Exception as e:           # this batch's requests fail; the worker lives on
+                for _, _, fut in reqs:
+                    if not fut.done():
+                        fut.set_exception(e)
+
+    def _synthesize(self, rows, seeds):
+        import torch
+        net = self.net
+        batch = self._collate(rows)
+        t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
+        o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
+                                  duration_control=t(batch.get("duration")), pitch_control=t(batch.get("f0")),
+                                  energy_control=t(batch.get("energy")), noise_seed=list(seeds), isolated=True)
+        frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
+        hop = net.dims.total_upsample
+        if self.output_rate is None:
+            return [pcm16(o[b, 0, : int(frames[b]) * hop]) for b in range(len(rows))]
+        eng = net._engine
+        return [_host_i16(eng.output(o[b:b + 1, 0, : int(frames[b]) * hop], pcm=True)[0]) for b in range(len(rows))]

@@ -177,7 +177,9 @@ def infer_sharded(net, phonemes, lengths, sid, *, noise: Optional[torch.Tensor] 
     count without communication; otherwise it is the all-reduce MAX of the local maxima that
     ``net.infer`` reports.  With ``noise_seed`` in ``infer_kwargs`` instead of ``noise`` the library draws the noise: this
     rank then draws ITS utterances' part of the global [B, C, Tf] stream (``noise_offset`` = lo * C * Tf), so the
-    result does not depend on the shard layout.  Returns (o_full [B,1,S] on ``dst`` else None, local result tuple)."""
+    result does not depend on the shard layout.  ``isolated=True`` is forwarded to ``net.infer``; its per-utterance
+    ``noise_seed`` sequence is sliced like the tensors (no offset: an utterance's noise is keyed by its own seed), and the
+    global frame count then only sizes the gather -- an isolated utterance does not depend on its padding.  Returns (o_full [B,1,S] on ``dst`` else None, local result tuple)."""
     world = _world(group)
     rank = dist.get_rank(group) if _active() else 0
     B = phonemes.shape[0]
@@ -193,7 +195,10 @@ def infer_sharded(net, phonemes, lengths, sid, *, noise: Optional[torch.Tensor] 
     else:
         raise ValueError("pass frame_counts or noise so that all ranks pad to the same frame count")
     t_f = global_max(t_f, phonemes.device, group)
-    if noise is None and kw.get("noise_seed") is not None:
+    if kw.get("isolated") and kw.get("noise_seed") is not None and not isinstance(kw["noise_seed"], int):
+        seeds = infer_kwargs["noise_seed"]                # (the GLOBAL sequence: a [B] tensor was already sliced above)
+        kw["noise_seed"] = [int(x) for x in (seeds.tolist() if isinstance(seeds, torch.Tensor) else seeds)][lo:hi]
+    elif noise is None and kw.get("noise_seed") is not None:
         kw["noise_offset"] = lo * int(net.dims.inter_channels) * t_f
     out = net.infer(phonemes[sl], lengths[sl], sid=sid[sl], noise=None if noise is None else noise[sl], t_f=t_f, **kw)
     shards = gather_batch(out[0], dst=dst, group=group, counts=shard_counts(B, world))
