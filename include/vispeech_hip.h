@@ -292,6 +292,39 @@ int64_t vsp_generator_stream_workspace_bytes(const vsp_ctx* ctx, int B, int chun
 int vsp_generator_stream_chunk(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g, int f0, int f1,
                                float* o_chunk, void* workspace, int64_t workspace_bytes);
 
+/* Streaming for batched requests (ABI 7, additive; round 11): ONE set of generator launches advances up to 64 requests by one
+ * chunk each, every request at its own position of its own utterance.  Row b is frames [f0, f1) of an utterance of L frames
+ * whose latent is z[c * z_channel_stride + t], c < inter_channels, t < L (a DEVICE pointer: rows may point into different
+ * tensors); g is its speaker vector, gin_channels floats on the device.  The row's window is lo = max(0, f0 - halo),
+ * hi = min(L, f1 + halo), halo = vsp_generator_halo_frames().  The rows array itself is HOST memory, read before the call
+ * returns; it reaches the device as a kernel argument.
+ *
+ * vsp_generator_stream_rows writes to out[b][0 .. (f1 - f0) * up), up = prod(upsample_rates), the waveform samples
+ * [f0 * up, f1 * up) of what vsp_generator_ragged returns for a B = 1 call on z[:, :L] -- to the tolerance between two launch
+ * shapes of this library, not bit for bit: kernels are chosen by launch size -- as float32 (pcm == 0) or as int16 by the rule of
+ * vsp_output_chunk (pcm == 1); the rest of the row, out[b][(f1 - f0) * up .. out_stride), is exactly 0.  out [B][out_stride],
+ * out_stride in ELEMENTS; chunk_frames = out_stride / up is the longest chunk the call accepts.  How: one gather launch packs
+ * every row's z[:, lo:hi) (zero behind it), g and hi - lo; the generator runs on the packed tensor with per-utterance ends as
+ * in vsp_generator_ragged, so a row's tensors end at hi - lo in every stage -- the utterance's true end where hi == L, else an
+ * artificial end a full halo behind the last delivered frame, and the same on the left; one collect launch cuts, quantises
+ * and zero-fills.  No allocation, no synchronisation, everything on the caller's stream.
+ * Arguments, checked on the host before anything is launched: 1 <= B <= 64, 0 <= f0 < f1 <= L, f1 - f0 <= chunk_frames, z and
+ * g non-NULL, z_channel_stride >= L, pcm 0 or 1: VSP_ERR_ARG otherwise.  Workspace: vsp_generator_stream_rows_workspace_bytes
+ * for any chunk_frames >= the call's out_stride / up (VSP_ERR_WORKSPACE if too small): vsp_generator_workspace_bytes(B,
+ * chunk_frames + 2 halo) plus the packed z, the g rows, the lengths and the span waveform, each rounded to 256 bytes.
+ * vsp_stream_rows_plan is the same host arithmetic without a device (z and g are not read): lo[b], hi[b] (each may be NULL)
+ * and *span_max = max(hi - lo) (may be NULL); it checks B and every row's 0 <= f0 < f1 <= L. */
+typedef struct vsp_stream_row {
+  const float* z;
+  int64_t z_channel_stride;
+  const float* g;
+  int32_t L, f0, f1;
+} vsp_stream_row;
+int vsp_stream_rows_plan(const vsp_ctx* ctx, int B, const vsp_stream_row* rows, int32_t* lo, int32_t* hi, int32_t* span_max);
+int64_t vsp_generator_stream_rows_workspace_bytes(const vsp_ctx* ctx, int B, int chunk_frames);
+int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row* rows, void* out, int64_t out_stride,
+                              int pcm, void* workspace, int64_t workspace_bytes);
+
 /* ---- voice conversion: replaces SynthesizerTrn.voice_conversion (reference models.py:724-732) */
 /* Needs cfg.spec_channels > 0 and every enc_q.* tensor set before vsp_finalize_weights
  * (VSP_ERR_STATE otherwise).  y [B][spec][T] linear spectrogram, y_lengths[B], sid_src/sid_tgt[B]

@@ -40,6 +40,15 @@ class VspConfig(C.Structure):
     ]
 
 
+class VspStreamRow(C.Structure):
+    """``vsp_stream_row`` of include/vispeech_hip.h: frames [f0, f1) of an utterance of L frames whose latent is
+    ``z[c * z_channel_stride + t]`` (device pointer) with the speaker vector ``g`` (device pointer)."""
+    _fields_ = [("z", C.c_void_p), ("z_channel_stride", C.c_int64), ("g", C.c_void_p),
+                ("L", C.c_int32), ("f0", C.c_int32), ("f1", C.c_int32)]
+
+
+STREAM_ROWS_MAX = 64
+
 _P = C.c_void_p
 _I = C.c_int
 _I64 = C.c_int64
@@ -94,6 +103,10 @@ SIGNATURES = {
     "vsp_generator_frame_dependence": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "vsp_generator_stream_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_generator_stream_chunk": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I64]),
+    "vsp_stream_rows_plan": (_I, [_P, _I, C.POINTER(VspStreamRow), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32)]),
+    "vsp_generator_stream_rows_workspace_bytes": (_I64, [_P, _I, _I]),
+    "vsp_generator_stream_rows": (_I, [_P, _P, _I, C.POINTER(VspStreamRow), _P, _I64, _I, _P, _I64]),
     "vsp_flow_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I64]),
     "vsp_voice_conversion_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_voice_conversion": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64]),

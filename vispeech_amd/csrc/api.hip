@@ -1933,6 +1933,100 @@ int vsp_generator_stream_chunk(vsp_ctx* ctx, void* stream, int B, int T, const f
   return e == hipSuccess ? VSP_OK : ctx->fail(VSP_ERR_HIP, "stream chunk copy: %s", hipGetErrorString(e));
 }
 
+// Streaming for batched requests: every row its own window of its own utterance, one set of generator launches.
+int vsp_stream_rows_plan(const vsp_ctx* ctx, int B, const vsp_stream_row* rows, int32_t* lo, int32_t* hi, int32_t* span_max) {
+  if (!ctx || !rows || B < 1 || B > STREAM_ROWS_MAX) return VSP_ERR_ARG;
+  const int halo = vsp_generator_halo_frames(ctx);
+  int mx = 0;
+  for (int b = 0; b < B; ++b) {
+    const vsp_stream_row& r = rows[b];
+    if (r.f0 < 0 || r.f1 <= r.f0 || r.f1 > r.L) return VSP_ERR_ARG;
+    const int l = std::max(0, r.f0 - halo);
+    const int h = (int)std::min<int64_t>(r.L, (int64_t)r.f1 + halo);
+    if (lo) lo[b] = l;
+    if (hi) hi[b] = h;
+    mx = std::max(mx, h - l);
+  }
+  if (span_max) *span_max = mx;
+  return VSP_OK;
+}
+
+namespace {
+// the workspace of a stream_rows call whose longest window is `span` frames: [span waveform | packed z | g rows | lengths |
+// generator]; the packed z's row stride is span rounded up to 4 frames (every packed quad is one aligned 16-byte store)
+struct StreamRowsWs {
+  int64_t o_span, zp, gp, len, gen, total;
+  int S4;
+};
+inline int64_t r256(int64_t n) { return (n + 255) / 256 * 256; }
+bool stream_rows_ws(const vsp_ctx* ctx, int B, int span, StreamRowsWs& w) {
+  w.S4 = (span + 3) / 4 * 4;
+  const int64_t gen = vsp_generator_workspace_bytes(ctx, B, span);
+  if (gen < 0) return false;
+  w.o_span = 0;
+  w.zp = w.o_span + r256((int64_t)B * span * total_upsample(ctx->cfg) * (int64_t)sizeof(float));
+  w.gp = w.zp + r256((int64_t)B * ctx->cfg.inter_channels * w.S4 * (int64_t)sizeof(float));
+  w.len = w.gp + r256((int64_t)B * ctx->cfg.gin_channels * (int64_t)sizeof(float));
+  w.gen = w.len + r256((int64_t)B * (int64_t)sizeof(int64_t));
+  w.total = w.gen + gen;
+  return true;
+}
+}  // namespace
+
+int64_t vsp_generator_stream_rows_workspace_bytes(const vsp_ctx* ctx, int B, int chunk_frames) {
+  if (!ctx || B < 1 || B > STREAM_ROWS_MAX || chunk_frames <= 0) return VSP_ERR_ARG;
+  StreamRowsWs w;
+  if (!stream_rows_ws(ctx, B, chunk_frames + 2 * vsp_generator_halo_frames(ctx), w)) return VSP_ERR_ARG;
+  return w.total;
+}
+
+int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row* rows, void* out, int64_t out_stride,
+                              int pcm, void* workspace, int64_t workspace_bytes) {
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  const long up = total_upsample(ctx->cfg);
+  if (B < 1 || B > STREAM_ROWS_MAX || !rows || !out || !workspace || (pcm != 0 && pcm != 1) || out_stride < up)
+    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: bad argument (1 <= B <= %d, out_stride >= one frame)", STREAM_ROWS_MAX);
+  int32_t lo[STREAM_ROWS_MAX], hi[STREAM_ROWS_MAX], span = 0;
+  if (vsp_stream_rows_plan(ctx, B, rows, lo, hi, &span) != VSP_OK)
+    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: a row is not 0 <= f0 < f1 <= L");
+  const int64_t chunk_frames = out_stride / up;
+  StreamGatherRows gr;
+  StreamCollectRows cr;
+  int64_t span_len[STREAM_ROWS_MAX];
+  for (int b = 0; b < B; ++b) {
+    const vsp_stream_row& r = rows[b];
+    if (!r.z || !r.g || r.z_channel_stride < r.L || r.f1 - r.f0 > chunk_frames)
+      return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: row %d: null z / g, channel stride below L, or a chunk of "
+                                    "%d frames where out_stride holds %lld", b, r.f1 - r.f0, (long long)chunk_frames);
+    gr.r[b] = StreamGatherRow{r.z, (long)r.z_channel_stride, r.g, lo[b], hi[b]};
+    cr.r[b] = StreamCollectRow{(int)((r.f0 - lo[b]) * up), (int)((r.f1 - r.f0) * up)};
+    span_len[b] = hi[b] - lo[b];
+  }
+  StreamRowsWs w;
+  if (!stream_rows_ws(ctx, B, span, w) || workspace_bytes < w.total)
+    return ctx->fail(VSP_ERR_WORKSPACE, "stream rows workspace too small (need %lld bytes)", (long long)w.total);
+  char* const base = static_cast<char*>(workspace);
+  float* const o_span = reinterpret_cast<float*>(base + w.o_span);
+  float* const zp = reinterpret_cast<float*>(base + w.zp);
+  float* const gp = reinterpret_cast<float*>(base + w.gp);
+  int64_t* const len = reinterpret_cast<int64_t*>(base + w.len);
+  hipStream_t s = (hipStream_t)stream;
+  const int inter = ctx->cfg.inter_channels;
+  hipError_t e = launch_stream_gather(gr, B, inter, w.S4, ctx->cfg.gin_channels, zp, gp, len, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "stream_gather: %s", hipGetErrorString(e));
+  Ws ws(base + w.gen, (size_t)(workspace_bytes - w.gen), false);
+  Run r{ctx, s, ws};
+  r.iso = true;
+  // the host knows every window: a tick whose windows are all `span` frames long runs without per-utterance extents
+  r.host_lengths = span_len;
+  run_gen(r, B, span, T3{zp, (long)inter * w.S4, (long)w.S4}, len, gp, o_span);
+  if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "stream rows workspace too small (need %zu bytes)", (size_t)w.gen + ws.cur);
+  if (r.rc != VSP_OK) return r.rc;
+  e = launch_stream_collect(o_span, (long)span * up, cr, B, out, (long)out_stride, pcm, s);
+  return e == hipSuccess ? VSP_OK : ctx->fail(VSP_ERR_HIP, "stream_collect: %s", hipGetErrorString(e));
+}
+
 int vsp_rq_spline(void* stream, int64_t n, int nb, const float* x, const float* uw, const float* uh, const float* ud,
                   int inverse, float tail_bound, float* y, float* logabsdet) {
   if (n < 0 || !x || !uw || !uh || !ud || !y || !logabsdet) return VSP_ERR_ARG;

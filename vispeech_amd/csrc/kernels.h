@@ -384,6 +384,24 @@ hipError_t launch_rq_spline(int64_t n, int nb, const float* x, const float* uw, 
                             const float* ud, int inverse, float tail_bound, float* y, float* lad,
                             hipStream_t s);
 
+// Streaming for batched requests (stream_rows.hip; include/vispeech_hip.h, vsp_generator_stream_rows).  The per-row
+// descriptors are kernel ARGUMENTS (by value): no copy to the device, nothing to keep alive behind the launch.
+constexpr int STREAM_ROWS_MAX = 64;
+struct StreamGatherRow {     // 32 B: the window [lo, hi) of one utterance's latent z[c * cs + t] and its speaker vector
+  const float* z; long cs; const float* g; int lo, hi;
+};
+struct StreamGatherRows { StreamGatherRow r[STREAM_ROWS_MAX]; };
+struct StreamCollectRow { int off, n; };   // row b delivers samples [off, off + n) of its span waveform
+struct StreamCollectRows { StreamCollectRow r[STREAM_ROWS_MAX]; };
+// zp[b][c][t] = t < hi_b - lo_b ? z_b[c * cs_b + lo_b + t] : 0 for t < S4 (zp [B][C][S4], 16-byte aligned, S4 % 4 == 0,
+// every window <= S4);  gp[b][k] = g_b[k], k < gin;  len[b] = hi_b - lo_b.  One launch.
+hipError_t launch_stream_gather(const StreamGatherRows& rows, int B, int C, int S4, int gin, float* zp, float* gp,
+                                int64_t* len, hipStream_t s);
+// out[b][i] = i < n_b ? o_span[b * o_bs + off_b + i] : 0 for i < out_stride; float32, or int16 by the rule of
+// vsp_output_chunk (pcm != 0).  off_b + n_b <= o_bs and n_b <= out_stride, checked before the launch.
+hipError_t launch_stream_collect(const float* o_span, long o_bs, const StreamCollectRows& rows, int B, void* out,
+                                 long out_stride, int pcm, hipStream_t s);
+
 hipError_t launch_stft_frames(const float* audio, long a_bs, float* f, long f_bs, long f_cs, int B, int L, int n_fft,
                               int hop, int T, hipStream_t s);
 hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* spec, int B, int spec_ch, int T,

@@ -579,6 +579,51 @@ class Engine:
             _lib.check(rc, self.ctx, "vsp_generator_stream_chunk")
             yield o
 
+    def stream_rows_plan(self, rows):
+        """``vsp_stream_rows_plan`` (host only): ([lo], [hi], span_max) of rows given as (L, f0, f1) triples -- the window
+        ``[max(0, f0 - halo), min(L, f1 + halo))`` each row's chunk is computed from."""
+        rows = list(rows)
+        arr = (_lib.VspStreamRow * max(len(rows), 1))()
+        for r, (L, f0, f1) in zip(arr, rows):
+            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        lo, hi = (C.c_int32 * max(len(rows), 1))(), (C.c_int32 * max(len(rows), 1))()
+        span = C.c_int32()
+        _lib.check(self.lib.vsp_stream_rows_plan(self.ctx, len(rows), arr, lo, hi, C.byref(span)), None, "vsp_stream_rows_plan")
+        return list(lo)[:len(rows)], list(hi)[:len(rows)], int(span.value)
+
+    def generator_stream_rows(self, rows, chunk_frames: int, pcm: bool = True) -> torch.Tensor:
+        """``vsp_generator_stream_rows``: one chunk of up to 64 requests in ONE set of generator launches.  ``rows`` is a
+        sequence of ``(z, g, L, f0, f1)``: ``z`` [inter, >= L] float32 on the device with contiguous frames (any channel
+        stride: a row of a batch's latent), ``g`` [gin], and the frames [f0, f1) of the utterance's L to deliver,
+        ``f1 - f0 <= chunk_frames``.  Returns [B, chunk_frames * up], int16 if ``pcm`` else float32: row b holds its
+        (f1 - f0) * up samples -- those of ``generator_ragged`` on the utterance alone -- and zeros behind them."""
+        rows = list(rows)
+        B, up, d = len(rows), self.dims.total_upsample, self.dims
+        if not 1 <= B <= _lib.STREAM_ROWS_MAX:
+            raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
+        arr = (_lib.VspStreamRow * B)()
+        keep = []
+        for r, (z, g, L, f0, f1) in zip(arr, rows):
+            if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.device != self.device or z.dim() != 2
+                    or z.shape[0] != d.inter_channels or z.shape[1] < int(L) or (z.shape[1] > 1 and z.stride(1) != 1)):
+                raise ValueError("a row's z must be a float32 [inter_channels, >= L] tensor on the engine's device with "
+                                 "contiguous frames")
+            g = _dev_f32(g, self.device).reshape(-1)
+            if g.numel() != d.gin_channels:
+                raise ValueError(f"a row's g must have {d.gin_channels} entries")
+            keep.append((z, g))
+            r.z, r.z_channel_stride, r.g = z.data_ptr(), max(int(z.stride(0)), int(L)), g.data_ptr()
+            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        chunk_frames = int(chunk_frames)
+        out = torch.empty((B, max(chunk_frames, 0) * up), dtype=torch.int16 if pcm else torch.float32, device=self.device)
+        ws = self._workspace("generator_stream_rows",
+                             self.lib.vsp_generator_stream_rows_workspace_bytes(self.ctx, B, chunk_frames))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_generator_stream_rows(self.ctx, self._stream(), B, arr, _ptr(out), out.shape[1],
+                                                    int(bool(pcm)), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_generator_stream_rows")
+        return out
+
     # ------------------------------------------------------------------ output stage
     def configure_output(self, out_rate: Optional[int], zeros: int = 32, beta: float = 9.62,
                          rolloff: Optional[float] = None, in_rate: Optional[int] = None) -> None:

@@ -11,6 +11,7 @@ libvispeech_hip through ``vispeech_amd.models.SynthesizerTrn``.
 """
 from __future__ import annotations
 
+import collections
 import io
 import threading
 import wave
@@ -399,3 +400,258 @@ class BatchingSynthesisService:
             return [pcm16(o[b, 0, : int(frames[b]) * hop]) for b in range(len(rows))]
         eng = net._engine
         return [_host_i16(eng.output(o[b:b + 1, 0, : int(frames[b]) * hop], pcm=True)[0]) for b in range(len(rows))]
+
+
+class _RowStream:
+    """Iterator over one request's PCM16 chunks of a ``StreamingBatchService``.  ``close()`` abandons the request: its row
+    leaves the batch at the next tick."""
+
+    _END = object()
+
+    def __init__(self):
+        self._q: "queue.Queue" = queue.Queue()
+        self._closed = False
+        self._done = False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> bytes:
+        if self._done or self._closed:
+            raise StopIteration
+        item = self._q.get()
+        if item is self._END:
+            self._done = True
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._done = True
+            raise item
+        return item
+
+    def close(self) -> None:
+        self._closed = True
+
+    @property
+    def closed(self) -> bool:
+        return self._closed
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class _StreamRequest:
+    """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
+
+    def __init__(self, row, seed: int):
+        self.row, self.seed, self.stream = row, seed, _RowStream()
+        self.z = self.g = None
+        self.L = self.pos = 0
+        # output stage (``output_rate``): the request's own Engine.output_stream, fed one window per tick
+        self.pieces = None
+        self.window = None            # the window the feeder hands over next
+        self.held = None              # float chunks that complete no output sample yet (merged into the next window)
+        self.seen = self.m_next = 0
+        self.last = False
+
+
+class StreamingBatchService:
+    """Streaming AND batching (round 11): a set of active requests, each at its own position of its own utterance; every
+    tick advances all of them by one chunk in ONE set of generator launches (``Engine.generator_stream_rows``), requests join
+    and leave between ticks, and each caller receives PCM16 bytes as its chunk completes.  ``submit`` returns an iterator
+    of ``bytes`` (with ``close()``); one worker thread loops over ``step()`` -- one synchronous tick -- and with
+    ``autostart=False`` the caller drives ``step()`` itself.  A tick, in order:
+
+    1. admit    queued requests while fewer than ``max_batch`` are active: one isolated ``encode`` / ``frame_lengths_host`` /
+                ``decode(max_len=0)`` with the requests' seeds for the admitted group; each keeps its z row, g row and L.  A
+                zero-frame request ends at once with no bytes; a failing admission fails that group's streams only.
+    2. generate one ``generator_stream_rows`` call for all active requests, each at its own ``f0`` (a request's first chunk
+                has ``first_chunk_frames`` frames if that is given: earlier first audio).
+    3. deliver  one device-to-host copy of the int16 block, ``check_numerics(sync=False)``, each request's bytes on its queue.
+    4. retire   finished and closed requests.
+
+    A request's audio is what the reference returns for it alone (isolated mode + the halo of the streamed vocoder), whoever
+    shares its ticks.  ``output_rate``: each request's float chunk goes through its own ``Engine.output_stream`` (one small
+    launch per request per tick); the bytes are those of the one-shot output stage.  ``stats``: ticks, rows per tick and
+    admitted groups.  No priorities, no retries, no backpressure."""
+
+    def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
+                 noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
+                 sampling_rate: int = 44100, autostart: bool = True):
+        if not 1 <= max_batch <= 64 or chunk_frames < 1:
+            raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
+        if first_chunk_frames is not None and not 1 <= first_chunk_frames <= chunk_frames:
+            raise ValueError("1 <= first_chunk_frames <= chunk_frames")
+        if collate is None:
+            if table is None or spk2id is None:
+                raise ValueError("pass table and spk2id (for collate_rows) or a collate callable")
+            from .text import collate_rows
+            collate = lambda rows: collate_rows(rows, table, spk2id)
+        self._collate = collate
+        self.net, self.max_batch, self.chunk_frames = net, int(max_batch), int(chunk_frames)
+        self.first_chunk_frames = None if first_chunk_frames is None else int(first_chunk_frames)
+        self.noise_scale = float(noise_scale)
+        self.output_rate = None if output_rate is None else int(output_rate)
+        if self.output_rate is not None:
+            net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
+        self.stats = {"ticks": 0, "rows_per_tick": [], "groups": 0}
+        self._pending: "collections.deque" = collections.deque()
+        self._active: list = []
+        self._cv = threading.Condition()     # guards _pending / _closed; the worker sleeps on it while there is no work
+        self._closed = False
+        self._worker = None
+        if autostart:
+            self._worker = threading.Thread(target=self._run, name="vispeech-stream-batching", daemon=True)
+            self._worker.start()
+
+    # ------------------------------------------------------------------ callers' side
+    def submit(self, row, noise_seed: int) -> _RowStream:
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it.  Returns the iterator of the request's PCM16
+        ``bytes``, one piece per tick the request takes part in."""
+        req = _StreamRequest(row, int(noise_seed))
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            self._pending.append(req)
+            self._cv.notify()
+        return req.stream
+
+    def close(self) -> None:
+        """Serve what is queued and active, then stop the worker and join it (without a worker: run the ticks here)."""
+        with self._cv:
+            self._closed = True
+            self._cv.notify()
+        if self._worker is not None:
+            self._worker.join()
+        else:
+            while self.step():
+                pass
+
+    def _run(self) -> None:
+        while True:
+            with self._cv:
+                while not self._pending and not self._active and not self._closed:
+                    self._cv.wait()
+                if self._closed and not self._pending and not self._active:
+                    return
+            self.step()
+
+    # ------------------------------------------------------------------ one tick
+    def step(self) -> bool:
+        """One tick (admit, generate, deliver, retire).  Returns whether requests are still queued or active."""
+        self._admit()
+        self._active = [r for r in self._active if not r.stream.closed]      # (closed by its caller: the row leaves here)
+        if self._active:
+            try:
+                self._generate_and_deliver()
+            except Exception as e:             # the tick's requests fail; the service lives on
+                for r in self._active:
+                    r.stream._q.put(e)
+                self._active = []
+        for r in self._active:
+            if r.pos >= r.L:
+                r.stream._q.put(_RowStream._END)
+        self._active = [r for r in self._active if r.pos < r.L]
+        with self._cv:
+            return bool(self._pending or self._active)
+
+    def _admit(self) -> None:
+        group = []
+        with self._cv:
+            while self._pending and len(self._active) + len(group) < self.max_batch:
+                req = self._pending.popleft()
+                if req.stream.closed:
+                    req.stream._q.put(_RowStream._END)
+                else:
+                    group.append(req)
+        if not group:
+            return
+        self.stats["groups"] += 1
+        try:
+            import torch
+            eng = self.net._engine
+            batch = self._collate([r.row for r in group])
+            t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
+            enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(batch.get("duration")),
+                             t(batch.get("f0")), t(batch.get("energy")), isolated=True)
+            frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
+            z = None
+            if tf > 0:
+                z = eng.decode(enc, tf, None, self.noise_scale, max_len=0, noise_seed=[r.seed for r in group],
+                               isolated=True)["z"]
+            for b, r in enumerate(group):
+                r.L, r.pos = int(frames[b]), 0
+                if r.L <= 0:
+                    r.stream._q.put(_RowStream._END)          # nothing to synthesise: no bytes
+                    continue
+                r.z, r.g = z[b], enc["g"][b]
+                self._active.append(r)
+        except Exception as e:                 # this group's requests fail; the active ones and the service live on
+            for r in group:
+                r.stream._q.put(e)
+
+    def _generate_and_deliver(self) -> None:
+        eng = self.net._engine
+        hop = self.net.dims.total_upsample
+        rows, counts = [], []
+        for r in self._active:
+            n = self.first_chunk_frames if (r.pos == 0 and self.first_chunk_frames is not None) else self.chunk_frames
+            f1 = min(r.L, r.pos + n)
+            rows.append((r.z, r.g, r.L, r.pos, f1))
+            counts.append(f1 - r.pos)
+        self.stats["ticks"] += 1
+        self.stats["rows_per_tick"].append(len(rows))
+        out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=self.output_rate is None)
+        if self.output_rate is None:
+            block = _host_i16_2d(out)                                        # the tick's one device-to-host copy
+            self._check_numerics()
+            for b, (r, n) in enumerate(zip(self._active, counts)):
+                r.pos += n
+                r.stream._q.put(block[b, : n * hop].tobytes())
+            return
+        for b, (r, n) in enumerate(zip(self._active, counts)):
+            r.pos += n
+            piece = self._through_output_stage(r, out[b:b + 1, : n * hop])
+            self._check_numerics()
+            if piece:
+                r.stream._q.put(piece)
+
+    def _through_output_stage(self, r: _StreamRequest, x) -> bytes:
+        """The request's float window through its own ``Engine.output_stream``; returns the PCM16 bytes it completes.  The
+        stream pulls its windows, a tick pushes one: a window that completes no output sample yet (``complete_outputs``) is
+        held back and handed over together with the next one -- consecutive windows of any lengths give the same bytes."""
+        import torch
+        from . import output_stage
+        eng = self.net._engine
+        if r.pieces is None:
+            def feed():
+                while r.window is not None:
+                    w, r.window = r.window, None
+                    yield w
+            r.pieces = eng.output_stream(feed(), None, pcm=True)
+        L, M, H = eng.output_plan
+        r.held = x if r.held is None else torch.cat([r.held, x], dim=1)
+        r.last = r.pos >= r.L
+        seen = r.seen + int(r.held.shape[1])
+        m_done = output_stage.complete_outputs(seen, L, M, H)
+        if not r.last and m_done <= r.m_next:
+            return b""
+        r.window, r.held, r.seen = r.held, None, seen
+        if not r.last:
+            r.m_next = m_done
+            return _host_i16(next(r.pieces)).tobytes()
+        return b"".join(_host_i16(y).tobytes() for y in r.pieces)      # the last window and the filter's tail
+
+    def _check_numerics(self) -> None:
+        eng = getattr(self.net, "_engine", None)
+        if eng is not None and hasattr(eng, "check_numerics"):
+            eng.check_numerics(sync=False)
+
+
+def _host_i16_2d(y) -> np.ndarray:
+    """[B, n] int16 block of the engine -> little-endian int16 [B, n] on the host (one copy)."""
+    a = y.detach().cpu().numpy() if hasattr(y, "detach") else np.asarray(y)
+    return np.ascontiguousarray(a, dtype="<i2")
