@@ -533,6 +533,46 @@ int vsp_output_chunk(vsp_ctx* ctx, void* stream, int B, const float* x, int64_t 
                      const int64_t* n_valid, int64_t n_max, int64_t m0, int64_t m1, void* out, int64_t out_stride,
                      int pcm);
 
+/* Streaming for batched requests THROUGH the output stage (ABI 7, additive; round 12): vsp_generator_stream_rows with the
+ * ragged output stage in place of the collect launch -- still one launch set per tick, and what crosses to the host is PCM16
+ * at the output rate.  Row b delivers frames [f0, f1) of an utterance of Lf frames (`row`, as above); with
+ * up = prod(upsample_rates), x_first = f0 up and n = (f1 - f0) up its new INPUT samples are [x_first, x_first + n), and with
+ * (L, M, H) of the configured stage (vsp_resample_plan)
+ *   complete(s, ended) = ended ? ceil(s L / M) : min(ceil(s L / M), max(0, ceil((L s - H) / M)))
+ *   start(m)           = max(0, ceil((m M - H) / L))
+ *   m0 = complete(x_first, 0)          m1 = complete(x_first + n, f1 == Lf)
+ *   k0 = min(x_first, start(m0))       k1 = min(x_first + n, start(m1))
+ * (the rule of vispeech_amd.output_stage: every call delivers every output its input completes, so m0 of a call is m1 of the
+ * call that ended at its f0 and no counter travels between calls).  The call writes output samples [m0, m1) of the
+ * utterance's one-shot output stage to out[b][0 .. m1 - m0) -- float32 (pcm == 0) or int16 (pcm == 1) by the rule of
+ * vsp_output_chunk, the same taps in the same order on the same input samples: the concatenation over an utterance's calls
+ * is what vsp_output_chunk returns for the concatenated float rows of vsp_generator_stream_rows, bit for bit -- and exactly 0
+ * to out[b][m1 - m0 .. out_stride).  m1 == m0 is legal (a short chunk at a low output rate): the row is all zeros.
+ * hist_in holds input samples [k0, x_first) as the row's previous call wrote them (ignored, may be NULL, when f0 == 0 or
+ * K == 0); the call writes samples [k1, x_first + n) to hist_out[0 ..).  Both are DEVICE buffers of
+ * K = vsp_output_history_samples floats and must differ (blocks of one launch read the one and write the other): a request
+ * owns two and alternates.  vsp_stream_rows_output_plan is the host arithmetic without a context (it reads L, f0, f1 of each
+ * row; every output may be NULL; it checks 1 <= B <= 64 and 0 <= f0 < f1 <= L like vsp_stream_rows_plan).
+ * vsp_output_history_samples = floor(2 H / L), which bounds both x_first - k0 and x_first + n - k1: the first incomplete
+ * output m >= (L s - H) / M starts at ceil((m M - H) / L) >= s - 2 H / L.  0 for the pass-through.
+ * vsp_stream_rows_out_samples = ceil(n L / M) + ceil(H / M) rounded up to a multiple of 4, n = chunk_frames up: an upper bound
+ * of m1 - m0 (reached only by a final call, which flushes the filter's tail); an out_stride of that many ELEMENTS always fits.
+ * Checked on the host before anything is launched: the output stage is configured (VSP_ERR_STATE); the arguments of
+ * vsp_generator_stream_rows (there is no chunk_frames here: the workspace bounds the windows), hist_out non-NULL when K > 0,
+ * hist_in non-NULL when K > 0 and f0 > 0, hist_in != hist_out (VSP_ERR_ARG); every m1 - m0 <= out_stride (VSP_ERR_SHAPE).
+ * Workspace: vsp_generator_stream_rows_workspace_bytes.  No allocation, no synchronisation, everything on the caller's stream. */
+typedef struct vsp_stream_row_out {
+  vsp_stream_row row;
+  const float* hist_in;
+  float* hist_out;
+} vsp_stream_row_out;
+int vsp_stream_rows_output_plan(int L, int M, int H, int up, int B, const vsp_stream_row* rows, int64_t* m0, int64_t* m1,
+                                int64_t* k0, int64_t* k1);
+int vsp_output_history_samples(int L, int M, int H);
+int64_t vsp_stream_rows_out_samples(int L, int M, int H, int up, int chunk_frames);
+int vsp_generator_stream_rows_output(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row_out* rows, void* out,
+                                     int64_t out_stride, int pcm, void* workspace, int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

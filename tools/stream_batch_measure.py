@@ -9,7 +9,15 @@
    utterances: the halo recompute alone predicts (chunk + 28) / chunk.
 3. The largest deviation of the ticked chunks from generator_ragged B = 1 on each utterance alone (the tests' 1e-5 bound).
 
-usage: tools/stream_batch_measure.py [repeats] [out.txt]"""
+usage: tools/stream_batch_measure.py [repeats] [out.txt]
+
+With --output-rate R the tool measures the service's output stage instead: 16 requests of ~5 s submitted to an idle
+StreamingBatchService driven by step(), chunk_frames 32 and 64, in ONE process -- the plain service (output_rate=None), the
+per-request output stage (output_rate=R) and, with --fused, the ragged output stage (fused_output=True), alternated
+within every repeat after a warm-up run of each.  Per run: the median wall time of the ticks that advance all 16 requests,
+delivered samples/s (first submit to last byte) and the time from submit to the first chunk in hand.
+
+usage: tools/stream_batch_measure.py --output-rate R [--fused] [repeats] [out.txt]"""
 import os
 import sys
 import time
@@ -27,8 +35,19 @@ from vispeech_amd.service import (BatchingSynthesisService, StreamingBatchServic
                                   SynthesisService)
 from vispeech_amd.synth import synth_batch, synth_state_dict             # noqa: E402
 
-REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-OUT = sys.argv[2] if len(sys.argv) > 2 else None
+ARGS = list(sys.argv[1:])
+FUSED = "--fused" in ARGS
+if FUSED:
+    ARGS.remove("--fused")
+OUTPUT_RATE = None
+if "--output-rate" in ARGS:
+    i = ARGS.index("--output-rate")
+    OUTPUT_RATE = int(ARGS[i + 1])
+    del ARGS[i:i + 2]
+if FUSED and OUTPUT_RATE is None:
+    sys.exit("--fused needs --output-rate")
+REPEATS = int(ARGS[0]) if len(ARGS) > 0 else 5
+OUT = ARGS[1] if len(ARGS) > 1 else None
 KEYS = ("phonemes", "lengths", "sid", "duration", "f0", "energy")
 
 
@@ -142,12 +161,64 @@ def ticking_throughput(net, n_utt, chunks):
     return lines
 
 
+def service_run(net, batch, n_req, chunk, **kw):
+    """One idle service, `n_req` requests submitted at once, driven by step() until everything is delivered.  Returns
+    (median ms of the ticks with all n_req rows, delivered samples per second, ms from submit to the first chunk, samples)."""
+    collate = lambda rows: {k: batch[k][rows] for k in KEYS}
+    svc = StreamingBatchService(net, max_batch=n_req, chunk_frames=chunk, collate=collate, autostart=False, **kw)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    streams = [svc.submit(b, 1000 + b) for b in range(n_req)]
+    more = svc.step()                                   # admission + the first tick
+    first = next(streams[0])
+    t_first = time.perf_counter() - t0
+    ticks = []
+    while more:
+        t1 = time.perf_counter()
+        more = svc.step()                               # (synchronous: it ends with the tick's device-to-host copy)
+        ticks.append(time.perf_counter() - t1)
+    total = time.perf_counter() - t0
+    samples = len(first) // 2 + sum(len(piece) // 2 for s in streams for piece in s)
+    svc.close()
+    full = [t for t, rows in zip(ticks, svc.stats["rows_per_tick"][1:]) if rows == n_req]
+    return med(full) * 1e3, samples / total, t_first * 1e3, samples
+
+
+def output_stage_mode(net, batch, n_req=16):
+    kinds = [("plain, output_rate=None", {}), (f"output_rate={OUTPUT_RATE}, per request", {"output_rate": OUTPUT_RATE})]
+    if FUSED:
+        kinds.append((f"output_rate={OUTPUT_RATE}, fused_output", {"output_rate": OUTPUT_RATE, "fused_output": True}))
+    frames = batch["frame_lengths"][:n_req]
+    lines = [f"{torch.cuda.get_device_name(0)}; {n_req} requests of {int(frames.min())} .. {int(frames.max())} frames submitted to "
+             f"an idle StreamingBatchService, step() driven; median [min .. max] of {REPEATS} runs, the kinds alternated "
+             "within every repeat after one warm-up run of each; profiler off"]
+    for chunk in (32, 64):
+        res = {name: [] for name, _ in kinds}
+        for rep in range(REPEATS + 1):
+            for name, kw in kinds:
+                r = service_run(net, batch, n_req, chunk, **kw)
+                if rep:
+                    res[name].append(r)
+        net._engine.configure_output(None)
+        lines.append(f"chunk_frames {chunk}:")
+        for name, _ in kinds:
+            t, sps, fc = ([r[i] for r in res[name]] for i in range(3))
+            lines.append(f"  {name:42s} tick {med(t):7.3f} [{min(t):.3f} .. {max(t):.3f}] ms   delivered {med(sps) / 1e6:7.2f} "
+                         f"[{min(sps) / 1e6:.2f} .. {max(sps) / 1e6:.2f}] Msamples/s ({res[name][0][3]} samples)   "
+                         f"first chunk {med(fc):6.2f} [{min(fc):.2f} .. {max(fc):.2f}] ms")
+    return lines
+
+
 def main():
     a, kw0 = vcfg.synthesizer_args(vcfg.default_hparams())
     sd = synth_state_dict(dims_from_ctor(*a, **kw0), seed=1234, infer_only=True)
     net = SynthesizerTrn(*a, device="cuda:0", **kw0).eval()
     net.load_state_dict(sd)
     batch = synth_batch(17, seed=11)
+    if OUTPUT_RATE is not None:
+        lines = output_stage_mode(net, batch)
+        assert net._engine.status() == 0
+        return report(lines)
     chunk = 64
     lines = [f"{torch.cuda.get_device_name(0)}; utterances of {int(batch['frame_lengths'].min())} .. "
              f"{int(batch['frame_lengths'].max())} frames; chunk_frames {chunk} (0.74 s); median [min .. max] of {REPEATS}",
@@ -161,6 +232,10 @@ def main():
                      f"BatchingSynthesisService (whole utterance) {med(w):8.2f} [{min(w):.2f} .. {max(w):.2f}]")
     lines += ticking_throughput(net, 16, (32, 64, 128))
     assert net._engine.status() == 0
+    report(lines)
+
+
+def report(lines):
     text = "\n".join(lines)
     print(text)
     if OUT:

@@ -47,6 +47,12 @@ class VspStreamRow(C.Structure):
                 ("L", C.c_int32), ("f0", C.c_int32), ("f1", C.c_int32)]
 
 
+class VspStreamRowOut(C.Structure):
+    """``vsp_stream_row_out``: a row of ``vsp_generator_stream_rows_output`` -- the stream row and the request's two history
+    buffers (device pointers to ``vsp_output_history_samples`` floats each; this call reads one and writes the other)."""
+    _fields_ = [("row", VspStreamRow), ("hist_in", C.c_void_p), ("hist_out", C.c_void_p)]
+
+
 STREAM_ROWS_MAX = 64
 
 _P = C.c_void_p
@@ -107,6 +113,11 @@ SIGNATURES = {
                                   C.POINTER(C.c_int32)]),
     "vsp_generator_stream_rows_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_generator_stream_rows": (_I, [_P, _P, _I, C.POINTER(VspStreamRow), _P, _I64, _I, _P, _I64]),
+    "vsp_stream_rows_output_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(VspStreamRow), C.POINTER(_I64), C.POINTER(_I64),
+                                         C.POINTER(_I64), C.POINTER(_I64)]),
+    "vsp_output_history_samples": (_I, [_I, _I, _I]),
+    "vsp_stream_rows_out_samples": (_I64, [_I, _I, _I, _I, _I]),
+    "vsp_generator_stream_rows_output": (_I, [_P, _P, _I, C.POINTER(VspStreamRowOut), _P, _I64, _I, _P, _I64]),
     "vsp_flow_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I64]),
     "vsp_voice_conversion_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_voice_conversion": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64]),

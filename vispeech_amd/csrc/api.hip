@@ -1980,27 +1980,22 @@ int64_t vsp_generator_stream_rows_workspace_bytes(const vsp_ctx* ctx, int B, int
   return w.total;
 }
 
-int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row* rows, void* out, int64_t out_stride,
-                              int pcm, void* workspace, int64_t workspace_bytes) {
-  int rc = check_ready(ctx);
-  if (rc) return rc;
-  const long up = total_upsample(ctx->cfg);
-  if (B < 1 || B > STREAM_ROWS_MAX || !rows || !out || !workspace || (pcm != 0 && pcm != 1) || out_stride < up)
-    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: bad argument (1 <= B <= %d, out_stride >= one frame)", STREAM_ROWS_MAX);
-  int32_t lo[STREAM_ROWS_MAX], hi[STREAM_ROWS_MAX], span = 0;
+namespace {
+// The gather launch and the generator run of a stream_rows call: the span waveform [B][*span * up] is left at *o_span, row
+// b's window starts at frame lo[b].  Every check runs before the first launch.
+int stream_rows_generate(vsp_ctx* ctx, hipStream_t s, int B, const vsp_stream_row* rows, int64_t chunk_frames, void* workspace,
+                         int64_t workspace_bytes, const char* who, int32_t* lo, float** o_span_out, int32_t* span_out) {
+  int32_t hi[STREAM_ROWS_MAX], span = 0;
   if (vsp_stream_rows_plan(ctx, B, rows, lo, hi, &span) != VSP_OK)
-    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: a row is not 0 <= f0 < f1 <= L");
-  const int64_t chunk_frames = out_stride / up;
+    return ctx->fail(VSP_ERR_ARG, "%s: a row is not 0 <= f0 < f1 <= L", who);
   StreamGatherRows gr;
-  StreamCollectRows cr;
   int64_t span_len[STREAM_ROWS_MAX];
   for (int b = 0; b < B; ++b) {
     const vsp_stream_row& r = rows[b];
     if (!r.z || !r.g || r.z_channel_stride < r.L || r.f1 - r.f0 > chunk_frames)
-      return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: row %d: null z / g, channel stride below L, or a chunk of "
-                                    "%d frames where out_stride holds %lld", b, r.f1 - r.f0, (long long)chunk_frames);
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: null z / g, channel stride below L, or a chunk of "
+                                    "%d frames where out_stride holds %lld", who, b, r.f1 - r.f0, (long long)chunk_frames);
     gr.r[b] = StreamGatherRow{r.z, (long)r.z_channel_stride, r.g, lo[b], hi[b]};
-    cr.r[b] = StreamCollectRow{(int)((r.f0 - lo[b]) * up), (int)((r.f1 - r.f0) * up)};
     span_len[b] = hi[b] - lo[b];
   }
   StreamRowsWs w;
@@ -2011,7 +2006,6 @@ int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_strea
   float* const zp = reinterpret_cast<float*>(base + w.zp);
   float* const gp = reinterpret_cast<float*>(base + w.gp);
   int64_t* const len = reinterpret_cast<int64_t*>(base + w.len);
-  hipStream_t s = (hipStream_t)stream;
   const int inter = ctx->cfg.inter_channels;
   hipError_t e = launch_stream_gather(gr, B, inter, w.S4, ctx->cfg.gin_channels, zp, gp, len, s);
   if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "stream_gather: %s", hipGetErrorString(e));
@@ -2023,8 +2017,72 @@ int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_strea
   run_gen(r, B, span, T3{zp, (long)inter * w.S4, (long)w.S4}, len, gp, o_span);
   if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "stream rows workspace too small (need %zu bytes)", (size_t)w.gen + ws.cur);
   if (r.rc != VSP_OK) return r.rc;
-  e = launch_stream_collect(o_span, (long)span * up, cr, B, out, (long)out_stride, pcm, s);
+  *o_span_out = o_span;
+  *span_out = span;
+  return VSP_OK;
+}
+}  // namespace
+
+int vsp_generator_stream_rows(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row* rows, void* out, int64_t out_stride,
+                              int pcm, void* workspace, int64_t workspace_bytes) {
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  const long up = total_upsample(ctx->cfg);
+  if (B < 1 || B > STREAM_ROWS_MAX || !rows || !out || !workspace || (pcm != 0 && pcm != 1) || out_stride < up)
+    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows: bad argument (1 <= B <= %d, out_stride >= one frame)", STREAM_ROWS_MAX);
+  int32_t lo[STREAM_ROWS_MAX], span = 0;
+  float* o_span = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  rc = stream_rows_generate(ctx, s, B, rows, out_stride / up, workspace, workspace_bytes, "vsp_generator_stream_rows", lo, &o_span,
+                            &span);
+  if (rc) return rc;
+  StreamCollectRows cr;
+  for (int b = 0; b < B; ++b) cr.r[b] = StreamCollectRow{(int)((rows[b].f0 - lo[b]) * up), (int)((rows[b].f1 - rows[b].f0) * up)};
+  hipError_t e = launch_stream_collect(o_span, (long)span * up, cr, B, out, (long)out_stride, pcm, s);
   return e == hipSuccess ? VSP_OK : ctx->fail(VSP_ERR_HIP, "stream_collect: %s", hipGetErrorString(e));
+}
+
+int vsp_generator_stream_rows_output(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row_out* rows, void* out,
+                                     int64_t out_stride, int pcm, void* workspace, int64_t workspace_bytes) {
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  if (!ctx->out_tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
+  if (B < 1 || B > STREAM_ROWS_MAX || !rows || !out || !workspace || (pcm != 0 && pcm != 1) || out_stride < 1)
+    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows_output: bad argument (1 <= B <= %d)", STREAM_ROWS_MAX);
+  const int up = (int)total_upsample(ctx->cfg);
+  const int L = ctx->out_L, M = ctx->out_M, H = ctx->out_H, K = vsp_output_history_samples(L, M, H);
+  vsp_stream_row plain[STREAM_ROWS_MAX];
+  int64_t m0[STREAM_ROWS_MAX], m1[STREAM_ROWS_MAX];
+  for (int b = 0; b < B; ++b) plain[b] = rows[b].row;
+  if (vsp_stream_rows_output_plan(L, M, H, up, B, plain, m0, m1, nullptr, nullptr) != VSP_OK)
+    return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows_output: a row is not 0 <= f0 < f1 <= L");
+  for (int b = 0; b < B; ++b) {
+    const vsp_stream_row_out& r = rows[b];
+    if (K > 0 && (!r.hist_out || (r.row.f0 > 0 && !r.hist_in)))
+      return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows_output: row %d: null history buffer (%d floats each)", b, K);
+    if (r.hist_out && r.hist_in == r.hist_out)
+      return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows_output: row %d: hist_in == hist_out", b);
+  }
+  for (int b = 0; b < B; ++b)
+    if (m1[b] - m0[b] > out_stride)
+      return ctx->fail(VSP_ERR_SHAPE, "vsp_generator_stream_rows_output: row %d completes %lld output samples, out_stride is %lld "
+                                      "(vsp_stream_rows_out_samples)", b, (long long)(m1[b] - m0[b]), (long long)out_stride);
+  int32_t lo[STREAM_ROWS_MAX], span = 0;
+  float* o_span = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  rc = stream_rows_generate(ctx, s, B, plain, INT32_MAX, workspace, workspace_bytes, "vsp_generator_stream_rows_output", lo,
+                            &o_span, &span);
+  if (rc) return rc;
+  StreamOutRows orows;
+  for (int b = 0; b < B; ++b) {
+    const vsp_stream_row& r = plain[b];
+    // (a first chunk has no history: whatever the caller left in hist_in is not passed on)
+    orows.r[b] = StreamOutRow{r.f0 > 0 ? rows[b].hist_in : nullptr, rows[b].hist_out, (int64_t)r.f0 * up, (int)((r.f0 - lo[b]) * up),
+                              (int)((r.f1 - r.f0) * up), r.f1 == r.L, 0};
+  }
+  const StreamOutFilter f{ctx->out_tab, L, M, H, ctx->out_J, ctx->out_P};
+  hipError_t e = launch_stream_output(o_span, (long)span * up, orows, B, f, K, out, (long)out_stride, pcm, s);
+  return e == hipSuccess ? VSP_OK : ctx->fail(VSP_ERR_HIP, "stream_output: %s", hipGetErrorString(e));
 }
 
 int vsp_rq_spline(void* stream, int64_t n, int nb, const float* x, const float* uw, const float* uh, const float* ud,

@@ -402,6 +402,44 @@ hipError_t launch_stream_gather(const StreamGatherRows& rows, int B, int C, int 
 hipError_t launch_stream_collect(const float* o_span, long o_bs, const StreamCollectRows& rows, int B, void* out,
                                  long out_stride, int pcm, hipStream_t s);
 
+// The ragged output stage (resample.hip; include/vispeech_hip.h, vsp_generator_stream_rows_output): instead of the collect,
+// row b's n new samples o_span[b * o_bs + off ..) -- input samples [x_first, x_first + n) of its utterance -- and its history
+// hist_in = samples [k0, x_first) go through the output stage's filter; m0, m1, k0, k1 follow from (x_first, n, ended) by
+// stream_output_plan, on the host and on the device alike.
+struct StreamOutRow {        // 40 B
+  const float* hist_in; float* hist_out; int64_t x_first; int off, n, ended, pad;
+};
+struct StreamOutRows { StreamOutRow r[STREAM_ROWS_MAX]; };
+struct StreamOutPlan { int64_t m0, m1, k0, k1; };
+struct StreamOutFilter { const float* tab; int L, M, H, J, P; };   // the context's configured output stage (tab [P][L])
+__host__ __device__ inline int64_t stream_output_complete(int64_t n_seen, bool ended, int64_t L, int64_t M, int64_t H) {
+  // vispeech_amd.output_stage.complete_outputs: output m is final when m M + H < L n_seen, or when the input has ended
+  const int64_t total = (n_seen * L + M - 1) / M, t = L * n_seen - H;
+  if (ended) return total;
+  const int64_t c = t <= 0 ? 0 : (t + M - 1) / M;
+  return c < total ? c : total;
+}
+__host__ __device__ inline int64_t stream_output_history_start(int64_t m, int64_t L, int64_t M, int64_t H) {
+  // vispeech_amd.output_stage.history_start: the first input sample output m reads, ceil((m M - H) / L) clamped to 0
+  const int64_t t = m * M - H;
+  return t <= 0 ? 0 : (t + L - 1) / L;
+}
+__host__ __device__ inline StreamOutPlan stream_output_plan(int64_t x_first, int64_t n, bool ended, int64_t L, int64_t M,
+                                                            int64_t H) {
+  StreamOutPlan p;
+  p.m0 = stream_output_complete(x_first, false, L, M, H);
+  p.m1 = stream_output_complete(x_first + n, ended, L, M, H);
+  const int64_t h0 = stream_output_history_start(p.m0, L, M, H), h1 = stream_output_history_start(p.m1, L, M, H);
+  p.k0 = h0 < x_first ? h0 : x_first;
+  p.k1 = h1 < x_first + n ? h1 : x_first + n;
+  return p;
+}
+// out[b][j] = j < m1_b - m0_b ? y_b[m0_b + j] : 0 for j < out_stride (float32, or int16 by the rule of vsp_output_chunk);
+// hist_out_b[j] = sample k1_b + j for k1_b + j < x_first_b + n_b.  K = the capacity of a history buffer in floats.  Checked
+// before the launch: every m1 - m0 <= out_stride, both histories <= K, hist_in != hist_out, off + n <= o_bs.  One launch.
+hipError_t launch_stream_output(const float* o_span, long o_bs, const StreamOutRows& rows, int B, const StreamOutFilter& f,
+                                int K, void* out, long out_stride, int pcm, hipStream_t s);
+
 hipError_t launch_stft_frames(const float* audio, long a_bs, float* f, long f_bs, long f_cs, int B, int L, int n_fft,
                               int hop, int T, hipStream_t s);
 hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* spec, int B, int spec_ch, int T,

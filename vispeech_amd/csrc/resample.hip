@@ -55,6 +55,36 @@ __device__ __forceinline__ int rs_pcm16(float y) {
   return (int)fminf(fmaxf(r, -32768.f), 32767.f);
 }
 
+// One output sample from global memory: acc = fmaf(tab[i][col], x[ks + i], acc), i = 0 .. P - 1 ascending; `sample(k)` is
+// input sample k of the utterance, 0 where it is not readable.  The LDS loops of resample_kernel run this very chain.
+template <class Sample>
+__device__ __forceinline__ float rs_one_output(const float* __restrict__ tcol, int L, int P, int64_t ks, Sample sample) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int i = 0; i < P; ++i) acc = fmaf(tcol[(size_t)i * L], sample(ks + i), acc);   // (loads in flight; the order stays)
+  return acc;
+}
+
+// Stores sample j of a row (float32, or PCM16 with even lanes storing packed pairs where the row allows it).  Every lane
+// of the wave calls it with a valid y (the shuffle takes all of them); `active` lanes store, `has_next`: lane + 1 is active.
+__device__ __forceinline__ void rs_store(void* row, int64_t j, float y, bool active, bool has_next, int pcm, int pair_ok) {
+  if (!pcm) {
+    if (active) static_cast<float*>(row)[j] = y;
+    return;
+  }
+  const int q = rs_pcm16(y);
+  const int q_next = __shfl_down(q, 1);
+  int16_t* o16 = static_cast<int16_t*>(row) + j;
+  if (pair_ok) {
+    if (!(threadIdx.x & 1) && active) {
+      if (has_next) *reinterpret_cast<uint32_t*>(o16) = (uint32_t)(q & 0xffff) | ((uint32_t)q_next << 16);
+      else *o16 = (int16_t)q;
+    }
+  } else if (active) {
+    *o16 = (int16_t)q;
+  }
+}
+
 __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a) {
   extern __shared__ float smem[];
   const int tid = threadIdx.x;
@@ -75,11 +105,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
   float acc = 0.f;
 
   if (a.mode == 2) {
-    for (int i = 0; i < a.P; ++i) {
-      const int64_t k = ks + i;
-      const float xv = (k >= lo && k < hi) ? xb[k] : 0.f;
-      acc = fmaf(tcol[(size_t)i * a.L], xv, acc);
-    }
+    acc = rs_one_output(tcol, a.L, a.P, ks, [&](int64_t k) { return (k >= lo && k < hi) ? xb[k] : 0.f; });
   } else {
     float* xs = smem;
     float* ts = smem + a.xs_words;
@@ -159,22 +185,37 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
   }
 
   const float y = m < out_len ? acc : 0.f;                           // behind the utterance's own output: silence
-  const int64_t j = m - a.m0;
-  if (!a.pcm) {
-    if (active) static_cast<float*>(a.out)[(int64_t)b * a.out_stride + j] = y;
+  // (all lanes take part in the store's shuffle; idle lanes hold a valid shadow)
+  rs_store(static_cast<char*>(a.out) + (int64_t)b * a.out_stride * (a.pcm ? 2 : 4), m - a.m0, y, active, m + 1 <= m_last, a.pcm,
+           a.pair_ok);
+}
+
+// The ragged output stage (kernels.h, launch_stream_output).  grid (out_blocks + hist_blocks, B), RS_TILE threads; a block
+// serves one row (blockIdx.y), whose descriptor is read through the constant kernel arguments.  Sample k of the row's
+// utterance is its new segment for k in [x_first, x_first + n), hist_in for k in [k0, x_first) and 0 elsewhere: before k0 no
+// output of [m0, m1) reads it, behind x_first + n it is the filter's tail.  The span's halo samples are never read.  Samples
+// come from global memory (L1 / L2: a tile's window is a few KB) -- the chain of resample_kernel, so the same bits.
+__global__ __launch_bounds__(RS_TILE) void stream_output_kernel(const vsp::StreamOutRows rows, const float* __restrict__ o_span,
+                                                                long o_bs, const vsp::StreamOutFilter f, int K, int out_blocks,
+                                                                void* __restrict__ out, long out_stride, int pcm, int pair_ok) {
+  const int b = blockIdx.y;
+  const vsp::StreamOutRow& r = rows.r[b];
+  const int64_t x_first = r.x_first, x_end = x_first + r.n;
+  const vsp::StreamOutPlan p = vsp::stream_output_plan(x_first, r.n, r.ended != 0, f.L, f.M, f.H);
+  const float* __restrict__ xn = o_span + (size_t)b * o_bs + r.off - x_first;      // xn[k], k in [x_first, x_end)
+  const float* __restrict__ xh = r.hist_in - p.k0;                                  // xh[k], k in [k0, x_first)
+  auto sample = [&](int64_t k) { return k >= x_first ? (k < x_end ? xn[k] : 0.f) : (k >= p.k0 ? xh[k] : 0.f); };
+  if ((int)blockIdx.x >= out_blocks) {
+    const int64_t j = (int64_t)((int)blockIdx.x - out_blocks) * RS_TILE + threadIdx.x, k = p.k1 + j;
+    if (j < K && k < x_end) r.hist_out[j] = sample(k);
     return;
   }
-  const int q = rs_pcm16(y);
-  const int q_next = __shfl_down(q, 1);                              // (all lanes take part; idle lanes hold a valid shadow)
-  int16_t* o16 = static_cast<int16_t*>(a.out) + (int64_t)b * a.out_stride + j;
-  if (a.pair_ok) {
-    if (!(tid & 1) && active) {
-      if (m + 1 <= m_last) *reinterpret_cast<uint32_t*>(o16) = (uint32_t)(q & 0xffff) | ((uint32_t)q_next << 16);
-      else *o16 = (int16_t)q;
-    }
-  } else if (active) {
-    *o16 = (int16_t)q;
-  }
+  const int64_t j = (int64_t)blockIdx.x * RS_TILE + threadIdx.x;
+  const int64_t m = p.m0 + j;
+  float y = 0.f;
+  if (m < p.m1) y = rs_one_output(f.tab + (int)(m % f.L), f.L, f.P, (m * f.M) / f.L - f.J, sample);
+  rs_store(static_cast<char*>(out) + (int64_t)b * out_stride * (pcm ? 2 : 4), j, y, j < out_stride, j + 1 < out_stride, pcm,
+           pair_ok);
 }
 
 // ---------------------------------------------------------------------------------------------- host: plan and filter
@@ -248,6 +289,60 @@ int64_t vsp_resample_out_len(int64_t n, int L, int M) {
   if (n < 0 || L < 1 || M < 1) return VSP_ERR_ARG;
   return (n * L + M - 1) / M;
 }
+
+int vsp_output_history_samples(int L, int M, int H) {
+  if (L < 1 || M < 1 || H < 0) return VSP_ERR_ARG;
+  // Between windows the first incomplete output is m = ceil((L n_seen - H) / M) (or 0 while L n_seen <= H), so its first
+  // input sample ceil((m M - H) / L) >= n_seen - 2 H / L: at most floor(2 H / L) samples are kept.
+  return (int)(((int64_t)2 * H) / L);
+}
+
+int64_t vsp_stream_rows_out_samples(int L, int M, int H, int up, int chunk_frames) {
+  if (L < 1 || M < 1 || H < 0 || up < 1 || chunk_frames < 1) return VSP_ERR_ARG;
+  // m1 - m0 <= ceil((n L + H) / M) for the final tick (its m0 >= (L x_first - H) / M, its m1 = ceil(L (x_first + n) / M)),
+  // ceil(n L / M) for any other
+  const int64_t n = (int64_t)chunk_frames * up;
+  return ((n * L + M - 1) / M + (H + M - 1) / M + 3) / 4 * 4;
+}
+
+int vsp_stream_rows_output_plan(int L, int M, int H, int up, int B, const vsp_stream_row* rows, int64_t* m0, int64_t* m1,
+                                int64_t* k0, int64_t* k1) {
+  if (L < 1 || M < 1 || H < 0 || up < 1 || !rows || B < 1 || B > vsp::STREAM_ROWS_MAX) return VSP_ERR_ARG;
+  for (int b = 0; b < B; ++b)
+    if (rows[b].f0 < 0 || rows[b].f1 <= rows[b].f0 || rows[b].f1 > rows[b].L) return VSP_ERR_ARG;
+  for (int b = 0; b < B; ++b) {
+    const vsp_stream_row& r = rows[b];
+    const vsp::StreamOutPlan p = vsp::stream_output_plan((int64_t)r.f0 * up, (int64_t)(r.f1 - r.f0) * up, r.f1 == r.L, L, M, H);
+    if (m0) m0[b] = p.m0;
+    if (m1) m1[b] = p.m1;
+    if (k0) k0[b] = p.k0;
+    if (k1) k1[b] = p.k1;
+  }
+  return VSP_OK;
+}
+
+namespace vsp {
+hipError_t launch_stream_output(const float* o_span, long o_bs, const StreamOutRows& rows, int B, const StreamOutFilter& f,
+                                int K, void* out, long out_stride, int pcm, hipStream_t s) {
+  if (B <= 0 || B > STREAM_ROWS_MAX || !o_span || !out || out_stride <= 0 || o_bs <= 0 || !f.tab || f.L < 1 || f.M < 1 ||
+      f.H < 0 || f.P < 1 || K < 0)
+    return hipErrorInvalidValue;
+  for (int b = 0; b < B; ++b) {
+    const StreamOutRow& r = rows.r[b];
+    if (r.x_first < 0 || r.off < 0 || r.n <= 0 || (long)r.off + r.n > o_bs) return hipErrorInvalidValue;
+    const StreamOutPlan p = stream_output_plan(r.x_first, r.n, r.ended != 0, f.L, f.M, f.H);
+    const int64_t h_in = r.x_first - p.k0, h_out = r.x_first + r.n - p.k1;
+    if (p.m1 - p.m0 > out_stride || h_in > K || h_out > K || (h_in > 0 && !r.hist_in) || (h_out > 0 && !r.hist_out) ||
+        (r.hist_out && r.hist_in == r.hist_out))
+      return hipErrorInvalidValue;
+  }
+  const int out_blocks = (int)((out_stride + RS_TILE - 1) / RS_TILE), hist_blocks = (K + RS_TILE - 1) / RS_TILE;
+  const int pair_ok = pcm && ((uintptr_t)out % 4 == 0) && (out_stride % 2 == 0);
+  hipLaunchKernelGGL(stream_output_kernel, dim3(out_blocks + hist_blocks, B), dim3(RS_TILE), 0, s, rows, o_span, o_bs, f, K,
+                     out_blocks, out, out_stride, pcm, pair_ok);
+  return hipGetLastError();
+}
+}  // namespace vsp
 
 int vsp_output_configure(vsp_ctx* ctx, int in_rate, int out_rate, int zeros, double beta, double rolloff) {
   if (!ctx) return VSP_ERR_ARG;

@@ -26,6 +26,25 @@ def _dev_i64(t, device) -> torch.Tensor:
     return torch.as_tensor(t).to(device=device, dtype=torch.int64).contiguous()
 
 
+class OutputHistory:
+    """What a streamed request keeps between two ``Engine.generator_stream_rows_output`` calls: a [2, K] float32 device
+    tensor -- the input samples the next outputs still need, K = ``vsp_output_history_samples`` -- and which side is
+    current.  A call reads the current side, writes the other, then flips."""
+
+    def __init__(self, K: int, device):
+        self.buf = torch.empty((2, max(K, 0)), dtype=torch.float32, device=device)
+        self.side = 0
+
+    def pointers(self):
+        """(hist_in, hist_out) as integers; None for both when K = 0 (the pass-through keeps nothing)."""
+        if self.buf.shape[1] == 0:
+            return None, None
+        return self.buf[self.side].data_ptr(), self.buf[1 - self.side].data_ptr()
+
+    def flip(self) -> None:
+        self.side = 1 - self.side
+
+
 class Engine:
     def __init__(self, dims: ModelDims, device: "torch.device | str | int" = "cuda:0"):
         self.lib = _lib.lib()                      # raises ImportError if the extension is absent
@@ -598,21 +617,15 @@ class Engine:
         ``f1 - f0 <= chunk_frames``.  Returns [B, chunk_frames * up], int16 if ``pcm`` else float32: row b holds its
         (f1 - f0) * up samples -- those of ``generator_ragged`` on the utterance alone -- and zeros behind them."""
         rows = list(rows)
-        B, up, d = len(rows), self.dims.total_upsample, self.dims
+        B, up = len(rows), self.dims.total_upsample
         if not 1 <= B <= _lib.STREAM_ROWS_MAX:
             raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
         arr = (_lib.VspStreamRow * B)()
         keep = []
         for r, (z, g, L, f0, f1) in zip(arr, rows):
-            if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.device != self.device or z.dim() != 2
-                    or z.shape[0] != d.inter_channels or z.shape[1] < int(L) or (z.shape[1] > 1 and z.stride(1) != 1)):
-                raise ValueError("a row's z must be a float32 [inter_channels, >= L] tensor on the engine's device with "
-                                 "contiguous frames")
-            g = _dev_f32(g, self.device).reshape(-1)
-            if g.numel() != d.gin_channels:
-                raise ValueError(f"a row's g must have {d.gin_channels} entries")
+            z, g, stride = self._stream_row_args(z, g, L)
             keep.append((z, g))
-            r.z, r.z_channel_stride, r.g = z.data_ptr(), max(int(z.stride(0)), int(L)), g.data_ptr()
+            r.z, r.z_channel_stride, r.g = z.data_ptr(), stride, g.data_ptr()
             r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
         chunk_frames = int(chunk_frames)
         out = torch.empty((B, max(chunk_frames, 0) * up), dtype=torch.int16 if pcm else torch.float32, device=self.device)
@@ -623,6 +636,83 @@ class Engine:
                                                     int(bool(pcm)), _ptr(ws), ws.numel())
         _lib.check(rc, self.ctx, "vsp_generator_stream_rows")
         return out
+
+    def _stream_row_args(self, z, g, L):
+        """Checks one row's latent and speaker vector; returns (z, g) to keep alive and the row's channel stride."""
+        d = self.dims
+        if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.device != self.device or z.dim() != 2
+                or z.shape[0] != d.inter_channels or z.shape[1] < int(L) or (z.shape[1] > 1 and z.stride(1) != 1)):
+            raise ValueError("a row's z must be a float32 [inter_channels, >= L] tensor on the engine's device with "
+                             "contiguous frames")
+        g = _dev_f32(g, self.device).reshape(-1)
+        if g.numel() != d.gin_channels:
+            raise ValueError(f"a row's g must have {d.gin_channels} entries")
+        return z, g, max(int(z.stride(0)), int(L))
+
+    def stream_rows_output_plan(self, rows):
+        """``vsp_stream_rows_output_plan`` (host only) for the configured output stage: ([m0], [m1], [k0], [k1]) of rows
+        given as (L, f0, f1) triples -- the tick delivers output samples [m0, m1), reads the history from input sample k0
+        and leaves the history from k1 (``vispeech_amd.output_stage.complete_outputs`` / ``history_start``)."""
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        rows = list(rows)
+        n = max(len(rows), 1)
+        arr = (_lib.VspStreamRow * n)()
+        for r, (L, f0, f1) in zip(arr, rows):
+            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        res = [(C.c_int64 * n)() for _ in range(4)]
+        Lo, Mo, Ho = self.output_plan
+        _lib.check(self.lib.vsp_stream_rows_output_plan(Lo, Mo, Ho, self.dims.total_upsample, len(rows), arr, *res), None,
+                   "vsp_stream_rows_output_plan")
+        return tuple(list(a)[:len(rows)] for a in res)
+
+    def output_history(self) -> "OutputHistory":
+        """The state one streamed request carries through ``generator_stream_rows_output``."""
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        return OutputHistory(int(self.lib.vsp_output_history_samples(*self.output_plan)), self.device)
+
+    def stream_rows_out_samples(self, chunk_frames: int) -> int:
+        """``vsp_stream_rows_out_samples``: the row length of ``generator_stream_rows_output`` for chunks of up to
+        ``chunk_frames`` frames."""
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+        n = int(self.lib.vsp_stream_rows_out_samples(*self.output_plan, self.dims.total_upsample, int(chunk_frames)))
+        if n < 0:
+            _lib.check(n, None, "vsp_stream_rows_out_samples")
+        return n
+
+    def generator_stream_rows_output(self, rows, chunk_frames: int, pcm: bool = True):
+        """``vsp_generator_stream_rows_output``: ``generator_stream_rows`` with the ragged output stage instead of the
+        collect -- one launch set per tick, delivered at the output rate.  ``rows`` is a sequence of
+        ``(z, g, L, f0, f1, state)``, ``state`` the request's ``OutputHistory`` (``output_history()``; its sides are swapped
+        here).  A request's ticks must be consecutive: f0 of a call is f1 of its previous one.  Returns
+        ``(out [B, stream_rows_out_samples(chunk_frames)], counts)``: row b holds its ``counts[b]`` output samples --
+        those ``output`` returns one-shot for the concatenated float chunks, bit for bit -- and zeros behind them."""
+        rows = list(rows)
+        B = len(rows)
+        if not 1 <= B <= _lib.STREAM_ROWS_MAX:
+            raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
+        m0, m1, _, _ = self.stream_rows_output_plan([(L, f0, f1) for _, _, L, f0, f1, _ in rows])
+        arr = (_lib.VspStreamRowOut * B)()
+        keep = []
+        for r, (z, g, L, f0, f1, state) in zip(arr, rows):
+            z, g, stride = self._stream_row_args(z, g, L)
+            keep.append((z, g))
+            r.row.z, r.row.z_channel_stride, r.row.g = z.data_ptr(), stride, g.data_ptr()
+            r.row.L, r.row.f0, r.row.f1 = int(L), int(f0), int(f1)
+            r.hist_in, r.hist_out = state.pointers()
+        out = torch.empty((B, self.stream_rows_out_samples(chunk_frames)), dtype=torch.int16 if pcm else torch.float32,
+                          device=self.device)
+        ws = self._workspace("generator_stream_rows",
+                             self.lib.vsp_generator_stream_rows_workspace_bytes(self.ctx, B, int(chunk_frames)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_generator_stream_rows_output(self.ctx, self._stream(), B, arr, _ptr(out), out.shape[1],
+                                                           int(bool(pcm)), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_generator_stream_rows_output")
+        for row in rows:
+            row[5].flip()
+        return out, [int(b - a) for a, b in zip(m0, m1)]
 
     # ------------------------------------------------------------------ output stage
     def configure_output(self, out_rate: Optional[int], zeros: int = 32, beta: float = 9.62,

@@ -456,6 +456,7 @@ class _StreamRequest:
         self.held = None              # float chunks that complete no output sample yet (merged into the next window)
         self.seen = self.m_next = 0
         self.last = False
+        self.history = None           # ``fused_output``: the request's Engine.output_history(), from admission on
 
 
 class StreamingBatchService:
@@ -475,14 +476,19 @@ class StreamingBatchService:
 
     A request's audio is what the reference returns for it alone (isolated mode + the halo of the streamed vocoder), whoever
     shares its ticks.  ``output_rate``: each request's float chunk goes through its own ``Engine.output_stream`` (one small
-    launch per request per tick); the bytes are those of the one-shot output stage.  ``stats``: ticks, rows per tick and
+    launch and one copy per request per tick); the bytes are those of the one-shot output stage.  With ``fused_output=True``
+    the tick instead makes one ``Engine.generator_stream_rows_output`` call -- the ragged output stage in place of the
+    collect launch -- and one device-to-host copy, as the plain path does; a request carries its filter history
+    (``Engine.output_history``) from admission on, and the bytes are the same.  ``stats``: ticks, rows per tick and
     admitted groups.  No priorities, no retries, no backpressure."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
-                 sampling_rate: int = 44100, autostart: bool = True):
+                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False):
         if not 1 <= max_batch <= 64 or chunk_frames < 1:
             raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
+        if fused_output and output_rate is None:
+            raise ValueError("fused_output needs an output_rate")
         if first_chunk_frames is not None and not 1 <= first_chunk_frames <= chunk_frames:
             raise ValueError("1 <= first_chunk_frames <= chunk_frames")
         if collate is None:
@@ -495,6 +501,7 @@ class StreamingBatchService:
         self.first_chunk_frames = None if first_chunk_frames is None else int(first_chunk_frames)
         self.noise_scale = float(noise_scale)
         self.output_rate = None if output_rate is None else int(output_rate)
+        self.fused_output = bool(fused_output)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self.stats = {"ticks": 0, "rows_per_tick": [], "groups": 0}
@@ -588,6 +595,8 @@ class StreamingBatchService:
                     r.stream._q.put(_RowStream._END)          # nothing to synthesise: no bytes
                     continue
                 r.z, r.g = z[b], enc["g"][b]
+                if self.fused_output:
+                    r.history = eng.output_history()
                 self._active.append(r)
         except Exception as e:                 # this group's requests fail; the active ones and the service live on
             for r in group:
@@ -604,6 +613,16 @@ class StreamingBatchService:
             counts.append(f1 - r.pos)
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
+        if self.fused_output:
+            out, done = eng.generator_stream_rows_output([row + (r.history,) for row, r in zip(rows, self._active)],
+                                                         self.chunk_frames, pcm=True)
+            block = _host_i16_2d(out)                                        # the tick's one device-to-host copy
+            self._check_numerics()
+            for b, (r, n) in enumerate(zip(self._active, counts)):
+                r.pos += n
+                if done[b]:
+                    r.stream._q.put(block[b, : done[b]].tobytes())
+            return
         out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=self.output_rate is None)
         if self.output_rate is None:
             block = _host_i16_2d(out)                                        # the tick's one device-to-host copy
