@@ -166,7 +166,8 @@ int vsp_weight_arena(const vsp_ctx* ctx, void** dev_arena, int64_t* bytes);
  *   speaker embedding, TextEncoder, duration / F0 / energy (predicted, or the *_ctl tensor when
  *   non-NULL -- the reference's isinstance(.., torch.Tensor) branches), pitch/energy prenets.
  * Inputs (device): phonemes[B*Tp] int64, lengths[B] int64, sid[B] int64; *_ctl [B*Tp] float or NULL
- *   with the scalar controls used instead (reference defaults 1.0).
+ *   with the scalar controls used instead (reference defaults 1.0).  With a row table (vsp_set_row_controls, isolated
+ *   mode) the choice and the scale are row b's own and the three scalar arguments are not read.
  * Outputs (device): x_var [B][H][Tp] (text encoding + prenets, the length regulator's input),
  *   g [B][gin], duration/f0/energy [B*Tp], frame_lengths[B] int64, cum_dur [B*Tp] int32.
  * workspace: >= vsp_encode_workspace_bytes(ctx,B,Tp). */
@@ -195,7 +196,8 @@ int vsp_frame_lengths_host(vsp_ctx* ctx, void* stream, int B, const int64_t* fra
  * noise [B][inter][Tf], or NULL: then the library draws it on the device -- vsp_randn(noise_seed) over the same
  * [B][inter][Tf] elements (ABI 4; the torch.randn_like(m_p) of models.py:718 for callers without a generator.  It is a
  * Philox4x32-10 stream of its own, NOT bit-compatible with torch.manual_seed(noise_seed); pass the tensor to
- * reproduce a torch run).  noise_seed is ignored when noise != NULL or noise_scale == 0.
+ * reproduce a torch run).  noise_seed is ignored when noise != NULL or noise_scale == 0.  With a row table
+ * (vsp_set_row_controls) row b's noise_scale replaces the argument, and noise is drawn iff some row's is non-zero.
  * Outputs (device, contiguous): o, x_mask[B*Tf] uint8, z, z_p, m_p, logs_p [B][inter][Tf]. */
 int64_t vsp_decode_workspace_bytes(const vsp_ctx* ctx, int B, int Tp, int Tf);
 int vsp_decode(vsp_ctx* ctx, void* stream, int B, int Tp, int Tf, int max_len,
@@ -398,6 +400,33 @@ int vsp_get_isolated(const vsp_ctx* ctx);
  * a drawing call whose B differs from the seeds set fails with VSP_ERR_STATE.  The noise_seed argument and
  * vsp_set_noise_offset are not read in isolated mode. */
 int vsp_set_noise_seeds(vsp_ctx* ctx, const uint64_t* seeds_host, int B);
+
+/* ---- per-row controls (ABI 7, additive; round 13): every utterance of a batch with its own arguments ---------- */
+/* Isolated mode makes row b of a batch what the reference returns for a B = 1 call; a row table makes that call's
+ * ARGUMENTS per row.  With a table set, every tensor vsp_encode / vsp_decode / vsp_infer return, restricted to utterance
+ * b's extent, is what the reference's infer (models.py:672-722) returns for a B = 1 call on b's unpadded inputs with
+ *   duration_control = row b of duration_ctl if rows[b].given & VSP_GIVEN_DURATION, else the scalar rows[b].duration_scale
+ *   pitch_control    = row b of pitch_ctl    if rows[b].given & VSP_GIVEN_PITCH,    else the scalar rows[b].pitch_scale
+ *   energy_control   = row b of energy_ctl   if rows[b].given & VSP_GIVEN_ENERGY,   else the scalar rows[b].energy_scale
+ *   noise_scale      = rows[b].noise_scale.
+ * A scale whose control is given is not read (the reference's tensor branch has no scalar).  A *_ctl pointer may be NULL
+ * only if no row has that bit set (else VSP_ERR_ARG); rows of a *_ctl tensor whose bit is clear may hold anything and are
+ * never read.  A predictor runs iff some row lacks its bit; library-drawn noise (noise == NULL, vsp_set_noise_seeds) is
+ * drawn iff some row's noise_scale is non-zero, and a row with noise_scale == 0 gets z_p = m_p exactly.
+ * State: sticky host state, copied (rows_host [B]; B = 0 forgets the table); each call copies the table into ITS
+ * workspace.  While a table is set the scalar duration_scale / pitch_scale / energy_scale / noise_scale arguments of
+ * vsp_encode / vsp_decode / vsp_infer are not read; a call whose B differs from the table's, or a call made while the
+ * context is not isolated (per-row values have no reference meaning in a padded batch), returns VSP_ERR_STATE.
+ * Validation needs no device: a non-finite scale, unknown `given` bits, B < 0, or NULL rows with B > 0: VSP_ERR_ARG.
+ * Nothing changes for callers that never set a table: the scalar launches run exactly as before. */
+#define VSP_GIVEN_DURATION 1u
+#define VSP_GIVEN_PITCH    2u
+#define VSP_GIVEN_ENERGY   4u
+typedef struct vsp_row_control {
+  float duration_scale, pitch_scale, energy_scale, noise_scale;
+  uint32_t given;
+} vsp_row_control;
+int vsp_set_row_controls(vsp_ctx* ctx, const vsp_row_control* rows_host, int B);
 
 /* ---- mel spectrogram (reference mel_processing.py:73-112) --------------------------------- */
 /* The mel basis the reference takes from librosa.filters.mel(sampling_rate, n_fft, n_mels, fmin, fmax) with that

@@ -53,6 +53,14 @@ class VspStreamRowOut(C.Structure):
     _fields_ = [("row", VspStreamRow), ("hist_in", C.c_void_p), ("hist_out", C.c_void_p)]
 
 
+class VspRowControl(C.Structure):
+    """``vsp_row_control``: one utterance's own scales and which of its controls are given (``GIVEN_*`` bits)."""
+    _fields_ = [("duration_scale", C.c_float), ("pitch_scale", C.c_float), ("energy_scale", C.c_float),
+                ("noise_scale", C.c_float), ("given", C.c_uint32)]
+
+
+GIVEN_DURATION, GIVEN_PITCH, GIVEN_ENERGY = 1, 2, 4                  # VSP_GIVEN_* (vsp_set_row_controls)
+
 STREAM_ROWS_MAX = 64
 
 _P = C.c_void_p
@@ -96,6 +104,7 @@ SIGNATURES = {
     "vsp_set_isolated": (_I, [_P, _I]),
     "vsp_get_isolated": (_I, [_P]),
     "vsp_set_noise_seeds": (_I, [_P, C.POINTER(_U64), _I]),
+    "vsp_set_row_controls": (_I, [_P, C.POINTER(VspRowControl), _I]),
     "vsp_encoder_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_encoder": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I64]),
     "vsp_length_regulate": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),

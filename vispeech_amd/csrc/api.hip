@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "model.h"
+#include "row_controls.h"
 
 using namespace vsp;
 
@@ -1192,6 +1193,17 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   // behind an utterance's end (what a B = 1 call's zero padding is), the EnergyPredictor masks like the duration
   // predictor, and every output is zero behind its extent.
   const bool iso = ctx->isolated;
+  // Per-row controls (vsp_set_row_controls; the entry points have checked B, the mode and the *_ctl pointers): a control's
+  // given path runs alone iff EVERY row has it, its predictor runs iff some row lacks it, and the per-row kernels select
+  // the source and the scale by row.  No table: the *_ctl pointers decide for the whole batch, as they always did.
+  const std::vector<vsp_row_control>& rows = ctx->row_controls;
+  const bool per_row = !rows.empty() && !ws.dry;   // (sizing: the largest launch set, whatever the context holds)
+  auto all_given = [&](uint32_t bit, const float* ctl) {
+    if (!per_row) return ctl != nullptr;
+    return std::all_of(rows.begin(), rows.end(), [bit](const vsp_row_control& r) { return (r.given & bit) != 0; });
+  };
+  const bool dur_given = all_given(VSP_GIVEN_DURATION, dctl), pit_given = all_given(VSP_GIVEN_PITCH, pctl),
+             en_given = all_given(VSP_GIVEN_ENERGY, ectl);
   const T3 XV = ext(x_var, h, Tp);
   T3 XE = ws.t3(B, h, Tp), TMP = ws.t3(B, h, Tp);
   float* cvec = ws.f((size_t)B * h);
@@ -1201,7 +1213,13 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   // duration-predictor / energy-predictor activations
   const int fmax_ = std::max(c.dur_filter, c.energy_filter);
   T3 P1 = ws.t3(B, fmax_, Tp), P2 = ws.t3(B, fmax_, Tp);
+  // the row table of THIS call (counted in every state: workspace sizes do not depend on context state)
+  vsp_row_control* rows_dev = reinterpret_cast<vsp_row_control*>(ws.bytes((size_t)B * sizeof(vsp_row_control)));
   const bool live = !ws.dry && !ws.overflow;
+  // (pageable source, like the noise seeds of vsp_decode: staged before this call returns, so a later
+  // vsp_set_row_controls may replace the vector while the copy is still queued)
+  if (live && per_row)
+    r.chk(hipMemcpyAsync(rows_dev, rows.data(), (size_t)B * sizeof(vsp_row_control), hipMemcpyHostToDevice, s), "row controls");
   if (live) {
     r.chk(launch_gather_rows(sid, r.A(m.emb_g), c.n_speakers, g, B, gin, s), "emb_g");
     r.chk(launch_embed(phonemes, r.A(m.emb_sym), c.n_vocab, sqrtf((float)h), XE.p, XE.bs, XE.cs, B, h, Tp, s),
@@ -1210,7 +1228,7 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   // ---- given durations (models.py:681): the frame counts need nothing computed here -- derive them FIRST and start their
   // copy to the host, so that vsp_frame_lengths_host returns while the text encoder runs (vsp_ctx::fl_pinned)
   if (live) { ctx->fl_src = nullptr; ctx->fl_known_src = nullptr; }
-  if (dctl && live) {
+  if (dur_given && live) {
     r.chk(hipMemcpyAsync(duration, dctl, (size_t)B * Tp * sizeof(float), hipMemcpyDeviceToDevice, s), "dur copy");
     // (a caller's pad values would count as frames: the reference's regulator loops over all Tp)
     if (iso) r.chk(launch_mask_rows(lengths, B, Tp, duration, nullptr, nullptr, nullptr, s), "duration mask");
@@ -1225,7 +1243,7 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
   mask3(r, XE, lengths, B, h, Tp);  // TextEncoder passes x * x_mask (models.py:173)
   run_encoder_masked(r, m.enc[0], B, Tp, XE, lengths, XV);   // XV = x_enc
   // ---- duration (models.py:681-688, 119-133)
-  if (!dctl) {
+  if (!dur_given) {
     const int f = c.dur_filter;
     T3 A1 = P1, A2 = P2;
     r.cond(m.dur_cond, g, cvec, B);
@@ -1240,12 +1258,13 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
     r.ln(A2, T3{}, m.dur_g2, m.dur_b2, A2, B, f, Tp);
     if (live) {
       r.chk(launch_chan_dot(A2.p, A2.bs, A2.cs, r.A(m.dur_pw), r.A(m.dur_pb), lengths, 1, 1, pred, B, f, Tp, s), "dur proj");
-      r.chk(launch_duration_from_logw(pred, lengths, dscale, duration, B, Tp, s), "duration");
+      if (per_row) r.chk(launch_duration_rows(pred, dctl, lengths, rows_dev, duration, B, Tp, s), "duration rows");
+      else r.chk(launch_duration_from_logw(pred, lengths, dscale, duration, B, Tp, s), "duration");
       if (iso) r.chk(launch_mask_rows(lengths, B, Tp, duration, nullptr, nullptr, nullptr, s), "duration mask");   // (ceil(-scale) at the pad)
     }
   }
   // ---- pitch (models.py:691-698, 505-514)
-  if (!pctl) {
+  if (!pit_given) {
     T3 PI = ws.t3(B, h, Tp);
     r.cond(m.pit_cond, g, cvec, B);
     if (live) r.chk(launch_add_cond(XV.p, XV.bs, XV.cs, cvec, h, TMP.p, TMP.bs, TMP.cs, B, h, Tp, s), "add_cond");
@@ -1254,13 +1273,14 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
     if (live) r.chk(launch_chan_dot(PI.p, PI.bs, PI.cs, r.A(m.pit_pw), r.A(m.pit_pb), lengths, 1, 0, pred, B, h, Tp, s), "proj_f0");
   }
   if (live) {
-    r.chk(launch_pitch(pctl, pred, pscale, lf0, f0, B * Tp, s), "pitch");
+    if (per_row) r.chk(launch_pitch_rows(pctl, pred, rows_dev, lf0, f0, B, Tp, s), "pitch rows");
+    else r.chk(launch_pitch(pctl, pred, pscale, lf0, f0, B * Tp, s), "pitch");
     // (the predicted lf0 carries proj_f0's bias at the pad, a control whatever the caller left there)
     if (iso) r.chk(launch_mask_rows(lengths, B, Tp, lf0, f0, nullptr, nullptr, s), "pitch mask");
     r.chk(launch_prenet_add(XV.p, XV.bs, XV.cs, r.A(m.ppre_w), r.A(m.ppre_b), lf0, B, h, Tp, s), "pitch_prenet");
   }
   // ---- energy (models.py:701-708; frame_prior_network.py:104-124: no mask anywhere)
-  if (!ectl) {
+  if (!en_given) {
     const int e = c.energy_filter;
     T3 A1 = P1, A2 = P2;
     r.cond(m.en_cond, g, cvec, B);
@@ -1278,16 +1298,34 @@ static int encode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, const
     if (live) r.chk(launch_chan_dot(A2.p, A2.bs, A2.cs, r.A(m.en_lw), r.A(m.en_lb), nullptr, 0, 0, pred, B, e, Tp, s), "energy linear");
   }
   if (live) {
-    r.chk(launch_energy(ectl, pred, escale, norm_e, energy, B * Tp, s), "energy");
+    if (per_row) r.chk(launch_energy_rows(ectl, pred, rows_dev, norm_e, energy, B, Tp, s), "energy rows");
+    else r.chk(launch_energy(ectl, pred, escale, norm_e, energy, B * Tp, s), "energy");
     // (norm_energy, not the control: a zero energy control is norm_energy = -60 / 36 at the pad)
     if (iso) r.chk(launch_mask_rows(lengths, B, Tp, norm_e, energy, nullptr, nullptr, s), "energy mask");
     r.chk(launch_prenet_add(XV.p, XV.bs, XV.cs, r.A(m.epre_w), r.A(m.epre_b), norm_e, B, h, Tp, s), "energy_prenet");
     // (the regulator never reads x_var behind an utterance's end; zero all the same: the stage's output contract)
     if (iso) r.chk(launch_mask3(XV.p, XV.bs, XV.cs, lengths, B, h, Tp, s), "x_var mask");
-    if (!dctl) r.chk(launch_duration_cumsum(duration, cum_dur, frame_lengths, B, Tp, s, ctx->flags_dev), "duration cumsum");
+    if (!dur_given) r.chk(launch_duration_cumsum(duration, cum_dur, frame_lengths, B, Tp, s, ctx->flags_dev), "duration cumsum");
   }
   if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "encode workspace too small (need %zu bytes)", ws.cur);
   return r.rc;
+}
+
+// Per-row controls at an entry point.  Host state only, so it runs before anything that needs the device or the weights:
+// a table has a meaning in isolated mode only, holds for one batch size, and a control some row is given must be there.
+static int check_row_controls(vsp_ctx* ctx, int B, const char* fn, bool encodes, const float* dctl, const float* pctl,
+                              const float* ectl) {
+  if (!ctx || ctx->row_controls.empty()) return VSP_OK;
+  if (!ctx->isolated)
+    return ctx->fail(VSP_ERR_STATE, "%s: row controls are set but the context is not isolated (vsp_set_isolated)", fn);
+  if ((int)ctx->row_controls.size() != B)
+    return ctx->fail(VSP_ERR_STATE, "%s: row controls are set for B = %d, the call has B = %d", fn, (int)ctx->row_controls.size(), B);
+  if (!encodes) return VSP_OK;
+  uint32_t any = 0;
+  for (const vsp_row_control& rc : ctx->row_controls) any |= rc.given;
+  if (((any & VSP_GIVEN_DURATION) && !dctl) || ((any & VSP_GIVEN_PITCH) && !pctl) || ((any & VSP_GIVEN_ENERGY) && !ectl))
+    return ctx->fail(VSP_ERR_ARG, "%s: a row is given a control whose tensor is NULL", fn);
+  return VSP_OK;
 }
 
 int64_t vsp_encode_workspace_bytes(const vsp_ctx* ctx, int B, int Tp) {
@@ -1303,7 +1341,8 @@ int vsp_encode(vsp_ctx* ctx, void* stream, int B, int Tp, const int64_t* phoneme
                float duration_scale, float pitch_scale, float energy_scale, float* x_var, float* g, float* duration,
                float* f0, float* energy, int64_t* frame_lengths, int32_t* cum_dur, void* workspace,
                int64_t workspace_bytes) {
-  int rc = check_ready(ctx);
+  int rc = check_row_controls(ctx, B, "vsp_encode", true, duration_ctl, pitch_ctl, energy_ctl);
+  if (rc == VSP_OK) rc = check_ready(ctx);
   if (rc) return rc;
   if (B <= 0 || Tp <= 0 || !phonemes || !lengths || !sid || !x_var || !g || !duration || !f0 || !energy ||
       !frame_lengths || !cum_dur || !workspace)
@@ -1355,8 +1394,17 @@ static int decode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, int T
   // noise == NULL: the library draws it (Philox4x32-10 keyed by noise_seed) -- the torch.randn_like of models.py:718
   float* drawn = ws.f((size_t)B * inter * Tf);
   uint64_t* seeds_dev = reinterpret_cast<uint64_t*>(ws.bytes((size_t)B * sizeof(uint64_t)));
+  vsp_row_control* rows_dev = reinterpret_cast<vsp_row_control*>(ws.bytes((size_t)B * sizeof(vsp_row_control)));
   const bool live = !ws.dry && !ws.overflow;
-  if (live && !noise && noise_scale != 0.f && r.iso) {
+  // per-row controls (vsp_set_row_controls): noise_scale[b] replaces the argument -- noise is drawn iff some row's is
+  // non-zero -- and the table is copied into THIS call's workspace, as the seeds are
+  const std::vector<vsp_row_control>& rows = ctx->row_controls;
+  const bool per_row = !rows.empty();
+  const bool want_noise = per_row ? std::any_of(rows.begin(), rows.end(), [](const vsp_row_control& rc) { return rc.noise_scale != 0.f; })
+                                  : noise_scale != 0.f;
+  if (live && per_row)
+    r.chk(hipMemcpyAsync(rows_dev, rows.data(), (size_t)B * sizeof(vsp_row_control), hipMemcpyHostToDevice, s), "row controls");
+  if (live && !noise && want_noise && r.iso) {
     // isolated mode: utterance b's own draw, keyed seeds[b], laid out [inter][L_b] -- what a B = 1 call with Tf = L_b and
     // noise_seed = seeds[b] draws (vsp_set_noise_seeds; noise_seed and the noise offset are not read)
     if ((int)ctx->noise_seeds.size() != B)
@@ -1368,7 +1416,7 @@ static int decode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, int T
     r.chk(hipMemcpyAsync(seeds_dev, ctx->noise_seeds.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, s), "noise seeds");
     if (r.ok()) r.chk(launch_randn_ragged(seeds_dev, frame_lengths, B, inter, Tf, drawn, s), "randn_ragged");
     noise = drawn;
-  } else if (live && !noise && noise_scale != 0.f) {
+  } else if (live && !noise && want_noise) {
     r.chk(launch_randn(noise_seed, (long)ctx->noise_first, (long)B * inter * Tf, drawn, s), "randn");
     noise = drawn;
   }
@@ -1385,7 +1433,9 @@ static int decode_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int Tp, int T
   r.conv(a, B);
   if (live) {
     const long n = (long)B * inter * Tf;
-    r.chk(launch_reparam(m_p, logs_p, noise, noise_scale, z_p, n, s, z, ctx->flags_dev), "reparam");   // (z = z_p: the flow transforms z in place)
+    // (z = z_p: the flow transforms z in place)
+    if (per_row) r.chk(launch_reparam_rows(m_p, logs_p, noise, rows_dev, z_p, B, (long)inter * Tf, s, z, ctx->flags_dev), "reparam rows");
+    else r.chk(launch_reparam(m_p, logs_p, noise, noise_scale, z_p, n, s, z, ctx->flags_dev), "reparam");
     if (r.iso) {   // m_p = logs_p = 0 at the pad: z_p is noise * noise_scale there
       r.chk(launch_mask3(z_p, (long)inter * Tf, Tf, frame_lengths, B, inter, Tf, s), "z_p mask");
       r.chk(launch_mask3(z, (long)inter * Tf, Tf, frame_lengths, B, inter, Tf, s), "z mask");
@@ -1410,7 +1460,8 @@ int vsp_decode(vsp_ctx* ctx, void* stream, int B, int Tp, int Tf, int max_len, c
                const int32_t* cum_dur, const int64_t* frame_lengths, const float* noise, uint64_t noise_seed,
                float noise_scale, float* o, uint8_t* x_mask, float* z, float* z_p, float* m_p, float* logs_p,
                void* workspace, int64_t workspace_bytes) {
-  int rc = check_ready(ctx);
+  int rc = check_row_controls(ctx, B, "vsp_decode", false, nullptr, nullptr, nullptr);
+  if (rc == VSP_OK) rc = check_ready(ctx);
   if (rc) return rc;
   if (B <= 0 || Tp <= 0 || Tf <= 0 || !x_var || !g || !cum_dur || !frame_lengths || !o || !x_mask || !z || !z_p ||
       !m_p || !logs_p || !workspace)
@@ -1460,7 +1511,8 @@ int vsp_infer(vsp_ctx* ctx, void* stream, int B, int Tp, int tf_pad, int max_len
               uint64_t noise_seed, float noise_scale, float* o, uint8_t* x_mask, float* z, float* z_p, float* m_p, float* logs_p,
               float* duration, float* f0, float* energy, int64_t* frame_lengths, void* workspace,
               int64_t workspace_bytes) {
-  int rc = check_ready(ctx);
+  int rc = check_row_controls(ctx, B, "vsp_infer", true, duration_ctl, pitch_ctl, energy_ctl);
+  if (rc == VSP_OK) rc = check_ready(ctx);
   if (rc) return rc;
   if (B <= 0 || Tp <= 0 || tf_pad <= 0 || !phonemes || !lengths || !sid || !o || !x_mask || !z || !z_p || !m_p ||
       !logs_p || !duration || !f0 || !energy || !frame_lengths || !workspace)
@@ -1675,6 +1727,21 @@ int vsp_set_noise_seeds(vsp_ctx* ctx, const uint64_t* seeds_host, int B) {
   if (!ctx) return VSP_ERR_ARG;
   if (B < 0 || (B > 0 && !seeds_host)) return ctx->fail(VSP_ERR_ARG, "vsp_set_noise_seeds: B < 0 or null seeds");
   ctx->noise_seeds.assign(seeds_host, seeds_host + B);     // (B = 0 forgets them)
+  return VSP_OK;
+}
+
+int vsp_set_row_controls(vsp_ctx* ctx, const vsp_row_control* rows_host, int B) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (B < 0 || (B > 0 && !rows_host)) return ctx->fail(VSP_ERR_ARG, "vsp_set_row_controls: B < 0 or null rows");
+  const uint32_t known = VSP_GIVEN_DURATION | VSP_GIVEN_PITCH | VSP_GIVEN_ENERGY;
+  for (int b = 0; b < B; ++b) {
+    const vsp_row_control& rc = rows_host[b];
+    if (rc.given & ~known) return ctx->fail(VSP_ERR_ARG, "vsp_set_row_controls: row %d has unknown given bits 0x%x", b, rc.given);
+    if (!std::isfinite(rc.duration_scale) || !std::isfinite(rc.pitch_scale) || !std::isfinite(rc.energy_scale) ||
+        !std::isfinite(rc.noise_scale))
+      return ctx->fail(VSP_ERR_ARG, "vsp_set_row_controls: row %d has a scale that is not finite", b);
+  }
+  ctx->row_controls.assign(rows_host, rows_host + B);     // (B = 0 forgets the table; a refused table changes nothing)
   return VSP_OK;
 }
 

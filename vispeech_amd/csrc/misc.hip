@@ -3,6 +3,7 @@
 // rational-quadratic spline.  All tensors are [B][C][T] float32 with T contiguous; threads run
 // along T so that every global access is coalesced.
 #include "kernels.h"
+#include "row_controls.h"   // (the control formulas, shared with the per-row kernels)
 
 #include <math.h>
 
@@ -248,8 +249,7 @@ __global__ void duration_kernel(const float* __restrict__ logw, const int64_t* _
   const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
   if (t >= T) return;
   const float m = t < (int)lengths[b] ? 1.f : 0.f;
-  const float e = expf(logw[(size_t)b * T + t]) * m;
-  dur[(size_t)b * T + t] = ceilf((e - 1.f) * scale);
+  dur[(size_t)b * T + t] = duration_from_logw(logw[(size_t)b * T + t], m, scale);
 }
 hipError_t launch_duration_from_logw(const float* logw, const int64_t* lengths, float scale, float* dur, int B,
                                      int T, hipStream_t s) {
@@ -264,12 +264,12 @@ __global__ void pitch_kernel(const float* __restrict__ pitch_ctl, const float* _
   if (i >= n) return;
   float l;
   if (pitch_ctl) {
-    l = (2595.f * log10f(1.f + pitch_ctl[i] / 700.f)) / 500.f;
+    l = lf0_from_control(pitch_ctl[i]);
   } else {
-    l = lf0_pred[i] * scale;
+    l = lf0_from_prediction(lf0_pred[i], scale);
   }
   lf0[i] = l;
-  f0[i] = (powf(10.f, l * 500.f / 2590.f) - 1.f) * 700.f;
+  f0[i] = f0_from_lf0(l);
 }
 hipError_t launch_pitch(const float* pitch_ctl, const float* lf0_pred, float scale, float* lf0, float* f0, int n,
                         hipStream_t s) {
@@ -284,12 +284,12 @@ __global__ void energy_kernel(const float* __restrict__ energy_ctl, const float*
   if (i >= n) return;
   float ne;
   if (energy_ctl) {
-    ne = (energy_ctl[i] - 60.f) / 36.f;
+    ne = norm_energy_from_control(energy_ctl[i]);
   } else {
-    ne = (((e_pred[i] * 36.f + 60.f) * scale) - 60.f) / 36.f;
+    ne = norm_energy_from_prediction(e_pred[i], scale);
   }
   norm_e[i] = ne;
-  energy[i] = ne * 36.f + 60.f;
+  energy[i] = energy_from_norm(ne);
 }
 hipError_t launch_energy(const float* energy_ctl, const float* e_pred, float scale, float* norm_e, float* energy,
                          int n, hipStream_t s) {
@@ -373,7 +373,7 @@ __global__ void reparam_kernel(const float* __restrict__ m_p, const float* __res
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float nz = noise ? noise[i] : 0.f;
-  const float v = m_p[i] + nz * expf(logs_p[i]) * noise_scale;
+  const float v = reparam_value(m_p[i], logs_p[i], nz, noise_scale);
   z_p[i] = v;
   if (copy) copy[i] = v;        // (the tensor the inverse flow then transforms in place: saves a copy launch)
   // the frame-rate stages behind m_p / logs_p (text encoder, frame prior network, projection) left the split-f16 range

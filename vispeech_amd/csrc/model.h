@@ -171,6 +171,9 @@ struct vsp_ctx {
   // and per-utterance noise keys (vsp_set_noise_seeds; noise_first is then ignored).  Off: the reference's padded batch.
   bool isolated = false;
   std::vector<uint64_t> noise_seeds;
+  // Per-row controls (vsp_set_row_controls, round 13): utterance b's own scales and which of its controls are given --
+  // the arguments of the B = 1 call isolated mode reproduces.  Empty: the scalar arguments of the call hold for every row.
+  std::vector<vsp_row_control> row_controls;
   bool adopted_pending = false;   // an adopted arena whose header has not been checked yet (vsp_commit_adopted_weights)
   int gen_mode = 1;  // 0: f32 MFMA channel-major generator, 1: split-f16 (fp32-accurate) channels-last generator,
                      // 2: same kernels with plain f16 operands (VSP_GENERATOR=f16, opt-in reduced precision)

@@ -179,6 +179,46 @@ class Engine:
         arr = (C.c_uint64 * max(len(seeds), 1))(*seeds)
         _lib.check(self.lib.vsp_set_noise_seeds(self.ctx, arr, len(seeds)), self.ctx, "vsp_set_noise_seeds")
 
+    # ------------------------------------------------------------------ per-row controls (vsp_set_row_controls)
+    def set_row_controls(self, rows) -> None:
+        """``vsp_set_row_controls``: every utterance's own ``duration_scale`` / ``pitch_scale`` / ``energy_scale`` /
+        ``noise_scale`` and which of its controls are given -- the arguments of the B = 1 reference call isolated mode
+        reproduces for it (include/vispeech_hip.h).  ``rows``: an object with those four ``[B]`` float arrays and a
+        ``[B, 3]`` bool ``given`` (duration, pitch, energy), e.g. ``models.RowControls``; None forgets the table.  Sticky
+        context state: ``encode`` / ``decode`` / ``infer_padded`` set it from their ``row_controls`` argument on every
+        call, so a call without one never runs with the table of an earlier call."""
+        if rows is None:
+            _lib.check(self.lib.vsp_set_row_controls(self.ctx, None, 0), self.ctx, "vsp_set_row_controls")
+            return
+        arr = self._row_control_array(rows)
+        _lib.check(self.lib.vsp_set_row_controls(self.ctx, arr, len(arr)), self.ctx, "vsp_set_row_controls")
+
+    @staticmethod
+    def _row_control_array(rows):
+        cols = [np.asarray(getattr(rows, k), dtype=np.float32).reshape(-1)
+                for k in ("duration_scale", "pitch_scale", "energy_scale", "noise_scale")]
+        given = np.asarray(rows.given, dtype=bool)
+        B = len(cols[0])
+        if B == 0 or any(len(c) != B for c in cols) or given.shape != (B, 3):
+            raise ValueError("row controls: four [B] scale arrays and a [B, 3] bool `given`, B > 0")
+        arr = (_lib.VspRowControl * B)()
+        for b in range(B):
+            bits = sum(bit for bit, on in zip((_lib.GIVEN_DURATION, _lib.GIVEN_PITCH, _lib.GIVEN_ENERGY), given[b]) if on)
+            arr[b] = _lib.VspRowControl(float(cols[0][b]), float(cols[1][b]), float(cols[2][b]), float(cols[3][b]), bits)
+        return arr
+
+    @staticmethod
+    def _check_row_controls(rows, isolated: bool, B: int, noise_scale):
+        """The ``noise_scale`` the seed rules see: with a table, whether ANY row draws noise."""
+        if rows is None:
+            return noise_scale
+        if not isolated:
+            raise ValueError("row_controls needs isolated=True (per-row values have no reference meaning in a padded batch)")
+        ns = np.asarray(rows.noise_scale, dtype=np.float32).reshape(-1)
+        if len(ns) != B:
+            raise ValueError(f"row_controls must have {B} rows, got {len(ns)}")
+        return 1.0 if bool((ns != 0).any()) else 0.0
+
     @staticmethod
     def _isolated_seeds(isolated: bool, noise, noise_scale, noise_seed, B: int):
         """(scalar seed for the C call, per-utterance seeds or None).  Isolated mode keys the noise per utterance: a plain
@@ -200,12 +240,16 @@ class Engine:
 
     # ------------------------------------------------------------------ the path
     def encode(self, phonemes, lengths, sid, duration_ctl=None, pitch_ctl=None, energy_ctl=None,
-               duration_scale=1.0, pitch_scale=1.0, energy_scale=1.0, isolated: bool = False) -> Dict[str, torch.Tensor]:
+               duration_scale=1.0, pitch_scale=1.0, energy_scale=1.0, isolated: bool = False,
+               row_controls=None) -> Dict[str, torch.Tensor]:
+        """``row_controls`` (``set_row_controls``; needs ``isolated``): per-row scales and given bits; the three scalar
+        scales are then not read, and a ``*_ctl`` tensor is read in the rows that are given it only."""
         d = self.dims
         ph = _dev_i64(phonemes, self.device)
         ln = _dev_i64(lengths, self.device)
         sd = _dev_i64(sid, self.device)
         B, Tp = ph.shape
+        self._check_row_controls(row_controls, isolated, B, 0.0)
         dc = None if duration_ctl is None else _dev_f32(duration_ctl, self.device).reshape(B, -1)
         pc = None if pitch_ctl is None else _dev_f32(pitch_ctl, self.device).reshape(B, -1)
         ec = None if energy_ctl is None else _dev_f32(energy_ctl, self.device).reshape(B, -1)
@@ -218,6 +262,7 @@ class Engine:
                    cum_dur=torch.empty(B, Tp, dtype=torch.int32, device=self.device))
         ws = self._workspace("encode", self.lib.vsp_encode_workspace_bytes(self.ctx, B, Tp))
         self.set_isolated(isolated)
+        self.set_row_controls(row_controls)
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_encode(self.ctx, self._stream(), B, Tp, _ptr(ph), _ptr(ln), _ptr(sd), _ptr(dc), _ptr(pc),
                                      _ptr(ec), float(duration_scale), float(pitch_scale), float(energy_scale),
@@ -278,15 +323,17 @@ class Engine:
 
     def decode(self, enc: Mapping[str, torch.Tensor], Tf: int, noise: Optional[torch.Tensor], noise_scale: float,
                max_len: Optional[int] = None, noise_seed=None, bufs=None,
-               noise_offset: int = 0, isolated: bool = False) -> Dict[str, torch.Tensor]:
+               noise_offset: int = 0, isolated: bool = False, row_controls=None) -> Dict[str, torch.Tensor]:
         """``noise`` None with ``noise_scale`` != 0: the library draws it on the device -- elements ``noise_offset`` ..
         of ``vsp_randn(noise_seed)``; the caller must then name the seed (a silent default would hand out the same
         "random" sample on every call).  ``noise_offset``: a shard [lo, hi) of a global batch passes lo * inter * Tf so
         that its utterances get the noise they would get unsharded.
         ``bufs``: a ``decode_buffers`` result for the same ``Tf`` / ``max_len`` (else allocated here).
         ``isolated``: every utterance as the reference computes it alone; ``noise_seed`` is then a sequence of B ints, one
-        key per utterance (``vsp_set_noise_seeds``), and ``noise_offset`` is not read."""
+        key per utterance (``vsp_set_noise_seeds``), and ``noise_offset`` is not read.
+        ``row_controls`` (``set_row_controls``; needs ``isolated``): row b's own ``noise_scale``; the argument is not read."""
         B, _, Tp = enc["x_var"].shape
+        noise_scale = self._check_row_controls(row_controls, isolated, B, noise_scale)
         noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
         if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
             raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
@@ -303,6 +350,7 @@ class Engine:
         self.set_isolated(isolated)
         if isolated:
             self.set_noise_seeds(seeds)
+        self.set_row_controls(row_controls)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_decode(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,
@@ -319,12 +367,14 @@ class Engine:
     def infer_padded(self, phonemes, lengths, sid, tf_pad: int, noise, noise_scale: float = 1.0, max_len=None,
                      duration_ctl=None, pitch_ctl=None, energy_ctl=None, duration_scale: float = 1.0,
                      pitch_scale: float = 1.0, energy_scale: float = 1.0, noise_seed=None,
-                     noise_offset: int = 0, isolated: bool = False) -> Dict[str, torch.Tensor]:
+                     noise_offset: int = 0, isolated: bool = False, row_controls=None) -> Dict[str, torch.Tensor]:
         """``vsp_infer``: the whole path in ONE call and without the host read of the frame counts, for
         callers that know an upper bound ``tf_pad`` of the frame count (supplied durations / fixed max_len).
-        ``noise`` None with ``noise_scale`` != 0 needs an explicit ``noise_seed`` (see ``decode``, also for ``isolated``)."""
+        ``noise`` None with ``noise_scale`` != 0 needs an explicit ``noise_seed`` (see ``decode``, also for ``isolated``
+        and ``row_controls``, which replaces the four scalar scales)."""
         ph = _dev_i64(phonemes, self.device)
         B, Tp = ph.shape
+        noise_scale = self._check_row_controls(row_controls, isolated, B, noise_scale)
         noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
         if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
             raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
@@ -349,6 +399,7 @@ class Engine:
         self.set_isolated(isolated)
         if isolated:
             self.set_noise_seeds(seeds)
+        self.set_row_controls(row_controls)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_infer(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,

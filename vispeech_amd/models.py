@@ -11,6 +11,7 @@ built, constructing the model raises ImportError.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Mapping, Optional
 
 import numpy as np
@@ -18,6 +19,38 @@ import torch
 
 from .engine import Engine
 from .schema import ModelDims, dims_from_ctor, state_dict_schema, used_by_infer
+
+
+@dataclass
+class RowControls:
+    """Per-row arguments of an isolated ``infer`` (``vsp_set_row_controls``): utterance b is synthesised as the reference's
+    B = 1 call with ``duration_control`` = row b of the tensor if ``given[b, 0]`` else the scalar ``duration_scale[b]``,
+    likewise pitch (``given[b, 1]``) and energy (``given[b, 2]``), and ``noise_scale[b]``.  Four ``[B]`` float arrays and
+    a ``[B, 3]`` bool array; a scale whose control is given is not read."""
+    duration_scale: np.ndarray
+    pitch_scale: np.ndarray
+    energy_scale: np.ndarray
+    noise_scale: np.ndarray
+    given: np.ndarray
+
+    def __post_init__(self):
+        for k in ("duration_scale", "pitch_scale", "energy_scale", "noise_scale"):
+            setattr(self, k, np.asarray(getattr(self, k), dtype=np.float32).reshape(-1))
+        self.given = np.asarray(self.given, dtype=bool)
+        B = len(self.duration_scale)
+        if any(len(getattr(self, k)) != B for k in ("pitch_scale", "energy_scale", "noise_scale")) or self.given.shape != (B, 3):
+            raise ValueError("RowControls: four [B] scale arrays and a [B, 3] bool `given`")
+
+    def __len__(self) -> int:
+        return len(self.duration_scale)
+
+    @classmethod
+    def uniform(cls, B: int, duration_scale: float = 1.0, pitch_scale: float = 1.0, energy_scale: float = 1.0,
+                noise_scale: float = 1.0, given=(False, False, False)) -> "RowControls":
+        """Every row with the same scales and given bits: what the scalar arguments of a call say."""
+        full = lambda v: np.full(int(B), v, dtype=np.float32)
+        return cls(full(duration_scale), full(pitch_scale), full(energy_scale), full(noise_scale),
+                   np.tile(np.asarray(given, dtype=bool).reshape(1, 3), (int(B), 1)))
 
 
 class SynthesizerTrn:
@@ -133,7 +166,8 @@ class SynthesizerTrn:
     @torch.no_grad()
     def infer(self, phonemes, phonemes_lengths, sid=None, noise_scale=1, max_len=None, energy_control=None,
               pitch_control=None, duration_control=None, *, noise: Optional[torch.Tensor] = None,
-              t_f: Optional[int] = None, noise_seed=None, noise_offset: int = 0, isolated: bool = False):
+              t_f: Optional[int] = None, noise_seed=None, noise_offset: int = 0, isolated: bool = False,
+              row_controls: Optional[RowControls] = None):
         """Reference models.py:672-722.  ``noise`` (keyword-only, optional) replaces the
         ``torch.randn_like`` draw of models.py:718 so runs can be reproduced; without it the draw is
         ``torch.randn`` on the GPU (torch's generator, as in the reference) unless ``noise_seed`` is given: then the
@@ -144,7 +178,11 @@ class SynthesizerTrn:
         utterance b's own extent, is what the reference returns for a B = 1 call on that utterance's unpadded inputs --
         independent of the batch it shares -- and exactly 0 behind the extent.  ``noise_seed`` is then a sequence of B
         ints, one Philox key per utterance (a plain int raises: it would hand every utterance the same draw), and
-        ``noise_offset`` is not read.  Returns
+        ``noise_offset`` is not read.
+        ``row_controls`` (a ``RowControls``; needs ``isolated``, else ValueError): utterance b's own scales, noise scale and
+        which of its controls are given.  ``duration_control`` / ``pitch_control`` / ``energy_control`` are then ``[B, Tp]``
+        tensors read in the rows that are given them (None if no row is), the positional ``noise_scale`` is not read, and
+        the returned ``duration`` is the one every row ended up with.  Returns
         ``(o, x_mask, (z, z_p, m_p, logs_p), duration, F0, energy)``."""
         eng = self._engine
         if not eng.ready:
@@ -152,6 +190,16 @@ class SynthesizerTrn:
         if sid is None:
             raise ValueError("sid is required (the reference's EnergyPredictor needs g; n_speakers > 0)")
         B, Tp = phonemes.shape
+        if row_controls is not None:
+            if not isolated:
+                raise ValueError("row_controls needs isolated=True: per-row values have no reference meaning in a padded batch")
+            if len(row_controls) != B:
+                raise ValueError(f"row_controls must have {B} rows, got {len(row_controls)}")
+            for name, ctl, col in (("duration", duration_control, 0), ("pitch", pitch_control, 1), ("energy", energy_control, 2)):
+                if ctl is not None and not isinstance(ctl, torch.Tensor):
+                    raise ValueError(f"row_controls: {name}_control is a [B, Tp] tensor or None (the scales are in the table)")
+                if ctl is None and bool(row_controls.given[:, col].any()):
+                    raise ValueError(f"row_controls: a row is given {name} but {name}_control is None")
 
         def split(ctl):
             if isinstance(ctl, torch.Tensor):      # the reference's isinstance(.., torch.Tensor) branches
@@ -163,6 +211,8 @@ class SynthesizerTrn:
         e_t, e_s = split(energy_control)
         # (the keyword is passed only when set: engine stand-ins of older callers and tests need not know it)
         iso = {"isolated": True} if isolated else {}
+        if row_controls is not None:
+            iso["row_controls"] = row_controls
         no_seed = noise_seed is None                     # the caller named no seed: torch draws the noise, in either mode
         noise_seed, seeds = eng._isolated_seeds(bool(isolated), noise, 0.0, noise_seed, B)
         enc = eng.encode(phonemes, phonemes_lengths, sid, d_t, p_t, e_t, d_s, p_s, e_s, **iso)
@@ -172,11 +222,12 @@ class SynthesizerTrn:
         Tf = tf_local if t_f is None else max(int(t_f), tf_local)
         if Tf <= 0:
             raise ValueError("all durations are zero: nothing to synthesise")
-        ns = float(noise_scale)
+        # (with a table: whether ANY row draws noise; the engine does not read the scalar then)
+        ns = float(noise_scale) if row_controls is None else float(bool((row_controls.noise_scale != 0).any()))
         if noise is None and ns != 0.0 and no_seed:
             noise = torch.randn(B, self.dims.inter_channels, Tf, dtype=torch.float32, device=eng.device)
         dec = eng.decode(enc, Tf, noise, ns, max_len, noise_seed=seeds if isolated else (0 if noise_seed is None else int(noise_seed)),
                          bufs=bufs, noise_offset=int(noise_offset), **iso)
-        duration = duration_control if d_t is not None else enc["duration"].view(B, 1, Tp)
+        duration = duration_control if d_t is not None and row_controls is None else enc["duration"].view(B, 1, Tp)
         return (dec["o"], dec["x_mask"], (dec["z"], dec["z_p"], dec["m_p"], dec["logs_p"]), duration, enc["F0"],
                 enc["energy"])

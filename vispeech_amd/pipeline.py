@@ -51,7 +51,10 @@ class InFlightPool:
         """``net.infer(*args, **kwargs)`` on the next context, enqueued on that context's stream.  ``after(result)`` runs
         inside the stream's scope (e.g. the start of a gather that orders itself behind this stream's work).  Returns
         ``(result, done)``: ``done`` is an event recorded behind the call -- wait for it (or synchronise) before the
-        result is read on another stream or by the host."""
+        result is read on another stream or by the host.  ``row_controls`` is refused (per-row tables are served by the
+        batching services, not by the pool)."""
+        if kwargs.get("row_controls") is not None:
+            raise ValueError("InFlightPool.infer does not take row_controls")
         net, st = self.next_slot()
         if st is None:
             res = net.infer(*args, **kwargs)

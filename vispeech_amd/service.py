@@ -311,6 +311,28 @@ class PooledSynthesisService:
         raise Busy("every synthesis slot is taken")
 
 
+def _row_table(batch, scales, noise_scale: float):
+    """The per-row table of a batch of requests (``models.RowControls``), or None where the batch needs none: no request
+    named a scale and every row carries all three controls -- then the services make the calls they always made.
+    ``scales``: per request ``(duration_scale, pitch_scale, energy_scale, noise_scale)``, None = 1.0 and the service's
+    ``noise_scale``.  ``given`` is ``collate_rows``' array; a collate callable that returns none gives every row the
+    controls its batch has."""
+    B = len(scales)
+    given = batch.get("given")
+    if all(v is None for sc in scales for v in sc) and (given is None or bool(np.all(given))):
+        return None
+    if given is None:
+        given = np.tile(np.array([[batch.get(k) is not None for k in ("duration", "f0", "energy")]], dtype=bool), (B, 1))
+    from .models import RowControls
+    col = lambda i, default: np.array([default if sc[i] is None else float(sc[i]) for sc in scales], dtype=np.float32)
+    return RowControls(col(0, 1.0), col(1, 1.0), col(2, 1.0), col(3, noise_scale), np.asarray(given, dtype=bool))
+
+
+def _table_controls(batch, rows_ctl):
+    """duration / f0 / energy of a batch that runs with a table: a control no row is given is not passed."""
+    return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
+
+
 class BatchingSynthesisService:
     """Requests from many callers, synthesised together (round 10).  The services above refuse a request while another is in
     flight, because in the reference's padded batch an utterance's audio depends on its batch-mates; in ISOLATED mode it
@@ -318,6 +340,9 @@ class BatchingSynthesisService:
     returns a future of its PCM16; one worker thread collects up to ``max_batch`` requests -- waiting at most
     ``max_wait_s`` after the first -- collates them and runs ONE ``net.infer(..., isolated=True)`` with the requests' seeds.
     A failing batch fails its own futures and nothing else.  No retry, no priority.
+    A request may leave any of durations / f0 / energy to the predictors (``text.request_row``) and name its own
+    ``duration_scale`` / ``pitch_scale`` / ``energy_scale`` / ``noise_scale``: such a batch runs with the per-row table built
+    from its requests (``infer(row_controls=...)``), and each request is still what the reference returns for it alone.
     ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays)."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
@@ -341,14 +366,16 @@ class BatchingSynthesisService:
         self._worker = threading.Thread(target=self._run, name="vispeech-batching", daemon=True)
         self._worker.start()
 
-    def submit(self, row, noise_seed: int) -> "concurrent.futures.Future":
-        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The future's
-        result is the request's PCM16 samples (numpy int16, valid part only)."""
+    def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
+               noise_scale=None) -> "concurrent.futures.Future":
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
+        request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
+        The future's result is the request's PCM16 samples (numpy int16, valid part only)."""
         fut: "concurrent.futures.Future" = concurrent.futures.Future()
         with self._gate:
             if self._closed:
                 raise RuntimeError("the service is closed")
-            self._q.put((row, int(noise_seed), fut))
+            self._q.put((row, int(noise_seed), fut, (duration_scale, pitch_scale, energy_scale, noise_scale)))
         return fut
 
     def close(self) -> None:
@@ -379,21 +406,27 @@ class BatchingSynthesisService:
             if not reqs:
                 continue
             try:
-                for (_, _, fut), pcm in zip(reqs, self._synthesize([r[0] for r in reqs], [r[1] for r in reqs])):
-                    fut.set_result(pcm)
+                pcms = self._synthesize([r[0] for r in reqs], [r[1] for r in reqs], [r[3] for r in reqs])
+                for r, pcm in zip(reqs, pcms):
+                    r[2].set_result(pcm)
             except Exception as e:           # this batch's requests fail; the worker lives on
-                for _, _, fut in reqs:
-                    if not fut.done():
-                        fut.set_exception(e)
+                for r in reqs:
+                    if not r[2].done():
+                        r[2].set_exception(e)
 
-    def _synthesize(self, rows, seeds):
+    def _synthesize(self, rows, seeds, scales=None):
         import torch
         net = self.net
         batch = self._collate(rows)
         t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
+        ctl = (batch.get("duration"), batch.get("f0"), batch.get("energy"))
+        table = _row_table(batch, scales if scales is not None else [(None,) * 4] * len(rows), self.noise_scale)
+        kw = {}
+        if table is not None:            # (the keyword is passed only when set: a batch without one makes the call it always made)
+            ctl, kw = _table_controls(batch, table), {"row_controls": table}
         o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
-                                  duration_control=t(batch.get("duration")), pitch_control=t(batch.get("f0")),
-                                  energy_control=t(batch.get("energy")), noise_seed=list(seeds), isolated=True)
+                                  duration_control=t(ctl[0]), pitch_control=t(ctl[1]),
+                                  energy_control=t(ctl[2]), noise_seed=list(seeds), isolated=True, **kw)
         frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
         hop = net.dims.total_upsample
         if self.output_rate is None:
@@ -446,8 +479,9 @@ class _RowStream:
 class _StreamRequest:
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
-    def __init__(self, row, seed: int):
+    def __init__(self, row, seed: int, scales=(None, None, None, None)):
         self.row, self.seed, self.stream = row, seed, _RowStream()
+        self.scales = scales          # the request's own (duration, pitch, energy, noise) scales; None: the defaults
         self.z = self.g = None
         self.L = self.pos = 0
         # output stage (``output_rate``): the request's own Engine.output_stream, fed one window per tick
@@ -467,7 +501,8 @@ class StreamingBatchService:
     ``autostart=False`` the caller drives ``step()`` itself.  A tick, in order:
 
     1. admit    queued requests while fewer than ``max_batch`` are active: one isolated ``encode`` / ``frame_lengths_host`` /
-                ``decode(max_len=0)`` with the requests' seeds for the admitted group; each keeps its z row, g row and L.  A
+                ``decode(max_len=0)`` with the requests' seeds -- and, where a request names a scale or leaves a control to
+                the predictors, the group's per-row table -- for the admitted group; each keeps its z row, g row and L.  A
                 zero-frame request ends at once with no bytes; a failing admission fails that group's streams only.
     2. generate one ``generator_stream_rows`` call for all active requests, each at its own ``f0`` (a request's first chunk
                 has ``first_chunk_frames`` frames if that is given: earlier first audio).
@@ -515,10 +550,12 @@ class StreamingBatchService:
             self._worker.start()
 
     # ------------------------------------------------------------------ callers' side
-    def submit(self, row, noise_seed: int) -> _RowStream:
-        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it.  Returns the iterator of the request's PCM16
-        ``bytes``, one piece per tick the request takes part in."""
-        req = _StreamRequest(row, int(noise_seed))
+    def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
+               noise_scale=None) -> _RowStream:
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
+        1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
+        request's PCM16 ``bytes``, one piece per tick the request takes part in."""
+        req = _StreamRequest(row, int(noise_seed), (duration_scale, pitch_scale, energy_scale, noise_scale))
         with self._cv:
             if self._closed:
                 raise RuntimeError("the service is closed")
@@ -582,13 +619,18 @@ class StreamingBatchService:
             eng = self.net._engine
             batch = self._collate([r.row for r in group])
             t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
-            enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(batch.get("duration")),
-                             t(batch.get("f0")), t(batch.get("energy")), isolated=True)
+            ctl = (batch.get("duration"), batch.get("f0"), batch.get("energy"))
+            table = _row_table(batch, [r.scales for r in group], self.noise_scale)
+            kw = {}
+            if table is not None:        # (passed only when set: a group without one makes the calls it always made)
+                ctl, kw = _table_controls(batch, table), {"row_controls": table}
+            enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]),
+                             t(ctl[1]), t(ctl[2]), isolated=True, **kw)
             frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
             z = None
             if tf > 0:
                 z = eng.decode(enc, tf, None, self.noise_scale, max_len=0, noise_seed=[r.seed for r in group],
-                               isolated=True)["z"]
+                               isolated=True, **kw)["z"]
             for b, r in enumerate(group):
                 r.L, r.pos = int(frames[b]), 0
                 if r.L <= 0:

@@ -179,7 +179,10 @@ def infer_sharded(net, phonemes, lengths, sid, *, noise: Optional[torch.Tensor] 
     rank then draws ITS utterances' part of the global [B, C, Tf] stream (``noise_offset`` = lo * C * Tf), so the
     result does not depend on the shard layout.  ``isolated=True`` is forwarded to ``net.infer``; its per-utterance
     ``noise_seed`` sequence is sliced like the tensors (no offset: an utterance's noise is keyed by its own seed), and the
-    global frame count then only sizes the gather -- an isolated utterance does not depend on its padding.  Returns (o_full [B,1,S] on ``dst`` else None, local result tuple)."""
+    global frame count then only sizes the gather -- an isolated utterance does not depend on its padding.
+    ``row_controls`` (per-row scales, ``net.infer``) is refused: its table is not sliced here.  Returns (o_full [B,1,S] on ``dst`` else None, local result tuple)."""
+    if infer_kwargs.get("row_controls") is not None:
+        raise ValueError("infer_sharded does not take row_controls: the per-row table is not sharded")
     world = _world(group)
     rank = dist.get_rank(group) if _active() else 0
     B = phonemes.shape[0]

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import json
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 
@@ -44,9 +44,21 @@ class FilelistRow:
     speaker: str
     utt_id: str
     phones: List[str]
-    durations: np.ndarray   # int frames per phoneme (MFA, hop 512)
-    f0: np.ndarray          # Hz per phoneme (0 = unvoiced)
-    energy: np.ndarray
+    # None: the request leaves this control to the model's predictor (a plain "this text, this voice" request, what the
+    # reference's inference.py:44 / inference_api.py:46 / gui.py:99 send) -- each of the three on its own
+    durations: Optional[np.ndarray] = None   # int frames per phoneme (MFA, hop 512)
+    f0: Optional[np.ndarray] = None          # Hz per phoneme (0 = unvoiced)
+    energy: Optional[np.ndarray] = None
+
+
+def request_row(speaker: str, phones: Sequence[str], durations=None, f0=None, energy=None, utt_id: str = "") -> FilelistRow:
+    """A synthesis request: speaker and phones, and whichever of durations / f0 / energy the caller brings (None: predicted)."""
+    arr = lambda a, dt: None if a is None else np.asarray(a, dtype=dt)
+    row = FilelistRow(speaker, utt_id, list(phones), arr(durations, np.int64), arr(f0, np.float32), arr(energy, np.float32))
+    for name, a in (("durations", row.durations), ("f0", row.f0), ("energy", row.energy)):
+        if a is not None and len(a) != len(row.phones):
+            raise ValueError(f"{name}: {len(a)} entries for {len(row.phones)} phones")
+    return row
 
 
 def parse_filelist_row(line: str) -> FilelistRow:
@@ -66,18 +78,21 @@ def parse_filelist_row(line: str) -> FilelistRow:
 
 def collate_rows(rows: Sequence[FilelistRow], table: SymbolTable, spk2id: Dict[str, int]):
     """Pad rows into the arrays ``SynthesizerTrn.infer`` takes with control tensors:
-    phonemes [B,Tp] int64, lengths [B], sid [B], duration / f0 / energy [B,Tp] float32 (zero padded)."""
+    phonemes [B,Tp] int64, lengths [B], sid [B], duration / f0 / energy [B,Tp] float32 (zero padded), and
+    given [B,3] bool: whether the row carries its durations / f0 / energy (a missing field is left zero; rows that carry
+    all three give the arrays they always gave)."""
     B = len(rows)
     tp = max(len(r.phones) for r in rows)
     out = dict(phonemes=np.zeros((B, tp), np.int64), lengths=np.zeros(B, np.int64), sid=np.zeros(B, np.int64),
                duration=np.zeros((B, tp), np.float32), f0=np.zeros((B, tp), np.float32),
-               energy=np.zeros((B, tp), np.float32))
+               energy=np.zeros((B, tp), np.float32), given=np.zeros((B, 3), bool))
     for b, r in enumerate(rows):
         n = len(r.phones)
         out["phonemes"][b, :n] = table.cleaned_text_to_sequence(r.phones)
         out["lengths"][b] = n
         out["sid"][b] = spk2id[r.speaker]
-        out["duration"][b, :n] = r.durations
-        out["f0"][b, :n] = r.f0
-        out["energy"][b, :n] = r.energy
+        for k, (key, a) in enumerate((("duration", r.durations), ("f0", r.f0), ("energy", r.energy))):
+            if a is not None:
+                out[key][b, :n] = a
+                out["given"][b, k] = True
     return out
