@@ -357,6 +357,40 @@ int vsp_spectrogram(vsp_ctx* ctx, void* stream, int B, int L, int hop, const flo
 /* 1 if the posterior-encoder weights are loaded (voice conversion available), else 0. */
 int vsp_has_voice_conversion(const vsp_ctx* ctx);
 
+/* ---- conversion from audio: recordings of different lengths in one batch (additive, ABI 7) */
+/* Frames of a recording of n_samples samples, host arithmetic only: with n_fft = 2 * (cfg.spec_channels - 1) and
+ * pad = (n_fft - hop) / 2, T(n) = 0 where n <= pad (the reflect padding is undefined) or n + 2 pad < n_fft (no full
+ * window), else 1 + (n + 2 pad - n_fft) / hop.  NOT vsp_spectrogram_frames: that one refuses n <= pad and, for
+ * n_fft < 3 hop, counts a frame where the padded signal is shorter than a window.  VSP_ERR_ARG: n_samples < 0, hop <= 0,
+ * n_fft < hop, or a context without spec_channels. */
+int vsp_convert_frames(const vsp_ctx* ctx, int64_t n_samples, int hop);
+/* Linear spectrogram of B recordings of different lengths: audio [B][audio_stride] (device, audio_stride >= L_max),
+ * n_samples [B] (device, clamped to [0, L_max]).  spec [B][spec_channels][T_max], T_max = vsp_convert_frames(L_max) > 0:
+ * row b's columns [0, T(n_b)) are what vsp_spectrogram returns for audio[b][0 .. n_b) alone (the reflect padding is around
+ * the row's own two ends), columns [T(n_b), T_max) are exactly 0.0, and frames[b] (device out) = T(n_b).  A sample at or
+ * behind n_b is never read: what a padded buffer holds there cannot reach an output.  The host does not read n_samples:
+ * grids and shape checks use L_max (the n_valid / n_max convention of vsp_output_chunk).  No allocation, no
+ * synchronisation, caller's stream; the DFT is the convolution vsp_spectrogram runs. */
+int64_t vsp_spectrogram_ragged_workspace_bytes(const vsp_ctx* ctx, int B, int L_max, int hop);
+int vsp_spectrogram_ragged(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, const float* audio, int64_t audio_stride,
+                           const int64_t* n_samples, float* spec, int64_t* frames, void* workspace, int64_t workspace_bytes);
+/* Audio to the converted latent in one call: ragged spectrogram, posterior encoder and forward flow with emb_g(sid_src),
+ * reverse flow with emb_g(sid_tgt) -- voice_conversion (reference models.py:724-732) without its generator, the counterpart
+ * of vsp_decode(max_len = 0).  Row b, restricted to T(n_b) frames, is what the reference computes up to z_hat for a B = 1
+ * call on spectrogram_torch(audio[b][:n_b]); every float output is exactly 0 behind the row's extent.  Outputs (device,
+ * contiguous): z_hat [B][inter][T_max], g_tgt [B][gin] (the row's speaker vector, for a generator call), frames [B],
+ * y_mask [B*T_max] uint8; z / z_p [B][inter][T_max] may be NULL.  noise [B][inter][T_max]: row b uses noise[b][:, :T(n_b)];
+ * NULL: row b's tensor is the first inter * T(n_b) elements of the Philox stream keyed seeds[b], laid out [inter][T(n_b)]
+ * (vsp_set_noise_seeds for exactly B rows first, VSP_ERR_STATE otherwise).  noise_scale multiplies the posterior's noise,
+ * z = m_q + noise * exp(logs_q) * noise_scale: 1.0 is the reference; with 0 nothing is drawn or read, no seeds are needed and
+ * z = m_q.  The isolated flag of the context is neither read nor changed (these stages mask by length already).  Needs the
+ * enc_q.* tensors (VSP_ERR_STATE otherwise).  No allocation, no synchronisation. */
+int64_t vsp_convert_latent_workspace_bytes(const vsp_ctx* ctx, int B, int L_max, int hop);
+int vsp_convert_latent(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, const float* audio, int64_t audio_stride,
+                       const int64_t* n_samples, const int64_t* sid_src, const int64_t* sid_tgt, const float* noise,
+                       float noise_scale, float* z_hat, float* g_tgt, int64_t* frames, uint8_t* y_mask, float* z, float* z_p,
+                       void* workspace, int64_t workspace_bytes);
+
 /* piecewise_rational_quadratic_transform with tails='linear' (reference transforms.py:12-193),
  * n elements, nb bins; uw/uh [n][nb], ud [n][nb-1]; outputs y[n], logabsdet[n]. */
 int vsp_rq_spline(void* stream, int64_t n, int nb, const float* x, const float* uw, const float* uh,

@@ -386,7 +386,7 @@ void run_flow(Run& r, int B, int T, T3 z, const float* g, const int64_t* lengths
 
 // PosteriorEncoder.forward (reference models.py:233-241): y [B][spec][T] -> m, logs, z [B][inter][T].
 void run_posterior(Run& r, int B, int T, T3 y, const int64_t* lengths, const float* g, const float* noise, T3 Z,
-                   T3 M, T3 LOGS) {
+                   T3 M, T3 LOGS, float noise_scale = 1.f) {
   const vsp_config& c = r.ctx->cfg;
   const PosteriorW& Q = r.ctx->model.enc_q;
   const int h = c.hidden_channels, ql = c.posterior_layers;
@@ -404,7 +404,7 @@ void run_posterior(Run& r, int B, int T, T3 y, const int64_t* lengths, const flo
   r.conv(a, B);
   if (r.ok()) {
     // z = (m + eps * exp(logs)) * mask   (contiguous [B][inter][T] outputs)
-    r.chk(launch_reparam(M.p, LOGS.p, noise, 1.f, Z.p, (long)B * c.inter_channels * T, r.s), "reparam");
+    r.chk(launch_reparam(M.p, LOGS.p, noise, noise_scale, Z.p, (long)B * c.inter_channels * T, r.s), "reparam");
     r.chk(launch_mask3(Z.p, Z.bs, Z.cs, lengths, B, c.inter_channels, T, r.s), "mask");
   }
 }
@@ -1892,6 +1892,157 @@ int vsp_voice_conversion(vsp_ctx* ctx, void* stream, int B, int T, const float* 
   Ws ws(workspace, (size_t)workspace_bytes, false);
   return vc_impl(ctx, (hipStream_t)stream, ws, B, T, y, y_lengths, sid_src, sid_tgt, noise, o_hat, y_mask, z, z_p, z_hat,
                  m_q, logs_q);
+}
+
+// ---------------------------------------------------------------------------------- conversion from audio
+// Frames of a recording of n samples: host arithmetic (kernels.h, stft_ragged_frames), 0 where there is no frame.
+static int convert_geometry(const vsp_ctx* ctx, int hop, int* n_fft) {
+  if (!ctx || ctx->cfg.spec_channels <= 1 || hop <= 0) return VSP_ERR_ARG;
+  *n_fft = 2 * (ctx->cfg.spec_channels - 1);
+  return *n_fft < hop ? VSP_ERR_ARG : VSP_OK;
+}
+
+int vsp_convert_frames(const vsp_ctx* ctx, int64_t n_samples, int hop) {
+  int n_fft = 0;
+  if (convert_geometry(ctx, hop, &n_fft) != VSP_OK || n_samples < 0) return VSP_ERR_ARG;
+  const long T = stft_ragged_frames((long)n_samples, n_fft, hop);
+  return T > 0x7fffffffL ? VSP_ERR_ARG : (int)T;
+}
+
+// frames of the padded shape, or <= 0: the shape the grids and the tensors of a ragged call are sized by
+static int convert_t_max(const vsp_ctx* ctx, int B, int L_max, int hop) {
+  int n_fft = 0;
+  if (convert_geometry(ctx, hop, &n_fft) != VSP_OK || B <= 0 || L_max <= 0 || stft_ragged_tile(n_fft, hop) <= 0) return VSP_ERR_ARG;
+  return vsp_convert_frames(ctx, L_max, hop);
+}
+
+static int spectrogram_ragged_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int L_max, int hop, int T, const float* audio,
+                                   int64_t audio_stride, const int64_t* n_samples, float* spec, int64_t* frames) {
+  const vsp_config& c = ctx->cfg;
+  const int n_fft = 2 * (c.spec_channels - 1);
+  Run r{ctx, s, ws};
+  T3 F = ws.t3(B, n_fft, T), RI = ws.t3(B, 2 * c.spec_channels, T);
+  if (ws.dry) return VSP_OK;
+  if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "ragged spectrogram workspace too small");
+  r.chk(launch_stft_frames_ragged(audio, (long)audio_stride, n_samples, F.p, F.bs, F.cs, B, L_max, n_fft, hop, T, s),
+        "stft frames ragged");
+  ConvArgs a = r.args(ctx->model.stft, F, RI, T, T);     // (the DFT of vsp_spectrogram: same convolution, same plan)
+  r.conv(a, B);
+  if (r.ok())
+    r.chk(launch_stft_magnitude_ragged(RI.p, RI.bs, RI.cs, n_samples, spec, frames, B, L_max, n_fft, hop, c.spec_channels, T, s),
+          "stft magnitude ragged");
+  return r.rc;
+}
+
+int64_t vsp_spectrogram_ragged_workspace_bytes(const vsp_ctx* ctx, int B, int L_max, int hop) {
+  const int T = convert_t_max(ctx, B, L_max, hop);
+  if (T <= 0) return VSP_ERR_ARG;
+  Ws ws(nullptr, 0, true);
+  spectrogram_ragged_impl(const_cast<vsp_ctx*>(ctx), nullptr, ws, B, L_max, hop, T, nullptr, 0, nullptr, nullptr, nullptr);
+  return (int64_t)ws.cur;
+}
+
+int vsp_spectrogram_ragged(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, const float* audio, int64_t audio_stride,
+                           const int64_t* n_samples, float* spec, int64_t* frames, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const int T = convert_t_max(ctx, B, L_max, hop);
+  if (T <= 0 || !audio || audio_stride < L_max || !n_samples || !spec || !frames || !workspace)
+    return ctx->fail(VSP_ERR_ARG, "vsp_spectrogram_ragged: bad argument (needs spec_channels, B > 0, hop > 0, a padded length "
+                                  "with at least one frame, audio_stride >= L_max and no null pointer)");
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  if (workspace_bytes < vsp_spectrogram_ragged_workspace_bytes(ctx, B, L_max, hop))
+    return ctx->fail(VSP_ERR_WORKSPACE, "ragged spectrogram workspace too small");
+  Ws ws(workspace, (size_t)workspace_bytes, false);
+  return spectrogram_ragged_impl(ctx, (hipStream_t)stream, ws, B, L_max, hop, T, audio, audio_stride, n_samples, spec, frames);
+}
+
+// Audio to the converted latent: ragged spectrogram -> enc_q(g_src) -> flow(g_src) -> flow(g_tgt, reverse), every stage
+// with the rows' own frame counts as lengths (voice_conversion, reference models.py:724-732, up to z_hat).
+static int convert_latent_impl(vsp_ctx* ctx, hipStream_t s, Ws& ws, int B, int L_max, int hop, int T, const float* audio,
+                               int64_t audio_stride, const int64_t* n_samples, const int64_t* sid_src, const int64_t* sid_tgt,
+                               const float* noise, float noise_scale, float* z_hat, float* g_tgt, int64_t* frames,
+                               uint8_t* y_mask, float* z, float* z_p) {
+  const vsp_config& c = ctx->cfg;
+  const Model& m = ctx->model;
+  const int inter = c.inter_channels, gin = c.gin_channels;
+  const long n = (long)B * inter * T;
+  Run r{ctx, s, ws};
+  float* g_src = ws.f((size_t)B * gin);
+  float* spec = ws.f((size_t)B * c.spec_channels * T);
+  float* zq = z ? z : ws.f((size_t)n);
+  float* zp = z_p ? z_p : ws.f((size_t)n);
+  float* m_q = ws.f((size_t)n);              // (launch_reparam walks contiguous tensors)
+  float* logs_q = ws.f((size_t)n);
+  float* drawn = ws.f((size_t)n);
+  uint64_t* seeds_dev = reinterpret_cast<uint64_t*>(ws.bytes((size_t)B * sizeof(uint64_t)));
+  const bool live = !ws.dry && !ws.overflow;
+  const size_t mark = ws.cur;                // the stages run one after another on one stream: they share scratch
+  int rc = spectrogram_ragged_impl(ctx, s, ws, B, L_max, hop, T, audio, audio_stride, n_samples, spec, frames);
+  if (rc) return rc;
+  size_t peak = ws.cur;
+  ws.cur = mark;
+  if (live) {
+    r.chk(launch_gather_rows(sid_src, r.A(m.emb_g), c.n_speakers, g_src, B, gin, s), "emb_g");
+    r.chk(launch_gather_rows(sid_tgt, r.A(m.emb_g), c.n_speakers, g_tgt, B, gin, s), "emb_g");
+    r.chk(launch_mask_u8(frames, y_mask, B, T, s), "y_mask");
+    if (noise_scale == 0.f) {
+      noise = nullptr;                       // z = m_q: nothing is drawn, nothing is read
+    } else if (!noise) {
+      // row b's own draw, keyed seeds[b], laid out [inter][T_b] (vsp_set_noise_seeds).  As in vsp_decode's isolated draw:
+      // the source is pageable, so the runtime stages it before this call returns (hipMemcpyAsync is asynchronous only for
+      // pinned host memory) and a later vsp_set_noise_seeds cannot race the copy; it lands in THIS call's workspace
+      r.chk(hipMemcpyAsync(seeds_dev, ctx->noise_seeds.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, s), "noise seeds");
+      if (r.ok()) r.chk(launch_randn_ragged(seeds_dev, frames, B, inter, T, drawn, s), "randn_ragged");
+      noise = drawn;
+    }
+  }
+  run_posterior(r, B, T, ext(spec, c.spec_channels, T), frames, g_src, noise, ext(zq, inter, T), ext(m_q, inter, T),
+                ext(logs_q, inter, T), noise_scale);
+  peak = std::max(peak, ws.cur);
+  ws.cur = mark;
+  if (live && r.ok()) r.chk(hipMemcpyAsync(zp, zq, n * sizeof(float), hipMemcpyDeviceToDevice, s), "z_p copy");
+  run_flow(r, B, T, ext(zp, inter, T), g_src, frames, false);
+  if (live && r.ok()) r.chk(hipMemcpyAsync(z_hat, zp, n * sizeof(float), hipMemcpyDeviceToDevice, s), "z_hat copy");
+  peak = std::max(peak, ws.cur);
+  ws.cur = mark;
+  run_flow(r, B, T, ext(z_hat, inter, T), g_tgt, frames, true);
+  ws.cur = std::max(peak, ws.cur);
+  if (ws.overflow) return ctx->fail(VSP_ERR_WORKSPACE, "convert_latent workspace too small (need %zu bytes)", ws.cur);
+  return r.rc;
+}
+
+int64_t vsp_convert_latent_workspace_bytes(const vsp_ctx* ctx, int B, int L_max, int hop) {
+  const int T = convert_t_max(ctx, B, L_max, hop);
+  if (T <= 0) return VSP_ERR_ARG;
+  Ws ws(nullptr, 0, true);
+  convert_latent_impl(const_cast<vsp_ctx*>(ctx), nullptr, ws, B, L_max, hop, T, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                      1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return (int64_t)ws.cur;
+}
+
+int vsp_convert_latent(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, const float* audio, int64_t audio_stride,
+                       const int64_t* n_samples, const int64_t* sid_src, const int64_t* sid_tgt, const float* noise,
+                       float noise_scale, float* z_hat, float* g_tgt, int64_t* frames, uint8_t* y_mask, float* z, float* z_p,
+                       void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const int T = convert_t_max(ctx, B, L_max, hop);
+  if (T <= 0 || !audio || audio_stride < L_max || !n_samples || !sid_src || !sid_tgt || !z_hat || !g_tgt || !frames ||
+      !y_mask || !workspace || !std::isfinite(noise_scale))
+    return ctx->fail(VSP_ERR_ARG, "vsp_convert_latent: bad argument (needs spec_channels, B > 0, hop > 0, a padded length with "
+                                  "at least one frame, audio_stride >= L_max, a finite noise_scale and no null pointer)");
+  int rc = check_vc(ctx);
+  if (rc) return rc;
+  if (!noise && noise_scale != 0.f && (int)ctx->noise_seeds.size() != B)
+    return ctx->fail(VSP_ERR_STATE, "vsp_convert_latent draws per-row noise: vsp_set_noise_seeds for B = %d first (%d set)", B,
+                     (int)ctx->noise_seeds.size());
+  const int64_t need = vsp_convert_latent_workspace_bytes(ctx, B, L_max, hop);
+  if (workspace_bytes < need)
+    return ctx->fail(VSP_ERR_WORKSPACE, "convert_latent workspace too small: %lld < %lld bytes", (long long)workspace_bytes,
+                     (long long)need);
+  Ws ws(workspace, (size_t)workspace_bytes, false);
+  return convert_latent_impl(ctx, (hipStream_t)stream, ws, B, L_max, hop, T, audio, audio_stride, n_samples, sid_src, sid_tgt,
+                             noise, noise_scale, z_hat, g_tgt, frames, y_mask, z, z_p);
 }
 
 int64_t vsp_generator_workspace_bytes(const vsp_ctx* ctx, int B, int T) {

@@ -445,6 +445,25 @@ hipError_t launch_stft_frames(const float* audio, long a_bs, float* f, long f_bs
 hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* spec, int B, int spec_ch, int T,
                                  hipStream_t s);
 
+// Ragged spectrogram front end (spectrogram_ragged.hip): row b is the recording audio[b][0 .. n_b), n_b = n_samples[b]
+// clamped to [0, L_max], with T_b = stft_ragged_frames(n_b) frames; grids come from T_max (the host never reads n_samples).
+// The frame count of a recording of n samples: 0 where the reflect padding is undefined (n <= pad) or no window fits.
+__host__ __device__ inline long stft_ragged_frames(long n, int n_fft, int hop) {
+  const long pad = (n_fft - hop) / 2;
+  if (n <= pad || n + 2 * pad < n_fft) return 0;
+  return 1 + (n + 2 * pad - n_fft) / hop;
+}
+// frames of a tile whose span of samples fits the LDS budget (0: n_fft alone does not fit)
+int stft_ragged_tile(int n_fft, int hop);
+// f [B][n_fft][T_max] (strides f_bs, f_cs): f[b][n][t] = the reflect-padded row's sample t * hop + n for t < T_b, 0 behind;
+// samples at and behind n_b are never read
+hipError_t launch_stft_frames_ragged(const float* audio, long a_bs, const int64_t* n_samples, float* f, long f_bs, long f_cs,
+                                     int B, int L_max, int n_fft, int hop, int T_max, hipStream_t s);
+// spec [B][spec_ch][T_max] = sqrt(re^2 + im^2 + 1e-6) for t < T_b, exactly 0 behind; frames[b] = T_b
+hipError_t launch_stft_magnitude_ragged(const float* ri, long r_bs, long r_cs, const int64_t* n_samples, float* spec,
+                                        int64_t* frames, int B, int L_max, int n_fft, int hop, int spec_ch, int T_max,
+                                        hipStream_t s);
+
 }  // namespace vsp
 
 #include "cl_args.h"   // (builders of the Cl*Args above)

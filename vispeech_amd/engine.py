@@ -581,6 +581,96 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_voice_conversion")
         return dict(o_hat=o, y_mask=y_mask, z=z, z_p=z_p, z_hat=z_hat, m_q=m_q, logs_q=logs_q)
 
+    # ------------------------------------------------------------------ conversion from audio (ragged front end)
+    def convert_frames(self, n_samples: int, hop_length: Optional[int] = None) -> int:
+        """``vsp_convert_frames``: frames of a recording of ``n_samples`` samples (0: too short for a frame).  Host only."""
+        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        T = int(self.lib.vsp_convert_frames(self.ctx, int(n_samples), hop))
+        if T < 0:
+            _lib.check(T, self.ctx, "vsp_convert_frames")
+        return T
+
+    def _ragged_audio(self, audio, n_samples, hop_length):
+        """(audio [B, stride] on the device, n_samples on the device and as host ints, L_max, hop, T_max, frames per row).
+        The host knows every length: the frame counts come from ``vsp_convert_frames``, nothing is read back."""
+        a = _dev_f32(audio, self.device)
+        if a.dim() != 2:
+            raise ValueError("audio must be [B, L] (rows padded to a common length)")
+        B, stride = a.shape
+        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        if len(n_host) != B:
+            raise ValueError(f"n_samples must have {B} entries")
+        if any(x < 0 or x > stride for x in n_host):
+            raise ValueError("0 <= n_samples[b] <= audio.shape[1]")
+        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        frames = [self.convert_frames(x, hop) for x in n_host]
+        L_max = max(n_host)
+        T = max(frames)
+        if T <= 0:
+            raise ValueError("every recording is too short for one spectrogram frame")
+        return a, _dev_i64(n_host, self.device), n_host, L_max, hop, T, frames
+
+    def spectrogram_ragged(self, audio, n_samples, hop_length: Optional[int] = None):
+        """``vsp_spectrogram_ragged``: recordings of different lengths in one padded ``audio`` [B, L]; row b is
+        ``audio[b, :n_samples[b]]``.  Returns (spec [B, spec_channels, T_max], frames [B] int64 on the device): row b's first
+        ``frames[b]`` columns are ``spectrogram(audio[b:b+1, :n_samples[b]])``, the rest is 0; samples behind a row's end
+        are never read."""
+        a, n_dev, _, L_max, hop, T, _ = self._ragged_audio(audio, n_samples, hop_length)
+        B = a.shape[0]
+        spec = self._f(B, self.dims.spec_channels, T)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        ws = self._workspace("spectrogram", self.lib.vsp_spectrogram_ragged_workspace_bytes(self.ctx, B, L_max, hop))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_spectrogram_ragged(self.ctx, self._stream(), B, L_max, hop, _ptr(a), a.shape[1], _ptr(n_dev),
+                                                 _ptr(spec), _ptr(frames), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_spectrogram_ragged")
+        return spec, frames
+
+    def convert_latent(self, audio, n_samples, sid_src, sid_tgt, noise=None, noise_seed=None, noise_scale: float = 1.0,
+                       hop_length: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """``vsp_convert_latent``: audio to the converted latent -- ragged spectrogram, posterior encoder and forward flow
+        with the source speaker, reverse flow with the target speaker; the generator does not run (the counterpart of
+        ``decode(max_len=0)``).  Row b is what ``voice_conversion`` computes up to ``z_hat`` for the recording alone.
+        ``noise`` [B, inter, T_max]: row b uses ``noise[b, :, :frames[b]]``; None: the library draws row b's tensor from the
+        Philox stream keyed ``noise_seed[b]`` (a list of B ints).  ``noise_scale`` multiplies the posterior's noise (1.0: the
+        reference; 0: nothing is drawn or read).  Returns ``z_hat, g, frames, y_mask, z, z_p`` (device) and ``frames_host``."""
+        a, n_dev, _, L_max, hop, T, frames_host = self._ragged_audio(audio, n_samples, hop_length)
+        B = a.shape[0]
+        if isinstance(noise_seed, (int, np.integer)):
+            raise ValueError("convert_latent takes one noise_seed per recording (a sequence of B ints), not a plain int")
+        seeds = None if noise_seed is None else [int(x) for x in noise_seed]
+        if seeds is not None and len(seeds) != B:
+            raise ValueError(f"noise_seed must have {B} entries, got {len(seeds)}")
+        ss, st = _dev_i64(sid_src, self.device).reshape(-1), _dev_i64(sid_tgt, self.device).reshape(-1)
+        if ss.numel() != B or st.numel() != B:
+            raise ValueError(f"sid_src and sid_tgt must have {B} entries")
+        inter = self.dims.inter_channels
+        if noise is not None:
+            noise = _dev_f32(noise, self.device)
+            if tuple(noise.shape) != (B, inter, T):
+                raise ValueError(f"noise must be [{B},{inter},{T}], got {tuple(noise.shape)}")
+        z, z_p, z_hat = (self._f(B, inter, T) for _ in range(3))
+        g = self._f(B, self.dims.gin_channels)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        y_mask = torch.empty((B, 1, T), dtype=torch.uint8, device=self.device)
+        ws = self._workspace("convert", self.lib.vsp_convert_latent_workspace_bytes(self.ctx, B, L_max, hop))
+        if noise is None and float(noise_scale) != 0.0:   # (scale 0 draws nothing: the context's seeds stay as they are)
+            self.set_noise_seeds(seeds)      # (None forgets them: the library then refuses to draw, VSP_ERR_STATE)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_convert_latent(self.ctx, self._stream(), B, L_max, hop, _ptr(a), a.shape[1], _ptr(n_dev),
+                                             _ptr(ss), _ptr(st), _ptr(noise), float(noise_scale), _ptr(z_hat), _ptr(g),
+                                             _ptr(frames), _ptr(y_mask), _ptr(z), _ptr(z_p), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_convert_latent")
+        return dict(z_hat=z_hat, g=g, frames=frames, y_mask=y_mask, z=z, z_p=z_p, frames_host=frames_host)
+
+    def convert(self, audio, n_samples, sid_src, sid_tgt, noise=None, noise_seed=None, noise_scale: float = 1.0,
+                hop_length: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """``convert_latent`` followed by ``generator_ragged``: ``o_hat`` [B, 1, T_max * up], row b the
+        ``frames[b] * up`` samples of the recording converted alone and 0 behind; plus what ``convert_latent`` returns."""
+        r = self.convert_latent(audio, n_samples, sid_src, sid_tgt, noise, noise_seed, noise_scale, hop_length)
+        r["o_hat"] = self.generator_ragged(r["z_hat"], r["g"], r["frames"])
+        return r
+
     def generator(self, z, g) -> torch.Tensor:
         z = _dev_f32(z, self.device)
         g = _dev_f32(g, self.device).reshape(z.shape[0], -1)

@@ -159,6 +159,26 @@ class SynthesizerTrn:
         r = eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, noise, **({"isolated": True} if isolated else {}))
         return r["o_hat"], r["y_mask"].to(torch.float32), (r["z"], r["z_p"], r["z_hat"])
 
+    @torch.no_grad()
+    def convert_audio(self, audio, n_samples, sid_src, sid_tgt, *, noise: Optional[torch.Tensor] = None, noise_seed=None,
+                      noise_scale: float = 1.0):
+        """``voice_conversion`` from audio, for a batch of recordings of different lengths: ``audio`` [B, L] at the model's
+        rate, row b the recording ``audio[b, :n_samples[b]]`` (what lies behind is never read).  Every recording is
+        converted as the reference converts it alone -- ``voice_conversion`` on ``spectrogram_torch`` of that recording,
+        B = 1 -- and every returned tensor is exactly 0 behind the row's ``T_b`` frames (``T_b * up`` samples).
+        ``noise`` [B, inter, T_max] replaces the posterior's ``torch.randn_like`` (row b uses its first ``T_b`` columns);
+        without it ``noise_seed`` is a list of B ints, one Philox key per recording (a plain int raises ``ValueError``, as in
+        ``infer(isolated=True)``).  ``noise_scale`` multiplies that noise: 1.0 is the reference, 0 needs neither noise nor
+        seeds.  Returns ``(o_hat, y_mask, (z, z_p, z_hat))`` like ``voice_conversion``."""
+        eng = self._engine
+        if not eng.ready:
+            raise RuntimeError("weights not loaded: call load_state_dict first")
+        assert self.n_speakers > 0, "n_speakers have to be larger than 0."      # models.py:725
+        if not eng.has_voice_conversion:
+            raise RuntimeError("convert_audio needs the enc_q.* tensors: the loaded state_dict had none")
+        r = eng.convert(audio, n_samples, sid_src, sid_tgt, noise=noise, noise_seed=noise_seed, noise_scale=noise_scale)
+        return r["o_hat"], r["y_mask"].to(torch.float32), (r["z"], r["z_p"], r["z_hat"])
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

@@ -333,6 +333,61 @@ def _table_controls(batch, rows_ctl):
     return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
 
 
+def _text_latents(eng, collate, rows, seeds, scales, noise_scale: float):
+    """The text requests of one batch or admitted group to their latent: ``collate``, the per-row table where the requests
+    need one, then ONE isolated ``encode`` / ``frame_lengths_host`` / ``decode(max_len=0)``.  Returns per request
+    ``(z row [inter, T], g row, frames)``; a request of no frames gives ``(None, None, 0)``."""
+    import torch
+    batch = collate(rows)
+    t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
+    ctl = (batch.get("duration"), batch.get("f0"), batch.get("energy"))
+    table = _row_table(batch, scales, noise_scale)
+    kw = {}
+    if table is not None:                # (passed only when set: a group without one makes the calls it always made)
+        ctl, kw = _table_controls(batch, table), {"row_controls": table}
+    enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
+                     isolated=True, **kw)
+    frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
+    z = None
+    if tf > 0:
+        z = eng.decode(enc, tf, None, noise_scale, max_len=0, noise_seed=list(seeds), isolated=True, **kw)["z"]
+    return [(z[b], enc["g"][b], int(frames[b])) if int(frames[b]) > 0 else (None, None, 0) for b in range(len(rows))]
+
+
+class _Conversion:
+    """A conversion request of the batching services (``submit_conversion``): a recording at the model's rate, the speaker
+    it was spoken by and the speaker to convert it to.  To the vocoder it is a row like any other -- a latent, a speaker
+    vector and a length -- so it shares generator calls and ticks with text requests."""
+
+    def __init__(self, audio, sid_src: int, sid_tgt: int, noise_scale):
+        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
+        if a.ndim != 1:
+            raise ValueError("audio must be a 1-D float32 array at the model's sampling rate")
+        self.audio, self.sid_src, self.sid_tgt = a, int(sid_src), int(sid_tgt)
+        self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)      # (1.0: the reference's posterior)
+
+
+def _convert_latents(eng, jobs, seeds):
+    """The conversion requests of one batch or admitted group through ``Engine.convert_latent``: ONE call (one per
+    distinct ``noise_scale``, which is an argument of the call, where the requests name several).  Returns per request
+    ``(z_hat row, g row, frames)``; a recording too short for a frame gives ``(None, None, 0)``.  The frame counts are
+    host arithmetic (``frames_host``): nothing is read back from the device."""
+    out = [(None, None, 0)] * len(jobs)
+    for scale in sorted({j.noise_scale for j in jobs}):
+        idx = [i for i, j in enumerate(jobs) if j.noise_scale == scale and eng.convert_frames(j.audio.size) > 0]
+        if not idx:
+            continue
+        n = [jobs[i].audio.size for i in idx]
+        audio = np.zeros((len(idx), max(n)), dtype=np.float32)
+        for k, i in enumerate(idx):
+            audio[k, : n[k]] = jobs[i].audio
+        r = eng.convert_latent(audio, n, [jobs[i].sid_src for i in idx], [jobs[i].sid_tgt for i in idx], None,
+                               noise_seed=[int(seeds[i]) for i in idx], noise_scale=scale)
+        for k, i in enumerate(idx):
+            out[i] = (r["z_hat"][k], r["g"][k], int(r["frames_host"][k]))
+    return out
+
+
 class BatchingSynthesisService:
     """Requests from many callers, synthesised together (round 10).  The services above refuse a request while another is in
     flight, because in the reference's padded batch an utterance's audio depends on its batch-mates; in ISOLATED mode it
@@ -343,6 +398,10 @@ class BatchingSynthesisService:
     A request may leave any of durations / f0 / energy to the predictors (``text.request_row``) and name its own
     ``duration_scale`` / ``pitch_scale`` / ``energy_scale`` / ``noise_scale``: such a batch runs with the per-row table built
     from its requests (``infer(row_controls=...)``), and each request is still what the reference returns for it alone.
+    ``submit_conversion`` queues a recording to convert from one speaker to another (``SynthesizerTrn.convert_audio``); a
+    collected batch may hold both kinds: the text rows go to their latent (``encode`` / ``frame_lengths_host`` /
+    ``decode(max_len=0)``), the conversions through one ``convert_latent``, and ONE ``generator_ragged`` call produces every
+    waveform.  A batch without a conversion makes exactly the ``net.infer`` call above.
     ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays)."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
@@ -376,6 +435,20 @@ class BatchingSynthesisService:
             if self._closed:
                 raise RuntimeError("the service is closed")
             self._q.put((row, int(noise_seed), fut, (duration_scale, pitch_scale, energy_scale, noise_scale)))
+        return fut
+
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *,
+                          noise_scale=None) -> "concurrent.futures.Future":
+        """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
+        PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
+        ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
+        ``noise_scale``); ``noise_seed`` keys that noise."""
+        fut: "concurrent.futures.Future" = concurrent.futures.Future()
+        job = _Conversion(audio, sid_src, sid_tgt, noise_scale)
+        with self._gate:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            self._q.put((job, int(noise_seed), fut, (None,) * 4))
         return fut
 
     def close(self) -> None:
@@ -417,6 +490,8 @@ class BatchingSynthesisService:
     def _synthesize(self, rows, seeds, scales=None):
         import torch
         net = self.net
+        if any(isinstance(r, _Conversion) for r in rows):
+            return self._synthesize_mixed(rows, seeds, scales)
         batch = self._collate(rows)
         t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
         ctl = (batch.get("duration"), batch.get("f0"), batch.get("energy"))
@@ -433,6 +508,46 @@ class BatchingSynthesisService:
             return [pcm16(o[b, 0, : int(frames[b]) * hop]) for b in range(len(rows))]
         eng = net._engine
         return [_host_i16(eng.output(o[b:b + 1, 0, : int(frames[b]) * hop], pcm=True)[0]) for b in range(len(rows))]
+
+    def _latents(self, rows, seeds, scales):
+        """Per request ``(z row [inter, T], g row, frames)``: the text rows of a mixed batch through ``_text_latents`` (the
+        streaming service's admission), its conversions through ``_convert_latents``."""
+        eng = self.net._engine
+        out = [None] * len(rows)
+        text = [i for i, r in enumerate(rows) if not isinstance(r, _Conversion)]
+        conv = [i for i, r in enumerate(rows) if isinstance(r, _Conversion)]
+        if text:
+            lats = _text_latents(eng, self._collate, [rows[i] for i in text], [seeds[i] for i in text],
+                                 [scales[i] for i in text], self.noise_scale)
+            for i, lat in zip(text, lats):
+                out[i] = lat
+        for i, lat in zip(conv, _convert_latents(eng, [rows[i] for i in conv], [seeds[i] for i in conv])):
+            out[i] = lat
+        return out
+
+    def _synthesize_mixed(self, rows, seeds, scales):
+        """A batch with conversions: every request's latent, speaker vector and length packed into one ragged batch, ONE
+        ``generator_ragged`` call, then the output stage as in ``_synthesize``."""
+        import torch
+        net, eng = self.net, self.net._engine
+        scales = scales if scales is not None else [(None,) * 4] * len(rows)
+        lat = self._latents(rows, seeds, scales)
+        live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
+        pcms = [np.zeros(0, dtype="<i2") for _ in rows]
+        if not live:
+            return pcms
+        T = max(lat[i][2] for i in live)
+        z0 = torch.as_tensor(lat[live[0]][0])
+        Z = torch.zeros((len(live), z0.shape[0], T), dtype=torch.float32, device=z0.device)
+        for b, i in enumerate(live):
+            Z[b, :, : lat[i][2]] = torch.as_tensor(lat[i][0])[:, : lat[i][2]]
+        G = torch.stack([torch.as_tensor(lat[i][1]).reshape(-1) for i in live])
+        o = eng.generator_ragged(Z, G, [lat[i][2] for i in live])
+        hop = net.dims.total_upsample
+        for b, i in enumerate(live):
+            x = o[b:b + 1, 0, : lat[i][2] * hop]
+            pcms[i] = pcm16(x) if self.output_rate is None else _host_i16(eng.output(x, pcm=True)[0])
+        return pcms
 
 
 class _RowStream:
@@ -480,7 +595,7 @@ class _StreamRequest:
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
     def __init__(self, row, seed: int, scales=(None, None, None, None)):
-        self.row, self.seed, self.stream = row, seed, _RowStream()
+        self.row, self.seed, self.stream = row, seed, _RowStream()       # (``row``: a collate row, or a ``_Conversion``)
         self.scales = scales          # the request's own (duration, pitch, energy, noise) scales; None: the defaults
         self.z = self.g = None
         self.L = self.pos = 0
@@ -515,7 +630,10 @@ class StreamingBatchService:
     the tick instead makes one ``Engine.generator_stream_rows_output`` call -- the ragged output stage in place of the
     collect launch -- and one device-to-host copy, as the plain path does; a request carries its filter history
     (``Engine.output_history``) from admission on, and the bytes are the same.  ``stats``: ticks, rows per tick and
-    admitted groups.  No priorities, no retries, no backpressure."""
+    admitted groups.  No priorities, no retries, no backpressure.
+    ``submit_conversion`` queues a recording to convert to another speaker: admission runs the group's conversions through
+    one ``convert_latent`` and keeps each one's ``z_hat`` row, target speaker vector and ``L = T(n)``; from then on it is an
+    ordinary row of the tick, next to text rows (a group without a conversion makes the calls it always made)."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
@@ -556,6 +674,19 @@ class StreamingBatchService:
         1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
         request's PCM16 ``bytes``, one piece per tick the request takes part in."""
         req = _StreamRequest(row, int(noise_seed), (duration_scale, pitch_scale, energy_scale, noise_scale))
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            self._pending.append(req)
+            self._cv.notify()
+        return req.stream
+
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> _RowStream:
+        """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
+        the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
+        frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
+        NOT the service's text-to-speech ``noise_scale``)."""
+        req = _StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale), int(noise_seed))
         with self._cv:
             if self._closed:
                 raise RuntimeError("the service is closed")
@@ -615,28 +746,21 @@ class StreamingBatchService:
             return
         self.stats["groups"] += 1
         try:
-            import torch
             eng = self.net._engine
-            batch = self._collate([r.row for r in group])
-            t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
-            ctl = (batch.get("duration"), batch.get("f0"), batch.get("energy"))
-            table = _row_table(batch, [r.scales for r in group], self.noise_scale)
-            kw = {}
-            if table is not None:        # (passed only when set: a group without one makes the calls it always made)
-                ctl, kw = _table_controls(batch, table), {"row_controls": table}
-            enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]),
-                             t(ctl[1]), t(ctl[2]), isolated=True, **kw)
-            frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
-            z = None
-            if tf > 0:
-                z = eng.decode(enc, tf, None, self.noise_scale, max_len=0, noise_seed=[r.seed for r in group],
-                               isolated=True, **kw)["z"]
-            for b, r in enumerate(group):
-                r.L, r.pos = int(frames[b]), 0
+            text = [r for r in group if not isinstance(r.row, _Conversion)]
+            conv = [r for r in group if isinstance(r.row, _Conversion)]
+            lats = []
+            if text:
+                lats += zip(text, _text_latents(eng, self._collate, [r.row for r in text], [r.seed for r in text],
+                                                [r.scales for r in text], self.noise_scale))
+            if conv:                         # the group's conversions: their z_hat, target speaker vector and T(n)
+                lats += zip(conv, _convert_latents(eng, [r.row for r in conv], [r.seed for r in conv]))
+            for r, (z, g, L) in lats:
+                r.z, r.g, r.L, r.pos = z, g, L, 0
+            for r in group:
                 if r.L <= 0:
                     r.stream._q.put(_RowStream._END)          # nothing to synthesise: no bytes
                     continue
-                r.z, r.g = z[b], enc["g"][b]
                 if self.fused_output:
                     r.history = eng.output_history()
                 self._active.append(r)
