@@ -1,5 +1,5 @@
 // Launch arguments of the channels-last split-f16 vocoder kernels (kernels.h: Cl*Args), built in ONE place for the model's
-// schedule (api.hip) and the stand-alone operators (ops.hip).  A builder takes device pointers and shapes and sets every
+// schedule (api_generator.hip) and the stand-alone operators (ops.hip).  A builder takes device pointers and shapes and sets every
 // field that follows from them -- dense tensors [B][T][C], "same" padding, the reference's leaky-relu slope, div = 1 --;
 // what only the caller knows stays with the caller: acc_prev / div, ring / rw64, the ragged batch's glen / grate.
 // Included by kernels.h, behind the structs.

@@ -1,7 +1,7 @@
 // 1x1 frame-rate convolutions in column-tile form (conv_cols.h): the generic epilogue of conv_mfma.hip's kernels (bias,
 // masks, scaling, residual, accumulate, two destinations -- reference modules.py:165-176, 324-343, models.py:526-529)
 // and the LayerNorm form (x + conv_o(att) normalised over the channels in the same launch: reference
-// attentions.py:40-42, modules.py:29-32).  launch_conv routes here for small grids; run_encoder_masked (api.hip) asks
+// attentions.py:40-42, modules.py:29-32).  launch_conv routes here for small grids; run_encoder_masked (api_frame.hip) asks
 // for the LayerNorm form directly.
 #include "conv_cols.h"
 

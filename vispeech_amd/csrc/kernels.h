@@ -289,7 +289,7 @@ hipError_t launch_conv_post_cl(const float* x, long x_bs, int x_ts, const float*
 // Trimmed tails (round 5).  The generator's input behind an utterance's last frame is exactly zero (reference
 // models.py:720: z * x_mask), so its output there is a bias-driven signal that depends on the distance to the utterance's
 // end and to the tensor's end only: periodic in one frame once the receptive field away from both.
-// Output frame F depends on input frames [F - back, F + fwd] (api.hip, generator_frame_dependence).
+// Output frame F depends on input frames [F - back, F + fwd] (api_generator.hip, generator_frame_dependence).
 //   gen_plan:  glen[b] = len[b] + back + 1 + fwd where that is < T (else T): the frames the generator computes for b;
 //   gen_tail_fill:  frames [len + back + 1, T - fwd) of o[b] = frame len + back (the steady state), frames
 //                   [T - fwd, T) = frames [len + back + 1, len + back + 1 + fwd) (the computed tensor end); up = samples per frame.
