@@ -391,6 +391,63 @@ int vsp_convert_latent(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, co
                        float noise_scale, float* z_hat, float* g_tgt, int64_t* frames, uint8_t* y_mask, float* z, float* z_p,
                        void* workspace, int64_t workspace_bytes);
 
+/* ---- live conversion: audio fed while it is recorded, exact chunks out (additive, ABI 7) */
+/* The conversion path is convolutional throughout (enc_q's WN, the two flow directions), so z_hat[:, t] of a recording
+ * depends on its spectrogram columns [t - H, t + H] only, H = vsp_convert_halo_frames() =
+ * posterior_layers (k - 1) / 2 + 2 n_flows flow_layers (k - 1) / 2 with k = flow_kernel: 96 for configs/config.json.
+ * Column t reads the samples [t hop - pad, t hop - pad + n_fft) of the recording, pad = (n_fft - hop) / 2, reflected at
+ * its two TRUE ends.  A recording can therefore be converted window by window while it arrives, and the result is not an
+ * approximation: a frame is delivered once every sample it depends on is there, and it never changes later.
+ *
+ * vsp_convert_window_plan is that arithmetic without a device or a context.  To deliver the frames [e0, e1) of a
+ * recording of which n_known samples have arrived, the window of frames is *w0 = max(0, e0 - halo) and *w1 = e1 + halo
+ * while the recording is open, min(T(n_known), e1 + halo) once it is closed (T = vsp_convert_frames); [*s_lo, *s_hi) are
+ * the samples the window's frames read, after reflection -- at sample 0 always, at the end only when closed.  Returns 1 if
+ * every one of them is below n_known (the window can run), 0 if not yet, and VSP_ERR_ARG for e0 < 0, e1 <= e0, a closed
+ * recording with e1 > T, hop <= 0, n_fft < hop, halo < 0 or n_known < 0.  The outputs (each may be NULL) are written
+ * whenever the result is not an error.  An open window reads no sample at or behind n_known -- the condition under which
+ * the one-shot front end does not reflect for its frames either: what is delivered early is what vsp_convert_latent
+ * computes for the finished recording.
+ *
+ * vsp_convert_stream_rows runs up to 64 such windows in one set of launches.  Row b (HOST memory, read before the call
+ * returns; it reaches the device as a kernel argument) holds the samples [first_sample, n_known) of its recording at
+ * `audio` (DEVICE: sample s is audio[s - first_sample]) and asks for the frames [e0, e1), e1 - e0 <= span_frames.
+ * z_hat [B][inter_channels][span_frames]: row b's columns [0, e1 - e0) are the frames [e0, e1) of what the reference
+ * computes up to z_hat (voice_conversion, models.py:724-732) on spectrogram_torch of the WHOLE recording alone, to the
+ * tolerance between two launch shapes of this library; the rest of the row is exactly 0.0.  g_tgt [B][gin] =
+ * emb_g(sid_tgt), for the generator call.  No sample outside [s_lo, s_hi) of the row's plan is read.
+ * NOISE LAYOUT: the posterior's noise for (channel c, frame t) of a row is noise_scale times element t * inter_channels + c
+ * of the Philox stream keyed `seed` (vsp_randn_at) -- FRAME-major, so that it does not depend on the final length, which
+ * an open recording does not have yet.  It is deliberately NOT the [inter][T_b] layout of vsp_convert_latent, which needs
+ * T_b: the same seed gives different noise in the two entry points.  With noise_scale == 0 nothing is drawn and z = m_q.
+ * How: the window framing (the ragged framing's scheme with a frame offset, a sample base and the end reflection only
+ * for closed rows), the DFT convolution of vsp_spectrogram and a magnitude masked by w1 - w0; the chain of
+ * vsp_convert_latent on the windows as utterances of w1 - w0 frames -- an artificial end a full halo from every delivered
+ * frame, the trick of vsp_generator_stream_rows --; one cut launch.  No per-layer state is kept between calls: the halo is
+ * recomputed, (chunk + 2 H) / chunk times the work of the chunk itself.  No allocation, no synchronisation, everything on
+ * the caller's stream.  Checked on the host before anything is launched, VSP_ERR_ARG otherwise: 1 <= B <= 64, hop > 0,
+ * span_frames >= 1, no null pointer, 0 <= first_sample <= s_lo, a finite noise_scale, speakers in [0, n_speakers), and
+ * every row ready by vsp_convert_window_plan.  Needs the enc_q.* tensors (VSP_ERR_STATE).  Workspace:
+ * vsp_convert_stream_rows_workspace_bytes -- sized by span_frames + 2 H frames per row, never by a recording's length.
+ * ALGORITHMIC DELAY of a live conversion into the streamed vocoder (halo G = vsp_generator_halo_frames): the chunk of
+ * frames [f0, f1) can run once sample (f1 + G + H - 1) hop - pad + n_fft - 1 has arrived, so the last frame of a chunk
+ * leaves (G + H) hop + n_fft - pad samples after it was spoken, and the first one a chunk later: 57600 samples, about
+ * 1.3 s at 44.1 kHz, for configs/config.json (G 14, H 96, hop 512, n_fft 2048). */
+typedef struct vsp_convert_row {
+  const float* audio;
+  int64_t first_sample, n_known;
+  int32_t closed, e0, e1;
+  int64_t sid_src, sid_tgt;
+  uint64_t seed;
+  float noise_scale;
+} vsp_convert_row;
+int vsp_convert_halo_frames(const vsp_ctx* ctx);
+int vsp_convert_window_plan(int n_fft, int hop, int halo, int64_t n_known, int closed, int e0, int e1, int* w0, int* w1,
+                            int64_t* s_lo, int64_t* s_hi);
+int64_t vsp_convert_stream_rows_workspace_bytes(const vsp_ctx* ctx, int B, int span_frames);
+int vsp_convert_stream_rows(vsp_ctx* ctx, void* stream, int B, int hop, const vsp_convert_row* rows, int span_frames,
+                            float* z_hat, float* g_tgt, void* workspace, int64_t workspace_bytes);
+
 /* piecewise_rational_quadratic_transform with tails='linear' (reference transforms.py:12-193),
  * n elements, nb bins; uw/uh [n][nb], ud [n][nb-1]; outputs y[n], logabsdet[n]. */
 int vsp_rq_spline(void* stream, int64_t n, int nb, const float* x, const float* uw, const float* uh,

@@ -59,6 +59,14 @@ class VspRowControl(C.Structure):
                 ("noise_scale", C.c_float), ("given", C.c_uint32)]
 
 
+class VspConvertRow(C.Structure):
+    """``vsp_convert_row``: one window of a live conversion -- the samples ``[first_sample, n_known)`` of a recording at
+    ``audio`` (device pointer), the frames ``[e0, e1)`` to deliver, the two speakers and the row's noise."""
+    _fields_ = [("audio", C.c_void_p), ("first_sample", C.c_int64), ("n_known", C.c_int64), ("closed", C.c_int32),
+                ("e0", C.c_int32), ("e1", C.c_int32), ("sid_src", C.c_int64), ("sid_tgt", C.c_int64), ("seed", C.c_uint64),
+                ("noise_scale", C.c_float)]
+
+
 GIVEN_DURATION, GIVEN_PITCH, GIVEN_ENERGY = 1, 2, 4                  # VSP_GIVEN_* (vsp_set_row_controls)
 
 STREAM_ROWS_MAX = 64
@@ -141,6 +149,11 @@ SIGNATURES = {
     "vsp_spectrogram_ragged": (_I, [_P, _P, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _I64]),
     "vsp_convert_latent_workspace_bytes": (_I64, [_P, _I, _I, _I]),
     "vsp_convert_latent": (_I, [_P, _P, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I64]),
+    "vsp_convert_halo_frames": (_I, [_P]),
+    "vsp_convert_window_plan": (_I, [_I, _I, _I, _I64, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I64),
+                                     C.POINTER(_I64)]),
+    "vsp_convert_stream_rows_workspace_bytes": (_I64, [_P, _I, _I]),
+    "vsp_convert_stream_rows": (_I, [_P, _P, _I, _I, C.POINTER(VspConvertRow), _I, _P, _P, _P, _I64]),
     "vsp_rq_spline": (_I, [_P, _I64, _I, _P, _P, _P, _P, _I, _F, _P, _P]),
     "vsp_mel_filterbank": (_I, [_I, _I, _I, _F, _F, _P]),
     "vsp_spec_to_mel": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _P]),

@@ -137,6 +137,55 @@ void convert_latent_impl(Run& r, int B, int L_max, int hop, int T, const Convert
                                           io.noise_scale, drawn, seeds_dev, g_src, io.g_tgt, io.y_mask, z, m_q, logs_q, z_p, io.z_hat});
 }
 
+// The rows of a vsp_convert_stream_rows call as its kernels take them (kernels.h), built and checked on the host.
+struct WindowRows {
+  ConvWinFrameRows frame; ConvWinNoiseRows noise; StreamCollectRows cut;
+  bool draws = false;          // some row has a noise_scale other than 0
+};
+struct WindowIO {
+  const WindowRows* rows;      // NULL in the sizing pass
+  int span_frames; float *z_hat, *g_tgt;
+};
+
+// Windows of live recordings to their z_hat: window framing -> DFT -> magnitude, then the chain of vsp_convert_latent on
+// the windows as utterances of w1 - w0 frames (their lengths and speakers written by the framing launch), then the cut.
+// T: the longest window of the call (the sizing pass: span_frames + 2 halo).
+void convert_window_impl(Run& r, int B, int hop, int T, const WindowIO& io) {
+  vsp_ctx* const ctx = r.ctx;
+  const vsp_config& c = ctx->cfg;
+  const int n_fft = 2 * (c.spec_channels - 1), inter = c.inter_channels;
+  const long n = (long)B * inter * T;
+  Ws& ws = r.ws;
+  int64_t* len = reinterpret_cast<int64_t*>(ws.bytes((size_t)B * sizeof(int64_t)));
+  int64_t* sid_src = reinterpret_cast<int64_t*>(ws.bytes((size_t)B * sizeof(int64_t)));
+  int64_t* sid_tgt = reinterpret_cast<int64_t*>(ws.bytes((size_t)B * sizeof(int64_t)));
+  uint8_t* y_mask = reinterpret_cast<uint8_t*>(ws.bytes((size_t)B * T));
+  float* g_src = ws.f((size_t)B * c.gin_channels);
+  float* spec = ws.f((size_t)B * c.spec_channels * T);
+  float *z = ws.f((size_t)n), *z_p = ws.f((size_t)n), *z_hat = ws.f((size_t)n);
+  float *m_q = ws.f((size_t)n), *logs_q = ws.f((size_t)n);      // (launch_reparam walks contiguous tensors)
+  float* drawn = ws.f((size_t)n);
+  Overlay stages(ws);
+  {
+    T3 F = ws.t3(B, n_fft, T), RI = ws.t3(B, 2 * c.spec_channels, T);
+    if (!ws.dry && !ws.overflow) {
+      r.chk(launch_window_frames(io.rows->frame, F.p, F.bs, F.cs, len, sid_src, sid_tgt, B, n_fft, hop, T, r.s), "window frames");
+      ConvArgs a = r.args(ctx->model.stft, F, RI, T, T);
+      r.conv(a, B);
+      if (r.ok()) r.chk(launch_window_magnitude(RI.p, RI.bs, RI.cs, len, spec, B, c.spec_channels, T, r.s), "window magnitude");
+      if (r.ok() && io.rows->draws) r.chk(launch_window_noise(io.rows->noise, B, inter, T, drawn, r.s), "window noise");
+    }
+  }
+  if (r.rc) return;
+  stages.next();
+  // (the rows' noise arrives scaled: noise_scale is each row's own; with no row drawing, nothing is read)
+  const bool draws = io.rows && io.rows->draws;
+  run_conversion(r, stages, B, T, ChainIO{ext(spec, c.spec_channels, T), len, sid_src, sid_tgt, draws ? drawn : nullptr,
+                                          draws ? 1.f : 0.f, nullptr, nullptr, g_src, io.g_tgt, y_mask, z, m_q, logs_q, z_p, z_hat});
+  if (!ws.dry && !ws.overflow && r.ok())
+    r.chk(launch_window_cut(z_hat, io.rows->cut, B, inter, T, io.z_hat, io.span_frames, r.s), "window cut");
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,6 +308,76 @@ int vsp_convert_latent(vsp_ctx* ctx, void* stream, int B, int L_max, int hop, co
   const ConvertIO io{{audio, nullptr, audio_stride, n_samples, frames}, sid_src, sid_tgt, noise, noise_scale, z_hat, g_tgt, y_mask, z, z_p};
   return run_sized(ctx, stream, "convert_latent", vsp_convert_latent_workspace_bytes(ctx, B, L_max, hop), workspace, workspace_bytes,
                    [&](Run& r) { convert_latent_impl(r, B, L_max, hop, T, io); });
+}
+
+// ---------------------------------------------------------------------------------- live conversion
+int vsp_convert_halo_frames(const vsp_ctx* ctx) {
+  if (!ctx) return VSP_ERR_ARG;
+  const vsp_config& c = ctx->cfg;
+  const int side = (c.flow_kernel - 1) / 2;
+  if (c.flow_kernel < 1 || c.posterior_layers < 0 || c.n_flows < 0 || c.flow_layers < 0) return VSP_ERR_ARG;
+  // enc_q's WN, then the flow forward and the flow in reverse: every WN layer widens the dependence by (k - 1) / 2 a side
+  return c.posterior_layers * side + 2 * c.n_flows * c.flow_layers * side;
+}
+
+int vsp_convert_window_plan(int n_fft, int hop, int halo, int64_t n_known, int closed, int e0, int e1, int* w0, int* w1,
+                            int64_t* s_lo, int64_t* s_hi) {
+  long lo = 0, hi = 0;
+  const int rc = convert_window_plan(n_fft, hop, halo, (long)n_known, closed, e0, e1, w0, w1, &lo, &hi);
+  if (rc < 0) return VSP_ERR_ARG;
+  if (s_lo) *s_lo = lo;
+  if (s_hi) *s_hi = hi;
+  return rc;
+}
+
+int64_t vsp_convert_stream_rows_workspace_bytes(const vsp_ctx* ctx, int B, int span_frames) {
+  if (!ctx || ctx->cfg.spec_channels <= 1 || B < 1 || B > STREAM_ROWS_MAX || span_frames < 1) return VSP_ERR_ARG;
+  const int halo = vsp_convert_halo_frames(ctx);
+  if (halo < 0 || span_frames > INT32_MAX / 2 - 2 * halo) return VSP_ERR_ARG;
+  return dry_bytes(ctx, [&](Run& r) { convert_window_impl(r, B, 1, span_frames + 2 * halo, WindowIO{}); });
+}
+
+int vsp_convert_stream_rows(vsp_ctx* ctx, void* stream, int B, int hop, const vsp_convert_row* rows, int span_frames,
+                            float* z_hat, float* g_tgt, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  int n_fft = 0;
+  const int halo = vsp_convert_halo_frames(ctx);
+  if (convert_geometry(ctx, hop, &n_fft) != VSP_OK || stft_ragged_tile(n_fft, hop) <= 0 || halo < 0 || B < 1 ||
+      B > STREAM_ROWS_MAX || !rows || span_frames < 1 || !z_hat || !g_tgt || !workspace)
+    return ctx->fail(VSP_ERR_ARG, "vsp_convert_stream_rows: bad argument (needs spec_channels, 1 <= B <= %d, hop > 0, "
+                                  "span_frames >= 1 and no null pointer)", STREAM_ROWS_MAX);
+  WindowRows w;
+  int T = 0;
+  for (int b = 0; b < B; ++b) {
+    const vsp_convert_row& r = rows[b];
+    if (!r.audio || r.first_sample < 0 || r.n_known < r.first_sample || r.e1 - (int64_t)r.e0 > span_frames ||
+        !std::isfinite(r.noise_scale) || r.sid_src < 0 || r.sid_src >= ctx->cfg.n_speakers || r.sid_tgt < 0 ||
+        r.sid_tgt >= ctx->cfg.n_speakers)
+      return ctx->fail(VSP_ERR_ARG, "vsp_convert_stream_rows: row %d: null audio, first_sample outside [0, n_known], more than "
+                                    "span_frames = %d frames, a noise_scale that is not finite or a speaker outside [0, %d)",
+                       b, span_frames, ctx->cfg.n_speakers);
+    int w0 = 0, w1 = 0;
+    long s_lo = 0, s_hi = 0;
+    const int ready = convert_window_plan(n_fft, hop, halo, (long)r.n_known, r.closed != 0, r.e0, r.e1, &w0, &w1, &s_lo, &s_hi);
+    if (ready < 0)
+      return ctx->fail(VSP_ERR_ARG, "vsp_convert_stream_rows: row %d: frames [%d, %d) are not 0 <= e0 < e1%s", b, r.e0, r.e1,
+                       r.closed ? " <= T(n_known)" : "");
+    if (ready == 0 || s_lo < r.first_sample)
+      return ctx->fail(VSP_ERR_ARG, "vsp_convert_stream_rows: row %d: frames [%d, %d) read samples [%lld, %lld), the buffer holds "
+                                    "[%lld, %lld) (vsp_convert_window_plan)", b, r.e0, r.e1, (long long)s_lo, (long long)s_hi,
+                       (long long)r.first_sample, (long long)r.n_known);
+    w.frame.r[b] = ConvWinFrameRow{r.audio, (long)r.first_sample, (long)r.n_known, w0, w1 - w0, r.closed != 0, (int)r.sid_src,
+                                   (int)r.sid_tgt, 0};
+    w.noise.r[b] = ConvWinNoiseRow{r.seed, w0, w1 - w0, r.noise_scale, 0};
+    w.cut.r[b] = StreamCollectRow{r.e0 - w0, r.e1 - r.e0};
+    w.draws = w.draws || r.noise_scale != 0.f;
+    T = std::max(T, w1 - w0);
+  }
+  int rc = check_vc(ctx);
+  if (rc) return rc;
+  const WindowIO io{&w, span_frames, z_hat, g_tgt};
+  return run_sized(ctx, stream, "convert_stream_rows", vsp_convert_stream_rows_workspace_bytes(ctx, B, span_frames), workspace,
+                   workspace_bytes, [&](Run& r) { convert_window_impl(r, B, hop, T, io); });
 }
 
 }  // extern "C"

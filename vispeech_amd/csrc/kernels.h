@@ -464,6 +464,33 @@ hipError_t launch_stft_magnitude_ragged(const float* ri, long r_bs, long r_cs, c
                                         int64_t* frames, int B, int L_max, int n_fft, int hop, int spec_ch, int T_max,
                                         hipStream_t s);
 
+// Live conversion windows (convert_window.hip; include/vispeech_hip.h, vsp_convert_stream_rows): row b is the window of
+// frames [w0, w0 + Tw) of a recording that may still be arriving.  Descriptors by value, as for the streamed vocoder.
+// The window that delivers frames [e0, e1) and the samples it reads -- the contract of vsp_convert_window_plan; host only.
+int convert_window_plan(int n_fft, int hop, int halo, long n_known, int closed, int e0, int e1, int* w0, int* w1, long* s_lo,
+                        long* s_hi);
+struct ConvWinFrameRow {     // 48 B: sample s of the recording is audio[s - first]; n samples are known
+  const float* audio; long first, n; int w0, Tw, closed, sid_src, sid_tgt, pad;
+};
+struct ConvWinFrameRows { ConvWinFrameRow r[STREAM_ROWS_MAX]; };
+struct ConvWinNoiseRow { uint64_t seed; int w0, Tw; float scale; int pad; };      // 24 B
+struct ConvWinNoiseRows { ConvWinNoiseRow r[STREAM_ROWS_MAX]; };
+// f [B][n_fft][T_max]: f[b][k][j] = sample (w0_b + j) * hop + k - pad of the row, reflected at sample 0 and -- closed rows
+// only -- at sample n_b, for j < Tw_b; exactly 0 behind.  len[b] = Tw_b, sid_src[b], sid_tgt[b]: the rows' scalars for the
+// stages behind (written by the row's first block).  Every sample the windows read is inside the rows' buffers: the
+// caller has run convert_window_plan.
+hipError_t launch_window_frames(const ConvWinFrameRows& rows, float* f, long f_bs, long f_cs, int64_t* len, int64_t* sid_src,
+                                int64_t* sid_tgt, int B, int n_fft, int hop, int T_max, hipStream_t s);
+// spec [B][spec_ch][T_max] = sqrt(re^2 + im^2 + 1e-6) for j < len[b], exactly 0 behind
+hipError_t launch_window_magnitude(const float* ri, long r_bs, long r_cs, const int64_t* len, float* spec, int B, int spec_ch,
+                                   int T_max, hipStream_t s);
+// out[b][c][j] = scale_b * element (w0_b + j) * C + c of the Philox stream keyed seed_b for j < Tw_b, else 0: FRAME-major in
+// the stream, so a frame's noise does not depend on how long the recording turns out to be.  scale_b == 0: nothing drawn.
+hipError_t launch_window_noise(const ConvWinNoiseRows& rows, int B, int C, int T_max, float* out, hipStream_t s);
+// out[b][c][j] = j < n_b ? z[b][c][off_b + j] : 0 for j < span (z [B][C][T_max] dense; off_b + n_b <= T_max, n_b <= span)
+hipError_t launch_window_cut(const float* z, const StreamCollectRows& rows, int B, int C, int T_max, float* out, int span,
+                             hipStream_t s);
+
 }  // namespace vsp
 
 #include "cl_args.h"   // (builders of the Cl*Args above)

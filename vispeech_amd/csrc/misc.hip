@@ -3,6 +3,7 @@
 // rational-quadratic spline.  All tensors are [B][C][T] float32 with T contiguous; threads run
 // along T so that every global access is coalesced.
 #include "kernels.h"
+#include "philox.h"
 #include "row_controls.h"   // (the control formulas, shared with the per-row kernels)
 
 #include <math.h>
@@ -391,19 +392,7 @@ hipError_t launch_reparam(const float* m_p, const float* logs_p, const float* no
 // models.py:718 / :240): Philox4x32-10 (Salmon et al., SC'11; key = seed lo | hi, counter = (i / 4, 0, 0, 0)) ->
 // four 32-bit words -> two Box-Muller pairs, element i = word i % 4 of counter i / 4.  A function of (seed, i) only:
 // the same seed gives the same tensor on any grid and any GPU.  NOT torch's generator: a torch.manual_seed(s) draw
-// is a different sequence (documented in include/vispeech_hip.h).
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// is a different sequence (documented in include/vispeech_hip.h).  philox4x32_10 itself: philox.h.
 // `first` = index of out[0] in the stream: a shard of a larger tensor draws ITS elements (sharded batches do not depend on
 // the shard layout).  Uniforms: the top 23 bits, (x + 0.5) / 2^23 -- exact in fp32, strictly inside (0, 1).
 __global__ void __launch_bounds__(256) randn_kernel(uint32_t k0, uint32_t k1, long first, long n, float* __restrict__ out) {

@@ -671,6 +671,58 @@ class Engine:
         r["o_hat"] = self.generator_ragged(r["z_hat"], r["g"], r["frames"])
         return r
 
+    @property
+    def convert_halo(self) -> int:
+        """``vsp_convert_halo_frames``: frames of spectrogram a frame of ``z_hat`` depends on, on each side."""
+        return int(self.lib.vsp_convert_halo_frames(self.ctx))
+
+    def convert_window_plan(self, n_known: int, closed: bool, e0: int, e1: int, hop_length: Optional[int] = None):
+        """``vsp_convert_window_plan`` (host only) with this model's geometry and halo: ``(ready, w0, w1, s_lo, s_hi)`` of the
+        window that delivers frames ``[e0, e1)`` (``vispeech_amd.schema.convert_window_plan`` is its pure-Python twin)."""
+        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        w0, w1, lo, hi = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+        rc = int(self.lib.vsp_convert_window_plan(2 * (self.dims.spec_channels - 1), hop, self.convert_halo, int(n_known),
+                                                  int(bool(closed)), int(e0), int(e1), C.byref(w0), C.byref(w1), C.byref(lo),
+                                                  C.byref(hi)))
+        if rc < 0:
+            _lib.check(rc, None, "vsp_convert_window_plan")
+        return bool(rc), int(w0.value), int(w1.value), int(lo.value), int(hi.value)
+
+    def convert_stream_rows(self, rows, span_frames: int, hop_length: Optional[int] = None):
+        """``vsp_convert_stream_rows``: up to 64 windows of recordings that may still be arriving, in ONE set of launches.
+        ``rows`` is a sequence of ``(audio, first_sample, n_known, closed, e0, e1, sid_src, sid_tgt, seed, noise_scale)``:
+        ``audio`` a 1-D float32 tensor on the device that holds the samples ``[first_sample, n_known)`` of the recording,
+        and the frames ``[e0, e1)`` to deliver, ``e1 - e0 <= span_frames``; every row must be ready
+        (``convert_window_plan``).  Returns ``(z_hat [B, inter, span_frames], g [B, gin])``: row b's first ``e1 - e0``
+        columns are those frames of ``z_hat`` of the WHOLE recording converted alone, zeros behind; ``g`` is
+        ``emb_g(sid_tgt)``.  The noise of (channel c, frame t) is ``noise_scale`` times element ``t * inter + c`` of the
+        Philox stream keyed ``seed`` -- ``randn(seed, T, inter).T``, NOT the ``[inter, T]`` layout of ``convert_latent``."""
+        rows = list(rows)
+        B = len(rows)
+        if not 1 <= B <= _lib.STREAM_ROWS_MAX:
+            raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
+        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        span_frames = int(span_frames)
+        arr = (_lib.VspConvertRow * B)()
+        keep = []
+        for r, (audio, first, n_known, closed, e0, e1, sid_src, sid_tgt, seed, noise_scale) in zip(arr, rows):
+            if (not torch.is_tensor(audio) or audio.dtype != torch.float32 or audio.device != self.device or audio.dim() != 1
+                    or not audio.is_contiguous() or audio.numel() < int(n_known) - int(first)):
+                raise ValueError("a row's audio must be a contiguous 1-D float32 tensor on the engine's device that holds "
+                                 "the samples [first_sample, n_known)")
+            keep.append(audio)
+            r.audio, r.first_sample, r.n_known = audio.data_ptr(), int(first), int(n_known)
+            r.closed, r.e0, r.e1 = int(bool(closed)), int(e0), int(e1)
+            r.sid_src, r.sid_tgt, r.seed, r.noise_scale = int(sid_src), int(sid_tgt), int(seed), float(noise_scale)
+        z_hat = self._f(B, self.dims.inter_channels, max(span_frames, 1))
+        g = self._f(B, self.dims.gin_channels)
+        ws = self._workspace("convert_stream_rows", self.lib.vsp_convert_stream_rows_workspace_bytes(self.ctx, B, span_frames))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_convert_stream_rows(self.ctx, self._stream(), B, hop, arr, span_frames, _ptr(z_hat), _ptr(g),
+                                                  _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_convert_stream_rows")
+        return z_hat, g
+
     def generator(self, z, g) -> torch.Tensor:
         z = _dev_f32(z, self.device)
         g = _dev_f32(g, self.device).reshape(z.shape[0], -1)

@@ -266,3 +266,42 @@ def dims_from_ctor(n_vocab, spec_channels, hop_length, sampling_rate, segment_si
         upsample_initial_channel=upsample_initial_channel,
         upsample_kernel_sizes=list(upsample_kernel_sizes),
         n_speakers=n_speakers, gin_channels=gin_channels)
+
+
+# --------------------------------------------------------------------------- live conversion: host arithmetic
+# The pure-Python twins of vsp_convert_halo_frames / vsp_convert_frames / vsp_convert_window_plan
+# (include/vispeech_hip.h, "live conversion"): what a scheduler needs to know without a device.
+def convert_halo_frames(dims: ModelDims) -> int:
+    """H: ``z_hat[:, t]`` of a conversion depends on spectrogram columns ``[t - H, t + H]`` only.  Every WN layer of
+    enc_q, of the forward flow and of the reverse flow widens the dependence by ``(flow_kernel - 1) / 2`` a side
+    (reference models.py:212-241, 202-209; modules.py:148-176): 32 + 32 + 32 = 96 for the default configuration."""
+    side = (dims.flow_kernel - 1) // 2
+    return dims.posterior_layers * side + 2 * dims.n_flows * dims.flow_layers * side
+
+
+def convert_frames(n_samples: int, n_fft: int, hop: int) -> int:
+    """T(n) of ``vsp_convert_frames``: 0 where the reflect padding is undefined (n <= pad) or no window fits."""
+    pad = (n_fft - hop) // 2
+    if n_samples <= pad or n_samples + 2 * pad < n_fft:
+        return 0
+    return 1 + (n_samples + 2 * pad - n_fft) // hop
+
+
+def convert_window_plan(n_fft: int, hop: int, halo: int, n_known: int, closed: bool, e0: int, e1: int):
+    """``vsp_convert_window_plan``: ``(ready, w0, w1, s_lo, s_hi)`` of the window that delivers the frames ``[e0, e1)`` of a
+    recording of which ``n_known`` samples are there -- frames ``[w0, w1)``, which read the samples ``[s_lo, s_hi)`` after
+    reflection (at sample 0 always, at the end only when ``closed``); ``ready``: every one of them has arrived.
+    ``ValueError`` where the library returns VSP_ERR_ARG."""
+    if hop <= 0 or n_fft < hop or halo < 0 or n_known < 0 or e0 < 0 or e1 <= e0 or e1 > 2 ** 31 - 1 - halo:
+        raise ValueError("convert_window_plan: needs 0 < hop <= n_fft, halo >= 0, n_known >= 0 and 0 <= e0 < e1")
+    pad = (n_fft - hop) // 2
+    T = convert_frames(n_known, n_fft, hop)
+    if closed and e1 > T:
+        raise ValueError(f"convert_window_plan: frames [{e0}, {e1}) of a closed recording of {T} frames")
+    w0, w1 = max(0, e0 - halo), e1 + halo
+    if closed:
+        w1 = min(T, w1)
+    lo, hi = max(0, w0 * hop - pad), (w1 - 1) * hop - pad + n_fft
+    if closed and hi > n_known:
+        lo, hi = min(lo, 2 * (n_known - 1) - (hi - 1)), n_known
+    return (lo >= 0 and hi <= n_known), w0, w1, lo, hi

@@ -608,6 +608,59 @@ class _StreamRequest:
         self.history = None           # ``fused_output``: the request's Engine.output_history(), from admission on
 
 
+class LiveConversion(_RowStream):
+    """A live conversion of a ``StreamingBatchService`` (``open_conversion``): the caller feeds the recording while it is
+    being made and iterates over the converted PCM16 ``bytes`` -- exact chunks, what the finished recording converted
+    alone gives.  ``feed`` and ``end`` may be called from any thread; ``close()`` abandons the session."""
+
+    def __init__(self, cv: "threading.Condition"):
+        super().__init__()
+        self._cv = cv                 # the service's condition: guards _fed / _ended / _wake, wakes the worker
+        self._fed: list = []          # pieces the worker has not taken yet
+        self._ended = False
+        self._wake = True             # something changed since the worker last looked at this session
+
+    def feed(self, samples) -> None:
+        """The next samples of the recording: 1-D float32 at the model's rate, a piece of any size (copied)."""
+        a = np.array(samples, dtype=np.float32, copy=True)
+        if a.ndim != 1:
+            raise ValueError("samples must be a 1-D float32 array at the model's sampling rate")
+        with self._cv:
+            if self._ended:
+                raise RuntimeError("the recording has ended")
+            if a.size:
+                self._fed.append(a)
+                self._wake = True
+                self._cv.notify_all()
+
+    def end(self) -> None:
+        """The recording is complete: what remains is converted, reflected at its true end, and the iterator ends."""
+        with self._cv:
+            if not self._ended:
+                self._ended = self._wake = True
+                self._cv.notify_all()
+
+    def close(self) -> None:
+        super().close()
+        with self._cv:
+            self._wake = True
+            self._cv.notify_all()
+
+
+class _LiveRequest(_StreamRequest):
+    """The worker's side of a ``LiveConversion``.  ``n`` samples have reached the device, ``buf`` holds those from ``first``
+    on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
+    ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
+
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale: float):
+        super().__init__(None, seed)
+        self.stream = stream
+        self.sid_src, self.sid_tgt, self.noise_scale = int(sid_src), int(sid_tgt), float(noise_scale)
+        self.buf = None
+        self.first = self.n = self.done = self.e0 = 0
+        self.closed = False
+
+
 class StreamingBatchService:
     """Streaming AND batching (round 11): a set of active requests, each at its own position of its own utterance; every
     tick advances all of them by one chunk in ONE set of generator launches (``Engine.generator_stream_rows``), requests join
@@ -633,7 +686,16 @@ class StreamingBatchService:
     admitted groups.  No priorities, no retries, no backpressure.
     ``submit_conversion`` queues a recording to convert to another speaker: admission runs the group's conversions through
     one ``convert_latent`` and keeps each one's ``z_hat`` row, target speaker vector and ``L = T(n)``; from then on it is an
-    ordinary row of the tick, next to text rows (a group without a conversion makes the calls it always made)."""
+    ordinary row of the tick, next to text rows (a group without a conversion makes the calls it always made).
+    ``open_conversion`` opens a LIVE conversion: the recording is fed while it is made (``LiveConversion.feed`` / ``end``).
+    A session joins a tick when the samples its next chunk depends on have arrived -- the chunk, the vocoder's halo G and
+    the conversion's halo H (``schema.convert_halo_frames``) behind it: an algorithmic delay of
+    ``(G + H) * hop + n_fft - pad`` samples, about 1.3 s for the default configuration --; the tick then runs ONE
+    ``Engine.convert_stream_rows`` for the ready sessions and hands each one's window of ``z_hat`` to the tick's vocoder call
+    as one more row.  A session that is not ready sits the tick out; while only such sessions exist the worker sleeps.  The
+    bytes are those of the finished recording converted alone, with the frame-major noise of ``vsp_convert_stream_rows``
+    (not the layout ``submit_conversion`` draws).  A session keeps on the device the samples its next window reads and
+    those behind them, nothing older.  No backpressure and no reduced-lookahead mode."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
@@ -660,7 +722,8 @@ class StreamingBatchService:
         self.stats = {"ticks": 0, "rows_per_tick": [], "groups": 0}
         self._pending: "collections.deque" = collections.deque()
         self._active: list = []
-        self._cv = threading.Condition()     # guards _pending / _closed; the worker sleeps on it while there is no work
+        self._live: list = []                # open live conversions (_LiveRequest); guarded by _cv
+        self._cv = threading.Condition()     # guards _pending / _live / _closed; the worker sleeps on it while there is no work
         self._closed = False
         self._worker = None
         if autostart:
@@ -694,11 +757,39 @@ class StreamingBatchService:
             self._cv.notify()
         return req.stream
 
+    def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> LiveConversion:
+        """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
+        ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
+        ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``)."""
+        if self.fused_output:
+            # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
+            # filter's phase and its history must not see the shift
+            eng = self.net._engine
+            L, M, H = eng.output_plan
+            shift = self.net.dims.total_upsample * L
+            if shift % M or 2 * H + M > eng.generator_halo * shift:
+                raise ValueError("fused_output cannot carry a live conversion at this output rate (one frame is not a whole "
+                                 "number of output samples, or the filter is longer than the vocoder's halo): "
+                                 "use fused_output=False")
+        stream = LiveConversion(self._cv)
+        req = _LiveRequest(stream, sid_src, sid_tgt, int(noise_seed), 1.0 if noise_scale is None else float(noise_scale))
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            if len(self._live) + len(self._active) >= self.max_batch:      # (a tick has at most max_batch rows)
+                raise Busy(f"{self.max_batch} requests are active")
+            self._live.append(req)
+        return stream
+
     def close(self) -> None:
-        """Serve what is queued and active, then stop the worker and join it (without a worker: run the ticks here)."""
+        """Serve what is queued and active, then stop the worker and join it (without a worker: run the ticks here).  Live
+        conversions still open are ended: what they were fed is converted."""
         with self._cv:
             self._closed = True
+            live = list(self._live)
             self._cv.notify()
+        for r in live:
+            r.stream.end()
         if self._worker is not None:
             self._worker.join()
         else:
@@ -708,9 +799,10 @@ class StreamingBatchService:
     def _run(self) -> None:
         while True:
             with self._cv:
-                while not self._pending and not self._active and not self._closed:
+                # (live sessions that wait for samples are no work: feed / end / close set their _wake and notify)
+                while not self._pending and not self._active and not self._closed and not any(r.stream._wake for r in self._live):
                     self._cv.wait()
-                if self._closed and not self._pending and not self._active:
+                if self._closed and not self._pending and not self._active and not self._live:
                     return
             self.step()
 
@@ -719,24 +811,114 @@ class StreamingBatchService:
         """One tick (admit, generate, deliver, retire).  Returns whether requests are still queued or active."""
         self._admit()
         self._active = [r for r in self._active if not r.stream.closed]      # (closed by its caller: the row leaves here)
-        if self._active:
+        live = self._ready_live()
+        if self._active or live:
             try:
-                self._generate_and_deliver()
+                self._generate_and_deliver(self._active + live)
             except Exception as e:             # the tick's requests fail; the service lives on
-                for r in self._active:
+                for r in self._active + live:
                     r.stream._q.put(e)
                 self._active = []
+                self._drop_live(live)
+                live = []
         for r in self._active:
             if r.pos >= r.L:
                 r.stream._q.put(_RowStream._END)
         self._active = [r for r in self._active if r.pos < r.L]
+        for r in live:
+            self._after_live_tick(r)
         with self._cv:
-            return bool(self._pending or self._active)
+            return bool(self._pending or self._active or any(r.stream._wake for r in self._live))
+
+    # ------------------------------------------------------------------ live conversions
+    def _drop_live(self, reqs) -> None:
+        with self._cv:
+            self._live = [r for r in self._live if not any(r is x for x in reqs)]
+
+    def _ready_live(self) -> list:
+        """Takes what the live sessions were fed, and runs the conversion windows of those whose next chunk is ready: ONE
+        ``convert_stream_rows`` call.  Returns them as rows of this tick's vocoder call; a session that must wait, and one
+        that fails, is not among them."""
+        import torch
+        from . import schema
+        with self._cv:
+            if not self._live:
+                return []
+            taken = []
+            for r in self._live:
+                taken.append((r, r.stream._fed, r.stream._ended, r.stream.closed))
+                r.stream._fed, r.stream._wake = [], False
+        eng, dims = self.net._engine, self.net.dims
+        hop, n_fft = dims.hop_length, 2 * (dims.spec_channels - 1)
+        G, H = eng.generator_halo, schema.convert_halo_frames(dims)
+        device = getattr(eng, "device", "cpu")
+        ready, rows, gone = [], [], []
+        for r, pieces, ended, closed in taken:
+            if closed:                           # abandoned by its caller: the session leaves here
+                gone.append(r)
+                continue
+            if pieces:
+                new = torch.as_tensor(np.concatenate(pieces)).to(device)
+                r.buf = new if r.buf is None else torch.cat([r.buf, new])
+                r.n += int(new.numel())
+            r.closed = ended
+            n = self.first_chunk_frames if (r.done == 0 and self.first_chunk_frames is not None) else self.chunk_frames
+            f1 = r.done + n
+            if r.closed:
+                T = schema.convert_frames(r.n, n_fft, hop)
+                if r.done >= T:                  # (a recording too short for a frame: no bytes)
+                    r.stream._q.put(_RowStream._END)
+                    gone.append(r)
+                    continue
+                f1 = min(T, f1)
+            e0 = max(0, r.done - G)
+            e1 = min(f1 + G, T) if r.closed else f1 + G
+            if not schema.convert_window_plan(n_fft, hop, H, r.n, r.closed, e0, e1)[0]:
+                continue                         # the samples this chunk depends on have not arrived: sit the tick out
+            r.e0, r.L, r.pos = e0, e1 - e0, r.done - e0
+            ready.append(r)
+            rows.append((r.buf, r.first, r.n, r.closed, e0, e1, r.sid_src, r.sid_tgt, r.seed, r.noise_scale))
+        if ready:
+            try:
+                z, g = eng.convert_stream_rows(rows, self.chunk_frames + 2 * G)
+                for b, r in enumerate(ready):
+                    r.z, r.g = z[b], g[b]
+                    if self.fused_output and r.history is None:
+                        r.history = eng.output_history()
+            except Exception as e:               # these sessions fail; the tick's other rows and the service live on
+                for r in ready:
+                    r.stream._q.put(e)
+                gone += ready
+                ready = []
+        if gone:
+            self._drop_live(gone)
+        return ready
+
+    def _after_live_tick(self, r: "_LiveRequest") -> None:
+        """A live session after its tick: the end of the stream, or the samples its next window no longer reads dropped."""
+        from . import schema
+        dims = self.net.dims
+        hop, pad = dims.hop_length, (2 * (dims.spec_channels - 1) - dims.hop_length) // 2
+        finished = r.pos >= r.L                  # (the window ended at the recording's last frame, and so did the chunk)
+        r.done = r.e0 + r.pos
+        r.z = r.g = None
+        if finished:
+            r.stream._q.put(_RowStream._END)
+            self._drop_live([r])
+            return
+        # the next window starts at frame done - G - H; a reflection at the end, whenever it comes, reaches back pad samples
+        w0 = max(0, r.done - self.net._engine.generator_halo - schema.convert_halo_frames(dims))
+        keep = max(0, min(w0 * hop - pad, r.n - 1 - pad))
+        if keep > r.first:
+            r.buf = r.buf[keep - r.first:].clone()
+            r.first = keep
+        with self._cv:
+            r.stream._wake = True                # (it may be ready again at once: the next step looks)
 
     def _admit(self) -> None:
         group = []
         with self._cv:
-            while self._pending and len(self._active) + len(group) < self.max_batch:
+            while self._pending and len(self._active) + len(self._live) + len(group) < self.max_batch:
                 req = self._pending.popleft()
                 if req.stream.closed:
                     req.stream._q.put(_RowStream._END)
@@ -768,11 +950,11 @@ class StreamingBatchService:
             for r in group:
                 r.stream._q.put(e)
 
-    def _generate_and_deliver(self) -> None:
+    def _generate_and_deliver(self, reqs) -> None:
         eng = self.net._engine
         hop = self.net.dims.total_upsample
         rows, counts = [], []
-        for r in self._active:
+        for r in reqs:
             n = self.first_chunk_frames if (r.pos == 0 and self.first_chunk_frames is not None) else self.chunk_frames
             f1 = min(r.L, r.pos + n)
             rows.append((r.z, r.g, r.L, r.pos, f1))
@@ -780,11 +962,11 @@ class StreamingBatchService:
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
         if self.fused_output:
-            out, done = eng.generator_stream_rows_output([row + (r.history,) for row, r in zip(rows, self._active)],
+            out, done = eng.generator_stream_rows_output([row + (r.history,) for row, r in zip(rows, reqs)],
                                                          self.chunk_frames, pcm=True)
             block = _host_i16_2d(out)                                        # the tick's one device-to-host copy
             self._check_numerics()
-            for b, (r, n) in enumerate(zip(self._active, counts)):
+            for b, (r, n) in enumerate(zip(reqs, counts)):
                 r.pos += n
                 if done[b]:
                     r.stream._q.put(block[b, : done[b]].tobytes())
@@ -793,11 +975,11 @@ class StreamingBatchService:
         if self.output_rate is None:
             block = _host_i16_2d(out)                                        # the tick's one device-to-host copy
             self._check_numerics()
-            for b, (r, n) in enumerate(zip(self._active, counts)):
+            for b, (r, n) in enumerate(zip(reqs, counts)):
                 r.pos += n
                 r.stream._q.put(block[b, : n * hop].tobytes())
             return
-        for b, (r, n) in enumerate(zip(self._active, counts)):
+        for b, (r, n) in enumerate(zip(reqs, counts)):
             r.pos += n
             piece = self._through_output_stage(r, out[b:b + 1, : n * hop])
             self._check_numerics()
