@@ -193,6 +193,44 @@ class _FakeNet:
         return (self.wave, x_mask, None, None, None, None)
 
 
+@pytest.mark.parametrize("rate", ref.RATES + (IN_RATE,))
+def test_pushed_stream_equals_one_shot(rate):
+    """``output_stage.Stream``, window by window, against ``one_shot``: the same numbers, a result for exactly the windows
+    that complete an output sample, and the ``output_chunk`` calls of ``stream()`` over the same windows."""
+    eng = _FakeEngine(None, None)
+    eng.configure_output(rate, in_rate=IN_RATE)
+    L, M, H = eng.output_plan
+    x = np.tanh(0.5 * np.random.default_rng(rate).standard_normal((1, 3001))).astype(np.float32)
+    sizes, windows, at = (64, 1, 512, 3, 7, 2), [], 0               # 1, 2, 3, 7, 64 and 512 samples, shuffled once
+    while at < x.shape[1]:
+        windows.append(x[:, at:at + sizes[len(windows) % len(sizes)]])
+        at += windows[-1].shape[1]
+    s = output_stage.Stream(eng, None, pcm=False)
+    got, seen, m_next, silent = [], 0, 0, 0
+    for w in windows:
+        seen += w.shape[1]
+        m_done = output_stage.complete_outputs(seen, L, M, H)
+        y = s.push(w)
+        assert (y is None) == (m_done == m_next), (seen, m_done, m_next)
+        if y is not None:
+            assert y.shape == (1, m_done - m_next)
+            got.append(y)
+        silent += y is None
+        m_next = m_done
+    assert silent > 0 or L >= M                                      # when decimating, the first 64 samples complete nothing
+    tail = s.finish()
+    assert (tail is None) == (m_next == output_stage.out_len(seen, L, M))
+    got += [] if tail is None else [tail]
+    pushed_calls = list(eng.calls)
+    eng.calls.clear()
+    np.testing.assert_array_equal(np.concatenate(got, axis=1), output_stage.one_shot(eng, x, None, False))
+    eng.calls.clear()
+    pulled = list(output_stage.stream(eng, iter(windows), None, False))
+    assert eng.calls == pushed_calls and len(pulled) == len(got)
+    for a, b in zip(pulled, got):
+        np.testing.assert_array_equal(a, b)
+
+
 BATCH = dict(phonemes=np.zeros((2, 3), np.int64), lengths=np.array([3, 3]), sid=np.array([0, 1]))
 
 

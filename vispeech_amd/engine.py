@@ -238,6 +238,31 @@ class Engine:
             raise ValueError(f"noise_seed must have {B} entries, got {len(seeds)}")
         return 0, seeds
 
+    def _noise_args(self, row_controls, isolated: bool, B: int, noise, noise_scale, noise_seed):
+        """What ``decode`` and ``infer_padded`` check before anything else: the table against the batch, the seed rules, and
+        that noise the library draws has a named seed.  Returns (noise_scale, scalar seed, per-utterance seeds or None)."""
+        noise_scale = self._check_row_controls(row_controls, isolated, B, noise_scale)
+        noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
+        if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
+            raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
+        return noise_scale, 0 if noise_seed is None else noise_seed, seeds
+
+    def _set_call_state(self, isolated: bool, seeds, row_controls, noise_offset: int) -> None:
+        """The sticky context state ``vsp_decode`` / ``vsp_infer`` read, set from the call's own arguments."""
+        self.set_isolated(isolated)
+        if isolated:
+            self.set_noise_seeds(seeds)
+        self.set_row_controls(row_controls)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
+
+    def _hop(self, hop_length: Optional[int]) -> int:
+        return int(self.dims.hop_length if hop_length is None else hop_length)
+
+    def _need_output(self) -> None:
+        if self.output_plan is None:
+            raise RuntimeError("configure_output() first")
+
     # ------------------------------------------------------------------ the path
     def encode(self, phonemes, lengths, sid, duration_ctl=None, pitch_ctl=None, energy_ctl=None,
                duration_scale=1.0, pitch_scale=1.0, energy_scale=1.0, isolated: bool = False,
@@ -333,11 +358,7 @@ class Engine:
         key per utterance (``vsp_set_noise_seeds``), and ``noise_offset`` is not read.
         ``row_controls`` (``set_row_controls``; needs ``isolated``): row b's own ``noise_scale``; the argument is not read."""
         B, _, Tp = enc["x_var"].shape
-        noise_scale = self._check_row_controls(row_controls, isolated, B, noise_scale)
-        noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
-        if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
-            raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
-        noise_seed = 0 if noise_seed is None else noise_seed
+        noise_scale, noise_seed, seeds = self._noise_args(row_controls, isolated, B, noise, noise_scale, noise_seed)
         d = self.dims
         inter = d.inter_channels
         if bufs is None or bufs["Tf"] != int(Tf) or bufs["max_len"] != max_len:
@@ -347,12 +368,8 @@ class Engine:
             noise = _dev_f32(noise, self.device)
             if tuple(noise.shape) != (B, inter, Tf):
                 raise ValueError(f"noise must be [{B},{inter},{Tf}], got {tuple(noise.shape)}")
-        self.set_isolated(isolated)
-        if isolated:
-            self.set_noise_seeds(seeds)
-        self.set_row_controls(row_controls)
+        self._set_call_state(isolated, seeds, row_controls, noise_offset)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_decode(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,
                                      _ptr(enc["x_var"]), _ptr(enc["g"]), _ptr(enc["cum_dur"]),
                                      _ptr(enc["frame_lengths"]), _ptr(noise), int(noise_seed) & (2**64 - 1),
@@ -374,11 +391,7 @@ class Engine:
         and ``row_controls``, which replaces the four scalar scales)."""
         ph = _dev_i64(phonemes, self.device)
         B, Tp = ph.shape
-        noise_scale = self._check_row_controls(row_controls, isolated, B, noise_scale)
-        noise_seed, seeds = self._isolated_seeds(isolated, noise, noise_scale, noise_seed, B)
-        if noise is None and float(noise_scale) != 0.0 and noise_seed is None:
-            raise ValueError("pass noise or an explicit noise_seed (noise_scale != 0)")
-        noise_seed = 0 if noise_seed is None else noise_seed
+        noise_scale, noise_seed, seeds = self._noise_args(row_controls, isolated, B, noise, noise_scale, noise_seed)
         ln, sd = _dev_i64(lengths, self.device), _dev_i64(sid, self.device)
         ctl = [None if t is None else _dev_f32(t, self.device).reshape(B, Tp) for t in (duration_ctl, pitch_ctl, energy_ctl)]
         Tf = int(tf_pad)
@@ -396,12 +409,8 @@ class Engine:
         dur, f0, en = (self._f(B, Tp) for _ in range(3))
         fl = torch.empty(B, dtype=torch.int64, device=self.device)
         ws = self._workspace("infer", self.lib.vsp_infer_workspace_bytes(self.ctx, B, Tp, Tf))
-        self.set_isolated(isolated)
-        if isolated:
-            self.set_noise_seeds(seeds)
-        self.set_row_controls(row_controls)
+        self._set_call_state(isolated, seeds, row_controls, noise_offset)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.vsp_set_noise_offset(self.ctx, int(noise_offset)), self.ctx, "vsp_set_noise_offset")
             rc = self.lib.vsp_infer(self.ctx, self._stream(), B, Tp, Tf, -1 if max_len is None else Tdec,
                                     _ptr(ph), _ptr(ln), _ptr(sd), _ptr(ctl[0]), _ptr(ctl[1]), _ptr(ctl[2]),
                                     float(duration_scale), float(pitch_scale), float(energy_scale), _ptr(nz),
@@ -510,7 +519,7 @@ class Engine:
         a = _dev_f32(audio, self.device)
         if a.dim() != 2:
             raise ValueError("audio must be [B, L]")
-        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        hop = self._hop(hop_length)
         B, L = a.shape
         T = int(self.lib.vsp_spectrogram_frames(self.ctx, L, hop))
         if T <= 0:
@@ -584,7 +593,7 @@ class Engine:
     # ------------------------------------------------------------------ conversion from audio (ragged front end)
     def convert_frames(self, n_samples: int, hop_length: Optional[int] = None) -> int:
         """``vsp_convert_frames``: frames of a recording of ``n_samples`` samples (0: too short for a frame).  Host only."""
-        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        hop = self._hop(hop_length)
         T = int(self.lib.vsp_convert_frames(self.ctx, int(n_samples), hop))
         if T < 0:
             _lib.check(T, self.ctx, "vsp_convert_frames")
@@ -602,7 +611,7 @@ class Engine:
             raise ValueError(f"n_samples must have {B} entries")
         if any(x < 0 or x > stride for x in n_host):
             raise ValueError("0 <= n_samples[b] <= audio.shape[1]")
-        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        hop = self._hop(hop_length)
         frames = [self.convert_frames(x, hop) for x in n_host]
         L_max = max(n_host)
         T = max(frames)
@@ -679,7 +688,7 @@ class Engine:
     def convert_window_plan(self, n_known: int, closed: bool, e0: int, e1: int, hop_length: Optional[int] = None):
         """``vsp_convert_window_plan`` (host only) with this model's geometry and halo: ``(ready, w0, w1, s_lo, s_hi)`` of the
         window that delivers frames ``[e0, e1)`` (``vispeech_amd.schema.convert_window_plan`` is its pure-Python twin)."""
-        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        hop = self._hop(hop_length)
         w0, w1, lo, hi = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
         rc = int(self.lib.vsp_convert_window_plan(2 * (self.dims.spec_channels - 1), hop, self.convert_halo, int(n_known),
                                                   int(bool(closed)), int(e0), int(e1), C.byref(w0), C.byref(w1), C.byref(lo),
@@ -701,7 +710,7 @@ class Engine:
         B = len(rows)
         if not 1 <= B <= _lib.STREAM_ROWS_MAX:
             raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
-        hop = int(self.dims.hop_length if hop_length is None else hop_length)
+        hop = self._hop(hop_length)
         span_frames = int(span_frames)
         arr = (_lib.VspConvertRow * B)()
         keep = []
@@ -791,13 +800,19 @@ class Engine:
             _lib.check(rc, self.ctx, "vsp_generator_stream_chunk")
             yield o
 
+    @staticmethod
+    def _plan_rows(rows):
+        """(L, f0, f1) triples as a ``VspStreamRow`` array (one unused element where there are no rows)."""
+        arr = (_lib.VspStreamRow * max(len(rows), 1))()
+        for r, (L, f0, f1) in zip(arr, rows):
+            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        return arr
+
     def stream_rows_plan(self, rows):
         """``vsp_stream_rows_plan`` (host only): ([lo], [hi], span_max) of rows given as (L, f0, f1) triples -- the window
         ``[max(0, f0 - halo), min(L, f1 + halo))`` each row's chunk is computed from."""
         rows = list(rows)
-        arr = (_lib.VspStreamRow * max(len(rows), 1))()
-        for r, (L, f0, f1) in zip(arr, rows):
-            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        arr = self._plan_rows(rows)
         lo, hi = (C.c_int32 * max(len(rows), 1))(), (C.c_int32 * max(len(rows), 1))()
         span = C.c_int32()
         _lib.check(self.lib.vsp_stream_rows_plan(self.ctx, len(rows), arr, lo, hi, C.byref(span)), None, "vsp_stream_rows_plan")
@@ -814,12 +829,7 @@ class Engine:
         if not 1 <= B <= _lib.STREAM_ROWS_MAX:
             raise ValueError(f"1 .. {_lib.STREAM_ROWS_MAX} rows per call, got {B}")
         arr = (_lib.VspStreamRow * B)()
-        keep = []
-        for r, (z, g, L, f0, f1) in zip(arr, rows):
-            z, g, stride = self._stream_row_args(z, g, L)
-            keep.append((z, g))
-            r.z, r.z_channel_stride, r.g = z.data_ptr(), stride, g.data_ptr()
-            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        keep = [self._fill_stream_row(r, *row) for r, row in zip(arr, rows)]
         chunk_frames = int(chunk_frames)
         out = torch.empty((B, max(chunk_frames, 0) * up), dtype=torch.int16 if pcm else torch.float32, device=self.device)
         ws = self._workspace("generator_stream_rows",
@@ -830,8 +840,8 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_generator_stream_rows")
         return out
 
-    def _stream_row_args(self, z, g, L):
-        """Checks one row's latent and speaker vector; returns (z, g) to keep alive and the row's channel stride."""
+    def _fill_stream_row(self, r, z, g, L, f0, f1):
+        """Checks one row's latent and speaker vector and fills the ``VspStreamRow`` ``r``; returns (z, g) to keep alive."""
         d = self.dims
         if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.device != self.device or z.dim() != 2
                 or z.shape[0] != d.inter_channels or z.shape[1] < int(L) or (z.shape[1] > 1 and z.stride(1) != 1)):
@@ -840,20 +850,18 @@ class Engine:
         g = _dev_f32(g, self.device).reshape(-1)
         if g.numel() != d.gin_channels:
             raise ValueError(f"a row's g must have {d.gin_channels} entries")
-        return z, g, max(int(z.stride(0)), int(L))
+        r.z, r.z_channel_stride, r.g = z.data_ptr(), max(int(z.stride(0)), int(L)), g.data_ptr()
+        r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
+        return z, g
 
     def stream_rows_output_plan(self, rows):
         """``vsp_stream_rows_output_plan`` (host only) for the configured output stage: ([m0], [m1], [k0], [k1]) of rows
         given as (L, f0, f1) triples -- the tick delivers output samples [m0, m1), reads the history from input sample k0
         and leaves the history from k1 (``vispeech_amd.output_stage.complete_outputs`` / ``history_start``)."""
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         rows = list(rows)
-        n = max(len(rows), 1)
-        arr = (_lib.VspStreamRow * n)()
-        for r, (L, f0, f1) in zip(arr, rows):
-            r.L, r.f0, r.f1 = int(L), int(f0), int(f1)
-        res = [(C.c_int64 * n)() for _ in range(4)]
+        arr = self._plan_rows(rows)
+        res = [(C.c_int64 * len(arr))() for _ in range(4)]
         Lo, Mo, Ho = self.output_plan
         _lib.check(self.lib.vsp_stream_rows_output_plan(Lo, Mo, Ho, self.dims.total_upsample, len(rows), arr, *res), None,
                    "vsp_stream_rows_output_plan")
@@ -861,15 +869,13 @@ class Engine:
 
     def output_history(self) -> "OutputHistory":
         """The state one streamed request carries through ``generator_stream_rows_output``."""
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         return OutputHistory(int(self.lib.vsp_output_history_samples(*self.output_plan)), self.device)
 
     def stream_rows_out_samples(self, chunk_frames: int) -> int:
         """``vsp_stream_rows_out_samples``: the row length of ``generator_stream_rows_output`` for chunks of up to
         ``chunk_frames`` frames."""
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         n = int(self.lib.vsp_stream_rows_out_samples(*self.output_plan, self.dims.total_upsample, int(chunk_frames)))
         if n < 0:
             _lib.check(n, None, "vsp_stream_rows_out_samples")
@@ -889,11 +895,8 @@ class Engine:
         m0, m1, _, _ = self.stream_rows_output_plan([(L, f0, f1) for _, _, L, f0, f1, _ in rows])
         arr = (_lib.VspStreamRowOut * B)()
         keep = []
-        for r, (z, g, L, f0, f1, state) in zip(arr, rows):
-            z, g, stride = self._stream_row_args(z, g, L)
-            keep.append((z, g))
-            r.row.z, r.row.z_channel_stride, r.row.g = z.data_ptr(), stride, g.data_ptr()
-            r.row.L, r.row.f0, r.row.f1 = int(L), int(f0), int(f1)
+        for r, (*row, state) in zip(arr, rows):
+            keep.append(self._fill_stream_row(r.row, *row))
             r.hist_in, r.hist_out = state.pointers()
         out = torch.empty((B, self.stream_rows_out_samples(chunk_frames)), dtype=torch.int16 if pcm else torch.float32,
                           device=self.device)
@@ -931,8 +934,7 @@ class Engine:
         """``vsp_output_chunk``: output samples [m0, m1) of every utterance from the window ``x`` [B, n] (float32 on the
         device, rows may be strided), which holds input samples [x_first, x_first + n).  ``n_valid``: None or the
         utterances' total valid lengths (int64 on the device).  Returns [B, m1 - m0], int16 if ``pcm`` else float32."""
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
             raise ValueError("x must be a float32 [B, n] tensor on the engine's device with contiguous rows")
         B, n = x.shape
@@ -954,8 +956,7 @@ class Engine:
         the valid samples per utterance (None: all n) -> (tensor [B, ceil(n L / M)], out_lengths).  What ``o`` holds
         behind an utterance's valid length is never read; the output behind ``out_lengths[b]`` is 0."""
         from . import output_stage
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         x = o.reshape(o.shape[0], -1) if o.dim() == 3 else o
         L, M, _ = self.output_plan
         nv = None if sample_lengths is None else _dev_i64(sample_lengths, self.device).clamp(0, x.shape[1])
@@ -970,8 +971,7 @@ class Engine:
         each chunk completes ([B, m] tensors) and flushes the tail when the chunks end.  The concatenation equals
         ``output`` of the concatenated waveform bit for bit (``vispeech_amd.output_stage.stream``)."""
         from . import output_stage
-        if self.output_plan is None:
-            raise RuntimeError("configure_output() first")
+        self._need_output()
         nv = None if n_valid is None else _dev_i64(n_valid, self.device)
         return output_stage.stream(self, chunks, nv, pcm)
 

@@ -78,24 +78,44 @@ def one_shot(eng, x, n_valid=None, pcm: bool = True):
     return eng.output_chunk(x, 0, n, 0, out_len(n, L, M), n_valid, pcm)
 
 
-def stream(eng, chunks: Iterable, n_valid=None, pcm: bool = True) -> Iterator:
-    """Consumes consecutive windows [B, n_i] of the input and yields, per window, the output samples it completes
-    ([B, m_i], possibly nothing for a short window), then the tail once the input has ended.  Between windows only the
-    input samples that incomplete outputs still need are kept (about 2 H / L of them, on the device for device chunks).
-    The concatenation equals ``one_shot`` of the concatenated input exactly: the same samples go through the same
+class Stream:
+    """The streamed output stage, one window at a time: ``push`` takes the next window [B, n_i] of the input and returns
+    the output samples it completes ([B, m_i]; None for a window too short to complete one), ``finish`` returns the tail
+    once the input has ended (or None).  Between windows only the input samples that incomplete outputs still need are
+    kept (``hist``, which starts at input sample ``first``: about 2 H / L of them, on the device for device windows).  The
+    concatenation equals ``one_shot`` of the concatenated input exactly: the same samples go through the same
     ``output_chunk`` arithmetic, whose result depends on (x, m) alone."""
-    L, M, H = eng.output_plan
-    hist, first, seen, m_next = None, 0, 0, 0
-    for c in chunks:
-        x = c.reshape(c.shape[0], -1)
-        win = x if hist is None or hist.shape[1] == 0 else _cat(hist, x)
-        seen += int(x.shape[1])
-        m_done = complete_outputs(seen, L, M, H)
-        if m_done > m_next:
-            yield eng.output_chunk(win, first, seen, m_next, m_done, n_valid, pcm)
-            m_next = m_done
-        k = min(seen, history_start(m_next, L, M, H))
-        hist, first = win[:, k - first:], k
-    m_end = out_len(seen, L, M)
-    if hist is not None and m_end > m_next:
-        yield eng.output_chunk(hist, first, seen, m_next, m_end, n_valid, pcm)
+
+    def __init__(self, eng, n_valid=None, pcm: bool = True):
+        self.eng, self.n_valid, self.pcm = eng, n_valid, pcm
+        self.plan = eng.output_plan
+        self.hist, self.first, self.seen, self.m_next = None, 0, 0, 0
+
+    def push(self, window):
+        x = window.reshape(window.shape[0], -1)
+        win = x if self.hist is None or self.hist.shape[1] == 0 else _cat(self.hist, x)
+        self.seen += int(x.shape[1])
+        m_done = complete_outputs(self.seen, *self.plan)
+        y = None
+        if m_done > self.m_next:
+            y = self.eng.output_chunk(win, self.first, self.seen, self.m_next, m_done, self.n_valid, self.pcm)
+            self.m_next = m_done
+        k = min(self.seen, history_start(self.m_next, *self.plan))
+        self.hist, self.first = win[:, k - self.first:], k
+        return y
+
+    def finish(self):
+        m_end = out_len(self.seen, *self.plan[:2])
+        if self.hist is None or m_end <= self.m_next:
+            return None
+        return self.eng.output_chunk(self.hist, self.first, self.seen, self.m_next, m_end, self.n_valid, self.pcm)
+
+
+def stream(eng, chunks: Iterable, n_valid=None, pcm: bool = True) -> Iterator:
+    """``Stream`` over consecutive windows: yields, per window that completes output samples, those samples, then the
+    tail once the windows have ended."""
+    s = Stream(eng, n_valid, pcm)
+    yield from (y for y in map(s.push, chunks) if y is not None)
+    tail = s.finish()
+    if tail is not None:
+        yield tail

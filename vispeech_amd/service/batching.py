@@ -1,0 +1,265 @@
+"""Requests from many callers in one batch: the request the batching services queue, the one way from a group of requests
+to their latents, and ``BatchingSynthesisService``."""
+from __future__ import annotations
+
+import concurrent.futures
+import queue
+import threading
+import time
+from typing import Optional
+
+import numpy as np
+
+from ._pcm import _row_pcm16
+
+
+class _Conversion:
+    """A conversion request of the batching services (``submit_conversion``): a recording at the model's rate, the speaker
+    it was spoken by and the speaker to convert it to.  To the vocoder it is a row like any other -- a latent, a speaker
+    vector and a length -- so it shares generator calls and ticks with text requests."""
+
+    def __init__(self, audio, sid_src: int, sid_tgt: int, noise_scale):
+        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
+        if a.ndim != 1:
+            raise ValueError("audio must be a 1-D float32 array at the model's sampling rate")
+        self.audio, self.sid_src, self.sid_tgt = a, int(sid_src), int(sid_tgt)
+        self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)      # (1.0: the reference's posterior)
+
+
+class _Request:
+    """One request of the batching services: ``row`` is a row as ``collate_rows`` takes it or a ``_Conversion``, ``seed``
+    keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
+    ``noise_scale``; a conversion's noise scale is its row's."""
+
+    def __init__(self, row, seed: int, scales=(None, None, None, None)):
+        self.row, self.seed, self.scales = row, int(seed), scales
+
+    @property
+    def is_conversion(self) -> bool:
+        return isinstance(self.row, _Conversion)
+
+
+def _collate_from(table, spk2id, collate):
+    """The rows -> batch arrays callable of a batching service: ``collate``, or ``collate_rows`` with ``table`` / ``spk2id``."""
+    if collate is not None:
+        return collate
+    if table is None or spk2id is None:
+        raise ValueError("pass table and spk2id (for collate_rows) or a collate callable")
+    from ..text import collate_rows
+    return lambda rows: collate_rows(rows, table, spk2id)
+
+
+def _row_table(batch, scales, noise_scale: float):
+    """The per-row table of a batch of requests (``models.RowControls``), or None where the batch needs none: no request
+    named a scale and every row carries all three controls -- then the services make the calls they always made.
+    ``scales``: per request ``(duration_scale, pitch_scale, energy_scale, noise_scale)``, None = 1.0 and the service's
+    ``noise_scale``.  ``given`` is ``collate_rows``' array; a collate callable that returns none gives every row the
+    controls its batch has."""
+    B = len(scales)
+    given = batch.get("given")
+    if all(v is None for sc in scales for v in sc) and (given is None or bool(np.all(given))):
+        return None
+    if given is None:
+        given = np.tile(np.array([[batch.get(k) is not None for k in ("duration", "f0", "energy")]], dtype=bool), (B, 1))
+    from ..models import RowControls
+    col = lambda i, default: np.array([default if sc[i] is None else float(sc[i]) for sc in scales], dtype=np.float32)
+    return RowControls(col(0, 1.0), col(1, 1.0), col(2, 1.0), col(3, noise_scale), np.asarray(given, dtype=bool))
+
+
+def _table_controls(batch, rows_ctl):
+    """duration / f0 / energy of a batch that runs with a table: a control no row is given is not passed."""
+    return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
+
+
+def _collated(collate, reqs, noise_scale: float):
+    """``(batch, (duration, f0, energy), keywords)`` of text requests: ``collate`` and, where the requests need one, the
+    per-row table -- the ``row_controls`` keyword is passed only then: a group without one makes the calls it always made."""
+    batch = collate([r.row for r in reqs])
+    table = _row_table(batch, [r.scales for r in reqs], noise_scale)
+    if table is None:
+        return batch, (batch.get("duration"), batch.get("f0"), batch.get("energy")), {}
+    return batch, _table_controls(batch, table), {"row_controls": table}
+
+
+def _text_latents(eng, collate, reqs, noise_scale: float):
+    """The text requests of one batch or admitted group to their latent: ``collate``, the per-row table where the requests
+    need one, then ONE isolated ``encode`` / ``frame_lengths_host`` / ``decode(max_len=0)``.  Returns per request
+    ``(z row [inter, T], g row, frames)``; a request of no frames gives ``(None, None, 0)``."""
+    import torch
+    batch, ctl, kw = _collated(collate, reqs, noise_scale)
+    t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
+    enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
+                     isolated=True, **kw)
+    frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
+    z = None
+    if tf > 0:
+        z = eng.decode(enc, tf, None, noise_scale, max_len=0, noise_seed=[r.seed for r in reqs], isolated=True, **kw)["z"]
+    return [(z[b], enc["g"][b], int(frames[b])) if int(frames[b]) > 0 else (None, None, 0) for b in range(len(reqs))]
+
+
+def _convert_latents(eng, reqs):
+    """The conversion requests of one batch or admitted group through ``Engine.convert_latent``: ONE call (one per
+    distinct ``noise_scale``, which is an argument of the call, where the requests name several).  Returns per request
+    ``(z_hat row, g row, frames)``; a recording too short for a frame gives ``(None, None, 0)``.  The frame counts are
+    host arithmetic (``frames_host``): nothing is read back from the device."""
+    jobs = [r.row for r in reqs]
+    out = [(None, None, 0)] * len(jobs)
+    for scale in sorted({j.noise_scale for j in jobs}):
+        idx = [i for i, j in enumerate(jobs) if j.noise_scale == scale and eng.convert_frames(j.audio.size) > 0]
+        if not idx:
+            continue
+        n = [jobs[i].audio.size for i in idx]
+        audio = np.zeros((len(idx), max(n)), dtype=np.float32)
+        for k, i in enumerate(idx):
+            audio[k, : n[k]] = jobs[i].audio
+        r = eng.convert_latent(audio, n, [jobs[i].sid_src for i in idx], [jobs[i].sid_tgt for i in idx], None,
+                               noise_seed=[reqs[i].seed for i in idx], noise_scale=scale)
+        for k, i in enumerate(idx):
+            out[i] = (r["z_hat"][k], r["g"][k], int(r["frames_host"][k]))
+    return out
+
+
+def latents(eng, collate, requests, noise_scale: float):
+    """Per request ``(z row [inter, T], g row, frames)``, in request order: the text rows of the group through
+    ``_text_latents``, then its conversions through ``_convert_latents``."""
+    text = [i for i, r in enumerate(requests) if not r.is_conversion]
+    conv = [i for i, r in enumerate(requests) if r.is_conversion]
+    done = []
+    if text:
+        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale))
+    if conv:
+        done += zip(conv, _convert_latents(eng, [requests[i] for i in conv]))
+    out = [None] * len(requests)
+    for i, lat in done:
+        out[i] = lat
+    return out
+
+
+class BatchingSynthesisService:
+    """Requests from many callers, synthesised together (round 10).  The single-flight services refuse a request while
+    another is in flight, because in the reference's padded batch an utterance's audio depends on its batch-mates; in ISOLATED mode it
+    does not, so requests can share a batch: ``submit`` queues one ``collate_rows`` row with its own noise seed and
+    returns a future of its PCM16; one worker thread collects up to ``max_batch`` requests -- waiting at most
+    ``max_wait_s`` after the first -- collates them and runs ONE ``net.infer(..., isolated=True)`` with the requests' seeds.
+    A failing batch fails its own futures and nothing else.  No retry, no priority.
+    A request may leave any of durations / f0 / energy to the predictors (``text.request_row``) and name its own
+    ``duration_scale`` / ``pitch_scale`` / ``energy_scale`` / ``noise_scale``: such a batch runs with the per-row table built
+    from its requests (``infer(row_controls=...)``), and each request is still what the reference returns for it alone.
+    ``submit_conversion`` queues a recording to convert from one speaker to another (``SynthesizerTrn.convert_audio``); a
+    collected batch may hold both kinds: the text rows go to their latent (``encode`` / ``frame_lengths_host`` /
+    ``decode(max_len=0)``), the conversions through one ``convert_latent``, and ONE ``generator_ragged`` call produces every
+    waveform.  A batch without a conversion makes exactly the ``net.infer`` call above.
+    ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays)."""
+
+    def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
+                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100):
+        if max_batch < 1 or max_wait_s < 0:
+            raise ValueError("max_batch >= 1 and max_wait_s >= 0")
+        self._collate = _collate_from(table, spk2id, collate)
+        self.net, self.max_batch, self.max_wait_s = net, int(max_batch), float(max_wait_s)
+        self.noise_scale = float(noise_scale)
+        self.output_rate = None if output_rate is None else int(output_rate)
+        if self.output_rate is not None:
+            net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
+        self._q: "queue.Queue" = queue.Queue()
+        self._closed = False
+        self._gate = threading.Lock()        # orders _enqueue's check + put against close's sentinel: nothing queues behind it
+        self._worker = threading.Thread(target=self._run, name="vispeech-batching", daemon=True)
+        self._worker.start()
+
+    def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
+               noise_scale=None) -> "concurrent.futures.Future":
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
+        request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
+        The future's result is the request's PCM16 samples (numpy int16, valid part only)."""
+        return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
+
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *,
+                          noise_scale=None) -> "concurrent.futures.Future":
+        """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
+        PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
+        ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
+        ``noise_scale``); ``noise_seed`` keys that noise."""
+        return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale), noise_seed))
+
+    def _enqueue(self, req: _Request) -> "concurrent.futures.Future":
+        req.future = concurrent.futures.Future()
+        with self._gate:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            self._q.put(req)
+        return req.future
+
+    def close(self) -> None:
+        """Serve what is queued, then stop the worker and join it."""
+        with self._gate:
+            if not self._closed:
+                self._closed = True
+                self._q.put(None)
+        self._worker.join()
+
+    def _run(self) -> None:
+        stop = False
+        while not stop:
+            first = self._q.get()
+            if first is None:
+                break
+            reqs, deadline = [first], time.monotonic() + self.max_wait_s
+            while len(reqs) < self.max_batch:
+                try:
+                    nxt = self._q.get(timeout=max(deadline - time.monotonic(), 0.0))
+                except queue.Empty:
+                    break
+                if nxt is None:
+                    stop = True
+                    break
+                reqs.append(nxt)
+            reqs = [r for r in reqs if r.future.set_running_or_notify_cancel()]
+            if not reqs:
+                continue
+            try:
+                for r, pcm in zip(reqs, self._synthesize(reqs)):
+                    r.future.set_result(pcm)
+            except Exception as e:           # this batch's requests fail; the worker lives on
+                for r in reqs:
+                    if not r.future.done():
+                        r.future.set_exception(e)
+
+    def _pcm16(self, x) -> np.ndarray:
+        return _row_pcm16(x, None if self.output_rate is None else self.net._engine)
+
+    def _synthesize(self, reqs):
+        import torch
+        net = self.net
+        if any(r.is_conversion for r in reqs):
+            return self._synthesize_mixed(reqs)
+        batch, ctl, kw = _collated(self._collate, reqs, self.noise_scale)
+        t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
+        o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
+                                  duration_control=t(ctl[0]), pitch_control=t(ctl[1]),
+                                  energy_control=t(ctl[2]), noise_seed=[r.seed for r in reqs], isolated=True, **kw)
+        frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
+        hop = net.dims.total_upsample
+        return [self._pcm16(o[b:b + 1, 0, : int(frames[b]) * hop]) for b in range(len(reqs))]
+
+    def _synthesize_mixed(self, reqs):
+        """A batch with conversions: every request's latent, speaker vector and length packed into one ragged batch, ONE
+        ``generator_ragged`` call, then the output stage as in ``_synthesize``."""
+        import torch
+        net, eng = self.net, self.net._engine
+        lat = latents(eng, self._collate, reqs, self.noise_scale)
+        live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
+        pcms = [np.zeros(0, dtype="<i2") for _ in reqs]
+        if not live:
+            return pcms
+        T = max(lat[i][2] for i in live)
+        z0 = torch.as_tensor(lat[live[0]][0])
+        Z = torch.zeros((len(live), z0.shape[0], T), dtype=torch.float32, device=z0.device)
+        for b, i in enumerate(live):
+            Z[b, :, : lat[i][2]] = torch.as_tensor(lat[i][0])[:, : lat[i][2]]
+        G = torch.stack([torch.as_tensor(lat[i][1]).reshape(-1) for i in live])
+        o = eng.generator_ragged(Z, G, [lat[i][2] for i in live])
+        hop = net.dims.total_upsample
+        for b, i in enumerate(live):
+            pcms[i] = self._pcm16(o[b:b + 1, 0, : lat[i][2] * hop])
+        return pcms

@@ -1,0 +1,438 @@
+"""Streaming and batching at once: ``StreamingBatchService``, its callers' iterators (``_RowStream``, ``LiveConversion``)
+and the worker's side of a request."""
+from __future__ import annotations
+
+import collections
+import queue
+import threading
+from typing import Optional
+
+import numpy as np
+
+from .. import output_stage
+from ._pcm import Busy, _check_numerics, _host_i16
+from .batching import _Conversion, _Request, _collate_from, latents
+
+
+class _RowStream:
+    """Iterator over one request's PCM16 chunks of a ``StreamingBatchService``.  ``close()`` abandons the request: its row
+    leaves the batch at the next tick."""
+
+    _END = object()
+
+    def __init__(self):
+        self._q: "queue.Queue" = queue.Queue()
+        self._closed = False
+        self._done = False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> bytes:
+        if self._done or self._closed:
+            raise StopIteration
+        item = self._q.get()
+        if item is self._END:
+            self._done = True
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._done = True
+            raise item
+        return item
+
+    def close(self) -> None:
+        self._closed = True
+
+    @property
+    def closed(self) -> bool:
+        return self._closed
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class _StreamRequest(_Request):
+    """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
+
+    def __init__(self, row, seed: int, scales=(None, None, None, None)):
+        super().__init__(row, seed, scales)
+        self.stream = _RowStream()
+        self.z = self.g = None
+        self.L = self.pos = 0
+        self.output = None            # ``output_rate``: the request's own ``output_stage.Stream``, one window per tick
+        self.history = None           # ``fused_output``: the request's Engine.output_history(), from admission on
+
+
+class LiveConversion(_RowStream):
+    """A live conversion of a ``StreamingBatchService`` (``open_conversion``): the caller feeds the recording while it is
+    being made and iterates over the converted PCM16 ``bytes`` -- exact chunks, what the finished recording converted
+    alone gives.  ``feed`` and ``end`` may be called from any thread; ``close()`` abandons the session."""
+
+    def __init__(self, cv: "threading.Condition"):
+        super().__init__()
+        self._cv = cv                 # the service's condition: guards _fed / _ended / _wake, wakes the worker
+        self._fed: list = []          # pieces the worker has not taken yet
+        self._ended = False
+        self._wake = True             # something changed since the worker last looked at this session
+
+    def feed(self, samples) -> None:
+        """The next samples of the recording: 1-D float32 at the model's rate, a piece of any size (copied)."""
+        a = np.array(samples, dtype=np.float32, copy=True)
+        if a.ndim != 1:
+            raise ValueError("samples must be a 1-D float32 array at the model's sampling rate")
+        with self._cv:
+            if self._ended:
+                raise RuntimeError("the recording has ended")
+            if a.size:
+                self._fed.append(a)
+                self._wake = True
+                self._cv.notify_all()
+
+    def end(self) -> None:
+        """The recording is complete: what remains is converted, reflected at its true end, and the iterator ends."""
+        with self._cv:
+            if not self._ended:
+                self._ended = self._wake = True
+                self._cv.notify_all()
+
+    def close(self) -> None:
+        super().close()
+        with self._cv:
+            self._wake = True
+            self._cv.notify_all()
+
+
+class _LiveRequest(_StreamRequest):
+    """The worker's side of a ``LiveConversion``.  ``n`` samples have reached the device, ``buf`` holds those from ``first``
+    on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
+    ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
+
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale):
+        super().__init__(None, seed)
+        self.stream = stream
+        self.sid_src, self.sid_tgt = int(sid_src), int(sid_tgt)
+        self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)
+        self.buf = None
+        self.first = self.n = self.done = self.e0 = 0
+        self.closed = False
+
+
+class StreamingBatchService:
+    """Streaming AND batching (round 11): a set of active requests, each at its own position of its own utterance; every
+    tick advances all of them by one chunk in ONE set of generator launches (``Engine.generator_stream_rows``), requests join
+    and leave between ticks, and each caller receives PCM16 bytes as its chunk completes.  ``submit`` returns an iterator
+    of ``bytes`` (with ``close()``); one worker thread loops over ``step()`` -- one synchronous tick -- and with
+    ``autostart=False`` the caller drives ``step()`` itself.  A tick, in order:
+
+    1. admit    queued requests while fewer than ``max_batch`` are active: one isolated ``encode`` / ``frame_lengths_host`` /
+                ``decode(max_len=0)`` with the requests' seeds -- and, where a request names a scale or leaves a control to
+                the predictors, the group's per-row table -- for the admitted group; each keeps its z row, g row and L.  A
+                zero-frame request ends at once with no bytes; a failing admission fails that group's streams only.
+    2. generate one ``generator_stream_rows`` call for all active requests, each at its own ``f0`` (a request's first chunk
+                has ``first_chunk_frames`` frames if that is given: earlier first audio).
+    3. deliver  one device-to-host copy of the int16 block, ``check_numerics(sync=False)``, each request's bytes on its queue.
+    4. retire   finished and closed requests.
+
+    A request's audio is what the reference returns for it alone (isolated mode + the halo of the streamed vocoder), whoever
+    shares its ticks.  ``output_rate``: each request's float chunk goes through its own ``output_stage.Stream`` (one small
+    launch and one copy per request per tick); the bytes are those of the one-shot output stage.  With ``fused_output=True``
+    the tick instead makes one ``Engine.generator_stream_rows_output`` call -- the ragged output stage in place of the
+    collect launch -- and one device-to-host copy, as the plain path does; a request carries its filter history
+    (``Engine.output_history``) from admission on, and the bytes are the same.  ``stats``: ticks, rows per tick and
+    admitted groups.  No priorities, no retries, no backpressure.
+    ``submit_conversion`` queues a recording to convert to another speaker: admission runs the group's conversions through
+    one ``convert_latent`` and keeps each one's ``z_hat`` row, target speaker vector and ``L = T(n)``; from then on it is an
+    ordinary row of the tick, next to text rows (a group without a conversion makes the calls it always made).
+    ``open_conversion`` opens a LIVE conversion: the recording is fed while it is made (``LiveConversion.feed`` / ``end``).
+    A session joins a tick when the samples its next chunk depends on have arrived -- the chunk, the vocoder's halo G and
+    the conversion's halo H (``schema.convert_halo_frames``) behind it: an algorithmic delay of
+    ``(G + H) * hop + n_fft - pad`` samples, about 1.3 s for the default configuration --; the tick then runs ONE
+    ``Engine.convert_stream_rows`` for the ready sessions and hands each one's window of ``z_hat`` to the tick's vocoder call
+    as one more row.  A session that is not ready sits the tick out; while only such sessions exist the worker sleeps.  The
+    bytes are those of the finished recording converted alone, with the frame-major noise of ``vsp_convert_stream_rows``
+    (not the layout ``submit_conversion`` draws).  A session keeps on the device the samples its next window reads and
+    those behind them, nothing older.  No backpressure and no reduced-lookahead mode."""
+
+    def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
+                 noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
+                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False):
+        if not 1 <= max_batch <= 64 or chunk_frames < 1:
+            raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
+        if fused_output and output_rate is None:
+            raise ValueError("fused_output needs an output_rate")
+        if first_chunk_frames is not None and not 1 <= first_chunk_frames <= chunk_frames:
+            raise ValueError("1 <= first_chunk_frames <= chunk_frames")
+        self._collate = _collate_from(table, spk2id, collate)
+        self.net, self.max_batch, self.chunk_frames = net, int(max_batch), int(chunk_frames)
+        self.first_chunk_frames = None if first_chunk_frames is None else int(first_chunk_frames)
+        self.noise_scale = float(noise_scale)
+        self.output_rate = None if output_rate is None else int(output_rate)
+        self.fused_output = bool(fused_output)
+        if self.output_rate is not None:
+            net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
+        self.stats = {"ticks": 0, "rows_per_tick": [], "groups": 0}
+        self._pending: "collections.deque" = collections.deque()
+        self._active: list = []
+        self._live: list = []                # open live conversions (_LiveRequest); guarded by _cv
+        self._geometry = None                # (hop, n_fft, pad, G, H) of live conversions, from the first open_conversion on
+        self._cv = threading.Condition()     # guards _pending / _live / _closed; the worker sleeps on it while there is no work
+        self._closed = False
+        self._worker = None
+        if autostart:
+            self._worker = threading.Thread(target=self._run, name="vispeech-stream-batching", daemon=True)
+            self._worker.start()
+
+    # ------------------------------------------------------------------ callers' side
+    def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
+               noise_scale=None) -> _RowStream:
+        """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
+        1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
+        request's PCM16 ``bytes``, one piece per tick the request takes part in."""
+        return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
+
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> _RowStream:
+        """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
+        the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
+        frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
+        NOT the service's text-to-speech ``noise_scale``)."""
+        return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale), noise_seed))
+
+    def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> LiveConversion:
+        """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
+        ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
+        ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``)."""
+        if self.fused_output:
+            # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
+            # filter's phase and its history must not see the shift
+            eng = self.net._engine
+            L, M, H = eng.output_plan
+            shift = self.net.dims.total_upsample * L
+            if shift % M or 2 * H + M > eng.generator_halo * shift:
+                raise ValueError("fused_output cannot carry a live conversion at this output rate (one frame is not a whole "
+                                 "number of output samples, or the filter is longer than the vocoder's halo): "
+                                 "use fused_output=False")
+        if self._geometry is None:
+            # (not in the constructor: a net that serves text only need not have the front end's dimensions)
+            from .. import schema
+            dims = self.net.dims
+            hop, n_fft = dims.hop_length, 2 * (dims.spec_channels - 1)
+            self._geometry = (hop, n_fft, (n_fft - hop) // 2, self.net._engine.generator_halo, schema.convert_halo_frames(dims))
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv), sid_src, sid_tgt, noise_seed, noise_scale))
+
+    def _enqueue(self, req: _StreamRequest) -> _RowStream:
+        """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("the service is closed")
+            if isinstance(req, _LiveRequest):
+                if len(self._live) + len(self._active) >= self.max_batch:      # (a tick has at most max_batch rows)
+                    raise Busy(f"{self.max_batch} requests are active")
+                self._live.append(req)
+            else:
+                self._pending.append(req)
+            self._cv.notify()
+        return req.stream
+
+    def close(self) -> None:
+        """Serve what is queued and active, then stop the worker and join it (without a worker: run the ticks here).  Live
+        conversions still open are ended: what they were fed is converted."""
+        with self._cv:
+            self._closed = True
+            live = list(self._live)
+            self._cv.notify()
+        for r in live:
+            r.stream.end()
+        if self._worker is not None:
+            self._worker.join()
+        else:
+            while self.step():
+                pass
+
+    def _run(self) -> None:
+        while True:
+            with self._cv:
+                # (live sessions that wait for samples are no work: feed / end / close set their _wake and notify)
+                while not self._pending and not self._active and not self._closed and not any(r.stream._wake for r in self._live):
+                    self._cv.wait()
+                if self._closed and not self._pending and not self._active and not self._live:
+                    return
+            self.step()
+
+    # ------------------------------------------------------------------ one tick
+    def step(self) -> bool:
+        """One tick (admit, generate, deliver, retire).  Returns whether requests are still queued or active."""
+        self._admit()
+        self._active = [r for r in self._active if not r.stream.closed]      # (closed by its caller: the row leaves here)
+        live = self._ready_live()
+        if self._active or live:
+            try:
+                self._generate_and_deliver(self._active + live)
+            except Exception as e:             # the tick's requests fail; the service lives on
+                for r in self._active + live:
+                    r.stream._q.put(e)
+                self._active = []
+                self._drop_live(live)
+                live = []
+        for r in self._active:
+            if r.pos >= r.L:
+                r.stream._q.put(_RowStream._END)
+        self._active = [r for r in self._active if r.pos < r.L]
+        for r in live:
+            self._after_live_tick(r)
+        with self._cv:
+            return bool(self._pending or self._active or any(r.stream._wake for r in self._live))
+
+    def _chunk_len(self, first: bool) -> int:
+        """Frames of a request's next chunk: ``first_chunk_frames`` for its first one, where that is given."""
+        return self.first_chunk_frames if first and self.first_chunk_frames is not None else self.chunk_frames
+
+    # ------------------------------------------------------------------ live conversions
+    def _drop_live(self, reqs) -> None:
+        with self._cv:
+            self._live = [r for r in self._live if not any(r is x for x in reqs)]
+
+    def _ready_live(self) -> list:
+        """Takes what the live sessions were fed, and runs the conversion windows of those whose next chunk is ready: ONE
+        ``convert_stream_rows`` call.  Returns them as rows of this tick's vocoder call; a session that must wait, and one
+        that fails, is not among them."""
+        import torch
+        from .. import schema
+        with self._cv:
+            if not self._live:
+                return []
+            taken = []
+            for r in self._live:
+                taken.append((r, r.stream._fed, r.stream._ended, r.stream.closed))
+                r.stream._fed, r.stream._wake = [], False
+        eng = self.net._engine
+        hop, n_fft, _, G, H = self._geometry
+        device = getattr(eng, "device", "cpu")
+        ready, rows, gone = [], [], []
+        for r, pieces, ended, closed in taken:
+            if closed:                           # abandoned by its caller: the session leaves here
+                gone.append(r)
+                continue
+            if pieces:
+                new = torch.as_tensor(np.concatenate(pieces)).to(device)
+                r.buf = new if r.buf is None else torch.cat([r.buf, new])
+                r.n += int(new.numel())
+            r.closed = ended
+            f1 = r.done + self._chunk_len(r.done == 0)
+            if r.closed:
+                T = schema.convert_frames(r.n, n_fft, hop)
+                if r.done >= T:                  # (a recording too short for a frame: no bytes)
+                    r.stream._q.put(_RowStream._END)
+                    gone.append(r)
+                    continue
+                f1 = min(T, f1)
+            e0 = max(0, r.done - G)
+            e1 = min(f1 + G, T) if r.closed else f1 + G
+            if not schema.convert_window_plan(n_fft, hop, H, r.n, r.closed, e0, e1)[0]:
+                continue                         # the samples this chunk depends on have not arrived: sit the tick out
+            r.e0, r.L, r.pos = e0, e1 - e0, r.done - e0
+            ready.append(r)
+            rows.append((r.buf, r.first, r.n, r.closed, e0, e1, r.sid_src, r.sid_tgt, r.seed, r.noise_scale))
+        if ready:
+            try:
+                z, g = eng.convert_stream_rows(rows, self.chunk_frames + 2 * G)
+                for b, r in enumerate(ready):
+                    r.z, r.g = z[b], g[b]
+                    if self.fused_output and r.history is None:
+                        r.history = eng.output_history()
+            except Exception as e:               # these sessions fail; the tick's other rows and the service live on
+                for r in ready:
+                    r.stream._q.put(e)
+                gone += ready
+                ready = []
+        if gone:
+            self._drop_live(gone)
+        return ready
+
+    def _after_live_tick(self, r: "_LiveRequest") -> None:
+        """A live session after its tick: the end of the stream, or the samples its next window no longer reads dropped."""
+        hop, _, pad, G, H = self._geometry
+        finished = r.pos >= r.L                  # (the window ended at the recording's last frame, and so did the chunk)
+        r.done = r.e0 + r.pos
+        r.z = r.g = None
+        if finished:
+            r.stream._q.put(_RowStream._END)
+            self._drop_live([r])
+            return
+        # the next window starts at frame done - G - H; a reflection at the end, whenever it comes, reaches back pad samples
+        w0 = max(0, r.done - G - H)
+        keep = max(0, min(w0 * hop - pad, r.n - 1 - pad))
+        if keep > r.first:
+            r.buf = r.buf[keep - r.first:].clone()
+            r.first = keep
+        with self._cv:
+            r.stream._wake = True                # (it may be ready again at once: the next step looks)
+
+    def _admit(self) -> None:
+        group = []
+        with self._cv:
+            while self._pending and len(self._active) + len(self._live) + len(group) < self.max_batch:
+                req = self._pending.popleft()
+                if req.stream.closed:
+                    req.stream._q.put(_RowStream._END)
+                else:
+                    group.append(req)
+        if not group:
+            return
+        self.stats["groups"] += 1
+        try:
+            eng = self.net._engine
+            for r, (z, g, L) in zip(group, latents(eng, self._collate, group, self.noise_scale)):
+                r.z, r.g, r.L, r.pos = z, g, L, 0
+            for r in group:
+                if r.L <= 0:
+                    r.stream._q.put(_RowStream._END)          # nothing to synthesise: no bytes
+                    continue
+                if self.fused_output:
+                    r.history = eng.output_history()
+                self._active.append(r)
+        except Exception as e:                 # this group's requests fail; the active ones and the service live on
+            for r in group:
+                r.stream._q.put(e)
+
+    def _generate_and_deliver(self, reqs) -> None:
+        eng = self.net._engine
+        hop = self.net.dims.total_upsample
+        rows, counts = [], []
+        for r in reqs:
+            f1 = min(r.L, r.pos + self._chunk_len(r.pos == 0))
+            rows.append((r.z, r.g, r.L, r.pos, f1))
+            counts.append(f1 - r.pos)
+        self.stats["ticks"] += 1
+        self.stats["rows_per_tick"].append(len(rows))
+        if self.fused_output:
+            out, done = eng.generator_stream_rows_output([row + (r.history,) for row, r in zip(rows, reqs)],
+                                                         self.chunk_frames, pcm=True)
+        else:
+            out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=self.output_rate is None)
+            done = [n * hop for n in counts]
+        if self.output_rate is not None and not self.fused_output:
+            for b, (r, n) in enumerate(zip(reqs, counts)):     # each float chunk through its request's own output stage
+                r.pos += n
+                piece = self._through_output_stage(r, out[b:b + 1, : done[b]])
+                _check_numerics(self.net)
+                if piece:
+                    r.stream._q.put(piece)
+            return
+        block = _host_i16(out, flat=False)                                   # the tick's one device-to-host copy
+        _check_numerics(self.net)
+        for b, (r, n) in enumerate(zip(reqs, counts)):
+            r.pos += n
+            if done[b]:                        # (a fused tick may complete no output sample of a request)
+                r.stream._q.put(block[b, : done[b]].tobytes())
+
+    def _through_output_stage(self, r: _StreamRequest, x) -> bytes:
+        """The request's float window through its own ``output_stage.Stream``; returns the PCM16 bytes it completes (none
+        for a window too short to complete an output sample), with the filter's tail behind the request's last window."""
+        if r.output is None:
+            r.output = output_stage.Stream(self.net._engine, None, pcm=True)
+        done = [r.output.push(x)] + ([r.output.finish()] if r.pos >= r.L else [])
+        return b"".join(_host_i16(y).tobytes() for y in done if y is not None)
