@@ -610,6 +610,34 @@ int vsp_cl_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K
 int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, int stride, const float* x,
                          const float* w_host, const float* bias_host, float in_slope, float* out);
 
+/* ---- attention operators, stand-alone (ABI 7, additive) ------------------------------------ */
+/* The two windowed relative-position attention kernels (reference attentions.py:148-179) as plain operators on the
+ * reference's layout, with every block form selectable: what tests/test_attention_ops.py drives.  Like the vocoder
+ * operators above they allocate, upload and synchronise the stream inside the call (not the fast path: vsp_encoder).
+ *
+ * vsp_rel_attention: qkv DEVICE fp32 [B][3 H][T] (rows [0, H) = q, [H, 2 H) = k, [2 H, 3 H) = v, T contiguous) ->
+ * out DEVICE fp32 [B][H][T].  emb_k_host / emb_v_host: HOST fp32 [2 window + 1][H / n_heads], shared over the heads.
+ * lengths: NULL or a DEVICE int64 [B], 0 <= lengths[b] <= T; pairs with a query or key at or beyond lengths[b] score
+ * -1e4, so a query row at or beyond it (every row of an utterance of length 0) is the uniform average over all T keys,
+ * as in the reference; all T columns of out are written.
+ * kernel 0: attention.hip (f32 MFMA, two passes), 1: attention_f16s.hip (split-f16, online softmax).
+ * variant -1: the launcher's choice from the grid size, as the model runs it; 0: the small-grid form (kernel 0: 32-query
+ * blocks whose four waves split the keys; kernel 1: 64-query blocks with two key-tile streams); 1: the 128-query form.
+ * VSP_ERR_ARG: a null pointer, B or T negative, kernel or variant out of range, a length outside [0, T].
+ * VSP_ERR_UNSUPPORTED: H / n_heads not 32, 64 or 96, H % n_heads != 0, window outside [0, 7].  B = 0 or T = 0: VSP_OK,
+ * nothing launched. */
+int vsp_rel_attention(void* stream, int B, int T, int H, int n_heads, int window, const float* qkv,
+                      const float* emb_k_host, const float* emb_v_host, const int64_t* lengths, int kernel, int variant,
+                      float* out);
+/* vsp_rel_attention_fused: the projections conv_q | conv_k | conv_v of x * mask (attentions.py:138-146) and the operand
+ * packing in ONE launch (attn_qkv_pack_f16s), then the split-f16 attention on the packed images -- an encoder layer's
+ * attention as vsp_encoder runs it on mid-size grids.  x DEVICE fp32 [B][H][T]; w_qkv_host HOST fp32 [3 H][H] (the three
+ * 1x1 convolution weights stacked q | k | v), bias_qkv_host [3 H]; the rest as above, variant for the attention launch.
+ * n_heads = 2 and H = 192, 128 or 64 only: VSP_ERR_UNSUPPORTED otherwise. */
+int vsp_rel_attention_fused(void* stream, int B, int T, int H, int n_heads, int window, const float* x,
+                            const float* w_qkv_host, const float* bias_qkv_host, const float* emb_k_host,
+                            const float* emb_v_host, const int64_t* lengths, int variant, float* out);
+
 /* ---- output stage (round 8, ABI 7, additive) ------------------------------------------------ */
 /* The last hop of the reference's /tts handler: it writes the 44.1 kHz waveform and runs `ffmpeg -i c.wav -ar 22050`
  * (inference_api.py:50-52); clients receive 22.05 kHz PCM16.  Here: waveform float32 at the model's rate -> polyphase FIR

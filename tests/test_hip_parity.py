@@ -626,6 +626,8 @@ def test_attention_stage_matches_oracle(net, weights, dims, T, lens):
         # zeroed by the encoder's final x * mask)
         for b, n in enumerate(lens):
             assert rel_err(to_np(out)[b, :, :n], ref.numpy()[b, :, :n]) <= STAGE_TOL, (T, which, b)
+        # ... and the masked rows too: both kernels give the reference's uniform average there (tests/test_attention_ops.py)
+        assert rel_err(to_np(out), ref.numpy()) <= STAGE_TOL, (T, which)
 
 
 @pytest.mark.parametrize("which,T,lens", [(1, 37, [37, 20, 1]), (3, 130, [130, 64])])

@@ -163,6 +163,8 @@ SIGNATURES = {
     "vsp_cl_resblock2": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_cl_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),
     "vsp_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P]),
+    "vsp_rel_attention": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "vsp_rel_attention_fused": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "vsp_resample_plan": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vsp_resample_filter": (_I, [_I, _I, _I, C.c_double, C.c_double, _P]),
     "vsp_resample_out_len": (_I64, [_I64, _I, _I]),

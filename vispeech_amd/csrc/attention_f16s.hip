@@ -530,9 +530,10 @@ static void launch_attn_f16s(const float* qkv, long qkv_bs, long qkv_cs, const _
 
 // workspace: 3 * attn_pack_bytes(B, n_heads, dk, T), 256-byte aligned
 // qkv == NULL: the images in `workspace` are already packed (launch_attn_qkv_pack_f16s)
+// block_mode 0 / 1 forces the 64-query two-stream form / the 128-query form, < 0 = automatic (as launch_attention's ksplit_mode)
 hipError_t launch_attention_f16s(const float* qkv, long qkv_bs, long qkv_cs, const float* emb_k, const float* emb_v,
                                  const int64_t* lengths, float* out, long o_bs, long o_cs, int B, int H, int n_heads, int T,
-                                 int window, void* workspace, hipStream_t s) {
+                                 int window, void* workspace, hipStream_t s, int block_mode) {
   if (n_heads <= 0 || H % n_heads != 0 || 2 * window + 1 > 16 || T <= 0 || !workspace) return hipErrorInvalidValue;
   const int dk = H / n_heads;
   const size_t one = attn_pack_bytes(B, n_heads, dk, T);
@@ -543,7 +544,7 @@ hipError_t launch_attention_f16s(const float* qkv, long qkv_bs, long qkv_cs, con
   // 128-query blocks when they fill the chip -- eight waves of one query tile each (C3 attention 0.66 -> 0.60 ms against
   // four waves of two tiles: same K / V traffic per query, twice the waves to overlap softmax and MFMAs) --; 64-query
   // blocks with two key-tile streams otherwise
-  const bool small = (long)((T + 127) / 128) * n_heads * B < 512;
+  const bool small = block_mode >= 0 ? block_mode == 0 : (long)((T + 127) / 128) * n_heads * B < 512;
 #define VSP_ATTF(DKV)                                                                                                   \
   if (qkv) hipLaunchKernelGGL((attn_pack_f16s<DKV>), pgrid, dim3(256), 0, s, qkv, qkv_bs, qkv_cs, H, T, Qp, Kp, Vp);    \
   if (small) launch_attn_f16s<DKV, 4, 1, 2>(qkv, qkv_bs, qkv_cs, Qp, Kp, Vp, emb_k, emb_v, lengths, out, o_bs, o_cs, B, H, n_heads, T, window, s); \

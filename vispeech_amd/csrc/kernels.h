@@ -312,11 +312,12 @@ hipError_t launch_attention(const float* qkv, long qkv_bs, long qkv_cs, const fl
                             long o_cs, int B, int H, int n_heads, int T, int window, int ksplit_mode, hipStream_t s);
 
 // the same on the f16 matrix core with split operands, one pass (attention_f16s.hip); workspace = 3 *
-// attn_pack_bytes(B, n_heads, H / n_heads, T) bytes (the packed q | k | v operand images)
+// attn_pack_bytes(B, n_heads, H / n_heads, T) bytes (the packed q | k | v operand images).  block_mode < 0: the launcher
+// picks the block form from the grid size; 0 / 1 force the 64-query form with two key streams / the 128-query form
 size_t attn_pack_bytes(int B, int n_heads, int DK, int T);
 hipError_t launch_attention_f16s(const float* qkv, long qkv_bs, long qkv_cs, const float* emb_k, const float* emb_v,
                                  const int64_t* lengths, float* out, long o_bs, long o_cs, int B, int H, int n_heads, int T,
-                                 int window, void* workspace, hipStream_t s);
+                                 int window, void* workspace, hipStream_t s, int block_mode = -1);
 // conv_q | conv_k | conv_v of x * x_mask AND the packing of their results in one launch: fills `workspace` with the images
 // launch_attention_f16s(qkv = NULL, ...) then consumes.  wg: pack_g16_weights of the stacked [3H][H] projection.
 bool attn_qkv_pack_supported(int H, int n_heads);

@@ -1,6 +1,6 @@
-// Stand-alone vocoder operators of the C-ABI (include/vispeech_hip.h): one convolution, ResBlock or up-convolution on the
-// caller's tensors with host weights, no context -- what tests/test_cl_ops.py, test_c16_ops.py, test_resblock2_ops.py and
-// test_upsample_ops.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
+// Stand-alone operators of the C-ABI (include/vispeech_hip.h): one convolution, ResBlock, up-convolution or attention on the
+// caller's tensors with host weights, no context -- what tests/test_cl_ops.py, test_c16_ops.py, test_resblock2_ops.py,
+// test_upsample_ops.py and test_attention_ops.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
 // uses (cl_args.h).  Every call allocates, uploads and synchronises: test and measurement entry points, not a hot path.
 #include <algorithm>
 #include <cstdlib>
@@ -39,6 +39,33 @@ int op_rc(hipError_t e) { return e == hipSuccess ? VSP_OK : (e == hipErrorInvali
 // the input padded by kt - 1, Nq = T + 1 input times, output rows n = stride q + r - (K - stride) / 2 kept in [0, stride T)
 // -- the shapes plan_model accepts
 bool ups_shape_ok(int K, int stride) { return stride >= 1 && K >= stride && K % stride == 0 && (K - stride) % 2 == 0; }
+// the shapes both attention launchers take (they answer hipErrorInvalidValue to the rest)
+bool attn_shape_ok(int H, int n_heads, int window) {
+  if (H <= 0 || n_heads <= 0 || H % n_heads || window < 0 || 2 * window + 1 > 16) return false;
+  const int dk = H / n_heads;
+  return dk == 32 || dk == 64 || dk == 96;
+}
+// device int64 lengths [B], each in [0, T] (the kernels index keys and queries by them)
+int check_lengths64(const int64_t* lengths, int B, int T, hipStream_t s) {
+  if (!lengths) return VSP_OK;
+  std::vector<int64_t> len(B);
+  hipError_t e = hipMemcpyAsync(len.data(), lengths, (size_t)B * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return op_rc(e);
+  for (int64_t l : len)
+    if (l < 0 || l > T) return VSP_ERR_ARG;
+  return VSP_OK;
+}
+// the relative-position tables [2 window + 1][dk] -> device
+hipError_t upload_emb(const float* emb_k_host, const float* emb_v_host, int window, int dk, DevBuf& ek, DevBuf& ev, hipStream_t s) {
+  const size_t bytes = (size_t)(2 * window + 1) * dk * 4;
+  hipError_t e = ek.alloc(bytes);
+  if (e == hipSuccess) e = ev.alloc(bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(ek.p, emb_k_host, bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ev.p, emb_v_host, bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);     // (pageable host memory: the caller's arrays may go after the call)
+  return e;
+}
 }  // namespace
 
 extern "C" {
@@ -310,6 +337,65 @@ int vsp_conv_transpose1d(void* stream, int B, int T, int Cin, int Cout, int K, i
   if (e == hipSuccess)
     e = hipMemcpy2DAsync(out, (size_t)T_out * 4, os.p, (size_t)tp_out * 4, (size_t)T_out * 4, (size_t)B * Cout,
                          hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_rel_attention(void* stream, int B, int T, int H, int n_heads, int window, const float* qkv, const float* emb_k_host,
+                      const float* emb_v_host, const int64_t* lengths, int kernel, int variant, float* out) {
+  if (!qkv || !emb_k_host || !emb_v_host || !out || B < 0 || T < 0 || kernel < 0 || kernel > 1 || variant < -1 || variant > 1)
+    return VSP_ERR_ARG;
+  if (!attn_shape_ok(H, n_heads, window)) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_lengths64(lengths, B, T, s); rc != VSP_OK) return rc;
+  const int dk = H / n_heads;
+  DevBuf ek, ev, ws;
+  hipError_t e = upload_emb(emb_k_host, emb_v_host, window, dk, ek, ev, s);
+  const float* ekd = static_cast<const float*>(ek.p);
+  const float* evd = static_cast<const float*>(ev.p);
+  if (kernel == 0) {
+    // variant 0 = the 32-query blocks whose waves split the keys (KSPLIT), 1 = the 128-query blocks
+    if (e == hipSuccess)
+      e = launch_attention(qkv, 3L * H * T, T, ekd, evd, lengths, out, (long)H * T, T, B, H, n_heads, T, window,
+                           variant < 0 ? -1 : 1 - variant, s);
+  } else {
+    if (e == hipSuccess) e = ws.alloc(3 * attn_pack_bytes(B, n_heads, dk, T));
+    if (e == hipSuccess)
+      e = launch_attention_f16s(qkv, 3L * H * T, T, ekd, evd, lengths, out, (long)H * T, T, B, H, n_heads, T, window, ws.p, s,
+                                variant);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_rel_attention_fused(void* stream, int B, int T, int H, int n_heads, int window, const float* x, const float* w_qkv_host,
+                            const float* bias_qkv_host, const float* emb_k_host, const float* emb_v_host,
+                            const int64_t* lengths, int variant, float* out) {
+  if (!x || !w_qkv_host || !bias_qkv_host || !emb_k_host || !emb_v_host || !out || B < 0 || T < 0 || variant < -1 || variant > 1)
+    return VSP_ERR_ARG;
+  if (!attn_shape_ok(H, n_heads, window) || !attn_qkv_pack_supported(H, n_heads)) return VSP_ERR_UNSUPPORTED;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = check_lengths64(lengths, B, T, s); rc != VSP_OK) return rc;
+  const int dk = H / n_heads;
+  // the stacked projection as the model holds it (weights.cpp: the wg image of an attention layer's qkv; the bias unscaled)
+  std::vector<uint16_t> wgh(packed_g16_halfs(3 * H, H, 1));
+  pack_g16_weights(wgh.data(), 3 * H, H, 1, w_qkv_host);
+  DevBuf ek, ev, ws, wg, bias;
+  hipError_t e = upload_emb(emb_k_host, emb_v_host, window, dk, ek, ev, s);
+  if (e == hipSuccess) e = wg.alloc(wgh.size() * 2);
+  if (e == hipSuccess) e = bias.alloc((size_t)3 * H * 4);
+  if (e == hipSuccess) e = ws.alloc(3 * attn_pack_bytes(B, n_heads, dk, T));
+  if (e == hipSuccess) e = hipMemcpyAsync(wg.p, wgh.data(), wgh.size() * 2, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bias_qkv_host, (size_t)3 * H * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess)
+    e = launch_attn_qkv_pack_f16s(x, (long)H * T, T, static_cast<const uint16_t*>(wg.p), static_cast<const float*>(bias.p),
+                                  lengths, B, H, n_heads, T, ws.p, s);
+  if (e == hipSuccess)
+    e = launch_attention_f16s(nullptr, 3L * H * T, T, static_cast<const float*>(ek.p), static_cast<const float*>(ev.p), lengths,
+                              out, (long)H * T, T, B, H, n_heads, T, window, ws.p, s, variant);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return op_rc(e);
 }
