@@ -721,6 +721,76 @@ int64_t vsp_stream_rows_out_samples(int L, int M, int H, int up, int chunk_frame
 int vsp_generator_stream_rows_output(vsp_ctx* ctx, void* stream, int B, const vsp_stream_row_out* rows, void* out,
                                      int64_t out_stride, int pcm, void* workspace, int64_t workspace_bytes);
 
+/* ---- input stage (round 16, ABI 7, additive) ------------------------------------------------ */
+/* The mirror of the output stage, in front of voice conversion: raw samples at the rate and in the encoding a recording
+ * arrives in -> float32 at the model's rate, on the GPU, ragged over a batch and exact under any split of a live feed.
+ * (The reference brings its data to the model's rate offline, with librosa, in its data preparation.  This filter is
+ * ours by specification -- the output stage's published formula with the rates swapped; it is NOT librosa's resample.)
+ *
+ *   g = gcd(in_rate, model_rate), L = model_rate / g, M = in_rate / g, Q = max(L, M)
+ *   H    = zeros * Q                                  (half length; 2 H + 1 taps)
+ *   fc   = rolloff / Q
+ *   h[n] = L fc sinc(fc n) kaiser(2 H + 1, beta)[n + H],  n = -H .. H        (numpy's sinc / kaiser conventions)
+ *   y[m] = sum_k h[m M - k L] x[k],  k in [0, n) with |m M - k L| <= H,  m = 0 .. ceil(n L / M) - 1
+ * computed in double precision and rounded to fp32 once.  Defaults: zeros 32, beta 9.62, rolloff 1 - 3.065 / zeros.
+ * L = M = 1 is the pass-through: H = 0, one unit tap -- decoding only.  Supported: L <= 441, M <= 640, 1 <= zeros <= 64
+ * (VSP_ERR_UNSUPPORTED beyond; other bad arguments VSP_ERR_ARG).  8 / 16 / 32 kHz -> 44.1 kHz are 441 / 80, 441 / 160 and
+ * 441 / 320; 48 / 96 / 192 kHz are 147 / 160, 147 / 320 and 147 / 640.
+ *
+ * x[k] is the decoded sample, float32:
+ *   VSP_IN_F32   the float32 taken as it is
+ *   VSP_IN_S16   x = s / 32768.0f, s the int16 (exact)
+ *   VSP_IN_ULAW  x = v / 32768.0f (exact), v the 16-bit linear value of ITU-T G.711 mu-law for code byte c:
+ *                  u = ~c & 0xFF;  e = (u >> 4) & 7;  q = u & 15;  t = (((q << 3) + 0x84) << e) - 0x84;  v = (u & 0x80) ? -t : t
+ *                (0xFF -> 0, 0x7F -> 0, 0x80 -> +32124, 0x00 -> -32124)
+ *   VSP_IN_ALAW  x = v / 32768.0f (exact), v the 16-bit linear value of ITU-T G.711 A-law for code byte c:
+ *                  a = c ^ 0x55;  e = (a >> 4) & 7;  q = a & 15;  t = (q << 4) + 8;  if (e >= 1) t = (t + 0x100) << (e - 1);
+ *                  v = (a & 0x80) ? t : -t
+ *                (0xD5 -> +8, 0x55 -> -8, 0xAA -> +32256, 0x2A -> -32256)
+ *
+ * vsp_input_plan / vsp_input_filter / vsp_input_decode_table are host-only (no device): the plan, the 2 H + 1 taps
+ * (rolloff <= 0 selects the default; zeros == 0: 32) and the 256 decoded values of a G.711 law as the kernel uses them
+ * (VSP_ERR_ARG for VSP_IN_F32 / VSP_IN_S16, which have no table).  ceil(n L / M) is vsp_resample_out_len. */
+#define VSP_IN_F32 0
+#define VSP_IN_S16 1
+#define VSP_IN_ULAW 2
+#define VSP_IN_ALAW 3
+#define VSP_INPUT_RATES_MAX 8
+int vsp_input_plan(int in_rate, int model_rate, int zeros, int* L, int* M, int* half_len);
+int vsp_input_filter(int in_rate, int model_rate, int zeros, double beta, double rolloff, float* taps_host);
+int vsp_input_decode_table(int enc, float* table256);
+/* Builds the filter of (in_rate -> model_rate) and uploads its table [P][L] (the output stage's layout) to the context's
+ * device.  A context holds up to VSP_INPUT_RATES_MAX input rates at once (one more: VSP_ERR_STATE); configuring a rate again
+ * replaces its table; model_rate == 0 drops the rate (VSP_OK also when it was not configured).  in_rate == model_rate
+ * configures the pass-through.  May allocate and synchronise, like vsp_output_configure; the tables are freed by vsp_destroy. */
+int vsp_input_configure(vsp_ctx* ctx, int in_rate, int model_rate, int zeros, double beta, double rolloff);
+/* One row of vsp_input_rows: a window of one recording and the output samples to compute from it.  The descriptors live in
+ * HOST memory, are read before the call returns and reach the device as kernel arguments. */
+typedef struct vsp_input_row {
+  const void* in;        /* DEVICE: raw samples [in_first, in_first + in_len) of the recording, in `enc` */
+  int64_t in_first, in_len;
+  int64_t n_total;       /* the recording's length in input samples once it has ended, -1 while it is open */
+  float* out;            /* DEVICE: receives output samples [m0, m1) at out[0 .. m1 - m0) */
+  int64_t m0, m1;
+  int64_t out_fill;      /* >= m1 - m0: out[m1 - m0 .. out_fill) is written as exactly 0.0f */
+} vsp_input_row;
+/* 1 <= B <= 64 rows of one (in_rate, enc), one launch (two when the descriptors exceed the kernel-argument space; the caller
+ * sees no difference).  No allocation, no synchronisation, caller's stream.  With (L, M, H) of the configured rate and
+ *   complete(s, ended) = ended ? ceil(s L / M) : min(ceil(s L / M), max(0, ceil((L s - H) / M)))
+ * (vispeech_amd.output_stage.complete_outputs), checked on the host before anything is launched:
+ *   the rate is configured (VSP_ERR_STATE);
+ *   enc is one of VSP_IN_*, rows non-NULL, `in` non-NULL (unless in_len == 0) and aligned to its element, `out` non-NULL
+ *   (unless out_fill == 0), in_len >= 0, n_total >= -1 (VSP_ERR_ARG);
+ *   0 <= in_first, 0 <= m0 <= m1 <= out_fill; a closed row (n_total >= 0): in_first + in_len <= n_total and
+ *   m1 <= ceil(n_total L / M); an open row: m1 <= complete(in_first + in_len, open); every input sample of the recording
+ *   that an output of [m0, m1) depends on, k in [0, n_total) with |m M - k L| <= H, lies in the window (VSP_ERR_SHAPE).
+ * No sample outside the window and no sample at or behind n_total is read.  An output sample's value depends on (decoded x,
+ * m) alone -- one thread per sample, fp32 FMAs in ascending k over the table -- not on the window, the tile or the batch:
+ * outputs computed window by window are the bytes of the one-shot call (in_first = 0, in_len = n_total, m0 = 0,
+ * m1 = ceil(n_total L / M)).  Between windows a caller keeps the raw samples from
+ * vispeech_amd.output_stage.history_start(m1) on: at most vsp_output_history_samples(L, M, H) = floor(2 H / L) of them. */
+int vsp_input_rows(vsp_ctx* ctx, void* stream, int in_rate, int enc, int B, const vsp_input_row* rows);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

@@ -67,6 +67,17 @@ class VspConvertRow(C.Structure):
                 ("noise_scale", C.c_float)]
 
 
+class VspInputRow(C.Structure):
+    """``vsp_input_row``: a window ``[in_first, in_first + in_len)`` of one recording at ``in`` (device pointer, raw samples
+    in the call's encoding), the recording's length ``n_total`` (-1 while it is open), and the output samples ``[m0, m1)`` to
+    write to ``out`` (device pointer, float32), zeros behind them up to ``out_fill``."""
+    _fields_ = [("in_", C.c_void_p), ("in_first", C.c_int64), ("in_len", C.c_int64), ("n_total", C.c_int64),
+                ("out", C.c_void_p), ("m0", C.c_int64), ("m1", C.c_int64), ("out_fill", C.c_int64)]
+
+
+IN_F32, IN_S16, IN_ULAW, IN_ALAW = 0, 1, 2, 3                        # VSP_IN_* (vsp_input_rows)
+INPUT_RATES_MAX = 8
+
 GIVEN_DURATION, GIVEN_PITCH, GIVEN_ENERGY = 1, 2, 4                  # VSP_GIVEN_* (vsp_set_row_controls)
 
 STREAM_ROWS_MAX = 64
@@ -170,6 +181,11 @@ SIGNATURES = {
     "vsp_resample_out_len": (_I64, [_I64, _I, _I]),
     "vsp_output_configure": (_I, [_P, _I, _I, _I, C.c_double, C.c_double]),
     "vsp_output_chunk": (_I, [_P, _P, _I, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I]),
+    "vsp_input_plan": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "vsp_input_filter": (_I, [_I, _I, _I, C.c_double, C.c_double, _P]),
+    "vsp_input_decode_table": (_I, [_I, _P]),
+    "vsp_input_configure": (_I, [_P, _I, _I, _I, C.c_double, C.c_double]),
+    "vsp_input_rows": (_I, [_P, _P, _I, _I, _I, C.POINTER(VspInputRow)]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -88,6 +88,7 @@ int vsp_destroy(vsp_ctx* ctx) {
   for (auto st : ctx->side) if (st) (void)hipStreamDestroy(st);
   if (ctx->arena && ctx->arena_owned) (void)hipFree(ctx->arena);
   if (ctx->out_tab) (void)hipFree(ctx->out_tab);
+  for (auto& r : ctx->in_rates) if (r.tab) (void)hipFree(r.tab);
   delete ctx;
   return VSP_OK;
 }

@@ -441,6 +441,29 @@ __host__ __device__ inline StreamOutPlan stream_output_plan(int64_t x_first, int
 hipError_t launch_stream_output(const float* o_span, long o_bs, const StreamOutRows& rows, int B, const StreamOutFilter& f,
                                 int K, void* out, long out_stride, int pcm, hipStream_t s);
 
+// The input stage (input_stage.hip; include/vispeech_hip.h, vsp_input_rows): raw samples in an encoding VSP_IN_* at the
+// caller's rate -> float32 at the model's rate.  A row is a window [in_first, in_first + in_len) of one recording and the
+// output samples [m0, m1) to compute from it; out[m1 - m0 .. out_fill) is written as 0.  (n_total of vsp_input_row stays on
+// the host: the window ends at or before it, and nothing outside the window is read.)
+struct InputRow {            // 56 B
+  const void* in; int64_t in_first, in_len; float* out; int64_t m0, m1, out_fill;
+};
+struct InputRows { InputRow r[STREAM_ROWS_MAX]; };
+struct InputFilter { const float* tab; int L, M, J, P; };          // a configured input rate (tab [P][L])
+// The 16-bit linear value of a G.711 code byte, by the arithmetic of include/vispeech_hip.h (host table and kernel alike)
+__host__ __device__ inline int g711_ulaw_linear(int c) {
+  const int u = ~c & 0xFF, e = (u >> 4) & 7, q = u & 15, t = (((q << 3) + 0x84) << e) - 0x84;
+  return (u & 0x80) ? -t : t;
+}
+__host__ __device__ inline int g711_alaw_linear(int c) {
+  const int a = (c ^ 0x55) & 0xFF, e = (a >> 4) & 7, q = a & 15;
+  int t = (q << 4) + 8;
+  if (e >= 1) t = (t + 0x100) << (e - 1);
+  return (a & 0x80) ? t : -t;
+}
+// Checked before the launch: 1 <= B <= STREAM_ROWS_MAX, enc one of VSP_IN_*, a table, aligned non-null pointers.  One launch.
+hipError_t launch_input_rows(const InputRows& rows, int B, const InputFilter& f, int enc, hipStream_t s);
+
 hipError_t launch_stft_frames(const float* audio, long a_bs, float* f, long f_bs, long f_cs, int B, int L, int n_fft,
                               int hop, int T, hipStream_t s);
 hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* spec, int B, int spec_ch, int T,

@@ -22,8 +22,11 @@
 #include <vector>
 
 #include "model.h"
+#include "resample_common.h"
 
 namespace {
+
+using namespace vsp::rs;
 
 constexpr int RS_TILE = 256;            // output samples (= threads) per block
 constexpr int RS_X_LDS_FLOATS = 12288;  // input staging area per block (48 KiB)
@@ -53,16 +56,6 @@ __device__ __forceinline__ int rs_pcm16(float y) {
   // service.pcm16: clip(rint(y * 32767.0f), -32768, 32767), product in fp32, round half to even
   const float r = rintf(y * 32767.0f);
   return (int)fminf(fmaxf(r, -32768.f), 32767.f);
-}
-
-// One output sample from global memory: acc = fmaf(tab[i][col], x[ks + i], acc), i = 0 .. P - 1 ascending; `sample(k)` is
-// input sample k of the utterance, 0 where it is not readable.  The LDS loops of resample_kernel run this very chain.
-template <class Sample>
-__device__ __forceinline__ float rs_one_output(const float* __restrict__ tcol, int L, int P, int64_t ks, Sample sample) {
-  float acc = 0.f;
-#pragma unroll 4
-  for (int i = 0; i < P; ++i) acc = fmaf(tcol[(size_t)i * L], sample(ks + i), acc);   // (loads in flight; the order stays)
-  return acc;
 }
 
 // Stores sample j of a row (float32, or PCM16 with even lanes storing packed pairs where the row allows it).  Every lane
@@ -219,50 +212,9 @@ __global__ __launch_bounds__(RS_TILE) void stream_output_kernel(const vsp::Strea
 }
 
 // ---------------------------------------------------------------------------------------------- host: plan and filter
-double bessel_i0(double x) {
-  const double q = x * x / 4.0;
-  double term = 1.0, sum = 1.0;
-  for (int k = 1; k < 500; ++k) {
-    term *= q / ((double)k * k);
-    sum += term;
-    if (term < sum * 1e-18) break;
-  }
-  return sum;
-}
+constexpr int RS_MAX_L = 320, RS_MAX_M = 441;   // what resample_kernel's staging covers
 
-struct Plan { int L = 0, M = 0, H = 0; };
-
-int make_plan(int in_rate, int out_rate, int zeros, Plan& p) {
-  if (in_rate <= 0 || out_rate <= 0 || zeros < 1) return VSP_ERR_ARG;
-  const int g = std::gcd(in_rate, out_rate);
-  p.L = out_rate / g;
-  p.M = in_rate / g;
-  if (p.L > 320 || p.M > 441 || zeros > 64) return VSP_ERR_UNSUPPORTED;
-  p.H = (p.L == 1 && p.M == 1) ? 0 : zeros * std::max(p.L, p.M);    // L = M = 1: the pass-through, one unit tap
-  return VSP_OK;
-}
-
-// h[n], n = -H .. H, in double precision (numpy's sinc and kaiser conventions)
-void make_filter(const Plan& p, int zeros, double beta, double rolloff, std::vector<double>& h) {
-  const int H = p.H;
-  h.assign((size_t)2 * H + 1, 0.0);
-  if (H == 0) { h[0] = 1.0; return; }
-  const double fc = rolloff / std::max(p.L, p.M);
-  const double i0b = bessel_i0(beta);
-  const double pi = 3.14159265358979323846;
-  for (int n = -H; n <= H; ++n) {
-    const double r = (double)n / H;
-    const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
-    const double a = pi * fc * n;
-    const double s = n == 0 ? 1.0 : std::sin(a) / a;
-    h[(size_t)(n + H)] = p.L * fc * s * w;
-  }
-}
-
-double default_rolloff(int zeros) { return 1.0 - 3.065 / zeros; }
-
-inline int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+int make_plan(int in_rate, int out_rate, int zeros, Plan& p) { return vsp::rs::make_plan(in_rate, out_rate, zeros, RS_MAX_L, RS_MAX_M, p); }
 
 }  // namespace
 
@@ -363,16 +315,9 @@ int vsp_output_configure(vsp_ctx* ctx, int in_rate, int out_rate, int zeros, dou
   std::vector<double> h;
   make_filter(p, zeros, beta, rolloff, h);
   const int L = p.L, M = p.M, H = p.H;
-  const int J = H / L;
-  const int P = J + (H + L - 1) / L + 1;
-  std::vector<float> tab((size_t)P * L, 0.f);
-  for (int c = 0; c < L; ++c) {
-    const int64_t ph = ((int64_t)c * M) % L;
-    for (int i = 0; i < P; ++i) {
-      const int64_t t = ph + (int64_t)(J - i) * L;
-      if (t >= -H && t <= H) tab[(size_t)i * L + c] = (float)h[(size_t)(t + H)];
-    }
-  }
+  int J, P;
+  std::vector<float> tab;
+  make_table(p, h, J, P, tab);
   void* d = nullptr;
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = hipMalloc(&d, tab.size() * sizeof(float));

@@ -975,6 +975,121 @@ class Engine:
         nv = None if n_valid is None else _dev_i64(n_valid, self.device)
         return output_stage.stream(self, chunks, nv, pcm)
 
+    # ------------------------------------------------------------------ input stage
+    def configure_input(self, rate: int, zeros: int = 32, beta: float = 9.62, rolloff: Optional[float] = None,
+                        model_rate: Optional[int] = None) -> None:
+        """``vsp_input_configure``: build and upload the filter that takes recordings from ``rate`` to ``model_rate`` (the
+        model's sampling rate).  Idempotent per rate: the same arguments again do nothing, others replace the rate's table;
+        a context holds up to 8 rates.  ``rate`` equal to the model's is the pass-through (decoding only).  Allocates:
+        call it outside the request path."""
+        from . import input_stage
+        rate = int(rate)
+        model_rate = int(self.dims.sampling_rate if model_rate is None else model_rate)
+        key = (model_rate, int(zeros), float(beta), None if rolloff is None else float(rolloff))
+        if self._input is None:
+            self._input = {}
+        if rate in self._input and self._input[rate][0] == key:
+            return
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_input_configure(self.ctx, rate, model_rate, int(zeros), float(beta),
+                                              0.0 if rolloff is None else float(rolloff))
+        _lib.check(rc, self.ctx, "vsp_input_configure")
+        self._input[rate] = (key, input_stage.plan(rate, model_rate, int(zeros)))
+
+    def drop_input(self, rate: int) -> None:
+        """Frees the table of an input rate (``vsp_input_configure`` with model_rate 0)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vsp_input_configure(self.ctx, int(rate), 0, 0, 0.0, 0.0), self.ctx, "vsp_input_configure")
+        (self._input or {}).pop(int(rate), None)
+
+    _input = None             # rate -> (configuration, (L, M, H)) of the configured input rates
+
+    @property
+    def input_rates(self):
+        """The configured input rates."""
+        return tuple(self._input or ())
+
+    def input_plan(self, rate: int):
+        """(L, M, H) of a configured input rate."""
+        if not self._input or int(rate) not in self._input:
+            raise RuntimeError(f"input rate {rate} Hz is not configured: call Engine.configure_input({rate}) first")
+        return self._input[int(rate)][1]
+
+    def _raw(self, raw, enc: int) -> torch.Tensor:
+        """Raw samples (bytes, numpy or torch) as a device tensor of the encoding's own dtype."""
+        from . import input_stage
+        dt = {0: torch.float32, 1: torch.int16, 2: torch.uint8, 3: torch.uint8}[enc]
+        if torch.is_tensor(raw):
+            if raw.dtype != dt and not (enc == 0 and raw.dtype.is_floating_point):
+                raise ValueError(f"encoding {enc} wants {dt} samples, got {raw.dtype}")
+            return raw.to(device=self.device, dtype=dt)
+        return torch.from_numpy(input_stage.as_raw(raw, enc)).to(self.device)
+
+    def input_rows(self, rows, rate: int, enc: int = 0, outs=None):
+        """``vsp_input_rows``: rows of ``(raw, in_first, n_total, m0, m1)`` in ONE call per 64 rows -- ``raw`` a 1-D tensor of
+        the encoding's dtype that holds input samples ``[in_first, in_first + len(raw))`` of a recording of ``n_total`` samples
+        (-1 while it is still open), ``[m0, m1)`` the output samples wanted.  ``outs``: per row a 1-D float32 device tensor that
+        receives them (all of it is written: zeros behind ``m1 - m0``); None: one is allocated.  Returns the rows' results,
+        each ``[m1 - m0]`` float32."""
+        from . import input_stage
+        enc = input_stage.encoding(enc)
+        L, M, H = self.input_plan(rate)
+        rows = list(rows)
+        B = len(rows)
+        if B == 0:
+            return []
+        raws = [self._raw(r[0], enc).reshape(-1) for r in rows]
+        counts = [int(r[4]) - int(r[3]) for r in rows]
+        if any(c < 0 for c in counts):
+            raise ValueError("a row needs m0 <= m1")
+        if outs is None:
+            offs = np.concatenate([[0], np.cumsum([(c + 3) // 4 * 4 for c in counts])])
+            flat = self._f(max(int(offs[-1]), 1))
+            outs = [flat[int(o):int(o) + c] for o, c in zip(offs[:-1], counts)]
+        elif len(outs) != B:
+            raise ValueError(f"outs must have {B} entries")
+        arr = (_lib.VspInputRow * B)()
+        for r, raw, (_, first, n_total, m0, m1), out, c in zip(arr, raws, rows, outs, counts):
+            if not raw.is_contiguous():
+                raise ValueError("a row's raw samples must be contiguous")
+            if (out.dtype != torch.float32 or out.device != self.device or out.dim() != 1 or out.numel() < c
+                    or (out.numel() > 1 and out.stride(0) != 1)):
+                raise ValueError("a row's out must be a contiguous 1-D float32 tensor on the engine's device of at least m1 - m0")
+            r.in_ = raw.data_ptr() if raw.numel() else None
+            r.in_first, r.in_len, r.n_total = int(first), raw.numel(), int(n_total)
+            r.out = out.data_ptr() if out.numel() else None
+            r.m0, r.m1, r.out_fill = int(m0), int(m1), out.numel()
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, _lib.STREAM_ROWS_MAX):
+                n = min(_lib.STREAM_ROWS_MAX, B - b0)
+                sub = C.cast(C.byref(arr, b0 * C.sizeof(_lib.VspInputRow)), C.POINTER(_lib.VspInputRow))
+                _lib.check(self.lib.vsp_input_rows(self.ctx, self._stream(), int(rate), enc, n, sub), self.ctx, "vsp_input_rows")
+        return [o[:c] for o, c in zip(outs, counts)]
+
+    def input_batch(self, raw, n_in, rate: int, enc: int = 0):
+        """Whole recordings of one (rate, encoding): ``raw`` [B, stride] (bytes are not accepted here: a 2-D array or tensor
+        of the encoding's dtype), row b the recording ``raw[b, :n_in[b]]`` -- what lies behind is never read.  Returns
+        ``(audio [B, ceil(max n L / M)] float32, n_out)``: row b holds its ``n_out[b] = ceil(n_in[b] L / M)`` samples at the
+        model's rate and exact zeros behind.  The lengths are computed on the host; nothing is read back."""
+        from . import input_stage
+        enc = input_stage.encoding(enc)
+        L, M, _ = self.input_plan(rate)
+        a = self._raw(raw, enc)
+        if a.dim() == 1:
+            a = a.reshape(1, -1)
+        if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+            raise ValueError("raw must be [B, stride] with contiguous rows")
+        B, stride = a.shape
+        n_host = [int(x) for x in (n_in.tolist() if hasattr(n_in, "tolist") else n_in)]
+        if len(n_host) != B or any(x < 0 or x > stride for x in n_host):
+            raise ValueError(f"n_in must have {B} entries with 0 <= n_in[b] <= raw.shape[1]")
+        n_out = [input_stage.out_len(x, L, M) for x in n_host]
+        audio = self._f(B, max(n_out) if B else 0)
+        if B and audio.shape[1]:
+            self.input_rows([(a[b, :n], 0, n, 0, m) for b, (n, m) in enumerate(zip(n_host, n_out))], rate, enc,
+                            outs=[audio[b] for b in range(B)])
+        return audio, n_out
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

@@ -161,7 +161,7 @@ class SynthesizerTrn:
 
     @torch.no_grad()
     def convert_audio(self, audio, n_samples, sid_src, sid_tgt, *, noise: Optional[torch.Tensor] = None, noise_seed=None,
-                      noise_scale: float = 1.0):
+                      noise_scale: float = 1.0, sample_rate: Optional[int] = None, encoding=None):
         """``voice_conversion`` from audio, for a batch of recordings of different lengths: ``audio`` [B, L] at the model's
         rate, row b the recording ``audio[b, :n_samples[b]]`` (what lies behind is never read).  Every recording is
         converted as the reference converts it alone -- ``voice_conversion`` on ``spectrogram_torch`` of that recording,
@@ -169,13 +169,22 @@ class SynthesizerTrn:
         ``noise`` [B, inter, T_max] replaces the posterior's ``torch.randn_like`` (row b uses its first ``T_b`` columns);
         without it ``noise_seed`` is a list of B ints, one Philox key per recording (a plain int raises ``ValueError``, as in
         ``infer(isolated=True)``).  ``noise_scale`` multiplies that noise: 1.0 is the reference, 0 needs neither noise nor
-        seeds.  Returns ``(o_hat, y_mask, (z, z_p, z_hat))`` like ``voice_conversion``."""
+        seeds.  Returns ``(o_hat, y_mask, (z, z_p, z_hat))`` like ``voice_conversion``.
+        ``sample_rate`` / ``encoding`` (``vispeech_amd.input_stage``: float32, PCM16, mu-law or A-law, by name or number):
+        ``audio`` [B, L] is then raw -- int16 or uint8 for the integer encodings -- at ``sample_rate`` (None: the model's),
+        ``n_samples`` counts INPUT samples, and the batch goes through the input stage (``Engine.input_batch``) first; the
+        rest is the path above on its result.  Without the two keywords nothing changes."""
         eng = self._engine
         if not eng.ready:
             raise RuntimeError("weights not loaded: call load_state_dict first")
         assert self.n_speakers > 0, "n_speakers have to be larger than 0."      # models.py:725
         if not eng.has_voice_conversion:
             raise RuntimeError("convert_audio needs the enc_q.* tensors: the loaded state_dict had none")
+        if sample_rate is not None or encoding is not None:
+            rate = int(self.dims.sampling_rate if sample_rate is None else sample_rate)
+            if rate not in eng.input_rates:
+                eng.configure_input(rate)
+            audio, n_samples = eng.input_batch(audio, n_samples, rate, 0 if encoding is None else encoding)
         r = eng.convert(audio, n_samples, sid_src, sid_tgt, noise=noise, noise_seed=noise_seed, noise_scale=noise_scale)
         return r["o_hat"], r["y_mask"].to(torch.float32), (r["z"], r["z_p"], r["z_hat"])
 

@@ -13,15 +13,31 @@ import numpy as np
 from ._pcm import _row_pcm16
 
 
+def _input_format(sample_rate, encoding, model_rate: int):
+    """``(rate, VSP_IN_*)`` of a request that names a sample rate or an encoding, None of one that names neither (its audio
+    is float32 at the model's rate and takes the path it always took)."""
+    if sample_rate is None and encoding is None:
+        return None
+    from .. import input_stage
+    return (int(model_rate if sample_rate is None else sample_rate), input_stage.encoding(encoding))
+
+
 class _Conversion:
     """A conversion request of the batching services (``submit_conversion``): a recording at the model's rate, the speaker
     it was spoken by and the speaker to convert it to.  To the vocoder it is a row like any other -- a latent, a speaker
-    vector and a length -- so it shares generator calls and ticks with text requests."""
+    vector and a length -- so it shares generator calls and ticks with text requests.  ``fmt`` = ``(rate, encoding)``: the
+    recording is ``raw`` in that format (``audio`` None) until admission has run it through the input stage."""
 
-    def __init__(self, audio, sid_src: int, sid_tgt: int, noise_scale):
-        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
-        if a.ndim != 1:
-            raise ValueError("audio must be a 1-D float32 array at the model's sampling rate")
+    def __init__(self, audio, sid_src: int, sid_tgt: int, noise_scale, fmt=None):
+        self.fmt, self.raw = fmt, None
+        if fmt is None:
+            a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
+        else:
+            from .. import input_stage
+            a, self.raw = None, input_stage.as_raw(audio, fmt[1])
+        if (self.raw if a is None else a).ndim != 1:
+            raise ValueError("audio must be a 1-D array: float32 at the model's sampling rate, or raw samples in the "
+                             "encoding the request names")
         self.audio, self.sid_src, self.sid_tgt = a, int(sid_src), int(sid_tgt)
         self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)      # (1.0: the reference's posterior)
 
@@ -97,21 +113,30 @@ def _text_latents(eng, collate, reqs, noise_scale: float):
     return [(z[b], enc["g"][b], int(frames[b])) if int(frames[b]) > 0 else (None, None, 0) for b in range(len(reqs))]
 
 
-def _convert_latents(eng, reqs):
+def _convert_latents(eng, reqs, model_rate=None):
     """The conversion requests of one batch or admitted group through ``Engine.convert_latent``: ONE call (one per
     distinct ``noise_scale``, which is an argument of the call, where the requests name several).  Returns per request
     ``(z_hat row, g row, frames)``; a recording too short for a frame gives ``(None, None, 0)``.  The frame counts are
     host arithmetic (``frames_host``): nothing is read back from the device."""
     jobs = [r.row for r in reqs]
     out = [(None, None, 0)] * len(jobs)
+    raw = [j for j in jobs if j.fmt is not None]
+    if raw:
+        _through_input_stage(eng, raw, model_rate)
     for scale in sorted({j.noise_scale for j in jobs}):
-        idx = [i for i, j in enumerate(jobs) if j.noise_scale == scale and eng.convert_frames(j.audio.size) > 0]
+        idx = [i for i, j in enumerate(jobs) if j.noise_scale == scale and eng.convert_frames(len(j.audio)) > 0]
         if not idx:
             continue
-        n = [jobs[i].audio.size for i in idx]
-        audio = np.zeros((len(idx), max(n)), dtype=np.float32)
-        for k, i in enumerate(idx):
-            audio[k, : n[k]] = jobs[i].audio
+        n = [len(jobs[i].audio) for i in idx]
+        if raw:                                  # (rows from the input stage are on the device: the batch is built there)
+            import torch
+            audio = torch.zeros((len(idx), max(n)), dtype=torch.float32, device=eng.device)
+            for k, i in enumerate(idx):
+                audio[k, : n[k]] = torch.as_tensor(jobs[i].audio)
+        else:
+            audio = np.zeros((len(idx), max(n)), dtype=np.float32)
+            for k, i in enumerate(idx):
+                audio[k, : n[k]] = jobs[i].audio
         r = eng.convert_latent(audio, n, [jobs[i].sid_src for i in idx], [jobs[i].sid_tgt for i in idx], None,
                                noise_seed=[reqs[i].seed for i in idx], noise_scale=scale)
         for k, i in enumerate(idx):
@@ -119,7 +144,26 @@ def _convert_latents(eng, reqs):
     return out
 
 
-def latents(eng, collate, requests, noise_scale: float):
+def _through_input_stage(eng, jobs, model_rate=None) -> None:
+    """The raw recordings of a group to float32 at the model's rate: ONE ``Engine.input_batch`` call per distinct
+    ``(rate, encoding)``; each job's ``audio`` becomes its row of the result (on the device, its own length)."""
+    for fmt in sorted({j.fmt for j in jobs}):
+        group = [j for j in jobs if j.fmt == fmt and j.audio is None]
+        if not group:
+            continue
+        rate, enc = fmt
+        if rate not in eng.input_rates:
+            eng.configure_input(rate, model_rate=model_rate)      # (allocates: configure the rates ahead where that matters)
+        n = [j.raw.size for j in group]
+        batch = np.zeros((len(group), max(max(n), 1)), dtype=group[0].raw.dtype)
+        for k, j in enumerate(group):
+            batch[k, : n[k]] = j.raw
+        audio, n_out = eng.input_batch(batch, n, rate, enc)
+        for k, j in enumerate(group):
+            j.audio = audio[k, : n_out[k]]
+
+
+def latents(eng, collate, requests, noise_scale: float, model_rate=None):
     """Per request ``(z row [inter, T], g row, frames)``, in request order: the text rows of the group through
     ``_text_latents``, then its conversions through ``_convert_latents``."""
     text = [i for i, r in enumerate(requests) if not r.is_conversion]
@@ -128,7 +172,7 @@ def latents(eng, collate, requests, noise_scale: float):
     if text:
         done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale))
     if conv:
-        done += zip(conv, _convert_latents(eng, [requests[i] for i in conv]))
+        done += zip(conv, _convert_latents(eng, [requests[i] for i in conv], model_rate))
     out = [None] * len(requests)
     for i, lat in done:
         out[i] = lat
@@ -159,6 +203,7 @@ class BatchingSynthesisService:
         self.net, self.max_batch, self.max_wait_s = net, int(max_batch), float(max_wait_s)
         self.noise_scale = float(noise_scale)
         self.output_rate = None if output_rate is None else int(output_rate)
+        self.sampling_rate = int(sampling_rate)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -174,13 +219,17 @@ class BatchingSynthesisService:
         The future's result is the request's PCM16 samples (numpy int16, valid part only)."""
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
 
-    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *,
-                          noise_scale=None) -> "concurrent.futures.Future":
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
+                          sample_rate: Optional[int] = None, encoding=None) -> "concurrent.futures.Future":
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
         PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
         ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
-        ``noise_scale``); ``noise_seed`` keys that noise."""
-        return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale), noise_seed))
+        ``noise_scale``); ``noise_seed`` keys that noise.
+        ``sample_rate`` / ``encoding`` (``vispeech_amd.input_stage``): ``audio`` is raw -- an array of the encoding's dtype or
+        ``bytes`` -- at that rate; the batch's raw recordings go through the input stage on the GPU, one call per distinct
+        (rate, encoding), before the one ``convert_latent``."""
+        fmt = _input_format(sample_rate, encoding, self.sampling_rate)
+        return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed))
 
     def _enqueue(self, req: _Request) -> "concurrent.futures.Future":
         req.future = concurrent.futures.Future()
@@ -247,7 +296,7 @@ class BatchingSynthesisService:
         ``generator_ragged`` call, then the output stage as in ``_synthesize``."""
         import torch
         net, eng = self.net, self.net._engine
-        lat = latents(eng, self._collate, reqs, self.noise_scale)
+        lat = latents(eng, self._collate, reqs, self.noise_scale, self.sampling_rate)
         live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
         pcms = [np.zeros(0, dtype="<i2") for _ in reqs]
         if not live:

@@ -9,9 +9,9 @@ from typing import Optional
 
 import numpy as np
 
-from .. import output_stage
+from .. import input_stage, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
-from .batching import _Conversion, _Request, _collate_from, latents
+from .batching import _Conversion, _Request, _collate_from, _input_format, latents
 
 
 class _RowStream:
@@ -72,18 +72,25 @@ class LiveConversion(_RowStream):
     being made and iterates over the converted PCM16 ``bytes`` -- exact chunks, what the finished recording converted
     alone gives.  ``feed`` and ``end`` may be called from any thread; ``close()`` abandons the session."""
 
-    def __init__(self, cv: "threading.Condition"):
+    def __init__(self, cv: "threading.Condition", fmt=None):
         super().__init__()
         self._cv = cv                 # the service's condition: guards _fed / _ended / _wake, wakes the worker
+        self._fmt = fmt               # (rate, encoding) of what is fed; None: float32 at the model's rate
         self._fed: list = []          # pieces the worker has not taken yet
         self._ended = False
         self._wake = True             # something changed since the worker last looked at this session
 
     def feed(self, samples) -> None:
-        """The next samples of the recording: 1-D float32 at the model's rate, a piece of any size (copied)."""
-        a = np.array(samples, dtype=np.float32, copy=True)
+        """The next samples of the recording: 1-D float32 at the model's rate, a piece of any size (copied) -- or, for a
+        session opened with a ``sample_rate`` / ``encoding``, raw samples in that format (an array of the encoding's dtype or
+        ``bytes``)."""
+        if self._fmt is None:
+            a = np.array(samples, dtype=np.float32, copy=True)
+        else:
+            a = np.array(input_stage.as_raw(samples, self._fmt[1]), copy=True)
         if a.ndim != 1:
-            raise ValueError("samples must be a 1-D float32 array at the model's sampling rate")
+            raise ValueError("samples must be a 1-D array: float32 at the model's sampling rate, or raw samples in the "
+                             "session's encoding")
         with self._cv:
             if self._ended:
                 raise RuntimeError("the recording has ended")
@@ -114,6 +121,9 @@ class _LiveRequest(_StreamRequest):
     def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale):
         super().__init__(None, seed)
         self.stream = stream
+        self.fmt = stream._fmt        # (rate, encoding) of the feed: its pieces go through ``input`` before they reach ``buf``
+        self.input = None             # the session's ``input_stage.Stream``, from its first piece on
+        self.input_ended = False      # the input stage's tail has been flushed
         self.sid_src, self.sid_tgt = int(sid_src), int(sid_tgt)
         self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)
         self.buf = None
@@ -172,6 +182,7 @@ class StreamingBatchService:
         self.noise_scale = float(noise_scale)
         self.output_rate = None if output_rate is None else int(output_rate)
         self.fused_output = bool(fused_output)
+        self.sampling_rate = int(sampling_rate)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self.stats = {"ticks": 0, "rows_per_tick": [], "groups": 0}
@@ -194,17 +205,27 @@ class StreamingBatchService:
         request's PCM16 ``bytes``, one piece per tick the request takes part in."""
         return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
 
-    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> _RowStream:
+    def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
+                          sample_rate: Optional[int] = None, encoding=None) -> _RowStream:
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
         the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
         frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
-        NOT the service's text-to-speech ``noise_scale``)."""
-        return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale), noise_seed))
+        NOT the service's text-to-speech ``noise_scale``).  ``sample_rate`` / ``encoding``: ``audio`` is raw samples in that
+        format (an array of the encoding's dtype or ``bytes``); admission runs the group's raw recordings through the
+        input stage, one call per distinct (rate, encoding), before its one ``convert_latent``."""
+        fmt = _input_format(sample_rate, encoding, self.sampling_rate)
+        return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed))
 
-    def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None) -> LiveConversion:
+    def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
+                        sample_rate: Optional[int] = None, encoding=None) -> LiveConversion:
         """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
         ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
-        ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``)."""
+        ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``).
+        ``sample_rate`` / ``encoding``: ``feed`` takes raw pieces in that format; every tick the worker resamples what
+        arrived -- one ``Engine.input_rows`` call per distinct (rate, encoding) among the sessions with new audio -- and
+        appends the model-rate samples that are complete to the session's buffer; ``end()`` flushes the filter's tail.
+        Readiness is decided on those samples, so the session's delay grows by the filter's half length: ``zeros`` = 32
+        input periods (2 ms at 16 kHz)."""
         if self.fused_output:
             # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
             # filter's phase and its history must not see the shift
@@ -221,7 +242,10 @@ class StreamingBatchService:
             dims = self.net.dims
             hop, n_fft = dims.hop_length, 2 * (dims.spec_channels - 1)
             self._geometry = (hop, n_fft, (n_fft - hop) // 2, self.net._engine.generator_halo, schema.convert_halo_frames(dims))
-        return self._enqueue(_LiveRequest(LiveConversion(self._cv), sid_src, sid_tgt, noise_seed, noise_scale))
+        fmt = _input_format(sample_rate, encoding, self.sampling_rate)
+        if fmt is not None and fmt[0] not in self.net._engine.input_rates:
+            self.net._engine.configure_input(fmt[0], model_rate=self.sampling_rate)      # (allocates: here, not in a tick)
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale))
 
     def _enqueue(self, req: _StreamRequest) -> _RowStream:
         """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
@@ -312,12 +336,13 @@ class StreamingBatchService:
         hop, n_fft, _, G, H = self._geometry
         device = getattr(eng, "device", "cpu")
         ready, rows, gone = [], [], []
+        failed = self._live_input(taken, device)
         for r, pieces, ended, closed in taken:
-            if closed:                           # abandoned by its caller: the session leaves here
+            if closed or any(r is x for x in failed):   # abandoned by its caller, or its input stage failed: it leaves here
                 gone.append(r)
                 continue
             if pieces:
-                new = torch.as_tensor(np.concatenate(pieces)).to(device)
+                new = torch.as_tensor(np.concatenate(pieces)).to(device) if r.fmt is None else torch.cat(pieces)
                 r.buf = new if r.buf is None else torch.cat([r.buf, new])
                 r.n += int(new.numel())
             r.closed = ended
@@ -352,6 +377,39 @@ class StreamingBatchService:
             self._drop_live(gone)
         return ready
 
+    def _live_input(self, taken, device) -> list:
+        """The raw pieces of this tick's sessions through the input stage: ONE ``Engine.input_rows`` call per distinct
+        (rate, encoding) among the sessions with new audio or a tail to flush.  Replaces each such session's pieces in
+        ``taken`` by the model-rate samples they complete (device tensors); returns the sessions whose call failed."""
+        import torch
+        eng = self.net._engine
+        jobs = {}                                # (rate, encoding) -> [(index into taken, row)]
+        for i, (r, pieces, ended, closed) in enumerate(taken):
+            if r.fmt is None or closed:
+                continue
+            taken[i] = (r, [], ended, closed)
+            if r.input is None:
+                r.input = input_stage.Stream(eng, *r.fmt)
+            rows = []
+            if pieces:
+                rows.append(r.input.take(torch.as_tensor(np.concatenate(pieces)).to(device)))
+            if ended and not r.input_ended:      # the recording has ended: the filter's tail, before the session is closed
+                r.input_ended = True
+                rows.append(r.input.take_tail())
+            for row in rows:
+                if row is not None:              # (a piece too short to complete an output sample gives none)
+                    jobs.setdefault(r.fmt, []).append((i, row))
+        failed = []
+        for (rate, enc), job in sorted(jobs.items()):
+            try:
+                for (i, _), y in zip(job, eng.input_rows([row for _, row in job], rate, enc)):
+                    taken[i][1].append(y)
+            except Exception as e:               # these sessions fail; the others and the service live on
+                for r in {id(taken[i][0]): taken[i][0] for i, _ in job}.values():
+                    r.stream._q.put(e)
+                    failed.append(r)
+        return failed
+
     def _after_live_tick(self, r: "_LiveRequest") -> None:
         """A live session after its tick: the end of the stream, or the samples its next window no longer reads dropped."""
         hop, _, pad, G, H = self._geometry
@@ -385,7 +443,7 @@ class StreamingBatchService:
         self.stats["groups"] += 1
         try:
             eng = self.net._engine
-            for r, (z, g, L) in zip(group, latents(eng, self._collate, group, self.noise_scale)):
+            for r, (z, g, L) in zip(group, latents(eng, self._collate, group, self.noise_scale, self.sampling_rate)):
                 r.z, r.g, r.L, r.pos = z, g, L, 0
             for r in group:
                 if r.L <= 0:
