@@ -791,6 +791,67 @@ typedef struct vsp_input_row {
  * vispeech_amd.output_stage.history_start(m1) on: at most vsp_output_history_samples(L, M, H) = floor(2 H / L) of them. */
 int vsp_input_rows(vsp_ctx* ctx, void* stream, int in_rate, int enc, int B, const vsp_input_row* rows);
 
+/* ---- output rows (round 17, ABI 7, additive) ------------------------------------------------ */
+/* The output-side counterpart of vsp_input_rows: up to 64 rows per call, every row with its OWN output rate and encoding,
+ * one launch (two when the descriptors exceed the kernel-argument space; the caller sees no difference).  The rates live in
+ * a set of up to VSP_OUTPUT_RATES_MAX tables BESIDE the single stage of vsp_output_configure, which these calls neither read
+ * nor change: the same filter formula, limits (L <= 320, M <= 441, 1 <= zeros <= 64), defaults (zeros == 0: 32;
+ * rolloff <= 0: 1 - 3.065 / zeros) and table layout.
+ *
+ * A row is a piece [x_first, x_first + n) of one utterance at the model's rate; with (L, M, H) of its rate and the rule
+ * published above for vsp_generator_stream_rows_output,
+ *   m0 = complete(x_first, 0)          m1 = complete(x_first + n, ended)
+ *   k0 = min(x_first, start(m0))       k1 = min(x_first + n, start(m1))
+ * the call writes output samples [m0, m1) to out[0 .. m1 - m0), the encoding's silence to out[m1 - m0 .. out_fill), and input
+ * samples [k1, x_first + n) to hist_out[0 ..); it reads input samples [k0, x_first) from hist_in.  Every call delivers
+ * everything its input completes: no counter travels between calls.  Both histories hold K = vsp_output_history_samples(L,
+ * M, H) floats; a request owns two and alternates.  The one-shot call is x_first = 0, n = total, ended = 1 with both
+ * histories NULL (a row with ended == 1 may leave hist_out NULL: nothing follows it).  vsp_output_rows_plan is the host
+ * arithmetic (any output may be NULL; VSP_ERR_ARG for L, M < 1, H, x_first, n < 0).
+ *
+ * Values.  Element j of a VSP_OUT_F32 row is, bit for bit, sample m0 + j of what vsp_output_chunk returns for the same
+ * utterance when the single stage is configured with the same (model_rate, out_rate, zeros, beta, rolloff): the same table,
+ * fp32 FMAs in ascending k.  VSP_OUT_S16 is the PCM16 rule of vsp_output_chunk on that value, s.  VSP_OUT_ULAW / VSP_OUT_ALAW
+ * are the truncating G.711 compressors of s -- the inverses of the expanders published for VSP_IN_ULAW / VSP_IN_ALAW
+ * (encode(decode(c)) == c for every code, except that mu-law's negative zero 0x7F comes back as 0xFF):
+ *   mu-law  neg = s < 0;  mag = min(|s|, 32635) + 0x84;  e = floor(log2(mag)) - 7;  q = (mag >> (e + 3)) & 15;
+ *           c = ~((neg ? 0x80 : 0) | e << 4 | q) & 0xFF
+ *   A-law   neg = s < 0;  mag = (neg ? ~s : s) >> 3;  e = mag ? max(floor(log2(mag)) - 4, 0) : 0;
+ *           q = e == 0 ? (mag >> 1) & 15 : (mag >> e) & 15;  c = ((neg ? 0 : 0x80) | e << 4 | q) ^ 0x55
+ * Silence, the code of 0: 0.0f, 0, 0xFF, 0xD5.  A value depends on (samples, m, rate, enc) alone -- not on the split, the
+ * tile, the other rows of the call or their formats.  vsp_output_encode is the compressor on the host (enc VSP_OUT_ULAW or
+ * VSP_OUT_ALAW, n PCM16 values -> n code bytes; VSP_ERR_ARG otherwise). */
+#define VSP_OUT_F32 0        /* the numbers of VSP_IN_* */
+#define VSP_OUT_S16 1
+#define VSP_OUT_ULAW 2
+#define VSP_OUT_ALAW 3
+#define VSP_OUTPUT_RATES_MAX 8
+int vsp_output_encode(int enc, const int16_t* pcm, int64_t n, uint8_t* codes);
+/* Builds the filter of (model_rate -> out_rate) and uploads its table into the context's set of output rates.  Configuring
+ * a rate again replaces its table; model_rate == 0 drops out_rate (VSP_OK also when it was not configured); a ninth rate:
+ * VSP_ERR_STATE.  May allocate and synchronise; the tables are freed by vsp_destroy. */
+int vsp_output_rate_configure(vsp_ctx* ctx, int model_rate, int out_rate, int zeros, double beta, double rolloff);
+typedef struct vsp_output_row {      /* HOST memory, read before the call returns */
+  const float* x;                    /* DEVICE: the row's NEW input samples [x_first, x_first + n) at the model's rate */
+  int64_t x_first, n;                /* n == 0 is legal only with ended == 1 (flush the tail) */
+  int32_t ended;                     /* 1: the utterance ends at x_first + n */
+  int32_t out_rate, enc;             /* a configured rate, one of VSP_OUT_* */
+  const float* hist_in;              /* DEVICE: samples [k0, x_first) as the row's previous call wrote them */
+  float* hist_out;                   /* DEVICE: receives samples [k1, x_first + n); differs from hist_in */
+  void* out;                         /* DEVICE: receives output samples [m0, m1) as elements of `enc` */
+  int64_t out_fill;                  /* >= m1 - m0 elements; out[m1 - m0 .. out_fill) is written as the encoding's silence */
+} vsp_output_row;
+int vsp_output_rows_plan(int L, int M, int H, int64_t x_first, int64_t n, int ended, int64_t* m0, int64_t* m1, int64_t* k0,
+                         int64_t* k1);
+/* 1 <= B <= 64.  No allocation, no synchronisation, caller's stream.  Decided on the host before anything is launched:
+ *   rows non-NULL, 1 <= B <= 64, enc one of VSP_OUT_*, n >= 0, n > 0 unless ended, 0 <= x_first, out_fill >= 0 (VSP_ERR_ARG);
+ *   the row's rate is configured (VSP_ERR_STATE);
+ *   x non-NULL (unless n == 0), out non-NULL (unless out_fill == 0), hist_in non-NULL while x_first > k0, hist_out non-NULL
+ *   while x_first + n > k1 and the row has not ended, every pointer aligned to its element, hist_in != hist_out
+ *   (VSP_ERR_ARG);  m1 - m0 <= out_fill (VSP_ERR_SHAPE).
+ * No sample outside a row's two segments is read; a refused call writes nothing. */
+int vsp_output_rows(vsp_ctx* ctx, void* stream, int B, const vsp_output_row* rows);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

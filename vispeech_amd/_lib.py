@@ -78,6 +78,19 @@ class VspInputRow(C.Structure):
 IN_F32, IN_S16, IN_ULAW, IN_ALAW = 0, 1, 2, 3                        # VSP_IN_* (vsp_input_rows)
 INPUT_RATES_MAX = 8
 
+
+class VspOutputRow(C.Structure):
+    """``vsp_output_row``: the new input samples ``[x_first, x_first + n)`` of one utterance at ``x`` (device pointer,
+    float32 at the model's rate), whether it ends there, the row's own output rate and encoding (``VSP_OUT_*``), its two
+    history buffers and where its output samples go (``out_fill`` elements of the encoding, silence behind the samples)."""
+    _fields_ = [("x", C.c_void_p), ("x_first", C.c_int64), ("n", C.c_int64), ("ended", C.c_int32),
+                ("out_rate", C.c_int32), ("enc", C.c_int32), ("hist_in", C.c_void_p), ("hist_out", C.c_void_p),
+                ("out", C.c_void_p), ("out_fill", C.c_int64)]
+
+
+OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
+OUTPUT_RATES_MAX = 8
+
 GIVEN_DURATION, GIVEN_PITCH, GIVEN_ENERGY = 1, 2, 4                  # VSP_GIVEN_* (vsp_set_row_controls)
 
 STREAM_ROWS_MAX = 64
@@ -186,6 +199,11 @@ SIGNATURES = {
     "vsp_input_decode_table": (_I, [_I, _P]),
     "vsp_input_configure": (_I, [_P, _I, _I, _I, C.c_double, C.c_double]),
     "vsp_input_rows": (_I, [_P, _P, _I, _I, _I, C.POINTER(VspInputRow)]),
+    "vsp_output_encode": (_I, [_I, _P, _I64, _P]),
+    "vsp_output_rate_configure": (_I, [_P, _I, _I, _I, C.c_double, C.c_double]),
+    "vsp_output_rows_plan": (_I, [_I, _I, _I, _I64, _I64, _I, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
+                                  C.POINTER(_I64)]),
+    "vsp_output_rows": (_I, [_P, _P, _I, C.POINTER(VspOutputRow)]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

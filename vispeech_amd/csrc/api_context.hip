@@ -89,6 +89,7 @@ int vsp_destroy(vsp_ctx* ctx) {
   if (ctx->arena && ctx->arena_owned) (void)hipFree(ctx->arena);
   if (ctx->out_tab) (void)hipFree(ctx->out_tab);
   for (auto& r : ctx->in_rates) if (r.tab) (void)hipFree(r.tab);
+  for (auto& r : ctx->out_rates) if (r.tab) (void)hipFree(r.tab);
   delete ctx;
   return VSP_OK;
 }

@@ -464,6 +464,38 @@ __host__ __device__ inline int g711_alaw_linear(int c) {
 // Checked before the launch: 1 <= B <= STREAM_ROWS_MAX, enc one of VSP_IN_*, a table, aligned non-null pointers.  One launch.
 hipError_t launch_input_rows(const InputRows& rows, int B, const InputFilter& f, int enc, hipStream_t s);
 
+// Output rows (output_rows.hip; include/vispeech_hip.h, vsp_output_rows): the ragged output stage with the row's rate AND
+// encoding inside its descriptor.  m0, m1, k0, k1 are stream_output_plan of (x_first, n, ended) under the row's filter,
+// computed on the host; `filt` indexes the launch's filter entries.
+struct OutRow {              // 96 B
+  const float* x; const float* hist_in; float* hist_out; void* out;
+  int64_t x_first, n, m0, m1, k0, k1, out_fill;
+  int enc, filt;
+};
+// a configured output rate (tab [P][L]) and how output_rows_kernel stages it: `pass` taps per staging pass, mode 0: the
+// tile's span in LDS, mode 2: samples from global memory
+struct OutFilter { const float* tab; int L, M, H, J, P, pass, mode, xs_words; };   // 40 B
+constexpr int OUT_FILTERS_MAX = 8;                                  // = VSP_OUTPUT_RATES_MAX
+constexpr int OUT_ROWS_PER_LAUNCH = (4096 - OUT_FILTERS_MAX * 40 - 16) / 96;     // 39: what 4 KiB of kernel arguments hold
+struct OutRowsArgs { OutRow r[OUT_ROWS_PER_LAUNCH]; OutFilter f[OUT_FILTERS_MAX]; int out_tiles, pad; };
+// The G.711 code byte of a 16-bit linear value, by the arithmetic of include/vispeech_hip.h ("output rows"): the
+// truncating compressors, inverse to the two expanders above (host function and kernel alike)
+__host__ __device__ inline int g711_ulaw_code(int s) {
+  const int neg = s < 0, a = neg ? -s : s, mag = (a < 32635 ? a : 32635) + 0x84;
+  const int e = (31 - __builtin_clz((unsigned)mag)) - 7, q = (mag >> (e + 3)) & 15;
+  return ~((neg ? 0x80 : 0) | (e << 4) | q) & 0xFF;
+}
+__host__ __device__ inline int g711_alaw_code(int s) {
+  const int neg = s < 0, mag = (neg ? ~s : s) >> 3;
+  int e = mag ? (31 - __builtin_clz((unsigned)mag)) - 4 : 0;
+  if (e < 0) e = 0;
+  const int q = e == 0 ? (mag >> 1) & 15 : (mag >> e) & 15;
+  return (((neg ? 0 : 0x80) | (e << 4) | q) ^ 0x55) & 0xFF;
+}
+// Checked before the launch: 1 <= B <= OUT_ROWS_PER_LAUNCH, every row's filt names an entry with a table.  One launch:
+// grid (out_tiles + hist_blocks, B).
+hipError_t launch_output_rows(OutRowsArgs& a, int B, hipStream_t s);
+
 hipError_t launch_stft_frames(const float* audio, long a_bs, float* f, long f_bs, long f_cs, int B, int L, int n_fft,
                               int hop, int T, hipStream_t s);
 hipError_t launch_stft_magnitude(const float* ri, long r_bs, long r_cs, float* spec, int B, int spec_ch, int T,

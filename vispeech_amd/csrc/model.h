@@ -168,6 +168,8 @@ struct vsp_ctx {
   // input stage (input_stage.hip, vsp_input_configure): one table of the same layout per configured input rate
   struct InputRate { int rate = 0; float* tab = nullptr; int L = 0, M = 0, H = 0, J = 0, P = 0; };
   InputRate in_rates[VSP_INPUT_RATES_MAX];
+  // output rows (output_rows.hip, vsp_output_rate_configure): the same per configured OUTPUT rate, beside out_tab
+  InputRate out_rates[VSP_OUTPUT_RATES_MAX];
   int64_t noise_first = 0;        // stream index of element 0 of a library-drawn noise tensor (vsp_set_noise_offset)
   // Isolated mode (vsp_set_isolated, round 10): every utterance of a batch as a B = 1 call on its own unpadded inputs
   // computes it -- masks where the reference applies none, the generator's tensors ending at the utterance's own length,

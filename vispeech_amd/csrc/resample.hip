@@ -52,12 +52,6 @@ struct ResampleArgs {
   int vec_ok;             // x rows are 16-byte aligned: the tile is staged with 16-byte loads
 };
 
-__device__ __forceinline__ int rs_pcm16(float y) {
-  // service.pcm16: clip(rint(y * 32767.0f), -32768, 32767), product in fp32, round half to even
-  const float r = rintf(y * 32767.0f);
-  return (int)fminf(fmaxf(r, -32768.f), 32767.f);
-}
-
 // Stores sample j of a row (float32, or PCM16 with even lanes storing packed pairs where the row allows it).  Every lane
 // of the wave calls it with a valid y (the shuffle takes all of them); `active` lanes store, `has_next`: lane + 1 is active.
 __device__ __forceinline__ void rs_store(void* row, int64_t j, float y, bool active, bool has_next, int pcm, int pair_ok) {

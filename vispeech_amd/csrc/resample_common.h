@@ -26,6 +26,13 @@ __device__ __forceinline__ float rs_one_output(const float* __restrict__ tcol, i
   return acc;
 }
 
+// The PCM16 value of an output sample (resample.hip and output_rows.hip alike)
+__device__ __forceinline__ int rs_pcm16(float y) {
+  // service.pcm16: clip(rint(y * 32767.0f), -32768, 32767), product in fp32, round half to even
+  const float r = rintf(y * 32767.0f);
+  return (int)fminf(fmaxf(r, -32768.f), 32767.f);
+}
+
 inline double bessel_i0(double x) {
   const double q = x * x / 4.0;
   double term = 1.0, sum = 1.0;

@@ -975,6 +975,138 @@ class Engine:
         nv = None if n_valid is None else _dev_i64(n_valid, self.device)
         return output_stage.stream(self, chunks, nv, pcm)
 
+    # ------------------------------------------------------------------ output rows
+    def configure_output_rate(self, rate: int, zeros: int = 32, beta: float = 9.62, rolloff: Optional[float] = None,
+                              in_rate: Optional[int] = None) -> None:
+        """``vsp_output_rate_configure``: build and upload the filter that takes waveforms from ``in_rate`` (the model's
+        sampling rate) to ``rate`` into the context's SET of output rates, which ``output_rows`` reads -- beside the single
+        stage of ``configure_output``, which it neither reads nor changes.  Idempotent per rate: the same arguments again
+        do nothing, others replace the rate's table; a context holds up to 8 rates.  Allocates: call it outside the
+        request path."""
+        from . import output_stage
+        rate = int(rate)
+        in_rate = int(self.dims.sampling_rate if in_rate is None else in_rate)
+        key = (in_rate, int(zeros), float(beta), None if rolloff is None else float(rolloff))
+        if self._out_rates is None:
+            self._out_rates = {}
+        if rate in self._out_rates and self._out_rates[rate][0] == key:
+            return
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_output_rate_configure(self.ctx, in_rate, rate, int(zeros), float(beta),
+                                                    0.0 if rolloff is None else float(rolloff))
+        _lib.check(rc, self.ctx, "vsp_output_rate_configure")
+        self._out_rates[rate] = (key, output_stage.plan(in_rate, rate, int(zeros)))
+
+    def drop_output_rate(self, rate: int) -> None:
+        """Frees the table of an output rate (``vsp_output_rate_configure`` with model_rate 0)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vsp_output_rate_configure(self.ctx, 0, int(rate), 0, 0.0, 0.0), self.ctx,
+                       "vsp_output_rate_configure")
+        (self._out_rates or {}).pop(int(rate), None)
+
+    _out_rates = None         # rate -> (configuration, (L, M, H)) of the configured output rates
+
+    @property
+    def output_rates(self):
+        """The rates of the set ``output_rows`` reads."""
+        return tuple(self._out_rates or ())
+
+    def output_rate_plan(self, rate: int):
+        """(L, M, H) of a rate of the set."""
+        if not self._out_rates or int(rate) not in self._out_rates:
+            raise RuntimeError(f"output rate {rate} Hz is not configured: call Engine.configure_output_rate({rate}) first")
+        return self._out_rates[int(rate)][1]
+
+    def output_row_buffers(self, K: int) -> torch.Tensor:
+        """The two history buffers of one request ([2, K] float32 on the device; ``output_stage.RowState``)."""
+        return torch.empty((2, max(int(K), 0)), dtype=torch.float32, device=self.device)
+
+    def output_rows(self, rows, outs=None):
+        """``vsp_output_rows``: rows of ``(x, ended, rate, enc, state)`` in ONE call per 64 rows, every row with its own
+        configured rate and encoding (name or ``VSP_OUT_*``).  ``x``: the row's NEW samples at the model's rate, a 1-D
+        contiguous float32 device tensor (None or empty: flush the tail, with ``ended``); ``state``: the request's
+        ``output_stage.RowState`` (advanced here), or None for a whole utterance in one call (``ended`` must hold).
+        Returns ``(buf, spans)``: one packed uint8 device buffer and per row ``(offset, count)`` -- its ``count`` output
+        samples start ``offset`` bytes into ``buf`` (a multiple of 16), as elements of its encoding; the gap up to the next
+        row holds the encoding's silence, so one device-to-host copy of ``buf`` delivers all rows.  ``outs``: per row a
+        1-D contiguous device tensor of the encoding's dtype that receives the samples instead (all of it is written);
+        ``buf`` is then None and the offsets are 0."""
+        from . import output_stage
+        rows = list(rows)
+        B = len(rows)
+        if B == 0:
+            return torch.empty(0, dtype=torch.uint8, device=self.device), []
+        if outs is not None and len(outs) != B:
+            raise ValueError(f"outs must have {B} entries")
+        arr = (_lib.VspOutputRow * B)()
+        keep, counts, sizes = [], [], []
+        for r, (x, ended, rate, enc, state) in zip(arr, rows):
+            enc = output_stage.encoding(enc)
+            L, M, H = self.output_rate_plan(rate)
+            if state is None and not ended:
+                raise ValueError("a row without a state is a whole utterance: ended must be true")
+            if state is not None and state.rate != int(rate):
+                raise ValueError(f"a row's state was made for {state.rate} Hz, the row asks for {rate} Hz")
+            n = 0 if x is None else int(x.numel())
+            if n and (x.dtype != torch.float32 or x.device != self.device or x.dim() != 1 or (n > 1 and x.stride(0) != 1)):
+                raise ValueError("a row's x must be a contiguous 1-D float32 tensor on the engine's device")
+            if n == 0 and not ended:
+                raise ValueError("a row without new samples must end its utterance")
+            first = 0 if state is None else state.x_first
+            m0, m1, _, _ = output_stage.rows_plan(L, M, H, first, n, ended)
+            keep.append(x)
+            r.x, r.x_first, r.n, r.ended = (x.data_ptr() if n else None), first, n, int(bool(ended))
+            r.out_rate, r.enc = int(rate), enc
+            if state is not None and state.K:
+                r.hist_in, r.hist_out = state.buf[state.side].data_ptr(), state.buf[1 - state.side].data_ptr()
+            counts.append(m1 - m0)
+            sizes.append(output_stage.element_size(enc))
+        if outs is None:
+            A = output_stage.ROW_ALIGN
+            slots = [(c * es + A - 1) // A * A for c, es in zip(counts, sizes)]
+            offs = [0]
+            for s in slots:
+                offs.append(offs[-1] + s)
+            buf = torch.empty(max(offs[-1], 1), dtype=torch.uint8, device=self.device)
+            for r, o, s, es in zip(arr, offs, slots, sizes):
+                r.out, r.out_fill = (buf.data_ptr() + o if s else None), s // es
+            spans = list(zip(offs[:-1], counts))
+        else:
+            buf = None
+            dts = {0: torch.float32, 1: torch.int16, 2: torch.uint8, 3: torch.uint8}
+            for r, out, c in zip(arr, outs, counts):
+                if (out.dtype != dts[r.enc] or out.device != self.device or out.dim() != 1 or out.numel() < c
+                        or (out.numel() > 1 and out.stride(0) != 1)):
+                    raise ValueError("a row's out must be a contiguous 1-D device tensor of its encoding's dtype, at least "
+                                     "as long as the row's output")
+                r.out, r.out_fill = (out.data_ptr() if out.numel() else None), out.numel()
+            spans = [(0, c) for c in counts]
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, _lib.STREAM_ROWS_MAX):
+                nb = min(_lib.STREAM_ROWS_MAX, B - b0)
+                sub = C.cast(C.byref(arr, b0 * C.sizeof(_lib.VspOutputRow)), C.POINTER(_lib.VspOutputRow))
+                _lib.check(self.lib.vsp_output_rows(self.ctx, self._stream(), nb, sub), self.ctx, "vsp_output_rows")
+        for (x, _, _, _, state), c in zip(rows, counts):
+            if state is not None:
+                state.advance(0 if x is None else int(x.numel()))
+        return buf, spans
+
+    def output_batch(self, o: torch.Tensor, sample_lengths, formats):
+        """One-shot output of a whole batch with a format per row: ``o`` [B, 1, n] or [B, n] as ``infer`` returns it,
+        ``sample_lengths`` the valid samples per utterance (host integers; None: all n), ``formats`` per row
+        ``(rate, enc)``.  Returns ``(buf, spans)`` as ``output_rows`` does: what ``o`` holds behind an utterance's valid
+        length is never read."""
+        x = o.reshape(o.shape[0], -1) if o.dim() == 3 else o
+        if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise ValueError("o must be a float32 [B, 1, n] or [B, n] tensor with contiguous rows")
+        B, n = x.shape
+        lens = [n] * B if sample_lengths is None else \
+            [int(v) for v in (sample_lengths.tolist() if hasattr(sample_lengths, "tolist") else sample_lengths)]
+        formats = list(formats)
+        if len(lens) != B or len(formats) != B or any(v < 0 or v > n for v in lens):
+            raise ValueError(f"sample_lengths and formats must have {B} entries, 0 <= sample_lengths[b] <= {n}")
+        return self.output_rows([(x[b, :v], True, rate, enc, None) for b, (v, (rate, enc)) in enumerate(zip(lens, formats))])
+
     # ------------------------------------------------------------------ input stage
     def configure_input(self, rate: int, zeros: int = 32, beta: float = 9.62, rolloff: Optional[float] = None,
                         model_rate: Optional[int] = None) -> None:

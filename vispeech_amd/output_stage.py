@@ -119,3 +119,97 @@ def stream(eng, chunks: Iterable, n_valid=None, pcm: bool = True) -> Iterator:
     tail = s.finish()
     if tail is not None:
         yield tail
+
+
+# ---------------------------------------------------------------------------------------------- output rows
+# Rows with their own rate and encoding (include/vispeech_hip.h, "output rows").  The functions below drive an engine with
+#
+#     output_rate_plan(rate)                 (L, M, H) of a rate of the engine's set (``configure_output_rate``)
+#     output_row_buffers(K)                  the two history buffers of one request: something indexable by 0 and 1
+#     output_rows(rows)                      rows of (x, ended, rate, enc, state_or_None) -> (packed bytes, [(offset, count)])
+F32, S16, ULAW, ALAW = 0, 1, 2, 3                                    # VSP_OUT_*, the numbers of VSP_IN_*
+NAMES = {"f32": F32, "float32": F32, "s16": S16, "pcm16": S16, "int16": S16, "ulaw": ULAW, "mulaw": ULAW, "alaw": ALAW}
+NUMPY_DTYPES = {F32: np.float32, S16: np.int16, ULAW: np.uint8, ALAW: np.uint8}
+RATES_MAX = 8
+ROWS_MAX = 64
+ROW_ALIGN = 16                 # bytes: where a row of a packed result starts
+
+
+def encoding(enc) -> int:
+    """``VSP_OUT_*`` of an encoding given by number or by name (None: PCM16, what the services deliver)."""
+    if enc is None:
+        return S16
+    if isinstance(enc, str):
+        if enc.lower() not in NAMES:
+            raise ValueError(f"unknown encoding {enc!r}: one of {sorted(NAMES)}")
+        return NAMES[enc.lower()]
+    if int(enc) not in NUMPY_DTYPES:
+        raise ValueError(f"unknown encoding {enc!r}: 0 (float32), 1 (PCM16), 2 (mu-law), 3 (A-law)")
+    return int(enc)
+
+
+def element_size(enc) -> int:
+    return np.dtype(NUMPY_DTYPES[encoding(enc)]).itemsize
+
+
+def encode(pcm16, enc) -> np.ndarray:
+    """``vsp_output_encode``: the G.711 compressor of the kernel on the host, int16 values -> code bytes (uint8); PCM16
+    comes back as it is."""
+    from . import _lib
+    enc = encoding(enc)
+    s = np.ascontiguousarray(pcm16)
+    if s.dtype != np.int16:
+        raise ValueError(f"encode wants int16 values, got {s.dtype}")
+    if enc == S16:
+        return s
+    codes = np.zeros(s.shape, dtype=np.uint8)
+    rc = _lib.lib().vsp_output_encode(enc, s.ctypes.data_as(C.c_void_p), s.size, codes.ctypes.data_as(C.c_void_p))
+    _lib.check(rc, None, "vsp_output_encode")
+    return codes
+
+
+def silence(enc):
+    """The encoding's code of 0: 0.0, 0, 0xFF, 0xD5."""
+    enc = encoding(enc)
+    return np.float32(0.0) if enc == F32 else encode(np.zeros(1, np.int16), enc)[0]
+
+
+def rows_plan(L: int, M: int, H: int, x_first: int, n: int, ended: bool) -> Tuple[int, int, int, int]:
+    """``vsp_output_rows_plan``: (m0, m1, k0, k1) of a call that brings input samples [x_first, x_first + n) -- it delivers
+    output samples [m0, m1), reads the history from input sample k0 and leaves the history from k1."""
+    from . import _lib
+    res = [C.c_int64() for _ in range(4)]
+    rc = _lib.lib().vsp_output_rows_plan(int(L), int(M), int(H), int(x_first), int(n), int(bool(ended)), *map(C.byref, res))
+    _lib.check(rc, None, f"vsp_output_rows_plan(L = {L}, M = {M}, H = {H}, x_first = {x_first}, n = {n})")
+    return tuple(r.value for r in res)
+
+
+def history_samples(L: int, M: int, H: int) -> int:
+    """``vsp_output_history_samples``: floor(2 H / L), the floats of one history buffer."""
+    return (2 * int(H)) // int(L)
+
+
+class RowState:
+    """What one request keeps between two ``output_rows`` calls at ``rate``: its two history buffers (``buf[side]`` is read
+    by the next call, ``buf[1 - side]`` written) and ``x_first``, the input samples it has brought so far."""
+
+    def __init__(self, eng, rate: int):
+        self.rate = int(rate)
+        self.plan = tuple(eng.output_rate_plan(self.rate))
+        self.K = history_samples(*self.plan)
+        self.buf = eng.output_row_buffers(self.K)
+        self.side, self.x_first = 0, 0
+
+    def advance(self, n: int) -> None:
+        """After a call that brought ``n`` samples: the written buffer becomes the one to read."""
+        self.side, self.x_first = 1 - self.side, self.x_first + int(n)
+
+
+def unpack(host_bytes, spans, encs):
+    """The rows of a packed result copied to the host (a uint8 array or bytes) as arrays of their encodings' dtypes."""
+    a = np.frombuffer(host_bytes, dtype=np.uint8) if not isinstance(host_bytes, np.ndarray) else host_bytes.reshape(-1).view(np.uint8)
+    out = []
+    for (off, cnt), enc in zip(spans, encs):
+        dt = np.dtype(NUMPY_DTYPES[encoding(enc)])
+        out.append(a[off:off + cnt * dt.itemsize].view(dt))
+    return out

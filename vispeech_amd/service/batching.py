@@ -22,6 +22,30 @@ def _input_format(sample_rate, encoding, model_rate: int):
     return (int(model_rate if sample_rate is None else sample_rate), input_stage.encoding(encoding))
 
 
+def _output_format(output_rate, output_encoding):
+    """``(rate or None, VSP_OUT_*)`` of a request that names an output rate or encoding (None: the service's rate; PCM16),
+    None of one that names neither -- its bytes are the ones it always got."""
+    if output_rate is None and output_encoding is None:
+        return None
+    from .. import output_stage
+    if output_rate is not None and int(output_rate) <= 0:
+        raise ValueError("output_rate must be positive")
+    return (None if output_rate is None else int(output_rate), output_stage.encoding(output_encoding))
+
+
+def _row_formats(eng, reqs, base_rate: int, model_rate: int):
+    """Per request the ``(rate, VSP_OUT_*)`` of its row in an ``Engine.output_rows`` call: its own format, or -- for a
+    request that names none -- (the service's rate, PCM16), the bytes it gets on the service's own path.  Rates the engine's
+    set does not hold yet are configured here (allocates: configure them ahead where that matters)."""
+    from .. import output_stage
+    fmts = [(base_rate, output_stage.S16) if r.out_fmt is None else (base_rate if r.out_fmt[0] is None else r.out_fmt[0], r.out_fmt[1])
+            for r in reqs]
+    for rate in sorted({f[0] for f in fmts}):
+        if rate not in eng.output_rates:
+            eng.configure_output_rate(rate, in_rate=model_rate)
+    return fmts
+
+
 class _Conversion:
     """A conversion request of the batching services (``submit_conversion``): a recording at the model's rate, the speaker
     it was spoken by and the speaker to convert it to.  To the vocoder it is a row like any other -- a latent, a speaker
@@ -47,8 +71,9 @@ class _Request:
     keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
     ``noise_scale``; a conversion's noise scale is its row's."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None)):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None):
         self.row, self.seed, self.scales = row, int(seed), scales
+        self.out_fmt = out_fmt        # ``_output_format``: the request's own output rate and encoding, or None
 
     @property
     def is_conversion(self) -> bool:
@@ -213,23 +238,30 @@ class BatchingSynthesisService:
         self._worker.start()
 
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None) -> "concurrent.futures.Future":
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
-        The future's result is the request's PCM16 samples (numpy int16, valid part only)."""
-        return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
+        The future's result is the request's PCM16 samples (numpy int16, valid part only).
+        ``output_rate`` / ``output_encoding`` (``vispeech_amd.output_stage``: "f32", "s16", "ulaw", "alaw"): the request's own
+        delivery format -- the result is then float32, int16 or uint8 (G.711 codes) at that rate.  When any request of a
+        collected batch names one, all its waveforms leave through ONE ``Engine.output_rows`` call and one device-to-host
+        copy; requests that name none ride as rows of (the service's rate, PCM16) and get the bytes they always got."""
+        return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
+                                      _output_format(output_rate, output_encoding)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
-                          sample_rate: Optional[int] = None, encoding=None) -> "concurrent.futures.Future":
+                          sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
+                          output_encoding=None) -> "concurrent.futures.Future":
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
         PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
         ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
         ``noise_scale``); ``noise_seed`` keys that noise.
         ``sample_rate`` / ``encoding`` (``vispeech_amd.input_stage``): ``audio`` is raw -- an array of the encoding's dtype or
         ``bytes`` -- at that rate; the batch's raw recordings go through the input stage on the GPU, one call per distinct
-        (rate, encoding), before the one ``convert_latent``."""
+        (rate, encoding), before the one ``convert_latent``.  ``output_rate`` / ``output_encoding``: as in ``submit``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
-        return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed))
+        return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
+                                      out_fmt=_output_format(output_rate, output_encoding)))
 
     def _enqueue(self, req: _Request) -> "concurrent.futures.Future":
         req.future = concurrent.futures.Future()
@@ -289,7 +321,28 @@ class BatchingSynthesisService:
                                   energy_control=t(ctl[2]), noise_seed=[r.seed for r in reqs], isolated=True, **kw)
         frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
         hop = net.dims.total_upsample
+        if any(r.out_fmt is not None for r in reqs):
+            return self._deliver_rows(reqs, [o[b, 0, : int(frames[b]) * hop] for b in range(len(reqs))])
         return [self._pcm16(o[b:b + 1, 0, : int(frames[b]) * hop]) for b in range(len(reqs))]
+
+    def _deliver_rows(self, reqs, waves):
+        """A batch in which a request names its own format: every request's valid samples (``waves``, 1-D float rows on the
+        device; None: nothing to deliver) as a row of ONE ``Engine.output_rows`` call, ONE device-to-host copy, and each
+        request's array in its encoding's dtype."""
+        from .. import output_stage
+        from ._pcm import _host
+        eng = self.net._engine
+        base = self.sampling_rate if self.output_rate is None else self.output_rate
+        fmts = _row_formats(eng, reqs, base, self.sampling_rate)
+        empty = lambda enc: np.zeros(0, dtype=np.dtype(output_stage.NUMPY_DTYPES[enc]).newbyteorder("<"))
+        out = [empty(enc) for _, enc in fmts]
+        live = [i for i, w in enumerate(waves) if w is not None and w.shape[-1] > 0]
+        if live:
+            buf, spans = eng.output_rows([(waves[i].reshape(-1), True, fmts[i][0], fmts[i][1], None) for i in live])
+            host = _host(buf)                                           # the batch's one device-to-host copy
+            for i, a in zip(live, output_stage.unpack(host, spans, [fmts[i][1] for i in live])):
+                out[i] = a.copy()
+        return out
 
     def _synthesize_mixed(self, reqs):
         """A batch with conversions: every request's latent, speaker vector and length packed into one ragged batch, ONE
@@ -300,7 +353,7 @@ class BatchingSynthesisService:
         live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
         pcms = [np.zeros(0, dtype="<i2") for _ in reqs]
         if not live:
-            return pcms
+            return self._deliver_rows(reqs, [None] * len(reqs)) if any(r.out_fmt is not None for r in reqs) else pcms
         T = max(lat[i][2] for i in live)
         z0 = torch.as_tensor(lat[live[0]][0])
         Z = torch.zeros((len(live), z0.shape[0], T), dtype=torch.float32, device=z0.device)
@@ -309,6 +362,11 @@ class BatchingSynthesisService:
         G = torch.stack([torch.as_tensor(lat[i][1]).reshape(-1) for i in live])
         o = eng.generator_ragged(Z, G, [lat[i][2] for i in live])
         hop = net.dims.total_upsample
+        if any(r.out_fmt is not None for r in reqs):
+            waves = [None] * len(reqs)
+            for b, i in enumerate(live):
+                waves[i] = o[b, 0, : lat[i][2] * hop]
+            return self._deliver_rows(reqs, waves)
         for b, i in enumerate(live):
             pcms[i] = self._pcm16(o[b:b + 1, 0, : lat[i][2] * hop])
         return pcms

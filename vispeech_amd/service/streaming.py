@@ -11,7 +11,7 @@ import numpy as np
 
 from .. import input_stage, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
-from .batching import _Conversion, _Request, _collate_from, _input_format, latents
+from .batching import _Conversion, _Request, _collate_from, _input_format, _output_format, _row_formats, latents
 
 
 class _RowStream:
@@ -58,13 +58,14 @@ class _RowStream:
 class _StreamRequest(_Request):
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None)):
-        super().__init__(row, seed, scales)
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None):
+        super().__init__(row, seed, scales, out_fmt)
         self.stream = _RowStream()
         self.z = self.g = None
         self.L = self.pos = 0
         self.output = None            # ``output_rate``: the request's own ``output_stage.Stream``, one window per tick
         self.history = None           # ``fused_output``: the request's Engine.output_history(), from admission on
+        self.row_state = None         # ticks with per-request formats: the request's ``output_stage.RowState``
 
 
 class LiveConversion(_RowStream):
@@ -118,8 +119,8 @@ class _LiveRequest(_StreamRequest):
     on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
     ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
 
-    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale):
-        super().__init__(None, seed)
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None):
+        super().__init__(None, seed, out_fmt=out_fmt)
         self.stream = stream
         self.fmt = stream._fmt        # (rate, encoding) of the feed: its pieces go through ``input`` before they reach ``buf``
         self.input = None             # the session's ``input_stage.Stream``, from its first piece on
@@ -165,7 +166,14 @@ class StreamingBatchService:
     as one more row.  A session that is not ready sits the tick out; while only such sessions exist the worker sleeps.  The
     bytes are those of the finished recording converted alone, with the frame-major noise of ``vsp_convert_stream_rows``
     (not the layout ``submit_conversion`` draws).  A session keeps on the device the samples its next window reads and
-    those behind them, nothing older.  No backpressure and no reduced-lookahead mode."""
+    those behind them, nothing older.  No backpressure and no reduced-lookahead mode.
+    ``submit`` / ``submit_conversion`` / ``open_conversion`` take ``output_rate=`` / ``output_encoding=``: the request's own
+    delivery format (float32, PCM16, G.711 mu-law or A-law at any rate of the output stage).  A tick in which an active
+    request names one runs ``generator_stream_rows(pcm=False)`` and then ONE ``Engine.output_rows`` call over all its rows,
+    each with its request's rate, encoding and ``output_stage.RowState``, and one device-to-host copy; a request that ends
+    gets its filter's tail in the same call; requests that name nothing ride at (the service's rate, PCM16) and get the
+    bytes of their own path.  A tick without such a request is the tick described above.  ``fused_output=True`` refuses
+    a request's own format (``ValueError``)."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
@@ -198,26 +206,40 @@ class StreamingBatchService:
             self._worker.start()
 
     # ------------------------------------------------------------------ callers' side
+    def _out_fmt(self, output_rate, output_encoding):
+        fmt = _output_format(output_rate, output_encoding)
+        if fmt is not None and self.fused_output:
+            raise ValueError("fused_output delivers every row at the service's rate as PCM16: a request's own output_rate / "
+                             "output_encoding needs fused_output=False")
+        return fmt
+
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None) -> _RowStream:
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None) -> _RowStream:
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
         1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
-        request's PCM16 ``bytes``, one piece per tick the request takes part in."""
-        return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale)))
+        request's PCM16 ``bytes``, one piece per tick the request takes part in.
+        ``output_rate`` / ``output_encoding`` ("f32", "s16", "ulaw", "alaw"): the request's own delivery format; its
+        ``bytes`` are then little-endian elements of that encoding at that rate (see the class text)."""
+        return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
+                                            self._out_fmt(output_rate, output_encoding)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
-                          sample_rate: Optional[int] = None, encoding=None) -> _RowStream:
+                          sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
+                          output_encoding=None) -> _RowStream:
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
         the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
         frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
         NOT the service's text-to-speech ``noise_scale``).  ``sample_rate`` / ``encoding``: ``audio`` is raw samples in that
         format (an array of the encoding's dtype or ``bytes``); admission runs the group's raw recordings through the
-        input stage, one call per distinct (rate, encoding), before its one ``convert_latent``."""
+        input stage, one call per distinct (rate, encoding), before its one ``convert_latent``.  ``output_rate`` /
+        ``output_encoding``: as in ``submit``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
-        return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed))
+        return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
+                                            out_fmt=self._out_fmt(output_rate, output_encoding)))
 
     def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
-                        sample_rate: Optional[int] = None, encoding=None) -> LiveConversion:
+                        sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
+                        output_encoding=None) -> LiveConversion:
         """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
         ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
         ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``).
@@ -225,7 +247,9 @@ class StreamingBatchService:
         arrived -- one ``Engine.input_rows`` call per distinct (rate, encoding) among the sessions with new audio -- and
         appends the model-rate samples that are complete to the session's buffer; ``end()`` flushes the filter's tail.
         Readiness is decided on those samples, so the session's delay grows by the filter's half length: ``zeros`` = 32
-        input periods (2 ms at 16 kHz)."""
+        input periods (2 ms at 16 kHz).  ``output_rate`` / ``output_encoding``: as in ``submit``; on that path a frame
+        need not be a whole number of output samples."""
+        out_fmt = self._out_fmt(output_rate, output_encoding)
         if self.fused_output:
             # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
             # filter's phase and its history must not see the shift
@@ -245,7 +269,7 @@ class StreamingBatchService:
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         if fmt is not None and fmt[0] not in self.net._engine.input_rates:
             self.net._engine.configure_input(fmt[0], model_rate=self.sampling_rate)      # (allocates: here, not in a tick)
-        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale))
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt))
 
     def _enqueue(self, req: _StreamRequest) -> _RowStream:
         """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
@@ -466,6 +490,11 @@ class StreamingBatchService:
             counts.append(f1 - r.pos)
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
+        if any(r.out_fmt is not None for r in reqs):
+            return self._deliver_rows(reqs, rows, counts)
+        for r in reqs:
+            if r.row_state is not None:        # it shared earlier ticks with requests that name a format
+                self._leave_rows_path(r)
         if self.fused_output:
             out, done = eng.generator_stream_rows_output([row + (r.history,) for row, r in zip(rows, reqs)],
                                                          self.chunk_frames, pcm=True)
@@ -486,6 +515,53 @@ class StreamingBatchService:
             r.pos += n
             if done[b]:                        # (a fused tick may complete no output sample of a request)
                 r.stream._q.put(block[b, : done[b]].tobytes())
+
+    def _deliver_rows(self, reqs, rows, counts) -> None:
+        """A tick in which a request names its own format: the float chunks of ``generator_stream_rows`` as rows of ONE
+        ``Engine.output_rows`` call -- each with its request's rate, encoding and ``RowState``; a request that names nothing
+        rides at (the service's rate, PCM16), the bytes of its own path -- then one device-to-host copy.  A request's last
+        chunk carries ``ended``: its tail comes in the same call."""
+        from ._pcm import _host
+        eng = self.net._engine
+        hop = self.net.dims.total_upsample
+        base = self.sampling_rate if self.output_rate is None else self.output_rate
+        fmts = _row_formats(eng, reqs, base, self.sampling_rate)
+        out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=False)
+        job = []
+        for b, (r, n, (rate, enc)) in enumerate(zip(reqs, counts, fmts)):
+            if r.row_state is None:
+                self._enter_rows_path(r, rate, (getattr(r, "e0", 0) + r.pos) * hop)
+            r.pos += n
+            job.append((out[b, : n * hop], r.pos >= r.L, rate, enc, r.row_state))
+        buf, spans = eng.output_rows(job)
+        host = _host(buf)                                               # the tick's one device-to-host copy
+        _check_numerics(self.net)
+        for r, (off, cnt), (_, enc) in zip(reqs, spans, fmts):
+            if cnt:                            # (a short chunk at a low rate may complete no output sample)
+                r.stream._q.put(host[off:off + cnt * output_stage.element_size(enc)].tobytes())
+
+    def _enter_rows_path(self, r: _StreamRequest, rate: int, x_first: int) -> None:
+        """The request's ``RowState`` at input sample ``x_first``; a request that came along on the service's own path
+        brings the samples its ``output_stage.Stream`` kept -- they start at the k0 of its next call."""
+        r.row_state = output_stage.RowState(self.net._engine, rate)
+        r.row_state.x_first = int(x_first)
+        s, r.output = r.output, None
+        if s is not None and s.hist is not None and s.hist.shape[1]:
+            r.row_state.buf[r.row_state.side][: s.hist.shape[1]] = s.hist[0]
+
+    def _leave_rows_path(self, r: _StreamRequest) -> None:
+        """Back to the service's own path (no request of the tick names a format): the ``output_stage.Stream`` of a service
+        with an ``output_rate`` continues from what the request's ``RowState`` holds."""
+        st, r.row_state = r.row_state, None
+        if self.output_rate is None or self.fused_output:
+            return
+        s = output_stage.Stream(self.net._engine, None, pcm=True)
+        L, M, H = s.plan
+        s.seen = st.x_first
+        s.m_next = output_stage.complete_outputs(s.seen, L, M, H)
+        s.first = min(s.seen, output_stage.history_start(s.m_next, L, M, H))
+        s.hist = st.buf[st.side][: s.seen - s.first].reshape(1, -1)
+        r.output = s
 
     def _through_output_stage(self, r: _StreamRequest, x) -> bytes:
         """The request's float window through its own ``output_stage.Stream``; returns the PCM16 bytes it completes (none
