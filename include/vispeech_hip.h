@@ -148,7 +148,9 @@ int vsp_missing_weights(const vsp_ctx* ctx);
 int64_t vsp_weight_arena_bytes(const vsp_ctx* ctx);
 /* Fold + pack (MFMA fragment order) + upload.  dev_arena may be NULL (the library allocates).  VSP_ERR_STATE while a
  * required tensor is missing; VSP_ERR_UNSUPPORTED when a folded convolution weight does not fit the packed split-f16 form
- * (|w| < 253: the images hold w * 2^8 as f16 pairs -- ABI 6). */
+ * (|w| < 253: the images hold w * 2^8 as f16 pairs -- ABI 6).  Both this call and vsp_commit_adopted_weights then build
+ * the context's per-speaker silence table (vsp_generator_tail_extents) on the device and return when it is finished; a
+ * table that cannot be built (memory) is not an error: the generator then runs without one. */
 int vsp_finalize_weights(vsp_ctx* ctx, void* dev_arena);
 /* Multi-GPU: a non-root rank adopts an arena that receives rank 0's packed bytes by an RCCL broadcast; no host
  * weights needed.  vsp_adopt_packed_weights only records the pointer (the bytes may still be in flight): the context
@@ -290,6 +292,12 @@ int vsp_generator_halo_frames(const vsp_ctx* ctx);
  * the padded run, frame L + back the steady state of the zero input behind the utterance (periodic in one frame), the
  * last fwd frames the tensor end's -- and the rest of the padded waveform is filled from those, bit for bit. */
 int vsp_generator_frame_dependence(const vsp_ctx* ctx, int* back, int* fwd);
+/* The same two extents and *reach1: output frame F depends on frames up to F + *reach1 of the FIRST stage's output tensor
+ * (the second up-convolution through conv_post; 2 for configs/config.json, *fwd + 1 for a generator of one stage).  An
+ * utterance whose speaker vector is a row of emb_g takes its steady-state frame and the tensor end's frames from the
+ * context's per-speaker silence table (built when weights are committed; VSP_TAIL_TABLE=0: none), so the stages behind
+ * the first compute it to L + back + reach1 frames only, where L + back + fwd <= T.  Additive; needs no weights. */
+int vsp_generator_tail_extents(const vsp_ctx* ctx, int* back, int* fwd, int* reach1);
 int64_t vsp_generator_stream_workspace_bytes(const vsp_ctx* ctx, int B, int chunk_frames);
 int vsp_generator_stream_chunk(vsp_ctx* ctx, void* stream, int B, int T, const float* z, const float* g, int f0, int f1,
                                float* o_chunk, void* workspace, int64_t workspace_bytes);

@@ -148,6 +148,7 @@ SIGNATURES = {
     "vsp_generator_kind": (_I, [_P]),
     "vsp_generator_halo_frames": (_I, [_P]),
     "vsp_generator_frame_dependence": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "vsp_generator_tail_extents": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vsp_generator_stream_workspace_bytes": (_I64, [_P, _I, _I]),
     "vsp_generator_stream_chunk": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I64]),
     "vsp_stream_rows_plan": (_I, [_P, _I, C.POINTER(VspStreamRow), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

@@ -281,5 +281,8 @@ void run_posterior(Run& r, int B, int T, T3 y, const int64_t* lengths, const flo
 void draw_noise_rows(Run& r, uint64_t* seeds_dev, const int64_t* lengths, int B, int C, int T, float* drawn);
 // api_generator.hip
 void run_gen(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const float* g, float* o);
+// the context's silence table (model.h): built, synchronously on s, when weights are committed; dropped when they change
+void tail_table_build(vsp_ctx* ctx, hipStream_t s);
+void tail_table_drop(vsp_ctx* ctx);
 
 }  // namespace vsp

@@ -56,6 +56,7 @@ int vsp_create_ex(const vsp_config* cfg, int32_t resblock, int device, vsp_ctx**
   if (const char* e = getenv("VSP_CHAIN")) ctx->chain_mask = atoi(e);
   if (const char* e = getenv("VSP_RW64")) ctx->rw64 = atoi(e) != 0;               // 1: g16_rw64 for the 64-channel k3 pairs (opt-in)
   if (const char* e = getenv("VSP_TRIM_TAILS")) ctx->trim_tails = atoi(e) != 0;   // 0: every utterance runs to the padded length
+  if (const char* e = getenv("VSP_TAIL_TABLE")) ctx->tail_table_on = atoi(e) != 0; // 0: no silence table (second implementation)
   if (const char* e = getenv("VSP_COLS")) ctx->cols = atoi(e) != 0;               // 0: no column-tile kernels (second implementation)
   if (const char* e = getenv("VSP_COLS_BLOCKS")) ctx->cols_blocks = atol(e);      // size limits of launch_conv's routing to them
   if (const char* e = getenv("VSP_COLS_MIN_BLOCKS")) ctx->cols_min_blocks = atol(e);
@@ -88,6 +89,7 @@ int vsp_destroy(vsp_ctx* ctx) {
   for (auto st : ctx->side) if (st) (void)hipStreamDestroy(st);
   if (ctx->arena && ctx->arena_owned) (void)hipFree(ctx->arena);
   if (ctx->out_tab) (void)hipFree(ctx->out_tab);
+  tail_table_drop(ctx);
   for (auto& r : ctx->in_rates) if (r.tab) (void)hipFree(r.tab);
   for (auto& r : ctx->out_rates) if (r.tab) (void)hipFree(r.tab);
   delete ctx;
@@ -110,6 +112,7 @@ int vsp_begin_weights(vsp_ctx* ctx) {
   ctx->raw.clear();
   ctx->ready = false;
   ctx->adopted_pending = false;
+  tail_table_drop(ctx);
   return VSP_OK;
 }
 
@@ -286,18 +289,21 @@ int vsp_finalize_weights(vsp_ctx* ctx, void* dev_arena) {
                              ctx->model.has_vc ? ARENA_FLAG_VC : 0u, config_hash(ctx)};
     std::memcpy(host.data(), hdr, sizeof hdr);
   }
+  tail_table_drop(ctx);                      // (the table belongs to the weights it was built from)
   rc = set_arena(ctx, dev_arena);
   if (rc) return rc;
   hipError_t e = hipMemcpy(ctx->arena, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "hipMemcpy(weight arena): %s", hipGetErrorString(e));
   ctx->adopted_pending = false;
   ctx->ready = true;
+  tail_table_build(ctx, nullptr);
   return VSP_OK;
 }
 
 int vsp_adopt_packed_weights(vsp_ctx* ctx, void* dev_arena) {
   if (!ctx || !dev_arena) return ctx ? ctx->fail(VSP_ERR_ARG, "null arena") : VSP_ERR_ARG;
   if (ctx->model.total_floats == 0) return ctx->fail(VSP_ERR_STATE, "context was not planned");
+  tail_table_drop(ctx);
   const int rc = set_arena(ctx, dev_arena);
   if (rc) return rc;
   // the bytes may not have arrived yet (the broadcast follows): nothing is known about them until
@@ -323,6 +329,7 @@ int vsp_commit_adopted_weights(vsp_ctx* ctx, void* stream) {
   ctx->model.has_vc = (hdr[4] & ARENA_FLAG_VC) != 0;
   ctx->adopted_pending = false;
   ctx->ready = true;
+  tail_table_build(ctx, (hipStream_t)stream);
   return VSP_OK;
 }
 

@@ -22,30 +22,57 @@ long resblock_support(const vsp_config& c, int resblock, int j) {
   return acc;
 }
 
-// Exact dependence of the generator's output FRAMES on its input frames, from the configuration (sample-exact supports;
-// vsp_generator_halo_frames below is the coarser per-stage bound the streamed vocoder uses): output frame F depends on
-// input frames [F - back, F + fwd].  An impulse at input position 0 reaches output samples [lo, hi]: conv_pre widens the
-// support by its padding, a transposed convolution (k, s, p) maps [lo, hi] to [lo s - p, hi s - p + k - 1], a stage's
-// ResBlocks widen it by max_k of the block's support (resblock_support), conv_post by its padding.
-void generator_frame_dependence(const vsp_config& c, int resblock, int pre_k, int post_k, int& back, int& fwd) {
-  long lo = -(pre_k - 1) / 2, hi = (pre_k - 1) / 2, up = 1;
-  for (int i = 0; i < c.n_upsamples; ++i) {
+// Support of the layers from stage `first` up to (not including) stage `end`, sample-exact from the configuration: an impulse
+// at position 0 of stage first's INPUT tensor reaches positions [lo, hi] of stage end - 1's output, `up` of them per input
+// position.  first == 0 starts in front of conv_pre, which widens the support by its padding; a transposed convolution
+// (k, s, p) maps [lo, hi] to [lo s - p, hi s - p + k - 1]; a stage's ResBlocks widen it by max_k of the block's support
+// (resblock_support); end == n_upsamples includes conv_post, which widens it by its padding.
+void generator_support(const vsp_config& c, int resblock, int pre_k, int post_k, int first, int end, long& lo, long& hi, long& up) {
+  lo = hi = 0; up = 1;
+  if (first == 0) { lo = -(pre_k - 1) / 2; hi = (pre_k - 1) / 2; }
+  for (int i = first; i < end && i < c.n_upsamples; ++i) {
     const long s = c.upsample_rates[i], k = c.upsample_kernel_sizes[i], p = (k - s) / 2;
     lo = lo * s - p; hi = hi * s - p + k - 1; up *= s;
     long rb = 0;
     for (int j = 0; j < c.n_resblock_kernels; ++j) rb = std::max(rb, resblock_support(c, resblock, j));
     lo -= rb; hi += rb;
   }
-  lo -= (post_k - 1) / 2; hi += (post_k - 1) / 2;
-  // output frame F = samples [up F, up F + up - 1] depends on input frames f with up f + lo <= n <= up f + hi
-  back = (int)(hi / up);                     // F - floor(hi / up)
-  fwd = (int)((up - 1 - lo) / up);           // F + floor((up - 1 - lo) / up)
+  if (end >= c.n_upsamples) { lo -= (post_k - 1) / 2; hi += (post_k - 1) / 2; }
 }
 
 long total_upsample(const vsp_config& c) {
   long u = 1;
   for (int i = 0; i < c.n_upsamples; ++i) u *= c.upsample_rates[i];
   return u;
+}
+
+// Exact dependence of the generator's output FRAMES on its input frames (vsp_generator_halo_frames below is the coarser
+// per-stage bound the streamed vocoder uses): output frame F depends on input frames [F - back, F + fwd].
+void generator_frame_dependence(const vsp_config& c, int resblock, int pre_k, int post_k, int& back, int& fwd) {
+  long lo, hi, up;
+  generator_support(c, resblock, pre_k, post_k, 0, c.n_upsamples, lo, hi, up);
+  // output frame F = samples [up F, up F + up - 1] depends on input frames f with up f + lo <= n <= up f + hi
+  back = (int)(hi / up);                     // F - floor(hi / up)
+  fwd = (int)((up - 1 - lo) / up);           // F + floor((up - 1 - lo) / up)
+}
+
+// The two extents of the silence table (kernels.h): output frame F depends on frames up to F + reach1 of stage 0's OUTPUT
+// tensor (up-convolution 1 .. conv_post; 2 for configs/config.json), and frame G of that tensor on input frames up to
+// G + fwd0 (conv_pre and stage 0; 11).  With `per` stage-0 columns per frame and `up1` samples per column, output frame F
+// = samples [per up1 F, per up1 (F + 1)) depends on columns c with up1 c + lo <= n: the last one is
+// per F + floor((per up1 - 1 - lo) / up1), which lies in frame F + floor((per up1 - 1 - lo) / (per up1)).
+// A generator of one stage has nothing behind stage 0: reach1 = fwd + 1 then (the whole extent; nothing to gain).
+void generator_tail_reach(const vsp_config& c, int resblock, int pre_k, int post_k, int& reach1, int& fwd0) {
+  int back = 0, fwd = 0;
+  generator_frame_dependence(c, resblock, pre_k, post_k, back, fwd);
+  reach1 = fwd + 1; fwd0 = fwd;
+  if (c.n_upsamples < 2) return;
+  const long total = total_upsample(c);
+  long lo, hi, up;
+  generator_support(c, resblock, pre_k, post_k, 1, c.n_upsamples, lo, hi, up);
+  reach1 = std::max(1, (int)((total - 1 - lo) / total));
+  generator_support(c, resblock, pre_k, post_k, 0, 1, lo, hi, up);
+  fwd0 = (int)((up - 1 - lo) / up);
 }
 
 // max over the generator's stages of f(channels, columns): stage i has upsample_initial_channel >> (i + 1) channels and
@@ -285,6 +312,15 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   const bool iso = r.iso && in_lengths;
   // (the plan is part of the workspace whatever the context's switches: its size does not depend on the context's state)
   int* glen_all = reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int)));
+  // Silence table (round 18; model.h, kernels.h): an utterance whose g is a row of emb_g takes the steady frame and the
+  // tensor end from the context's table, so stages 1 .. conv_post end it at len + back + reach1 frames (glen1) -- the
+  // transition frames [len, len + back) see stage 0's output no further -- while conv_pre's successors in stage 0 keep
+  // glen0 = len + back + 1 + fwd: stage 0's output is then exact up to frame glen0 - 1 - fwd0 >= len + back + reach1 - 1
+  // (tail_table_build checks fwd0 + reach1 <= fwd + 1).  Eligible: len + back + fwd <= T -- exactly when no frame before
+  // len + back sees the true tensor end, so everything from frame len + back on is the zero input's response.
+  // (both arrays are part of the workspace whether the table exists or not)
+  int* glen1_all = reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int)));
+  int* tail_row = reinterpret_cast<int*>(r.ws.bytes((size_t)B * sizeof(int)));
   // (gen_tail_fill keeps the computed tensor end -- fwd frames of the waveform -- in 64 KB of LDS: other configurations run untrimmed)
   bool trim = in_lengths && (iso || (r.ctx->trim_tails && T > back + fwd + 1 &&
                                                  (size_t)fwd * total_upsample(c) * sizeof(float) <= 64 * 1024));
@@ -296,14 +332,26 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
     for (int b = 0; b < B; ++b) any = any || std::max<int64_t>(r.host_lengths[b], 0) + (iso ? 0 : back + 1 + fwd) < T;
     trim = any;
   }
-  if (trim && !r.dry() && r.ok())
-    r.chk(iso ? launch_gen_plan_isolated(in_lengths, B, T, glen_all, r.s) : launch_gen_plan(in_lengths, B, T, back, fwd, glen_all, r.s),
+  // the table serves this call when it was built for these extents (a context whose weights changed has none)
+  const float* const table = r.ctx->tail_table;
+  const bool tabled = trim && !iso && table && r.ctx->tail_back == back && r.ctx->tail_fwd == fwd;
+  const int* glen1 = tabled ? glen1_all : glen_all;   // the extent of stage 1 .. conv_post
+  if (trim && !r.dry() && r.ok()) {
+    if (tabled)
+      r.chk(launch_gen_tail_rows(g, r.A(m.emb_g), c.n_speakers, c.gin_channels, B, tail_row, r.s), "gen_tail_rows");
+    r.chk(iso ? launch_gen_plan_isolated(in_lengths, B, T, glen_all, r.s)
+              : launch_gen_plan(in_lengths, B, T, back, fwd, tabled ? r.ctx->tail_reach1 : fwd + 1, tabled ? tail_row : nullptr,
+                                glen_all, glen1_all, r.s),
           "gen_plan");
-  // profiled (untimed) passes charge every launch the frames it COMPUTES: read the plan back (a host wait -- profiling only)
-  std::vector<int> glen_host;
+  }
+  // profiled (untimed) passes charge every launch the frames it COMPUTES, in the stage it belongs to: read the plan back
+  // (a host wait -- profiling only)
+  std::vector<int> glen_host, glen1_host;
   if (trim && r.ctx->prof_on && !r.dry() && r.ok()) {
     glen_host.resize(B);
+    glen1_host.resize(B);
     hipError_t e = hipMemcpyAsync(glen_host.data(), glen_all, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, r.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(glen1_host.data(), glen1, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, r.s);
     if (e == hipSuccess) e = hipStreamSynchronize(r.s);
     r.chk(e, "gen_plan read-back (profiling)");
   }
@@ -348,12 +396,14 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
     }
     for (int b0 = 0; b0 < B; b0 += Bc) {
       const int nb = std::min(Bc, B - b0);
-      r.glen = trim ? glen_all + b0 : nullptr;
+      // stage 0 runs every utterance to glen0, the stages behind it to glen1 (the silence table; the same array without it)
+      r.glen = trim ? (i == 0 ? glen_all : glen1) + b0 : nullptr;
       r.grate_in = (int)(Tn / T); r.grate_out = (int)(Tout / T);
       r.work_frac = 1.0;
       if (!glen_host.empty() && r.ok()) {
+        const std::vector<int>& gh = i == 0 ? glen_host : glen1_host;
         double fr = 0.0;
-        for (int b = b0; b < b0 + nb; ++b) fr += glen_host[b];
+        for (int b = b0; b < b0 + nb; ++b) fr += gh[b];
         r.work_frac = fr / ((double)nb * T);
       }
       const float* xin = buf[cur] + (size_t)b0 * xbs;
@@ -426,9 +476,11 @@ void run_generator_cl(Run& r, int B, int T, T3 z, const int64_t* in_lengths, con
   r.work_frac = 1.0;
   if (!r.dry() && r.ok()) {
     r.chk(launch_conv_post_cl(buf[cur], Tn * ch, ch, r.A(m.post_wt), m.post_c, m.post_k, 0.01f, o, Tn, B, (int)Tn, r.s,
-                              trim ? glen_all : nullptr, (int)(Tn / T), 1.f / r.ctx->act_scale, r.ctx->flags_dev), "conv_post_cl");
+                              trim ? glen1 : nullptr, (int)(Tn / T), 1.f / r.ctx->act_scale, r.ctx->flags_dev), "conv_post_cl");
     if (trim && iso) r.chk(launch_gen_tail_zero(o, Tn, in_lengths, B, T, (int)(Tn / T), r.s), "gen_tail_zero");
-    else if (trim) r.chk(launch_gen_tail_fill(o, Tn, in_lengths, glen_all, B, T, back, fwd, (int)(Tn / T), r.s), "gen_tail_fill");
+    else if (trim)
+      r.chk(launch_gen_tail_fill(o, Tn, in_lengths, glen_all, glen1, tabled ? tail_row : nullptr, table, B, T, back, fwd, (int)(Tn / T),
+                                 r.s), "gen_tail_fill");
   }
 }
 
@@ -439,6 +491,77 @@ namespace vsp {
 void run_gen(Run& r, int B, int T, T3 z, const int64_t* in_lengths, const float* g, float* o) {
   if (r.ctx->gen_mode >= 1 && r.ctx->model.has_cl) run_generator_cl(r, B, T, z, in_lengths, g, o);
   else run_generator(r, B, T, z, in_lengths, g, o);
+}
+
+void tail_table_drop(vsp_ctx* ctx) {
+  if (ctx->tail_table) (void)hipFree(ctx->tail_table);
+  ctx->tail_table = nullptr;
+}
+
+// The silence table of a context whose weights have just been committed (model.h): the generator's ordinary launch sequence
+// on zero input of back + 1 + fwd frames, TAIL_BUILD_B speakers per run, frames [back, back + 1 + fwd) of every waveform
+// kept.  Synchronous on `s` (its scratch is allocated and freed here), so every later call finds a finished table whatever
+// stream it arrives on; not profiled, and the status word is not touched.  A configuration the table does not cover, or a
+// build that fails, leaves the context without one: the generator then runs as it did before.
+void tail_table_build(vsp_ctx* ctx, hipStream_t s) {
+  constexpr int TAIL_BUILD_B = 64;
+  tail_table_drop(ctx);
+  const vsp_config& c = ctx->cfg;
+  const Model& m = ctx->model;
+  if (!ctx->tail_table_on || !ctx->trim_tails || ctx->gen_mode != 1 || !m.has_cl || !ctx->arena) return;
+  if (c.n_speakers < 1 || c.n_speakers > 4096) return;
+  int back = 0, fwd = 0, reach1 = 0, fwd0 = 0;
+  generator_frame_dependence(c, ctx->resblock, m.g_pre.K, m.post_k, back, fwd);
+  generator_tail_reach(c, ctx->resblock, m.g_pre.K, m.post_k, reach1, fwd0);
+  const long up = total_upsample(c);
+  if ((size_t)fwd * up * sizeof(float) > 64 * 1024) return;
+  // nothing to gain, or stage 0's output would not be exact as far as the stages behind it read it
+  if (reach1 >= fwd + 1 || fwd0 + reach1 > fwd + 1) return;
+  const int T = back + 1 + fwd, Bc = std::min(c.n_speakers, TAIL_BUILD_B);
+  const size_t row = (size_t)(1 + fwd) * up;
+  const int64_t gen = dry_bytes(ctx, [&](Run& r) { run_gen(r, Bc, T, T3{}, nullptr, nullptr, nullptr); });
+  if (gen < 0) return;
+  const size_t z_bytes = (size_t)r256((int64_t)Bc * c.inter_channels * T * (int64_t)sizeof(float));
+  const size_t o_bytes = (size_t)r256((int64_t)Bc * T * up * (int64_t)sizeof(float));
+  char* scratch = nullptr;
+  float* table = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&table), (size_t)c.n_speakers * row * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&scratch), z_bytes + o_bytes + (size_t)gen);
+  if (e == hipSuccess) e = hipMemsetAsync(scratch, 0, z_bytes, s);
+  // (the build is no call of the caller's: no profile entries, no status flags, no error text left behind)
+  const bool prof_on = ctx->prof_on;
+  unsigned* const flags_dev = ctx->flags_dev;
+  const std::string err = ctx->err;
+  ctx->prof_on = false;
+  ctx->flags_dev = nullptr;
+  int rc = VSP_OK;
+  for (int s0 = 0; s0 < c.n_speakers && e == hipSuccess && rc == VSP_OK; s0 += Bc) {
+    const int nb = std::min(Bc, c.n_speakers - s0);
+    float* const z = reinterpret_cast<float*>(scratch);
+    float* const o = reinterpret_cast<float*>(scratch + z_bytes);
+    Ws ws(scratch + z_bytes + o_bytes, (size_t)gen, false);
+    Run r{ctx, s, ws};
+    run_gen(r, nb, T, ext(z, c.inter_channels, T), nullptr, ctx->arena + m.emb_g + (size_t)s0 * c.gin_channels, o);
+    rc = ws.overflow ? VSP_ERR_WORKSPACE : r.rc;
+    if (rc == VSP_OK)
+      e = hipMemcpy2DAsync(table + (size_t)s0 * row, row * sizeof(float), o + (size_t)back * up, (size_t)T * up * sizeof(float),
+                           row * sizeof(float), (size_t)nb, hipMemcpyDeviceToDevice, s);
+  }
+  ctx->prof_on = prof_on;
+  ctx->flags_dev = flags_dev;
+  ctx->err = err;
+  if (scratch || table) {
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+  }
+  if (scratch) (void)hipFree(scratch);
+  if (e != hipSuccess || rc != VSP_OK) {
+    if (table) (void)hipFree(table);
+    (void)hipGetLastError();
+    return;
+  }
+  ctx->tail_table = table;
+  ctx->tail_back = back; ctx->tail_fwd = fwd; ctx->tail_reach1 = reach1;
 }
 
 }  // namespace vsp
@@ -497,6 +620,15 @@ int vsp_generator_frame_dependence(const vsp_ctx* ctx, int* back, int* fwd) {
   if (!ctx || !back || !fwd) return VSP_ERR_ARG;
   generator_frame_dependence(ctx->cfg, ctx->resblock, ctx->model.g_pre.K > 0 ? ctx->model.g_pre.K : 7, ctx->model.post_k,
                              *back, *fwd);
+  return VSP_OK;
+}
+
+int vsp_generator_tail_extents(const vsp_ctx* ctx, int* back, int* fwd, int* reach1) {
+  if (!ctx || !back || !fwd || !reach1) return VSP_ERR_ARG;
+  const int pre_k = ctx->model.g_pre.K > 0 ? ctx->model.g_pre.K : 7;
+  int fwd0 = 0;
+  generator_frame_dependence(ctx->cfg, ctx->resblock, pre_k, ctx->model.post_k, *back, *fwd);
+  generator_tail_reach(ctx->cfg, ctx->resblock, pre_k, ctx->model.post_k, *reach1, fwd0);
   return VSP_OK;
 }
 

@@ -134,46 +134,94 @@ hipError_t launch_cl_img_zero_pads(uint16_t* img, int B, int C, int T, hipStream
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Trimmed tails (kernels.h).  gen_plan: the frames the generator computes per utterance.
-__global__ void gen_plan_kernel(const int64_t* __restrict__ lengths, int B, int T, int ext, int* __restrict__ glen) {
+// Trimmed tails and the silence table (kernels.h).
+// gen_tail_rows: one block per utterance; thread t compares g[b] with rows t, t + 256, .. of emb_g word by word (a memcmp:
+// -0 and +0 differ, equal NaN patterns match) and the block keeps the lowest matching row.
+__global__ void __launch_bounds__(256) gen_tail_rows_kernel(const unsigned* __restrict__ g, const unsigned* __restrict__ emb_g,
+                                                            int n_speakers, int gin, int* __restrict__ tail_row) {
+  __shared__ int best;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) best = 0x7fffffff;
+  __syncthreads();
+  const unsigned* gb = g + (size_t)b * gin;
+  for (int s = threadIdx.x; s < n_speakers; s += blockDim.x) {
+    const unsigned* row = emb_g + (size_t)s * gin;
+    int i = 0;
+    while (i < gin && row[i] == gb[i]) ++i;
+    if (i == gin) { atomicMin(&best, s); break; }   // (this thread's later rows are higher)
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) tail_row[b] = best == 0x7fffffff ? -1 : best;
+}
+hipError_t launch_gen_tail_rows(const float* g, const float* emb_g, int n_speakers, int gin, int B, int* tail_row, hipStream_t s) {
+  if (!g || !emb_g || !tail_row || n_speakers <= 0 || gin <= 0 || B <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gen_tail_rows_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const unsigned*>(g),
+                     reinterpret_cast<const unsigned*>(emb_g), n_speakers, gin, tail_row);
+  return hipGetLastError();
+}
+// gen_plan: the frames the generator computes per utterance, in stage 0 (glen0) and behind it (glen1).
+__global__ void gen_plan_kernel(const int64_t* __restrict__ lengths, int B, int T, int back, int fwd, int reach1,
+                                const int* __restrict__ tail_row, int* __restrict__ glen0, int* __restrict__ glen1) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   long len = lengths[b];
   len = len < 0 ? 0 : len;
-  const long e = len + ext;
-  glen[b] = e < T ? (int)e : T;
+  const long e = len + back + 1 + fwd;
+  const int e0 = e < T ? (int)e : T;
+  int e1 = e0;
+  if (tail_row && tail_row[b] >= 0 && len + back + fwd <= T) {
+    const long e1l = len + back + reach1;
+    e1 = e1l < e0 ? (int)e1l : e0;
+  }
+  glen0[b] = e0;
+  glen1[b] = e1;
 }
-hipError_t launch_gen_plan(const int64_t* lengths, int B, int T, int back, int fwd, int* glen, hipStream_t s) {
-  if (!lengths || !glen || B <= 0 || T <= 0 || back < 0 || fwd < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gen_plan_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lengths, B, T, back + 1 + fwd, glen);
+hipError_t launch_gen_plan(const int64_t* lengths, int B, int T, int back, int fwd, int reach1, const int* tail_row, int* glen0,
+                           int* glen1, hipStream_t s) {
+  if (!lengths || !glen0 || !glen1 || B <= 0 || T <= 0 || back < 0 || fwd < 0 || reach1 < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gen_plan_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lengths, B, T, back, fwd, reach1, tail_row, glen0, glen1);
   return hipGetLastError();
 }
-// gen_tail_fill: one block per utterance.  The computed tensor end -- frames [len + back + 1, len + back + 1 + fwd) -- is
-// read into LDS first (the steady-state fill overwrites it), then frames [len + back + 1, T - fwd) get the steady-state
-// frame len + back and frames [T - fwd, T) the saved tensor end.  Utterances the plan did not trim (glen[b] == T) are skipped.
+// gen_tail_fill: one block per utterance.
+//   Served by the table (glen1[b] < glen0[b]): frames [len + back, T - fwd) get the row's steady frame, frames [T - fwd, T) its
+//   end frames -- whatever conv_post wrote at and behind frame len + back (a tensor that ended early) is overwritten.
+//   Trimmed without the table (glen0[b] < T): the computed tensor end -- frames [len + back + 1, len + back + 1 + fwd) -- is
+//   read into LDS first (the steady-state fill overwrites it), then frames [len + back + 1, T - fwd) get the steady-state
+//   frame len + back and frames [T - fwd, T) the saved tensor end.
+//   Utterances the plan did not trim are skipped.
 __global__ void __launch_bounds__(1024) gen_tail_fill_kernel(float* __restrict__ o, long o_bs, const int64_t* __restrict__ lengths,
-                                                             const int* __restrict__ glen, int T, int back, int fwd, int up) {
+                                                             const int* __restrict__ glen0, const int* __restrict__ glen1,
+                                                             const int* __restrict__ tail_row, const float* __restrict__ table,
+                                                             int T, int back, int fwd, int up) {
   extern __shared__ float tail[];                 // [fwd * up]
   const int b = blockIdx.x;
-  if (glen[b] >= T) return;
+  const int g0 = glen0[b], g1 = glen1[b];
   long len = lengths[b];
   len = len < 0 ? 0 : len;
   float* ob = o + (size_t)b * o_bs;
   const long s0 = (len + back) * up;              // the steady-state frame
-  const long e0 = s0 + up;                        // the computed tensor end: fwd frames from here
+  const long fill_end = (long)(T - fwd) * up;
   const int nt = fwd * up;
+  if (g1 < g0) {
+    const float* row = table + (size_t)tail_row[b] * (size_t)(1 + fwd) * up;
+    for (long i = s0 + threadIdx.x; i < fill_end; i += blockDim.x) ob[i] = row[(i - s0) % up];
+    for (int i = threadIdx.x; i < nt; i += blockDim.x) ob[fill_end + i] = row[up + i];
+    return;
+  }
+  if (g0 >= T) return;
+  const long e0 = s0 + up;                        // the computed tensor end: fwd frames from here
   for (int i = threadIdx.x; i < nt; i += blockDim.x) tail[i] = ob[e0 + i];
   __syncthreads();
-  const long fill_end = (long)(T - fwd) * up;
   for (long i = e0 + threadIdx.x; i < fill_end; i += blockDim.x) ob[i] = ob[s0 + (i - e0) % up];
   for (int i = threadIdx.x; i < nt; i += blockDim.x) ob[fill_end + i] = tail[i];
 }
-hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, const int* glen, int B, int T, int back, int fwd,
-                                int up, hipStream_t s) {
-  if (!o || !lengths || !glen || B <= 0 || T <= 0 || back < 0 || fwd < 0 || up <= 0) return hipErrorInvalidValue;
+hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, const int* glen0, const int* glen1, const int* tail_row,
+                                const float* table, int B, int T, int back, int fwd, int up, hipStream_t s) {
+  if (!o || !lengths || !glen0 || !glen1 || B <= 0 || T <= 0 || back < 0 || fwd < 0 || up <= 0) return hipErrorInvalidValue;
   const size_t lds = (size_t)fwd * up * sizeof(float);
   if (lds > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gen_tail_fill_kernel, dim3(B), dim3(1024), lds, s, o, o_bs, lengths, glen, T, back, fwd, up);
+  hipLaunchKernelGGL(gen_tail_fill_kernel, dim3(B), dim3(1024), lds, s, o, o_bs, lengths, glen0, glen1, tail_row, table, T, back, fwd,
+                     up);
   return hipGetLastError();
 }
 

@@ -290,12 +290,24 @@ hipError_t launch_conv_post_cl(const float* x, long x_bs, int x_ts, const float*
 // models.py:720: z * x_mask), so its output there is a bias-driven signal that depends on the distance to the utterance's
 // end and to the tensor's end only: periodic in one frame once the receptive field away from both.
 // Output frame F depends on input frames [F - back, F + fwd] (api_generator.hip, generator_frame_dependence).
-//   gen_plan:  glen[b] = len[b] + back + 1 + fwd where that is < T (else T): the frames the generator computes for b;
-//   gen_tail_fill:  frames [len + back + 1, T - fwd) of o[b] = frame len + back (the steady state), frames
-//                   [T - fwd, T) = frames [len + back + 1, len + back + 1 + fwd) (the computed tensor end); up = samples per frame.
-hipError_t launch_gen_plan(const int64_t* lengths, int B, int T, int back, int fwd, int* glen, hipStream_t s);
-hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, const int* glen, int B, int T, int back, int fwd,
-                                int up, hipStream_t s);
+// Silence table (round 18): the steady-state frame and the fwd tensor-end frames depend on the weights and on g only, so a
+// context keeps them per speaker (model.h, vsp_ctx::tail_table: row s = [steady frame | fwd end frames] for g = emb_g[s]).
+// An utterance served by the table needs the zero-input context only as far as the layers BEHIND stage 0 see: reach1 = the
+// forward dependence, in frames, of the output on stage 0's output tensor (api_generator.hip, generator_support).
+//   gen_tail_rows:  tail_row[b] = the lowest s with g[b] == emb_g[s] bit for bit (gin words each), else -1; one block per b;
+//   gen_plan:  glen0[b] = len[b] + back + 1 + fwd where that is < T (else T): the frames conv_pre's successors up to and
+//              including stage 0 compute for b;  glen1[b] = len[b] + back + reach1 where tail_row[b] >= 0 and
+//              len[b] + back + fwd <= T (no frame before len + back sees the true tensor end), else glen0[b]: the frames
+//              stage 1 .. conv_post compute.  tail_row == NULL: glen1 = glen0;
+//   gen_tail_fill:  glen1[b] < glen0[b]: frames [len + back, T - fwd) of o[b] = the table row's steady frame, frames
+//                   [T - fwd, T) = its end frames;  else glen0[b] < T: frames [len + back + 1, T - fwd) = frame len + back (the
+//                   steady state), frames [T - fwd, T) = frames [len + back + 1, len + back + 1 + fwd) (the computed tensor
+//                   end, staged in LDS);  else nothing.  up = samples per frame; a table row is (1 + fwd) * up floats.
+hipError_t launch_gen_tail_rows(const float* g, const float* emb_g, int n_speakers, int gin, int B, int* tail_row, hipStream_t s);
+hipError_t launch_gen_plan(const int64_t* lengths, int B, int T, int back, int fwd, int reach1, const int* tail_row, int* glen0,
+                           int* glen1, hipStream_t s);
+hipError_t launch_gen_tail_fill(float* o, long o_bs, const int64_t* lengths, const int* glen0, const int* glen1, const int* tail_row,
+                                const float* table, int B, int T, int back, int fwd, int up, hipStream_t s);
 // Isolated mode (round 10; include/vispeech_hip.h, vsp_set_isolated): every utterance of a batch as a B = 1 call on its
 // own unpadded tensors computes it.  The generator then ENDS utterance b's tensor at its own length -- the same per-utterance
 // extent as above with no frames behind the utterance -- and the padded rest of the waveform is zero.

@@ -139,6 +139,15 @@ struct vsp_ctx {
                                   // kernels (conv_cols.hip; VSP_COLS=0: the row-tiled kernels + separate LayerNorm / pack launches)
   bool trim_tails = true;         // ragged batches: the generator runs each utterance to length + 2 halo + 1 frames and fills the
                                   // padded tail from the steady state (VSP_TRIM_TAILS=0: to the padded length; bit-identical)
+  // Silence table (round 18; VSP_TAIL_TABLE=0: off, second implementation, bit-identical): behind an utterance the generator's
+  // input is zero, so the steady-state frame and the fwd frames at the tensor's end depend on the weights and on g only.
+  // Row s = frames [back, back + 1 + fwd) of the generator's output for a zero input of back + 1 + fwd frames with
+  // g = emb_g[s], [n_speakers][(1 + fwd) * up] floats on the device, built when weights are committed (tail_table_build,
+  // api_generator.hip) and dropped whenever they change.  An utterance whose g IS a row of emb_g (compared bit for bit on the
+  // device) takes its padded tail from the table, and stages 1 .. of the generator end it at len + back + reach1 frames.
+  bool tail_table_on = true;
+  float* tail_table = nullptr;      // NULL: no table (switch off, not built, or the configuration is not covered): today's path
+  int tail_back = 0, tail_fwd = 0, tail_reach1 = 0;   // the extents the table was built for
   // round 5, measured and NOT adopted (profiles/r05_resblock_chains_on_side_streams.txt): the ResBlocks of a generator stage
   // (independent until their sum, reference models.py:276-285) on the caller's stream and two side streams of the context,
   // forked / joined by events, so that the ramp and the partial last round of one launch are covered by another chain's

@@ -780,6 +780,14 @@ class Engine:
                    "vsp_generator_frame_dependence")
         return int(b.value), int(f.value)
 
+    def generator_tail_extents(self):
+        """(back, fwd, reach1) (``vsp_generator_tail_extents``; 13 / 13 / 2 for configs/config.json): an utterance served by
+        the per-speaker silence table is computed to min(T, L + back + reach1) frames behind the first stage."""
+        b, f, r = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self.lib.vsp_generator_tail_extents(self.ctx, C.byref(b), C.byref(f), C.byref(r)), self.ctx,
+                   "vsp_generator_tail_extents")
+        return int(b.value), int(f.value), int(r.value)
+
     def generator_stream(self, z, g, chunk_frames: int = 256):
         """Streamed vocoder (BASELINE config 5): yields the waveform of ``z`` [B][C][T] chunk by chunk
         ([B,1,512*n] tensors) so that the first audio is available after one chunk instead of after
