@@ -577,6 +577,61 @@ int vsp_cl_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dila
 int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilation, const float* x, const float* w_host,
                const float* bias_host, const int64_t* lengths, int mask_in, int in_act, float in_slope, int act,
                const float* res, int mask_out, int split_f16, float* out);
+/* vsp_conv1d_ex (ABI 7, additive): the same kernels with the WHOLE fused epilogue the frame-rate layers use, on strided
+ * tensors, and a report of which kernel form the launch took -- what tests/test_frame_conv_epilogue.py and
+ * tests/test_conv_form_host.py drive.  Like vsp_conv1d: host weights packed per call, no context, synchronises.
+ *   y   = conv1d(prologue(x), w, dilation, padding = dilation (K - 1) / 2) + bias
+ *   rows >= split_row (split_row > 0):  out2[row - split_row] = (y [+ out2 when acc_prev2]) [* mask when mask_post2]
+ *   the other rows:  y + cond[b][row] -> relu (act 1) / WN gate (act 2, as vsp_conv1d: out has Cout / 2 rows)
+ *                    -> * mask when mask_pre -> * alpha -> + res -> + out when acc_prev -> / div -> * mask when mask_post
+ *   ln 1 / 2:  out = LayerNorm_channels(that + res, eps 1e-5) * ln_gamma + ln_beta   (res enters HERE, not above)
+ * out has split_row rows when split_row > 0 and out2 the Cout - split_row others.  res == out and res == x are allowed.
+ * Strides are in ELEMENTS; 0 = dense ([B][rows][T]); a channel stride >= T, a batch stride >= rows * channel stride: a
+ * tensor may be a channel window of a larger one, or have rows that are not 16-byte aligned.
+ * The WN gate reads its tanh / sigmoid halves from interleaved 32-row tiles: kernel row r holds the reference's row
+ * (r / 32 % 2) * Cout / 2 + (r / 64) * 32 + r % 32.  w and bias (host) are given in the REFERENCE's order and permuted here;
+ * cond is a device array the kernels read in place with the caller's stride and alignment, so the CALLER stores it in
+ * kernel row order.
+ * split_f16 1: split-f16 MFMA, 0: f32 MFMA.  cols 1: the column-tile kernel (conv_cols.hip) or VSP_ERR_UNSUPPORTED.
+ * ln 1: LayerNorm fused into the column-tile launch (needs cols 1; Cin = Cout = 192, no masks, no alpha / acc_prev);
+ * ln 2: the convolution into a scratch tensor, then the LayerNorm kernel (any Cout).
+ * plan_only: validate and fill *form_out, no device access, no HIP call (x is then any address of the alignment in
+ * question: the kernel choice reads it, nothing dereferences it).  form_out may be NULL otherwise.
+ * VSP_ERR_ARG: a null or contradictory pointer (out2 without split_row, masks without lengths, ln without gamma / beta
+ * or the reverse, ln 1 without cols), a gate with res or split_row, split_row outside (0, Cout), div == 0, a stride
+ * below the extent it spans, a length outside [0, T].  VSP_ERR_UNSUPPORTED: what the launchers refuse (even K, the halo,
+ * a gate with Cout % 64 or with mask_pre / alpha / acc_prev / div -- its epilogue is cond and mask_post --, split_row % 32,
+ * cols outside conv_cols.hip's shapes, ln with the gate, split_row or acc_prev) and a tensor whose largest byte offset
+ * (rows * channel stride + T) * 4 reaches 2^31.  B = 0 or T = 0: VSP_OK, nothing launched. */
+enum {
+  VSP_CONV_FORM_NONE = 0,
+  VSP_CONV_FORM_COLS = 1,         /* conv_cols_kernel */
+  VSP_CONV_FORM_COLS_LN = 2,      /* conv_cols_kernel with the fused LayerNorm */
+  VSP_CONV_FORM_GEMV = 3,         /* conv_t1_gemv: one time step */
+  VSP_CONV_FORM_SPLITK = 4,       /* conv_frame_splitk<k, gate> */
+  VSP_CONV_FORM_FRAME_SHORT = 5,  /* conv_frame_f16s<2, 1, 1, 2, k>: Nq <= 96 */
+  VSP_CONV_FORM_FRAME = 6,        /* conv_frame_f16s<2, 1, 1, 4, k> */
+  VSP_CONV_FORM_TILE = 7          /* conv1d_f32_mfma<mt, nt, wm, wn, f16s, ring, prune> */
+};
+typedef struct vsp_conv_form {
+  int32_t kernel;                 /* VSP_CONV_FORM_* */
+  int32_t mt, nt, wm, wn;         /* TILE: the tile tuple (rows 32 mt wm, columns 32 nt wn); FRAME*: likewise; else 0 */
+  int32_t f16s, ring, prune;      /* TILE: the instantiation's flags */
+  int32_t k, gate;                /* SPLITK / FRAME*: the tap-count instantiation; SPLITK: the gate instantiation */
+} vsp_conv_form;
+typedef struct vsp_conv1d_desc {
+  int32_t B, T, Cin, Cout, K, dilation;
+  int64_t x_bs, x_cs, o_bs, o_cs, r_bs, r_cs, o2_bs, o2_cs;     /* element strides, 0 = dense */
+  const float* x; float* out; const float* res; float* out2;    /* device */
+  const int64_t* lengths;                                       /* device [B] or NULL */
+  const float* cond; int64_t cond_bs;                           /* device, cond[b * cond_bs + kernel row] or NULL */
+  const float *w, *bias, *ln_gamma, *ln_beta;                   /* host: [Cout][Cin][K], [Cout], [Cout], [Cout] */
+  int32_t mask_in, in_act; float in_slope;
+  int32_t act, mask_pre; float alpha; int32_t acc_prev; float div;
+  int32_t mask_post, split_row, acc_prev2, mask_post2;
+  int32_t split_f16, cols, ln, plan_only;
+} vsp_conv1d_desc;
+int vsp_conv1d_ex(void* stream, const vsp_conv1d_desc* d, vsp_conv_form* form_out);
 /* vsp_cl_resblock: ResBlock1.forward without the mask (reference modules.py:210-223):
  *   for p < n_pairs:  x = x + conv2_p(lrelu(conv1_p(lrelu(x), dilations[p]))), slope 0.1
  * w_host[2 p], w_host[2 p + 1] = conv1_p, conv2_p dense [C][C][K]; bias_host likewise [C].

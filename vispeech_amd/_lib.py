@@ -88,6 +88,33 @@ class VspOutputRow(C.Structure):
                 ("out", C.c_void_p), ("out_fill", C.c_int64)]
 
 
+class VspConvForm(C.Structure):
+    """``vsp_conv_form``: the kernel a frame-rate convolution launch takes (``CONV_FORM_*``), the tile tuple and flags of
+    the throughput kernel, the tap-count / gate instantiation of the channel-split and latency kernels."""
+    _fields_ = [("kernel", C.c_int32), ("mt", C.c_int32), ("nt", C.c_int32), ("wm", C.c_int32), ("wn", C.c_int32),
+                ("f16s", C.c_int32), ("ring", C.c_int32), ("prune", C.c_int32), ("k", C.c_int32), ("gate", C.c_int32)]
+
+
+class VspConv1dDesc(C.Structure):
+    """``vsp_conv1d_desc`` of ``vsp_conv1d_ex`` (field order is ABI): shape, element strides (0 = dense), device and host
+    pointers, prologue, epilogue and path."""
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("K", C.c_int32),
+                ("dilation", C.c_int32),
+                ("x_bs", C.c_int64), ("x_cs", C.c_int64), ("o_bs", C.c_int64), ("o_cs", C.c_int64), ("r_bs", C.c_int64),
+                ("r_cs", C.c_int64), ("o2_bs", C.c_int64), ("o2_cs", C.c_int64),
+                ("x", C.c_void_p), ("out", C.c_void_p), ("res", C.c_void_p), ("out2", C.c_void_p), ("lengths", C.c_void_p),
+                ("cond", C.c_void_p), ("cond_bs", C.c_int64),
+                ("w", C.c_void_p), ("bias", C.c_void_p), ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p),
+                ("mask_in", C.c_int32), ("in_act", C.c_int32), ("in_slope", C.c_float),
+                ("act", C.c_int32), ("mask_pre", C.c_int32), ("alpha", C.c_float), ("acc_prev", C.c_int32), ("div", C.c_float),
+                ("mask_post", C.c_int32), ("split_row", C.c_int32), ("acc_prev2", C.c_int32), ("mask_post2", C.c_int32),
+                ("split_f16", C.c_int32), ("cols", C.c_int32), ("ln", C.c_int32), ("plan_only", C.c_int32)]
+
+
+# VSP_CONV_FORM_* (vsp_conv_form.kernel)
+(CONV_FORM_NONE, CONV_FORM_COLS, CONV_FORM_COLS_LN, CONV_FORM_GEMV, CONV_FORM_SPLITK, CONV_FORM_FRAME_SHORT, CONV_FORM_FRAME,
+ CONV_FORM_TILE) = range(8)
+
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
 OUTPUT_RATES_MAX = 8
 
@@ -184,6 +211,7 @@ SIGNATURES = {
     "vsp_spec_to_mel": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _P]),
     "vsp_cl_conv1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),
     "vsp_conv1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _I, _P]),
+    "vsp_conv1d_ex": (_I, [_P, C.POINTER(VspConv1dDesc), C.POINTER(VspConvForm)]),
     "vsp_cl_resblock": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_cl_resblock2": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_cl_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),

@@ -1732,10 +1732,25 @@ static long fr_splitk_blocks() {
 #endif
 }
 
-hipError_t launch_conv(const ConvArgs& a, int B, hipStream_t s) {
+// The decision tree of launch_conv (kernels.h): every threshold and predicate that picks a kernel lives here.
+static ConvForm form_of(int kernel, int k = 0, bool gate = false) {
+  ConvForm f{};
+  f.kernel = kernel; f.k = k; f.gate = gate;
+  if (kernel == VSP_CONV_FORM_FRAME_SHORT || kernel == VSP_CONV_FORM_FRAME) {
+    f.mt = 2; f.nt = 1; f.wm = 1; f.wn = kernel == VSP_CONV_FORM_FRAME ? 4 : 2; f.f16s = 1;
+  }
+  return f;
+}
+static ConvForm form_tile(int mt, int nt, int wm, int wn, bool f16s = false, bool ring = false, bool prune = false) {
+  ConvForm f{};
+  f.kernel = VSP_CONV_FORM_TILE; f.mt = mt; f.nt = nt; f.wm = wm; f.wn = wn; f.f16s = f16s; f.ring = ring; f.prune = prune;
+  return f;
+}
+
+ConvForm conv_form(const ConvArgs& a, int B) {
   if ((a.K - 1) * a.dil + 3 > CONV_HALO || a.K < 1 || a.Nq <= 0 || B <= 0 || (a.split_row & 31) ||
       (a.split_row && (a.ups_s > 0 || a.act == 2 || !a.out2)))
-    return hipErrorInvalidValue;
+    return form_of(VSP_CONV_FORM_NONE);
   const bool gate = a.act == 2;
   // (ring = 0: weights from global memory into registers, the round-1 form of these kernels; an experiment knob)
 #ifdef VSP_EXPERIMENTS
@@ -1745,42 +1760,38 @@ hipError_t launch_conv(const ConvArgs& a, int B, hipStream_t s) {
   constexpr bool ring = true;
 #endif
   if (ring && a.f16s) {
-    if (a.ups_s > 0) return hipErrorInvalidValue;
+    if (a.ups_s > 0) return form_of(VSP_CONV_FORM_NONE);
     // small grids: a 1x1 convolution whose weights have the column-tile image runs every row of a 64-column tile in one
     // block (conv_cols.hip) -- the row-tiled kernels below are 3-9 blocks per column tile, each a chain of window round trips
     // (a few blocks -- one utterance -- keep the row-tiled kernels: a column-tile block is one chain of round trips of ~10 us)
     if (a.wg && conv_cols_supported(a) && (long)B * ((a.Nq + 63) / 64) <= a.wg_max_blocks &&
-        (long)B * ((a.Nq + 63) / 64) >= a.wg_min_blocks) return launch_conv_cols(a, B, s);
+        (long)B * ((a.Nq + 63) / 64) >= a.wg_min_blocks) return form_of(VSP_CONV_FORM_COLS);
     // one time step, plain epilogue: the cond(g) projections
     if (a.K == 1 && a.T_in == 1 && a.Nq == 1 && a.Cin <= 2048 && a.act == 0 && !a.res && !a.cond && !a.in_mask && !a.in_act &&
-        !a.mask_pre && !a.mask_post && !a.acc_prev && !a.split_row && a.alpha == 1.f && a.div == 1.f) {
-      hipLaunchKernelGGL(conv_t1_gemv, dim3((a.M + 31) / 32, B), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
+        !a.mask_pre && !a.mask_post && !a.acc_prev && !a.split_row && a.alpha == 1.f && a.div == 1.f)
+      return form_of(VSP_CONV_FORM_GEMV);
     // the latency form (conv_frame_f16s) where the grid does not fill the chip: 64-row tiles, at most two rounds of blocks
     const bool vec = ((a.x_cs & 3) == 0) && ((a.x_bs & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.x) & 15) == 0);
     const float sl = a.in_act ? a.in_slope : 1.f;
     if (vec && (a.K - 1) * a.dil + 6 <= FR_HALO && (a.K > 1 || a.pad == 0) && sl >= 0.f && sl <= 1.f && (a.M > 32 || gate)) {
       const long blocks = (long)B * ((a.Nq + 127) / 128) * ((a.M + 63) / 64);
-      hipError_t e = hipSuccess;
+      // the tap counts the channel-split and latency kernels are instantiated for (other tap counts: the throughput kernel)
+      const bool k135 = a.K == 1 || a.K == 3 || a.K == 5;
       // a few dozen blocks: the channel-split form
       const long blocks64 = (long)B * ((a.Nq + 31) / 32) * ((a.M + 63) / 64);
       // (short time axes -- the phoneme-rate encoder of a whole batch -- have nothing better up to a few rounds of blocks)
-      if (blocks64 <= (a.Nq <= 96 ? 8 : 1) * fr_splitk_blocks() && a.nchunks >= 2) {
-        if (a.K == 1) return launch_splitk<1>(a, B, s);
-        if (a.K == 3) return launch_splitk<3>(a, B, s);
-        if (a.K == 5) return launch_splitk<5>(a, B, s);
-        // (k7 = the generator's conv_pre stays on ONE kernel at every size: the streamed vocoder and the locality
-        // tests compare generator outputs of different lengths bit for bit)
-      }
-      if (a.Nq <= 96) { if (blocks * 2 <= fr_max_blocks() && launch_frame_k<2, 1, 1, 2>(a, B, s, e)) return e; }
-      else if (blocks <= (a.K == 1 ? fr_max_blocks_k1() : fr_max_blocks())) { if (launch_frame_k<2, 1, 1, 4>(a, B, s, e)) return e; }
+      // (k7 = the generator's conv_pre stays on ONE kernel at every size: the streamed vocoder and the locality
+      // tests compare generator outputs of different lengths bit for bit)
+      if (blocks64 <= (a.Nq <= 96 ? 8 : 1) * fr_splitk_blocks() && a.nchunks >= 2 && k135)
+        return form_of(VSP_CONV_FORM_SPLITK, a.K, gate);
+      if (a.Nq <= 96) { if (blocks * 2 <= fr_max_blocks() && k135) return form_of(VSP_CONV_FORM_FRAME_SHORT, a.K); }
+      else if (blocks <= (a.K == 1 ? fr_max_blocks_k1() : fr_max_blocks())) { if (k135) return form_of(VSP_CONV_FORM_FRAME, a.K); }
     }
     if (a.M <= 32 && !gate) {
-      if (a.Nq >= 1024) return launch_tile<1, 4, 1, 4, true, true>(a, B, s);
-      return launch_tile<1, 1, 1, 2, true, true>(a, B, s);
+      if (a.Nq >= 1024) return form_tile(1, 4, 1, 4, true, true);
+      return form_tile(1, 1, 1, 2, true, true);
     }
-    if (a.Nq <= 96) return launch_tile<2, 1, 1, 2, true, true>(a, B, s);
+    if (a.Nq <= 96) return form_tile(2, 1, 1, 2, true, true);
     // M % 128 == 0: 128-row x 128-column tiles (two blocks per CU) for long time axes; utterance-sized ones take the
     // 64-row tile -- twice the blocks at three per CU fill the chip's rounds better than the halved window reuse
     // costs (C3 -0.15 ms, one utterance -11 %; the 5168-frame utterance +4 % if it did).
@@ -1796,37 +1807,98 @@ hipError_t launch_conv(const ConvArgs& a, int B, hipStream_t s) {
     const float sl_eff = a.in_act ? a.in_slope : 1.f;
     const bool prune_ok = vec_ok && sl_eff >= 0.f && sl_eff <= 1.f && a.ups_s == 0 && !(CONV_DIAG & 2);
     if (a.M <= 64 || (a.M % 128 != 0 && a.M < 256) || !wide) {
-      if (a.Nq >= 1024) return launch_tile<2, 2, 1, 4, true, true>(a, B, s);
-      if (prune_ok) return launch_tile<2, 1, 1, 4, true, true, true>(a, B, s);
-      return launch_tile<2, 1, 1, 4, true, true>(a, B, s);
+      if (a.Nq >= 1024) return form_tile(2, 2, 1, 4, true, true);
+      if (prune_ok) return form_tile(2, 1, 1, 4, true, true, true);
+      return form_tile(2, 1, 1, 4, true, true);
     }
-    if (prune_ok) return launch_tile<2, 2, 2, 2, true, true, true>(a, B, s);
-    return launch_tile<2, 2, 2, 2, true, true>(a, B, s);
+    if (prune_ok) return form_tile(2, 2, 2, 2, true, true, true);
+    return form_tile(2, 2, 2, 2, true, true);
   }
   if (a.f16s) {
     // split-f16 path: two accumulators per tile, so at most MT*NT = 4 tiles per wave
-    if (a.ups_s > 0) return hipErrorInvalidValue;
+    if (a.ups_s > 0) return form_of(VSP_CONV_FORM_NONE);
     if (a.M <= 32 && !gate) {
-      if (a.Nq >= 1024) return launch_tile<1, 4, 1, 4, true>(a, B, s);
-      return launch_tile<1, 1, 1, 2, true>(a, B, s);
+      if (a.Nq >= 1024) return form_tile(1, 4, 1, 4, true);
+      return form_tile(1, 1, 1, 2, true);
     }
-    if (a.Nq <= 96) return launch_tile<2, 1, 1, 2, true>(a, B, s);
+    if (a.Nq <= 96) return form_tile(2, 1, 1, 2, true);
     if (a.M <= 64 || (a.M % 128 != 0 && a.M < 256)) {
-      if (a.Nq >= 1024) return launch_tile<2, 2, 1, 4, true>(a, B, s);
-      return launch_tile<2, 1, 1, 4, true>(a, B, s);
+      if (a.Nq >= 1024) return form_tile(2, 2, 1, 4, true);
+      return form_tile(2, 1, 1, 4, true);
     }
-    return launch_tile<2, 2, 2, 2, true>(a, B, s);
+    return form_tile(2, 2, 2, 2, true);
   }
   if (a.M <= 32 && !gate) {
-    if (a.Nq >= 1024) return launch_tile<1, 4, 1, 4>(a, B, s);
-    return launch_tile<1, 1, 1, 2>(a, B, s);
+    if (a.Nq >= 1024) return form_tile(1, 4, 1, 4);
+    return form_tile(1, 1, 1, 2);
   }
-  if (a.Nq <= 96) return launch_tile<2, 1, 1, 2>(a, B, s);
+  if (a.Nq <= 96) return form_tile(2, 1, 1, 2);
   if (a.M <= 64 || (a.M % 128 != 0 && a.M < 256)) {
-    if (a.Nq >= 1024) return launch_tile<2, 4, 1, 4>(a, B, s);
-    return launch_tile<2, 1, 1, 4>(a, B, s);
+    if (a.Nq >= 1024) return form_tile(2, 4, 1, 4);
+    return form_tile(2, 1, 1, 4);
   }
-  return launch_tile<2, 2, 2, 2>(a, B, s);
+  return form_tile(2, 2, 2, 2);
+}
+
+// the throughput kernel's instantiations, by tile tuple and flags
+static hipError_t launch_tile_form(const ConvForm& f, const ConvArgs& a, int B, hipStream_t s) {
+  const int shape = f.mt * 1000 + f.nt * 100 + f.wm * 10 + f.wn;
+  if (f.prune) {
+    switch (shape) {
+      case 2114: return launch_tile<2, 1, 1, 4, true, true, true>(a, B, s);
+      case 2222: return launch_tile<2, 2, 2, 2, true, true, true>(a, B, s);
+    }
+  } else if (f.ring) {
+    switch (shape) {
+      case 1414: return launch_tile<1, 4, 1, 4, true, true>(a, B, s);
+      case 1112: return launch_tile<1, 1, 1, 2, true, true>(a, B, s);
+      case 2112: return launch_tile<2, 1, 1, 2, true, true>(a, B, s);
+      case 2214: return launch_tile<2, 2, 1, 4, true, true>(a, B, s);
+      case 2114: return launch_tile<2, 1, 1, 4, true, true>(a, B, s);
+      case 2222: return launch_tile<2, 2, 2, 2, true, true>(a, B, s);
+    }
+  } else if (f.f16s) {
+    switch (shape) {
+      case 1414: return launch_tile<1, 4, 1, 4, true>(a, B, s);
+      case 1112: return launch_tile<1, 1, 1, 2, true>(a, B, s);
+      case 2112: return launch_tile<2, 1, 1, 2, true>(a, B, s);
+      case 2214: return launch_tile<2, 2, 1, 4, true>(a, B, s);
+      case 2114: return launch_tile<2, 1, 1, 4, true>(a, B, s);
+      case 2222: return launch_tile<2, 2, 2, 2, true>(a, B, s);
+    }
+  } else {
+    switch (shape) {
+      case 1414: return launch_tile<1, 4, 1, 4>(a, B, s);
+      case 1112: return launch_tile<1, 1, 1, 2>(a, B, s);
+      case 2112: return launch_tile<2, 1, 1, 2>(a, B, s);
+      case 2414: return launch_tile<2, 4, 1, 4>(a, B, s);
+      case 2114: return launch_tile<2, 1, 1, 4>(a, B, s);
+      case 2222: return launch_tile<2, 2, 2, 2>(a, B, s);
+    }
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_conv(const ConvArgs& a, int B, hipStream_t s) {
+  const ConvForm f = conv_form(a, B);
+  hipError_t e = hipErrorInvalidValue;
+  switch (f.kernel) {
+    case VSP_CONV_FORM_COLS: return launch_conv_cols(a, B, s);
+    case VSP_CONV_FORM_GEMV:
+      hipLaunchKernelGGL(conv_t1_gemv, dim3((a.M + 31) / 32, B), dim3(256), 0, s, a);
+      return hipGetLastError();
+    case VSP_CONV_FORM_SPLITK:
+      switch (f.k) {
+        case 1: return launch_splitk<1>(a, B, s);
+        case 3: return launch_splitk<3>(a, B, s);
+        case 5: return launch_splitk<5>(a, B, s);
+      }
+      return e;
+    case VSP_CONV_FORM_FRAME_SHORT: (void)launch_frame_k<2, 1, 1, 2>(a, B, s, e); return e;
+    case VSP_CONV_FORM_FRAME: (void)launch_frame_k<2, 1, 1, 4>(a, B, s, e); return e;
+    case VSP_CONV_FORM_TILE: return launch_tile_form(f, a, B, s);
+    default: return e;
+  }
 }
 
 }  // namespace vsp

@@ -65,7 +65,13 @@ struct ConvArgs {
   long wg_min_blocks, wg_max_blocks;   // launch_conv takes the column-tile kernel for this range of 64-column tiles (B * ceil(Nq / 64))
 };
 
-// the tile shape is chosen from M and Nq
+// The kernel launch_conv takes for (a, B): which of the frame-rate kernels, and for the throughput kernel its tile tuple
+// and ring / prune flags (include/vispeech_hip.h: VSP_CONV_FORM_*; kernel == VSP_CONV_FORM_NONE: launch_conv answers
+// hipErrorInvalidValue).  A pure host function -- no HIP call -- of the arguments, B and the VSP_EXPERIMENTS knobs: the
+// ONE place the grid-size thresholds live, shared with the tests through vsp_conv1d_ex (ops.hip).
+using ConvForm = vsp_conv_form;
+ConvForm conv_form(const ConvArgs& a, int B);
+// the kernel and tile shape are chosen by conv_form
 hipError_t launch_conv(const ConvArgs& a, int B, hipStream_t s);
 // Column-tile form of a 1x1 convolution (conv_cols.hip): every output row of a 64-column tile in ONE block.
 // ln_gamma / ln_beta != NULL: out = LayerNorm_channels(conv + bias + res) * gamma + beta (M = Cin = 192, no masks).

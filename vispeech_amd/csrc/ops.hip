@@ -1,6 +1,6 @@
 // Stand-alone operators of the C-ABI (include/vispeech_hip.h): one convolution, ResBlock, up-convolution or attention on the
 // caller's tensors with host weights, no context -- what tests/test_cl_ops.py, test_c16_ops.py, test_resblock2_ops.py,
-// test_upsample_ops.py and test_attention_ops.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
+// test_upsample_ops.py, test_attention_ops.py, test_frame_conv_epilogue.py and test_conv_form_host.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
 // uses (cl_args.h).  Every call allocates, uploads and synchronises: test and measurement entry points, not a hot path.
 #include <algorithm>
 #include <cstdlib>
@@ -147,6 +147,129 @@ int vsp_conv1d(void* stream, int B, int T, int Cin, int Cout, int K, int dilatio
     return op_rc(e);
   }
   e = launch_conv(a, B, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return op_rc(e);
+}
+
+int vsp_conv1d_ex(void* stream, const vsp_conv1d_desc* dp, vsp_conv_form* form_out) {
+  if (!dp || (dp->plan_only && !form_out)) return VSP_ERR_ARG;
+  const vsp_conv1d_desc& d = *dp;
+  const int B = d.B, T = d.T, Cin = d.Cin, Cout = d.Cout, K = d.K;
+  const bool masks = d.mask_in || d.mask_pre || d.mask_post || d.mask_post2;
+  if (!d.x || !d.w || !d.out || B < 0 || T < 0 || d.act < 0 || d.act > 2 || (masks && !d.lengths) ||
+      (d.act == 2 && (d.res || d.split_row)) || d.split_f16 < 0 || d.split_f16 > 1 || d.cols < 0 || d.cols > 1 || d.ln < 0 ||
+      d.ln > 2 || (d.ln == 1 && !d.cols) || (d.ln != 0) != (d.ln_gamma != nullptr) || (d.ln != 0) != (d.ln_beta != nullptr) ||
+      (d.split_row != 0) != (d.out2 != nullptr) || ((d.acc_prev2 || d.mask_post2) && !d.split_row) || d.cond_bs < 0 ||
+      !(d.div != 0.f))
+    return VSP_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || K < 1 || !(K & 1) || d.dilation < 1 || (K - 1) * d.dilation + 3 > CONV_HALO ||
+      (d.act == 2 && (Cout % 64 || d.mask_pre || d.alpha != 1.f || d.acc_prev || d.div != 1.f)) ||   // (the gate's epilogue: cond, mask_post)
+      (d.ln && (d.act == 2 || d.split_row || d.acc_prev)) || (d.cols && !d.split_f16))
+    return VSP_ERR_UNSUPPORTED;
+  if (d.split_row && (d.split_row < 0 || d.split_row >= Cout)) return VSP_ERR_ARG;
+  if (d.split_row & 31) return VSP_ERR_UNSUPPORTED;
+  if (form_out) *form_out = vsp_conv_form{};
+  if (B == 0 || T == 0) return VSP_OK;
+  // rows of the destinations; strides in elements, 0 = dense
+  const int rows_out = d.act == 2 ? Cout / 2 : (d.split_row ? d.split_row : Cout), rows2 = d.split_row ? Cout - d.split_row : 0;
+  struct View { long bs, cs; int rows; };
+  auto view = [&](int64_t bs, int64_t cs, int rows) {
+    View v{(long)bs, (long)cs, rows};
+    if (!v.cs) v.cs = T;
+    if (!v.bs) v.bs = (long)rows * v.cs;
+    return v;
+  };
+  const View vx = view(d.x_bs, d.x_cs, Cin), vo = view(d.o_bs, d.o_cs, rows_out), vr = view(d.r_bs, d.r_cs, rows_out),
+             v2 = view(d.o2_bs, d.o2_cs, rows2);
+  for (const View* v : {&vx, &vo, &vr, &v2}) {
+    if (v == &vr && !d.res) continue;
+    if (v == &v2 && !d.split_row) continue;
+    if (v->cs < T || (B > 1 && v->bs < (long)(v->rows - 1) * v->cs + T)) return VSP_ERR_ARG;
+    // (the epilogues address a tensor with 32-bit byte offsets from the utterance's base)
+    if (((long)v->rows * v->cs + T) * 4 >= (1L << 31)) return VSP_ERR_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  ConvArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = d.x; a.x_bs = vx.bs; a.x_cs = vx.cs;
+  a.out = d.out; a.o_bs = vo.bs; a.o_cs = vo.cs;
+  // (ln: the residual enters the LayerNorm, not the convolution's epilogue)
+  if (d.res && (!d.ln || d.ln == 1)) { a.res = d.res; a.r_bs = vr.bs; a.r_cs = vr.cs; }
+  a.cond = d.cond; a.cond_bs = (long)d.cond_bs;
+  a.lengths = d.lengths;
+  a.Cin = Cin; a.M = Cout; a.K = K; a.dil = d.dilation; a.pad = d.dilation * (K - 1) / 2;
+  a.T_in = T; a.Nq = T; a.nchunks = (Cin + CONV_CK - 1) / CONV_CK;
+  a.in_mask = d.mask_in ? 1 : 0; a.in_act = d.in_act ? 1 : 0; a.in_slope = d.in_slope;
+  a.act = d.act; a.mask_pre = d.mask_pre ? 1 : 0; a.alpha = d.alpha; a.acc_prev = d.acc_prev ? 1 : 0; a.div = d.div;
+  a.mask_post = d.mask_post ? 1 : 0;
+  a.split_row = d.split_row; a.out2 = d.out2; a.o2_bs = v2.bs; a.o2_cs = v2.cs; a.acc_prev2 = d.acc_prev2 ? 1 : 0;
+  a.mask_post2 = d.mask_post2 ? 1 : 0;
+  a.f16s = d.split_f16 ? 1 : 0;
+  // ---- the kernel this launch takes
+  const bool cols_shape = K == 1 && Cin % 32 == 0 && Cout % 16 == 0;
+  vsp_conv_form form{};
+  if (d.cols) {
+    if (!cols_shape) return VSP_ERR_UNSUPPORTED;
+    static const uint16_t no_image = 0;
+    a.wg = &no_image;                                  // (any non-null address: conv_cols_supported reads no weight)
+    if (!conv_cols_supported(a)) return VSP_ERR_UNSUPPORTED;
+    if (d.ln == 1 && (Cout != 192 || Cin != 192 || a.mask_pre || a.mask_post || a.alpha != 1.f)) return VSP_ERR_UNSUPPORTED;
+    form.kernel = d.ln == 1 ? VSP_CONV_FORM_COLS_LN : VSP_CONV_FORM_COLS;
+    a.wg = nullptr;
+  } else {
+    form = conv_form(a, B);
+    if (form.kernel == VSP_CONV_FORM_NONE) return VSP_ERR_UNSUPPORTED;
+  }
+  if (form_out) *form_out = form;
+  if (d.plan_only) return VSP_OK;
+  if (int rc = check_lengths64(d.lengths, B, T, s); rc != VSP_OK) return rc;
+  // ---- weights and bias in kernel row order (the gate's interleaved 32-row tiles: weights.cpp packs WN in_layers the same way)
+  std::vector<float> wd((size_t)Cout * Cin * K), bd(Cout, 0.f);
+  for (int r = 0; r < Cout; ++r) {
+    int src = r;
+    if (d.act == 2) { const int tile = r / 32, in = r % 32; src = (tile & 1) * (Cout / 2) + (tile >> 1) * 32 + in; }
+    std::memcpy(&wd[(size_t)r * Cin * K], d.w + (size_t)src * Cin * K, (size_t)Cin * K * sizeof(float));
+    if (d.bias) bd[r] = d.bias[src];
+  }
+  DevBuf w, bias, wgd, scratch, gamma, beta;
+  hipError_t e = bias.alloc((size_t)Cout * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(bias.p, bd.data(), (size_t)Cout * 4, hipMemcpyHostToDevice, s);
+  std::vector<float> packed;
+  std::vector<uint16_t> wgh;
+  if (d.cols) {
+    wgh.resize(packed_g16_halfs(Cout, Cin, 1));
+    pack_g16_weights(wgh.data(), Cout, Cin, 1, wd.data());
+    if (e == hipSuccess) e = wgd.alloc(wgh.size() * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(wgd.p, wgh.data(), wgh.size() * 2, hipMemcpyHostToDevice, s);
+    a.wg = static_cast<const uint16_t*>(wgd.p);
+  } else {
+    packed.resize(packed_conv_floats(Cout, Cin, K));
+    if (d.split_f16) pack_conv_weights_f16s(packed.data(), Cout, Cin, K, wd.data());
+    else pack_conv_weights(packed.data(), Cout, Cin, K, wd.data());
+    if (e == hipSuccess) e = w.alloc(packed.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.p, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s);
+    a.wp = static_cast<const float*>(w.p);
+  }
+  if (d.bias) a.bias = static_cast<const float*>(bias.p);
+  if (d.ln) {
+    if (e == hipSuccess) e = gamma.alloc((size_t)Cout * 4);
+    if (e == hipSuccess) e = beta.alloc((size_t)Cout * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(gamma.p, d.ln_gamma, (size_t)Cout * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(beta.p, d.ln_beta, (size_t)Cout * 4, hipMemcpyHostToDevice, s);
+  }
+  if (d.ln == 2) {
+    // the two-launch path: the convolution into a dense scratch tensor, then LayerNorm(scratch + res) into out
+    if (e == hipSuccess) e = scratch.alloc((size_t)B * Cout * T * 4);
+    a.out = static_cast<float*>(scratch.p); a.o_bs = (long)Cout * T; a.o_cs = T;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);     // (pageable host memory: the vectors die with this frame)
+  if (e != hipSuccess) return op_rc(e);
+  if (d.ln == 1) e = launch_conv_cols(a, B, s, static_cast<const float*>(gamma.p), static_cast<const float*>(beta.p));
+  else if (d.cols) e = launch_conv_cols(a, B, s);
+  else e = launch_conv(a, B, s);
+  if (e == hipSuccess && d.ln == 2)
+    e = launch_layernorm(a.out, a.o_bs, a.o_cs, d.res, vr.bs, vr.cs, static_cast<const float*>(gamma.p),
+                         static_cast<const float*>(beta.p), d.out, vo.bs, vo.cs, B, Cout, T, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return op_rc(e);
 }
