@@ -915,6 +915,59 @@ int vsp_output_rows_plan(int L, int M, int H, int64_t x_first, int64_t n, int en
  * No sample outside a row's two segments is read; a refused call writes nothing. */
 int vsp_output_rows(vsp_ctx* ctx, void* stream, int B, const vsp_output_row* rows);
 
+/* ---- prosody (round 18, ABI 7, additive) ---------------------------------------------------- */
+/* Per-phoneme F0 and energy of a recording: the producer of the pitch_control / energy_control tensors vsp_encode reads,
+ * what the reference's data preparation (f0energy.py) computes with parselmouth and librosa.  The specification is this
+ * project's own (restated in fp64 in tests/prosody_ref.py) and is NOT bit-compatible with parselmouth:
+ * no path finder, no sinc interpolation.
+ *
+ * Constants: fs = VSP_PROSODY_FS, n_fft = VSP_PROSODY_NFFT; `hop` is the model's (512).  A row of n samples has
+ * F(n) = n / hop + 1 frames, frame k centred on sample hop * k, and needs n >= n_fft / 2 + 1 (for the reflection).
+ *   energy_k   reflect-pad the row by n_fft / 2 a side, s = x_pad[hop k .. hop k + n_fft) times the periodic Hann window;
+ *              e_k = sqrt(sum over the n_fft / 2 + 1 one-sided DFT bins of |X|^2), computed without a DFT as
+ *              sqrt((n_fft sum s^2 + (sum s)^2 + (sum (-1)^j s_j)^2) / 2).
+ *   f0_k       Boersma's autocorrelation method on the W = round(3 fs / floor) (made even) samples around hop k, zeros outside
+ *              the row: subtract their mean, lpk = max |s|, a = s w with w_j = 0.5 - 0.5 cos(2 pi (j + 0.5) / W),
+ *              r(t) = (r_a(t) / r_a(0)) * fl32(r_w(0) / r_w(t)); candidates are the integer lags t in [floor(fs / ceiling),
+ *              ceil(fs / floor)] with r(t) > r(t - 1) and r(t) >= r(t + 1), refined by a parabola (d, R), f = fs / (t + d),
+ *              strength S = R + octave_cost log2(f / floor); unvoiced strength U = voicing_threshold + max(0, 2 - (lpk / gpk) /
+ *              (silence_threshold / (1 + voicing_threshold))), gpk = the row's max |x - mean(x)|.  f0_k = f of the strongest
+ *              candidate (the lowest lag among equals) if S > U, else 0; 0 also when r_a(0) = 0, gpk = 0 or no candidate.
+ *   phonemes   F0: unvoiced frames between voiced ones are interpolated linearly, frames before the first voiced frame
+ *              take its value, frames behind the last take the last; with fewer than two voiced frames the contour stays.
+ *              Phoneme i of d_i > 0 frames gets the mean of its OWN frames [sum_{j<i} d_j, + d_i) of the interpolated
+ *              F0 / of the energy, one of d_i = 0 gets 0.  (f0energy.py averages in place and so reads averaged values
+ *              where sum_{j<i} d_j < i; this call averages the untouched contour.)
+ * params NULL: floor 80 Hz, ceiling 750 Hz, voicing threshold 0.6, silence threshold 0.03, octave cost 0.01.
+ * Refused (VSP_ERR_ARG): floor < 40 Hz (the window must fit in LDS), ceiling > fs / 4 or <= floor. */
+#define VSP_PROSODY_FS 44100
+#define VSP_PROSODY_NFFT 1280
+typedef struct vsp_prosody_params {
+  float floor_hz, ceiling_hz, voicing_threshold, silence_threshold, octave_cost;
+} vsp_prosody_params;
+/* F(n), host arithmetic only.  VSP_ERR_ARG: n_samples < n_fft / 2 + 1 or > 2^30, hop outside [1, 2048]. */
+int vsp_prosody_frames(int64_t n_samples, int hop);
+/* Workspace of either call below for B rows of up to L_max samples and Tp phonemes (VSP_ERR_ARG as a negative size). */
+int64_t vsp_prosody_workspace_bytes(int B, int64_t L_max, int hop, int Tp, const vsp_prosody_params* params);
+/* audio [B][audio_stride] float32 at fs (device, audio_stride >= L_max); n_samples_host [B]: HOST memory, read before the
+ * call returns -- row b is audio[b][0 .. n_b), n_fft / 2 + 1 <= n_b <= L_max, and nothing at or behind n_b is read.
+ * Outputs (device): f0_frames, energy_frames [B][F_max], F_max = F(L_max): row b's first F(n_b) columns, exact 0.0 behind;
+ * frames [B] = F(n_b).  A row's result does not depend on the rows it is batched with.  Two launches (row peak,
+ * contours) behind two small uploads into the workspace (the lengths and about 14 KB of window tables: copies from pageable
+ * host memory, which the runtime stages before they return -- they block the host for the copy, and the call cannot be
+ * captured into a graph); no allocation, no device synchronisation, caller's stream.
+ * Every refusal is decided on the host before anything is launched and names the row. */
+int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                         const int64_t* n_samples_host, const vsp_prosody_params* params, float* f0_frames,
+                         float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes);
+/* The contours of the call above (device, [B][F_max]) to per-phoneme means.  HOST memory, read before the call returns:
+ * frames_host [B] (F(n_b)), durations_host [B][Tp] (frames per phoneme) and lengths_host [B] (phonemes per row); a row
+ * needs 0 <= d and sum d <= frames_host[b] (VSP_ERR_ARG, naming the row).  Outputs (device): f0, energy [B][Tp], exact 0.0
+ * for a phoneme of no frames and behind lengths_host[b].  One launch behind one upload of the same kind. */
+int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const float* f0_frames, const float* energy_frames,
+                         const int64_t* frames_host, const int64_t* durations_host, const int64_t* lengths_host, float* f0,
+                         float* energy, void* workspace, int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

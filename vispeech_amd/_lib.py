@@ -115,6 +115,13 @@ class VspConv1dDesc(C.Structure):
 (CONV_FORM_NONE, CONV_FORM_COLS, CONV_FORM_COLS_LN, CONV_FORM_GEMV, CONV_FORM_SPLITK, CONV_FORM_FRAME_SHORT, CONV_FORM_FRAME,
  CONV_FORM_TILE) = range(8)
 
+class VspProsodyParams(C.Structure):
+    """``vsp_prosody_params``: pitch floor and ceiling (Hz), voicing threshold, silence threshold, octave cost."""
+    _fields_ = [("floor_hz", C.c_float), ("ceiling_hz", C.c_float), ("voicing_threshold", C.c_float),
+                ("silence_threshold", C.c_float), ("octave_cost", C.c_float)]
+
+
+PROSODY_FS, PROSODY_NFFT = 44100, 1280                              # VSP_PROSODY_*
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
 OUTPUT_RATES_MAX = 8
 
@@ -233,6 +240,12 @@ SIGNATURES = {
     "vsp_output_rows_plan": (_I, [_I, _I, _I, _I64, _I64, _I, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64),
                                   C.POINTER(_I64)]),
     "vsp_output_rows": (_I, [_P, _P, _I, C.POINTER(VspOutputRow)]),
+    "vsp_prosody_frames": (_I, [_I64, _I]),
+    "vsp_prosody_workspace_bytes": (_I64, [_I, _I64, _I, _I, C.POINTER(VspProsodyParams)]),
+    "vsp_prosody_contours": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), C.POINTER(VspProsodyParams), _P, _P, _P,
+                                  _P, _I64]),
+    "vsp_prosody_phonemes": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P, _P,
+                                  _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

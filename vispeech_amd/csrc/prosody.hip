@@ -1,0 +1,571 @@
+// Prosody from a recording (include/vispeech_hip.h, "prosody"): per-frame F0 by Boersma's 1993
+// autocorrelation method and per-frame energy (the L2 norm of a 1280-point one-sided STFT column), then both averaged over
+// each phoneme's frames -- what the reference's data preparation (f0energy.py) computes with parselmouth and librosa on the
+// CPU, restated as three launches.  Everything is ragged over the batch: row b is audio[b][0 .. n_b), nothing at or behind
+// n_b is read (loads are predicated, not selected after the fact), outputs behind a row's frames or phonemes are exact
+// zeros, and a row's result is a function of the row alone.
+//
+//   row_peak_kernel   one block per row, ONE pass: sum (double), min and max -> mean and gpk = max |x - mean|
+//                     (= max(fl(max - mean), fl(mean - min)): fl(x - mean) is monotone in x, so this IS the maximum of the
+//                     rounded differences).
+//   contour_kernel    one block = PR_FPB consecutive frames of a row, one wave per frame.  The block stages the raw span of
+//                     its frames once (consecutive frames share W - hop samples); each wave builds its mean-free windowed
+//                     frame a[] in LDS, zero padded behind W, and runs r_a(t) = sum_n a[n] a[n + t] for the lags
+//                     t0 + 4 lane + {0..3} (+ 256 per further lag block): per step of four n, ONE ds_read_b128 of a[n .. n+4)
+//                     at the same address in every lane (a broadcast), ONE ds_read_b128 of the next four a[n + t ..]
+//                     (consecutive across lanes, conflict free) and 16 FMAs; the sliding operand stays in registers.
+//                     Lag 0 is the frame's sum of squares.  Candidates, parabola, strengths and the argmax are a wave
+//                     reduction.  The three energy sums of the same frame (Parseval: no DFT) ride in the same launch.
+//                     Bound: the vector FMA pipe, the LDS close behind -- two lag blocks share each broadcast quad, 3 LDS
+//                     reads (12 LDS cycles) per 32 FMAs (64 SIMD cycles), three quarters of the LDS's cycles with four
+//                     SIMDs issuing -- and nothing here is a matrix product an MFMA could take in fp32 faster.
+//   phoneme_kernel    one wave per row: previous voiced frame by a forward wave64 max-scan, next voiced frame by a backward
+//                     min-scan, linear interpolation in between, then one lane per phoneme sums its OWN frames (no
+//                     prefix-sum differences: they would lose the digits the 1e-4 gate needs).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "kernels.h"
+#include "model.h"
+
+namespace {
+
+constexpr int PR_FS = VSP_PROSODY_FS, PR_NFFT = VSP_PROSODY_NFFT, PR_MIN_SAMPLES = PR_NFFT / 2 + 1;
+constexpr int PR_FPB = 4;               // frames (= waves) per block of the contour kernel
+constexpr int PR_LAGS_PER_WAVE = 256;   // four consecutive lags per lane
+constexpr int PR_MAX_HOP = 2048;
+constexpr int PR_MAX_B = 65535;
+constexpr int64_t PR_MAX_SAMPLES = (int64_t)1 << 30;
+
+struct Plan {
+  int W;      // samples of an analysis frame: round(3 fs / floor), made even
+  int W4;     // ... rounded up to a multiple of 4 (the zero padding starts at W)
+  int tmin, tmax;   // candidate lags [tmin, tmax] = [floor(fs / ceiling), ceil(fs / floor)]
+  int t0;     // first lag of lane 0: (tmin - 1) rounded down to a multiple of 4
+  int LB;     // lag blocks of 256: the lags t0 .. t0 + 256 LB - 1 cover tmin - 1 .. tmax + 1
+  int NA;     // floats of one wave's frame buffer: W4 + t0 + 256 LB + 4
+  vsp_prosody_params p;
+};
+
+const vsp_prosody_params kDefaults = {80.f, 750.f, 0.6f, 0.03f, 0.01f};
+
+// 0: ok; else the refused field (1 floor, 2 ceiling, 3 the thresholds)
+int make_plan(const vsp_prosody_params* params, Plan& pl) {
+  const vsp_prosody_params p = params ? *params : kDefaults;
+  if (!(p.floor_hz >= 40.f)) return 1;
+  if (!(p.ceiling_hz <= (float)PR_FS / 4) || !(p.ceiling_hz > p.floor_hz)) return 2;
+  if (!(p.voicing_threshold > -1.f && p.voicing_threshold < 1e6f) || !(p.silence_threshold > 0.f && p.silence_threshold < 1e6f) ||
+      !(std::fabs(p.octave_cost) < 1e6f))
+    return 3;
+  pl.p = p;
+  int W = (int)std::floor(3.0 * PR_FS / (double)p.floor_hz + 0.5);
+  W += W & 1;
+  pl.W = W;
+  pl.W4 = (W + 3) & ~3;
+  pl.tmin = (int)std::floor((double)PR_FS / (double)p.ceiling_hz);
+  pl.tmax = (int)std::ceil((double)PR_FS / (double)p.floor_hz);
+  pl.t0 = (pl.tmin - 1) & ~3;
+  pl.LB = (pl.tmax + 2 - pl.t0 + PR_LAGS_PER_WAVE - 1) / PR_LAGS_PER_WAVE;
+  pl.NA = pl.W4 + pl.t0 + PR_LAGS_PER_WAVE * pl.LB + 4;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ row peak
+struct RowStat { float mean, gpk; };
+
+__global__ void __launch_bounds__(1024) row_peak_kernel(const float* __restrict__ audio, int64_t a_bs,
+                                                        const int64_t* __restrict__ n_samples, RowStat* __restrict__ stat) {
+  __shared__ double s_sum[16];
+  __shared__ float s_min[16], s_max[16];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t n = n_samples[b];
+  const float* row = audio + (size_t)b * a_bs;
+  double sum = 0.0;
+  float mn = INFINITY, mx = -INFINITY;
+#pragma unroll 8
+  for (int64_t i = tid; i < n; i += 1024) {                        // (unrolled: eight loads in flight; the order of the adds stays)
+    const float v = row[i];
+    sum += (double)v;
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    sum += __shfl_xor(sum, off);
+    mn = fminf(mn, __shfl_xor(mn, off));
+    mx = fmaxf(mx, __shfl_xor(mx, off));
+  }
+  if (lane == 0) { s_sum[wave] = sum; s_min[wave] = mn; s_max[wave] = mx; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w) { sum += s_sum[w]; mn = fminf(mn, s_min[w]); mx = fmaxf(mx, s_max[w]); }
+    const float mean = n > 0 ? (float)(sum / (double)n) : 0.f;
+    // (a NaN sample makes gpk NaN or 0: every comparison below then says "unvoiced")
+    stat[b] = RowStat{mean, n > 0 ? fmaxf(mx - mean, mean - mn) : 0.f};
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ contours
+struct ContourArgs {
+  const float* audio; int64_t a_bs;
+  const int64_t* n_samples;      // [B] (device copy of the host's array)
+  const RowStat* stat;           // [B]
+  const float* hann;             // [PR_NFFT] periodic Hann
+  const float* win;              // [W] the analysis window w_n = 0.5 - 0.5 cos(2 pi (n + 0.5) / W)
+  const float* inv_rw;           // [256 LB] r_w(0) / r_w(t0 + i), 0 where the lag is not used
+  float* f0; float* energy;      // [B][F_max]
+  int64_t* frames;               // [B]
+  int F_max, hop;
+  int W, W4, tmin, tmax, t0, LB, NA;
+  int rbuf_off;                  // first float of the lag buffers in the block's LDS
+  float fs, floor_hz, vt, st_scale, oc;     // st_scale = silence_threshold / (1 + voicing_threshold)
+};
+
+// Four floats as one value: the hot loop works on whole vectors (shuffles of the two loaded quads, element-wise FMA), so
+// that each LDS read stays ONE ds_read_b128 -- written element by element, the compiler takes the vector loads apart into the
+// elements each unrolled step uses and puts them together again as 8-byte pairs, a quarter of the LDS rate per byte.
+typedef float pr_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ pr_f4 pr_lds128(const float* p) { return *reinterpret_cast<const pr_f4*>(p); }
+
+// acc[j][e] = sum_n a[n] a[n + t], t = the lag sp points at + 256 j + e, for NB lag blocks: per step of four n one
+// broadcast quad a[n .. n+4) and, per block, the next quad of the sliding operand (lo | hi = a[n + t .. n + t + 8)).
+template <int NB>
+__device__ __forceinline__ void pr_autocorr(const float* abuf, const float* sp, int W4, pr_f4 (&acc)[2]) {
+  pr_f4 lo[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    lo[j] = pr_lds128(sp + PR_LAGS_PER_WAVE * j);
+    acc[j] = pr_f4{0.f, 0.f, 0.f, 0.f};
+  }
+#pragma unroll 2
+  for (int i = 0; i < W4; i += 4) {
+    const pr_f4 c = pr_lds128(abuf + i);                                     // the same address in every lane
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const pr_f4 hi = pr_lds128(sp + PR_LAGS_PER_WAVE * j + i + 4);
+      acc[j] = __builtin_elementwise_fma(pr_f4(c.x), lo[j], acc[j]);
+      acc[j] = __builtin_elementwise_fma(pr_f4(c.y), __builtin_shufflevector(lo[j], hi, 1, 2, 3, 4), acc[j]);
+      acc[j] = __builtin_elementwise_fma(pr_f4(c.z), __builtin_shufflevector(lo[j], hi, 2, 3, 4, 5), acc[j]);
+      acc[j] = __builtin_elementwise_fma(pr_f4(c.w), __builtin_shufflevector(lo[j], hi, 3, 4, 5, 6), acc[j]);
+      lo[j] = hi;
+    }
+  }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+// grid (ceil(F_max / PR_FPB), B), 64 PR_FPB threads.  Dynamic LDS (floats): [raw span: W + (PR_FPB - 1) hop, to a multiple
+// of 4] [PR_FPB frame buffers of NA] and PR_FPB lag buffers of 256 LB + 4, over the raw span or behind.  Control flow is uniform over the block: a wave
+// whose frame lies behind the row's frames computes on the zeros the staging selected and stores 0.
+__global__ void __launch_bounds__(64 * PR_FPB) contour_kernel(const ContourArgs g) {
+  extern __shared__ __align__(16) float pr_smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, k0 = blockIdx.x * PR_FPB, k = k0 + wave;
+  const int64_t n = g.n_samples[b];
+  const int64_t F = n / g.hop + 1;
+  if (tid == 0 && blockIdx.x == 0) g.frames[b] = F;
+  float* f0_out = g.f0 + (size_t)b * g.F_max;
+  float* en_out = g.energy + (size_t)b * g.F_max;
+  if (k0 >= F) {                                                   // (uniform) the whole block lies behind the row's frames
+    if (lane == 0 && k < g.F_max) { f0_out[k] = 0.f; en_out[k] = 0.f; }
+    return;
+  }
+  const int span = g.W + (PR_FPB - 1) * g.hop, span4 = (span + 3) & ~3;
+  float* raw = pr_smem;
+  float* abuf = pr_smem + span4 + (size_t)wave * g.NA;
+  // (the lag buffers lie over the raw span where they fit: the span is dead once the frames are built, a barrier before)
+  float* rbuf = pr_smem + g.rbuf_off + (size_t)wave * (PR_LAGS_PER_WAVE * g.LB + 4);
+  const float* __restrict__ row = g.audio + (size_t)b * g.a_bs;
+  const bool live = k < F;                                         // (uniform over the wave)
+
+  // the raw span of the block's frames, zeros outside the row
+  const int64_t first = (int64_t)k0 * g.hop - g.W / 2;
+  for (int i = tid; i < span; i += 64 * PR_FPB) {
+    const int64_t j = first + i;
+    float v = 0.f;
+    if (j >= 0 && j < n) v = row[j];
+    raw[i] = v;
+  }
+
+  // energy of frame k: the frame's 1280 samples around hop k, reflected at the row's own two ends (n >= 641: one reflection
+  // reaches every index), times the periodic Hann window; sum s^2, sum s, sum (-1)^j s_j
+  float energy = 0.f;
+  if (live) {
+    float q = 0.f, s0 = 0.f, s1 = 0.f;
+    const int64_t e_first = (int64_t)k * g.hop - PR_NFFT / 2;
+    for (int j = lane; j < PR_NFFT; j += 64) {                     // (64 is even: a lane's samples all have the parity of the lane)
+      int64_t i = e_first + j;
+      if (i < 0) i = -i;
+      if (i >= n) i = 2 * (n - 1) - i;
+      const float s = row[i] * g.hann[j];
+      q = fmaf(s, s, q);
+      s0 += s;
+      s1 += s;
+    }
+    if (lane & 1) s1 = -s1;
+    q = wave_sum(q); s0 = wave_sum(s0); s1 = wave_sum(s1);
+    energy = sqrtf(0.5f * fmaf((float)PR_NFFT, q, fmaf(s0, s0, s1 * s1)));
+  }
+  __syncthreads();
+
+  // the frame: mean over its W samples (zeros outside the row included), local peak, window, zero padding
+  const float* x = raw + wave * g.hop;
+  float m = 0.f;
+  for (int i = lane; i < g.W; i += 64) m += x[i];
+  const float mean = wave_sum(m) / (float)g.W;
+  float lpk = 0.f, ra0 = 0.f;
+  for (int i = lane; i < g.NA; i += 64) {
+    float a = 0.f;
+    if (i < g.W) {
+      const float s = x[i] - mean;
+      lpk = fmaxf(lpk, fabsf(s));
+      a = s * g.win[i];
+      ra0 = fmaf(a, a, ra0);
+    }
+    abuf[i] = a;
+  }
+  lpk = wave_max(lpk);
+  ra0 = wave_sum(ra0);
+  __syncthreads();
+
+  // autocorrelation: lane l of lag block lb owns the lags t0 + 256 lb + 4 l + {0, 1, 2, 3}
+  // and, two lag blocks at a time, the same four of the next block: one broadcast read then feeds 32 FMAs (3 LDS reads per
+  // 32 FMAs instead of 4: with every SIMD of the CU issuing FMAs at its rate, 4 would ask the LDS for all of its cycles)
+  const float inv0 = ra0 > 0.f ? 1.f / ra0 : 0.f;
+  for (int lb = 0; lb < g.LB; lb += 2) {
+    const float* sp = abuf + g.t0 + PR_LAGS_PER_WAVE * lb + 4 * lane;
+    const int li = PR_LAGS_PER_WAVE * lb + 4 * lane;
+    pr_f4 acc[2];
+    if (lb + 1 < g.LB) pr_autocorr<2>(abuf, sp, g.W4, acc);                  // (uniform over the block)
+    else pr_autocorr<1>(abuf, sp, g.W4, acc);
+    // r(t) = (r_a(t) / r_a(0)) * (r_w(0) / r_w(t)); the table holds 0 for lags outside [tmin - 1, tmax + 1]
+    for (int j = 0; j < 2 && lb + j < g.LB; ++j) {
+      const float4 iw = *reinterpret_cast<const float4*>(g.inv_rw + li + PR_LAGS_PER_WAVE * j);
+      *reinterpret_cast<float4*>(rbuf + li + PR_LAGS_PER_WAVE * j) =
+          make_float4(acc[j].x * inv0 * iw.x, acc[j].y * inv0 * iw.y, acc[j].z * inv0 * iw.z, acc[j].w * inv0 * iw.w);
+    }
+  }
+  __syncthreads();
+
+  // candidates: local maxima of r at the integer lags of [tmin, tmax], refined by a parabola; the strongest wins, the
+  // lowest lag among equals
+  float best_s = -INFINITY, best_f = 0.f;
+  int best_t = 0x7fffffff;
+  for (int t = g.tmin + lane; t <= g.tmax; t += 64) {
+    const int i = t - g.t0;
+    const float rm = rbuf[i - 1], r0 = rbuf[i], rp = rbuf[i + 1];
+    if (r0 > rm && r0 >= rp) {
+      const float d = 0.5f * (rm - rp) / (rm - 2.f * r0 + rp);
+      const float R = r0 - 0.25f * (rm - rp) * d;
+      const float f = g.fs / ((float)t + d);
+      const float S = R + g.oc * log2f(f / g.floor_hz);
+      if (S > best_s) { best_s = S; best_f = f; best_t = t; }      // (t ascends within a lane: the first of equals stays)
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float os = __shfl_xor(best_s, off), of = __shfl_xor(best_f, off);
+    const int ot = __shfl_xor(best_t, off);
+    if (os > best_s || (os == best_s && ot < best_t)) { best_s = os; best_f = of; best_t = ot; }
+  }
+  if (lane == 0 && k < g.F_max) {
+    const float gpk = g.stat[b].gpk;
+    float f0 = 0.f;
+    if (live && ra0 > 0.f && gpk > 0.f && best_t != 0x7fffffff) {
+      const float U = g.vt + fmaxf(0.f, 2.f - (lpk / gpk) / g.st_scale);
+      if (best_s > U) f0 = best_f;
+    }
+    f0_out[k] = f0;
+    en_out[k] = live ? energy : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ phonemes
+struct PhonemeArgs {
+  const float* f0_frames; const float* energy_frames;   // [B][F_max]
+  const int32_t* start; const int32_t* dur;             // [B][Tp] first frame and frame count of every phoneme
+  const int32_t* frames; const int32_t* lengths;        // [B]
+  float* interp;                                        // [B][F_max] scratch: the interpolated contour
+  int32_t* prev;                                        // [B][F_max] scratch: previous voiced frame (-1: none)
+  float* f0; float* energy;                             // [B][Tp]
+  int F_max, Tp;
+};
+
+// grid B, one wave.  Frames at or behind frames[b] are not read.
+__global__ void __launch_bounds__(64) phoneme_kernel(const PhonemeArgs g) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int F = g.frames[b], Tl = g.lengths[b];
+  const float* __restrict__ f0 = g.f0_frames + (size_t)b * g.F_max;
+  const float* __restrict__ en = g.energy_frames + (size_t)b * g.F_max;
+  float* ip = g.interp + (size_t)b * g.F_max;
+  int32_t* pv = g.prev + (size_t)b * g.F_max;
+
+  // forward: the last voiced frame at or before i (inclusive max-scan of voiced ? i : -1, carried across the chunks)
+  int carry = -1, first_voiced = 0x7fffffff;
+  for (int base = 0; base < F; base += 64) {
+    const int i = base + lane;
+    int v = (i < F && f0[i] != 0.f) ? i : -1;
+    if (v >= 0) first_voiced = min(first_voiced, v);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(v, off);
+      if (lane >= off) v = max(v, o);
+    }
+    v = max(v, carry);
+    if (i < F) pv[i] = v;
+    carry = __shfl(v, 63);
+  }
+  const int last_voiced = carry;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) first_voiced = min(first_voiced, __shfl_xor(first_voiced, off));
+  const bool interpolate = last_voiced >= 0 && first_voiced != last_voiced;     // two voiced frames or more
+  __syncthreads();
+  // backward: the first voiced frame at or behind i (inclusive min-scan from the end), then the interpolation
+  carry = 0x7fffffff;
+  for (int base = ((F - 1) / 64) * 64; base >= 0; base -= 64) {
+    const int i = base + lane;
+    const float fi = i < F ? f0[i] : 0.f;
+    int v = (i < F && fi != 0.f) ? i : 0x7fffffff;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_down(v, off);
+      if (lane + off < 64) v = min(v, o);
+    }
+    v = min(v, carry);
+    if (i < F) {
+      float r = fi;
+      if (interpolate && fi == 0.f) {
+        const int p = pv[i], q = v;
+        if (p < 0) r = f0[q];                                       // before the first voiced frame
+        else if (q == 0x7fffffff) r = f0[p];                        // behind the last
+        else r = f0[p] + (f0[q] - f0[p]) * ((float)(i - p) / (float)(q - p));
+      }
+      ip[i] = r;
+    }
+    carry = __shfl(v, 0);
+  }
+  __syncthreads();
+  // one lane per phoneme: the mean of its own frames, summed directly
+  for (int j = lane; j < g.Tp; j += 64) {
+    float mf = 0.f, me = 0.f;
+    if (j < Tl) {
+      const int s = g.start[(size_t)b * g.Tp + j], d = g.dur[(size_t)b * g.Tp + j];
+      if (d > 0) {
+        float af = 0.f, ae = 0.f;
+        for (int i = s; i < s + d; ++i) { af += ip[i]; ae += en[i]; }
+        mf = af / (float)d;
+        me = ae / (float)d;
+      }
+    }
+    g.f0[(size_t)b * g.Tp + j] = mf;
+    g.energy[(size_t)b * g.Tp + j] = me;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+// The tables of a plan, in double on the host, stored as float32: the periodic Hann window of the energy frame, the
+// analysis window and the reciprocals of its normalised autocorrelation.  One entry is kept (a service uses one plan).
+struct Tables {
+  int W = 0, t0 = 0, LB = 0, tmin = 0, tmax = 0;
+  std::vector<float> host;       // [hann PR_NFFT][win W4][inv_rw 256 LB]
+};
+std::mutex g_tables_mu;
+Tables g_tables;
+
+void build_tables(const Plan& pl, Tables& t) {
+  t.W = pl.W; t.t0 = pl.t0; t.LB = pl.LB; t.tmin = pl.tmin; t.tmax = pl.tmax;
+  const int nl = PR_LAGS_PER_WAVE * pl.LB;
+  t.host.assign((size_t)PR_NFFT + pl.W4 + nl, 0.f);
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int j = 0; j < PR_NFFT; ++j) t.host[j] = (float)(0.5 - 0.5 * std::cos(two_pi * j / PR_NFFT));
+  std::vector<double> w(pl.W);
+  for (int i = 0; i < pl.W; ++i) {
+    w[i] = 0.5 - 0.5 * std::cos(two_pi * (i + 0.5) / pl.W);
+    t.host[PR_NFFT + i] = (float)w[i];
+  }
+  double r0 = 0.0;
+  for (int i = 0; i < pl.W; ++i) r0 += w[i] * w[i];
+  for (int lag = pl.tmin - 1; lag <= pl.tmax + 1; ++lag) {
+    double r = 0.0;
+    for (int i = 0; i + lag < pl.W; ++i) r += w[i] * w[i + lag];
+    t.host[(size_t)PR_NFFT + pl.W4 + (lag - pl.t0)] = (float)(r0 / r);
+  }
+}
+
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+struct ContourWs { size_t n_samples, stat, tables, end; };
+ContourWs contour_ws(int B, const Plan& pl) {
+  ContourWs w;
+  size_t cur = 0;
+  w.n_samples = cur; cur += align256((size_t)B * sizeof(int64_t));
+  w.stat = cur; cur += align256((size_t)B * sizeof(RowStat));
+  w.tables = cur; cur += align256(((size_t)PR_NFFT + pl.W4 + (size_t)PR_LAGS_PER_WAVE * pl.LB) * sizeof(float));
+  w.end = cur;
+  return w;
+}
+
+struct PhonemeWs { size_t ints, interp, prev, end; };
+PhonemeWs phoneme_ws(int B, int64_t F_max, int Tp) {
+  PhonemeWs w;
+  size_t cur = 0;
+  w.ints = cur; cur += align256(((size_t)2 * B * Tp + 2 * (size_t)B) * sizeof(int32_t));     // start, dur, frames, lengths
+  w.interp = cur; cur += align256((size_t)B * F_max * sizeof(float));
+  w.prev = cur; cur += align256((size_t)B * F_max * sizeof(int32_t));
+  w.end = cur;
+  return w;
+}
+
+std::atomic<uint64_t> g_contour_lds_done{0};
+
+}  // namespace
+
+int vsp_prosody_frames(int64_t n_samples, int hop) {
+  if (hop < 1 || hop > PR_MAX_HOP || n_samples < PR_MIN_SAMPLES || n_samples > PR_MAX_SAMPLES) return VSP_ERR_ARG;
+  return (int)(n_samples / hop) + 1;
+}
+
+int64_t vsp_prosody_workspace_bytes(int B, int64_t L_max, int hop, int Tp, const vsp_prosody_params* params) {
+  Plan pl;
+  if (B < 1 || B > PR_MAX_B || Tp < 0 || make_plan(params, pl)) return VSP_ERR_ARG;
+  const int F_max = vsp_prosody_frames(L_max, hop);
+  if (F_max < 0) return VSP_ERR_ARG;
+  return (int64_t)std::max(contour_ws(B, pl).end, phoneme_ws(B, F_max, std::max(Tp, 1)).end);
+}
+
+int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                         const int64_t* n_samples_host, const vsp_prosody_params* params, float* f0_frames,
+                         float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  Plan pl;
+  if (const int bad = make_plan(params, pl)) {
+    if (bad == 1) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: the pitch floor must be at least 40 Hz (the analysis window must fit in LDS)");
+    if (bad == 2) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: the pitch ceiling must be above the floor and at most fs / 4 = %d Hz", PR_FS / 4);
+    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: thresholds out of range (the silence threshold must be positive)");
+  }
+  if (B < 1 || B > PR_MAX_B || !n_samples_host) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: 1 <= B <= %d rows and their lengths", PR_MAX_B);
+  const int F_max = vsp_prosody_frames(L_max, hop);
+  if (F_max < 0)
+    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: 1 <= hop <= %d and %d <= L_max <= 2^30 samples", PR_MAX_HOP, PR_MIN_SAMPLES);
+  for (int b = 0; b < B; ++b)
+    if (n_samples_host[b] < PR_MIN_SAMPLES || n_samples_host[b] > L_max)
+      return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: row %d has %lld samples: a row needs %d (n_fft / 2 + 1, for the reflection) "
+                       "to L_max = %lld", b, (long long)n_samples_host[b], PR_MIN_SAMPLES, (long long)L_max);
+  if (!audio || !f0_frames || !energy_frames || !frames || audio_stride < L_max)
+    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: null pointer, or audio_stride < L_max");
+  const ContourWs lay = contour_ws(B, pl);
+  if (!workspace || workspace_bytes < (int64_t)lay.end)
+    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_contours: the workspace needs %lld bytes", (long long)lay.end);
+  const int span4 = (pl.W + (PR_FPB - 1) * hop + 3) & ~3;
+  // the lag buffers share the raw span's floats where they fit (48 KiB per block at the defaults: three blocks per CU)
+  const int rbuf_floats = PR_FPB * (PR_LAGS_PER_WAVE * pl.LB + 4);
+  const bool rbuf_over_span = rbuf_floats <= span4;
+  const int rbuf_off = rbuf_over_span ? 0 : span4 + PR_FPB * pl.NA;
+  const size_t lds = ((size_t)span4 + (size_t)PR_FPB * pl.NA + (rbuf_over_span ? 0 : (size_t)rbuf_floats)) * sizeof(float);
+  if (lds > 160 * 1024) return ctx->fail(VSP_ERR_UNSUPPORTED, "vsp_prosody_contours: %zu bytes of LDS", lds);
+
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  // The uploads here and in vsp_prosody_phonemes read PAGEABLE host memory -- the caller's array, the process-wide table
+  // whose lock is dropped right after the call, a local vector -- and rest on the runtime reading such memory into its own
+  // staging buffer before hipMemcpyAsync returns (as api_frame.hip does for the noise seeds and the row controls).  That
+  // blocks the host for the copy, and it is why these calls cannot be captured into a graph.
+  hipError_t e = hipMemcpyAsync(ws + lay.n_samples, n_samples_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(g_tables_mu);
+    Tables& t = g_tables;
+    if (t.W != pl.W || t.t0 != pl.t0 || t.LB != pl.LB || t.tmin != pl.tmin || t.tmax != pl.tmax) build_tables(pl, t);
+    e = hipMemcpyAsync(ws + lay.tables, t.host.data(), t.host.size() * sizeof(float), hipMemcpyHostToDevice, s);
+  }
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "vsp_prosody_contours (tables): %s", hipGetErrorString(e));
+  const int64_t* n_dev = reinterpret_cast<const int64_t*>(ws + lay.n_samples);
+  RowStat* stat = reinterpret_cast<RowStat*>(ws + lay.stat);
+  const float* tab = reinterpret_cast<const float*>(ws + lay.tables);
+  hipLaunchKernelGGL(row_peak_kernel, dim3(B), dim3(1024), 0, s, audio, audio_stride, n_dev, stat);
+  e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "row_peak_kernel: %s", hipGetErrorString(e));
+  if (lds > 64 * 1024) {
+    // (the size follows the caller's floor and hop; the attribute is set ONCE per device, so it is the cap checked above,
+    // the largest request the kernel can get -- a later call with a lower floor must not find a smaller one)
+    e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel), 160 * 1024, g_contour_lds_done);
+    if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel (LDS): %s", hipGetErrorString(e));
+  }
+  ContourArgs a;
+  a.audio = audio; a.a_bs = audio_stride; a.n_samples = n_dev; a.stat = stat;
+  a.hann = tab; a.win = tab + PR_NFFT; a.inv_rw = tab + PR_NFFT + pl.W4;
+  a.f0 = f0_frames; a.energy = energy_frames; a.frames = frames;
+  a.F_max = F_max; a.hop = hop;
+  a.W = pl.W; a.W4 = pl.W4; a.tmin = pl.tmin; a.tmax = pl.tmax; a.t0 = pl.t0; a.LB = pl.LB; a.NA = pl.NA; a.rbuf_off = rbuf_off;
+  a.fs = (float)PR_FS; a.floor_hz = pl.p.floor_hz; a.vt = pl.p.voicing_threshold;
+  a.st_scale = pl.p.silence_threshold / (1.f + pl.p.voicing_threshold); a.oc = pl.p.octave_cost;
+  hipLaunchKernelGGL(contour_kernel, dim3((F_max + PR_FPB - 1) / PR_FPB, B), dim3(64 * PR_FPB), lds, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}
+
+int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const float* f0_frames, const float* energy_frames,
+                         const int64_t* frames_host, const int64_t* durations_host, const int64_t* lengths_host, float* f0,
+                         float* energy, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (B < 1 || B > PR_MAX_B || F_max < 1 || Tp < 1 || (int64_t)B * Tp > ((int64_t)1 << 28) || !frames_host || !durations_host ||
+      !lengths_host)
+    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_phonemes: 1 <= B <= %d rows, F_max >= 1, Tp >= 1, and the host arrays", PR_MAX_B);
+  std::vector<int32_t> ints((size_t)2 * B * Tp + 2 * (size_t)B, 0);
+  int32_t* start = ints.data();
+  int32_t* dur = start + (size_t)B * Tp;
+  int32_t* fr = dur + (size_t)B * Tp;
+  int32_t* len = fr + B;
+  for (int b = 0; b < B; ++b) {
+    if (frames_host[b] < 1 || frames_host[b] > F_max || lengths_host[b] < 0 || lengths_host[b] > Tp)
+      return ctx->fail(VSP_ERR_ARG, "vsp_prosody_phonemes: row %d: 1 <= frames <= F_max and 0 <= length <= Tp", b);
+    int64_t pos = 0;
+    for (int j = 0; j < (int)lengths_host[b]; ++j) {
+      const int64_t d = durations_host[(size_t)b * Tp + j];
+      if (d < 0 || d > frames_host[b] || pos + d > frames_host[b])
+        return ctx->fail(VSP_ERR_ARG, "vsp_prosody_phonemes: row %d: its durations sum to more than its %lld frames (or one is "
+                         "negative) at phoneme %d", b, (long long)frames_host[b], j);
+      start[(size_t)b * Tp + j] = (int32_t)pos;
+      dur[(size_t)b * Tp + j] = (int32_t)d;
+      pos += d;
+    }
+    fr[b] = (int32_t)frames_host[b];
+    len[b] = (int32_t)lengths_host[b];
+  }
+  if (!f0_frames || !energy_frames || !f0 || !energy) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_phonemes: null pointer");
+  const PhonemeWs lay = phoneme_ws(B, F_max, Tp);
+  if (!workspace || workspace_bytes < (int64_t)lay.end)
+    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_phonemes: the workspace needs %lld bytes", (long long)lay.end);
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  hipError_t e = hipMemcpyAsync(ws + lay.ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "vsp_prosody_phonemes (durations): %s", hipGetErrorString(e));
+  PhonemeArgs a;
+  a.f0_frames = f0_frames; a.energy_frames = energy_frames;
+  a.start = reinterpret_cast<const int32_t*>(ws + lay.ints);
+  a.dur = a.start + (size_t)B * Tp;
+  a.frames = a.dur + (size_t)B * Tp;
+  a.lengths = a.frames + B;
+  a.interp = reinterpret_cast<float*>(ws + lay.interp);
+  a.prev = reinterpret_cast<int32_t*>(ws + lay.prev);
+  a.f0 = f0; a.energy = energy; a.F_max = F_max; a.Tp = Tp;
+  hipLaunchKernelGGL(phoneme_kernel, dim3(B), dim3(64), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "phoneme_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}

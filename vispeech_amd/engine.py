@@ -1230,6 +1230,102 @@ class Engine:
                             outs=[audio[b] for b in range(B)])
         return audio, n_out
 
+    # ------------------------------------------------------------------ prosody from a recording
+    @staticmethod
+    def _prosody_params(params):
+        """None, a ``VspProsodyParams``, or a mapping / sequence of (floor_hz, ceiling_hz, voicing_threshold,
+        silence_threshold, octave_cost) -- missing keys take the defaults -- as a ``VspProsodyParams`` or None."""
+        if params is None or isinstance(params, _lib.VspProsodyParams):
+            return params
+        names = [f[0] for f in _lib.VspProsodyParams._fields_]
+        vals = dict(zip(names, (80.0, 750.0, 0.6, 0.03, 0.01)))
+        if isinstance(params, Mapping):
+            unknown = set(params) - set(names)
+            if unknown:
+                raise ValueError(f"prosody params: unknown {sorted(unknown)}; the fields are {names}")
+            vals.update(params)
+        else:
+            params = list(params)
+            if len(params) != len(names):
+                raise ValueError(f"prosody params: {len(names)} values {names}")
+            vals = dict(zip(names, params))
+        return _lib.VspProsodyParams(*(float(vals[k]) for k in names))
+
+    def prosody_frames(self, n_samples: int, hop_length: Optional[int] = None) -> int:
+        """``vsp_prosody_frames``: ``n_samples // hop + 1``; a recording below 641 samples is refused.  Host only."""
+        F = int(self.lib.vsp_prosody_frames(int(n_samples), self._hop(hop_length)))
+        if F < 0:
+            raise ValueError(f"prosody: a recording of {int(n_samples)} samples: it needs {_lib.PROSODY_NFFT // 2 + 1} to 2^30")
+        return F
+
+    def prosody_contours(self, audio, n_samples, params=None, hop_length: Optional[int] = None):
+        """``vsp_prosody_contours``: recordings of different lengths in one padded ``audio`` [B, L] at the model's rate; row
+        b is ``audio[b, :n_samples[b]]`` (what lies behind is never read).  Returns ``(f0_frames, energy_frames, frames,
+        frames_host)``: two ``[B, F_max]`` float32 tensors -- per-frame F0 in Hz (0: unvoiced) and energy, row b's first
+        ``frames[b] = n_samples[b] // hop + 1`` columns, exact zeros behind --, the frame counts on the device and as host
+        ints (host arithmetic: nothing is read back).  ``params``: ``_prosody_params``."""
+        a = _dev_f32(audio, self.device)
+        if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+            raise ValueError("audio must be [B, L] (rows padded to a common length, contiguous)")
+        B, stride = a.shape[0], (a.stride(0) if a.shape[0] > 1 else a.shape[1])
+        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        if len(n_host) != B or B == 0:
+            raise ValueError(f"n_samples must have {B} entries (at least one row)")
+        hop = self._hop(hop_length)
+        for b, n in enumerate(n_host):
+            if n > a.shape[1]:
+                raise ValueError(f"row {b}: n_samples {n} > audio.shape[1] = {a.shape[1]}")
+        L_max = max(n_host)
+        frames_host = []
+        for b, n in enumerate(n_host):
+            F = int(self.lib.vsp_prosody_frames(n, hop))
+            if F < 0:
+                raise ValueError(f"row {b}: a recording of {n} samples: prosody needs {_lib.PROSODY_NFFT // 2 + 1} to 2^30")
+            frames_host.append(F)
+        F_max = max(frames_host)
+        p = self._prosody_params(params)
+        f0 = self._f(B, F_max)
+        en = self._f(B, F_max)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        ws = self._workspace("prosody", self.lib.vsp_prosody_workspace_bytes(B, L_max, hop, 1, p))
+        n_arr = (C.c_int64 * B)(*n_host)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_prosody_contours(self.ctx, self._stream(), B, L_max, hop, _ptr(a), int(stride), n_arr, p, _ptr(f0),
+                                               _ptr(en), _ptr(frames), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_prosody_contours")
+        return f0, en, frames, frames_host
+
+    def prosody_phonemes(self, f0_frames, energy_frames, frames_host, durations, lengths):
+        """``vsp_prosody_phonemes``: the contours of ``prosody_contours`` to per-phoneme means.  ``durations`` [B, Tp] (frames
+        per phoneme, integers) and ``lengths`` [B] are read on the HOST (a device tensor is copied back: bring host arrays
+        on the request path); row b needs ``sum(durations[b, :lengths[b]]) <= frames_host[b]``.  Returns ``(f0, energy)``,
+        ``[B, Tp]`` float32 on the device: F0 interpolated across unvoiced frames, then both averaged over each phoneme's own
+        frames; exact 0 for a phoneme of no frames and behind ``lengths[b]``."""
+        f0f, enf = _dev_f32(f0_frames, self.device), _dev_f32(energy_frames, self.device)
+        if f0f.dim() != 2 or f0f.shape != enf.shape or not f0f.is_contiguous() or not enf.is_contiguous():
+            raise ValueError("f0_frames and energy_frames must be contiguous [B, F_max] tensors of one shape")
+        B, F_max = f0f.shape
+        d = durations.detach().cpu().numpy() if torch.is_tensor(durations) else np.asarray(durations)
+        d = d.reshape(B, -1)
+        di = np.ascontiguousarray(d, dtype=np.int64)
+        if not np.array_equal(di, d):
+            raise ValueError("durations must be whole numbers of frames")
+        Tp = di.shape[1]
+        ln = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        fh = [int(x) for x in frames_host]
+        if len(ln) != B or len(fh) != B or Tp < 1:
+            raise ValueError(f"lengths and frames_host must have {B} entries, durations at least one column")
+        f0, en = self._f(B, Tp), self._f(B, Tp)
+        # (the size is monotone in every argument: F_max frames cover any row of the batch)
+        ws = self._workspace("prosody", self.lib.vsp_prosody_workspace_bytes(B, max((F_max - 1) * self._hop(None), 641),
+                                                                             self._hop(None), Tp, None))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_prosody_phonemes(self.ctx, self._stream(), B, F_max, Tp, _ptr(f0f), _ptr(enf), (C.c_int64 * B)(*fh),
+                                               di.ctypes.data_as(C.POINTER(C.c_int64)), (C.c_int64 * B)(*ln), _ptr(f0), _ptr(en),
+                                               _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_prosody_phonemes")
+        return f0, en
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

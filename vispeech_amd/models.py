@@ -188,6 +188,29 @@ class SynthesizerTrn:
         r = eng.convert(audio, n_samples, sid_src, sid_tgt, noise=noise, noise_seed=noise_seed, noise_scale=noise_scale)
         return r["o_hat"], r["y_mask"].to(torch.float32), (r["z"], r["z_p"], r["z_hat"])
 
+    @torch.no_grad()
+    def prosody_from_audio(self, audio, n_samples, durations, phonemes_lengths, *, sample_rate: Optional[int] = None,
+                           encoding=None, params=None):
+        """Per-phoneme F0 and energy of recordings -- what the reference's data preparation (f0energy.py) writes into a
+        filelist row -- for a batch of recordings of different lengths: ``audio`` [B, L] at the model's rate, row b the
+        recording ``audio[b, :n_samples[b]]`` (what lies behind is never read), ``durations`` [B, Tp] the frames of each of
+        its ``phonemes_lengths[b]`` phonemes (whole numbers; ``sum <= n_samples[b] // hop + 1``).  Returns ``(f0, energy)``,
+        both ``[B, Tp]`` float32 on the device, exact 0 for a phoneme of no frames and behind a row's phonemes: pass them
+        straight to ``infer(..., isolated=True, duration_control=durations, pitch_control=f0, energy_control=energy)`` to
+        speak a text with the melody and loudness of the recording.  F0 is Boersma's autocorrelation method as DESIGN.md
+        section 4m states it (``params``: floor_hz, ceiling_hz, voicing_threshold, silence_threshold, octave_cost; None: 80,
+        750, 0.6, 0.03, 0.01) -- NOT bit-compatible with parselmouth.  Works without the ``enc_q.*`` tensors.
+        ``sample_rate`` / ``encoding``: as in ``convert_audio`` -- ``audio`` is raw at that rate, ``n_samples`` counts input
+        samples, and the batch goes through the input stage (``Engine.input_batch``) first."""
+        eng = self._engine
+        if sample_rate is not None or encoding is not None:
+            rate = int(self.dims.sampling_rate if sample_rate is None else sample_rate)
+            if rate not in eng.input_rates:
+                eng.configure_input(rate)
+            audio, n_samples = eng.input_batch(audio, n_samples, rate, 0 if encoding is None else encoding)
+        f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n_samples, params)
+        return eng.prosody_phonemes(f0_frames, energy_frames, frames_host, durations, phonemes_lengths)
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

@@ -66,14 +66,41 @@ class _Conversion:
         self.noise_scale = 1.0 if noise_scale is None else float(noise_scale)      # (1.0: the reference's posterior)
 
 
+class _Recording:
+    """The recording a text request takes its melody and loudness from (``submit(prosody_audio=...)``): float32 at the
+    model's rate in ``audio``, or -- ``fmt`` = ``(rate, encoding)`` -- ``raw`` until the worker has run it through the input
+    stage (the attributes ``_through_input_stage`` reads and writes)."""
+
+    def __init__(self, audio, fmt=None):
+        self.fmt, self.raw = fmt, None
+        if fmt is None:
+            a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
+        else:
+            from .. import input_stage
+            a, self.raw = None, input_stage.as_raw(audio, fmt[1])
+        if (self.raw if a is None else a).ndim != 1:
+            raise ValueError("prosody_audio must be a 1-D array: float32 at the model's sampling rate, or raw samples in the "
+                             "encoding the request names")
+        self.audio = a
+
+    def samples(self, model_rate: int) -> int:
+        """Samples at the model's rate, host arithmetic."""
+        if self.fmt is None:
+            return int(self.audio.size)
+        from .. import input_stage
+        L, M, _ = input_stage.plan(self.fmt[0], model_rate)
+        return input_stage.out_len(int(self.raw.size), L, M)
+
+
 class _Request:
     """One request of the batching services: ``row`` is a row as ``collate_rows`` takes it or a ``_Conversion``, ``seed``
     keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
     ``noise_scale``; a conversion's noise scale is its row's."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None):
         self.row, self.seed, self.scales = row, int(seed), scales
         self.out_fmt = out_fmt        # ``_output_format``: the request's own output rate and encoding, or None
+        self.prosody = prosody        # a ``_Recording``: the row's f0 / energy come from it (``_prosody_controls``), or None
 
     @property
     def is_conversion(self) -> bool:
@@ -112,23 +139,69 @@ def _table_controls(batch, rows_ctl):
     return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
 
 
-def _collated(collate, reqs, noise_scale: float):
-    """``(batch, (duration, f0, energy), keywords)`` of text requests: ``collate`` and, where the requests need one, the
-    per-row table -- the ``row_controls`` keyword is passed only then: a group without one makes the calls it always made."""
+def _prosody_controls(eng, batch, reqs, model_rate):
+    """The requests that name a recording (``submit(prosody_audio=...)``): their raw recordings through the input stage,
+    then ONE ``Engine.prosody_contours`` and ONE ``Engine.prosody_phonemes`` call for all of them, with the durations their
+    rows brought.  The results go into the batch's ``f0`` / ``energy`` control rows ON THE DEVICE (the two arrays become
+    device tensors; nothing is read back) and the rows are marked ``given``.  A batch without such a request is not touched."""
+    idx = [i for i, r in enumerate(reqs) if r.prosody is not None]
+    if not idx:
+        return batch
+    import torch
+    jobs = [reqs[i].prosody for i in idx]
+    if any(j.fmt is not None for j in jobs):
+        _through_input_stage(eng, jobs, model_rate)
+    n = [len(j.audio) for j in jobs]
+    audio = torch.zeros((len(idx), max(n)), dtype=torch.float32, device=eng.device)
+    for k, j in enumerate(jobs):
+        audio[k, : n[k]] = torch.as_tensor(j.audio)
+    f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n)
+    dur = np.asarray(batch["duration"])
+    B, Tp = dur.shape
+    f0, energy = eng.prosody_phonemes(f0_frames, energy_frames, frames_host, dur[idx], np.asarray(batch["lengths"])[idx])
+    batch = dict(batch)
+    rows = torch.as_tensor(idx, device=eng.device)
+    for key, val in (("f0", f0), ("energy", energy)):
+        have = batch.get(key)
+        ctl = (torch.zeros((B, Tp), dtype=torch.float32) if have is None else torch.as_tensor(np.asarray(have), dtype=torch.float32))
+        ctl = ctl.to(eng.device)
+        ctl[rows] = val
+        batch[key] = ctl
+    given = batch.get("given")
+    if given is None:
+        given = np.tile(np.array([[batch.get(k) is not None for k in ("duration", "f0", "energy")]], dtype=bool), (B, 1))
+    given = np.array(given, dtype=bool)
+    given[idx, 1:] = True
+    batch["given"] = given
+    return batch
+
+
+def _collated(collate, reqs, noise_scale: float, eng=None, model_rate=None):
+    """``(batch, (duration, f0, energy), keywords)`` of text requests: ``collate``, the controls of the requests that name a
+    recording (``_prosody_controls``) and, where the requests need one, the per-row table -- the ``row_controls`` keyword is
+    passed only then: a group without one makes the calls it always made."""
     batch = collate([r.row for r in reqs])
+    if eng is not None:
+        batch = _prosody_controls(eng, batch, reqs, model_rate)
     table = _row_table(batch, [r.scales for r in reqs], noise_scale)
     if table is None:
         return batch, (batch.get("duration"), batch.get("f0"), batch.get("energy")), {}
     return batch, _table_controls(batch, table), {"row_controls": table}
 
 
-def _text_latents(eng, collate, reqs, noise_scale: float):
+def _as_tensor(a):
+    """A batch array as a tensor: numpy through ``torch.as_tensor``, a control that is on the device already as it is."""
+    import torch
+    return None if a is None else a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+
+
+def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None):
     """The text requests of one batch or admitted group to their latent: ``collate``, the per-row table where the requests
     need one, then ONE isolated ``encode`` / ``frame_lengths_host`` / ``decode(max_len=0)``.  Returns per request
     ``(z row [inter, T], g row, frames)``; a request of no frames gives ``(None, None, 0)``."""
-    import torch
-    batch, ctl, kw = _collated(collate, reqs, noise_scale)
-    t = lambda a: None if a is None else torch.as_tensor(np.asarray(a))
+    prosody = any(getattr(r, "prosody", None) is not None for r in reqs)
+    batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate) if prosody else ()))
+    t = _as_tensor
     enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
                      isolated=True, **kw)
     frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
@@ -195,7 +268,7 @@ def latents(eng, collate, requests, noise_scale: float, model_rate=None):
     conv = [i for i, r in enumerate(requests) if r.is_conversion]
     done = []
     if text:
-        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale))
+        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale, model_rate))
     if conv:
         done += zip(conv, _convert_latents(eng, [requests[i] for i in conv], model_rate))
     out = [None] * len(requests)
@@ -238,16 +311,36 @@ class BatchingSynthesisService:
         self._worker.start()
 
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None) -> "concurrent.futures.Future":
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, prosody_audio=None,
+               prosody_sample_rate: Optional[int] = None, prosody_encoding=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
         The future's result is the request's PCM16 samples (numpy int16, valid part only).
         ``output_rate`` / ``output_encoding`` (``vispeech_amd.output_stage``: "f32", "s16", "ulaw", "alaw"): the request's own
         delivery format -- the result is then float32, int16 or uint8 (G.711 codes) at that rate.  When any request of a
         collected batch names one, all its waveforms leave through ONE ``Engine.output_rows`` call and one device-to-host
-        copy; requests that name none ride as rows of (the service's rate, PCM16) and get the bytes they always got."""
+        copy; requests that name none ride as rows of (the service's rate, PCM16) and get the bytes they always got.
+        ``prosody_audio`` (prosody transfer): a 1-D recording -- float32 at the model's rate, or raw at
+        ``prosody_sample_rate`` / in ``prosody_encoding`` (``vispeech_amd.input_stage``) -- whose melody and loudness the
+        request is spoken with.  The row brings phones and durations (refused here without them, and where the durations
+        claim more frames than the recording has); the worker computes the recording's per-phoneme F0 and energy
+        (``SynthesizerTrn.prosody_from_audio``: ONE contour call and ONE phoneme call for all such requests of a batch) and
+        they take the place of whatever f0 / energy the row carries.  The request is then what
+        ``infer(isolated=True, duration_control=.., pitch_control=f0, energy_control=energy)`` returns for it alone."""
+        prosody = None
+        if prosody_audio is not None:
+            prosody = _Recording(prosody_audio, _input_format(prosody_sample_rate, prosody_encoding, self.sampling_rate))
+            durations = getattr(row, "durations", None)
+            if durations is None:
+                raise ValueError("prosody_audio: the row must bring its durations (the phonemes' frames in the recording)")
+            n, hop = prosody.samples(self.sampling_rate), int(self.net.dims.total_upsample)
+            if n < 641 or int(np.sum(durations)) > n // hop + 1:
+                raise ValueError(f"prosody_audio: {n} samples at the model's rate ({n // hop + 1} frames): it needs 641, and "
+                                 f"the row's durations claim {int(np.sum(durations))} frames")
+        elif prosody_sample_rate is not None or prosody_encoding is not None:
+            raise ValueError("prosody_sample_rate / prosody_encoding describe prosody_audio: pass it")
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                      _output_format(output_rate, output_encoding)))
+                                      _output_format(output_rate, output_encoding), prosody))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
@@ -314,13 +407,14 @@ class BatchingSynthesisService:
         net = self.net
         if any(r.is_conversion for r in reqs):
             return self._synthesize_mixed(reqs)
-        batch, ctl, kw = _collated(self._collate, reqs, self.noise_scale)
-        t = lambda a: None if a is None else torch.as_tensor(np.asarray(a)).to(net.device)
+        hop = net.dims.total_upsample
+        prosody = (net._engine, self.sampling_rate) if any(r.prosody is not None for r in reqs) else ()
+        batch, ctl, kw = _collated(self._collate, reqs, self.noise_scale, *prosody)
+        t = lambda a: None if a is None else _as_tensor(a).to(net.device)
         o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
                                   duration_control=t(ctl[0]), pitch_control=t(ctl[1]),
                                   energy_control=t(ctl[2]), noise_seed=[r.seed for r in reqs], isolated=True, **kw)
         frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
-        hop = net.dims.total_upsample
         if any(r.out_fmt is not None for r in reqs):
             return self._deliver_rows(reqs, [o[b, 0, : int(frames[b]) * hop] for b in range(len(reqs))])
         return [self._pcm16(o[b:b + 1, 0, : int(frames[b]) * hop]) for b in range(len(reqs))]

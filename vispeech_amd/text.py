@@ -76,6 +76,22 @@ def parse_filelist_row(line: str) -> FilelistRow:
     return FilelistRow(spk, uid, ph, d, f0, en)
 
 
+def format_filelist_row(row: FilelistRow) -> str:
+    """The line ``parse_filelist_row`` reads: ``spk|id|phones|durations|f0|energy``, fields space separated, F0 and energy
+    as ``'{:.3f}'`` (reference f0energy.py:99-116) -- what data preparation writes for every training recording once
+    ``SynthesizerTrn.prosody_from_audio`` has produced the two tensors.  The row must carry all three controls."""
+    n = len(row.phones)
+    for name, a in (("durations", row.durations), ("f0", row.f0), ("energy", row.energy)):
+        if a is None or len(a) != n:
+            raise ValueError(f"{name}: a filelist row carries one value per phone ({n})")
+    for name, s in (("speaker", row.speaker), ("utt_id", row.utt_id), *(("phone", p) for p in row.phones)):
+        if "|" in s or "\n" in s or (name == "phone" and (" " in s or s == "")):
+            raise ValueError(f"{name} {s!r} cannot be written into a filelist row")
+    nums = lambda a: " ".join("{:.3f}".format(float(v)) for v in a)
+    return "|".join([row.speaker, row.utt_id, " ".join(row.phones), " ".join(str(int(d)) for d in row.durations),
+                     nums(row.f0), nums(row.energy)])
+
+
 def collate_rows(rows: Sequence[FilelistRow], table: SymbolTable, spk2id: Dict[str, int]):
     """Pad rows into the arrays ``SynthesizerTrn.infer`` takes with control tensors:
     phonemes [B,Tp] int64, lengths [B], sid [B], duration / f0 / energy [B,Tp] float32 (zero padded), and
