@@ -88,7 +88,7 @@ int vsp_destroy(vsp_ctx* ctx) {
   if (ctx->flags_host) (void)hipHostFree(ctx->flags_host);
   for (auto st : ctx->side) if (st) (void)hipStreamDestroy(st);
   if (ctx->arena && ctx->arena_owned) (void)hipFree(ctx->arena);
-  if (ctx->out_tab) (void)hipFree(ctx->out_tab);
+  if (ctx->out_stage.tab) (void)hipFree(ctx->out_stage.tab);
   tail_table_drop(ctx);
   for (auto& r : ctx->in_rates) if (r.tab) (void)hipFree(r.tab);
   for (auto& r : ctx->out_rates) if (r.tab) (void)hipFree(r.tab);

@@ -773,11 +773,12 @@ int vsp_generator_stream_rows_output(vsp_ctx* ctx, void* stream, int B, const vs
                                      int64_t out_stride, int pcm, void* workspace, int64_t workspace_bytes) {
   int rc = check_ready(ctx);
   if (rc) return rc;
-  if (!ctx->out_tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
+  const vsp_ctx::RateTable& t = ctx->out_stage;
+  if (!t.tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
   if (B < 1 || B > STREAM_ROWS_MAX || !rows || !out || !workspace || (pcm != 0 && pcm != 1) || out_stride < 1)
     return ctx->fail(VSP_ERR_ARG, "vsp_generator_stream_rows_output: bad argument (1 <= B <= %d)", STREAM_ROWS_MAX);
   const int up = (int)total_upsample(ctx->cfg);
-  const int L = ctx->out_L, M = ctx->out_M, H = ctx->out_H, K = vsp_output_history_samples(L, M, H);
+  const int L = t.L, M = t.M, H = t.H, K = vsp_output_history_samples(L, M, H);
   vsp_stream_row plain[STREAM_ROWS_MAX];
   int64_t m0[STREAM_ROWS_MAX], m1[STREAM_ROWS_MAX];
   for (int b = 0; b < B; ++b) plain[b] = rows[b].row;
@@ -807,7 +808,7 @@ int vsp_generator_stream_rows_output(vsp_ctx* ctx, void* stream, int B, const vs
     orows.r[b] = StreamOutRow{r.f0 > 0 ? rows[b].hist_in : nullptr, rows[b].hist_out, (int64_t)r.f0 * up, (int)((r.f0 - lo[b]) * up),
                               (int)((r.f1 - r.f0) * up), r.f1 == r.L, 0};
   }
-  const StreamOutFilter f{ctx->out_tab, L, M, H, ctx->out_J, ctx->out_P};
+  const StreamOutFilter f{t.tab, L, M, H, t.J, t.P};
   hipError_t e = launch_stream_output(o_span, (long)span * up, orows, B, f, K, out, (long)out_stride, pcm, s);
   return e == hipSuccess ? VSP_OK : ctx->fail(VSP_ERR_HIP, "stream_output: %s", hipGetErrorString(e));
 }

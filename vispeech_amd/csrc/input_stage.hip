@@ -9,7 +9,10 @@
 // through a 256-entry table in LDS -- and every lane then runs acc = fmaf(tab[i][m mod L], x[ks + i], acc), i ascending:
 // neighbouring lanes read neighbouring words of a table row (coalesced, the table stays in L2) and LDS words at most
 // ceil(M / L) apart.  Taps that do not fit the staging area beside the span take several passes; a span that does not fit
-// at all (M / L above 7) reads and decodes from global memory, the same chain.
+// at all (M / L above 7) reads and decodes from global memory, the same chain.  Both are the routines of resample_common.h
+// (rs_tile_output with E = 4, 8 or 16 raw samples per 16-byte load, rs_one_output), sized by its stage_plan; this file
+// passes its decoders (in_decode_vec, in_decode_one) and owns the G.711 table in LDS.  The set of rates is configured by
+// resample_common.h's configure_rate into vsp_ctx::in_rates.
 //
 // A sample's value is a function of (decoded x, m) alone -- not of the tile, the window or the batch -- so a recording fed
 // piece by piece gives the bytes of the one-shot call.  Samples outside a row's window are never read (selected to zero
@@ -25,9 +28,8 @@ namespace {
 
 using namespace vsp::rs;
 
-constexpr int IN_TILE = 256;            // output samples (= threads) per block; also the entries of a G.711 table
+constexpr int IN_TILE = RS_TILE;        // output samples (= threads) per block; also the entries of a G.711 table
 constexpr int IN_X_LDS_FLOATS = 2048;   // input staging area per block (8 KiB: eight blocks per CU keep their LDS)
-constexpr int IN_MIN_PASS = 32;         // fewer taps per staging pass than this: read x from global memory instead
 constexpr int IN_VEC = 16;              // raw samples of the widest 16-byte load (G.711); passes are multiples of it
 constexpr int IN_MAX_L = 441, IN_MAX_M = 640;
 
@@ -88,97 +90,31 @@ __global__ __launch_bounds__(IN_TILE) void input_kernel(const vsp::InputRows row
     if (j < r.out_fill) r.out[j] = 0.f;
     return;
   }
-  const int64_t m_first = r.m0 + j0;
-  const int64_t m_last = min(m_first + IN_TILE, r.m1) - 1;
-  const int64_t m = m_first + tid;
-  const bool active = m <= m_last;
-  const int64_t mm = active ? m : m_last;                           // idle lanes shadow the last sample: offsets stay in the tile
+  const int64_t m_first = r.m0 + j0, m_last = min(m_first + IN_TILE, r.m1) - 1;
   const int64_t lo = r.in_first, hi = r.in_first + r.in_len;        // readable samples [lo, hi); sample k is element k - lo
-  const int64_t ks = (mm * f.M) / f.L - f.J;                        // first input sample of this output
-  const float* __restrict__ tcol = f.tab + (int)(mm % f.L);
-  float acc = 0.f;
-
   if (G711) {
     g711[tid] = (float)(ENC == VSP_IN_ULAW ? vsp::g711_ulaw_linear(tid) : vsp::g711_alaw_linear(tid)) * (1.0f / 32768.0f);
     __syncthreads();
   }
-  if (mode == 2) {
-    acc = rs_one_output(tcol, f.L, f.P, ks,
-                        [&](int64_t k) { return (k >= lo && k < hi) ? in_decode_one<ENC>(r.in, k - lo, g711) : 0.f; });
-  } else {
-    int64_t kb = (m_first * f.M) / f.L - f.J;                       // first input sample of the tile
-    kb -= ((int64_t)((uintptr_t)r.in / ES) + (kb - lo)) & (E - 1);  // ... moved down to a 16-byte boundary of the row's memory
-    const int off = (int)(ks - kb);
-    const int span = (int)((m_last * f.M) / f.L - f.J - kb) + 1;    // tile words before the pass's taps are added
-    for (int i0 = 0; i0 < f.P; i0 += pass) {                        // (pass % IN_VEC == 0 when there is more than one)
-      const int n_i = min(pass, f.P - i0);
-      const int need = span + n_i - 1;
-      const int64_t k_base = kb + i0;
-      if (i0) __syncthreads();
-      for (int o = tid * E; o < need; o += IN_TILE * E) {
-        const int64_t k = k_base + o;
-        float v[E];
-        if (k >= lo && k + E <= hi) {
-          in_decode_vec<ENC>(static_cast<const char*>(r.in) + (k - lo) * ES, v, g711);
-        } else {
-#pragma unroll
-          for (int q = 0; q < E; ++q) v[q] = (k + q >= lo && k + q < hi) ? in_decode_one<ENC>(r.in, k + q - lo, g711) : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < E; q += 4) *reinterpret_cast<float4*>(xs + o + q) = make_float4(v[q], v[q + 1], v[q + 2], v[q + 3]);
-      }
-      __syncthreads();
-      const float* __restrict__ tp = tcol + (size_t)i0 * f.L;
-      const float* xo = xs + off;
-      int i = 0;
-      for (; i + 4 <= n_i; i += 4) {                                // (four table loads in flight; the FMA order stays ascending)
-        const float t0 = tp[(size_t)i * f.L], t1 = tp[(size_t)(i + 1) * f.L], t2 = tp[(size_t)(i + 2) * f.L],
-                    t3 = tp[(size_t)(i + 3) * f.L];
-        acc = fmaf(t0, xo[i], acc);
-        acc = fmaf(t1, xo[i + 1], acc);
-        acc = fmaf(t2, xo[i + 2], acc);
-        acc = fmaf(t3, xo[i + 3], acc);
-      }
-      for (; i < n_i; ++i) acc = fmaf(tp[(size_t)i * f.L], xo[i], acc);
-    }
-  }
+  auto sample = [&](int64_t k) { return (k >= lo && k < hi) ? in_decode_one<ENC>(r.in, k - lo, g711) : 0.f; };
+  auto load = [&](int64_t k, float* v) { in_decode_vec<ENC>(static_cast<const char*>(r.in) + (k - lo) * ES, v, g711); };
+  float acc;
+  if (mode == 2) acc = rs_one_output(f.tab, f.L, f.M, f.J, f.P, min(m_first + tid, m_last), sample);
+  else acc = rs_tile_output<E>(xs, f.tab, f.L, f.M, f.J, f.P, pass, m_first, m_last, (int64_t)((uintptr_t)r.in / ES) - lo, lo, hi,
+                               load, sample);
+  const bool active = m_first + tid <= m_last;
   if (active) r.out[j] = acc;
   else if (j < r.out_fill) r.out[j] = 0.f;
-}
-
-int make_plan(int in_rate, int model_rate, int zeros, Plan& p) {
-  return vsp::rs::make_plan(in_rate, model_rate, zeros, IN_MAX_L, IN_MAX_M, p);
-}
-
-int enc_bytes(int enc) { return enc == VSP_IN_F32 ? 4 : enc == VSP_IN_S16 ? 2 : 1; }
-
-vsp_ctx::InputRate* find_rate(vsp_ctx* ctx, int rate) {
-  for (auto& r : ctx->in_rates)
-    if (r.tab && r.rate == rate) return &r;
-  return nullptr;
 }
 
 }  // namespace
 
 int vsp_input_plan(int in_rate, int model_rate, int zeros, int* L, int* M, int* half_len) {
-  Plan p;
-  if (!L || !M || !half_len) return VSP_ERR_ARG;
-  if (zeros == 0) zeros = 32;
-  if (int rc = make_plan(in_rate, model_rate, zeros, p)) return rc;
-  *L = p.L; *M = p.M; *half_len = p.H;
-  return VSP_OK;
+  return plan_api(in_rate, model_rate, zeros ? zeros : 32, IN_MAX_L, IN_MAX_M, L, M, half_len);
 }
 
 int vsp_input_filter(int in_rate, int model_rate, int zeros, double beta, double rolloff, float* taps_host) {
-  Plan p;
-  if (!taps_host || !(beta >= 0.0) || !(rolloff <= 1.0)) return VSP_ERR_ARG;
-  if (zeros == 0) zeros = 32;
-  if (int rc = make_plan(in_rate, model_rate, zeros, p)) return rc;
-  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
-  std::vector<double> h;
-  make_filter(p, zeros, beta, rolloff, h);
-  for (size_t i = 0; i < h.size(); ++i) taps_host[i] = (float)h[i];
-  return VSP_OK;
+  return filter_api(in_rate, model_rate, zeros ? zeros : 32, beta, rolloff, IN_MAX_L, IN_MAX_M, taps_host);
 }
 
 int vsp_input_decode_table(int enc, float* table256) {
@@ -201,17 +137,9 @@ hipError_t launch_input_rows(const InputRows& rows, int B, const InputFilter& f,
     fill = std::max(fill, r.out_fill);
   }
   if (fill == 0) return hipSuccess;
-  // tile words: the outputs of a tile start within (TILE - 1) M / L + 1 samples of each other, + IN_VEC - 1 for the alignment
-  const int64_t span = ((int64_t)(IN_TILE - 1) * f.M) / f.L + 2 + (IN_VEC - 1);
-  const int64_t room = IN_X_LDS_FLOATS - span - IN_VEC;              // (the last 16-byte store's overhang)
-  int pass = f.P, mode = 2;
-  int64_t xs_words = 0;
-  if (room >= std::min<int64_t>(f.P, IN_MIN_PASS)) {
-    pass = room >= f.P ? f.P : (int)(room & ~(int64_t)(IN_VEC - 1));
-    mode = 0;
-    xs_words = (span + pass + IN_VEC + 3) & ~(int64_t)3;
-  }
-  const size_t lds = (size_t)(xs_words + (enc >= VSP_IN_ULAW ? IN_TILE : 0)) * sizeof(float);
+  const StagePlan sp = stage_plan(IN_X_LDS_FLOATS, IN_VEC - 1, IN_VEC, IN_VEC, f.L, f.M, f.P);
+  const int pass = sp.pass, mode = sp.mode;
+  const size_t lds = (size_t)(sp.xs_words + (enc >= VSP_IN_ULAW ? IN_TILE : 0)) * sizeof(float);
   const dim3 grid((unsigned)((fill + IN_TILE - 1) / IN_TILE), (unsigned)B);
   switch (enc) {
     case VSP_IN_F32: hipLaunchKernelGGL(input_kernel<VSP_IN_F32>, grid, dim3(IN_TILE), lds, s, rows, f, pass, mode); break;
@@ -226,52 +154,17 @@ hipError_t launch_input_rows(const InputRows& rows, int B, const InputFilter& f,
 int vsp_input_configure(vsp_ctx* ctx, int in_rate, int model_rate, int zeros, double beta, double rolloff) {
   if (!ctx) return VSP_ERR_ARG;
   if (in_rate <= 0) return ctx->fail(VSP_ERR_ARG, "input stage: in_rate must be positive");
-  vsp_ctx::InputRate* slot = find_rate(ctx, in_rate);
   if (model_rate == 0) {                                  // drop the rate
-    if (slot) {
-      (void)hipSetDevice(ctx->device);
-      (void)hipFree(slot->tab);
-      *slot = vsp_ctx::InputRate();
-    }
+    drop_rate(ctx, find_rate(ctx->in_rates, VSP_INPUT_RATES_MAX, in_rate));
     return VSP_OK;
   }
-  if (zeros == 0) zeros = 32;
-  if (!(beta >= 0.0)) return ctx->fail(VSP_ERR_ARG, "input stage: beta must be >= 0");
-  if (!(rolloff <= 1.0)) return ctx->fail(VSP_ERR_ARG, "input stage: rolloff must be in (0, 1] (<= 0: 1 - 3.065 / zeros)");
-  Plan p;
-  if (int rc = make_plan(in_rate, model_rate, zeros, p))
-    return ctx->fail(rc, "input stage %d -> %d Hz, %d zeros: rates must be positive, L <= %d, M <= %d, 1 <= zeros <= 64", in_rate,
-                     model_rate, zeros, IN_MAX_L, IN_MAX_M);
-  if (!slot) {
-    for (auto& r : ctx->in_rates)
-      if (!r.tab) { slot = &r; break; }
-    if (!slot) return ctx->fail(VSP_ERR_STATE, "input stage: %d input rates are configured already", VSP_INPUT_RATES_MAX);
-  }
-  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
-  std::vector<double> h;
-  make_filter(p, zeros, beta, rolloff, h);
-  int J, P;
-  std::vector<float> tab;
-  make_table(p, h, J, P, tab);
-  void* d = nullptr;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc(&d, tab.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d) (void)hipFree(d);
-    return ctx->fail(VSP_ERR_HIP, "input stage table: %s", hipGetErrorString(e));
-  }
-  float* old = slot->tab;
-  slot->rate = in_rate;
-  slot->L = p.L; slot->M = p.M; slot->H = p.H; slot->J = J; slot->P = P;
-  slot->tab = static_cast<float*>(d);                     // (last: a slot counts as configured once it has a table)
-  if (old) (void)hipFree(old);
-  return VSP_OK;
+  return configure_rate(ctx, "input stage", "input", ctx->in_rates, VSP_INPUT_RATES_MAX, in_rate, in_rate, model_rate, zeros, beta,
+                        rolloff, IN_MAX_L, IN_MAX_M);
 }
 
 int vsp_input_rows(vsp_ctx* ctx, void* stream, int in_rate, int enc, int B, const vsp_input_row* rows) {
   if (!ctx) return VSP_ERR_ARG;
-  const vsp_ctx::InputRate* t = find_rate(ctx, in_rate);
+  const vsp_ctx::RateTable* t = find_rate(ctx->in_rates, VSP_INPUT_RATES_MAX, in_rate);
   if (!t) return ctx->fail(VSP_ERR_STATE, "input stage: rate %d Hz is not configured (vsp_input_configure)", in_rate);
   if (!rows || B < 1 || B > vsp::STREAM_ROWS_MAX || enc < VSP_IN_F32 || enc > VSP_IN_ALAW)
     return ctx->fail(VSP_ERR_ARG, "vsp_input_rows: 1 <= B <= %d rows, enc one of VSP_IN_*", vsp::STREAM_ROWS_MAX);

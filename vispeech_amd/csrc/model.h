@@ -170,15 +170,13 @@ struct vsp_ctx {
   const int64_t* fl_known_src = nullptr;
   hipStream_t side[2] = {nullptr, nullptr};
   std::vector<hipEvent_t> sync_ev;
-  // output stage (resample.hip, vsp_output_configure): the polyphase table [P][L] on the device and its plan -- resampling
-  // by L / M with 2 H + 1 prototype taps, P taps per output starting J = H / L input samples before the output's own
-  float* out_tab = nullptr;
-  int out_L = 0, out_M = 0, out_H = 0, out_J = 0, out_P = 0;
-  // input stage (input_stage.hip, vsp_input_configure): one table of the same layout per configured input rate
-  struct InputRate { int rate = 0; float* tab = nullptr; int L = 0, M = 0, H = 0, J = 0, P = 0; };
-  InputRate in_rates[VSP_INPUT_RATES_MAX];
-  // output rows (output_rows.hip, vsp_output_rate_configure): the same per configured OUTPUT rate, beside out_tab
-  InputRate out_rates[VSP_OUTPUT_RATES_MAX];
+  // A configured sample-rate conversion (resample_common.h, configure_rate): the polyphase table [P][L] on the device and
+  // its plan -- resampling by L / M with 2 H + 1 prototype taps, P taps per output starting J = H / L input samples before
+  // the output's own.  `rate` is the key within a set of rates; a slot counts as configured once it has a table.
+  struct RateTable { int rate = 0; float* tab = nullptr; int L = 0, M = 0, H = 0, J = 0, P = 0; };
+  RateTable out_stage;                         // output stage (resample.hip, vsp_output_configure): a set of one, key 0
+  RateTable in_rates[VSP_INPUT_RATES_MAX];     // input stage (input_stage.hip, vsp_input_configure): one per INPUT rate
+  RateTable out_rates[VSP_OUTPUT_RATES_MAX];   // output rows (output_rows.hip, vsp_output_rate_configure): one per OUTPUT rate
   int64_t noise_first = 0;        // stream index of element 0 of a library-drawn noise tensor (vsp_set_noise_offset)
   // Isolated mode (vsp_set_isolated, round 10): every utterance of a batch as a B = 1 call on its own unpadded inputs
   // computes it -- masks where the reference applies none, the generator's tensors ending at the utterance's own length,

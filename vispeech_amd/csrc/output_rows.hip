@@ -10,11 +10,14 @@
 // [k0, x_first), x serves [x_first, x_first + n), everything outside is zero; 16 bytes per load inside x (the tile's first
 // staged sample is moved down to a 16-byte boundary of the row's own memory) -- and every lane then runs
 // acc = fmaf(tab[i][m mod L], xs[off + i], acc), i ascending.  Taps that do not fit the staging area beside the span take
-// several passes; a span that does not fit at all (M / L above 7) reads from global memory, the same chain.
+// several passes; a span that does not fit at all (M / L above 7) reads from global memory, the same chain.  Both are the
+// routines of resample_common.h (rs_tile_output with E = 4, rs_one_output), sized by its stage_plan; this file passes its
+// two-segment `sample` and the 16-byte load of x.
 //
-// The epilogue is the row's: PCM16 as packed pairs from even lanes, G.711 codes four to a 32-bit store (wave shuffles)
-// where the row's `out` is 4-byte aligned and the four lie inside out_fill; single elements only at a row's ragged end.
-// Behind m1 - m0 a lane encodes y = 0: the encoding's silence.  Extra blocks of the same grid write hist_out.
+// The epilogue is the row's (out_store, resample_common.h): PCM16 as packed pairs from even lanes, G.711 codes four to a
+// 32-bit store (wave shuffles) where the row's `out` is 4-byte aligned and the four lie inside out_fill; single elements
+// only at a row's ragged end.  Behind m1 - m0 a lane encodes y = 0: the encoding's silence.  Extra blocks of the same grid
+// write hist_out.  The set of rates is configured by resample_common.h's configure_rate into vsp_ctx::out_rates.
 #include <algorithm>
 #include <vector>
 
@@ -25,53 +28,17 @@ namespace {
 
 using namespace vsp::rs;
 
-constexpr int OUT_TILE = 256;           // output samples (= threads) per block
+constexpr int OUT_TILE = RS_TILE;        // output samples (= threads) per block
 constexpr int OUT_X_LDS_FLOATS = 2048;  // input staging area per block (8 KiB: eight blocks per CU keep their LDS)
-constexpr int OUT_MIN_PASS = 32;        // fewer taps per staging pass than this: read x from global memory instead
-constexpr int OUT_MAX_L = 320, OUT_MAX_M = 441;   // the output stage's own limits (resample.hip)
 
 static_assert(sizeof(vsp::OutRow) == 96 && sizeof(vsp::OutFilter) == 40, "descriptor layout");
 static_assert(sizeof(vsp::OutRowsArgs) <= 4096, "kernel arguments must fit 4 KiB");
 static_assert(vsp::OUT_FILTERS_MAX == VSP_OUTPUT_RATES_MAX, "one filter entry per configured rate");
 static_assert(2 * vsp::OUT_ROWS_PER_LAUNCH >= vsp::STREAM_ROWS_MAX, "64 rows take at most two launches");
 
-// Stores element j of a row in its encoding.  Every lane of the block calls it (the shuffles take all of them) with a valid
-// y; lanes with j < fill store.  j - threadIdx.x is a multiple of OUT_TILE, so j and the lane agree modulo 2 and 4.
-__device__ __forceinline__ void out_store(void* out, int enc, int64_t j, float y, int64_t fill) {
-  const bool active = j < fill;
-  if (enc == VSP_OUT_F32) {
-    if (active) static_cast<float*>(out)[j] = y;
-    return;
-  }
-  const int q = rs_pcm16(y);
-  const bool word_ok = ((uintptr_t)out & 3) == 0;
-  if (enc == VSP_OUT_S16) {
-    const int q_next = __shfl_down(q, 1);
-    int16_t* o = static_cast<int16_t*>(out) + j;
-    if (word_ok) {
-      if (!(threadIdx.x & 1) && active) {
-        if (j + 1 < fill) *reinterpret_cast<uint32_t*>(o) = (uint32_t)(q & 0xffff) | ((uint32_t)q_next << 16);
-        else *o = (int16_t)q;
-      }
-    } else if (active) {
-      *o = (int16_t)q;
-    }
-    return;
-  }
-  const uint32_t c = (uint32_t)(enc == VSP_OUT_ULAW ? vsp::g711_ulaw_code(q) : vsp::g711_alaw_code(q));
-  const uint32_t c1 = __shfl_down(c, 1), c2 = __shfl_down(c, 2), c3 = __shfl_down(c, 3);
-  uint8_t* o = static_cast<uint8_t*>(out) + j;
-  if (word_ok && (j | 3) < fill) {                                  // the lane's whole group of four is stored
-    if (!(threadIdx.x & 3)) *reinterpret_cast<uint32_t*>(o) = c | (c1 << 8) | (c2 << 16) | (c3 << 24);
-  } else if (active) {
-    *o = (uint8_t)c;
-  }
-}
-
 // grid (out_tiles + hist blocks, rows), OUT_TILE threads.  Dynamic LDS: the staging area of the launch's widest filter.
 __global__ __launch_bounds__(OUT_TILE) void output_rows_kernel(const vsp::OutRowsArgs a) {
   extern __shared__ __align__(16) float out_xs[];
-  float* xs = out_xs;
   const int tid = threadIdx.x;
   const vsp::OutRow& r = a.r[blockIdx.y];
   const vsp::OutFilter& f = a.f[r.filt];
@@ -91,80 +58,25 @@ __global__ __launch_bounds__(OUT_TILE) void output_rows_kernel(const vsp::OutRow
   if (j0 >= r.out_fill) return;                                     // (uniform over the block, like the next branch)
   float acc = 0.f;
   if (j0 < cnt) {
-    const int64_t m_first = r.m0 + j0;
-    const int64_t m_last = min(m_first + OUT_TILE, r.m1) - 1;
-    const int64_t m = m_first + tid;
-    const int64_t mm = m <= m_last ? m : m_last;                    // idle lanes shadow the last sample: offsets stay in the tile
-    const int64_t ks = (mm * f.M) / f.L - f.J;                      // first input sample of this output
-    const float* __restrict__ tcol = f.tab + (int)(mm % f.L);
+    const int64_t m_first = r.m0 + j0, m_last = min(m_first + OUT_TILE, r.m1) - 1;
     if (f.mode == 2) {
-      acc = rs_one_output(tcol, f.L, f.P, ks, sample);
+      acc = rs_one_output(f.tab, f.L, f.M, f.J, f.P, min(m_first + tid, m_last), sample);
     } else {
-      int64_t kb = (m_first * f.M) / f.L - f.J;                     // first input sample of the tile
-      kb -= ((int64_t)((uintptr_t)r.x / 4) + (kb - x_first)) & 3;   // ... moved down to a 16-byte boundary of x's memory
-      const int off = (int)(ks - kb);
-      const int span = (int)((m_last * f.M) / f.L - f.J - kb) + 1;  // tile words before the pass's taps are added
-      for (int i0 = 0; i0 < f.P; i0 += f.pass) {                    // (pass % 4 == 0 when there is more than one)
-        const int n_i = min(f.pass, f.P - i0);
-        const int need = span + n_i - 1;
-        const int64_t k_base = kb + i0;
-        if (i0) __syncthreads();
-        for (int o = tid * 4; o < need; o += OUT_TILE * 4) {
-          const int64_t k = k_base + o;
-          float4 v;
-          if (k >= x_first && k + 4 <= x_end) {
-            v = *reinterpret_cast<const float4*>(r.x + (k - x_first));
-          } else {
-            v.x = sample(k);
-            v.y = sample(k + 1);
-            v.z = sample(k + 2);
-            v.w = sample(k + 3);
-          }
-          *reinterpret_cast<float4*>(xs + o) = v;
-        }
-        __syncthreads();
-        const float* __restrict__ tp = tcol + (size_t)i0 * f.L;
-        const float* xo = xs + off;
-        int i = 0;
-        for (; i + 4 <= n_i; i += 4) {                              // (four table loads in flight; the FMA order stays ascending)
-          const float t0 = tp[(size_t)i * f.L], t1 = tp[(size_t)(i + 1) * f.L], t2 = tp[(size_t)(i + 2) * f.L],
-                      t3 = tp[(size_t)(i + 3) * f.L];
-          acc = fmaf(t0, xo[i], acc);
-          acc = fmaf(t1, xo[i + 1], acc);
-          acc = fmaf(t2, xo[i + 2], acc);
-          acc = fmaf(t3, xo[i + 3], acc);
-        }
-        for (; i < n_i; ++i) acc = fmaf(tp[(size_t)i * f.L], xo[i], acc);
-      }
+      auto load = [&](int64_t k, float* v) {
+        const float4 w = *reinterpret_cast<const float4*>(r.x + (k - x_first));
+        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+      };
+      acc = rs_tile_output<4>(out_xs, f.tab, f.L, f.M, f.J, f.P, f.pass, m_first, m_last, (int64_t)((uintptr_t)r.x / 4) - x_first,
+                              x_first, x_end, load, sample);
     }
   }
   out_store(r.out, r.enc, j, j < cnt ? acc : 0.f, r.out_fill);     // behind the row's outputs: the code of 0
 }
 
-int make_plan(int model_rate, int out_rate, int zeros, Plan& p) {
-  return vsp::rs::make_plan(model_rate, out_rate, zeros, OUT_MAX_L, OUT_MAX_M, p);
-}
-
-int enc_bytes(int enc) { return enc == VSP_OUT_F32 ? 4 : enc == VSP_OUT_S16 ? 2 : 1; }
-
-vsp_ctx::InputRate* find_rate(vsp_ctx* ctx, int rate) {
-  for (auto& r : ctx->out_rates)
-    if (r.tab && r.rate == rate) return &r;
-  return nullptr;
-}
-
-// how output_rows_kernel stages a rate: the arithmetic of vsp_output_chunk's launch with this kernel's staging area
-vsp::OutFilter make_filter_entry(const vsp_ctx::InputRate& t) {
-  vsp::OutFilter f{t.tab, t.L, t.M, t.H, t.J, t.P, t.P, 2, 0};
-  // tile words: the outputs of a tile start within (TILE - 1) M / L + 1 samples of each other, + 3 for the alignment
-  const int64_t span = ((int64_t)(OUT_TILE - 1) * t.M) / t.L + 2 + 3;
-  const int64_t room = OUT_X_LDS_FLOATS - span - 8;                 // (the last 16-byte store's overhang)
-  if (room >= std::min<int64_t>(t.P, OUT_MIN_PASS)) {
-    f.pass = room >= t.P ? t.P : (int)(room & ~(int64_t)3);
-    f.mode = 0;
-    f.xs_words = (int)((span + f.pass + 8 + 3) & ~(int64_t)3);
-  }
-  return f;
+// how output_rows_kernel stages a rate
+vsp::OutFilter make_filter_entry(const vsp_ctx::RateTable& t) {
+  const StagePlan sp = stage_plan(OUT_X_LDS_FLOATS, 3, 8, 4, t.L, t.M, t.P);
+  return vsp::OutFilter{t.tab, t.L, t.M, t.H, t.J, t.P, sp.pass, sp.mode, sp.xs_words};
 }
 
 }  // namespace
@@ -215,47 +127,12 @@ hipError_t launch_output_rows(OutRowsArgs& a, int B, hipStream_t s) {
 int vsp_output_rate_configure(vsp_ctx* ctx, int model_rate, int out_rate, int zeros, double beta, double rolloff) {
   if (!ctx) return VSP_ERR_ARG;
   if (out_rate <= 0) return ctx->fail(VSP_ERR_ARG, "output rows: out_rate must be positive");
-  vsp_ctx::InputRate* slot = find_rate(ctx, out_rate);
   if (model_rate == 0) {                                  // drop the rate
-    if (slot) {
-      (void)hipSetDevice(ctx->device);
-      (void)hipFree(slot->tab);
-      *slot = vsp_ctx::InputRate();
-    }
+    drop_rate(ctx, find_rate(ctx->out_rates, VSP_OUTPUT_RATES_MAX, out_rate));
     return VSP_OK;
   }
-  if (zeros == 0) zeros = 32;
-  if (!(beta >= 0.0)) return ctx->fail(VSP_ERR_ARG, "output rows: beta must be >= 0");
-  if (!(rolloff <= 1.0)) return ctx->fail(VSP_ERR_ARG, "output rows: rolloff must be in (0, 1] (<= 0: 1 - 3.065 / zeros)");
-  Plan p;
-  if (int rc = make_plan(model_rate, out_rate, zeros, p))
-    return ctx->fail(rc, "output rows %d -> %d Hz, %d zeros: rates must be positive, L <= %d, M <= %d, 1 <= zeros <= 64", model_rate,
-                     out_rate, zeros, OUT_MAX_L, OUT_MAX_M);
-  if (!slot) {
-    for (auto& r : ctx->out_rates)
-      if (!r.tab) { slot = &r; break; }
-    if (!slot) return ctx->fail(VSP_ERR_STATE, "output rows: %d output rates are configured already", VSP_OUTPUT_RATES_MAX);
-  }
-  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
-  std::vector<double> h;
-  make_filter(p, zeros, beta, rolloff, h);
-  int J, P;
-  std::vector<float> tab;
-  make_table(p, h, J, P, tab);
-  void* d = nullptr;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc(&d, tab.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d) (void)hipFree(d);
-    return ctx->fail(VSP_ERR_HIP, "output rows table: %s", hipGetErrorString(e));
-  }
-  float* old = slot->tab;
-  slot->rate = out_rate;
-  slot->L = p.L; slot->M = p.M; slot->H = p.H; slot->J = J; slot->P = P;
-  slot->tab = static_cast<float*>(d);                     // (last: a slot counts as configured once it has a table)
-  if (old) (void)hipFree(old);
-  return VSP_OK;
+  return configure_rate(ctx, "output rows", "output", ctx->out_rates, VSP_OUTPUT_RATES_MAX, out_rate, model_rate, out_rate, zeros,
+                        beta, rolloff, OUT_MAX_L, OUT_MAX_M);
 }
 
 int vsp_output_rows(vsp_ctx* ctx, void* stream, int B, const vsp_output_row* rows) {
@@ -271,7 +148,7 @@ int vsp_output_rows(vsp_ctx* ctx, void* stream, int B, const vsp_output_row* row
     if (r.n < 0 || r.n > big || r.x_first < 0 || r.x_first > big || r.out_fill < 0 || r.out_fill > big * 512)
       return ctx->fail(VSP_ERR_ARG, "vsp_output_rows: row %d has a negative x_first, n or out_fill", b);
     if (r.n == 0 && !r.ended) return ctx->fail(VSP_ERR_ARG, "vsp_output_rows: row %d: n == 0 is legal only with ended == 1", b);
-    const vsp_ctx::InputRate* t = find_rate(ctx, r.out_rate);
+    const vsp_ctx::RateTable* t = find_rate(ctx->out_rates, VSP_OUTPUT_RATES_MAX, r.out_rate);
     if (!t)
       return ctx->fail(VSP_ERR_STATE, "vsp_output_rows: row %d: rate %d Hz is not configured (vsp_output_rate_configure)", b,
                        r.out_rate);

@@ -15,6 +15,12 @@
 // the window a streaming caller passes or the batch layout -- which is what makes the streamed output byte-identical to
 // the one-shot one.  Samples outside [0, n_valid[b]) and outside the passed window are never read (selected to zero while
 // the tile is staged), so whatever a padded batch holds behind an utterance's end cannot reach the output.
+//
+// What this file shares with input_stage.hip and output_rows.hip lives in resample_common.h: the staged tile of mode 0
+// (rs_tile_output, with 16-byte loads of four floats where the rows are aligned, element by element where not), the
+// global-memory chain of mode 2 (rs_one_output), the store (out_store), the staging plan (stage_plan) and the way a rate is
+// configured (configure_rate into vsp_ctx::out_stage).  Its own: the [lo, hi) window of resample_kernel (x_first, x_len,
+// n_valid), the one-phase tile of mode 1 and its sizing, and stream_output_kernel.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -28,10 +34,8 @@ namespace {
 
 using namespace vsp::rs;
 
-constexpr int RS_TILE = 256;            // output samples (= threads) per block
 constexpr int RS_X_LDS_FLOATS = 12288;  // input staging area per block (48 KiB)
 constexpr int RS_TAB_LDS_FLOATS = 4096; // a one-phase table (L = 1) up to this size is held in LDS (16 KiB)
-constexpr int RS_MIN_PASS = 32;         // fewer taps per staging pass than this: read x from global memory instead
 
 struct ResampleArgs {
   const float* x;
@@ -44,137 +48,93 @@ struct ResampleArgs {
   int L, M, J, P;
   int pass;               // taps per staging pass (multiple of 4, or P)
   int xs_words;           // LDS words of the input tile (the one-phase table follows it)
-  int seg;                // L = 1 staging: words per polyphase segment of the de-interleaved tile (0: linear tile)
-  int mode;               // 0: x tile in LDS, table from global / L2;  1: L = 1, de-interleaved x tile + table in LDS;
-                          // 2: x and table from global memory (spans too long for LDS)
-  int pcm;                // 0: float32 out, 1: int16 out
-  int pair_ok;            // int16 rows are 4-byte aligned: even lanes store packed pairs
+  int seg;                // mode 1: words per polyphase segment of the de-interleaved tile
+  int mode;               // 0: x tile in LDS, table from global / L2 (rs_tile_output);  1: L = 1, de-interleaved x tile +
+                          // table in LDS;  2: x and table from global memory (spans too long for LDS; rs_one_output)
+  int enc;                // VSP_OUT_F32 or VSP_OUT_S16
   int vec_ok;             // x rows are 16-byte aligned: the tile is staged with 16-byte loads
 };
 
-// Stores sample j of a row (float32, or PCM16 with even lanes storing packed pairs where the row allows it).  Every lane
-// of the wave calls it with a valid y (the shuffle takes all of them); `active` lanes store, `has_next`: lane + 1 is active.
-__device__ __forceinline__ void rs_store(void* row, int64_t j, float y, bool active, bool has_next, int pcm, int pair_ok) {
-  if (!pcm) {
-    if (active) static_cast<float*>(row)[j] = y;
-    return;
-  }
-  const int q = rs_pcm16(y);
-  const int q_next = __shfl_down(q, 1);
-  int16_t* o16 = static_cast<int16_t*>(row) + j;
-  if (pair_ok) {
-    if (!(threadIdx.x & 1) && active) {
-      if (has_next) *reinterpret_cast<uint32_t*>(o16) = (uint32_t)(q & 0xffff) | ((uint32_t)q_next << 16);
-      else *o16 = (int16_t)q;
+// Mode 1 of resample_kernel, L = 1: the tile is staged DE-INTERLEAVED (word o at (o mod M) seg + o / M) beside the table.
+// Lane t reads tile word off + i = (off0 + t M) + i, so the lanes of a wave read consecutive words of one segment: no bank
+// conflict where the linear tile would be read at stride M; the tap is the same for all lanes (a broadcast LDS read).
+// Taps are fetched four at a time (one 16-byte broadcast read): 1.25 LDS reads per FMA instead of 2.  Geometry, passes and
+// FMA order are rs_tile_output's.
+template <class Sample>
+__device__ __forceinline__ float one_phase_output(const ResampleArgs& a, float* smem, int64_t m_first, int64_t m_last, int64_t a0,
+                                                  int64_t lo, int64_t hi, const float* __restrict__ xb, Sample sample) {
+  const int tid = threadIdx.x;
+  float* xs = smem;
+  float* ts = smem + a.xs_words;
+  for (int i = tid; i < a.P; i += RS_TILE) ts[i] = a.tab[i];
+  const int64_t ks = min(m_first + tid, m_last) * a.M - a.J;        // first input sample of this output
+  int64_t kb = m_first * a.M - a.J;                                 // first input sample of the tile
+  if (a.vec_ok) kb -= (a0 + kb) & 3;                                // ... moved down to a 16-byte boundary of x
+  const int off = (int)(ks - kb);
+  const int span = (int)(m_last * a.M - a.J - kb) + 1;              // tile words before the pass's taps are added
+  float acc = 0.f;
+  for (int i0 = 0; i0 < a.P; i0 += a.pass) {
+    const int n_i = min(a.pass, a.P - i0);
+    const int need = span + n_i - 1;
+    const int64_t k_base = kb + i0;
+    if (i0) __syncthreads();
+    if (a.vec_ok) {
+      for (int o = tid * 4; o < need; o += RS_TILE * 4) {
+        const int64_t k = k_base + o;
+        float4 v;
+        if (k >= lo && k + 3 < hi) v = *reinterpret_cast<const float4*>(xb + k);
+        else v = make_float4(sample(k), sample(k + 1), sample(k + 2), sample(k + 3));
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xs[((o + q) % a.M) * a.seg + (o + q) / a.M] = e[q];
+      }
+    } else {
+      for (int o = tid; o < need; o += RS_TILE) xs[(o % a.M) * a.seg + o / a.M] = sample(k_base + o);
     }
-  } else if (active) {
-    *o16 = (int16_t)q;
+    __syncthreads();
+    int r = off % a.M;
+    const float* xp = xs + r * a.seg + off / a.M;
+    const int wrap = a.M * a.seg - 1;
+    auto step = [&]() { xp += a.seg; if (++r == a.M) { r = 0; xp -= wrap; } };
+    int i = 0;
+    for (; i + 4 <= n_i; i += 4) {
+      const float4 t = *reinterpret_cast<const float4*>(ts + i0 + i);
+      acc = fmaf(t.x, *xp, acc); step();
+      acc = fmaf(t.y, *xp, acc); step();
+      acc = fmaf(t.z, *xp, acc); step();
+      acc = fmaf(t.w, *xp, acc); step();
+    }
+    for (; i < n_i; ++i) { acc = fmaf(ts[i0 + i], *xp, acc); step(); }
   }
+  return acc;
 }
 
 __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a) {
   extern __shared__ float smem[];
-  const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int64_t m_first = a.m0 + (int64_t)blockIdx.x * RS_TILE;
   const int64_t m_last = min(m_first + RS_TILE, a.m1) - 1;         // (the grid covers [m0, m1): m_first <= m_last)
-  const int64_t m = m_first + tid;
-  const bool active = m <= m_last;
-  const int64_t mm = active ? m : m_last;                            // idle lanes shadow the last sample: offsets stay in the tile
+  const int64_t m = m_first + threadIdx.x;
   int64_t nv = a.n_valid ? a.n_valid[b] : a.n_max;
   nv = min(max(nv, (int64_t)0), a.n_max);
   const int64_t lo = max(a.x_first, (int64_t)0), hi = min(nv, a.x_first + a.x_len);   // readable samples [lo, hi)
   const int64_t out_len = (nv * a.L + a.M - 1) / a.M;
-  const float* __restrict__ xb = a.x + (int64_t)b * a.x_stride - a.x_first;             // xb[k] = sample k of utterance b
-  const int64_t ks = (mm * a.M) / a.L - a.J;                                             // first input sample of this output
-  const int col = (int)(mm % a.L);
-  const float* __restrict__ tcol = a.tab + col;
-  float acc = 0.f;
+  const int64_t a0 = (int64_t)b * a.x_stride - a.x_first;                               // (x itself is 16-byte aligned where it matters)
+  const float* __restrict__ xb = a.x + a0;                                              // xb[k] = sample k of utterance b
+  auto sample = [&](int64_t k) { return (k >= lo && k < hi) ? xb[k] : 0.f; };
+  auto load = [&](int64_t k, float* v) {
+    const float4 w = *reinterpret_cast<const float4*>(xb + k);
+    v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+  };
+  float acc;
+  if (a.mode == 2) acc = rs_one_output(a.tab, a.L, a.M, a.J, a.P, min(m, m_last), sample);
+  else if (a.mode == 1) acc = one_phase_output(a, smem, m_first, m_last, a0, lo, hi, xb, sample);
+  else if (a.vec_ok) acc = rs_tile_output<4>(smem, a.tab, a.L, a.M, a.J, a.P, a.pass, m_first, m_last, a0, lo, hi, load, sample);
+  else acc = rs_tile_output<1>(smem, a.tab, a.L, a.M, a.J, a.P, a.pass, m_first, m_last, a0, lo, hi, load, sample);
 
-  if (a.mode == 2) {
-    acc = rs_one_output(tcol, a.L, a.P, ks, [&](int64_t k) { return (k >= lo && k < hi) ? xb[k] : 0.f; });
-  } else {
-    float* xs = smem;
-    float* ts = smem + a.xs_words;
-    if (a.mode == 1) {
-      for (int i = tid; i < a.P; i += RS_TILE) ts[i] = a.tab[i];
-    }
-    int64_t kb = (m_first * a.M) / a.L - a.J;                        // first input sample of the tile
-    if (a.vec_ok) kb -= (((int64_t)b * a.x_stride - a.x_first + kb) & 3);   // ... moved down to a 16-byte boundary of x
-    const int off = (int)(ks - kb);
-    const int span = (int)((m_last * a.M) / a.L - a.J - kb) + 1;    // tile words before the pass's taps are added
-    for (int i0 = 0; i0 < a.P; i0 += a.pass) {
-      const int n_i = min(a.pass, a.P - i0);
-      const int need = span + n_i - 1;
-      const int64_t k_base = kb + i0;
-      if (i0) __syncthreads();
-      if (a.vec_ok) {
-        for (int o = tid * 4; o < need; o += RS_TILE * 4) {
-          const int64_t k = k_base + o;
-          float4 v;
-          if (k >= lo && k + 3 < hi) {
-            v = *reinterpret_cast<const float4*>(xb + k);
-          } else {
-            v.x = (k >= lo && k < hi) ? xb[k] : 0.f;
-            v.y = (k + 1 >= lo && k + 1 < hi) ? xb[k + 1] : 0.f;
-            v.z = (k + 2 >= lo && k + 2 < hi) ? xb[k + 2] : 0.f;
-            v.w = (k + 3 >= lo && k + 3 < hi) ? xb[k + 3] : 0.f;
-          }
-          if (a.seg) {
-            const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xs[((o + q) % a.M) * a.seg + (o + q) / a.M] = e[q];
-          } else {
-            *reinterpret_cast<float4*>(xs + o) = v;
-          }
-        }
-      } else {
-        for (int o = tid; o < need; o += RS_TILE) {
-          const int64_t k = k_base + o;
-          const float v = (k >= lo && k < hi) ? xb[k] : 0.f;
-          xs[a.seg ? (o % a.M) * a.seg + o / a.M : o] = v;
-        }
-      }
-      __syncthreads();
-      if (a.mode == 1) {
-        // L = 1: lane t reads tile word off + i = (off0 + t M) + i.  In the de-interleaved tile (word o at
-        // (o mod M) seg + o / M) the lanes of a wave read consecutive words of one segment: no bank conflict where the
-        // linear tile would be read at stride M; the tap is the same for all lanes (a broadcast LDS read).
-        // Taps are fetched four at a time (one 16-byte broadcast read): 1.25 LDS reads per FMA instead of 2.
-        int r = off % a.M;
-        const float* xp = xs + r * a.seg + off / a.M;
-        const int wrap = a.M * a.seg - 1;
-        auto step = [&]() { xp += a.seg; if (++r == a.M) { r = 0; xp -= wrap; } };
-        int i = 0;
-        for (; i + 4 <= n_i; i += 4) {
-          const float4 t = *reinterpret_cast<const float4*>(ts + i0 + i);
-          acc = fmaf(t.x, *xp, acc); step();
-          acc = fmaf(t.y, *xp, acc); step();
-          acc = fmaf(t.z, *xp, acc); step();
-          acc = fmaf(t.w, *xp, acc); step();
-        }
-        for (; i < n_i; ++i) { acc = fmaf(ts[i0 + i], *xp, acc); step(); }
-      } else {
-        const float* __restrict__ tp = tcol + (size_t)i0 * a.L;
-        const float* xo = xs + off;
-        int i = 0;
-        for (; i + 4 <= n_i; i += 4) {                               // (four table loads in flight; the FMA order stays ascending)
-          const float t0 = tp[(size_t)i * a.L], t1 = tp[(size_t)(i + 1) * a.L], t2 = tp[(size_t)(i + 2) * a.L],
-                      t3 = tp[(size_t)(i + 3) * a.L];
-          acc = fmaf(t0, xo[i], acc);
-          acc = fmaf(t1, xo[i + 1], acc);
-          acc = fmaf(t2, xo[i + 2], acc);
-          acc = fmaf(t3, xo[i + 3], acc);
-        }
-        for (; i < n_i; ++i) acc = fmaf(tp[(size_t)i * a.L], xo[i], acc);
-      }
-    }
-  }
-
-  const float y = m < out_len ? acc : 0.f;                           // behind the utterance's own output: silence
-  // (all lanes take part in the store's shuffle; idle lanes hold a valid shadow)
-  rs_store(static_cast<char*>(a.out) + (int64_t)b * a.out_stride * (a.pcm ? 2 : 4), m - a.m0, y, active, m + 1 <= m_last, a.pcm,
-           a.pair_ok);
+  // behind the utterance's own output: silence  (all lanes take part in the store's shuffle; idle lanes hold a valid shadow)
+  out_store(static_cast<char*>(a.out) + (int64_t)b * a.out_stride * (a.enc == VSP_OUT_S16 ? 2 : 4), a.enc, m - a.m0,
+            m < out_len ? acc : 0.f, a.m1 - a.m0);
 }
 
 // The ragged output stage (kernels.h, launch_stream_output).  grid (out_blocks + hist_blocks, B), RS_TILE threads; a block
@@ -184,7 +144,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const ResampleArgs a)
 // come from global memory (L1 / L2: a tile's window is a few KB) -- the chain of resample_kernel, so the same bits.
 __global__ __launch_bounds__(RS_TILE) void stream_output_kernel(const vsp::StreamOutRows rows, const float* __restrict__ o_span,
                                                                 long o_bs, const vsp::StreamOutFilter f, int K, int out_blocks,
-                                                                void* __restrict__ out, long out_stride, int pcm, int pair_ok) {
+                                                                void* __restrict__ out, long out_stride, int enc) {
   const int b = blockIdx.y;
   const vsp::StreamOutRow& r = rows.r[b];
   const int64_t x_first = r.x_first, x_end = x_first + r.n;
@@ -200,35 +160,18 @@ __global__ __launch_bounds__(RS_TILE) void stream_output_kernel(const vsp::Strea
   const int64_t j = (int64_t)blockIdx.x * RS_TILE + threadIdx.x;
   const int64_t m = p.m0 + j;
   float y = 0.f;
-  if (m < p.m1) y = rs_one_output(f.tab + (int)(m % f.L), f.L, f.P, (m * f.M) / f.L - f.J, sample);
-  rs_store(static_cast<char*>(out) + (int64_t)b * out_stride * (pcm ? 2 : 4), j, y, j < out_stride, j + 1 < out_stride, pcm,
-           pair_ok);
+  if (m < p.m1) y = rs_one_output(f.tab, f.L, f.M, f.J, f.P, m, sample);
+  out_store(static_cast<char*>(out) + (int64_t)b * out_stride * (enc == VSP_OUT_S16 ? 2 : 4), enc, j, y, out_stride);
 }
-
-// ---------------------------------------------------------------------------------------------- host: plan and filter
-constexpr int RS_MAX_L = 320, RS_MAX_M = 441;   // what resample_kernel's staging covers
-
-int make_plan(int in_rate, int out_rate, int zeros, Plan& p) { return vsp::rs::make_plan(in_rate, out_rate, zeros, RS_MAX_L, RS_MAX_M, p); }
 
 }  // namespace
 
 int vsp_resample_plan(int in_rate, int out_rate, int zeros, int* L, int* M, int* half_len) {
-  Plan p;
-  if (!L || !M || !half_len) return VSP_ERR_ARG;
-  if (int rc = make_plan(in_rate, out_rate, zeros, p)) return rc;
-  *L = p.L; *M = p.M; *half_len = p.H;
-  return VSP_OK;
+  return plan_api(in_rate, out_rate, zeros, OUT_MAX_L, OUT_MAX_M, L, M, half_len);
 }
 
 int vsp_resample_filter(int in_rate, int out_rate, int zeros, double beta, double rolloff, float* taps_host) {
-  Plan p;
-  if (!taps_host || !(beta >= 0.0) || !(rolloff <= 1.0)) return VSP_ERR_ARG;
-  if (int rc = make_plan(in_rate, out_rate, zeros, p)) return rc;
-  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
-  std::vector<double> h;
-  make_filter(p, zeros, beta, rolloff, h);
-  for (size_t i = 0; i < h.size(); ++i) taps_host[i] = (float)h[i];
-  return VSP_OK;
+  return filter_api(in_rate, out_rate, zeros, beta, rolloff, OUT_MAX_L, OUT_MAX_M, taps_host);
 }
 
 int64_t vsp_resample_out_len(int64_t n, int L, int M) {
@@ -283,9 +226,8 @@ hipError_t launch_stream_output(const float* o_span, long o_bs, const StreamOutR
       return hipErrorInvalidValue;
   }
   const int out_blocks = (int)((out_stride + RS_TILE - 1) / RS_TILE), hist_blocks = (K + RS_TILE - 1) / RS_TILE;
-  const int pair_ok = pcm && ((uintptr_t)out % 4 == 0) && (out_stride % 2 == 0);
   hipLaunchKernelGGL(stream_output_kernel, dim3(out_blocks + hist_blocks, B), dim3(RS_TILE), 0, s, rows, o_span, o_bs, f, K,
-                     out_blocks, out, out_stride, pcm, pair_ok);
+                     out_blocks, out, out_stride, pcm ? VSP_OUT_S16 : VSP_OUT_F32);
   return hipGetLastError();
 }
 }  // namespace vsp
@@ -293,46 +235,21 @@ hipError_t launch_stream_output(const float* o_span, long o_bs, const StreamOutR
 int vsp_output_configure(vsp_ctx* ctx, int in_rate, int out_rate, int zeros, double beta, double rolloff) {
   if (!ctx) return VSP_ERR_ARG;
   if (out_rate == 0) {                                   // off
-    if (ctx->out_tab) (void)hipFree(ctx->out_tab);
-    ctx->out_tab = nullptr;
-    ctx->out_L = ctx->out_M = ctx->out_H = ctx->out_J = ctx->out_P = 0;
+    drop_rate(ctx, &ctx->out_stage);
     return VSP_OK;
   }
-  if (zeros == 0) zeros = 32;
-  if (!(beta >= 0.0)) return ctx->fail(VSP_ERR_ARG, "output stage: beta must be >= 0");
-  if (!(rolloff <= 1.0)) return ctx->fail(VSP_ERR_ARG, "output stage: rolloff must be in (0, 1] (<= 0: 1 - 3.065 / zeros)");
-  Plan p;
-  if (int rc = make_plan(in_rate, out_rate, zeros, p))
-    return ctx->fail(rc, "output stage %d -> %d Hz, %d zeros: rates must be positive, L <= 320, M <= 441, 1 <= zeros <= 64",
-                     in_rate, out_rate, zeros);
-  if (!(rolloff > 0.0)) rolloff = default_rolloff(zeros);
-  std::vector<double> h;
-  make_filter(p, zeros, beta, rolloff, h);
-  const int L = p.L, M = p.M, H = p.H;
-  int J, P;
-  std::vector<float> tab;
-  make_table(p, h, J, P, tab);
-  void* d = nullptr;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess) e = hipMalloc(&d, tab.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d) (void)hipFree(d);
-    return ctx->fail(VSP_ERR_HIP, "output stage table: %s", hipGetErrorString(e));
-  }
-  if (ctx->out_tab) (void)hipFree(ctx->out_tab);
-  ctx->out_tab = static_cast<float*>(d);
-  ctx->out_L = L; ctx->out_M = M; ctx->out_H = H; ctx->out_J = J; ctx->out_P = P;
-  return VSP_OK;
+  return configure_rate(ctx, "output stage", "output", &ctx->out_stage, 1, 0, in_rate, out_rate, zeros, beta, rolloff, OUT_MAX_L,
+                        OUT_MAX_M);
 }
 
 int vsp_output_chunk(vsp_ctx* ctx, void* stream, int B, const float* x, int64_t x_stride, int64_t x_first, int64_t x_len,
                      const int64_t* n_valid, int64_t n_max, int64_t m0, int64_t m1, void* out, int64_t out_stride,
                      int pcm) {
   if (!ctx) return VSP_ERR_ARG;
-  if (!ctx->out_tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
+  const vsp_ctx::RateTable& t = ctx->out_stage;
+  if (!t.tab) return ctx->fail(VSP_ERR_STATE, "output stage not configured (vsp_output_configure)");
   if (B < 0 || B > 65535 || !x || !out || (pcm != 0 && pcm != 1)) return ctx->fail(VSP_ERR_ARG, "vsp_output_chunk: null or bad argument");
-  const int64_t L = ctx->out_L, M = ctx->out_M, H = ctx->out_H;
+  const int64_t L = t.L, M = t.M, H = t.H;
   if (n_max < 0 || n_max > ((int64_t)1 << 40) || x_first < 0 || x_len < 0 || x_first + x_len > n_max || x_len > x_stride)
     return ctx->fail(VSP_ERR_SHAPE, "vsp_output_chunk: window [%lld, +%lld) outside [0, n_max = %lld) or longer than its row",
                      (long long)x_first, (long long)x_len, (long long)n_max);
@@ -351,26 +268,23 @@ int vsp_output_chunk(vsp_ctx* ctx, void* stream, int B, const float* x, int64_t 
   a.x = x; a.x_stride = x_stride; a.x_first = x_first; a.x_len = x_len;
   a.n_valid = n_valid; a.n_max = n_max; a.m0 = m0; a.m1 = m1;
   a.out = out; a.out_stride = out_stride;
-  a.tab = ctx->out_tab;
-  a.L = (int)L; a.M = (int)M; a.J = ctx->out_J; a.P = ctx->out_P;
-  a.pcm = pcm;
-  a.pair_ok = pcm && ((uintptr_t)out % 4 == 0) && (out_stride % 2 == 0);
+  a.tab = t.tab;
+  a.L = t.L; a.M = t.M; a.J = t.J; a.P = t.P;
+  a.enc = pcm ? VSP_OUT_S16 : VSP_OUT_F32;
   a.vec_ok = ((uintptr_t)x % 16 == 0) && (x_stride % 4 == 0);
-  // tile words: the outputs of a tile start within (TILE - 1) M / L + 1 samples of each other, + 3 for the alignment
-  const int64_t span = ((int64_t)(RS_TILE - 1) * M) / L + 2 + 3;
-  const bool one_phase = L == 1 && a.P <= RS_TAB_LDS_FLOATS;
-  const int64_t room = one_phase ? RS_X_LDS_FLOATS - span - 2 * M - 8 : RS_X_LDS_FLOATS - span - 8;
-  a.seg = 0;
-  if (room >= std::min<int64_t>(a.P, RS_MIN_PASS)) {
-    a.pass = room >= a.P ? a.P : (int)(room & ~(int64_t)3);
-    a.mode = one_phase ? 1 : 0;
-    if (one_phase) a.seg = (int)((span + a.pass + 3) / M + 2);          // (every tile word, the 16-byte loads' overhang included)
-    a.xs_words = one_phase ? (int)(M * a.seg) : (int)(span + a.pass + 8);
-    a.xs_words = (a.xs_words + 3) & ~3;
-  } else {
-    a.pass = a.P;
-    a.mode = 2;
-    a.xs_words = 0;
+  const StagePlan sp = stage_plan(RS_X_LDS_FLOATS, 3, 8, 4, t.L, t.M, t.P);
+  a.pass = sp.pass; a.mode = sp.mode; a.xs_words = sp.xs_words; a.seg = 0;
+  if (L == 1 && a.P <= RS_TAB_LDS_FLOATS) {
+    // one phase: the de-interleaved tile of mode 1 (stage_plan's span, 2 M words of headroom), or global memory
+    const int64_t span = ((int64_t)(RS_TILE - 1) * M) / L + 2 + 3;
+    const int64_t room = RS_X_LDS_FLOATS - span - 2 * M - 8;
+    a.pass = a.P; a.mode = 2; a.xs_words = 0;
+    if (room >= std::min<int64_t>(a.P, RS_MIN_PASS)) {
+      a.pass = room >= a.P ? a.P : (int)(room & ~(int64_t)3);
+      a.mode = 1;
+      a.seg = (int)((span + a.pass + 3) / M + 2);                        // (every tile word, the 16-byte loads' overhang included)
+      a.xs_words = (int)(M * a.seg + 3) & ~3;
+    }
   }
   const size_t lds = (size_t)(a.xs_words + (a.mode == 1 ? a.P : 0)) * sizeof(float);   // <= 48 KiB + 16 KiB
   const dim3 grid((unsigned)((m1 - m0 + RS_TILE - 1) / RS_TILE), (unsigned)B);

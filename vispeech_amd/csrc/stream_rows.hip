@@ -8,6 +8,7 @@
 // to keep alive behind the launch.  A block serves one row (blockIdx.y), so a descriptor is read through scalar loads.
 // Both kernels move 16 bytes per lane where the addresses allow and go element by element at the ragged edges.
 #include "kernels.h"
+#include "resample_common.h"   // (rs_pcm16: the output stage's PCM16 value)
 
 namespace vsp {
 
@@ -47,12 +48,6 @@ __global__ void __launch_bounds__(256) stream_gather_kernel(const StreamGatherRo
   *reinterpret_cast<float4*>(zp + ((size_t)b * C + c) * S4 + t) = v;
 }
 
-// service.pcm16 / vsp_output_chunk: clip(rint(y * 32767.0f), -32768, 32767), product in fp32, round half to even
-__device__ __forceinline__ int16_t collect_pcm16(float y) {
-  const float q = rintf(y * 32767.0f);
-  return (int16_t)(int)fminf(fmaxf(q, -32768.f), 32767.f);
-}
-
 // grid (quads of out_stride, B), 256 threads: out[b][i] = i < n ? o_span[b][off + i] : 0 for i < out_stride.
 template <bool PCM>
 __global__ void __launch_bounds__(256) stream_collect_kernel(const float* __restrict__ o_span, long o_bs,
@@ -77,12 +72,12 @@ __global__ void __launch_bounds__(256) stream_collect_kernel(const float* __rest
     int16_t* o = static_cast<int16_t*>(out) + (size_t)b * out_stride + i;
     // (a sample behind n is the quantised 0.0f = 0: the row's rest is exactly zero)
     if (whole) {
-      const uint32_t w0 = (uint32_t)(uint16_t)collect_pcm16(v[0]) | ((uint32_t)(uint16_t)collect_pcm16(v[1]) << 16);
-      const uint32_t w1 = (uint32_t)(uint16_t)collect_pcm16(v[2]) | ((uint32_t)(uint16_t)collect_pcm16(v[3]) << 16);
+      const uint32_t w0 = (uint32_t)(uint16_t)rs::rs_pcm16(v[0]) | ((uint32_t)(uint16_t)rs::rs_pcm16(v[1]) << 16);
+      const uint32_t w1 = (uint32_t)(uint16_t)rs::rs_pcm16(v[2]) | ((uint32_t)(uint16_t)rs::rs_pcm16(v[3]) << 16);
       *reinterpret_cast<uint2*>(o) = make_uint2(w0, w1);
       return;
     }
-    for (int k = 0; k < 4 && i + k < out_stride; ++k) o[k] = collect_pcm16(v[k]);
+    for (int k = 0; k < 4 && i + k < out_stride; ++k) o[k] = (int16_t)rs::rs_pcm16(v[k]);
   } else {
     float* o = static_cast<float*>(out) + (size_t)b * out_stride + i;
     if (whole) {
