@@ -919,7 +919,8 @@ int vsp_output_rows(vsp_ctx* ctx, void* stream, int B, const vsp_output_row* row
 /* Per-phoneme F0 and energy of a recording: the producer of the pitch_control / energy_control tensors vsp_encode reads,
  * what the reference's data preparation (f0energy.py) computes with parselmouth and librosa.  The specification is this
  * project's own (restated in fp64 in tests/prosody_ref.py) and is NOT bit-compatible with parselmouth:
- * no path finder, no sinc interpolation.
+ * no sinc interpolation, and in the three calls of this section every frame decides for itself (the path finder is the
+ * next section's, round 19).
  *
  * Constants: fs = VSP_PROSODY_FS, n_fft = VSP_PROSODY_NFFT; `hop` is the model's (512).  A row of n samples has
  * F(n) = n / hop + 1 frames, frame k centred on sample hop * k, and needs n >= n_fft / 2 + 1 (for the reflection).
@@ -967,6 +968,50 @@ int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int h
 int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const float* f0_frames, const float* energy_frames,
                          const int64_t* frames_host, const int64_t* durations_host, const int64_t* lengths_host, float* f0,
                          float* energy, void* workspace, int64_t workspace_bytes);
+
+/* ---- prosody: the path finder (round 19, ABI 7, additive) ------------- */
+/* The second half of Boersma's method (1993, section 2 step 4): several candidates per frame and the path through them
+ * that maximises the summed strengths minus a cost per octave jumped and per voicing change, instead of every frame's own
+ * decision.  Restated in fp64 in tests/prosody_path_ref.py.  S and U below are a frame's strengths exactly as above.
+ *   candidates  A frame has 16 slots of (f, delta), N <= VSP_PROSODY_MAX_CANDIDATES of them used.  Slot 0 is the unvoiced
+ *               candidate (0, U); slots 1 .. max_candidates - 1 are the strongest voiced candidates (f, S) in descending S, the
+ *               lower lag first among equals; unused slots (slot 15 always) are (0, -inf).  A frame with r_a(0) = 0 or gpk = 0
+ *               has slot 0 alone, with delta = voicing_threshold + 2.  Behind a row's frames both tables are exact 0.
+ *   path        For a row of F frames, c_0 .. c_{F-1} maximising sum_k delta_k(c_k) - sum_{k>=1} T(c_{k-1}, c_k): T = 0 between two
+ *               unvoiced candidates (f = 0), voiced_unvoiced_cost kappa between a voiced and an unvoiced one,
+ *               octave_jump_cost kappa |log2(f_a / f_b)| between two voiced ones; kappa = fs / (100 hop) (0.861 at hop 512).
+ *               s_0 = delta_0, s_k(c) = delta_k(c) + max_p (s_{k-1}(p) - T(p, c)), the lowest p among equals; every frame's s_k
+ *               is then normalised by subtracting its maximum (the best entry is exactly 0.0f); the end takes the lowest c
+ *               among equals.  f0_k = f of the chosen candidate, bit for bit.  With both costs 0 the path is the
+ *               per-frame decision of vsp_prosody_contours in every bit.
+ * One stated difference from Praat: its voiced strength is R - octave_cost log2(ceiling / f), this one's R + octave_cost
+ * log2(f / floor): a constant octave_cost log2(ceiling / floor) (0.032 at the defaults) in favour of voiced.
+ * path NULL: octave-jump cost 0.35, voiced/unvoiced cost 0.14, max_candidates 15.  Refused (VSP_ERR_ARG): a negative cost,
+ * max_candidates outside [2, 15], and everything vsp_prosody_contours refuses -- on the host, before any launch. */
+#define VSP_PROSODY_MAX_CANDIDATES 15
+typedef struct vsp_prosody_path_params {
+  float octave_jump_cost, voiced_unvoiced_cost;
+  int32_t max_candidates;
+} vsp_prosody_path_params;
+/* Workspace of any of the three calls below (VSP_ERR_ARG as a negative size). */
+int64_t vsp_prosody_path_workspace_bytes(int B, int64_t L_max, int hop, const vsp_prosody_params* params,
+                                         const vsp_prosody_path_params* path);
+/* The candidates alone: vsp_prosody_contours with the tables cand_f, cand_s [B][F_max][16] float32 (device) in place of
+ * f0_frames; energy_frames and frames as there.  Two launches. */
+int vsp_prosody_candidates(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                           const int64_t* n_samples_host, const vsp_prosody_params* params, int max_candidates, float* cand_f,
+                           float* cand_s, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes);
+/* The path alone, a stand-alone operator on any candidate tables [B][F_max][16] (device): delta finite or -inf, at least one
+ * finite per frame, f = 0 for an unvoiced candidate.  frames_host [B]: HOST memory, 1 <= frames <= F_max; frames at or behind
+ * frames_host[b] are not read.  f0_frames [B][F_max] (device): exact 0.0 behind a row's frames.  One launch, one wave per
+ * row, behind one small upload; back-pointers (16 bytes a frame) go through the workspace. */
+int vsp_prosody_path(vsp_ctx* ctx, void* stream, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
+                     const int64_t* frames_host, const vsp_prosody_path_params* path, float* f0_frames, void* workspace,
+                     int64_t workspace_bytes);
+/* Both: vsp_prosody_contours' arguments and `path`; the candidate tables live in the workspace.  Three launches. */
+int vsp_prosody_contours_path(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                              const int64_t* n_samples_host, const vsp_prosody_params* params, const vsp_prosody_path_params* path,
+                              float* f0_frames, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch

@@ -8,7 +8,11 @@
 The GPU figures are device-event times per call (``torch.cuda.Event``) over a window of ``steps`` calls after a warm-up of
 the same shape; best / median / spread of ``rounds`` rounds that alternate over the calls.  No gate is set on any of them.
 
-usage: tools/prosody_measure.py [steps] [rounds] [out.txt]     (default out: profiles/r18_prosody.txt)"""
+``--path`` measures the path finder instead: the contour call without and with the path, the
+candidate call and the path alone on its tables, the same recordings, timer and rounds.
+
+usage: tools/prosody_measure.py [--path] [steps] [rounds] [out.txt]
+       (default out: profiles/r18_prosody.txt, with --path profiles/r19_prosody_path.txt)"""
 import os
 import platform
 import sys
@@ -27,9 +31,11 @@ from vispeech_amd.models import SynthesizerTrn          # noqa: E402
 from vispeech_amd.schema import dims_from_ctor          # noqa: E402
 from vispeech_amd.synth import synth_state_dict         # noqa: E402
 
-STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r18_prosody.txt")
+PATH = "--path" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--path"]
+STEPS = int(ARGS[0]) if len(ARGS) > 0 else 10
+ROUNDS = int(ARGS[1]) if len(ARGS) > 1 else 3
+OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "r19_prosody_path.txt" if PATH else "r18_prosody.txt")
 SECONDS, B, TP = 10, 16, 31
 
 
@@ -65,6 +71,46 @@ def fmt(v):
     return f"best {min(v):8.3f} ms  median {float(np.median(v)):8.3f} ms  spread {max(v) - min(v):6.3f} ms"
 
 
+def measure_path(net, dims, audio, n_samples):
+    """The contour call without and with the path finder, and the two halves of the latter on their own."""
+    eng = net._engine
+    F = n_samples[0] // dims.hop_length + 1
+    cand_f, cand_s, _, _, frames_host = eng.prosody_candidates(audio, n_samples)
+    f0 = eng.prosody_contours(audio, n_samples)[0]
+    p0 = eng.prosody_contours(audio, n_samples, path=True)[0]
+    z0 = eng.prosody_contours(audio, n_samples, path=(0.0, 0.0, 15))[0]
+    assert torch.equal(z0, f0), "with both costs 0 the path must be the per-frame decision"
+    changed = int((p0 != f0).sum())
+    jobs = {
+        "prosody_contours": lambda: eng.prosody_contours(audio, n_samples),
+        "prosody_contours(path=True)": lambda: eng.prosody_contours(audio, n_samples, path=True),
+        "prosody_candidates": lambda: eng.prosody_candidates(audio, n_samples),
+        "prosody_path (alone)": lambda: eng.prosody_path(cand_f, cand_s, frames_host),
+    }
+    ms = {k: [] for k in jobs}
+    for _ in range(ROUNDS):
+        for k, fn in jobs.items():
+            ms[k].append(timed(fn, STEPS))
+    med = lambda k: float(np.median(ms[k]))
+    props = torch.cuda.get_device_properties(0)
+    lines = [f"prosody path finder: default configuration ({dims.sampling_rate} Hz, hop {dims.hop_length}), {B} recordings of "
+             f"{SECONDS} s ({F} frames each); defaults (octave jump 0.35, voiced/unvoiced 0.14, 15 candidates); {ROUNDS} rounds, "
+             f"a window of {STEPS} calls",
+             f"device {torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', 'arch not available')}, "
+             f"{props.multi_processor_count} CUs), host {platform.node()}",
+             "timer: device events around a window of calls, per call", ""]
+    for k in jobs:
+        lines.append(f"   {k:29s} {fmt(ms[k])}")
+    lines += ["",
+              f"   the path adds {med('prosody_contours(path=True)') - med('prosody_contours'):.3f} ms to the contour call (medians): "
+              f"{med('prosody_candidates') - med('prosody_contours'):+.3f} ms in the candidate kernel's tail and its tables, "
+              f"{med('prosody_path (alone)'):.3f} ms the path kernel ({B} waves, {F} frames each in sequence: "
+              f"{med('prosody_path (alone)') / F * 1e3:.2f} us per frame, forward and backward)",
+              f"   frames whose F0 the path changes: {changed} of {B * F}; with both costs 0: none, bit for bit"]
+    assert eng.status() == 0
+    return "\n".join(lines)
+
+
 def main():
     a, kw0 = vcfg.synthesizer_args(vcfg.default_hparams())
     dims = dims_from_ctor(*a, **kw0)
@@ -75,6 +121,13 @@ def main():
     host = recordings(n)
     audio = torch.from_numpy(host).to("cuda:0")
     n_samples = [n] * B
+    if PATH:
+        text = measure_path(net, dims, audio, n_samples)
+        print(text)
+        os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+        with open(OUT, "w") as f:
+            f.write(text + "\n")
+        return
     F = n // dims.hop_length + 1
     dur = np.full((B, TP), F // TP, np.int64)
     lengths = [TP] * B

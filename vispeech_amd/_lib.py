@@ -121,7 +121,13 @@ class VspProsodyParams(C.Structure):
                 ("silence_threshold", C.c_float), ("octave_cost", C.c_float)]
 
 
+class VspProsodyPathParams(C.Structure):
+    """``vsp_prosody_path_params``: octave-jump cost, voiced/unvoiced cost, candidates per frame (the unvoiced one included)."""
+    _fields_ = [("octave_jump_cost", C.c_float), ("voiced_unvoiced_cost", C.c_float), ("max_candidates", C.c_int32)]
+
+
 PROSODY_FS, PROSODY_NFFT = 44100, 1280                              # VSP_PROSODY_*
+PROSODY_MAX_CANDIDATES, PROSODY_SLOTS = 15, 16                       # VSP_PROSODY_MAX_CANDIDATES; floats of a frame in a table
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
 OUTPUT_RATES_MAX = 8
 
@@ -246,6 +252,12 @@ SIGNATURES = {
                                   _P, _I64]),
     "vsp_prosody_phonemes": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _P, _P, _P,
                                   _I64]),
+    "vsp_prosody_path_workspace_bytes": (_I64, [_I, _I64, _I, C.POINTER(VspProsodyParams), C.POINTER(VspProsodyPathParams)]),
+    "vsp_prosody_candidates": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), C.POINTER(VspProsodyParams), _I, _P, _P, _P,
+                                    _P, _P, _I64]),
+    "vsp_prosody_path": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I64), C.POINTER(VspProsodyPathParams), _P, _P, _I64]),
+    "vsp_prosody_contours_path": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), C.POINTER(VspProsodyParams),
+                                       C.POINTER(VspProsodyPathParams), _P, _P, _P, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

@@ -19,6 +19,9 @@
 //                     Bound: the vector FMA pipe, the LDS close behind -- two lag blocks share each broadcast quad, 3 LDS
 //                     reads (12 LDS cycles) per 32 FMAs (64 SIMD cycles), three quarters of the LDS's cycles with four
 //                     SIMDs issuing -- and nothing here is a matrix product an MFMA could take in fp32 faster.
+//                     A second instantiation (CAND) writes every frame's strongest candidates instead of its decision, for
+//   path_kernel       one wave per row (section 4n): the best path through the frames' candidates, Boersma's step 4 -- forward
+//                     with back-pointers through the workspace, backward in LDS.  No sinc interpolation of the peaks.
 //   phoneme_kernel    one wave per row: previous voiced frame by a forward wave64 max-scan, next voiced frame by a backward
 //                     min-scan, linear interpolation in between, then one lane per phoneme sums its OWN frames (no
 //                     prefix-sum differences: they would lose the digits the 1e-4 gate needs).
@@ -42,6 +45,7 @@ constexpr int PR_LAGS_PER_WAVE = 256;   // four consecutive lags per lane
 constexpr int PR_MAX_HOP = 2048;
 constexpr int PR_MAX_B = 65535;
 constexpr int64_t PR_MAX_SAMPLES = (int64_t)1 << 30;
+constexpr int PR_SLOTS = VSP_PROSODY_MAX_CANDIDATES + 1;   // floats of a frame in the candidate tables: 64 bytes
 
 struct Plan {
   int W;      // samples of an analysis frame: round(3 fs / floor), made even
@@ -125,6 +129,9 @@ struct ContourArgs {
   int W, W4, tmin, tmax, t0, LB, NA;
   int rbuf_off;                  // first float of the lag buffers in the block's LDS
   float fs, floor_hz, vt, st_scale, oc;     // st_scale = silence_threshold / (1 + voicing_threshold)
+  // the candidate instantiation only (appended: the fields above keep their places)
+  float* cand_f; float* cand_s;  // [B][F_max][PR_SLOTS]
+  int n_voiced;                  // voiced slots to fill: max_candidates - 1
 };
 
 // Four floats as one value: the hot loop works on whole vectors (shuffles of the two loaded quads, element-wise FMA), so
@@ -172,6 +179,10 @@ __device__ __forceinline__ float wave_max(float v) {
 // grid (ceil(F_max / PR_FPB), B), 64 PR_FPB threads.  Dynamic LDS (floats): [raw span: W + (PR_FPB - 1) hop, to a multiple
 // of 4] [PR_FPB frame buffers of NA] and PR_FPB lag buffers of 256 LB + 4, over the raw span or behind.  Control flow is uniform over the block: a wave
 // whose frame lies behind the row's frames computes on the zeros the staging selected and stores 0.
+// CAND: instead of the frame's decision, its PR_SLOTS (f, delta) pairs for the path finder (section 4n): slot 0 the
+// unvoiced candidate (0, U), slots 1 .. n_voiced the strongest maxima in descending (S, then ascending lag), the rest
+// (0, -inf); exact zeros in both tables behind the row's frames.
+template <bool CAND>
 __global__ void __launch_bounds__(64 * PR_FPB) contour_kernel(const ContourArgs g) {
   extern __shared__ __align__(16) float pr_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -182,7 +193,16 @@ __global__ void __launch_bounds__(64 * PR_FPB) contour_kernel(const ContourArgs 
   float* f0_out = g.f0 + (size_t)b * g.F_max;
   float* en_out = g.energy + (size_t)b * g.F_max;
   if (k0 >= F) {                                                   // (uniform) the whole block lies behind the row's frames
-    if (lane == 0 && k < g.F_max) { f0_out[k] = 0.f; en_out[k] = 0.f; }
+    if constexpr (CAND) {
+      if (lane < PR_SLOTS && k < g.F_max) {
+        const size_t e = ((size_t)b * g.F_max + k) * PR_SLOTS + lane;
+        g.cand_f[e] = 0.f;
+        g.cand_s[e] = 0.f;
+      }
+      if (lane == 0 && k < g.F_max) en_out[k] = 0.f;
+    } else {
+      if (lane == 0 && k < g.F_max) { f0_out[k] = 0.f; en_out[k] = 0.f; }
+    }
     return;
   }
   const int span = g.W + (PR_FPB - 1) * g.hop, span4 = (span + 3) & ~3;
@@ -266,32 +286,222 @@ __global__ void __launch_bounds__(64 * PR_FPB) contour_kernel(const ContourArgs 
   // lowest lag among equals
   float best_s = -INFINITY, best_f = 0.f;
   int best_t = 0x7fffffff;
-  for (int t = g.tmin + lane; t <= g.tmax; t += 64) {
-    const int i = t - g.t0;
-    const float rm = rbuf[i - 1], r0 = rbuf[i], rp = rbuf[i + 1];
-    if (r0 > rm && r0 >= rp) {
-      const float d = 0.5f * (rm - rp) / (rm - 2.f * r0 + rp);
-      const float R = r0 - 0.25f * (rm - rp) * d;
-      const float f = g.fs / ((float)t + d);
-      const float S = R + g.oc * log2f(f / g.floor_hz);
-      if (S > best_s) { best_s = S; best_f = f; best_t = t; }      // (t ascends within a lane: the first of equals stays)
+  if constexpr (!CAND) {
+    for (int t = g.tmin + lane; t <= g.tmax; t += 64) {
+      const int i = t - g.t0;
+      const float rm = rbuf[i - 1], r0 = rbuf[i], rp = rbuf[i + 1];
+      if (r0 > rm && r0 >= rp) {
+        const float d = 0.5f * (rm - rp) / (rm - 2.f * r0 + rp);
+        const float R = r0 - 0.25f * (rm - rp) * d;
+        const float f = g.fs / ((float)t + d);
+        const float S = R + g.oc * log2f(f / g.floor_hz);
+        if (S > best_s) { best_s = S; best_f = f; best_t = t; }    // (t ascends within a lane: the first of equals stays)
+      }
     }
-  }
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const float os = __shfl_xor(best_s, off), of = __shfl_xor(best_f, off);
-    const int ot = __shfl_xor(best_t, off);
-    if (os > best_s || (os == best_s && ot < best_t)) { best_s = os; best_f = of; best_t = ot; }
-  }
-  if (lane == 0 && k < g.F_max) {
-    const float gpk = g.stat[b].gpk;
-    float f0 = 0.f;
-    if (live && ra0 > 0.f && gpk > 0.f && best_t != 0x7fffffff) {
-      const float U = g.vt + fmaxf(0.f, 2.f - (lpk / gpk) / g.st_scale);
-      if (best_s > U) f0 = best_f;
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float os = __shfl_xor(best_s, off), of = __shfl_xor(best_f, off);
+      const int ot = __shfl_xor(best_t, off);
+      if (os > best_s || (os == best_s && ot < best_t)) { best_s = os; best_f = of; best_t = ot; }
     }
-    f0_out[k] = f0;
-    en_out[k] = live ? energy : 0.f;
+    if (lane == 0 && k < g.F_max) {
+      const float gpk = g.stat[b].gpk;
+      float f0 = 0.f;
+      if (live && ra0 > 0.f && gpk > 0.f && best_t != 0x7fffffff) {
+        const float U = g.vt + fmaxf(0.f, 2.f - (lpk / gpk) / g.st_scale);
+        if (best_s > U) f0 = best_f;
+      }
+      f0_out[k] = f0;
+      en_out[k] = live ? energy : 0.f;
+    }
+  } else {
+    // The strongest n_voiced maxima, in order.  Every lane evaluates its lags ONCE and keeps (S, f) in the wave's own frame
+    // buffer -- dead since the barrier above, and 2 (tmax - tmin + 1) < W floats always fit -- where it reads back only
+    // what it wrote itself.  Then one round of the wave arg-max per slot, each restricted to the maxima behind the last
+    // winner in (S descending, lag ascending): lane r keeps the winner of round r.
+    const float gpk = g.stat[b].gpk;
+    const bool alive = live && ra0 > 0.f && gpk > 0.f;             // (uniform over the wave)
+    const int nl = g.tmax - g.tmin + 1;
+    float* cs = abuf;
+    float* cf = abuf + nl;
+    float my_f = 0.f, my_s = -INFINITY;
+    if (alive) {
+      for (int t = g.tmin + lane; t <= g.tmax; t += 64) {
+        // (the expressions of the decision above, letter for letter: with both path costs 0 the two are held to the same bits)
+        const int i = t - g.t0;
+        const float rm = rbuf[i - 1], r0 = rbuf[i], rp = rbuf[i + 1];
+        float cand_f = 0.f, cand_S = -INFINITY;
+        if (r0 > rm && r0 >= rp) {
+          const float d = 0.5f * (rm - rp) / (rm - 2.f * r0 + rp);
+          const float R = r0 - 0.25f * (rm - rp) * d;
+          const float f = g.fs / ((float)t + d);
+          const float S = R + g.oc * log2f(f / g.floor_hz);
+          cand_f = f;
+          cand_S = S;
+        }
+        cs[t - g.tmin] = cand_S;
+        cf[t - g.tmin] = cand_f;
+      }
+      float last_s = INFINITY;
+      int last_t = -1;
+      for (int r = 1; r <= g.n_voiced; ++r) {
+        best_s = -INFINITY; best_f = 0.f; best_t = 0x7fffffff;
+        for (int t = g.tmin + lane; t <= g.tmax; t += 64) {
+          const float S = cs[t - g.tmin];
+          if ((S < last_s || (S == last_s && t > last_t)) && S > best_s) { best_s = S; best_f = cf[t - g.tmin]; best_t = t; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+          const float os = __shfl_xor(best_s, off), of = __shfl_xor(best_f, off);
+          const int ot = __shfl_xor(best_t, off);
+          if (os > best_s || (os == best_s && ot < best_t)) { best_s = os; best_f = of; best_t = ot; }
+        }
+        if (best_t == 0x7fffffff) break;                           // (uniform) no maximum is left
+        if (lane == r) { my_f = best_f; my_s = best_s; }
+        last_s = best_s;
+        last_t = best_t;
+      }
+    }
+    if (lane == 0) {
+      // (a dead frame -- r_a(0) = 0 or gpk = 0 -- has the unvoiced candidate alone, at the formula's value for lpk = 0)
+      my_s = g.vt + (alive ? fmaxf(0.f, 2.f - (lpk / gpk) / g.st_scale) : 2.f);
+    }
+    if (lane < PR_SLOTS && k < g.F_max) {
+      const size_t e = ((size_t)b * g.F_max + k) * PR_SLOTS + lane;
+      g.cand_f[e] = live ? my_f : 0.f;
+      g.cand_s[e] = live ? my_s : 0.f;
+    }
+    if (lane == 0 && k < g.F_max) en_out[k] = live ? energy : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ the path
+// Section 4n.  One wave per row, grid B.  Lane = candidate c (lane & 15) x group g (lane >> 4) of the four previous
+// candidates 4 g .. 4 g + 3: a lane takes the best of its four in registers, two cross-lane steps (xor 16, 32) finish
+// max_p (s(p) - T(p, c)), the lowest p among equals.  A chunk of PR_CH frames is staged in LDS as (log2 f, delta) -- the next
+// chunk's loads are in flight while this one runs -- so a voiced transition is |difference| times a constant, computed from
+// LDS alone and so ahead of the chain; serial per frame are the subtract, the max steps, the add, the max over the 16
+// candidates that normalises the frame (the best score is exactly 0.0f) and the four shuffles that hand every lane its
+// group's new scores.  Back-pointers: one byte per (frame, candidate), collected in LDS and flushed per chunk as 16 bytes
+// per lane.  Backward: the chunks come back the same way (every lane reads the 16 bytes it wrote) and the 64 frames are
+// walked in LDS, by every lane alike (broadcast reads), so the walk costs an LDS read per frame, not a trip to memory.
+// Frames at or behind frames[b] are neither read nor written, but for the zeros behind the row in f0.
+constexpr int PR_CH = 64;
+
+struct PathArgs {
+  const float* cand_f; const float* cand_s;   // [B][F_max][PR_SLOTS]
+  const int32_t* frames;                      // [B]
+  uint8_t* bp;                                // [B][F_max][PR_SLOTS] scratch: the best previous candidate
+  float* f0;                                  // [B][F_max]
+  int F_max;
+  float c_oct, c_vuv;                         // octave_jump_cost kappa, voiced_unvoiced_cost kappa
+};
+
+__device__ __forceinline__ float pr_log2_or_unvoiced(float f) { return f > 0.f ? log2f(f) : -INFINITY; }
+
+__global__ void __launch_bounds__(64) path_kernel(const PathArgs g) {
+  __shared__ __align__(16) float s_lf[PR_CH][PR_SLOTS];
+  __shared__ __align__(16) float s_d[PR_CH][PR_SLOTS];
+  __shared__ __align__(16) uint8_t s_bp[PR_CH][PR_SLOTS];
+  const int b = blockIdx.x, lane = threadIdx.x, c = lane & 15, grp = lane >> 4;
+  const int F = g.frames[b];
+  const size_t row = (size_t)b * g.F_max;
+  const float* __restrict__ cand_f = g.cand_f + row * PR_SLOTS;
+  const float* __restrict__ cand_s = g.cand_s + row * PR_SLOTS;
+  uint8_t* bp = g.bp + row * PR_SLOTS;
+  float* f0 = g.f0 + row;
+  for (int k = F + lane; k < g.F_max; k += 64) f0[k] = 0.f;
+
+  // a chunk is 1024 (f, delta) pairs: lane l holds the quads (64 i + l), frame 16 i + l / 4, slots 4 (l & 3) ..
+  pr_f4 nf[4], ns[4];
+  auto fetch = [&](int base) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int fr = base + 16 * i + (lane >> 2);
+      nf[i] = pr_f4{0.f, 0.f, 0.f, 0.f};
+      ns[i] = nf[i];
+      if (fr < F) {
+        const size_t e = (size_t)fr * PR_SLOTS + 4 * (lane & 3);
+        nf[i] = *reinterpret_cast<const pr_f4*>(cand_f + e);
+        ns[i] = *reinterpret_cast<const pr_f4*>(cand_s + e);
+      }
+    }
+  };
+  fetch(0);
+  float sp[4] = {0.f, 0.f, 0.f, 0.f};       // the previous frame's scores of this lane's group
+  pr_f4 lfq = {0.f, 0.f, 0.f, 0.f};         // ... and their log2 f
+  float s = 0.f;
+  for (int base = 0; base < F; base += PR_CH) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int fr = 16 * i + (lane >> 2), sl = 4 * (lane & 3);
+      *reinterpret_cast<pr_f4*>(&s_lf[fr][sl]) = pr_f4{pr_log2_or_unvoiced(nf[i].x), pr_log2_or_unvoiced(nf[i].y),
+                                                       pr_log2_or_unvoiced(nf[i].z), pr_log2_or_unvoiced(nf[i].w)};
+      *reinterpret_cast<pr_f4*>(&s_d[fr][sl]) = ns[i];
+    }
+    __syncthreads();
+    if (base + PR_CH < F) fetch(base + PR_CH);
+    const int n = min(PR_CH, F - base);
+    for (int i = 0; i < n; ++i) {
+      const float my_lf = s_lf[i][c], my_d = s_d[i][c];
+      float bv = 0.f;
+      int bi = 0;
+      if (base + i > 0) {                                          // (uniform)
+        const bool uc = my_lf == -INFINITY;
+        const float lq[4] = {lfq.x, lfq.y, lfq.z, lfq.w};
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool up = lq[j] == -INFINITY;
+          const float cost = (up && uc) ? 0.f : (up || uc) ? g.c_vuv : g.c_oct * fabsf(lq[j] - my_lf);
+          v[j] = sp[j] - cost;
+        }
+        bv = v[0];
+        bi = 4 * grp;
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+          if (v[j] > bv) { bv = v[j]; bi = 4 * grp + j; }
+#pragma unroll
+        for (int off = 16; off <= 32; off <<= 1) {
+          const float ov = __shfl_xor(bv, off);
+          const int oi = __shfl_xor(bi, off);
+          if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+      }
+      s = my_d + bv;
+      float m = s;
+#pragma unroll
+      for (int off = 1; off <= 8; off <<= 1) m = fmaxf(m, __shfl_xor(m, off));
+      if (m > -INFINITY) s -= m;                                   // (a frame of -inf alone stays -inf, not NaN)
+      if (grp == 0) s_bp[i][c] = (uint8_t)bi;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sp[j] = __shfl(s, 4 * grp + j);
+      lfq = *reinterpret_cast<const pr_f4*>(&s_lf[i][4 * grp]);
+    }
+    __syncthreads();
+    if (lane < n) *reinterpret_cast<uint4*>(bp + (size_t)(base + lane) * PR_SLOTS) = *reinterpret_cast<const uint4*>(s_bp[lane]);
+    __syncthreads();
+  }
+  // the end: the best candidate of the last frame, the lowest among equals
+  int cur = c;
+#pragma unroll
+  for (int off = 1; off <= 8; off <<= 1) {
+    const float os = __shfl_xor(s, off);
+    const int oc = __shfl_xor(cur, off);
+    if (os > s || (os == s && oc < cur)) { s = os; cur = oc; }
+  }
+  for (int base = ((F - 1) / PR_CH) * PR_CH; base >= 0; base -= PR_CH) {
+    const int n = min(PR_CH, F - base);
+    // (lane l wrote these 16 bytes itself: no other thread's store is read)
+    if (lane < n) *reinterpret_cast<uint4*>(s_bp[lane]) = *reinterpret_cast<const uint4*>(bp + (size_t)(base + lane) * PR_SLOTS);
+    __syncthreads();
+    int mine = 0;
+    for (int i = n - 1; i >= 0; --i) {
+      if (lane == i) mine = cur;
+      cur = s_bp[i][cur];
+    }
+    if (lane < n) f0[base + lane] = cand_f[(size_t)(base + lane) * PR_SLOTS + mine];
+    __syncthreads();
   }
 }
 
@@ -431,7 +641,68 @@ PhonemeWs phoneme_ws(int B, int64_t F_max, int Tp) {
   return w;
 }
 
-std::atomic<uint64_t> g_contour_lds_done{0};
+std::atomic<uint64_t> g_contour_lds_done{0}, g_candidate_lds_done{0};
+
+// ---- the path finder's host side
+const vsp_prosody_path_params kPathDefaults = {0.35f, 0.14f, VSP_PROSODY_MAX_CANDIDATES};
+
+// 0: ok; else the refused field (1 the costs, 2 max_candidates)
+int check_path(const vsp_prosody_path_params* path, vsp_prosody_path_params& pp) {
+  pp = path ? *path : kPathDefaults;
+  if (!(pp.octave_jump_cost >= 0.f && pp.octave_jump_cost < 1e6f) || !(pp.voiced_unvoiced_cost >= 0.f && pp.voiced_unvoiced_cost < 1e6f))
+    return 1;
+  if (pp.max_candidates < 2 || pp.max_candidates > VSP_PROSODY_MAX_CANDIDATES) return 2;
+  return 0;
+}
+
+int refuse_path(vsp_ctx* ctx, const char* who, int bad) {
+  if (bad == 1) return ctx->fail(VSP_ERR_ARG, "%s: the octave-jump cost and the voiced/unvoiced cost must be at least 0", who);
+  return ctx->fail(VSP_ERR_ARG, "%s: max_candidates must lie in [2, %d] (the unvoiced candidate and at least one voiced one)", who,
+                   VSP_PROSODY_MAX_CANDIDATES);
+}
+
+struct PathWs { size_t frames, bp, end; };
+PathWs path_ws(int B, int64_t F_max) {
+  PathWs w;
+  size_t cur = 0;
+  w.frames = cur; cur += align256((size_t)B * sizeof(int32_t));
+  w.bp = cur; cur += align256((size_t)B * F_max * PR_SLOTS);
+  w.end = cur;
+  return w;
+}
+
+// vsp_prosody_contours_path: [the contour call's] [cand_f] [cand_s] [the path's]
+struct ContourPathWs { size_t cand_f, cand_s, path, end; };
+ContourPathWs contour_path_ws(int B, int64_t F_max, const Plan& pl) {
+  ContourPathWs w;
+  size_t cur = contour_ws(B, pl).end;
+  w.cand_f = cur; cur += align256((size_t)B * F_max * PR_SLOTS * sizeof(float));
+  w.cand_s = cur; cur += align256((size_t)B * F_max * PR_SLOTS * sizeof(float));
+  w.path = cur; cur += path_ws(B, F_max).end;
+  w.end = cur;
+  return w;
+}
+
+// The launch of the path kernel behind the upload of the rows' frame counts (already checked).
+int launch_path(vsp_ctx* ctx, const char* who, hipStream_t s, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
+                const std::vector<int32_t>& frames, const vsp_prosody_path_params& pp, float* f0_frames, char* ws) {
+  const PathWs lay = path_ws(B, F_max);
+  hipError_t e = hipMemcpyAsync(ws + lay.frames, frames.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (frames): %s", who, hipGetErrorString(e));
+  // kappa = 0.01 fs / hop, Praat's time-step correction, written so that it is exactly 1 where fs = 100 hop
+  const double kappa = (double)PR_FS / (100.0 * (double)hop);
+  PathArgs a;
+  a.cand_f = cand_f; a.cand_s = cand_s;
+  a.frames = reinterpret_cast<const int32_t*>(ws + lay.frames);
+  a.bp = reinterpret_cast<uint8_t*>(ws + lay.bp);
+  a.f0 = f0_frames; a.F_max = F_max;
+  a.c_oct = (float)((double)pp.octave_jump_cost * kappa);
+  a.c_vuv = (float)((double)pp.voiced_unvoiced_cost * kappa);
+  hipLaunchKernelGGL(path_kernel, dim3(B), dim3(64), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "path_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}
 
 }  // namespace
 
@@ -448,36 +719,43 @@ int64_t vsp_prosody_workspace_bytes(int B, int64_t L_max, int hop, int Tp, const
   return (int64_t)std::max(contour_ws(B, pl).end, phoneme_ws(B, F_max, std::max(Tp, 1)).end);
 }
 
-int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
-                         const int64_t* n_samples_host, const vsp_prosody_params* params, float* f0_frames,
-                         float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
-  if (!ctx) return VSP_ERR_ARG;
+// The contour call of all three entry points; `who` names the one in every message.  n_voiced = 0: the per-frame decision
+// into f0_frames (vsp_prosody_contours).  n_voiced >= 1: the candidate tables instead -- the caller's (cand_f, cand_s), or,
+// where both are NULL, the workspace's, for the path that follows (vsp_prosody_contours_path: f0_frames is the path's
+// output and is not touched here; the workspace must then hold that call's whole layout).
+static int contours_impl(const char* who, vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio,
+                         int64_t audio_stride, const int64_t* n_samples_host, const vsp_prosody_params* params, int n_voiced,
+                         float* f0_frames, float* cand_f, float* cand_s, float* energy_frames, int64_t* frames, void* workspace,
+                         int64_t workspace_bytes) {
+  const bool own_tables = n_voiced > 0 && !cand_f && !cand_s;
   Plan pl;
   if (const int bad = make_plan(params, pl)) {
-    if (bad == 1) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: the pitch floor must be at least 40 Hz (the analysis window must fit in LDS)");
-    if (bad == 2) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: the pitch ceiling must be above the floor and at most fs / 4 = %d Hz", PR_FS / 4);
-    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: thresholds out of range (the silence threshold must be positive)");
+    if (bad == 1) return ctx->fail(VSP_ERR_ARG, "%s: the pitch floor must be at least 40 Hz (the analysis window must fit in LDS)", who);
+    if (bad == 2) return ctx->fail(VSP_ERR_ARG, "%s: the pitch ceiling must be above the floor and at most fs / 4 = %d Hz", who, PR_FS / 4);
+    return ctx->fail(VSP_ERR_ARG, "%s: thresholds out of range (the silence threshold must be positive)", who);
   }
-  if (B < 1 || B > PR_MAX_B || !n_samples_host) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: 1 <= B <= %d rows and their lengths", PR_MAX_B);
+  if (B < 1 || B > PR_MAX_B || !n_samples_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their lengths", who, PR_MAX_B);
   const int F_max = vsp_prosody_frames(L_max, hop);
   if (F_max < 0)
-    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: 1 <= hop <= %d and %d <= L_max <= 2^30 samples", PR_MAX_HOP, PR_MIN_SAMPLES);
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= hop <= %d and %d <= L_max <= 2^30 samples", who, PR_MAX_HOP, PR_MIN_SAMPLES);
   for (int b = 0; b < B; ++b)
     if (n_samples_host[b] < PR_MIN_SAMPLES || n_samples_host[b] > L_max)
-      return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: row %d has %lld samples: a row needs %d (n_fft / 2 + 1, for the reflection) "
-                       "to L_max = %lld", b, (long long)n_samples_host[b], PR_MIN_SAMPLES, (long long)L_max);
-  if (!audio || !f0_frames || !energy_frames || !frames || audio_stride < L_max)
-    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_contours: null pointer, or audio_stride < L_max");
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d has %lld samples: a row needs %d (n_fft / 2 + 1, for the reflection) "
+                       "to L_max = %lld", who, b, (long long)n_samples_host[b], PR_MIN_SAMPLES, (long long)L_max);
+  if (!audio || (!f0_frames && (n_voiced == 0 || own_tables)) || (n_voiced > 0 && !own_tables && (!cand_f || !cand_s)) ||
+      !energy_frames || !frames || audio_stride < L_max)
+    return ctx->fail(VSP_ERR_ARG, "%s: null pointer, or audio_stride < L_max", who);
   const ContourWs lay = contour_ws(B, pl);
-  if (!workspace || workspace_bytes < (int64_t)lay.end)
-    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_contours: the workspace needs %lld bytes", (long long)lay.end);
+  const size_t need = own_tables ? contour_path_ws(B, F_max, pl).end : lay.end;
+  if (!workspace || workspace_bytes < (int64_t)need)
+    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
   const int span4 = (pl.W + (PR_FPB - 1) * hop + 3) & ~3;
   // the lag buffers share the raw span's floats where they fit (48 KiB per block at the defaults: three blocks per CU)
   const int rbuf_floats = PR_FPB * (PR_LAGS_PER_WAVE * pl.LB + 4);
   const bool rbuf_over_span = rbuf_floats <= span4;
   const int rbuf_off = rbuf_over_span ? 0 : span4 + PR_FPB * pl.NA;
   const size_t lds = ((size_t)span4 + (size_t)PR_FPB * pl.NA + (rbuf_over_span ? 0 : (size_t)rbuf_floats)) * sizeof(float);
-  if (lds > 160 * 1024) return ctx->fail(VSP_ERR_UNSUPPORTED, "vsp_prosody_contours: %zu bytes of LDS", lds);
+  if (lds > 160 * 1024) return ctx->fail(VSP_ERR_UNSUPPORTED, "%s: %zu bytes of LDS", who, lds);
 
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
@@ -492,7 +770,7 @@ int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int h
     if (t.W != pl.W || t.t0 != pl.t0 || t.LB != pl.LB || t.tmin != pl.tmin || t.tmax != pl.tmax) build_tables(pl, t);
     e = hipMemcpyAsync(ws + lay.tables, t.host.data(), t.host.size() * sizeof(float), hipMemcpyHostToDevice, s);
   }
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "vsp_prosody_contours (tables): %s", hipGetErrorString(e));
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (tables): %s", who, hipGetErrorString(e));
   const int64_t* n_dev = reinterpret_cast<const int64_t*>(ws + lay.n_samples);
   RowStat* stat = reinterpret_cast<RowStat*>(ws + lay.stat);
   const float* tab = reinterpret_cast<const float*>(ws + lay.tables);
@@ -500,9 +778,10 @@ int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int h
   e = hipGetLastError();
   if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "row_peak_kernel: %s", hipGetErrorString(e));
   if (lds > 64 * 1024) {
-    // (the size follows the caller's floor and hop; the attribute is set ONCE per device, so it is the cap checked above,
-    // the largest request the kernel can get -- a later call with a lower floor must not find a smaller one)
-    e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel), 160 * 1024, g_contour_lds_done);
+    // (the size follows the caller's floor and hop; the attribute is set ONCE per device and instantiation, so it is the cap
+    // checked above, the largest request the kernel can get -- a later call with a lower floor must not find a smaller one)
+    e = n_voiced > 0 ? vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel<true>), 160 * 1024, g_candidate_lds_done)
+                     : vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel<false>), 160 * 1024, g_contour_lds_done);
     if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel (LDS): %s", hipGetErrorString(e));
   }
   ContourArgs a;
@@ -513,10 +792,91 @@ int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int h
   a.W = pl.W; a.W4 = pl.W4; a.tmin = pl.tmin; a.tmax = pl.tmax; a.t0 = pl.t0; a.LB = pl.LB; a.NA = pl.NA; a.rbuf_off = rbuf_off;
   a.fs = (float)PR_FS; a.floor_hz = pl.p.floor_hz; a.vt = pl.p.voicing_threshold;
   a.st_scale = pl.p.silence_threshold / (1.f + pl.p.voicing_threshold); a.oc = pl.p.octave_cost;
-  hipLaunchKernelGGL(contour_kernel, dim3((F_max + PR_FPB - 1) / PR_FPB, B), dim3(64 * PR_FPB), lds, s, a);
+  a.cand_f = cand_f; a.cand_s = cand_s; a.n_voiced = n_voiced;
+  if (own_tables) {
+    const ContourPathWs cp = contour_path_ws(B, F_max, pl);
+    a.cand_f = reinterpret_cast<float*>(ws + cp.cand_f);
+    a.cand_s = reinterpret_cast<float*>(ws + cp.cand_s);
+  }
+  const dim3 grid((F_max + PR_FPB - 1) / PR_FPB, B), block(64 * PR_FPB);
+  if (n_voiced > 0) hipLaunchKernelGGL(contour_kernel<true>, grid, block, lds, s, a);
+  else hipLaunchKernelGGL(contour_kernel<false>, grid, block, lds, s, a);
   e = hipGetLastError();
   if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel: %s", hipGetErrorString(e));
   return VSP_OK;
+}
+
+int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                         const int64_t* n_samples_host, const vsp_prosody_params* params, float* f0_frames,
+                         float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  return contours_impl("vsp_prosody_contours", ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params, 0, f0_frames,
+                       nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes);
+}
+
+int64_t vsp_prosody_path_workspace_bytes(int B, int64_t L_max, int hop, const vsp_prosody_params* params,
+                                         const vsp_prosody_path_params* path) {
+  Plan pl;
+  vsp_prosody_path_params pp;
+  if (B < 1 || B > PR_MAX_B || make_plan(params, pl) || check_path(path, pp)) return VSP_ERR_ARG;
+  const int F_max = vsp_prosody_frames(L_max, hop);
+  if (F_max < 0) return VSP_ERR_ARG;
+  return (int64_t)contour_path_ws(B, F_max, pl).end;      // (the candidate call and the path alone each need a part of it)
+}
+
+int vsp_prosody_candidates(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                           const int64_t* n_samples_host, const vsp_prosody_params* params, int max_candidates, float* cand_f,
+                           float* cand_s, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (max_candidates < 2 || max_candidates > VSP_PROSODY_MAX_CANDIDATES) return refuse_path(ctx, "vsp_prosody_candidates", 2);
+  if (!cand_f || !cand_s) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_candidates: null pointer, or audio_stride < L_max");
+  return contours_impl("vsp_prosody_candidates", ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params,
+                       max_candidates - 1, nullptr, cand_f, cand_s, energy_frames, frames, workspace, workspace_bytes);
+}
+
+int vsp_prosody_path(vsp_ctx* ctx, void* stream, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
+                     const int64_t* frames_host, const vsp_prosody_path_params* path, float* f0_frames, void* workspace,
+                     int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  vsp_prosody_path_params pp;
+  if (const int bad = check_path(path, pp)) return refuse_path(ctx, "vsp_prosody_path", bad);
+  if (B < 1 || B > PR_MAX_B || F_max < 1 || hop < 1 || hop > PR_MAX_HOP || !frames_host)
+    return ctx->fail(VSP_ERR_ARG, "vsp_prosody_path: 1 <= B <= %d rows, F_max >= 1, 1 <= hop <= %d, and the rows' frame counts", PR_MAX_B,
+                     PR_MAX_HOP);
+  std::vector<int32_t> fr(B);
+  for (int b = 0; b < B; ++b) {
+    if (frames_host[b] < 1 || frames_host[b] > F_max)
+      return ctx->fail(VSP_ERR_ARG, "vsp_prosody_path: row %d: 1 <= frames <= F_max = %d", b, F_max);
+    fr[b] = (int32_t)frames_host[b];
+  }
+  if (!cand_f || !cand_s || !f0_frames) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_path: null pointer");
+  const PathWs lay = path_ws(B, F_max);
+  if (!workspace || workspace_bytes < (int64_t)lay.end)
+    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_path: the workspace needs %lld bytes", (long long)lay.end);
+  return launch_path(ctx, "vsp_prosody_path", (hipStream_t)stream, B, F_max, hop, cand_f, cand_s, fr, pp, f0_frames,
+                     static_cast<char*>(workspace));
+}
+
+int vsp_prosody_contours_path(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                              const int64_t* n_samples_host, const vsp_prosody_params* params, const vsp_prosody_path_params* path,
+                              float* f0_frames, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_prosody_contours_path";
+  vsp_prosody_path_params pp;
+  if (const int bad = check_path(path, pp)) return refuse_path(ctx, who, bad);
+  // (everything else is refused in there, before its first launch: the rows, the pointers, the whole layout's size)
+  const int rc = contours_impl(who, ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params, pp.max_candidates - 1,
+                               f0_frames, nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes);
+  if (rc != VSP_OK) return rc;
+  Plan pl;
+  make_plan(params, pl);
+  const int F_max = vsp_prosody_frames(L_max, hop);
+  const ContourPathWs cp = contour_path_ws(B, F_max, pl);
+  std::vector<int32_t> fr(B);
+  for (int b = 0; b < B; ++b) fr[b] = (int32_t)(n_samples_host[b] / hop) + 1;
+  char* ws = static_cast<char*>(workspace);
+  return launch_path(ctx, who, (hipStream_t)stream, B, F_max, hop, reinterpret_cast<const float*>(ws + cp.cand_f),
+                     reinterpret_cast<const float*>(ws + cp.cand_s), fr, pp, f0_frames, ws + cp.path);
 }
 
 int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const float* f0_frames, const float* energy_frames,

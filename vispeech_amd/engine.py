@@ -1258,12 +1258,126 @@ class Engine:
             raise ValueError(f"prosody: a recording of {int(n_samples)} samples: it needs {_lib.PROSODY_NFFT // 2 + 1} to 2^30")
         return F
 
-    def prosody_contours(self, audio, n_samples, params=None, hop_length: Optional[int] = None):
+    @staticmethod
+    def _prosody_path(path):
+        """None (no path finder), True (Praat's costs: octave jump 0.35, voiced/unvoiced 0.14, 15 candidates), a
+        ``VspProsodyPathParams``, or a mapping / sequence of (octave_jump_cost, voiced_unvoiced_cost, max_candidates) --
+        missing keys take the defaults -- as a ``VspProsodyPathParams`` or None."""
+        if path is None or path is False or isinstance(path, _lib.VspProsodyPathParams):
+            return path or None
+        names = [f[0] for f in _lib.VspProsodyPathParams._fields_]
+        vals = dict(zip(names, (0.35, 0.14, _lib.PROSODY_MAX_CANDIDATES)))
+        if path is True:
+            pass
+        elif isinstance(path, Mapping):
+            unknown = set(path) - set(names)
+            if unknown:
+                raise ValueError(f"prosody path: unknown {sorted(unknown)}; the fields are {names}")
+            vals.update(path)
+        else:
+            path = list(path)
+            if len(path) != len(names):
+                raise ValueError(f"prosody path: {len(names)} values {names}")
+            vals = dict(zip(names, path))
+        oj, vu, n = float(vals[names[0]]), float(vals[names[1]]), vals[names[2]]
+        if not (oj >= 0.0 and vu >= 0.0):
+            raise ValueError("prosody path: the octave-jump cost and the voiced/unvoiced cost must be at least 0")
+        if int(n) != n or not 2 <= int(n) <= _lib.PROSODY_MAX_CANDIDATES:
+            raise ValueError(f"prosody path: max_candidates must be a whole number in [2, {_lib.PROSODY_MAX_CANDIDATES}]")
+        return _lib.VspProsodyPathParams(oj, vu, int(n))
+
+    def _prosody_rows(self, audio, n_samples, hop_length):
+        """The checks every contour call makes of its rows: ``(audio, B, stride, n_host, hop, L_max, frames_host)``."""
+        a = _dev_f32(audio, self.device)
+        if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+            raise ValueError("audio must be [B, L] (rows padded to a common length, contiguous)")
+        B, stride = a.shape[0], (a.stride(0) if a.shape[0] > 1 else a.shape[1])
+        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        if len(n_host) != B or B == 0:
+            raise ValueError(f"n_samples must have {B} entries (at least one row)")
+        hop = self._hop(hop_length)
+        frames_host = []
+        for b, n in enumerate(n_host):
+            if n > a.shape[1]:
+                raise ValueError(f"row {b}: n_samples {n} > audio.shape[1] = {a.shape[1]}")
+            F = int(self.lib.vsp_prosody_frames(n, hop))
+            if F < 0:
+                raise ValueError(f"row {b}: a recording of {n} samples: prosody needs {_lib.PROSODY_NFFT // 2 + 1} to 2^30")
+            frames_host.append(F)
+        return a, B, int(stride), n_host, hop, max(n_host), frames_host
+
+    def prosody_candidates(self, audio, n_samples, params=None, max_candidates: int = _lib.PROSODY_MAX_CANDIDATES,
+                           hop_length: Optional[int] = None):
+        """``vsp_prosody_candidates``: the rows of ``prosody_contours``; instead of a decision, every frame's candidates for
+        the path finder.  Returns ``(cand_f, cand_s, energy_frames, frames, frames_host)``: the two
+        tables ``[B, F_max, 16]`` float32 -- slot 0 the unvoiced candidate (0, U), slots 1 .. ``max_candidates - 1`` the
+        strongest voiced candidates (f, S) in descending S, unused slots (0, -inf), exact zeros behind a row's frames."""
+        a, B, stride, n_host, hop, L_max, frames_host = self._prosody_rows(audio, n_samples, hop_length)
+        if int(max_candidates) != max_candidates or not 2 <= int(max_candidates) <= _lib.PROSODY_MAX_CANDIDATES:
+            raise ValueError(f"prosody path: max_candidates must be a whole number in [2, {_lib.PROSODY_MAX_CANDIDATES}]")
+        F_max = max(frames_host)
+        p = self._prosody_params(params)
+        cand_f, cand_s = self._f(B, F_max, _lib.PROSODY_SLOTS), self._f(B, F_max, _lib.PROSODY_SLOTS)
+        en = self._f(B, F_max)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        ws = self._workspace("prosody", self.lib.vsp_prosody_workspace_bytes(B, L_max, hop, 1, p))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_prosody_candidates(self.ctx, self._stream(), B, L_max, hop, _ptr(a), stride, (C.c_int64 * B)(*n_host),
+                                                 p, int(max_candidates), _ptr(cand_f), _ptr(cand_s), _ptr(en), _ptr(frames),
+                                                 _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_prosody_candidates")
+        return cand_f, cand_s, en, frames, frames_host
+
+    def prosody_path(self, cand_f, cand_s, frames_host, path=True, hop_length: Optional[int] = None):
+        """``vsp_prosody_path``: the best path through candidate tables ``[B, F_max, 16]`` (``prosody_candidates``', or any:
+        f = 0 marks an unvoiced candidate, delta is finite or -inf).  ``frames_host`` [B]: host ints, frames at or behind
+        them are not read.  Returns ``f0_frames`` [B, F_max]: the chosen candidate's f in every bit, exact 0 behind a row's
+        frames.  ``path``: ``_prosody_path`` (None is refused here: there is nothing to run without one)."""
+        cf, cs = _dev_f32(cand_f, self.device), _dev_f32(cand_s, self.device)
+        if cf.dim() != 3 or cf.shape[2] != _lib.PROSODY_SLOTS or cf.shape != cs.shape or not cf.is_contiguous() or not cs.is_contiguous():
+            raise ValueError(f"cand_f and cand_s must be contiguous [B, F_max, {_lib.PROSODY_SLOTS}] tensors of one shape")
+        pp = self._prosody_path(path)
+        if pp is None:
+            raise ValueError("prosody_path needs path parameters (True for the defaults)")
+        B, F_max = int(cf.shape[0]), int(cf.shape[1])
+        fh = [int(x) for x in frames_host]
+        if len(fh) != B or B == 0 or F_max == 0:
+            raise ValueError(f"frames_host must have {B} entries (at least one row of at least one frame)")
+        for b, F in enumerate(fh):
+            if not 1 <= F <= F_max:
+                raise ValueError(f"row {b}: {F} frames: 1 <= frames <= F_max = {F_max}")
+        hop = self._hop(hop_length)
+        f0 = self._f(B, F_max)
+        # (the size is monotone in the length: F_max frames cover any row of the batch)
+        ws = self._workspace("prosody", self.lib.vsp_prosody_path_workspace_bytes(B, max((F_max - 1) * hop, 641), hop, None, pp))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_prosody_path(self.ctx, self._stream(), B, F_max, hop, _ptr(cf), _ptr(cs), (C.c_int64 * B)(*fh), pp,
+                                           _ptr(f0), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_prosody_path")
+        return f0
+
+    def prosody_contours(self, audio, n_samples, params=None, hop_length: Optional[int] = None, path=None):
         """``vsp_prosody_contours``: recordings of different lengths in one padded ``audio`` [B, L] at the model's rate; row
         b is ``audio[b, :n_samples[b]]`` (what lies behind is never read).  Returns ``(f0_frames, energy_frames, frames,
         frames_host)``: two ``[B, F_max]`` float32 tensors -- per-frame F0 in Hz (0: unvoiced) and energy, row b's first
         ``frames[b] = n_samples[b] // hop + 1`` columns, exact zeros behind --, the frame counts on the device and as host
-        ints (host arithmetic: nothing is read back).  ``params``: ``_prosody_params``."""
+        ints (host arithmetic: nothing is read back).  ``params``: ``_prosody_params``.  ``path``: None -- every frame decides
+        for itself --, or ``_prosody_path`` (True: Praat's costs): ``vsp_prosody_contours_path``, F0 from the best path through
+        every frame's candidates."""
+        pp = self._prosody_path(path)
+        if pp is not None:
+            a, B, stride, n_host, hop, L_max, frames_host = self._prosody_rows(audio, n_samples, hop_length)
+            F_max = max(frames_host)
+            p = self._prosody_params(params)
+            f0, en = self._f(B, F_max), self._f(B, F_max)
+            frames = torch.empty(B, dtype=torch.int64, device=self.device)
+            ws = self._workspace("prosody", self.lib.vsp_prosody_path_workspace_bytes(B, L_max, hop, p, pp))
+            with torch.cuda.device(self.device):
+                rc = self.lib.vsp_prosody_contours_path(self.ctx, self._stream(), B, L_max, hop, _ptr(a), stride,
+                                                        (C.c_int64 * B)(*n_host), p, pp, _ptr(f0), _ptr(en), _ptr(frames), _ptr(ws),
+                                                        ws.numel())
+            _lib.check(rc, self.ctx, "vsp_prosody_contours_path")
+            return f0, en, frames, frames_host
         a = _dev_f32(audio, self.device)
         if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
             raise ValueError("audio must be [B, L] (rows padded to a common length, contiguous)")

@@ -190,7 +190,7 @@ class SynthesizerTrn:
 
     @torch.no_grad()
     def prosody_from_audio(self, audio, n_samples, durations, phonemes_lengths, *, sample_rate: Optional[int] = None,
-                           encoding=None, params=None):
+                           encoding=None, params=None, path=None):
         """Per-phoneme F0 and energy of recordings -- what the reference's data preparation (f0energy.py) writes into a
         filelist row -- for a batch of recordings of different lengths: ``audio`` [B, L] at the model's rate, row b the
         recording ``audio[b, :n_samples[b]]`` (what lies behind is never read), ``durations`` [B, Tp] the frames of each of
@@ -200,6 +200,9 @@ class SynthesizerTrn:
         speak a text with the melody and loudness of the recording.  F0 is Boersma's autocorrelation method as DESIGN.md
         section 4m states it (``params``: floor_hz, ceiling_hz, voicing_threshold, silence_threshold, octave_cost; None: 80,
         750, 0.6, 0.03, 0.01) -- NOT bit-compatible with parselmouth.  Works without the ``enc_q.*`` tensors.
+        ``path``: None -- every frame decides for itself --, True or (octave_jump_cost, voiced_unvoiced_cost,
+        max_candidates) / a dict of them (True: 0.35, 0.14, 15) -- F0 from the best path through every frame's candidates
+        (section 4n), which neither jumps an octave for a frame nor drops a weak frame of a voiced stretch.
         ``sample_rate`` / ``encoding``: as in ``convert_audio`` -- ``audio`` is raw at that rate, ``n_samples`` counts input
         samples, and the batch goes through the input stage (``Engine.input_batch``) first."""
         eng = self._engine
@@ -208,7 +211,10 @@ class SynthesizerTrn:
             if rate not in eng.input_rates:
                 eng.configure_input(rate)
             audio, n_samples = eng.input_batch(audio, n_samples, rate, 0 if encoding is None else encoding)
-        f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n_samples, params)
+        if path is None:
+            f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n_samples, params)
+        else:
+            f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n_samples, params, path=path)
         return eng.prosody_phonemes(f0_frames, energy_frames, frames_host, durations, phonemes_lengths)
 
     def __call__(self, *a, **k):

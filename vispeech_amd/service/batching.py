@@ -139,11 +139,12 @@ def _table_controls(batch, rows_ctl):
     return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
 
 
-def _prosody_controls(eng, batch, reqs, model_rate):
+def _prosody_controls(eng, batch, reqs, model_rate, path=None):
     """The requests that name a recording (``submit(prosody_audio=...)``): their raw recordings through the input stage,
     then ONE ``Engine.prosody_contours`` and ONE ``Engine.prosody_phonemes`` call for all of them, with the durations their
     rows brought.  The results go into the batch's ``f0`` / ``energy`` control rows ON THE DEVICE (the two arrays become
-    device tensors; nothing is read back) and the rows are marked ``given``.  A batch without such a request is not touched."""
+    device tensors; nothing is read back) and the rows are marked ``given``.  A batch without such a request is not touched.
+    ``path``: the service's ``prosody_path`` -- None: the contour call as it always was; else its ``path`` keyword (still ONE call)."""
     idx = [i for i, r in enumerate(reqs) if r.prosody is not None]
     if not idx:
         return batch
@@ -155,7 +156,8 @@ def _prosody_controls(eng, batch, reqs, model_rate):
     audio = torch.zeros((len(idx), max(n)), dtype=torch.float32, device=eng.device)
     for k, j in enumerate(jobs):
         audio[k, : n[k]] = torch.as_tensor(j.audio)
-    f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n)
+    f0_frames, energy_frames, _, frames_host = (eng.prosody_contours(audio, n) if path is None
+                                                else eng.prosody_contours(audio, n, path=path))
     dur = np.asarray(batch["duration"])
     B, Tp = dur.shape
     f0, energy = eng.prosody_phonemes(f0_frames, energy_frames, frames_host, dur[idx], np.asarray(batch["lengths"])[idx])
@@ -176,13 +178,13 @@ def _prosody_controls(eng, batch, reqs, model_rate):
     return batch
 
 
-def _collated(collate, reqs, noise_scale: float, eng=None, model_rate=None):
+def _collated(collate, reqs, noise_scale: float, eng=None, model_rate=None, prosody_path=None):
     """``(batch, (duration, f0, energy), keywords)`` of text requests: ``collate``, the controls of the requests that name a
     recording (``_prosody_controls``) and, where the requests need one, the per-row table -- the ``row_controls`` keyword is
     passed only then: a group without one makes the calls it always made."""
     batch = collate([r.row for r in reqs])
     if eng is not None:
-        batch = _prosody_controls(eng, batch, reqs, model_rate)
+        batch = _prosody_controls(eng, batch, reqs, model_rate, prosody_path)
     table = _row_table(batch, [r.scales for r in reqs], noise_scale)
     if table is None:
         return batch, (batch.get("duration"), batch.get("f0"), batch.get("energy")), {}
@@ -195,12 +197,12 @@ def _as_tensor(a):
     return None if a is None else a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
 
 
-def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None):
+def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None, prosody_path=None):
     """The text requests of one batch or admitted group to their latent: ``collate``, the per-row table where the requests
     need one, then ONE isolated ``encode`` / ``frame_lengths_host`` / ``decode(max_len=0)``.  Returns per request
     ``(z row [inter, T], g row, frames)``; a request of no frames gives ``(None, None, 0)``."""
     prosody = any(getattr(r, "prosody", None) is not None for r in reqs)
-    batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate) if prosody else ()))
+    batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate, prosody_path) if prosody else ()))
     t = _as_tensor
     enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
                      isolated=True, **kw)
@@ -261,14 +263,14 @@ def _through_input_stage(eng, jobs, model_rate=None) -> None:
             j.audio = audio[k, : n_out[k]]
 
 
-def latents(eng, collate, requests, noise_scale: float, model_rate=None):
+def latents(eng, collate, requests, noise_scale: float, model_rate=None, prosody_path=None):
     """Per request ``(z row [inter, T], g row, frames)``, in request order: the text rows of the group through
     ``_text_latents``, then its conversions through ``_convert_latents``."""
     text = [i for i, r in enumerate(requests) if not r.is_conversion]
     conv = [i for i, r in enumerate(requests) if r.is_conversion]
     done = []
     if text:
-        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale, model_rate))
+        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale, model_rate, prosody_path))
     if conv:
         done += zip(conv, _convert_latents(eng, [requests[i] for i in conv], model_rate))
     out = [None] * len(requests)
@@ -291,10 +293,13 @@ class BatchingSynthesisService:
     collected batch may hold both kinds: the text rows go to their latent (``encode`` / ``frame_lengths_host`` /
     ``decode(max_len=0)``), the conversions through one ``convert_latent``, and ONE ``generator_ragged`` call produces every
     waveform.  A batch without a conversion makes exactly the ``net.infer`` call above.
-    ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays)."""
+    ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays).
+    ``prosody_path``: how every ``prosody_audio`` request of this service gets its F0 -- None: each frame decides for itself;
+    True or (octave_jump_cost, voiced_unvoiced_cost, max_candidates) / a dict of them: the path finder
+    (``Engine.prosody_contours(path=...)``).  A batch still makes ONE contour call."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
-                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100):
+                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -302,6 +307,10 @@ class BatchingSynthesisService:
         self.noise_scale = float(noise_scale)
         self.output_rate = None if output_rate is None else int(output_rate)
         self.sampling_rate = int(sampling_rate)
+        if prosody_path is not None and prosody_path is not False:
+            from ..engine import Engine
+            prosody_path = Engine._prosody_path(prosody_path)         # (refused here, not in the worker)
+        self.prosody_path = prosody_path or None
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -408,7 +417,7 @@ class BatchingSynthesisService:
         if any(r.is_conversion for r in reqs):
             return self._synthesize_mixed(reqs)
         hop = net.dims.total_upsample
-        prosody = (net._engine, self.sampling_rate) if any(r.prosody is not None for r in reqs) else ()
+        prosody = (net._engine, self.sampling_rate, self.prosody_path) if any(r.prosody is not None for r in reqs) else ()
         batch, ctl, kw = _collated(self._collate, reqs, self.noise_scale, *prosody)
         t = lambda a: None if a is None else _as_tensor(a).to(net.device)
         o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
@@ -443,7 +452,7 @@ class BatchingSynthesisService:
         ``generator_ragged`` call, then the output stage as in ``_synthesize``."""
         import torch
         net, eng = self.net, self.net._engine
-        lat = latents(eng, self._collate, reqs, self.noise_scale, self.sampling_rate)
+        lat = latents(eng, self._collate, reqs, self.noise_scale, self.sampling_rate, self.prosody_path)
         live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
         pcms = [np.zeros(0, dtype="<i2") for _ in reqs]
         if not live:
