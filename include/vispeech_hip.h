@@ -1013,6 +1013,64 @@ int vsp_prosody_contours_path(vsp_ctx* ctx, void* stream, int B, int64_t L_max, 
                               const int64_t* n_samples_host, const vsp_prosody_params* params, const vsp_prosody_path_params* path,
                               float* f0_frames, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes);
 
+/* ---- align: durations from a recording (round 20, ABI 7, additive) ---- */
+/* Monotonic alignment of a recording to a text, the one control of vsp_encode this library could not produce from audio
+ * (the reference takes it from the Montreal Forced Aligner).  Both sides meet in the prior's space: from the text,
+ * vsp_encode + vsp_decode(max_len = 0) give m_p, logs_p [B][C][K_max] and cum_dur; from the recording,
+ * vsp_convert_latent(noise_scale = 0) gives z_p [B][C][F_max].  The specification is this project's own, restated in fp64 in
+ * tests/align_ref.py.  Row b has F_b frames (frames_host) and K_b states (states_host), a state being a frame of the template.
+ *   scores     S[b][j][k] = sum_c -0.5 (x[b][c][j] - m[b][c][k])^2 exp(-2 logs[b][c][k]) - sum_c logs[b][c][k] for j < F_b, k < K_b
+ *              (the C/2 log 2 pi constant is dropped), computed in the direct form -- the difference, then its square -- in
+ *              fp32, c ascending whatever the batch.  S [B][F_max][K_max] float32: exact 0 outside a row's F_b x K_b; nothing
+ *              outside a row's extent of x, m or logs is read.
+ *   path       k(0) = 0, k(F - 1) = K - 1, k(j) - k(j - 1) in {0 .. max_advance}; the path maximises sum_j S[j][k(j)]
+ *              - stay_cost #(advance 0) - skip_cost #(advance 2).  Q_0(0) = S[0][0], Q_0(k > 0) = -inf, Q_j(k) = S[j][k] +
+ *              max(Q_{j-1}(k) - stay_cost, Q_{j-1}(k - 1), Q_{j-1}(k - 2) - skip_cost), the LOWEST advance among equals.  Q is
+ *              accumulated in fp64 (the fp32 scores and costs widened exactly: subtractions, an exact max, one add), so the
+ *              path is the fp64 restatement's on the same scores bit for bit, ties included.  Scores inside a row's extent
+ *              must be finite.  states [B][F_max] int32: k(j), exact 0 behind a row's frames; scores behind a row's extent
+ *              are not read.  A row needs K_b <= max_advance (F_b - 1) + 1 and K_b <= vsp_align_max_states().
+ *   durations  cum_dur_host [B][Tp] int32 (HOST memory): the row's inclusive cumulative template frames as vsp_encode writes
+ *              them (read back by the caller).  d_i = #{ j : cum_{i-1} <= k(j) < cum_i } -- the difference of two lower
+ *              bounds over the monotone states --, 0 for a phoneme of no template frames and behind lengths_host[b];
+ *              sum_i d_i = F_b where cum_dur ends at K_b.  durations [B][Tp] int32 (device).
+ * params NULL: max_advance 2, both costs 0.  Refused with VSP_ERR_ARG on the host, before any launch, naming the row: an
+ * infeasible row, max_advance outside {1, 2}, a negative cost, K_b above the state limit, F_b < 1 or > F_max, K_b < 1 or >
+ * K_max, and (vsp_align) cum_dur[lengths - 1] != K_b; in vsp_align_durations and vsp_align also a row of no phonemes
+ * (1 <= lengths_host[b] <= Tp) and a cum_dur that decreases.  frames_host, states_host, lengths_host: HOST arrays [B].
+ * Each call runs on `stream` behind an upload of its rows (2 B int32; with durations also the phoneme map, B Tp int32),
+ * allocates nothing and does not synchronise the stream.  The uploads read pageable host memory, as the prosody calls' do:
+ * the host is held for the copy into the runtime's staging buffer, which is noticeable only for a large B Tp, and the
+ * calls cannot be captured into a graph. */
+typedef struct vsp_align_params {
+  int32_t max_advance;
+  float stay_cost, skip_cost;
+} vsp_align_params;
+/* The most states a row of vsp_align_path / vsp_align may have (4096). */
+int vsp_align_max_states(void);
+/* Workspaces (VSP_ERR_ARG as a negative size); each is monotone in every argument.  vsp_align_workspace_bytes covers
+ * vsp_align and vsp_align_durations. */
+int64_t vsp_align_scores_workspace_bytes(int B, int F_max, int K_max);
+int64_t vsp_align_path_workspace_bytes(int B, int F_max, int K_max);
+int64_t vsp_align_workspace_bytes(int B, int F_max, int K_max, int Tp);
+/* The score matrix alone: x [B][C][F_max], m and logs [B][C][K_max] (device, channels first as the library returns
+ * them).  One launch. */
+int vsp_align_scores(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, const float* x, const float* m, const float* logs,
+                     const int64_t* frames_host, const int64_t* states_host, float* scores, void* workspace, int64_t workspace_bytes);
+/* The path alone, a stand-alone operator on any score matrix [B][F_max][K_max] (device).  One launch, one block per row;
+ * back-pointers (2 bits a cell) go through the workspace. */
+int vsp_align_path(vsp_ctx* ctx, void* stream, int B, int F_max, int K_max, const float* scores, const int64_t* frames_host,
+                   const int64_t* states_host, const vsp_align_params* params, int32_t* states, void* workspace,
+                   int64_t workspace_bytes);
+/* Per-phoneme durations of states [B][F_max] (device).  One launch, one thread per phoneme. */
+int vsp_align_durations(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const int32_t* states, const int64_t* frames_host,
+                        const int32_t* cum_dur_host, const int64_t* lengths_host, int32_t* durations, void* workspace,
+                        int64_t workspace_bytes);
+/* All three: scores, path, durations; the score matrix and the back-pointers live in the workspace.  Three launches. */
+int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, int Tp, const float* x, const float* m, const float* logs,
+              const int64_t* frames_host, const int64_t* states_host, const int32_t* cum_dur_host, const int64_t* lengths_host,
+              const vsp_align_params* params, int32_t* states, int32_t* durations, void* workspace, int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

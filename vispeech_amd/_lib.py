@@ -126,6 +126,11 @@ class VspProsodyPathParams(C.Structure):
     _fields_ = [("octave_jump_cost", C.c_float), ("voiced_unvoiced_cost", C.c_float), ("max_candidates", C.c_int32)]
 
 
+class VspAlignParams(C.Structure):
+    """``vsp_align_params``: the largest advance of a frame (1 or 2), the cost of staying, the cost of skipping a state."""
+    _fields_ = [("max_advance", C.c_int32), ("stay_cost", C.c_float), ("skip_cost", C.c_float)]
+
+
 PROSODY_FS, PROSODY_NFFT = 44100, 1280                              # VSP_PROSODY_*
 PROSODY_MAX_CANDIDATES, PROSODY_SLOTS = 15, 16                       # VSP_PROSODY_MAX_CANDIDATES; floats of a frame in a table
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
@@ -258,6 +263,15 @@ SIGNATURES = {
     "vsp_prosody_path": (_I, [_P, _P, _I, _I, _I, _P, _P, C.POINTER(_I64), C.POINTER(VspProsodyPathParams), _P, _P, _I64]),
     "vsp_prosody_contours_path": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), C.POINTER(VspProsodyParams),
                                        C.POINTER(VspProsodyPathParams), _P, _P, _P, _P, _I64]),
+    "vsp_align_max_states": (_I, []),
+    "vsp_align_scores_workspace_bytes": (_I64, [_I, _I, _I]),
+    "vsp_align_path_workspace_bytes": (_I64, [_I, _I, _I]),
+    "vsp_align_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "vsp_align_scores": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64), _P, _P, _I64]),
+    "vsp_align_path": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(VspAlignParams), _P, _P, _I64]),
+    "vsp_align_durations": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I64), C.POINTER(C.c_int32), C.POINTER(_I64), _P, _P, _I64]),
+    "vsp_align": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int32),
+                       C.POINTER(_I64), C.POINTER(VspAlignParams), _P, _P, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

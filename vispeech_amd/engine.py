@@ -1440,6 +1440,190 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_prosody_phonemes")
         return f0, en
 
+    # ------------------------------------------------------------------ align: durations from a recording (section 4o)
+    @staticmethod
+    def _align_params(params):
+        """None or True (max_advance 2, both costs 0), a ``VspAlignParams``, or a mapping / sequence of (max_advance,
+        stay_cost, skip_cost) -- missing keys take the defaults -- as a ``VspAlignParams``."""
+        if isinstance(params, _lib.VspAlignParams):
+            return params
+        names = [f[0] for f in _lib.VspAlignParams._fields_]
+        vals = dict(zip(names, (2, 0.0, 0.0)))
+        if params is None or params is True:
+            pass
+        elif isinstance(params, Mapping):
+            unknown = set(params) - set(names)
+            if unknown:
+                raise ValueError(f"align: unknown {sorted(unknown)}; the fields are {names}")
+            vals.update(params)
+        else:
+            params = list(params)
+            if len(params) != len(names):
+                raise ValueError(f"align: {len(names)} values {names}")
+            vals = dict(zip(names, params))
+        A, stay, skip = vals[names[0]], float(vals[names[1]]), float(vals[names[2]])
+        if A not in (1, 2):
+            raise ValueError("align: max_advance must be 1 or 2")
+        if not (stay >= 0.0 and skip >= 0.0):
+            raise ValueError("align: the stay cost and the skip cost must be at least 0")
+        return _lib.VspAlignParams(int(A), stay, skip)
+
+    @property
+    def align_max_states(self) -> int:
+        return int(self.lib.vsp_align_max_states())
+
+    @staticmethod
+    def _align_rows(B, F_max, K_max, frames_host, states_host, pp=None, limit=None):
+        """The rows of an align call as host ints, refused here as the library refuses them (a ``ValueError`` naming the row)."""
+        fh, kh = [int(v) for v in frames_host], [int(v) for v in states_host]
+        if len(fh) != B or len(kh) != B or B == 0:
+            raise ValueError(f"frames_host and states_host must have {B} entries (at least one row)")
+        for b, (F, K) in enumerate(zip(fh, kh)):
+            if not 1 <= F <= F_max:
+                raise ValueError(f"align: row {b} has {F} frames: 1 <= frames <= F_max = {F_max}")
+            if not 1 <= K <= K_max:
+                raise ValueError(f"align: row {b} has {K} states: 1 <= states <= K_max = {K_max}")
+            if pp is not None:
+                if K > limit:
+                    raise ValueError(f"align: row {b} has {K} states: the limit is {limit}")
+                if K > pp.max_advance * (F - 1) + 1:
+                    raise ValueError(f"align: row {b} is infeasible: {F} frames cannot reach {K} states advancing at most "
+                                     f"{pp.max_advance} a frame (the recording is too short for its text)")
+        return fh, kh
+
+    def _align_inputs(self, x, m, logs):
+        x, m, logs = (_dev_f32(a, self.device).contiguous() for a in (x, m, logs))
+        if x.dim() != 3 or m.dim() != 3 or m.shape != logs.shape or x.shape[:2] != m.shape[:2]:
+            raise ValueError("align: x [B, C, F_max], m and logs [B, C, K_max]")
+        return x, m, logs
+
+    @staticmethod
+    def _align_cum(cum_dur, lengths, B):
+        """``cum_dur`` [B, Tp] and ``lengths`` [B] on the HOST (a device tensor is copied back)."""
+        c = cum_dur.detach().cpu().numpy() if torch.is_tensor(cum_dur) else np.asarray(cum_dur)
+        c = np.ascontiguousarray(c.reshape(B, -1), dtype=np.int32)
+        ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(ln) != B or c.shape[1] < 1:
+            raise ValueError(f"lengths must have {B} entries, cum_dur at least one column")
+        return c, ln
+
+    def align_scores(self, x, m, logs, frames_host, states_host):
+        """``vsp_align_scores``: ``S`` [B, F_max, K_max] float32, row b's ``frames_host[b] x states_host[b]`` corner the
+        Gaussian log-likelihood of every frame of ``x`` [B, C, F_max] under every state of ``m``, ``logs`` [B, C, K_max]
+        (the direct form), exact 0 outside; nothing outside a row's extent is read."""
+        x, m, logs = self._align_inputs(x, m, logs)
+        B, Cc, F_max = x.shape
+        K_max = m.shape[2]
+        fh, kh = self._align_rows(B, F_max, K_max, frames_host, states_host)
+        S = self._f(B, F_max, K_max)
+        ws = self._workspace("align", self.lib.vsp_align_scores_workspace_bytes(B, F_max, K_max))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_align_scores(self.ctx, self._stream(), B, Cc, F_max, K_max, _ptr(x), _ptr(m), _ptr(logs),
+                                           (C.c_int64 * B)(*fh), (C.c_int64 * B)(*kh), _ptr(S), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_align_scores")
+        return S
+
+    def align_path(self, scores, frames_host, states_host, params=None):
+        """``vsp_align_path``: the best monotone path through score tables ``[B, F_max, K_max]`` (``align_scores``', or
+        any finite ones): ``states`` [B, F_max] int32, frame j's state, from 0 to ``states_host[b] - 1`` advancing at most
+        ``max_advance`` a frame; exact 0 behind a row's frames.  fp64 accumulation: the fp64 restatement's path on the same
+        scores bit for bit.  ``params``: ``_align_params``."""
+        S = _dev_f32(scores, self.device)
+        if S.dim() != 3 or not S.is_contiguous():
+            raise ValueError("scores must be a contiguous [B, F_max, K_max] tensor")
+        pp = self._align_params(params)
+        B, F_max, K_max = S.shape
+        fh, kh = self._align_rows(B, F_max, K_max, frames_host, states_host, pp, self.align_max_states)
+        states = torch.empty((B, F_max), dtype=torch.int32, device=self.device)
+        ws = self._workspace("align", self.lib.vsp_align_path_workspace_bytes(B, F_max, K_max))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_align_path(self.ctx, self._stream(), B, F_max, K_max, _ptr(S), (C.c_int64 * B)(*fh),
+                                         (C.c_int64 * B)(*kh), pp, _ptr(states), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_align_path")
+        return states
+
+    def align_durations(self, states, frames_host, cum_dur, lengths):
+        """``vsp_align_durations``: ``states`` [B, F_max] int32 to per-phoneme frame counts ``[B, Tp]`` int32 (device):
+        phoneme i of row b gets the frames whose state lies in ``[cum_dur[b, i - 1], cum_dur[b, i])`` -- ``cum_dur`` as
+        ``encode`` returns it, read on the HOST --, 0 behind ``lengths[b]``."""
+        st = torch.as_tensor(states).to(device=self.device, dtype=torch.int32).contiguous()
+        if st.dim() != 2:
+            raise ValueError("states must be [B, F_max]")
+        B, F_max = st.shape
+        cum, ln = self._align_cum(cum_dur, lengths, B)
+        Tp = cum.shape[1]
+        fh = [int(v) for v in frames_host]
+        for b, F in enumerate(fh):
+            if not 1 <= F <= F_max:
+                raise ValueError(f"align: row {b} has {F} frames: 1 <= frames <= F_max = {F_max}")
+        dur = torch.empty((B, Tp), dtype=torch.int32, device=self.device)
+        ws = self._workspace("align", self.lib.vsp_align_workspace_bytes(B, F_max, 1, Tp))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_align_durations(self.ctx, self._stream(), B, F_max, Tp, _ptr(st), (C.c_int64 * B)(*fh),
+                                              cum.ctypes.data_as(C.POINTER(C.c_int32)), (C.c_int64 * B)(*ln), _ptr(dur), _ptr(ws),
+                                              ws.numel())
+        _lib.check(rc, self.ctx, "vsp_align_durations")
+        return dur
+
+    def align(self, x, m, logs, frames_host, states_host, cum_dur, lengths, params=None):
+        """``vsp_align``: scores, path and durations in one call (three launches; the score matrix stays in the workspace).
+        ``x`` [B, C, F_max]: the recordings' latent (``convert_latent(noise_scale=0)['z_p']``); ``m``, ``logs`` [B, C, K_max]
+        and ``cum_dur`` [B, Tp]: the text's frame-level prior and phoneme map (``decode(max_len=0)``, ``encode``).  Returns
+        ``(states [B, F_max], durations [B, Tp])`` int32 on the device; ``sum(durations[b]) == frames_host[b]``.  A row whose
+        recording is too short for its template is a ``ValueError`` naming it."""
+        x, m, logs = self._align_inputs(x, m, logs)
+        pp = self._align_params(params)
+        B, Cc, F_max = x.shape
+        K_max = m.shape[2]
+        fh, kh = self._align_rows(B, F_max, K_max, frames_host, states_host, pp, self.align_max_states)
+        cum, ln = self._align_cum(cum_dur, lengths, B)
+        Tp = cum.shape[1]
+        for b in range(B):
+            if not 1 <= ln[b] <= Tp or int(cum[b, ln[b] - 1]) != kh[b]:
+                raise ValueError(f"align: row {b}: cum_dur must end at the row's {kh[b]} states (1 <= length <= Tp = {Tp})")
+        states = torch.empty((B, F_max), dtype=torch.int32, device=self.device)
+        dur = torch.empty((B, Tp), dtype=torch.int32, device=self.device)
+        ws = self._workspace("align", self.lib.vsp_align_workspace_bytes(B, F_max, K_max, Tp))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_align(self.ctx, self._stream(), B, Cc, F_max, K_max, Tp, _ptr(x), _ptr(m), _ptr(logs),
+                                    (C.c_int64 * B)(*fh), (C.c_int64 * B)(*kh), cum.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    (C.c_int64 * B)(*ln), pp, _ptr(states), _ptr(dur), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_align")
+        return states, dur
+
+    def align_audio(self, phonemes, lengths, sid, audio, n_samples, sid_audio=None, params=None, fit_length: bool = True):
+        """What ``SynthesizerTrn.align_audio`` runs on recordings at the model's rate: the text through an isolated
+        ``encode`` (twice with ``fit_length``: the second time with row b's ``duration_scale = T_b / K_b``) and
+        ``decode(max_len=0)``, the recordings through ``convert_latent(noise_scale=0)``, then ``align``.  Returns
+        ``durations`` [B, Tp] int64 on the device."""
+        from types import SimpleNamespace
+        pp = self._align_params(params)
+        n_host = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        frames = [self.convert_frames(n) for n in n_host]
+        for b, T in enumerate(frames):
+            if T < 1:
+                raise ValueError(f"align_audio: row {b}: a recording of {n_host[b]} samples is too short for one frame")
+        B = len(frames)
+        enc = self.encode(phonemes, lengths, sid, isolated=True)
+        states, tf = self.frame_lengths_host(enc["frame_lengths"])
+        kw = {}
+        if fit_length:
+            one, flat = np.ones(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+            scale = np.array([frames[b] / states[b] if states[b] > 0 else 1.0 for b in range(B)], dtype=np.float32)
+            kw["row_controls"] = SimpleNamespace(duration_scale=scale, pitch_scale=one, energy_scale=one, noise_scale=flat,
+                                                 given=np.zeros((B, 3), dtype=bool))
+            enc = self.encode(phonemes, lengths, sid, isolated=True, **kw)
+            states, tf = self.frame_lengths_host(enc["frame_lengths"])
+        for b, K in enumerate(states):
+            if K < 1:
+                raise ValueError(f"align_audio: row {b}: its text has no template frames")
+        self._align_rows(B, max(frames), tf, frames, states, pp, self.align_max_states)     # (refused before the device works)
+        dec = self.decode(enc, tf, None, 0.0, max_len=0, isolated=True, **kw)
+        sid_a = sid if sid_audio is None else sid_audio
+        lat = self.convert_latent(audio, n_host, sid_a, sid_a, noise_scale=0.0)
+        _, dur = self.align(lat["z_p"], dec["m_p"], dec["logs_p"], lat["frames_host"], states, enc["cum_dur"], lengths, pp)
+        return dur.to(torch.int64)
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

@@ -217,6 +217,39 @@ class SynthesizerTrn:
             f0_frames, energy_frames, _, frames_host = eng.prosody_contours(audio, n_samples, params, path=path)
         return eng.prosody_phonemes(f0_frames, energy_frames, frames_host, durations, phonemes_lengths)
 
+    @torch.no_grad()
+    def align_audio(self, phonemes, phonemes_lengths, sid, audio, n_samples, *, sid_audio=None,
+                    sample_rate: Optional[int] = None, encoding=None, params=None, fit_length: bool = True):
+        """The frames each phoneme of a text occupies in a recording of it -- the ``durations`` that ``prosody_from_audio``
+        and ``infer(duration_control=)`` take, which the reference gets from an external forced aligner -- by monotonic
+        alignment in the model's own prior space.  ``phonemes`` [B, Tp], ``phonemes_lengths`` [B],
+        ``sid`` [B]: the texts; ``audio`` [B, L], ``n_samples`` [B]: their recordings as in ``convert_audio``
+        (``sample_rate`` / ``encoding``: raw recordings through the input stage first); ``sid_audio`` [B]: who speaks the
+        recordings (None: ``sid``).  The text is encoded in isolated mode with predicted durations, pitch and energy and
+        decoded to its frame-level prior (``m_p``, ``logs_p``: a state per template frame, ``cum_dur`` maps states to
+        phonemes); the recording goes through the posterior encoder and the forward flow without noise (``z_p``); every
+        recording frame is scored under every state and the best left-to-right path is cut at the phoneme boundaries.
+        ``fit_length``: encode a second time with each row's ``duration_scale = T_b / K_b`` (its recording's frames over its
+        predicted frames), so that the template is about as long as the recording and the advance limit rarely binds.
+        ``params``: (max_advance, stay_cost, skip_cost) or a dict of them (None: 2, 0, 0).  Returns ``durations`` [B, Tp]
+        int64 on the device, ``sum(durations[b]) = vsp_convert_frames(n_samples[b]) <= n_samples[b] // hop + 1``, 0 behind a
+        row's phonemes.  A recording too short for its text (fewer than (K_b - 1) / max_advance + 1 frames) is a
+        ``ValueError`` naming the row.  Needs the ``enc_q.*`` tensors.  Alignment quality depends on the checkpoint."""
+        eng = self._engine
+        if not eng.ready:
+            raise RuntimeError("weights not loaded: call load_state_dict first")
+        assert self.n_speakers > 0, "n_speakers have to be larger than 0."
+        if not eng.has_voice_conversion:
+            raise RuntimeError("align_audio needs the enc_q.* tensors: the loaded state_dict had none")
+        pp = eng._align_params(params)
+        if sample_rate is not None or encoding is not None:
+            rate = int(self.dims.sampling_rate if sample_rate is None else sample_rate)
+            if rate not in eng.input_rates:
+                eng.configure_input(rate)
+            audio, n_samples = eng.input_batch(audio, n_samples, rate, 0 if encoding is None else encoding)
+        return eng.align_audio(phonemes, phonemes_lengths, sid, audio, n_samples, sid_audio=sid_audio, params=pp,
+                               fit_length=fit_length)
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

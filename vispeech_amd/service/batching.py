@@ -71,8 +71,9 @@ class _Recording:
     model's rate in ``audio``, or -- ``fmt`` = ``(rate, encoding)`` -- ``raw`` until the worker has run it through the input
     stage (the attributes ``_through_input_stage`` reads and writes)."""
 
-    def __init__(self, audio, fmt=None):
+    def __init__(self, audio, fmt=None, sid=None):
         self.fmt, self.raw = fmt, None
+        self.sid = None if sid is None else int(sid)      # who speaks the recording (alignment only); None: the row's speaker
         if fmt is None:
             a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32))
         else:
@@ -139,12 +140,45 @@ def _table_controls(batch, rows_ctl):
     return tuple(batch.get(k) if rows_ctl.given[:, i].any() else None for i, k in enumerate(("duration", "f0", "energy")))
 
 
-def _prosody_controls(eng, batch, reqs, model_rate, path=None):
+def _aligned_durations(eng, batch, reqs, idx, audio, n, align):
+    """The prosody requests whose rows brought no durations (a service with ``prosody_align``): ONE ``Engine.align_audio``
+    call for all of them -- the row's text against its recording, spoken by the row's speaker unless the request named
+    ``prosody_sid`` -- and the result in the batch's ``duration`` rows, marked ``given``.  A batch whose prosody rows all
+    brought their durations is not touched."""
+    need = [k for k, i in enumerate(idx) if getattr(reqs[i].row, "durations", None) is None]
+    if not need:
+        return batch
+    if align is None:
+        raise ValueError("prosody_audio: the row must bring its durations (the phonemes' frames in the recording)")
+    B, Tp = np.asarray(batch["phonemes"]).shape
+    given = batch.get("given")
+    if given is None:                        # (a collate callable that returns none: every row has what its batch has,
+        have = [batch.get(k) is not None for k in ("duration", "f0", "energy")]      # but for the rows aligned here)
+        given = np.tile(np.array([have], dtype=bool), (B, 1))
+        given[[idx[k] for k in need], 0] = False
+    rows = [idx[k] for k in need]
+    sid = np.asarray(batch["sid"])[rows]
+    sid_audio = [int(sid[q]) if reqs[i].prosody.sid is None else reqs[i].prosody.sid for q, i in enumerate(rows)]
+    d = eng.align_audio(_as_tensor(np.asarray(batch["phonemes"])[rows]), _as_tensor(np.asarray(batch["lengths"])[rows]),
+                        _as_tensor(sid), audio[need], [n[k] for k in need], sid_audio=sid_audio, params=align)
+    batch = dict(batch)
+    dur = (np.zeros((B, Tp), dtype=np.float32) if batch.get("duration") is None
+           else np.array(batch["duration"], dtype=np.float32))
+    dur[rows] = d.cpu().numpy()
+    given = np.array(given, dtype=bool)
+    given[rows, 0] = True
+    batch["duration"], batch["given"] = dur, given
+    return batch
+
+
+def _prosody_controls(eng, batch, reqs, model_rate, path=None, align=None):
     """The requests that name a recording (``submit(prosody_audio=...)``): their raw recordings through the input stage,
     then ONE ``Engine.prosody_contours`` and ONE ``Engine.prosody_phonemes`` call for all of them, with the durations their
     rows brought.  The results go into the batch's ``f0`` / ``energy`` control rows ON THE DEVICE (the two arrays become
     device tensors; nothing is read back) and the rows are marked ``given``.  A batch without such a request is not touched.
-    ``path``: the service's ``prosody_path`` -- None: the contour call as it always was; else its ``path`` keyword (still ONE call)."""
+    ``path``: the service's ``prosody_path`` -- None: the contour call as it always was; else its ``path`` keyword (still ONE call).
+    ``align``: the service's ``prosody_align`` -- rows that brought no durations are aligned to their recordings first
+    (``_aligned_durations``); rows that brought them make the calls they always made."""
     idx = [i for i, r in enumerate(reqs) if r.prosody is not None]
     if not idx:
         return batch
@@ -156,6 +190,7 @@ def _prosody_controls(eng, batch, reqs, model_rate, path=None):
     audio = torch.zeros((len(idx), max(n)), dtype=torch.float32, device=eng.device)
     for k, j in enumerate(jobs):
         audio[k, : n[k]] = torch.as_tensor(j.audio)
+    batch = _aligned_durations(eng, batch, reqs, idx, audio, n, align)
     f0_frames, energy_frames, _, frames_host = (eng.prosody_contours(audio, n) if path is None
                                                 else eng.prosody_contours(audio, n, path=path))
     dur = np.asarray(batch["duration"])
@@ -178,13 +213,13 @@ def _prosody_controls(eng, batch, reqs, model_rate, path=None):
     return batch
 
 
-def _collated(collate, reqs, noise_scale: float, eng=None, model_rate=None, prosody_path=None):
+def _collated(collate, reqs, noise_scale: float, eng=None, model_rate=None, prosody_path=None, prosody_align=None):
     """``(batch, (duration, f0, energy), keywords)`` of text requests: ``collate``, the controls of the requests that name a
     recording (``_prosody_controls``) and, where the requests need one, the per-row table -- the ``row_controls`` keyword is
     passed only then: a group without one makes the calls it always made."""
     batch = collate([r.row for r in reqs])
     if eng is not None:
-        batch = _prosody_controls(eng, batch, reqs, model_rate, prosody_path)
+        batch = _prosody_controls(eng, batch, reqs, model_rate, prosody_path, prosody_align)
     table = _row_table(batch, [r.scales for r in reqs], noise_scale)
     if table is None:
         return batch, (batch.get("duration"), batch.get("f0"), batch.get("energy")), {}
@@ -197,12 +232,12 @@ def _as_tensor(a):
     return None if a is None else a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
 
 
-def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None, prosody_path=None):
+def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None, prosody_path=None, prosody_align=None):
     """The text requests of one batch or admitted group to their latent: ``collate``, the per-row table where the requests
     need one, then ONE isolated ``encode`` / ``frame_lengths_host`` / ``decode(max_len=0)``.  Returns per request
     ``(z row [inter, T], g row, frames)``; a request of no frames gives ``(None, None, 0)``."""
     prosody = any(getattr(r, "prosody", None) is not None for r in reqs)
-    batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate, prosody_path) if prosody else ()))
+    batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate, prosody_path, prosody_align) if prosody else ()))
     t = _as_tensor
     enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
                      isolated=True, **kw)
@@ -263,14 +298,14 @@ def _through_input_stage(eng, jobs, model_rate=None) -> None:
             j.audio = audio[k, : n_out[k]]
 
 
-def latents(eng, collate, requests, noise_scale: float, model_rate=None, prosody_path=None):
+def latents(eng, collate, requests, noise_scale: float, model_rate=None, prosody_path=None, prosody_align=None):
     """Per request ``(z row [inter, T], g row, frames)``, in request order: the text rows of the group through
     ``_text_latents``, then its conversions through ``_convert_latents``."""
     text = [i for i, r in enumerate(requests) if not r.is_conversion]
     conv = [i for i, r in enumerate(requests) if r.is_conversion]
     done = []
     if text:
-        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale, model_rate, prosody_path))
+        done += zip(text, _text_latents(eng, collate, [requests[i] for i in text], noise_scale, model_rate, prosody_path, prosody_align))
     if conv:
         done += zip(conv, _convert_latents(eng, [requests[i] for i in conv], model_rate))
     out = [None] * len(requests)
@@ -296,10 +331,14 @@ class BatchingSynthesisService:
     ``table`` / ``spk2id``: what ``collate_rows`` needs to pad the rows (or ``collate``: any callable rows -> batch arrays).
     ``prosody_path``: how every ``prosody_audio`` request of this service gets its F0 -- None: each frame decides for itself;
     True or (octave_jump_cost, voiced_unvoiced_cost, max_candidates) / a dict of them: the path finder
-    (``Engine.prosody_contours(path=...)``).  A batch still makes ONE contour call."""
+    (``Engine.prosody_contours(path=...)``).  A batch still makes ONE contour call.
+    ``prosody_align``: None -- a ``prosody_audio`` request must bring its durations, as always; True or (max_advance, stay_cost,
+    skip_cost) / a dict of them (True: 2, 0, 0): a request whose row brings none gets them from its recording first
+    (``Engine.align_audio``; needs the ``enc_q.*`` tensors), ONE call per batch."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
-                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None):
+                 spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None,
+                 prosody_align=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -311,6 +350,10 @@ class BatchingSynthesisService:
             from ..engine import Engine
             prosody_path = Engine._prosody_path(prosody_path)         # (refused here, not in the worker)
         self.prosody_path = prosody_path or None
+        if prosody_align is not None and prosody_align is not False:
+            from ..engine import Engine
+            prosody_align = Engine._align_params(prosody_align)      # (refused here, not in the worker)
+        self.prosody_align = prosody_align or None
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -321,7 +364,7 @@ class BatchingSynthesisService:
 
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
                noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, prosody_audio=None,
-               prosody_sample_rate: Optional[int] = None, prosody_encoding=None) -> "concurrent.futures.Future":
+               prosody_sample_rate: Optional[int] = None, prosody_encoding=None, prosody_sid=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
         The future's result is the request's PCM16 samples (numpy int16, valid part only).
@@ -335,19 +378,30 @@ class BatchingSynthesisService:
         claim more frames than the recording has); the worker computes the recording's per-phoneme F0 and energy
         (``SynthesizerTrn.prosody_from_audio``: ONE contour call and ONE phoneme call for all such requests of a batch) and
         they take the place of whatever f0 / energy the row carries.  The request is then what
-        ``infer(isolated=True, duration_control=.., pitch_control=f0, energy_control=energy)`` returns for it alone."""
+        ``infer(isolated=True, duration_control=.., pitch_control=f0, energy_control=energy)`` returns for it alone.
+        On a service with ``prosody_align`` a row without durations is accepted: the worker aligns its text to the recording
+        first (``prosody_sid``: the recording's speaker where it is not the row's)."""
         prosody = None
+        if prosody_sid is not None:
+            n_spk = getattr(self.net, "n_speakers", None)
+            if int(prosody_sid) != prosody_sid or int(prosody_sid) < 0 or (n_spk is not None and int(prosody_sid) >= int(n_spk)):
+                raise ValueError(f"prosody_sid must be a speaker number in [0, {n_spk if n_spk is not None else 'n_speakers'})")
         if prosody_audio is not None:
-            prosody = _Recording(prosody_audio, _input_format(prosody_sample_rate, prosody_encoding, self.sampling_rate))
+            prosody = _Recording(prosody_audio, _input_format(prosody_sample_rate, prosody_encoding, self.sampling_rate), prosody_sid)
             durations = getattr(row, "durations", None)
-            if durations is None:
+            if durations is None and self.prosody_align is None:
                 raise ValueError("prosody_audio: the row must bring its durations (the phonemes' frames in the recording)")
             n, hop = prosody.samples(self.sampling_rate), int(self.net.dims.total_upsample)
-            if n < 641 or int(np.sum(durations)) > n // hop + 1:
+            if durations is None:
+                if n < 641:
+                    raise ValueError(f"prosody_audio: {n} samples at the model's rate: it needs 641")
+            elif n < 641 or int(np.sum(durations)) > n // hop + 1:
                 raise ValueError(f"prosody_audio: {n} samples at the model's rate ({n // hop + 1} frames): it needs 641, and "
                                  f"the row's durations claim {int(np.sum(durations))} frames")
         elif prosody_sample_rate is not None or prosody_encoding is not None:
             raise ValueError("prosody_sample_rate / prosody_encoding describe prosody_audio: pass it")
+        elif prosody_sid is not None:
+            raise ValueError("prosody_sid names the speaker of prosody_audio: pass it")
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
                                       _output_format(output_rate, output_encoding), prosody))
 
@@ -417,7 +471,7 @@ class BatchingSynthesisService:
         if any(r.is_conversion for r in reqs):
             return self._synthesize_mixed(reqs)
         hop = net.dims.total_upsample
-        prosody = (net._engine, self.sampling_rate, self.prosody_path) if any(r.prosody is not None for r in reqs) else ()
+        prosody = (net._engine, self.sampling_rate, self.prosody_path, self.prosody_align) if any(r.prosody is not None for r in reqs) else ()
         batch, ctl, kw = _collated(self._collate, reqs, self.noise_scale, *prosody)
         t = lambda a: None if a is None else _as_tensor(a).to(net.device)
         o, x_mask, *_ = net.infer(t(batch["phonemes"]), t(batch["lengths"]), sid=t(batch["sid"]), noise_scale=self.noise_scale,
@@ -452,7 +506,7 @@ class BatchingSynthesisService:
         ``generator_ragged`` call, then the output stage as in ``_synthesize``."""
         import torch
         net, eng = self.net, self.net._engine
-        lat = latents(eng, self._collate, reqs, self.noise_scale, self.sampling_rate, self.prosody_path)
+        lat = latents(eng, self._collate, reqs, self.noise_scale, self.sampling_rate, self.prosody_path, self.prosody_align)
         live = [i for i, (_, _, L) in enumerate(lat) if L > 0]
         pcms = [np.zeros(0, dtype="<i2") for _ in reqs]
         if not live:
