@@ -650,6 +650,79 @@ int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const
  * VSP_ERR_UNSUPPORTED.  C = 16 (additive): both modes on g16_c16. */
 int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
                      const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out);
+/* vsp_cl_block_ex (ABI 7, additive): the two ResBlock operators above as ONE descriptor-based operator that also takes the
+ * launch inputs only the generator's schedule sets otherwise -- the accumulate / divide epilogue of a block's last launch,
+ * the ragged batch, the kernel-choice flags -- and reports which kernel every launch of the block took.  What
+ * tests/test_cl_block_ops.py and tests/test_cl_block_route_host.py drive; vsp_cl_resblock and vsp_cl_resblock2 are this
+ * operator with acc_prev 0, div 1, lengths NULL and the flags read from VSP_PAIR / VSP_RW64 / VSP_CHAIN_RING.
+ *   kind 1: ResBlock1 of n_pairs pairs (w[2 p], w[2 p + 1] = conv1_p, conv2_p);  kind 2: ResBlock2 (w[0], w[1]; n_pairs ignored)
+ *   mode 0: one launch per convolution;  1: one launch per pair, or the fused ResBlock2;  2: one launch for a ResBlock1
+ *   out = (block(x) [+ out when acc_prev]) / div, computed by the block's LAST launch (the generator's sum over a stage's
+ *   ResBlocks, reference models.py:276-285); x != out.
+ *   lengths: NULL or a DEVICE int32 [B]; utterance b's tensor then ends after lengths[b] * grate columns
+ *   (1 <= lengths[b], lengths[b] * grate <= T): the rows at and behind the end read as zero -- whatever they hold -- and
+ *   no row of out there is written.  Every launch of the block gets the same ragged extent.
+ *   ring: the LDS-ring pair kernel where g16_rw exists;  rw64: g16_rw64 for 64-channel kernel-3 pairs;  chain_ring: the
+ *   LDS-ring chain kernel where g16_rc exists;  no_image: mode 0 of a ResBlock1 keeps a pair's intermediate as an fp32
+ *   tensor (what the generator's stages below 128 channels do) where the operator otherwise hands it over as an operand
+ *   image (terms 3, K >= 3, C >= 32: the >= 128-channel stages).  Identical bits.
+ *   plan_only: validate and fill *route, no device access, no HIP call (x, out, lengths are then any non-null addresses,
+ *   the lengths are not read; the tables w and bias are read for NULL entries, the weights behind them are not).
+ * route (may be NULL unless plan_only): the launches in order, for each the kernel (VSP_CL_KERNEL_*), the columns one of its
+ * tiles STORES (tile_cols), for g16_conv the rows of its row tile, and the instantiation (variant: CONV 1 = the image-only
+ * epilogue through the LDS; PAIR the waves of a block; RB2 1 = the 512-column block).  The launchers switch on the same
+ * route functions (kernels.h: g16_conv_route, g16_pair_route, g16_chain_route, g16_rb2_route, g16_c16_route).
+ * VSP_ERR_ARG: a null pointer, x == out, kind / mode / terms out of range, div == 0, grate < 1, a length outside
+ * [1, T / grate], plan_only without route.  VSP_ERR_UNSUPPORTED: the shapes vsp_cl_resblock / vsp_cl_resblock2 refuse.
+ * B = 0 or T = 0: VSP_OK, nothing launched.  With lengths the call copies them to the host and synchronises first. */
+enum {
+  VSP_CL_KERNEL_NONE = 0,
+  VSP_CL_KERNEL_CONV = 1,         /* g16_conv tile, fp32 input */
+  VSP_CL_KERNEL_CONV_IMG = 2,     /* g16_conv tile reading an operand image */
+  VSP_CL_KERNEL_PIPE = 3,         /* g16_convp: persistent image-input tiles (uniform batches only) */
+  VSP_CL_KERNEL_PAIR = 4,         /* g16_pair: the LDS-ring pair tile */
+  VSP_CL_KERNEL_RW = 5,           /* g16_rw<K, ACC> */
+  VSP_CL_KERNEL_RW64 = 6,         /* g16_rw64<ACC> */
+  VSP_CL_KERNEL_PP = 7,           /* g16_pp: the ping-pong pair tile, 128 channels */
+  VSP_CL_KERNEL_CHAIN = 8,        /* g16_chain: the LDS-ring chain tile (32 channels: the 256-column block) */
+  VSP_CL_KERNEL_CHAIN_WIDE = 9,   /* g16_chain, 32 channels, the 512-column block */
+  VSP_CL_KERNEL_RC = 10,          /* g16_rc */
+  VSP_CL_KERNEL_RB2 = 11,         /* g16_rb2 */
+  VSP_CL_KERNEL_C16 = 12,         /* g16_c16 */
+  VSP_CL_KERNEL_UPS = 13          /* g16_ups: the streaming up-convolution (never part of a ResBlock) */
+};
+typedef struct vsp_cl_launch_route {
+  int32_t kernel;                 /* VSP_CL_KERNEL_* */
+  int32_t tile_cols;              /* columns one tile stores */
+  int32_t rows;                   /* CONV / CONV_IMG / PIPE: output rows of the row tile (128, 64, 32); else 0 */
+  int32_t variant;                /* see above */
+} vsp_cl_launch_route;
+#define VSP_CL_BLOCK_MAX_LAUNCHES 16
+typedef struct vsp_cl_block_route {
+  int32_t n;                                               /* launches of the block */
+  vsp_cl_launch_route launch[VSP_CL_BLOCK_MAX_LAUNCHES];
+} vsp_cl_block_route;
+typedef struct vsp_cl_block_desc {
+  int32_t kind, mode, B, T, C, K, n_pairs, terms;
+  const int32_t* dilations;                                /* host: kind 1 [n_pairs], kind 2 [2] */
+  const float* x; float* out;                              /* device [B][T][C] */
+  const float* const* w; const float* const* bias;         /* host: dense [C][C][K] and [C] per convolution, execution order */
+  const int32_t* lengths;                                  /* device [B] or NULL */
+  int32_t grate;
+  int32_t acc_prev; float div;
+  int32_t ring, rw64, chain_ring, no_image;
+  int32_t plan_only;
+} vsp_cl_block_desc;
+int vsp_cl_block_ex(void* stream, const vsp_cl_block_desc* d, vsp_cl_block_route* route);
+/* vsp_cl_conv_post (ABI 7, additive): the channels-last generator's last layer as a plain operator (reference
+ * models.py:286-288: F.leaky_relu, conv_post without bias, tanh),
+ *   out[b][t] = tanh(unscale * sum_{c, j} w[0][c][j] * lrelu(x[b][t + j - (K - 1) / 2][c], slope))
+ * x DEVICE [B][T][C] channels-last, C 16 / 32 / 64; w_host HOST [1][C][K] (the reference's layout), K odd and <= 7;
+ * out DEVICE [B][T].  lengths / grate as in vsp_cl_block_ex: utterance b ends after lengths[b] * grate columns, the rows
+ * behind read as zero and out behind is not written.  No status word is passed to the kernel.
+ * VSP_ERR_ARG: a null pointer, grate < 1, a length outside [1, T / grate];  VSP_ERR_UNSUPPORTED: C or K outside the above. */
+int vsp_cl_conv_post(void* stream, int B, int T, int C, int K, const float* x, const float* w_host, float slope, float unscale,
+                     const int32_t* lengths, int grate, float* out);
 /* vsp_cl_conv_transpose1d (ABI 7, additive): HiFi-GAN's up-convolution as the channels-last generator runs it
  * (reference models.py:253-256, 277-278: F.leaky_relu + ConvTranspose1d),
  *   out = conv_transpose1d(lrelu(x, in_slope), w, bias, stride, padding = (K - stride) / 2)

@@ -115,6 +115,37 @@ class VspConv1dDesc(C.Structure):
 (CONV_FORM_NONE, CONV_FORM_COLS, CONV_FORM_COLS_LN, CONV_FORM_GEMV, CONV_FORM_SPLITK, CONV_FORM_FRAME_SHORT, CONV_FORM_FRAME,
  CONV_FORM_TILE) = range(8)
 
+
+class VspClLaunchRoute(C.Structure):
+    """``vsp_cl_launch_route``: the kernel one launch of a channels-last block takes (``CL_KERNEL_*``), the columns one of
+    its tiles stores, g16_conv's row tile, the instantiation."""
+    _fields_ = [("kernel", C.c_int32), ("tile_cols", C.c_int32), ("rows", C.c_int32), ("variant", C.c_int32)]
+
+
+CL_BLOCK_MAX_LAUNCHES = 16
+
+
+class VspClBlockRoute(C.Structure):
+    """``vsp_cl_block_route``: the launches of one ``vsp_cl_block_ex`` call, in order."""
+    _fields_ = [("n", C.c_int32), ("launch", VspClLaunchRoute * CL_BLOCK_MAX_LAUNCHES)]
+
+
+class VspClBlockDesc(C.Structure):
+    """``vsp_cl_block_desc`` of ``vsp_cl_block_ex`` (field order is ABI): a ResBlock1 (kind 1) or ResBlock2 (kind 2) on
+    channels-last tensors, the accumulate / divide epilogue of its last launch, the ragged batch and the kernel flags."""
+    _fields_ = [("kind", C.c_int32), ("mode", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32),
+                ("K", C.c_int32), ("n_pairs", C.c_int32), ("terms", C.c_int32),
+                ("dilations", C.c_void_p), ("x", C.c_void_p), ("out", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("lengths", C.c_void_p), ("grate", C.c_int32), ("acc_prev", C.c_int32), ("div", C.c_float),
+                ("ring", C.c_int32), ("rw64", C.c_int32), ("chain_ring", C.c_int32), ("no_image", C.c_int32),
+                ("plan_only", C.c_int32)]
+
+
+# VSP_CL_KERNEL_* (vsp_cl_launch_route.kernel)
+(CL_KERNEL_NONE, CL_KERNEL_CONV, CL_KERNEL_CONV_IMG, CL_KERNEL_PIPE, CL_KERNEL_PAIR, CL_KERNEL_RW, CL_KERNEL_RW64, CL_KERNEL_PP,
+ CL_KERNEL_CHAIN, CL_KERNEL_CHAIN_WIDE, CL_KERNEL_RC, CL_KERNEL_RB2, CL_KERNEL_C16, CL_KERNEL_UPS) = range(14)
+
+
 class VspProsodyParams(C.Structure):
     """``vsp_prosody_params``: pitch floor and ceiling (Hz), voicing threshold, silence threshold, octave cost."""
     _fields_ = [("floor_hz", C.c_float), ("ceiling_hz", C.c_float), ("voicing_threshold", C.c_float),
@@ -232,6 +263,8 @@ SIGNATURES = {
     "vsp_conv1d_ex": (_I, [_P, C.POINTER(VspConv1dDesc), C.POINTER(VspConvForm)]),
     "vsp_cl_resblock": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "vsp_cl_resblock2": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "vsp_cl_block_ex": (_I, [_P, C.POINTER(VspClBlockDesc), C.POINTER(VspClBlockRoute)]),
+    "vsp_cl_conv_post": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _F, _P, _I, _P]),
     "vsp_cl_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _I, _P]),
     "vsp_conv_transpose1d": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P]),
     "vsp_rel_attention": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),

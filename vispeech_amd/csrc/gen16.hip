@@ -714,49 +714,31 @@ static hipError_t launch_g16_ups(const ClConvArgs& a, int B, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s) {
-  // 16 -> 16 channels (the last stage of a five-stage generator): one step of g16_c16 (gen16_c16.hip), whose weight
-  // image is pack_g16c16_weights'.  fp32 tensors only, "same" padding, one extent for input and output.
-  if (cl_is_c16(a.Cout, a.Cin, a.phases)) {
-    if (a.x_img || a.o_img || !a.x || !a.out || a.x_ts != 16 || a.o_ts != 16 || (a.res && a.r_ts != 16) || a.K < 1 || !(a.K & 1) ||
-        a.pad != a.dil * (a.K - 1) / 2 || a.T_in != a.Nq || a.T_store != a.Nq || (a.glen && a.g_in != a.g_store) || a.ups_p)
-      return hipErrorInvalidValue;
-    ClC16Args c;
-    std::memset(&c, 0, sizeof c);
-    c.x = a.x; c.x_bs = a.x_bs; c.res = a.res; c.r_bs = a.r_bs; c.out = a.out; c.o_bs = a.o_bs;
-    c.w[0] = a.wh; c.b[0] = a.bias; c.dil[0] = a.dil; c.add[0] = a.res ? 1 : 0;
-    c.nsteps = 1; c.K = a.K; c.T = a.Nq;
-    c.slope = a.in_act ? a.in_slope : 1.f;                // (leaky-relu with slope 1 is the identity)
-    c.acc_prev = a.acc_prev; c.div = a.div; c.terms = a.terms;
-    c.glen = a.glen; c.grate = a.g_store;
-    return launch_g16_c16(c, B, s);
-  }
-  if ((a.K - 1) * a.dil > G16_HALO || a.K < 1 || a.Nq <= 0 || B <= 0 || a.Cout % 16 || a.Cin % 32 || a.phases < 1 ||
-      (a.x_ts & 3) || (a.x_bs & 3) || (reinterpret_cast<uintptr_t>(a.x) & 15) || (a.o_ts & 3) || (a.o_bs & 3) ||
-      (reinterpret_cast<uintptr_t>(a.out) & 15) || (!a.out && !a.o_img) || (!a.x && !a.x_img))
-    return hipErrorInvalidValue;
-  if ((a.x_img || a.o_img) && (a.terms != 3 || a.phases != 1)) return hipErrorInvalidValue;
-  if (a.o_img && (a.oi_tpad < cl_img_tpad(a.T_store) || (a.oi_bs & 7) || (reinterpret_cast<uintptr_t>(a.o_img) & 15)))
-    return hipErrorInvalidValue;
-  // an utterance's operand image is addressed with 32-bit byte offsets (descriptor num_records, `unit` in the epilogue);
-  // the image-input windows are raw pointer reads of rows [t0 - pad, t0 + BT + halo): only the pad rows cover an overshoot
-  if ((a.o_img && (size_t)a.Cout * 4 * (size_t)a.oi_tpad >= (size_t)1 << 31) ||
-      (a.x_img && ((size_t)a.Cin * 4 * (size_t)a.xi_tpad >= (size_t)1 << 31 || a.Nq > a.T_in)))
-    return hipErrorInvalidValue;
+// a 16 -> 16 convolution as one step of g16_c16
+static ClC16Args g16_conv_as_c16(const ClConvArgs& a) {
+  ClC16Args c;
+  std::memset(&c, 0, sizeof c);
+  c.x = a.x; c.x_bs = a.x_bs; c.res = a.res; c.r_bs = a.r_bs; c.out = a.out; c.o_bs = a.o_bs;
+  c.w[0] = a.wh; c.b[0] = a.bias; c.dil[0] = a.dil; c.add[0] = a.res ? 1 : 0;
+  c.nsteps = 1; c.K = a.K; c.T = a.Nq;
+  c.slope = a.in_act ? a.in_slope : 1.f;                // (leaky-relu with slope 1 is the identity)
+  c.acc_prev = a.acc_prev; c.div = a.div; c.terms = a.terms;
+  c.glen = a.glen; c.grate = a.g_store;
+  return c;
+}
+
+ClRoute g16_conv_route(const ClConvArgs& a, int B) {
+  const ClRoute none{VSP_CL_KERNEL_NONE, 0, 0, 0};
+  if (cl_is_c16(a.Cout, a.Cin, a.phases)) return g16_c16_route(g16_conv_as_c16(a));
   const int rows = a.phases * a.Cout;
   // the short up-convs (kernel 4 at stride 4 or 2): streaming kernel (no residual / accumulate operands there)
   if (a.terms == 3 && a.phases > 1 && a.dil == 1 && a.pad == a.K - 1 && !a.res && !a.acc_prev && a.div == 1.f &&
       a.in_slope >= 0.f && a.in_slope <= 1.f && g16_ups_on()) {
-    if (a.K == 2 && a.Cin == 64 && rows == 64) return launch_g16_ups<2, 2, 4, 1>(a, B, s);      // 64 -> 32 channels, stride 2
-    if (a.K == 1 && a.Cin == 128 && rows == 256) return launch_g16_ups<1, 4, 4, 4>(a, B, s);    // 128 -> 64 channels, stride 4
+    if (a.K == 2 && a.Cin == 64 && rows == 64) return ClRoute{VSP_CL_KERNEL_UPS, 16, rows, 2};     // 64 -> 32 channels, stride 2
+    if (a.K == 1 && a.Cin == 128 && rows == 256) return ClRoute{VSP_CL_KERNEL_UPS, 16, rows, 1};   // 128 -> 64 channels, stride 4
   }
-  // <MW, NW, WM, WN, TERMS>
-  if (a.terms == 1) {
-    if (rows % 128 == 0) return launch_g16_tile<4, 4, 2, 4, 1>(a, B, s);
-    if (rows % 64 == 0) return launch_g16_tile<4, 2, 1, 8, 1>(a, B, s);
-    if (rows % 32 == 0) return launch_g16_tile<2, 2, 1, 8, 1>(a, B, s);
-    return hipErrorInvalidValue;
-  }
+  const int any_rows = rows % 128 == 0 ? 128 : rows % 64 == 0 ? 64 : rows % 32 == 0 ? 32 : 0;
+  if (a.terms == 1) return any_rows ? ClRoute{VSP_CL_KERNEL_CONV, 256, any_rows, 0} : none;
   // Row tile: 128 rows x 256 columns (one block per CU) when that fills the chip; a launch with fewer blocks than CUs
   // (one or two utterances: the 256 / 128-channel stages) takes the 64- or 32-row tile and spreads over 2-4x the CUs.
 #ifdef VSP_EXPERIMENTS
@@ -772,26 +754,69 @@ hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s) {
   int want = 128;
   if (force) want = force;
   else if (col_tiles * (rows / 128 > 0 ? rows / 128 : 1) < fill) want = col_tiles * (rows / 64 > 0 ? rows / 64 : 1) < fill ? 32 : 64;
+  const int tile_rows = (rows % 128 == 0 && want >= 128) ? 128 : (rows % 64 == 0 && want >= 64) ? 64 : rows % 32 == 0 ? 32 : 0;
+  if (!tile_rows) return none;
   if (a.x_img) {                                                                        // input = operand image (LDS-DMA windows)
-    if (a.K < 3 || a.phases != 1 || a.pad > CL_IMG_PADF || a.xi_tpad < cl_img_tpad(a.T_in) || (a.xi_bs & 7)) return hipErrorInvalidValue;
-    if (rows % 128 == 0 && want >= 128) {
-      if (!a.glen && g16_pipe_supported(a)) return launch_g16_pipe(a, B, s);             // persistent, pipelined across tiles (uniform batches)
-      return launch_g16_tile<4, 4, 2, 4, 3, true>(a, B, s);
-    }
-    if (rows % 64 == 0 && want >= 64) return launch_g16_tile<4, 2, 1, 8, 3, true>(a, B, s);
-    if (rows % 32 == 0) return launch_g16_tile<2, 2, 1, 8, 3, true>(a, B, s);
-    return hipErrorInvalidValue;
+    if (a.K < 3 || a.phases != 1 || a.pad > CL_IMG_PADF || a.xi_tpad < cl_img_tpad(a.T_in) || (a.xi_bs & 7)) return none;
+    // persistent, pipelined across tiles (uniform batches only: a ragged launch never goes there)
+    if (tile_rows == 128 && !a.glen && g16_pipe_supported(a)) return ClRoute{VSP_CL_KERNEL_PIPE, 256, 128, 0};
+    return ClRoute{VSP_CL_KERNEL_CONV_IMG, 256, tile_rows, 0};
   }
   // (an image-only result -- a ResBlock pair's intermediate -- of the 128-row tile: the instantiation whose epilogue goes
   // through the LDS, 1 KiB contiguous per store; bit-identical images)
 #if G16_EPI_LDS && G16_IMG_EPI
-  if (rows % 128 == 0 && want >= 128 && a.phases == 1 && !a.out && a.o_img && !a.res && !a.acc_prev)
-    return launch_g16_tile<4, 4, 2, 4, 3, false, true>(a, B, s);
+  if (tile_rows == 128 && a.phases == 1 && !a.out && a.o_img && !a.res && !a.acc_prev) return ClRoute{VSP_CL_KERNEL_CONV, 256, 128, 1};
 #endif
-  if (rows % 128 == 0 && want >= 128) return launch_g16_tile<4, 4, 2, 4, 3>(a, B, s);   // 128 rows x 256 columns, one block per CU
-  if (rows % 64 == 0 && want >= 64) return launch_g16_tile<4, 2, 1, 8, 3>(a, B, s);     //  64 rows x 256 columns
-  if (rows % 32 == 0) return launch_g16_tile<2, 2, 1, 8, 3>(a, B, s);                   //  32 rows x 256 columns
-  return hipErrorInvalidValue;
+  return ClRoute{VSP_CL_KERNEL_CONV, 256, tile_rows, 0};
+}
+
+hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s) {
+  // 16 -> 16 channels (the last stage of a five-stage generator): one step of g16_c16 (gen16_c16.hip), whose weight
+  // image is pack_g16c16_weights'.  fp32 tensors only, "same" padding, one extent for input and output.
+  if (cl_is_c16(a.Cout, a.Cin, a.phases)) {
+    if (a.x_img || a.o_img || !a.x || !a.out || a.x_ts != 16 || a.o_ts != 16 || (a.res && a.r_ts != 16) || a.K < 1 || !(a.K & 1) ||
+        a.pad != a.dil * (a.K - 1) / 2 || a.T_in != a.Nq || a.T_store != a.Nq || (a.glen && a.g_in != a.g_store) || a.ups_p)
+      return hipErrorInvalidValue;
+    return launch_g16_c16(g16_conv_as_c16(a), B, s);
+  }
+  if ((a.K - 1) * a.dil > G16_HALO || a.K < 1 || a.Nq <= 0 || B <= 0 || a.Cout % 16 || a.Cin % 32 || a.phases < 1 ||
+      (a.x_ts & 3) || (a.x_bs & 3) || (reinterpret_cast<uintptr_t>(a.x) & 15) || (a.o_ts & 3) || (a.o_bs & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out) & 15) || (!a.out && !a.o_img) || (!a.x && !a.x_img))
+    return hipErrorInvalidValue;
+  if ((a.x_img || a.o_img) && (a.terms != 3 || a.phases != 1)) return hipErrorInvalidValue;
+  if (a.o_img && (a.oi_tpad < cl_img_tpad(a.T_store) || (a.oi_bs & 7) || (reinterpret_cast<uintptr_t>(a.o_img) & 15)))
+    return hipErrorInvalidValue;
+  // an utterance's operand image is addressed with 32-bit byte offsets (descriptor num_records, `unit` in the epilogue);
+  // the image-input windows are raw pointer reads of rows [t0 - pad, t0 + BT + halo): only the pad rows cover an overshoot
+  if ((a.o_img && (size_t)a.Cout * 4 * (size_t)a.oi_tpad >= (size_t)1 << 31) ||
+      (a.x_img && ((size_t)a.Cin * 4 * (size_t)a.xi_tpad >= (size_t)1 << 31 || a.Nq > a.T_in)))
+    return hipErrorInvalidValue;
+  // the kernel and its tile: g16_conv_route above.  <MW, NW, WM, WN, TERMS, XIN, IMG_EPI>
+  const ClRoute r = g16_conv_route(a, B);
+  switch (r.kernel) {
+    case VSP_CL_KERNEL_UPS:
+      return r.variant == 2 ? launch_g16_ups<2, 2, 4, 1>(a, B, s) : launch_g16_ups<1, 4, 4, 4>(a, B, s);
+    case VSP_CL_KERNEL_PIPE:
+      return launch_g16_pipe(a, B, s);
+    case VSP_CL_KERNEL_CONV_IMG:
+      if (r.rows == 128) return launch_g16_tile<4, 4, 2, 4, 3, true>(a, B, s);
+      if (r.rows == 64) return launch_g16_tile<4, 2, 1, 8, 3, true>(a, B, s);
+      return launch_g16_tile<2, 2, 1, 8, 3, true>(a, B, s);
+    case VSP_CL_KERNEL_CONV:
+      if (a.terms == 1) {
+        if (r.rows == 128) return launch_g16_tile<4, 4, 2, 4, 1>(a, B, s);
+        if (r.rows == 64) return launch_g16_tile<4, 2, 1, 8, 1>(a, B, s);
+        return launch_g16_tile<2, 2, 1, 8, 1>(a, B, s);
+      }
+#if G16_EPI_LDS && G16_IMG_EPI
+      if (r.variant == 1) return launch_g16_tile<4, 4, 2, 4, 3, false, true>(a, B, s);
+#endif
+      if (r.rows == 128) return launch_g16_tile<4, 4, 2, 4, 3>(a, B, s);   // 128 rows x 256 columns, one block per CU
+      if (r.rows == 64) return launch_g16_tile<4, 2, 1, 8, 3>(a, B, s);    //  64 rows x 256 columns
+      return launch_g16_tile<2, 2, 1, 8, 3>(a, B, s);                      //  32 rows x 256 columns
+    default:
+      return hipErrorInvalidValue;
+  }
 }
 
 // pair kernel: a wave copies 0, 1 or 2 pieces of a slice (partial last slices of a chunk)
@@ -1095,14 +1120,14 @@ __global__ void __launch_bounds__(64 * NWV, 4) g16_pair(ClPairArgs a) {
 }
 
 template <int NCH, int G, int TERMS, int NWV, int NS = 3>
-static hipError_t launch_g16_pair_tile(ClPairArgs a, int B, hipStream_t s) {
+static hipError_t launch_g16_pair_tile(ClPairArgs a, int B, hipStream_t s, int R2) {
   constexpr int BT = 32 * NWV;
   constexpr size_t lds = (size_t)2 * 4 * (BT + G16_HALO) * 16 + (size_t)NS * G * 2 * NCH * 2048;
   static_assert(lds <= (NWV == 8 ? 80 : 160) * 1024, "two 8-wave blocks or one 16-wave block per CU");
   static std::atomic<uint64_t> attr_done{0};
   auto kern = g16_pair<NCH, G, TERMS, NWV, NS>;
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done); e != hipSuccess) return e;
-  const int R2 = BT - (a.K - 1);
+  if (R2 != BT - (a.K - 1)) return hipErrorInvalidValue;     // (the route's tile_cols: what the kernel stores per tile)
   a.tiles = (a.T + R2 - 1) / R2;
   const long n = (long)a.tiles * B;
   if (n <= 0 || n > 0x7fffffffL) return hipErrorInvalidValue;
@@ -1122,11 +1147,8 @@ bool g16_pair_supported(int C, int K, int dil) {
   return (C == 32 || C == 64) && K >= 1 && (K & 1) && (K - 1) * dil <= G16_HALO && K - 1 < 128;
 }
 
-hipError_t launch_g16_pair(const ClPairArgs& a, int B, hipStream_t s) {
-  if (a.C == 128) return launch_g16_pp(a, B, s);       // the ping-pong tile pair (gen16_pp.hip)
-  if (!g16_pair_supported(a.C, a.K, a.dil) || a.T <= 0 || B <= 0 || (a.x_bs & 3) || (a.o_bs & 3) ||
-      (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out)
-    return hipErrorInvalidValue;
+ClRoute g16_pair_route(const ClPairArgs& a) {
+  if (a.C == 128) return ClRoute{VSP_CL_KERNEL_PP, g16_pp_tile_cols(a.K), 0, 0};       // the ping-pong tile pair (gen16_pp.hip)
   // block shape: 8 waves x 32 columns, two blocks per CU (the 16-wave one-block-per-CU form -- one weight ring per CU,
   // half the LDS-DMA pieces -- measured 12 % slower: profiles/r02_same_box_ab.txt; experiment builds keep it)
 #ifdef VSP_EXPERIMENTS
@@ -1137,19 +1159,37 @@ hipError_t launch_g16_pair(const ClPairArgs& a, int B, hipStream_t s) {
 #endif
   // round 4: weights in registers, persistent blocks (gen16_rw.hip) where that kernel exists; ClPairArgs::ring (VSP_PAIR=ring) keeps the
   // LDS-ring kernel below (the second implementation under test: bit-identical)
-  if (!a.ring && g16_rw_supported(a.C, a.K, a.dil, a.terms)) return launch_g16_rw(a, B, s);
+  if (!a.ring && g16_rw_supported(a.C, a.K, a.dil, a.terms)) return ClRoute{VSP_CL_KERNEL_RW, g16_rw_tile_cols(a.K), 0, 0};
   // round 5: the same for the kernel-3 pairs of the 64-channel stage (gen16_rw64.hip) -- bit-identical, measured 2-5 % SLOWER
   // than the ring kernel below (profiles/r05_g16_rw64_k3_pairs_64_channels.txt): opt-in (ClPairArgs::rw64, VSP_RW64=1)
-  if (!a.ring && a.rw64 && g16_rw64_supported(a.C, a.K, a.dil, a.terms)) return launch_g16_rw64(a, B, s);
+  if (!a.ring && a.rw64 && g16_rw64_supported(a.C, a.K, a.dil, a.terms)) return ClRoute{VSP_CL_KERNEL_RW64, g16_rw64_tile_cols(), 0, 0};
+  // the LDS-ring tile: 32 columns per wave (launch_g16_pair_tile: BT = 32 * NWV)
+  if (a.terms == 1 || nwv == 8) return ClRoute{VSP_CL_KERNEL_PAIR, 32 * 8 - (a.K - 1), 0, 8};
+#ifdef VSP_EXPERIMENTS
+  return ClRoute{VSP_CL_KERNEL_PAIR, 32 * 16 - (a.K - 1), 0, 16};
+#else
+  return ClRoute{VSP_CL_KERNEL_NONE, 0, 0, 0};
+#endif
+}
+
+hipError_t launch_g16_pair(const ClPairArgs& a, int B, hipStream_t s) {
+  const ClRoute r = g16_pair_route(a);
+  if (r.kernel == VSP_CL_KERNEL_PP) return launch_g16_pp(a, B, s);
+  if (!g16_pair_supported(a.C, a.K, a.dil) || a.T <= 0 || B <= 0 || (a.x_bs & 3) || (a.o_bs & 3) ||
+      (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out)
+    return hipErrorInvalidValue;
+  if (r.kernel == VSP_CL_KERNEL_RW) return launch_g16_rw(a, B, s);
+  if (r.kernel == VSP_CL_KERNEL_RW64) return launch_g16_rw64(a, B, s);
+  if (r.kernel != VSP_CL_KERNEL_PAIR) return hipErrorInvalidValue;
   if (a.terms == 1)
-    return a.C == 32 ? launch_g16_pair_tile<1, 2, 1, 8>(a, B, s) : launch_g16_pair_tile<2, 1, 1, 8>(a, B, s);
+    return a.C == 32 ? launch_g16_pair_tile<1, 2, 1, 8>(a, B, s, r.tile_cols) : launch_g16_pair_tile<2, 1, 1, 8>(a, B, s, r.tile_cols);
   // round 3: TWO ring slots of twice the taps (32 channels: 4 taps = 16 KB, 64 channels: 2 taps = 16 KB; 72 KB of LDS
   // per block, still two blocks per CU): the slice hand-over -- counted wait, barrier, LDS-DMA issue: 0.5 us per slice
   // in the stamps of profiles/r03_pair_kernel_phase_stamps.txt, more than the slice's MFMAs -- happens half as often
   // (generator -1.2 ms same box; the request is only one slice ahead now, which gives part of it back)
-  if (nwv == 8) return a.C == 32 ? launch_g16_pair_tile<1, 4, 3, 8, 2>(a, B, s) : launch_g16_pair_tile<2, 2, 3, 8, 2>(a, B, s);
+  if (r.variant == 8) return a.C == 32 ? launch_g16_pair_tile<1, 4, 3, 8, 2>(a, B, s, r.tile_cols) : launch_g16_pair_tile<2, 2, 3, 8, 2>(a, B, s, r.tile_cols);
 #ifdef VSP_EXPERIMENTS
-  return a.C == 32 ? launch_g16_pair_tile<1, 2, 3, 16>(a, B, s) : launch_g16_pair_tile<2, 1, 3, 16>(a, B, s);
+  return a.C == 32 ? launch_g16_pair_tile<1, 2, 3, 16>(a, B, s, r.tile_cols) : launch_g16_pair_tile<2, 1, 3, 16>(a, B, s, r.tile_cols);
 #else
   return hipErrorInvalidValue;
 #endif
@@ -1434,15 +1474,14 @@ __global__ void __launch_bounds__(64 * NWV, 2) g16_chain(ClChainArgs a) {
 }
 
 template <int NCH, int NW, int G, int TERMS, int NWV>
-static hipError_t launch_g16_chain_tile(ClChainArgs a, int B, hipStream_t s) {
+static hipError_t launch_g16_chain_tile(ClChainArgs a, int B, hipStream_t s, int R) {
   constexpr int BT = 16 * NW * NWV;
   constexpr size_t lds = (size_t)NCH * 2 * 4 * (BT + G16_HALO) * 16 + (size_t)3 * G * 2 * NCH * 2048;
   static_assert(lds <= 160 * 1024, "LDS budget");
   static std::atomic<uint64_t> attr_done{0};
   auto kern = g16_chain<NCH, NW, G, TERMS, NWV>;
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done); e != hipSuccess) return e;
-  const int R = BT - 2 * a.halo;
-  if (R < 32) return hipErrorInvalidValue;
+  if (R != BT - 2 * a.halo || R < 32) return hipErrorInvalidValue;   // (the route's tile_cols: what the kernel stores per tile)
   a.tiles = (a.T + R - 1) / R;
   const long n = (long)a.tiles * B;
   if (n <= 0 || n > 0x7fffffffL) return hipErrorInvalidValue;
@@ -1472,14 +1511,11 @@ bool g16_chain_supported(int C, int K, const int* dil, int np) {
   return (C == 128 ? 128 : 256) - 2 * g16_chain_halo(K, dil, np) >= 32;
 }
 
-hipError_t launch_g16_chain(const ClChainArgs& a0, int B, hipStream_t s) {
-  ClChainArgs a = a0;
-  if (!g16_chain_supported(a.C, a.K, a.dil, a.np) || a.T <= 0 || B <= 0 || (a.x_bs & 3) || (a.o_bs & 3) ||
-      (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out)
-    return hipErrorInvalidValue;
+ClRoute g16_chain_route(const ClChainArgs& a) {
   // round 4: the kernel-3 ResBlock of the 32-channel stage as a role pipeline with the weights in registers (gen16_rc.hip)
-  if (!a.ring && g16_rc_supported(a.C, a.K, a.dil, a.np, a.terms, a.acc_prev)) return launch_g16_rc(a, B, s);
-  a.halo = g16_chain_halo(a.K, a.dil, a.np);
+  if (!a.ring && g16_rc_supported(a.C, a.K, a.dil, a.np, a.terms, a.acc_prev))
+    return ClRoute{VSP_CL_KERNEL_RC, g16_rc_tile_cols(a.K, a.dil, a.np), 0, 0};
+  const int halo = g16_chain_halo(a.K, a.dil, a.np);
   // few, fat waves (64 columns x all channels each, up to 256 registers).  32 channels: one 8-wave block of 512
   // columns per CU when the halo would eat more than a quarter of a 256-column tile, else two 4-wave blocks of 256
   // columns (their convolution hand-offs overlap)
@@ -1489,15 +1525,29 @@ hipError_t launch_g16_chain(const ClChainArgs& a0, int B, hipStream_t s) {
 #else
   constexpr int force = 0;
 #endif
-  const bool wide = a.C == 32 && (force ? force == 8 : 2 * a.halo > 64);
+  const bool wide = a.C == 32 && (force ? force == 8 : 2 * halo > 64);
+  // 128 channels: 128-column blocks; 64 channels: 256 (launch_g16_chain_tile: BT = 16 * NW * NWV)
+  if (wide) return ClRoute{VSP_CL_KERNEL_CHAIN_WIDE, 512 - 2 * halo, 0, 0};
+  return ClRoute{VSP_CL_KERNEL_CHAIN, (a.C == 128 ? 128 : 256) - 2 * halo, 0, 0};
+}
+
+hipError_t launch_g16_chain(const ClChainArgs& a0, int B, hipStream_t s) {
+  ClChainArgs a = a0;
+  if (!g16_chain_supported(a.C, a.K, a.dil, a.np) || a.T <= 0 || B <= 0 || (a.x_bs & 3) || (a.o_bs & 3) ||
+      (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out)
+    return hipErrorInvalidValue;
+  const ClRoute r = g16_chain_route(a);
+  if (r.kernel == VSP_CL_KERNEL_RC) return launch_g16_rc(a, B, s);
+  a.halo = g16_chain_halo(a.K, a.dil, a.np);
+  const bool wide = r.kernel == VSP_CL_KERNEL_CHAIN_WIDE;
   // <NCH, NW, G, TERMS, NWV>
-  if (a.C == 128) return a.terms == 1 ? launch_g16_chain_tile<4, 1, 1, 1, 8>(a, B, s) : launch_g16_chain_tile<4, 1, 1, 3, 8>(a, B, s);
+  if (a.C == 128) return a.terms == 1 ? launch_g16_chain_tile<4, 1, 1, 1, 8>(a, B, s, r.tile_cols) : launch_g16_chain_tile<4, 1, 1, 3, 8>(a, B, s, r.tile_cols);
   if (a.terms == 1) {
-    if (a.C == 64) return launch_g16_chain_tile<2, 2, 2, 1, 8>(a, B, s);
-    return wide ? launch_g16_chain_tile<1, 4, 4, 1, 8>(a, B, s) : launch_g16_chain_tile<1, 4, 2, 1, 4>(a, B, s);
+    if (a.C == 64) return launch_g16_chain_tile<2, 2, 2, 1, 8>(a, B, s, r.tile_cols);
+    return wide ? launch_g16_chain_tile<1, 4, 4, 1, 8>(a, B, s, r.tile_cols) : launch_g16_chain_tile<1, 4, 2, 1, 4>(a, B, s, r.tile_cols);
   }
-  if (a.C == 64) return launch_g16_chain_tile<2, 2, 2, 3, 8>(a, B, s);
-  return wide ? launch_g16_chain_tile<1, 4, 4, 3, 8>(a, B, s) : launch_g16_chain_tile<1, 4, 2, 3, 4>(a, B, s);
+  if (a.C == 64) return launch_g16_chain_tile<2, 2, 2, 3, 8>(a, B, s, r.tile_cols);
+  return wide ? launch_g16_chain_tile<1, 4, 4, 3, 8>(a, B, s, r.tile_cols) : launch_g16_chain_tile<1, 4, 2, 3, 4>(a, B, s, r.tile_cols);
 }
 
 }  // namespace vsp

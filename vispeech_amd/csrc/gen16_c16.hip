@@ -202,6 +202,10 @@ bool g16_c16_rb2_supported(int K, const int* dil) {
   return g16_c16_supported(K, d, cl_c16_steps(2, dil, 2, d, add));
 }
 
+ClRoute g16_c16_route(const ClC16Args& a) {
+  return ClRoute{VSP_CL_KERNEL_C16, C16_BT - 2 * g16_c16_halo(a.K, a.dil, a.nsteps), 0, 0};
+}
+
 template <int TERMS>
 static hipError_t launch_g16_c16_terms(const ClC16Args& a, int B, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
@@ -224,7 +228,7 @@ hipError_t launch_g16_c16(const ClC16Args& a0, int B, hipStream_t s) {
   // an utterance is addressed with 32-bit byte offsets (buffer descriptors: num_records, t * 64)
   if ((size_t)a.T * 64 >= (size_t)1 << 31) return hipErrorInvalidValue;
   a.halo = g16_c16_halo(a.K, a.dil, a.nsteps);
-  const int R = C16_BT - 2 * a.halo;
+  const int R = g16_c16_route(a).tile_cols;
   a.tiles = (a.T + R - 1) / R;
   if ((long)a.tiles * B > 0x7fffffffL) return hipErrorInvalidValue;
   return a.terms == 1 ? launch_g16_c16_terms<1>(a, B, s) : launch_g16_c16_terms<3>(a, B, s);

@@ -407,6 +407,9 @@ __global__ void __launch_bounds__(512) g16_pp(ClPairArgs a) {
 #endif
 }
 
+constexpr int PP_NW = 3;                    // waves along time, 64 columns each: 192 conv1 columns per tile
+int g16_pp_tile_cols(int K) { return 64 * PP_NW - (K - 1); }
+
 template <int NW, int HALO>
 static hipError_t launch_g16_pp_tile(ClPairArgs a, int B, hipStream_t s) {
   constexpr int BT = 64 * NW;
@@ -414,7 +417,8 @@ static hipError_t launch_g16_pp_tile(ClPairArgs a, int B, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   auto kern = g16_pp<NW, HALO>;
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done); e != hipSuccess) return e;
-  const int R2 = BT - (a.K - 1);
+  static_assert(NW == PP_NW, "g16_pp_tile_cols");
+  const int R2 = g16_pp_tile_cols(a.K);
   a.tiles = (a.T + R2 - 1) / R2;
   const long n = (long)a.tiles * B;
   if (n <= 0 || n > 0x7fffffffL) return hipErrorInvalidValue;
@@ -438,7 +442,7 @@ hipError_t launch_g16_pp(const ClPairArgs& a, int B, hipStream_t s) {
       (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out ||
       (long)a.T * a.C * 4 >= (1L << 31))
     return hipErrorInvalidValue;
-  return a.K == 3 ? launch_g16_pp_tile<3, 16>(a, B, s) : launch_g16_pp_tile<3, 32>(a, B, s);
+  return a.K == 3 ? launch_g16_pp_tile<PP_NW, 16>(a, B, s) : launch_g16_pp_tile<PP_NW, 32>(a, B, s);
 }
 
 }  // namespace vsp

@@ -241,15 +241,14 @@ __global__ void __launch_bounds__(64 * NWV, 2) g16_rb2(ClRb2Args a) {
 }
 
 template <int NCH, int NW, int G, int TERMS, int NWV>
-static hipError_t launch_g16_rb2_tile(ClRb2Args a, int B, hipStream_t s) {
+static hipError_t launch_g16_rb2_tile(ClRb2Args a, int B, hipStream_t s, int R) {
   constexpr int BT = 16 * NW * NWV;
   constexpr size_t lds = (size_t)NCH * 2 * 4 * (BT + G16_HALO) * 16 + (size_t)3 * G * 2 * NCH * 2048;
   static_assert(lds <= 160 * 1024, "LDS budget");
   static std::atomic<uint64_t> attr_done{0};
   auto kern = g16_rb2<NCH, NW, G, TERMS, NWV>;
   if (hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds, attr_done); e != hipSuccess) return e;
-  const int R = BT - 2 * a.halo;
-  if (R < 32) return hipErrorInvalidValue;
+  if (R != BT - 2 * a.halo || R < 32) return hipErrorInvalidValue;   // (the route's tile_cols: what the kernel stores per tile)
   a.tiles = (a.T + R - 1) / R;
   const long n = (long)a.tiles * B;
   if (n <= 0 || n > 0x7fffffffL) return hipErrorInvalidValue;
@@ -267,6 +266,14 @@ bool g16_rb2_supported(int C, int K, const int* dil) {
   return 256 - 2 * g16_rb2_halo(K, dil) >= 32;
 }
 
+ClRoute g16_rb2_route(const ClRb2Args& a) {
+  const int halo = g16_rb2_halo(a.K, a.dil);
+  // g16_chain's shapes: 64 channels, 8 waves x 32 columns; 32 channels, two 4-wave blocks of 256 columns per CU, or one
+  // 8-wave block of 512 columns when the halo would eat more than a quarter of a 256-column tile
+  const bool wide = a.C == 32 && 2 * halo > 64;
+  return ClRoute{VSP_CL_KERNEL_RB2, (wide ? 512 : 256) - 2 * halo, 0, wide ? 1 : 0};
+}
+
 hipError_t launch_g16_rb2(const ClRb2Args& a0, int B, hipStream_t s) {
   ClRb2Args a = a0;
   if (!g16_rb2_supported(a.C, a.K, a.dil) || a.T <= 0 || B <= 0 || (a.terms != 1 && a.terms != 3) || (a.x_bs & 3) ||
@@ -276,16 +283,15 @@ hipError_t launch_g16_rb2(const ClRb2Args& a0, int B, hipStream_t s) {
   // an utterance is addressed with 32-bit byte offsets (buffer descriptors: num_records, t * C * 4)
   if ((size_t)a.T * a.C * 4 >= (size_t)1 << 31) return hipErrorInvalidValue;
   a.halo = g16_rb2_halo(a.K, a.dil);
-  // g16_chain's shapes: 64 channels, 8 waves x 32 columns; 32 channels, two 4-wave blocks of 256 columns per CU, or one
-  // 8-wave block of 512 columns when the halo would eat more than a quarter of a 256-column tile
-  const bool wide = a.C == 32 && 2 * a.halo > 64;
+  const ClRoute r = g16_rb2_route(a);
+  const bool wide = r.variant == 1;
   // <NCH, NW, G, TERMS, NWV>
   if (a.terms == 1) {
-    if (a.C == 64) return launch_g16_rb2_tile<2, 2, 2, 1, 8>(a, B, s);
-    return wide ? launch_g16_rb2_tile<1, 4, 4, 1, 8>(a, B, s) : launch_g16_rb2_tile<1, 4, 2, 1, 4>(a, B, s);
+    if (a.C == 64) return launch_g16_rb2_tile<2, 2, 2, 1, 8>(a, B, s, r.tile_cols);
+    return wide ? launch_g16_rb2_tile<1, 4, 4, 1, 8>(a, B, s, r.tile_cols) : launch_g16_rb2_tile<1, 4, 2, 1, 4>(a, B, s, r.tile_cols);
   }
-  if (a.C == 64) return launch_g16_rb2_tile<2, 2, 2, 3, 8>(a, B, s);
-  return wide ? launch_g16_rb2_tile<1, 4, 4, 3, 8>(a, B, s) : launch_g16_rb2_tile<1, 4, 2, 3, 4>(a, B, s);
+  if (a.C == 64) return launch_g16_rb2_tile<2, 2, 2, 3, 8>(a, B, s, r.tile_cols);
+  return wide ? launch_g16_rb2_tile<1, 4, 4, 3, 8>(a, B, s, r.tile_cols) : launch_g16_rb2_tile<1, 4, 2, 3, 4>(a, B, s, r.tile_cols);
 }
 
 }  // namespace vsp

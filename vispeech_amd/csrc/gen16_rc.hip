@@ -407,15 +407,21 @@ bool g16_rc_supported(int C, int K, const int* dil, int np, int terms, int acc_p
   return true;
 }
 
+static int g16_rc_halo(int K, const int* dil, int np) {
+  int h = 0;
+  for (int p = 0; p < np; ++p) h += (dil[p] + 1) * ((K - 1) / 2);
+  return h;
+}
+int g16_rc_tile_cols(int K, const int* dil, int np) { return RC_BT - 2 * g16_rc_halo(K, dil, np); }
+
 hipError_t launch_g16_rc(const ClChainArgs& a0, int B, hipStream_t s) {
   ClChainArgs a = a0;
   if (!g16_rc_supported(a.C, a.K, a.dil, a.np, a.terms, a.acc_prev) || a.T <= 0 || B <= 0 || (a.x_bs & 3) || (a.o_bs & 3) ||
       (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15) || a.x == a.out ||
       (size_t)a.T * 128 >= (size_t)1 << 31)
     return hipErrorInvalidValue;
-  a.halo = 0;
-  for (int p = 0; p < a.np; ++p) a.halo += (a.dil[p] + 1) * ((a.K - 1) / 2);
-  const int R = RC_BT - 2 * a.halo;
+  a.halo = g16_rc_halo(a.K, a.dil, a.np);
+  const int R = g16_rc_tile_cols(a.K, a.dil, a.np);
   if (R < 32) return hipErrorInvalidValue;
   a.tiles = (a.T + R - 1) / R;
   if (B > 256) {                                  // (a tile cursor keeps the utterance in 8 bits: 256 utterances per launch)

@@ -444,13 +444,15 @@ bool g16_rw_supported(int C, int K, int dil, int terms) {
   return C == 32 && (K == 3 || K == 7 || K == 11) && dil >= 1 && (K - 1) * dil <= RW_MAXHALO && terms == 3;
 }
 
+int g16_rw_tile_cols(int K) { return RW_BT - (K - 1); }
+
 template <int K, bool ACC>
 static hipError_t launch_g16_rw_k(ClPairArgs a, int B, hipStream_t s) {
   auto kern = g16_rw<K, ACC>;
   static std::atomic<uint64_t> attr_done{0};
   hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), RW_LDS, attr_done);
   if (e != hipSuccess) return e;
-  constexpr int R2 = RW_BT - (K - 1);
+  const int R2 = g16_rw_tile_cols(K);
   a.tiles = (a.T + R2 - 1) / R2;
   if (B > 256) {                                // (a tile cursor keeps the utterance in 8 bits: 256 utterances per launch)
     for (int b0 = 0; b0 < B; b0 += 256) {

@@ -393,13 +393,15 @@ bool g16_rw64_supported(int C, int K, int dil, int terms) {
   return C == 64 && K == R6_K && dil >= 1 && dil <= R6_MAXDIL && terms == 3;
 }
 
+int g16_rw64_tile_cols() { return R6_BT - (R6_K - 1); }
+
 template <bool ACC>
 static hipError_t launch_g16_rw64_k(ClPairArgs a, int B, hipStream_t s) {
   auto kern = g16_rw64<ACC>;
   static std::atomic<uint64_t> attr_done{0};
   hipError_t e = set_max_dynamic_lds(reinterpret_cast<const void*>(kern), R6_LDS, attr_done);
   if (e != hipSuccess) return e;
-  constexpr int R2 = R6_BT - (R6_K - 1);
+  const int R2 = g16_rw64_tile_cols();
   a.tiles = (a.T + R2 - 1) / R2;
   if (B > 256) {                                // (a tile cursor keeps the utterance in 8 bits: 256 utterances per launch)
     for (int b0 = 0; b0 < B; b0 += 256) {

@@ -161,6 +161,12 @@ struct ClConvArgs {
   // utterance's own extent read as zero and are never stored: the tensor ENDS there for that utterance.  NULL = uniform.
   const int* glen; int g_in, g_store;
 };
+// The kernel a channels-last launcher takes for its arguments and the columns one tile of it stores
+// (include/vispeech_hip.h: VSP_CL_KERNEL_*, vsp_cl_launch_route; kernel == VSP_CL_KERNEL_NONE: the launcher answers
+// hipErrorInvalidValue).  The *_route functions below are pure host functions -- no HIP call; they read pointers as
+// flags and addresses only -- and the ONE place each launcher's decision ladder lives: the launcher switches on its route,
+// vsp_cl_block_ex (ops.hip) reports it to the tests.  A route does not repeat the launcher's argument checks.
+using ClRoute = vsp_cl_launch_route;
 constexpr int CL_IMG_PADF = 64, CL_IMG_PADB = 320;
 inline int cl_img_tpad(int T) { return T + CL_IMG_PADF + CL_IMG_PADB; }
 inline size_t cl_img_halfs(int C, int T) { return (size_t)C * 2 * cl_img_tpad(T); }   // per utterance
@@ -207,7 +213,11 @@ struct ClChainArgs {
 // launch_g16_chain routes there unless ClChainArgs::ring (VSP_CHAIN_RING=1) asks for the LDS-ring chain (bit-identical)
 bool g16_rc_supported(int C, int K, const int* dil, int np, int terms, int acc_prev);
 hipError_t launch_g16_rc(const ClChainArgs& a, int B, hipStream_t s);
+int g16_rc_tile_cols(int K, const int* dil, int np);        // RC_BT - 2 * halo
 bool g16_chain_supported(int C, int K, const int* dil, int np);
+// RC, or the LDS-ring tile: CHAIN (32 channels: two 4-wave blocks of 256 columns per CU; 64: 256; 128: 128) or CHAIN_WIDE
+// (32 channels, one 8-wave block of 512 columns); tile_cols = the block's columns - 2 * halo
+ClRoute g16_chain_route(const ClChainArgs& a);
 hipError_t launch_g16_chain(const ClChainArgs& a, int B, hipStream_t s);
 // Fused ResBlock2 on channels-last activations (gen16_rb2.hip, round 7): both convolutions of the block in one launch,
 //   y = x + conv_a(lrelu(x), dil[0]) + b_a,   out = y + conv_b(lrelu(y), dil[1]) + b_b  [+ out] [/ div];  x != out.
@@ -224,7 +234,12 @@ struct ClRb2Args {
   const int* glen; int grate;               // ragged batch (see ClConvArgs): utterance b's T = glen[b] * grate; NULL = uniform
 };
 bool g16_rb2_supported(int C, int K, const int* dil);
+ClRoute g16_rb2_route(const ClRb2Args& a);                  // RB2; variant 1 = the 512-column block; tile_cols = columns - 2 * halo
 hipError_t launch_g16_rb2(const ClRb2Args& a, int B, hipStream_t s);
+// C16 (16 -> 16), UPS (the streaming up-convolutions), PIPE, CONV_IMG or CONV with the row tile in `rows` (terms 3: chosen
+// from the grid size B * ceil(Nq / 256)); variant 1 = the image-only epilogue through the LDS.  Every tile stores 256 columns
+// (UPS: 16 input times; C16: see g16_c16_route).
+ClRoute g16_conv_route(const ClConvArgs& a, int B);
 hipError_t launch_g16_conv(const ClConvArgs& a, int B, hipStream_t s);
 // The 16-channel last stage of a five-stage generator (gen16_c16.hip): a SEQUENCE of 1 .. 6 convolutions 16 -> 16 of one
 // channels-last tensor in one launch.  Step i convolves the leaky-relu of its input with w[i] at dilation dil[i]; its result
@@ -246,6 +261,7 @@ struct ClC16Args {
 };
 constexpr int G16_C16_BT = 512;             // columns per block; a launch stores G16_C16_BT - 2 * sum_i (K - 1) dil[i] / 2 of them
 bool g16_c16_supported(int K, const int* dil, int nsteps);
+ClRoute g16_c16_route(const ClC16Args& a);                  // C16; tile_cols = G16_C16_BT - 2 * halo
 hipError_t launch_g16_c16(const ClC16Args& a, int B, hipStream_t s);
 // the step lists (cl_args.h, cl_c16_steps) of np pairs of a ResBlock1 and of a ResBlock2
 bool g16_c16_rb1_supported(int K, const int* dil, int np);
@@ -261,16 +277,21 @@ inline bool cl_is_c16(int Cout, int Cin, int phases) { return Cout == 16 && Cin 
 bool g16_pipe_supported(const ClConvArgs& a);
 hipError_t launch_g16_pipe(const ClConvArgs& a, int B, hipStream_t s);
 bool g16_pair_supported(int C, int K, int dil);
+// PP (128 channels), RW, RW64, or the LDS-ring tile PAIR (variant = waves per block); tile_cols = conv1's columns - (K - 1)
+ClRoute g16_pair_route(const ClPairArgs& a);
 hipError_t launch_g16_pair(const ClPairArgs& a, int B, hipStream_t s);
 // the same pair with the weights held in registers by persistent blocks (gen16_rw.hip: 32 channels, kernel 7 / 11);
 // launch_g16_pair routes there unless ClPairArgs::ring (VSP_PAIR=ring) asks for the LDS-ring kernel (second implementation, bit-identical)
 bool g16_rw_supported(int C, int K, int dil, int terms);
+int g16_rw_tile_cols(int K);                                // RW_BT - (K - 1)
 hipError_t launch_g16_rw(const ClPairArgs& a, int B, hipStream_t s);
 // ... and the kernel-3 pairs of the 64-channel stage (gen16_rw64.hip, round 5: two row halves x two column halves per role)
 bool g16_rw64_supported(int C, int K, int dil, int terms);
+int g16_rw64_tile_cols();                                   // R6_BT - (R6_K - 1)
 hipError_t launch_g16_rw64(const ClPairArgs& a, int B, hipStream_t s);
 // the pair of the 128-channel stage on the ping-pong tile, kernel 3 / 7 (gen16_pp.hip); VSP_PP=0 (read per context): two launches (bit-identical)
 bool g16_pp_supported(int C, int K, int dil, int terms);
+int g16_pp_tile_cols(int K);                                // 192 - (K - 1)
 hipError_t launch_g16_pp(const ClPairArgs& a, int B, hipStream_t s);
 size_t packed_g16_halfs(int rows, int Cin, int K);
 void pack_g16_weights(uint16_t* dst, int rows, int Cin, int K, const float* dense /* [rows][Cin][K] */);

@@ -1,10 +1,12 @@
 // Stand-alone operators of the C-ABI (include/vispeech_hip.h): one convolution, ResBlock, up-convolution or attention on the
 // caller's tensors with host weights, no context -- what tests/test_cl_ops.py, test_c16_ops.py, test_resblock2_ops.py,
-// test_upsample_ops.py, test_attention_ops.py, test_frame_conv_epilogue.py and test_conv_form_host.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
+// test_cl_block_ops.py, test_cl_block_route_host.py, test_upsample_ops.py, test_attention_ops.py, test_frame_conv_epilogue.py
+// and test_conv_form_host.py drive.  The channels-last ones fill their launch arguments with the builders the model's schedule
 // uses (cl_args.h).  Every call allocates, uploads and synchronises: test and measurement entry points, not a hot path.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "kernels.h"
@@ -65,6 +67,170 @@ hipError_t upload_emb(const float* emb_k_host, const float* emb_v_host, int wind
   if (e == hipSuccess) e = hipMemcpyAsync(ev.p, emb_v_host, bytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);     // (pageable host memory: the caller's arrays may go after the call)
   return e;
+}
+// device int32 lengths [B] of a ragged channels-last batch: utterance b ends after lengths[b] * grate columns, 1 <= lengths[b]
+// and lengths[b] * grate <= T (a zero length is refused: the persistent kernels' cursors step to t0 = 0 of the next utterance
+// and clamp reads to row T - 1; the generator's plans never produce one)
+int check_glen(const int32_t* lengths, int grate, int B, int T, hipStream_t s) {
+  if (!lengths) return VSP_OK;
+  std::vector<int32_t> len(B);
+  hipError_t e = hipMemcpyAsync(len.data(), lengths, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return op_rc(e);
+  for (int32_t l : len)
+    if (l < 1 || (long)l * grate > T) return VSP_ERR_ARG;
+  return VSP_OK;
+}
+
+// the descriptor of vsp_cl_resblock / vsp_cl_resblock2: no accumulate, no divide, a uniform batch, the kernel-choice flags
+// from the environment (read per call: the test API has no context)
+vsp_cl_block_desc cl_block_plain(int kind, int mode, int B, int T, int C, int K, int n_pairs, int terms, const int* dilations,
+                                 const float* x, float* out, const float* const* w_host, const float* const* bias_host) {
+  vsp_cl_block_desc d;
+  std::memset(&d, 0, sizeof d);
+  d.kind = kind; d.mode = mode; d.B = B; d.T = T; d.C = C; d.K = K; d.n_pairs = n_pairs; d.terms = terms;
+  d.dilations = dilations; d.x = x; d.out = out; d.w = w_host; d.bias = bias_host;
+  d.grate = 1; d.div = 1.f;
+  if (const char* ev = getenv("VSP_PAIR")) d.ring = !strcmp(ev, "ring");
+  if (const char* ev = getenv("VSP_RW64")) d.rw64 = atoi(ev) != 0;
+  if (const char* ev = getenv("VSP_CHAIN_RING")) d.chain_ring = atoi(ev) != 0;
+  return d;
+}
+
+// vsp_cl_block_ex (include/vispeech_hip.h).  One sequence builds every launch's arguments, asks the launcher's route
+// function which kernel they take, and -- unless plan_only -- launches: the report and the run cannot disagree.
+int cl_block_run(void* stream, const vsp_cl_block_desc& d, vsp_cl_block_route* route_out) {
+  const int B = d.B, T = d.T, C = d.C, K = d.K, mode = d.mode, terms = d.terms;
+  const bool rb2 = d.kind == 2, plan = d.plan_only != 0;
+  if (d.kind != 1 && d.kind != 2) return VSP_ERR_ARG;
+  const int n_pairs = rb2 ? 1 : d.n_pairs, nconv = rb2 ? 2 : 2 * n_pairs;
+  if (!d.x || !d.w || !d.bias || !d.dilations || !d.out || d.x == d.out || B < 0 || T < 0 || n_pairs < 1 || n_pairs > 8 ||
+      mode < 0 || mode > (rb2 ? 1 : 2) || (terms != 1 && terms != 3) || (rb2 && (!d.w[0] || !d.w[1])) || !(d.div != 0.f) ||
+      d.grate < 1 || (plan && !route_out))
+    return VSP_ERR_ARG;
+  const int* dil = d.dilations;
+  const bool c16 = C == 16;                              // (g16_c16: mode 1 = a pair's two steps / the ResBlock2, mode 2 = the whole ResBlock1)
+  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
+  if (rb2) {
+    for (int c = 0; c < 2; ++c)
+      if (dil[c] < 1 || (K - 1) * dil[c] > 64) return VSP_ERR_UNSUPPORTED;
+    if (mode == 1 && (c16 ? !g16_c16_rb2_supported(K, dil) : !g16_rb2_supported(C, K, dil))) return VSP_ERR_UNSUPPORTED;
+  } else {
+    for (int p = 0; p < n_pairs; ++p) {
+      if (dil[p] < 1 || (K - 1) * dil[p] > 64) return VSP_ERR_UNSUPPORTED;
+      if (mode == 1 && (c16 ? !g16_c16_rb1_supported(K, dil + p, 1)
+                            : !g16_pair_supported(C, K, dil[p]) && !g16_pp_supported(C, K, dil[p], terms)))
+        return VSP_ERR_UNSUPPORTED;
+      if (!d.w[2 * p] || !d.w[2 * p + 1]) return VSP_ERR_ARG;
+    }
+    if (mode == 2 && (n_pairs > 3 || (c16 ? !g16_c16_rb1_supported(K, dil, n_pairs) : !g16_chain_supported(C, K, dil, n_pairs))))
+      return VSP_ERR_UNSUPPORTED;
+  }
+  vsp_cl_block_route rt;
+  std::memset(&rt, 0, sizeof rt);
+  if (route_out) *route_out = rt;
+  if (B == 0 || T == 0) return VSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (!plan)
+    if (int rc = check_glen(d.lengths, d.grate, B, T, s); rc != VSP_OK) return rc;
+  const bool fused1 = mode == 2 || (rb2 && mode == 1);   // the whole block in one launch: no intermediate tensor
+  const bool image = !rb2 && mode == 0 && terms == 3 && K >= 3 && !c16 && !d.no_image;   // the pair's intermediate as an operand image
+  // a plan dereferences nothing: the intermediates are then distinct aligned addresses that only answer "is there one"
+  alignas(16) static float plan_buf[4][4];
+  std::vector<DevBuf> w(nconv), bias(nconv);
+  DevBuf t1, ya, yb, timg;
+  hipError_t e = hipSuccess;
+  if (!plan) {
+    for (int i = 0; i < nconv && e == hipSuccess; ++i) e = upload_cl_conv(d.w[i], d.bias[i], C, C, K, w[i], bias[i], s);
+    const size_t el = (size_t)B * T * C;
+    if (e == hipSuccess && !fused1) e = t1.alloc(el * 4);
+    if (e == hipSuccess && !fused1 && !rb2) e = ya.alloc(el * 4);
+    if (e == hipSuccess && !fused1 && !rb2) e = yb.alloc(el * 4);
+    if (e == hipSuccess && image) e = timg.alloc((size_t)B * cl_img_halfs(C, T) * 2);
+    // Every intermediate starts as NaN (all-ones words, fp32 and f16 alike): the generator's workspace holds whatever the
+    // last call left, so a launch that reads a row no launch before it wrote -- behind a ragged end, in an image's pads --
+    // must show in the result instead of meeting fresh, zeroed memory.
+    const std::pair<DevBuf*, size_t> scratch[] = {{&t1, el * 4}, {&ya, el * 4}, {&yb, el * 4}, {&timg, (size_t)B * cl_img_halfs(C, T) * 2}};
+    for (const auto& sc : scratch)
+      if (e == hipSuccess && sc.first->p) e = hipMemsetAsync(sc.first->p, 0xFF, sc.second, s);
+    if (e == hipSuccess && image) e = launch_cl_img_zero_pads(static_cast<uint16_t*>(timg.p), B, C, T, s, d.lengths, d.grate);
+    if (e != hipSuccess) return op_rc(e);
+  }
+  float* const t1p = plan ? plan_buf[0] : static_cast<float*>(t1.p);
+  float* const yap = plan ? plan_buf[1] : static_cast<float*>(ya.p);
+  float* const ybp = plan ? plan_buf[2] : static_cast<float*>(yb.p);
+  uint16_t* const img = !image ? nullptr : plan ? reinterpret_cast<uint16_t*>(plan_buf[3]) : static_cast<uint16_t*>(timg.p);
+  std::vector<ClW> conv(nconv);                         // (execution order: conv1, conv2 of pair 0, 1, ..; conv_a, conv_b)
+  for (int i = 0; i < nconv; ++i) conv[i] = cw(w[i], bias[i]);
+  // One launch: its route into the report, then the launch itself.  `last`: the block's last launch carries the
+  // accumulate / divide epilogue (where run_generator_cl puts them); every launch carries the ragged extent.
+  auto step = [&](const ClRoute& r, auto launch) -> hipError_t {
+    if (r.kernel == VSP_CL_KERNEL_NONE || rt.n >= VSP_CL_BLOCK_MAX_LAUNCHES) return hipErrorInvalidValue;
+    rt.launch[rt.n++] = r;
+    return plan ? hipSuccess : launch();
+  };
+  auto one_conv = [&](ClConvArgs a, bool last) {
+    if (last) { a.acc_prev = d.acc_prev ? 1 : 0; a.div = d.div; }
+    a.glen = d.lengths; a.g_in = d.grate; a.g_store = d.grate;
+    return step(g16_conv_route(a, B), [&] { return launch_g16_conv(a, B, s); });
+  };
+  // ResBlock1 pairs [p0, p0 + np), or the ResBlock2, as one launch: g16_c16 at 16 channels, else g16_rb2, g16_pair
+  // (as_pair) or g16_chain
+  auto fused = [&](const float* xin, float* yout, int p0, int np, bool as_pair, bool last) {
+    auto fin = [&](auto& a) {
+      if (last) { a.acc_prev = d.acc_prev ? 1 : 0; a.div = d.div; }
+      a.glen = d.lengths; a.grate = d.grate;
+    };
+    if (c16) {
+      ClC16Args a = cl_c16_args(d.kind, &conv[2 * p0], K, dil + p0, np, xin, yout, T, terms);
+      fin(a);
+      return step(g16_c16_route(a), [&] { return launch_g16_c16(a, B, s); });
+    }
+    if (rb2) {
+      ClRb2Args a = cl_rb2_args(conv.data(), C, K, dil, xin, yout, T, terms);
+      fin(a);
+      return step(g16_rb2_route(a), [&] { return launch_g16_rb2(a, B, s); });
+    }
+    if (as_pair) {
+      ClPairArgs a = cl_pair_args(&conv[2 * p0], C, K, dil[p0], xin, yout, T, terms);
+      a.ring = d.ring ? 1 : 0; a.rw64 = d.rw64 ? 1 : 0;
+      fin(a);
+      return step(g16_pair_route(a), [&] { return launch_g16_pair(a, B, s); });
+    }
+    ClChainArgs a = cl_chain_args(&conv[2 * p0], C, K, dil + p0, np, xin, yout, T, terms);
+    a.ring = d.chain_ring ? 1 : 0;
+    fin(a);
+    return step(g16_chain_route(a), [&] { return launch_g16_chain(a, B, s); });
+  };
+  if (fused1) {
+    e = fused(d.x, d.out, 0, n_pairs, false, true);
+  } else if (rb2) {
+    // one g16_conv per convolution: y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y))
+    e = one_conv(cl_conv_args(conv[0], C, C, K, dil[0], d.x, T, CL_LRELU_SLOPE, d.x, t1p, terms), false);
+    if (e == hipSuccess) e = one_conv(cl_conv_args(conv[1], C, C, K, dil[1], t1p, T, CL_LRELU_SLOPE, t1p, d.out, terms), true);
+  } else {
+    // the running y ping-pongs between two buffers (a tile reads halo rows its neighbour writes)
+    const float* yin = d.x;
+    for (int p = 0; p < n_pairs && e == hipSuccess; ++p) {
+      const bool last = p == n_pairs - 1;
+      float* yout = last ? d.out : ((p & 1) ? ybp : yap);
+      if (mode == 1) {
+        e = fused(yin, yout, p, 1, true, last);
+      } else {
+        // one launch per convolution; the intermediate as an operand image where the kernels take one (terms 3, K >= 3):
+        // the path the >= 128-channel stages of the generator run
+        ClConvArgs a1 = cl_conv_args(conv[2 * p], C, C, K, dil[p], yin, T, CL_LRELU_SLOPE, nullptr, img ? nullptr : t1p, terms);
+        ClConvArgs a2 = cl_conv_args(conv[2 * p + 1], C, C, K, 1, t1p, T, CL_LRELU_SLOPE, yin, yout, terms);
+        a1.o_img = img; a2.x_img = img;
+        e = one_conv(a1, false);
+        if (e == hipSuccess) e = one_conv(a2, last);
+      }
+      yin = yout;
+    }
+  }
+  if (route_out) *route_out = rt;
+  if (e == hipSuccess && !plan) e = hipStreamSynchronize(s);
+  return op_rc(e);
 }
 }  // namespace
 
@@ -274,109 +440,42 @@ int vsp_conv1d_ex(void* stream, const vsp_conv1d_desc* dp, vsp_conv_form* form_o
   return op_rc(e);
 }
 
+int vsp_cl_block_ex(void* stream, const vsp_cl_block_desc* d, vsp_cl_block_route* route) {
+  if (!d) return VSP_ERR_ARG;
+  return cl_block_run(stream, *d, route);
+}
+
 int vsp_cl_resblock(void* stream, int B, int T, int C, int K, int n_pairs, const int* dilations, const float* x,
                     const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
-  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || n_pairs < 1 || n_pairs > 8 ||
-      mode < 0 || mode > 2 || (terms != 1 && terms != 3))
-    return VSP_ERR_ARG;
-  const bool c16 = C == 16;                              // (g16_c16: mode 1 = a pair's two steps, mode 2 = the whole block)
-  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
-  for (int p = 0; p < n_pairs; ++p) {
-    if (dilations[p] < 1 || (K - 1) * dilations[p] > 64) return VSP_ERR_UNSUPPORTED;
-    if (mode == 1 && (c16 ? !g16_c16_rb1_supported(K, dilations + p, 1)
-                          : !g16_pair_supported(C, K, dilations[p]) && !g16_pp_supported(C, K, dilations[p], terms)))
-      return VSP_ERR_UNSUPPORTED;
-    if (!w_host[2 * p] || !w_host[2 * p + 1]) return VSP_ERR_ARG;
-  }
-  if (mode == 2 && (n_pairs > 3 || (c16 ? !g16_c16_rb1_supported(K, dilations, n_pairs) : !g16_chain_supported(C, K, dilations, n_pairs))))
-    return VSP_ERR_UNSUPPORTED;
-  if (B == 0 || T == 0) return VSP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<DevBuf> w(2 * n_pairs), bias(2 * n_pairs);
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 2 * n_pairs && e == hipSuccess; ++i) e = upload_cl_conv(w_host[i], bias_host[i], C, C, K, w[i], bias[i], s);
-  const size_t el = (size_t)B * T * C;
-  DevBuf t1, ya, yb;
-  if (e == hipSuccess && mode != 2) e = t1.alloc(el * 4);
-  if (e == hipSuccess && mode != 2) e = ya.alloc(el * 4);
-  if (e == hipSuccess && mode != 2) e = yb.alloc(el * 4);
-  DevBuf timg;
-  if (e == hipSuccess && mode == 0 && terms == 3 && K >= 3 && !c16) {
-    e = timg.alloc((size_t)B * cl_img_halfs(C, T) * 2);
-    if (e == hipSuccess) e = launch_cl_img_zero_pads(static_cast<uint16_t*>(timg.p), B, C, T, s);
-  }
-  if (e != hipSuccess) return op_rc(e);
-  std::vector<ClW> conv(2 * n_pairs);                   // (execution order: conv1, conv2 of pair 0, 1, ..)
-  for (int i = 0; i < 2 * n_pairs; ++i) conv[i] = cw(w[i], bias[i]);
-  // pairs [p0, p0 + np) as one launch: g16_c16 at 16 channels, else g16_pair (as_pair) or g16_chain
-  auto fused = [&](const float* xin, float* yout, int p0, int np, bool as_pair) {
-    if (c16) return launch_g16_c16(cl_c16_args(1, &conv[2 * p0], K, dilations + p0, np, xin, yout, T, terms), B, s);
-    if (as_pair) {
-      ClPairArgs a = cl_pair_args(&conv[2 * p0], C, K, dilations[p0], xin, yout, T, terms);
-      if (const char* ev = getenv("VSP_PAIR")) a.ring = !strcmp(ev, "ring");     // (read per call: the test API has no context)
-      if (const char* ev = getenv("VSP_RW64")) a.rw64 = atoi(ev) != 0;
-      return launch_g16_pair(a, B, s);
-    }
-    ClChainArgs a = cl_chain_args(&conv[2 * p0], C, K, dilations + p0, np, xin, yout, T, terms);
-    if (const char* ev = getenv("VSP_CHAIN_RING")) a.ring = atoi(ev) != 0;
-    return launch_g16_chain(a, B, s);
-  };
-  if (mode == 2) {
-    e = fused(x, out, 0, n_pairs, false);
-  } else {
-    // the running y ping-pongs between two buffers (a tile reads halo rows its neighbour writes)
-    const float* yin = x;
-    for (int p = 0; p < n_pairs && e == hipSuccess; ++p) {
-      float* yout = p == n_pairs - 1 ? out : static_cast<float*>((p & 1) ? yb.p : ya.p);
-      if (mode == 1) {
-        e = fused(yin, yout, p, 1, true);
-      } else {
-        // one launch per convolution; the intermediate as an operand image where the kernels take one (terms 3, K >= 3):
-        // the path the >= 128-channel stages of the generator run
-        uint16_t* const img = static_cast<uint16_t*>(timg.p);   // (NULL where none was allocated above)
-        ClConvArgs a1 = cl_conv_args(conv[2 * p], C, C, K, dilations[p], yin, T, CL_LRELU_SLOPE, nullptr,
-                                     img ? nullptr : static_cast<float*>(t1.p), terms);
-        ClConvArgs a2 = cl_conv_args(conv[2 * p + 1], C, C, K, 1, static_cast<const float*>(t1.p), T, CL_LRELU_SLOPE, yin, yout, terms);
-        a1.o_img = img; a2.x_img = img;
-        e = launch_g16_conv(a1, B, s);
-        if (e == hipSuccess) e = launch_g16_conv(a2, B, s);
-      }
-      yin = yout;
-    }
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return op_rc(e);
+  if (n_pairs < 1 || n_pairs > 8) return VSP_ERR_ARG;
+  vsp_cl_block_desc d = cl_block_plain(1, mode, B, T, C, K, n_pairs, terms, dilations, x, out, w_host, bias_host);
+  return cl_block_run(stream, d, nullptr);
 }
 
 int vsp_cl_resblock2(void* stream, int B, int T, int C, int K, const int* dilations, const float* x,
                      const float* const* w_host, const float* const* bias_host, int mode, int terms, float* out) {
-  if (!x || !w_host || !bias_host || !dilations || !out || x == out || B < 0 || T < 0 || mode < 0 || mode > 1 ||
-      (terms != 1 && terms != 3) || !w_host[0] || !w_host[1])
-    return VSP_ERR_ARG;
-  const bool c16 = C == 16;                              // (g16_c16: two steps with a residual each)
-  if (C <= 0 || (!c16 && C % 32) || K < 1 || !(K & 1) || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
-  for (int c = 0; c < 2; ++c)
-    if (dilations[c] < 1 || (K - 1) * dilations[c] > 64) return VSP_ERR_UNSUPPORTED;
-  if (mode == 1 && (c16 ? !g16_c16_rb2_supported(K, dilations) : !g16_rb2_supported(C, K, dilations))) return VSP_ERR_UNSUPPORTED;
+  vsp_cl_block_desc d = cl_block_plain(2, mode, B, T, C, K, 2, terms, dilations, x, out, w_host, bias_host);
+  return cl_block_run(stream, d, nullptr);
+}
+
+int vsp_cl_conv_post(void* stream, int B, int T, int C, int K, const float* x, const float* w_host, float slope, float unscale,
+                     const int32_t* lengths, int grate, float* out) {
+  if (!x || !w_host || !out || B < 0 || T < 0 || grate < 1) return VSP_ERR_ARG;
+  if ((C != 16 && C != 32 && C != 64) || K < 1 || !(K & 1) || K > 7 || (size_t)T * C * 4 >= (size_t)1 << 31) return VSP_ERR_UNSUPPORTED;
   if (B == 0 || T == 0) return VSP_OK;
   hipStream_t s = (hipStream_t)stream;
-  DevBuf w[2], bias[2];
-  hipError_t e = hipSuccess;
-  for (int c = 0; c < 2 && e == hipSuccess; ++c) e = upload_cl_conv(w_host[c], bias_host[c], C, C, K, w[c], bias[c], s);
-  DevBuf y;
-  if (e == hipSuccess && mode == 0) e = y.alloc((size_t)B * T * C * 4);
-  if (e != hipSuccess) return op_rc(e);
-  const ClW conv[2] = {cw(w[0], bias[0]), cw(w[1], bias[1])};
-  if (mode == 1 && c16) {
-    e = launch_g16_c16(cl_c16_args(2, conv, K, dilations, 2, x, out, T, terms), B, s);
-  } else if (mode == 1) {
-    e = launch_g16_rb2(cl_rb2_args(conv, C, K, dilations, x, out, T, terms), B, s);
-  } else {
-    // one g16_conv per convolution: y = x + conv_a(lrelu(x)), out = y + conv_b(lrelu(y))
-    float* yp = static_cast<float*>(y.p);
-    e = launch_g16_conv(cl_conv_args(conv[0], C, C, K, dilations[0], x, T, CL_LRELU_SLOPE, x, yp, terms), B, s);
-    if (e == hipSuccess) e = launch_g16_conv(cl_conv_args(conv[1], C, C, K, dilations[1], yp, T, CL_LRELU_SLOPE, yp, out, terms), B, s);
-  }
+  if (int rc = check_glen(lengths, grate, B, T, s); rc != VSP_OK) return rc;
+  // the model's tap-major image [K][C] of the reference's [1][C][K] (weights.cpp: post_wt)
+  std::vector<float> wt((size_t)K * C);
+  for (int c = 0; c < C; ++c)
+    for (int j = 0; j < K; ++j) wt[(size_t)j * C + c] = w_host[(size_t)c * K + j];
+  DevBuf w;
+  hipError_t e = w.alloc(wt.size() * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);     // (pageable host memory: the vector dies with this frame)
+  if (e == hipSuccess)
+    e = launch_conv_post_cl(x, (long)T * C, C, static_cast<const float*>(w.p), C, K, slope, out, T, B, T, s, lengths, grate, unscale,
+                            nullptr);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return op_rc(e);
 }
