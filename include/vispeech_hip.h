@@ -1144,6 +1144,66 @@ int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, in
               const int64_t* frames_host, const int64_t* states_host, const int32_t* cum_dur_host, const int64_t* lengths_host,
               const vsp_align_params* params, int32_t* states, int32_t* durations, void* workspace, int64_t workspace_bytes);
 
+/* ---- loudness (round 21, ABI 7, additive) ---------------------------- */
+/* The integrated loudness of ITU-R BS.1770-4 / EBU R 128 per row of a ragged batch of mono float32 recordings, a gain per
+ * row derived from it and applied, all on the device.  The specification is this project's own, restated in fp64 in
+ * tests/loudness_ref.py.  Row b is audio[b][0 .. n_b) at sample_rate = fs, 8000 <= fs <= 192000 (an argument: the
+ * services pass the model's rate).
+ *   K-weighting  two biquads in cascade, designed on the host in double for fs, both from zero state at the row's sample 0.
+ *                Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs),
+ *                Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2; b = [Vh + Vb K/Q + K^2, 2 (K^2 - Vh),
+ *                Vh - Vb K/Q + K^2] / a0, a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0].  High-pass: f0 = 38.13547087602444,
+ *                Q = 0.5003270373238773, b = [1, -2, 1], a from its own K as above.  At 48 kHz these are BS.1770's tables.
+ *   segments     h = (fs + 5) / 10 in integers (100 ms); S = ceil(n / h); seg[s] = the sum of y^2 over the filtered row's
+ *                samples [s h, min((s + 1) h, n)), a double.  States and sums are carried in double.
+ *   blocks       n >= 4 h: NB = n / h - 3 (complete 400 ms blocks, 75 % overlap), E_j = ((seg[j] + seg[j+1]) + seg[j+2]) +
+ *                seg[j+3], D = 4 h.  n < 4 h: NB = 1, E_0 = the row's segments summed ascending, D = n.
+ *   gates        in double, means over ascending j.  Block j passes the absolute gate iff E_j / D > Z_abs = 10^((-70 + 0.691) /
+ *                10); mean_abs = the mean E_j of those; j is kept iff it passes and 10 E_j > mean_abs (strict: the relative
+ *                gate at -10 LU).  L = -0.691 + 10 log10(mean of the kept E_j / D) as float32; -inf where none is kept.
+ *                blocks[b] = (NB, kept); peak[b] = max |x| (float32, exact; the SAMPLE peak).
+ *   gain         g = 10^((target_lufs - L) / 20), then min(g, 10^(max_gain_db / 20)), then min(g, peak_ceiling / peak) where
+ *                peak > 0; g = 1 exactly for a row with L = -inf and for a row whose target_lufs is NaN ("leave this row
+ *                alone": apply neither reads nor writes it).
+ *   apply        out[b][i] = fl32(g_b x[b][i]) for i < n_b, in place or into another buffer.
+ * Nothing at or behind n_b is read or written (a NaN there changes no output bit); a row's bits do not depend on the rows it
+ * is batched with; seg holds exact zeros behind a row's segments.  Refused with VSP_ERR_ARG on the host before any launch,
+ * naming the row: n_b < 1 or > L_max (the gate: > S_max h), fs out of range, peak_ceiling <= 0, a negative or NaN
+ * max_gain_db; a workspace too small is VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload of its rows (20
+ * bytes a row: the lengths and the params, pageable host memory as the prosody calls'), allocates nothing and does not
+ * synchronise.  n_samples_host, params_host: HOST arrays [B].
+ * Not computed: true peak (sample peak only), stereo and channel weights, momentary and short-term loudness, loudness range. */
+typedef struct vsp_loudness_params {
+  float target_lufs, peak_ceiling, max_gain_db;
+} vsp_loudness_params;
+/* coef[10] = the shelf's b0 b1 b2 a1 a2, then the high-pass's.  Host only. */
+int vsp_loudness_kweighting(int sample_rate, double* coef);
+/* S(n) = ceil(n / h), host only (VSP_ERR_ARG as a negative count: n outside [1, 2^30], fs out of range). */
+int64_t vsp_loudness_segments_count(int64_t n_samples, int sample_rate);
+/* Workspace of any call below for B rows of up to L_max samples (VSP_ERR_ARG as a negative size); monotone in B and L_max. */
+int64_t vsp_loudness_workspace_bytes(int B, int64_t L_max, int sample_rate);
+/* audio [B][audio_stride] (device, audio_stride >= L_max) to seg [B][S_max] double, S_max = S(L_max), and peak [B] float32
+ * (device).  Three launches: segment end states from zero (one wave per row and segment), the states carried along each row
+ * (one wave per row), segment energies from the true states. */
+int vsp_loudness_segments(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                          const int64_t* n_samples_host, double* seg, float* peak, void* workspace, int64_t workspace_bytes);
+/* The gates alone, a stand-alone operator on ANY double table seg [B][S_max] (device) with the rows' n_samples_host
+ * (1 <= n_b <= S_max h): lufs [B] float32, blocks [B][2] int32.  With params_host (else NULL) also gains [B] float32 from
+ * peak [B] (device).  One launch, one wave per row. */
+int vsp_loudness_gate(vsp_ctx* ctx, void* stream, int B, int S_max, int sample_rate, const double* seg, const int64_t* n_samples_host,
+                      const float* peak, const vsp_loudness_params* params_host, float* lufs, int32_t* blocks, float* gains,
+                      void* workspace, int64_t workspace_bytes);
+/* out = gains[b] in over each row's own samples; in == out is allowed.  params_host (or NULL: every row): a row whose
+ * target_lufs is NaN is neither read nor written.  One launch; 16-byte accesses where both rows are 16-byte aligned. */
+int vsp_loudness_apply(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float* in, int64_t in_stride, float* out,
+                       int64_t out_stride, const int64_t* n_samples_host, const float* gains, const vsp_loudness_params* params_host,
+                       void* workspace, int64_t workspace_bytes);
+/* All three behind one upload: segments, gate and gains, apply (five launches); seg lives in the workspace; lufs, peak and
+ * gains [B] stay on the device, so no host read sits between measuring and applying.  blocks may be NULL. */
+int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                           float* out, int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_params* params_host,
+                           float* lufs, float* peak, float* gains, int32_t* blocks, void* workspace, int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

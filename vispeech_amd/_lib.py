@@ -162,7 +162,13 @@ class VspAlignParams(C.Structure):
     _fields_ = [("max_advance", C.c_int32), ("stay_cost", C.c_float), ("skip_cost", C.c_float)]
 
 
-PROSODY_FS, PROSODY_NFFT = 44100, 1280                              # VSP_PROSODY_*
+class VspLoudnessParams(C.Structure):
+    """``vsp_loudness_params``: one row's target (LUFS; NaN: leave the row alone), sample-peak ceiling and largest gain (dB)."""
+    _fields_ = [("target_lufs", C.c_float), ("peak_ceiling", C.c_float), ("max_gain_db", C.c_float)]
+
+
+LOUDNESS_FS_MIN, LOUDNESS_FS_MAX = 8000, 192000                      # the sample rates the loudness calls take
+PROSODY_FS, PROSODY_NFFT = 44100, 1280                             # VSP_PROSODY_*
 PROSODY_MAX_CANDIDATES, PROSODY_SLOTS = 15, 16                       # VSP_PROSODY_MAX_CANDIDATES; floats of a frame in a table
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
 OUTPUT_RATES_MAX = 8
@@ -305,6 +311,14 @@ SIGNATURES = {
     "vsp_align_durations": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I64), C.POINTER(C.c_int32), C.POINTER(_I64), _P, _P, _I64]),
     "vsp_align": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int32),
                        C.POINTER(_I64), C.POINTER(VspAlignParams), _P, _P, _P, _I64]),
+    "vsp_loudness_kweighting": (_I, [_I, C.POINTER(C.c_double)]),
+    "vsp_loudness_segments_count": (_I64, [_I64, _I]),
+    "vsp_loudness_workspace_bytes": (_I64, [_I, _I64, _I]),
+    "vsp_loudness_segments": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), _P, _P, _P, _I64]),
+    "vsp_loudness_gate": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I64), _P, C.POINTER(VspLoudnessParams), _P, _P, _P, _P, _I64]),
+    "vsp_loudness_apply": (_I, [_P, _P, _I, _I64, _P, _I64, _P, _I64, C.POINTER(_I64), _P, C.POINTER(VspLoudnessParams), _P, _I64]),
+    "vsp_loudness_normalize": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(VspLoudnessParams), _P, _P,
+                                    _P, _P, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

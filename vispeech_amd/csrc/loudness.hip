@@ -1,0 +1,613 @@
+// Loudness (include/vispeech_hip.h, "loudness"): the integrated loudness of ITU-R BS.1770-4 / EBU R 128
+// per row of a ragged batch of mono float32 recordings, a gain per row from it, and the gain applied -- all on the device,
+// nothing read back between measuring and applying.  The specification is this project's own (fp64 restatement in
+// tests/loudness_ref.py).  Row b is audio[b][0 .. n_b); nothing at or behind n_b is read, and a row's result is a function of
+// the row alone: every partition below follows the row's own n_b and the rate's segment h, never L_max.
+//
+// K-weighting is two cascaded biquads, a linear recurrence over the whole row with a 4-value state s (transposed direct
+// form II: two values a biquad): s' = M s + x v.  Its poles sit at radius 0.9946 at 44.1 kHz, so nothing may be truncated;
+// instead the row is cut into its 100 ms segments and a segment into 64 lane runs of r = ceil(h / 64) samples, and states are
+// carried across the cuts exactly: the end state of a chunk of k samples is M^k s_in + e, e its end state from zero.  The
+// powers needed -- M^r 2^i for the lane scan, M^(h mod r) for a segment's partial lane, M^h for the row -- are host constants
+// in double and travel as kernel arguments.  States and sums are double throughout (as align.hip's scores are).
+//
+//   lk_ends_kernel    one wave per (row, full segment but the row's last).  The segment is staged into LDS (16-byte loads
+//                     where a quad lies inside it), lane l's run at pitch r | 1 words: the run loop's ds_read_b32 has the
+//                     lanes r | 1 words apart, odd, so a 32-lane half covers 32 banks.  Every lane runs its run from zero
+//                     state; a Hillis-Steele scan v_l += M^(r 2^i) v_(l - 2^i) gives the end state of every FULL lane; the
+//                     partial lane (h is no multiple of 64 at 44.1, 22.05 or 8 kHz, and a padded sample is no no-op) ends
+//                     the segment with M^(h mod r) v + its own e; where r divides h the last full lane ends it.
+//   lk_carry_kernel   one wave per row: 64 segment ends a load, then state <- M^h state + e through the wave in order; lane i
+//                     keeps the state its segment starts from.  Also zeroes the row's peak.
+//   lk_energy_kernel  one wave per (row, segment), the same lane split: lane 0 now runs from the segment's true start state,
+//                     the same scan gives every lane its true start state, and a second run sums y^2 in double; a butterfly
+//                     reduces the wave into seg[b][s].  The staging pass keeps max |x|: one unsigned atomic max per wave on
+//                     the float's bits (exact, and independent of the order).  Segments behind the row: exact 0.
+//   lk_gate_kernel    one wave per row: block energies, both gates, L, (NB, kept), and the gain.  Sums run over ascending j
+//                     (the passing lanes are walked in order through the wave), so they are the restatement's in every bit.
+//   lk_apply_kernel   out = g x over each row's own samples, 16 bytes a lane where both rows are aligned.
+// What bounds the first three is the dependent chain of a lane's run (two fp64 FMAs deep per biquad and sample, r samples,
+// three runs a sample in all) and the scan's shuffles, not a pipe: 7 M samples for 16 rows of 10 s is no load on HBM or the
+// vector unit.
+// The one-pass closed form (zero-state energy + cross term + Gram term of the incoming state) is NOT used: under DC the
+// high-pass's output is about 0 and the three terms cancel catastrophically.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "kernels.h"
+#include "model.h"
+
+namespace {
+
+constexpr int LK_MAX_B = 65535;
+constexpr int64_t LK_MAX_SAMPLES = (int64_t)1 << 30;
+constexpr int LK_FS_MIN = 8000, LK_FS_MAX = 192000;
+constexpr int LK_APPLY_SPAN = 4096;      // samples of a row per block of the apply kernel (256 threads, four quads each)
+
+struct KW {                              // the constants of one sample rate
+  double c[10];                          // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
+  double P[6][16];                       // M^(r 2^i), row-major
+  double T[16];                          // M^(h mod r)
+  double H[16];                          // M^h
+  int h, r, pitch, nf, p;                // segment; lane run; its pitch in LDS (words); full lanes of a full segment; h mod r
+};
+
+struct Rows {                            // uploaded with every call: the head of the workspace
+  const int32_t* n;                      // [B] samples
+  const int32_t* n_apply;                // [B] samples the apply kernel touches (0: a row left alone)
+  const float* params;                   // [B][3] target_lufs, peak_ceiling, max_gain_db
+};
+
+__device__ __forceinline__ double kstep(const double (&c)[10], double x, double (&s)[4]) {
+  const double u = fma(c[0], x, s[0]);
+  s[0] = fma(-c[3], u, fma(c[1], x, s[1]));
+  s[1] = fma(-c[4], u, c[2] * x);
+  const double y = fma(c[5], u, s[2]);
+  s[2] = fma(-c[8], y, fma(c[6], u, s[3]));
+  s[3] = fma(-c[9], y, c[7] * u);
+  return y;
+}
+
+__device__ __forceinline__ void matvec_add(const double (&A)[16], const double (&v)[4], double (&acc)[4]) {   // acc += A v
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    acc[i] = fma(A[4 * i + 3], v[3], fma(A[4 * i + 2], v[2], fma(A[4 * i + 1], v[1], fma(A[4 * i], v[0], acc[i]))));
+}
+
+// The segment row[0 .. len) into LDS, sample i at (i / r) * pitch + i % r; returns this lane's max |x|.  Quads that lie inside
+// the segment are 16-byte loads; the samples before the first aligned quad and behind the last are single loads, so nothing
+// outside [0, len) is touched.
+__device__ __forceinline__ float stage_segment(const float* __restrict__ row, int len, float* lds, int r, int pitch, int lane) {
+  const int head = min(len, (int)((4u - (unsigned)(((uintptr_t)row >> 2) & 3u)) & 3u));
+  const int nquads = (len - head) >> 2;
+  float pk = 0.f;
+  auto put = [&](int i, float v) {
+    const int q = i / r;
+    lds[q * pitch + (i - q * r)] = v;
+    pk = fmaxf(pk, fabsf(v));
+  };
+  if (lane < head) put(lane, row[lane]);
+  const float4* __restrict__ quads = reinterpret_cast<const float4*>(row + head);
+  for (int q = lane; q < nquads; q += 64) {
+    const float4 v = quads[q];
+    const int i = head + 4 * q;
+    put(i, v.x); put(i + 1, v.y); put(i + 2, v.z); put(i + 3, v.w);
+  }
+  const int tail = head + 4 * nquads + lane;      // (fewer than 4 samples are left)
+  if (tail < len) put(tail, row[tail]);
+  return pk;
+}
+
+// Lane `lane` runs its samples from `s` (in: the state it starts from; out: the state it ends in); with SUM the sum of y^2.
+template <bool SUM>
+__device__ __forceinline__ double run_lane(const KW& kw, const float* lds, int lane, int len, double (&s)[4]) {
+  const int mine = max(0, min(kw.r, len - lane * kw.r));
+  const float* x = lds + lane * kw.pitch;
+  double acc = 0.0;
+  for (int i = 0; i < kw.r; ++i)                   // (uniform trip count; only the row's ragged end predicates)
+    if (i < mine) {
+      const double y = kstep(kw.c, (double)x[i], s);
+      if (SUM) acc = fma(y, y, acc);
+    }
+  return acc;
+}
+
+// v_l <- sum_{k <= l} M^(r (l - k)) v_k: the end state of lane l where the lanes 0 .. l all ran r samples.
+__device__ __forceinline__ void scan_lanes(const KW& kw, int lane, double (&v)[4]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = __shfl_up(v[i], 1 << k);
+    if (lane >= (1 << k)) matvec_add(kw.P[k], o, v);
+  }
+}
+
+struct SegArgs {
+  const float* audio;      // [B][stride]
+  int64_t stride;
+  Rows rows;
+  double* ends;            // [B][S_max][4]   zero-state end states (lk_ends) ...
+  double* starts;          // [B][S_max][4]   ... and the states the segments start from (lk_carry)
+  double* seg;             // [B][S_max]
+  unsigned* peak_bits;     // [B]
+  int S_max;
+};
+
+__global__ void __launch_bounds__(64) lk_ends_kernel(const SegArgs g, const KW kw) {
+  extern __shared__ __align__(16) float lk_lds[];
+  const int b = blockIdx.y, s = blockIdx.x, lane = threadIdx.x;
+  const int n = g.rows.n[b];
+  const int S = (n + kw.h - 1) / kw.h;
+  if (s >= S - 1) return;                          // (uniform) the row's last segment hands its state to nobody
+  stage_segment(g.audio + (size_t)b * g.stride + (size_t)s * kw.h, kw.h, lk_lds, kw.r, kw.pitch, lane);
+  __syncthreads();
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  run_lane<false>(kw, lk_lds, lane, kw.h, v);
+  const double e[4] = {v[0], v[1], v[2], v[3]};
+  scan_lanes(kw, lane, v);
+  double prev[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) prev[i] = __shfl_up(v[i], 1);
+  double* out = g.ends + ((size_t)b * g.S_max + s) * 4;
+  if (kw.p == 0) {                                 // every lane that ran is full: lane nf - 1 ends the segment
+    if (lane == kw.nf - 1)
+      for (int i = 0; i < 4; ++i) out[i] = v[i];
+  } else if (lane == kw.nf) {                      // the partial lane: M^p (the state it starts from) + its own end from zero
+    double end[4] = {e[0], e[1], e[2], e[3]};
+    if (lane == 0) prev[0] = prev[1] = prev[2] = prev[3] = 0.0;
+    matvec_add(kw.T, prev, end);
+    for (int i = 0; i < 4; ++i) out[i] = end[i];
+  }
+}
+
+__global__ void __launch_bounds__(64) lk_carry_kernel(const SegArgs g, const KW kw) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = g.rows.n[b];
+  const int S = (n + kw.h - 1) / kw.h;
+  if (lane == 0) g.peak_bits[b] = 0u;
+  double st[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int s0 = 0; s0 < S; s0 += 64) {
+    const int s = s0 + lane;
+    double e[4] = {0.0, 0.0, 0.0, 0.0};
+    if (s < S - 1) {
+      const double* p = g.ends + ((size_t)b * g.S_max + s) * 4;
+      for (int i = 0; i < 4; ++i) e[i] = p[i];
+    }
+    double mine[4] = {0.0, 0.0, 0.0, 0.0};
+    const int cnt = min(64, S - s0);
+    for (int j = 0; j < cnt; ++j) {                // (every lane walks alike)
+      double ej[4], nx[4];
+      for (int i = 0; i < 4; ++i) {
+        ej[i] = __shfl(e[i], j);
+        if (lane == j) mine[i] = st[i];
+        nx[i] = ej[i];
+      }
+      matvec_add(kw.H, st, nx);
+      for (int i = 0; i < 4; ++i) st[i] = nx[i];
+    }
+    if (s < S) {
+      double* p = g.starts + ((size_t)b * g.S_max + s) * 4;
+      for (int i = 0; i < 4; ++i) p[i] = mine[i];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) lk_energy_kernel(const SegArgs g, const KW kw) {
+  extern __shared__ __align__(16) float lk_lds[];
+  const int b = blockIdx.y, s = blockIdx.x, lane = threadIdx.x;
+  const int n = g.rows.n[b];
+  const int S = (n + kw.h - 1) / kw.h;
+  if (s >= S) {                                    // (uniform) behind the row: an exact zero, nothing read
+    if (lane == 0) g.seg[(size_t)b * g.S_max + s] = 0.0;
+    return;
+  }
+  const int len = min(kw.h, n - s * kw.h);
+  float pk = stage_segment(g.audio + (size_t)b * g.stride + (size_t)s * kw.h, len, lk_lds, kw.r, kw.pitch, lane);
+  __syncthreads();
+  const double* sp = g.starts + ((size_t)b * g.S_max + s) * 4;
+  const double in[4] = {sp[0], sp[1], sp[2], sp[3]};
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  if (lane == 0)
+    for (int i = 0; i < 4; ++i) v[i] = in[i];
+  run_lane<false>(kw, lk_lds, lane, len, v);       // lane 0 from the true state: the scan then carries it to every lane
+  scan_lanes(kw, lane, v);
+  double st[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    st[i] = __shfl_up(v[i], 1);
+    if (lane == 0) st[i] = in[i];
+  }
+  double acc = run_lane<true>(kw, lk_lds, lane, len, st);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    acc += __shfl_xor(acc, d);
+    pk = fmaxf(pk, __shfl_xor(pk, d));
+  }
+  if (lane == 0) {
+    g.seg[(size_t)b * g.S_max + s] = acc;
+    atomicMax(g.peak_bits + b, __float_as_uint(pk));     // (|x| >= 0: its bits order as the floats do)
+  }
+}
+
+struct GateArgs {
+  const double* seg;       // [B][S_max]
+  Rows rows;
+  const float* peak;       // [B] (read with params)
+  float* lufs;             // [B]
+  int32_t* blocks;         // [B][2]
+  float* gains;            // [B] (written with params)
+  int S_max, h, with_params;
+  double z_abs;
+};
+
+__global__ void __launch_bounds__(64) lk_gate_kernel(const GateArgs g) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = g.rows.n[b];
+  const double* __restrict__ seg = g.seg + (size_t)b * g.S_max;
+  const bool four = n >= 4 * g.h;
+  const int NB = four ? n / g.h - 3 : 1;
+  const double D = four ? 4.0 * (double)g.h : (double)n;
+  auto energy = [&](int j) {
+    if (four) return ((seg[j] + seg[j + 1]) + seg[j + 2]) + seg[j + 3];
+    double E = 0.0;
+    const int S = (n + g.h - 1) / g.h;
+    for (int s = 0; s < S; ++s) E += seg[s];
+    return E;
+  };
+  // the sum of E_j over the blocks that `keep` accepts, ascending j, and their number
+  auto gated = [&](auto keep, double& sum, int& cnt) {
+    sum = 0.0;
+    cnt = 0;
+    for (int j0 = 0; j0 < NB; j0 += 64) {
+      const int j = j0 + lane;
+      const double E = j < NB ? energy(j) : 0.0;
+      unsigned long long m = __ballot(j < NB && keep(E));
+      cnt += __popcll(m);
+      while (m) {                                  // (uniform: every lane adds the same values in the same order)
+        const int i = __ffsll((long long)m) - 1;
+        sum += __shfl(E, i);
+        m &= m - 1;
+      }
+    }
+  };
+  double sum_abs, sum_kept;
+  int n_abs, n_kept;
+  gated([&](double E) { return E / D > g.z_abs; }, sum_abs, n_abs);
+  const double mean_abs = n_abs ? sum_abs / (double)n_abs : 0.0;
+  gated([&](double E) { return E / D > g.z_abs && 10.0 * E > mean_abs; }, sum_kept, n_kept);
+  const float L = n_kept ? (float)(-0.691 + 10.0 * log10(sum_kept / (double)n_kept / D)) : -INFINITY;
+  if (lane != 0) return;
+  g.lufs[b] = L;
+  g.blocks[2 * b] = NB;
+  g.blocks[2 * b + 1] = n_kept;
+  if (!g.with_params) return;
+  const float target = g.rows.params[3 * b], ceiling = g.rows.params[3 * b + 1], max_db = g.rows.params[3 * b + 2];
+  float gain = 1.f;
+  if (!(target != target) && n_kept) {
+    double gd = pow(10.0, ((double)target - (double)L) / 20.0);
+    gd = fmin(gd, pow(10.0, (double)max_db / 20.0));
+    const float pk = g.peak[b];
+    if (pk > 0.f) gd = fmin(gd, (double)ceiling / (double)pk);
+    gain = (float)gd;
+  }
+  g.gains[b] = gain;
+}
+
+struct ApplyArgs {
+  const float* in;
+  float* out;
+  int64_t in_stride, out_stride;
+  const int32_t* n_apply;  // [B]
+  const float* gains;      // [B]
+};
+
+__global__ void __launch_bounds__(256) lk_apply_kernel(const ApplyArgs a) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int n = a.n_apply[b];
+  const int i0 = blockIdx.x * LK_APPLY_SPAN;
+  if (i0 >= n) return;                             // (a row left alone has n = 0: neither read nor written)
+  const float g = a.gains[b];
+  const float* __restrict__ x = a.in + (size_t)b * a.in_stride;
+  float* o = a.out + (size_t)b * a.out_stride;
+  if ((((uintptr_t)x | (uintptr_t)o) & 15u) == 0) {
+#pragma unroll
+    for (int k = 0; k < LK_APPLY_SPAN / 1024; ++k) {
+      const int i = i0 + (k * 256 + tid) * 4;
+      if (i + 3 < n) {
+        float4 v = *reinterpret_cast<const float4*>(x + i);
+        v.x *= g; v.y *= g; v.z *= g; v.w *= g;
+        *reinterpret_cast<float4*>(o + i) = v;
+      } else {
+        for (int j = i; j < min(i + 4, n); ++j) o[j] = g * x[j];
+      }
+    }
+  } else {
+#pragma unroll 4
+    for (int k = 0; k < LK_APPLY_SPAN / 256; ++k) {
+      const int i = i0 + k * 256 + tid;
+      if (i < n) o[i] = g * x[i];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+bool fs_ok(int fs) { return fs >= LK_FS_MIN && fs <= LK_FS_MAX; }
+int segment_samples(int fs) { return (fs + 5) / 10; }
+int64_t segments_of(int64_t n, int fs) { const int h = segment_samples(fs); return (n + h - 1) / h; }
+
+void kweighting(int fs, double (&c)[10]) {
+  const double pi = 3.14159265358979323846;
+  {
+    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+    const double K = std::tan(pi * f0 / fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+    const double a0 = 1.0 + K / Q + K * K;
+    c[0] = (Vh + Vb * K / Q + K * K) / a0;
+    c[1] = 2.0 * (K * K - Vh) / a0;
+    c[2] = (Vh - Vb * K / Q + K * K) / a0;
+    c[3] = 2.0 * (K * K - 1.0) / a0;
+    c[4] = (1.0 - K / Q + K * K) / a0;
+  }
+  {
+    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+    const double K = std::tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+    c[5] = 1.0; c[6] = -2.0; c[7] = 1.0;
+    c[8] = 2.0 * (K * K - 1.0) / a0;
+    c[9] = (1.0 - K / Q + K * K) / a0;
+  }
+}
+
+void mat_mul(const double* A, const double* B, double* C) {
+  double t[16];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
+      t[4 * i + j] = s;
+    }
+  std::memcpy(C, t, sizeof t);
+}
+
+void mat_pow(const double* M, int64_t k, double* out) {          // M^k by squaring (M^0 = I)
+  double base[16], acc[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::memcpy(base, M, sizeof base);
+  for (; k > 0; k >>= 1) {
+    if (k & 1) mat_mul(base, acc, acc);
+    mat_mul(base, base, base);
+  }
+  std::memcpy(out, acc, sizeof acc);
+}
+
+KW make_kw(int fs) {
+  KW kw;
+  kweighting(fs, kw.c);
+  const double* c = kw.c;
+  // the state's transition: kstep() with x = 0
+  const double M[16] = {-c[3], 1, 0, 0,
+                        -c[4], 0, 0, 0,
+                        c[6] - c[8] * c[5], 0, -c[8], 1,
+                        c[7] - c[9] * c[5], 0, -c[9], 0};
+  kw.h = segment_samples(fs);
+  kw.r = (kw.h + 63) / 64;
+  kw.pitch = kw.r | 1;
+  kw.nf = kw.h / kw.r;
+  kw.p = kw.h - kw.nf * kw.r;
+  mat_pow(M, kw.r, kw.P[0]);
+  for (int k = 1; k < 6; ++k) mat_mul(kw.P[k - 1], kw.P[k - 1], kw.P[k]);
+  mat_pow(M, kw.p, kw.T);
+  mat_pow(M, kw.h, kw.H);
+  return kw;
+}
+
+// [rows: n, n_apply (int32 [B] each), params (float [B][3])] [ends] [starts] [seg] [blocks]
+struct Ws { size_t rows, ends, starts, seg, blocks, end; };
+size_t rows_bytes(int B) { return align256((size_t)5 * B * sizeof(int32_t)); }
+Ws layout(int B, int64_t S_max) {
+  Ws w;
+  w.rows = 0;
+  w.ends = rows_bytes(B);
+  w.starts = w.ends + align256((size_t)B * S_max * 4 * sizeof(double));
+  w.seg = w.starts + align256((size_t)B * S_max * 4 * sizeof(double));
+  w.blocks = w.seg + align256((size_t)B * S_max * sizeof(double));
+  w.end = w.blocks + align256((size_t)2 * B * sizeof(int32_t));
+  return w;
+}
+
+bool sizes_ok(int B, int64_t L_max) { return B >= 1 && B <= LK_MAX_B && L_max >= 1 && L_max <= LK_MAX_SAMPLES; }
+
+const vsp_loudness_params kLeaveAlone = {NAN, 1.f, 0.f};
+
+// The rows of a call, refused on the host naming the row; fills the upload: n, n_apply, params.
+int check_rows(vsp_ctx* ctx, const char* who, int B, int64_t L_max, const int64_t* n_host, const vsp_loudness_params* params,
+               std::vector<int32_t>& up) {
+  up.assign((size_t)5 * B, 0);
+  for (int b = 0; b < B; ++b) {
+    const int64_t n = n_host[b];
+    if (n < 1 || n > L_max)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d has %lld samples: 1 <= n_samples <= %lld", who, b, (long long)n, (long long)L_max);
+    const vsp_loudness_params p = params ? params[b] : kLeaveAlone;
+    if (params) {
+      if (!(p.peak_ceiling > 0.f))
+        return ctx->fail(VSP_ERR_ARG, "%s: row %d: peak_ceiling must be above 0", who, b);
+      if (!(p.max_gain_db >= 0.f))
+        return ctx->fail(VSP_ERR_ARG, "%s: row %d: max_gain_db must be at least 0", who, b);
+    }
+    up[b] = (int32_t)n;
+    up[(size_t)B + b] = (params && p.target_lufs != p.target_lufs) ? 0 : (int32_t)n;      // a NaN target: the row is left alone
+    const float f[3] = {p.target_lufs, p.peak_ceiling, p.max_gain_db};
+    std::memcpy(&up[(size_t)2 * B + (size_t)3 * b], f, sizeof f);
+  }
+  return VSP_OK;
+}
+
+int need_ws(vsp_ctx* ctx, const char* who, void* workspace, int64_t workspace_bytes, size_t need) {
+  if (!workspace || workspace_bytes < (int64_t)need)
+    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
+  return VSP_OK;
+}
+
+int upload_rows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, const std::vector<int32_t>& up, Rows& rows) {
+  // (pageable host memory: the runtime stages it before hipMemcpyAsync returns, as the prosody and align uploads rest on)
+  const hipError_t e = hipMemcpyAsync(ws, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
+  rows.n = reinterpret_cast<const int32_t*>(ws);
+  rows.n_apply = rows.n + B;
+  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
+  return VSP_OK;
+}
+
+int launch_segments(vsp_ctx* ctx, hipStream_t s, int B, int S_max, const KW& kw, const float* audio, int64_t stride, const Rows& rows,
+                    char* ws, const Ws& lay, double* seg, float* peak) {
+  SegArgs a;
+  a.audio = audio; a.stride = stride; a.rows = rows;
+  a.ends = reinterpret_cast<double*>(ws + lay.ends);
+  a.starts = reinterpret_cast<double*>(ws + lay.starts);
+  a.seg = seg;
+  a.peak_bits = reinterpret_cast<unsigned*>(peak);
+  a.S_max = S_max;
+  const size_t lds = (size_t)64 * kw.pitch * sizeof(float);      // (77 KiB at 192 kHz)
+  static std::atomic<uint64_t> done_e{0}, done_c{0};
+  if (lds > 48 * 1024) {
+    hipError_t e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(lk_ends_kernel), 96 * 1024, done_e);
+    if (e == hipSuccess) e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(lk_energy_kernel), 96 * 1024, done_c);
+    if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "loudness (LDS): %s", hipGetErrorString(e));
+  }
+  const dim3 grid(S_max, B);
+  if (S_max > 1) hipLaunchKernelGGL(lk_ends_kernel, grid, dim3(64), lds, s, a, kw);
+  hipLaunchKernelGGL(lk_carry_kernel, dim3(B), dim3(64), 0, s, a, kw);
+  hipLaunchKernelGGL(lk_energy_kernel, grid, dim3(64), lds, s, a, kw);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "loudness segments: %s", hipGetErrorString(e));
+  return VSP_OK;
+}
+
+int launch_gate(vsp_ctx* ctx, hipStream_t s, int B, int S_max, int h, const double* seg, const Rows& rows, bool with_params,
+                const float* peak, float* lufs, int32_t* blocks, float* gains) {
+  GateArgs a;
+  a.seg = seg; a.rows = rows; a.peak = peak; a.lufs = lufs; a.blocks = blocks; a.gains = gains;
+  a.S_max = S_max; a.h = h; a.with_params = with_params ? 1 : 0;
+  a.z_abs = std::pow(10.0, (-70.0 + 0.691) / 10.0);
+  hipLaunchKernelGGL(lk_gate_kernel, dim3(B), dim3(64), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lk_gate_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}
+
+int launch_apply(vsp_ctx* ctx, hipStream_t s, int B, int64_t L_max, const float* in, int64_t in_stride, float* out, int64_t out_stride,
+                 const Rows& rows, const float* gains) {
+  ApplyArgs a;
+  a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride; a.n_apply = rows.n_apply; a.gains = gains;
+  hipLaunchKernelGGL(lk_apply_kernel, dim3((unsigned)((L_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lk_apply_kernel: %s", hipGetErrorString(e));
+  return VSP_OK;
+}
+
+}  // namespace
+
+int vsp_loudness_kweighting(int sample_rate, double* coef) {
+  if (!fs_ok(sample_rate) || !coef) return VSP_ERR_ARG;
+  double c[10];
+  kweighting(sample_rate, c);
+  std::memcpy(coef, c, sizeof c);
+  return VSP_OK;
+}
+
+int64_t vsp_loudness_segments_count(int64_t n_samples, int sample_rate) {
+  if (!fs_ok(sample_rate) || n_samples < 1 || n_samples > LK_MAX_SAMPLES) return VSP_ERR_ARG;
+  return segments_of(n_samples, sample_rate);
+}
+
+int64_t vsp_loudness_workspace_bytes(int B, int64_t L_max, int sample_rate) {
+  if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
+  return (int64_t)layout(B, segments_of(L_max, sample_rate)).end;
+}
+
+int vsp_loudness_segments(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                          const int64_t* n_samples_host, double* seg, float* peak, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_segments";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, and the rows' samples", who, LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
+  if (!audio || !seg || !peak) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  const Ws lay = layout(B, S_max);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  Rows rows;
+  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
+  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak);
+}
+
+int vsp_loudness_gate(vsp_ctx* ctx, void* stream, int B, int S_max, int sample_rate, const double* seg, const int64_t* n_samples_host,
+                      const float* peak, const vsp_loudness_params* params_host, float* lufs, int32_t* blocks, float* gains,
+                      void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_gate";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const int h = segment_samples(sample_rate);
+  if (B < 1 || B > LK_MAX_B || S_max < 1 || (int64_t)S_max * h > LK_MAX_SAMPLES + h || !n_samples_host)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, S_max >= 1 segments (at most 2^30 samples), and the rows' samples", who, LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, std::min((int64_t)S_max * h, LK_MAX_SAMPLES), n_samples_host, params_host, up)) return rc;
+  if (!seg || !lufs || !blocks || (params_host && (!peak || !gains))) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_bytes(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Rows rows;
+  if (const int rc = upload_rows(ctx, who, s, static_cast<char*>(workspace), B, up, rows)) return rc;
+  return launch_gate(ctx, s, B, S_max, h, seg, rows, params_host != nullptr, peak, lufs, blocks, gains);
+}
+
+int vsp_loudness_apply(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float* in, int64_t in_stride, float* out,
+                       int64_t out_stride, const int64_t* n_samples_host, const float* gains, const vsp_loudness_params* params_host,
+                       void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_apply";
+  if (!sizes_ok(B, L_max) || in_stride < L_max || out_stride < L_max || !n_samples_host)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, and the rows' samples", who, LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, params_host, up)) return rc;
+  if (!in || !out || !gains) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_bytes(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  Rows rows;
+  if (const int rc = upload_rows(ctx, who, s, static_cast<char*>(workspace), B, up, rows)) return rc;
+  return launch_apply(ctx, s, B, L_max, in, in_stride, out, out_stride, rows, gains);
+}
+
+int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                           float* out, int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_params* params_host,
+                           float* lufs, float* peak, float* gains, int32_t* blocks, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_normalize";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (!sizes_ok(B, L_max) || audio_stride < L_max || out_stride < L_max || !n_samples_host || !params_host)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, the rows' samples and their params", who, LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, params_host, up)) return rc;
+  if (!audio || !out || !lufs || !peak || !gains) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  const Ws lay = layout(B, S_max);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  Rows rows;
+  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
+  const KW kw = make_kw(sample_rate);
+  double* seg = reinterpret_cast<double*>(ws + lay.seg);
+  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws, lay, seg, peak)) return rc;
+  if (!blocks) blocks = reinterpret_cast<int32_t*>(ws + lay.blocks);
+  if (const int rc = launch_gate(ctx, s, B, S_max, kw.h, seg, rows, true, peak, lufs, blocks, gains)) return rc;
+  return launch_apply(ctx, s, B, L_max, audio, audio_stride, out, out_stride, rows, gains);
+}

@@ -1624,6 +1624,147 @@ class Engine:
         _, dur = self.align(lat["z_p"], dec["m_p"], dec["logs_p"], lat["frames_host"], states, enc["cum_dur"], lengths, pp)
         return dur.to(torch.int64)
 
+    # ------------------------------------------------------------------ loudness (section 4p)
+    @staticmethod
+    def loudness_params(B: int, target_lufs=-23.0, peak_ceiling=1.0, max_gain_db=30.0):
+        """``vsp_loudness_params`` [B] from three values, each a scalar or one value per row.  A row's ``target_lufs`` may be
+        None or NaN: the row is left alone.  Refused here as the library refuses them (a ``ValueError`` naming the row)."""
+        def col(v, name):
+            if v is None or np.ndim(v) == 0:
+                return [float("nan") if v is None else float(v)] * B
+            v = [float("nan") if x is None else float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+            if len(v) != B:
+                raise ValueError(f"loudness: {name} must be a scalar or have {B} entries")
+            return v
+        t, c, m = col(target_lufs, "target_lufs"), col(peak_ceiling, "peak_ceiling"), col(max_gain_db, "max_gain_db")
+        out = (_lib.VspLoudnessParams * B)()
+        for b in range(B):
+            if not c[b] > 0.0:
+                raise ValueError(f"loudness: row {b}: peak_ceiling must be above 0")
+            if not m[b] >= 0.0:
+                raise ValueError(f"loudness: row {b}: max_gain_db must be at least 0")
+            out[b] = _lib.VspLoudnessParams(t[b], c[b], m[b])
+        return out
+
+    def _loudness_rows(self, audio, n_samples, sample_rate, what: str = "audio"):
+        """The checks every loudness call makes of its rows: ``(audio, B, stride, n_host, fs)``.  A float32 tensor on the
+        device with contiguous rows is used as it is (so that ``loudness_apply`` can work in place)."""
+        a = audio if (torch.is_tensor(audio) and audio.dtype == torch.float32 and audio.device == self.device) \
+            else _dev_f32(audio, self.device)
+        if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+            raise ValueError(f"{what} must be [B, L] (rows padded to a common length, each contiguous)")
+        B = a.shape[0]
+        stride = a.stride(0) if B > 1 else a.shape[1]
+        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        if len(n_host) != B or B == 0:
+            raise ValueError(f"n_samples must have {B} entries (at least one row)")
+        if stride < a.shape[1]:
+            raise ValueError(f"{what}: rows overlap")
+        for b, n in enumerate(n_host):
+            if not 1 <= n <= a.shape[1]:
+                raise ValueError(f"loudness: row {b} has {n} samples: 1 <= n_samples <= {what}.shape[1] = {a.shape[1]}")
+        fs = None
+        if sample_rate is not None:
+            fs = int(sample_rate)
+            if not _lib.LOUDNESS_FS_MIN <= fs <= _lib.LOUDNESS_FS_MAX:
+                raise ValueError(f"loudness: sample_rate {fs}: {_lib.LOUDNESS_FS_MIN} <= sample_rate <= {_lib.LOUDNESS_FS_MAX}")
+        return a, B, int(stride), n_host, fs
+
+    def loudness_segments(self, audio, n_samples, sample_rate: int):
+        """``vsp_loudness_segments``: ``audio`` [B, L] float32 at ``sample_rate``, row b ``audio[b, :n_samples[b]]`` (what lies
+        behind is never read).  Returns ``(seg, peak)``: the K-weighted energy of every 100 ms segment, ``[B, S_max]`` float64
+        with exact zeros behind a row's segments, and the rows' sample peaks ``[B]`` float32 (exact)."""
+        a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
+        L_max = max(n_host)
+        S_max = int(self.lib.vsp_loudness_segments_count(L_max, fs))
+        seg = torch.empty((B, S_max), dtype=torch.float64, device=self.device)
+        peak = self._f(B)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_workspace_bytes(B, L_max, fs))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_segments(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, (C.c_int64 * B)(*n_host),
+                                                _ptr(seg), _ptr(peak), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_segments")
+        return seg, peak
+
+    def loudness_gate(self, seg, n_samples, sample_rate: int, peak=None, params=None):
+        """``vsp_loudness_gate``: any float64 segment table ``[B, S_max]`` (``loudness_segments``', or any) with the rows'
+        ``n_samples`` to ``(lufs [B] float32, blocks [B, 2] int32)`` -- the integrated loudness (-inf where no block is
+        kept) and (blocks, kept blocks) --; with ``params`` (``loudness_params``) and the rows' ``peak`` also ``gains`` [B]."""
+        t = torch.as_tensor(seg).to(device=self.device, dtype=torch.float64).contiguous()
+        if t.dim() != 2 or t.shape[1] < 1:
+            raise ValueError("seg must be [B, S_max]")
+        B, S_max = t.shape
+        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        fs = int(sample_rate)
+        if len(n_host) != B or B == 0:
+            raise ValueError(f"n_samples must have {B} entries (at least one row)")
+        h = (fs + 5) // 10
+        for b, n in enumerate(n_host):
+            if not 1 <= n <= S_max * h:
+                raise ValueError(f"loudness: row {b} has {n} samples: 1 <= n_samples <= S_max h = {S_max * h}")
+        lufs = self._f(B)
+        blocks = torch.empty((B, 2), dtype=torch.int32, device=self.device)
+        gains = pk = None
+        if params is not None:
+            if peak is None:
+                raise ValueError("loudness_gate: gains need the rows' peak")
+            pk = _dev_f32(peak, self.device)
+            gains = self._f(B)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_gate(self.ctx, self._stream(), B, S_max, fs, _ptr(t), (C.c_int64 * B)(*n_host), _ptr(pk),
+                                            params, _ptr(lufs), _ptr(blocks), _ptr(gains), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_gate")
+        return (lufs, blocks) if params is None else (lufs, blocks, gains)
+
+    def loudness(self, audio, n_samples, sample_rate: int):
+        """The integrated loudness of every row: ``loudness_segments`` then ``loudness_gate``.  Returns ``(lufs, peak,
+        blocks)``, all on the device."""
+        seg, peak = self.loudness_segments(audio, n_samples, sample_rate)
+        lufs, blocks = self.loudness_gate(seg, n_samples, sample_rate)
+        return lufs, peak, blocks
+
+    def loudness_apply(self, audio, n_samples, gains, params=None, out=None):
+        """``vsp_loudness_apply``: ``out[b, :n_b] = gains[b] * audio[b, :n_b]``; ``out`` None: in place where ``audio`` is a
+        float32 device tensor (a copy of it otherwise).  With ``params`` a row whose target is NaN is neither read nor
+        written.  Nothing at or behind ``n_b`` is touched.  Returns ``out``."""
+        a, B, stride, n_host, _ = self._loudness_rows(audio, n_samples, None)
+        o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
+        if out is not None and o is not out:
+            raise ValueError("out must be a float32 tensor on the engine's device")
+        g = _dev_f32(gains, self.device)
+        if g.shape != (B,):
+            raise ValueError(f"gains must have {B} entries")
+        L_max = max(n_host)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_apply(self.ctx, self._stream(), B, L_max, _ptr(a), stride, _ptr(o), o_stride,
+                                             (C.c_int64 * B)(*n_host), _ptr(g), params, _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_apply")
+        return o
+
+    def loudness_normalize(self, audio, n_samples, sample_rate: int, params, out=None):
+        """``vsp_loudness_normalize``: measure, derive every row's gain from its ``params`` (``loudness_params``) and apply
+        it, in ONE call (five launches behind one upload; nothing is read back in between).  ``out`` None: in place where
+        ``audio`` is a float32 device tensor.  Returns ``(out, gains, lufs, peak, blocks)``, all on the device; a row whose
+        target is NaN keeps its samples (gain exactly 1, neither read nor written by the apply)."""
+        a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
+        o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
+        if out is not None and o is not out:
+            raise ValueError("out must be a float32 tensor on the engine's device")
+        if len(params) != B:
+            raise ValueError(f"loudness: params must have {B} rows")
+        L_max = max(n_host)
+        lufs, peak, gains = self._f(B), self._f(B), self._f(B)
+        blocks = torch.empty((B, 2), dtype=torch.int32, device=self.device)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_workspace_bytes(B, L_max, fs))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_normalize(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, _ptr(o), o_stride,
+                                                 (C.c_int64 * B)(*n_host), params, _ptr(lufs), _ptr(peak), _ptr(gains),
+                                                 _ptr(blocks), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_normalize")
+        return o, gains, lufs, peak, blocks
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

@@ -250,6 +250,30 @@ class SynthesizerTrn:
         return eng.align_audio(phonemes, phonemes_lengths, sid, audio, n_samples, sid_audio=sid_audio, params=pp,
                                fit_length=fit_length)
 
+    @torch.no_grad()
+    def loudness(self, audio, n_samples, sample_rate: Optional[int] = None):
+        """The integrated loudness (ITU-R BS.1770-4 / EBU R 128, mono) of every row of a ragged batch:
+        ``audio`` [B, L] float32 at ``sample_rate`` (None: the model's), row b ``audio[b, :n_samples[b]]`` (what lies behind
+        is never read).  Returns ``(lufs, peak)``, both ``[B]`` float32 on the device: LUFS (-inf for a row all of whose
+        blocks are gated out) and the SAMPLE peak (true peak is not computed).  Needs no weights."""
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        lufs, peak, _ = self._engine.loudness(audio, n_samples, fs)
+        return lufs, peak
+
+    @torch.no_grad()
+    def normalize_loudness(self, audio, n_samples, target_lufs=-23.0, peak_ceiling=1.0, max_gain_db=30.0,
+                           sample_rate: Optional[int] = None, out=None):
+        """Every row of ``audio`` [B, L] scaled to its target loudness, on the device in one call: ``g = 10^((target - L) /
+        20)``, at most ``max_gain_db`` and at most ``peak_ceiling / peak``.  The three values are scalars or one per row; a row
+        whose target is None or NaN, and a row of no loudness (-inf), is left as it is (gain exactly 1).  In place where
+        ``audio`` is a float32 tensor on the model's device and ``out`` is None; samples at or behind ``n_samples[b]`` are not
+        touched.  Returns ``(audio, gains)``.  ``infer(...)[0][:, 0]`` and ``convert_audio(...)[0][:, 0]`` are such batches."""
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        eng = self._engine
+        B = len(n_samples)
+        res = eng.loudness_normalize(audio, n_samples, fs, eng.loudness_params(B, target_lufs, peak_ceiling, max_gain_db), out=out)
+        return res[0], res[1]
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

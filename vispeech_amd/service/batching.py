@@ -33,6 +33,32 @@ def _output_format(output_rate, output_encoding):
     return (None if output_rate is None else int(output_rate), output_stage.encoding(output_encoding))
 
 
+def _loudness_spec(loudness):
+    """``(target_lufs, peak_ceiling, max_gain_db)`` of a request or service that names a loudness -- a target in LUFS, or a
+    mapping of the three (``peak_ceiling`` 1.0 and ``max_gain_db`` 30.0 where it leaves them out) --, None of one that names
+    none (None or False).  Refused here, not in the worker."""
+    if loudness is None or loudness is False:
+        return None
+    vals = {"target_lufs": None, "peak_ceiling": 1.0, "max_gain_db": 30.0}
+    if hasattr(loudness, "keys"):
+        unknown = set(loudness) - set(vals)
+        if unknown:
+            raise ValueError(f"loudness: unknown {sorted(unknown)}; the fields are {list(vals)}")
+        vals.update(loudness)
+    else:
+        vals["target_lufs"] = loudness
+    if vals["target_lufs"] is None or isinstance(vals["target_lufs"], bool):
+        raise ValueError("loudness: a target in LUFS, or a mapping with target_lufs")
+    t, c, m = float(vals["target_lufs"]), float(vals["peak_ceiling"]), float(vals["max_gain_db"])
+    if not (t == t and abs(t) != float("inf")):
+        raise ValueError("loudness: target_lufs must be finite")
+    if not c > 0.0:
+        raise ValueError("loudness: peak_ceiling must be above 0")
+    if not m >= 0.0:
+        raise ValueError("loudness: max_gain_db must be at least 0")
+    return (t, c, m)
+
+
 def _row_formats(eng, reqs, base_rate: int, model_rate: int):
     """Per request the ``(rate, VSP_OUT_*)`` of its row in an ``Engine.output_rows`` call: its own format, or -- for a
     request that names none -- (the service's rate, PCM16), the bytes it gets on the service's own path.  Rates the engine's
@@ -98,8 +124,9 @@ class _Request:
     keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
     ``noise_scale``; a conversion's noise scale is its row's."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None, loudness=None):
         self.row, self.seed, self.scales = row, int(seed), scales
+        self.loudness = loudness      # ``_loudness_spec``: the level the request's waveform is brought to, or None
         self.out_fmt = out_fmt        # ``_output_format``: the request's own output rate and encoding, or None
         self.prosody = prosody        # a ``_Recording``: the row's f0 / energy come from it (``_prosody_controls``), or None
 
@@ -334,11 +361,15 @@ class BatchingSynthesisService:
     (``Engine.prosody_contours(path=...)``).  A batch still makes ONE contour call.
     ``prosody_align``: None -- a ``prosody_audio`` request must bring its durations, as always; True or (max_advance, stay_cost,
     skip_cost) / a dict of them (True: 2, 0, 0): a request whose row brings none gets them from its recording first
-    (``Engine.align_audio``; needs the ``enc_q.*`` tensors), ONE call per batch."""
+    (``Engine.align_audio``; needs the ``enc_q.*`` tensors), ONE call per batch.
+    ``loudness``: the level every request of this service is brought to unless it names its own (``submit(loudness=)``;
+    False there: none) -- a target in LUFS or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: none.  A batch in
+    which a request has one makes ONE ``Engine.loudness_normalize`` call on the generator's output, in place, before the
+    output stage; a batch in which nobody has one makes exactly the calls it always made."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
                  spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None,
-                 prosody_align=None):
+                 prosody_align=None, loudness=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -354,6 +385,7 @@ class BatchingSynthesisService:
             from ..engine import Engine
             prosody_align = Engine._align_params(prosody_align)      # (refused here, not in the worker)
         self.prosody_align = prosody_align or None
+        self.loudness = _loudness_spec(loudness)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -364,7 +396,8 @@ class BatchingSynthesisService:
 
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
                noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, prosody_audio=None,
-               prosody_sample_rate: Optional[int] = None, prosody_encoding=None, prosody_sid=None) -> "concurrent.futures.Future":
+               prosody_sample_rate: Optional[int] = None, prosody_encoding=None, prosody_sid=None,
+               loudness=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
         The future's result is the request's PCM16 samples (numpy int16, valid part only).
@@ -380,7 +413,9 @@ class BatchingSynthesisService:
         they take the place of whatever f0 / energy the row carries.  The request is then what
         ``infer(isolated=True, duration_control=.., pitch_control=f0, energy_control=energy)`` returns for it alone.
         On a service with ``prosody_align`` a row without durations is accepted: the worker aligns its text to the recording
-        first (``prosody_sid``: the recording's speaker where it is not the row's)."""
+        first (``prosody_sid``: the recording's speaker where it is not the row's).
+        ``loudness``: the integrated loudness (BS.1770, LUFS) the request's waveform is brought to before it is encoded -- a
+        target, or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: the service's; False: none."""
         prosody = None
         if prosody_sid is not None:
             n_spk = getattr(self.net, "n_speakers", None)
@@ -403,21 +438,37 @@ class BatchingSynthesisService:
         elif prosody_sid is not None:
             raise ValueError("prosody_sid names the speaker of prosody_audio: pass it")
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                      _output_format(output_rate, output_encoding), prosody))
+                                      _output_format(output_rate, output_encoding), prosody, self._loudness_of(loudness)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None) -> "concurrent.futures.Future":
+                          output_encoding=None, loudness=None) -> "concurrent.futures.Future":
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
         PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
         ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
         ``noise_scale``); ``noise_seed`` keys that noise.
         ``sample_rate`` / ``encoding`` (``vispeech_amd.input_stage``): ``audio`` is raw -- an array of the encoding's dtype or
         ``bytes`` -- at that rate; the batch's raw recordings go through the input stage on the GPU, one call per distinct
-        (rate, encoding), before the one ``convert_latent``.  ``output_rate`` / ``output_encoding``: as in ``submit``."""
+        (rate, encoding), before the one ``convert_latent``.  ``output_rate`` / ``output_encoding`` / ``loudness``: as in
+        ``submit`` (the level is that of the converted waveform; the recording is not normalised before conversion)."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
-                                      out_fmt=_output_format(output_rate, output_encoding)))
+                                      out_fmt=_output_format(output_rate, output_encoding), loudness=self._loudness_of(loudness)))
+
+    def _loudness_of(self, loudness):
+        return self.loudness if loudness is None else _loudness_spec(loudness)
+
+    def _normalize(self, reqs, waves, n) -> None:
+        """The requests that have a loudness: ONE ``Engine.loudness_normalize`` call over the batch's rows ``waves`` [B, L]
+        (the generator's output, row b's first ``n[b]`` samples), in place, at the model's rate.  A row that asks for nothing
+        carries a NaN target and is neither read nor written by the apply; a batch in which nobody asks makes no call."""
+        if all(r.loudness is None for r in reqs) or waves.shape[-1] == 0:
+            return
+        from ..engine import Engine
+        nan = float("nan")
+        spec = [(nan, 1.0, 0.0) if r.loudness is None or n[b] < 1 else r.loudness for b, r in enumerate(reqs)]
+        params = Engine.loudness_params(len(reqs), *zip(*spec))
+        self.net._engine.loudness_normalize(waves, [max(int(v), 1) for v in n], self.sampling_rate, params)
 
     def _enqueue(self, req: _Request) -> "concurrent.futures.Future":
         req.future = concurrent.futures.Future()
@@ -478,6 +529,7 @@ class BatchingSynthesisService:
                                   duration_control=t(ctl[0]), pitch_control=t(ctl[1]),
                                   energy_control=t(ctl[2]), noise_seed=[r.seed for r in reqs], isolated=True, **kw)
         frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
+        self._normalize(reqs, o[:, 0, :], [int(frames[b]) * hop for b in range(len(reqs))])
         if any(r.out_fmt is not None for r in reqs):
             return self._deliver_rows(reqs, [o[b, 0, : int(frames[b]) * hop] for b in range(len(reqs))])
         return [self._pcm16(o[b:b + 1, 0, : int(frames[b]) * hop]) for b in range(len(reqs))]
@@ -519,6 +571,7 @@ class BatchingSynthesisService:
         G = torch.stack([torch.as_tensor(lat[i][1]).reshape(-1) for i in live])
         o = eng.generator_ragged(Z, G, [lat[i][2] for i in live])
         hop = net.dims.total_upsample
+        self._normalize([reqs[i] for i in live], o[:, 0, :], [lat[i][2] * hop for i in live])
         if any(r.out_fmt is not None for r in reqs):
             waves = [None] * len(reqs)
             for b, i in enumerate(live):
