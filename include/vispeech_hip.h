@@ -1172,7 +1172,7 @@ int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, in
  * max_gain_db; a workspace too small is VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload of its rows (20
  * bytes a row: the lengths and the params, pageable host memory as the prosody calls'), allocates nothing and does not
  * synchronise.  n_samples_host, params_host: HOST arrays [B].
- * Not computed: true peak (sample peak only), stereo and channel weights, momentary and short-term loudness, loudness range. */
+ * Not computed: true peak (sample peak only; the meter of the next section has it), stereo and channel weights, momentary and short-term loudness, loudness range. */
 typedef struct vsp_loudness_params {
   float target_lufs, peak_ceiling, max_gain_db;
 } vsp_loudness_params;
@@ -1203,6 +1203,64 @@ int vsp_loudness_apply(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const f
 int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                            float* out, int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_params* params_host,
                            float* lufs, float* peak, float* gains, int32_t* blocks, void* workspace, int64_t workspace_bytes);
+
+/* ---- true peak and look-ahead limiter (round 22, ABI 7, additive) --- */
+/* A true-peak meter and a look-ahead limiter without a recurrence, per row of a ragged batch of mono float32 rows or of a
+ * set of streams, on the device.  The specification is this project's own, restated in fp64 in tests/limiter_ref.py.  A
+ * row is x[0 .. N), zero outside.
+ *   true peak    4x oversampling with the resampling core's filter formula ("output stage" above) at L = 4, M = 1,
+ *                zeros = 12, beta = 9.62, the default rolloff: H = 48, 97 taps h[-48 .. 48] computed in double and rounded
+ *                to float32 once.  y[m] = sum_k h[m - 4 k] x[k] over |m - 4 k| <= 48, a float32 FMA chain from 0 in
+ *                ascending k (reach J = 12 samples a side).  p[n] = max(|x[n]|, |y[4n]|, |y[4n+1]|, |y[4n+2]|, |y[4n+3]|);
+ *                TP = max_n p[n].  (|x[n]| is in the max because the low-pass attenuates a lone click.)
+ *   gain wanted  e[n] = g p[n]; r[n] = e[n] > c ? c / e[n] : 1 inside the row, 1 outside it (float32, IEEE division).
+ *   hold, look-ahead   m[n] = min r[j], j = n - H .. n + A.
+ *   smoothing    s[n] = (m[n - A] + ... + m[n]) * fl32(1 / (A + 1)): a float32 sum from 0 in ascending order.
+ *   output       o[n] = clamp((g x[n]) s[n], -c, c) in float32.  s[n] <= r[n] in exact arithmetic (every m[k] summed has n
+ *                in its own window), so |o[n]| <= c at the samples and the clamp only removes a last-place rounding.
+ * A (attack = look-ahead, 0 .. 1024 samples) and H (hold, 0 .. 8192 samples) are per call; the ceiling c > 0 and the static
+ * gain g are per row.  o[n] depends on x[n - (A + H + J) .. n + A + J] and on nothing else, so a stream is limited exactly
+ * in pieces: vsp_limiter_history gives the two extents.  The true peak of the OUTPUT may exceed c slightly (the varying
+ * gain spreads the spectrum; measured about 0.01 dB on the tests' fixtures): the sample ceiling is exact, the true-peak
+ * ceiling is not promised.
+ * Nothing outside a row's provided samples is read and nothing outside its outputs is written; a row's bits do not depend
+ * on the rows it is batched with, nor on how a stream is cut.  Every refusal happens on the host before any launch, naming
+ * the row.  Each call runs on `stream` behind ONE upload of its rows (pageable host memory), allocates nothing and does
+ * not synchronise. */
+typedef struct vsp_limiter_row {
+  const float* in;      /* device: the stream's samples [first, first + count) */
+  int64_t first, count;
+  float* out;           /* device: receives the limited samples [out_first, out_first + out_count); may alias `in` at the same positions */
+  int64_t out_first, out_count;
+  int64_t total;        /* the stream's length, or -1 while its end is unknown */
+  float ceiling;        /* c > 0; NaN: the row is neither read nor written */
+} vsp_limiter_row;
+/* taps97_host[n + 48] = fl32(h[n]), n = -48 .. 48.  Host only. */
+int vsp_true_peak_filter(float* taps97_host);
+/* *behind = A + H + J, *ahead = A + J, J = 12: the samples before an output and after it that reach it.  Host only;
+ * VSP_ERR_ARG for A outside [0, 1024] or H outside [0, 8192]. */
+int vsp_limiter_history(int A, int H, int64_t* behind, int64_t* ahead);
+/* Workspace of vsp_limiter_rows for B rows of up to L_max OUTPUTS each (VSP_ERR_ARG as a negative size); monotone in every
+ * argument.  vsp_true_peak needs vsp_limiter_workspace_bytes(B, 1, 0, 0). */
+int64_t vsp_limiter_workspace_bytes(int B, int64_t L_max, int A, int H);
+/* tp[b] = the true peak of audio[b][0 .. n_b), [B] float32 on the device (audio_stride >= L_max >= n_b >= 1).  One launch
+ * behind a memset: tiles x rows, the block's maximum folded into tp[b] by an unsigned maximum on the float's bits (exact,
+ * independent of the order).  A row whose peak is a sample value reads that value in every bit. */
+int vsp_true_peak(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float* audio, int64_t audio_stride,
+                  const int64_t* n_samples_host, float* tp, void* workspace, int64_t workspace_bytes);
+/* The limiter over B rows, each at its own position of its own stream; rows_host: HOST array [B].  gains: [B] float32 on
+ * the DEVICE (as vsp_loudness_gate leaves them), or NULL for 1.  min_gain: [B] float32 on the device, or NULL: the smallest
+ * s[n] among the row's outputs of this call (1 for a row left alone): how hard the row was limited.  Two launches: r into
+ * the workspace (with A + H values before and A behind the outputs), then sliding minimum, boxcar, product and clamp.
+ * VSP_ERR_ARG when
+ *   first > max(0, out_first - behind): history is missing;
+ *   first + count < out_first + out_count + ahead while the provided samples do not reach the stream's end (total unknown,
+ *   or total > first + count): look-ahead is missing;
+ *   the outputs are not among the provided samples, the samples lie behind `total`, a position or count is negative or
+ *   above 2^30, a pointer of a row that has samples (outputs) is NULL, the ceiling is not above 0, A or H is out of range.
+ * A whole utterance of n samples is first = out_first = 0, count = out_count = total = n. */
+int vsp_limiter_rows(vsp_ctx* ctx, void* stream, int B, int A, int H, const vsp_limiter_row* rows_host, const float* gains,
+                     float* min_gain, void* workspace, int64_t workspace_bytes);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch

@@ -167,6 +167,14 @@ class VspLoudnessParams(C.Structure):
     _fields_ = [("target_lufs", C.c_float), ("peak_ceiling", C.c_float), ("max_gain_db", C.c_float)]
 
 
+class VspLimiterRow(C.Structure):
+    """``vsp_limiter_row``: a stream's samples ``[first, first + count)`` at ``in``, the outputs ``[out_first, out_first +
+    out_count)`` at ``out``, the stream's length (-1: unknown yet) and the row's ceiling (NaN: leave the row alone)."""
+    _fields_ = [("inp", C.c_void_p), ("first", C.c_int64), ("count", C.c_int64), ("out", C.c_void_p), ("out_first", C.c_int64),
+                ("out_count", C.c_int64), ("total", C.c_int64), ("ceiling", C.c_float)]
+
+
+LIMITER_MAX_ATTACK, LIMITER_MAX_HOLD, LIMITER_REACH = 1024, 8192, 12   # samples: A, H and the meter's reach J a side
 LOUDNESS_FS_MIN, LOUDNESS_FS_MAX = 8000, 192000                      # the sample rates the loudness calls take
 PROSODY_FS, PROSODY_NFFT = 44100, 1280                             # VSP_PROSODY_*
 PROSODY_MAX_CANDIDATES, PROSODY_SLOTS = 15, 16                       # VSP_PROSODY_MAX_CANDIDATES; floats of a frame in a table
@@ -319,6 +327,11 @@ SIGNATURES = {
     "vsp_loudness_apply": (_I, [_P, _P, _I, _I64, _P, _I64, _P, _I64, C.POINTER(_I64), _P, C.POINTER(VspLoudnessParams), _P, _I64]),
     "vsp_loudness_normalize": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(VspLoudnessParams), _P, _P,
                                     _P, _P, _P, _I64]),
+    "vsp_true_peak_filter": (_I, [C.POINTER(C.c_float)]),
+    "vsp_limiter_history": (_I, [_I, _I, C.POINTER(_I64), C.POINTER(_I64)]),
+    "vsp_limiter_workspace_bytes": (_I64, [_I, _I64, _I, _I]),
+    "vsp_true_peak": (_I, [_P, _P, _I, _I64, _P, _I64, C.POINTER(_I64), _P, _P, _I64]),
+    "vsp_limiter_rows": (_I, [_P, _P, _I, _I, _I, C.POINTER(VspLimiterRow), _P, _P, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

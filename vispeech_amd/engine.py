@@ -1765,6 +1765,116 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_loudness_normalize")
         return o, gains, lufs, peak, blocks
 
+    # ------------------------------------------------------------------ true peak and limiter (section 4q)
+    def limiter_history(self, attack: int, hold: int):
+        """``vsp_limiter_history``: ``(behind, ahead)`` -- the samples before an output and after it that reach it."""
+        behind, ahead = C.c_int64(), C.c_int64()
+        rc = self.lib.vsp_limiter_history(int(attack), int(hold), C.byref(behind), C.byref(ahead))
+        _lib.check(rc, None, f"vsp_limiter_history(attack = {attack}, hold = {hold})")
+        return behind.value, ahead.value
+
+    def true_peak(self, audio, n_samples):
+        """``vsp_true_peak``: the true peak (4x oversampled) of every row ``audio[b, :n_samples[b]]``,
+        ``[B]`` float32 on the device.  What lies behind a row's end is never read."""
+        a, B, stride, n_host, _ = self._loudness_rows(audio, n_samples, None)
+        tp = self._f(B)
+        ws = self._workspace("limiter", self.lib.vsp_limiter_workspace_bytes(B, 1, 0, 0))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_true_peak(self.ctx, self._stream(), B, max(n_host), _ptr(a), stride, (C.c_int64 * B)(*n_host),
+                                        _ptr(tp), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_true_peak")
+        return tp
+
+    def limiter_rows(self, rows, attack: int, hold: int, gains=None):
+        """``vsp_limiter_rows``: ONE call over rows ``(x, first, out_first, out_count, total, ceiling)`` -- ``x`` a 1-D
+        float32 device tensor holding the stream's samples ``[first, first + len(x))``, ``total`` the stream's length or -1,
+        ``ceiling`` None / NaN for a row left alone -- each at its own position.  ``gains``: one per row (a device tensor
+        stays on the device) or None for 1.  Returns ``(outs, min_gain)``: the rows' limited samples ``[out_first, out_first +
+        out_count)`` as new 1-D tensors, and ``[B]`` float32."""
+        B = len(rows)
+        if B == 0:
+            raise ValueError("limiter_rows: at least one row")
+        A, H = int(attack), int(hold)
+        desc = (_lib.VspLimiterRow * B)()
+        keep, outs = [], []
+        for b, (x, first, out_first, out_count, total, ceiling) in enumerate(rows):
+            x = x if (torch.is_tensor(x) and x.dtype == torch.float32 and x.device == self.device and x.is_contiguous()) \
+                else _dev_f32(x, self.device)
+            if x.dim() != 1:
+                raise ValueError(f"limiter_rows: row {b}: samples must be 1-D")
+            o = self._f(max(int(out_count), 0))
+            keep.append(x)
+            outs.append(o)
+            desc[b] = _lib.VspLimiterRow(x.data_ptr() if x.numel() else None, int(first), x.numel(),
+                                         o.data_ptr() if o.numel() else None, int(out_first), int(out_count),
+                                         -1 if total is None else int(total), float("nan") if ceiling is None else float(ceiling))
+        g = None
+        if gains is not None:
+            g = _dev_f32(gains, self.device)
+            if g.shape != (B,):
+                raise ValueError(f"gains must have {B} entries")
+        mg = self._f(B)
+        L_max = max(1, max(int(r[3]) for r in rows))
+        ws = self._workspace("limiter", self.lib.vsp_limiter_workspace_bytes(B, L_max, min(max(A, 0), _lib.LIMITER_MAX_ATTACK),
+                                                                             min(max(H, 0), _lib.LIMITER_MAX_HOLD)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_limiter_rows(self.ctx, self._stream(), B, A, H, desc, _ptr(g), _ptr(mg), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_limiter_rows")
+        return outs, mg
+
+    def limit(self, audio, n_samples, ceiling, gains=None, attack: int = 66, hold: int = 882, out=None):
+        """The look-ahead limiter over whole rows ``audio[b, :n_samples[b]]``: ``out = clamp(g x s,
+        -c, c)`` with the smoothed gain ``s`` that keeps ``g |x|`` -- and, up to the measured overshoot, its true peak --
+        under the row's ``ceiling`` (a scalar or one per row; None / NaN: the row is neither read nor written).  ``gains``:
+        the rows' static gains ``g`` (a device tensor stays there), None for 1.  ``attack`` (= look-ahead) and ``hold`` in
+        samples.  ``out`` None: in place where ``audio`` is a float32 device tensor.  Returns ``(out, min_gain)``."""
+        a, B, stride, n_host, _ = self._loudness_rows(audio, n_samples, None)
+        o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
+        if out is not None and o is not out:
+            raise ValueError("out must be a float32 tensor on the engine's device")
+        if ceiling is None or np.ndim(ceiling) == 0:
+            c = [float("nan") if ceiling is None else float(ceiling)] * B
+        else:
+            c = [float("nan") if v is None else float(v) for v in (ceiling.tolist() if hasattr(ceiling, "tolist") else ceiling)]
+            if len(c) != B:
+                raise ValueError(f"limiter: ceiling must be a scalar or have {B} entries")
+        A, H = int(attack), int(hold)
+        desc = (_lib.VspLimiterRow * B)()
+        for b, n in enumerate(n_host):
+            desc[b] = _lib.VspLimiterRow(a.data_ptr() + 4 * b * stride, 0, n, o.data_ptr() + 4 * b * o_stride, 0, n, n, c[b])
+        g = None
+        if gains is not None:
+            g = _dev_f32(gains, self.device)
+            if g.shape != (B,):
+                raise ValueError(f"gains must have {B} entries")
+        mg = self._f(B)
+        ws = self._workspace("limiter", self.lib.vsp_limiter_workspace_bytes(B, max(n_host), min(max(A, 0), _lib.LIMITER_MAX_ATTACK),
+                                                                             min(max(H, 0), _lib.LIMITER_MAX_HOLD)))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_limiter_rows(self.ctx, self._stream(), B, A, H, desc, _ptr(g), _ptr(mg), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_limiter_rows")
+        return o, mg
+
+    def loudness_limit(self, audio, n_samples, sample_rate: int, params, attack: int = 66, hold: int = 882, ceilings=None,
+                       static_gains=None, out=None):
+        """Normalisation with the limiter behind the gain: ``loudness_segments``, ``loudness_gate`` with the rows' ``params``
+        but an infinite ceiling -- so a row's gain is ``min(target gain, max_gain_db)``, not cut by its peak --, then ``limit``
+        at the rows' ``peak_ceiling`` (or ``ceilings``: one per row, None / NaN for a row the limiter leaves alone).  The
+        gains stay on the device.  ``static_gains`` (one per row) multiply the gate's, for rows that name a gain and no
+        target (whose gate gain is exactly 1).  A row with a NaN target and no entry in ``ceilings`` is left as it is.
+        Returns ``(out, gains, lufs, peak, blocks, min_gain)``."""
+        B = len(params)
+        inf = float("inf")
+        free = (_lib.VspLoudnessParams * B)(*[_lib.VspLoudnessParams(p.target_lufs, inf, p.max_gain_db) for p in params])
+        if ceilings is None:
+            ceilings = [float("nan") if p.target_lufs != p.target_lufs else p.peak_ceiling for p in params]
+        seg, peak = self.loudness_segments(audio, n_samples, sample_rate)
+        lufs, blocks, gains = self.loudness_gate(seg, n_samples, sample_rate, peak=peak, params=free)
+        if static_gains is not None:
+            gains = gains * _dev_f32(static_gains, self.device)
+        o, mg = self.limit(audio, n_samples, ceilings, gains=gains, attack=attack, hold=hold, out=out)
+        return o, gains, lufs, peak, blocks, mg
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

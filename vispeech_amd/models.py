@@ -262,17 +262,48 @@ class SynthesizerTrn:
 
     @torch.no_grad()
     def normalize_loudness(self, audio, n_samples, target_lufs=-23.0, peak_ceiling=1.0, max_gain_db=30.0,
-                           sample_rate: Optional[int] = None, out=None):
+                           sample_rate: Optional[int] = None, out=None, limiter=None):
         """Every row of ``audio`` [B, L] scaled to its target loudness, on the device in one call: ``g = 10^((target - L) /
         20)``, at most ``max_gain_db`` and at most ``peak_ceiling / peak``.  The three values are scalars or one per row; a row
         whose target is None or NaN, and a row of no loudness (-inf), is left as it is (gain exactly 1).  In place where
         ``audio`` is a float32 tensor on the model's device and ``out`` is None; samples at or behind ``n_samples[b]`` are not
-        touched.  Returns ``(audio, gains)``.  ``infer(...)[0][:, 0]`` and ``convert_audio(...)[0][:, 0]`` are such batches."""
+        touched.  Returns ``(audio, gains)``.  ``infer(...)[0][:, 0]`` and ``convert_audio(...)[0][:, 0]`` are such batches.
+
+        ``limiter``: ``True`` or ``dict(attack_ms=, hold_ms=)`` puts the look-ahead limiter (``limit``) behind the gain: a
+        row's gain is ``min(target gain, max_gain_db)``, no longer cut by its sample peak -- one transient does not pull the
+        whole row under its target --, and the limiter holds the row under ``peak_ceiling``.  Segments, gate and limiter run
+        in this order with the gains staying on the device."""
         fs = int(self.sampling_rate if sample_rate is None else sample_rate)
         eng = self._engine
         B = len(n_samples)
-        res = eng.loudness_normalize(audio, n_samples, fs, eng.loudness_params(B, target_lufs, peak_ceiling, max_gain_db), out=out)
+        params = eng.loudness_params(B, target_lufs, peak_ceiling, max_gain_db)
+        if limiter is None or limiter is False:
+            res = eng.loudness_normalize(audio, n_samples, fs, params, out=out)
+            return res[0], res[1]
+        from . import limiter as _limiter
+        if limiter is not True and set(limiter) - {"attack_ms", "hold_ms"}:
+            raise ValueError("normalize_loudness: limiter is True or a mapping of attack_ms and hold_ms")
+        A, H, _, _ = _limiter.spec(limiter, fs)
+        res = eng.loudness_limit(audio, n_samples, fs, params, attack=A, hold=H, out=out)
         return res[0], res[1]
+
+    @torch.no_grad()
+    def true_peak(self, audio, n_samples):
+        """The true peak (4x oversampled) of every row ``audio[b, :n_samples[b]]``: ``[B]`` float32 on the
+        device, linear.  What lies behind a row's end is never read.  Needs no weights."""
+        return self._engine.true_peak(audio, n_samples)
+
+    @torch.no_grad()
+    def limit(self, audio, n_samples, ceiling=1.0, gains=None, attack_ms: Optional[float] = None, hold_ms: Optional[float] = None,
+              sample_rate: Optional[int] = None, out=None):
+        """The look-ahead limiter over every row of a ragged batch: ``gains[b] * audio[b]`` held under
+        ``ceiling`` (a scalar or one per row; None / NaN leaves the row alone) by a smoothed gain that looks ``attack_ms``
+        (1.5) ahead and holds for ``hold_ms`` (20).  In place where ``audio`` is a float32 tensor on the model's device and
+        ``out`` is None.  Returns ``(audio, min_gain)``: ``min_gain[b]`` is the smallest gain the limiter applied to the row."""
+        from . import limiter as _limiter
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        A, H = _limiter.window(fs, attack_ms, hold_ms)
+        return self._engine.limit(audio, n_samples, ceiling, gains=gains, attack=A, hold=H, out=out)
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)

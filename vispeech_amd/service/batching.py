@@ -59,6 +59,41 @@ def _loudness_spec(loudness):
     return (t, c, m)
 
 
+def _limiter_spec(value, loudness, fs: int):
+    """``(attack, hold, ceiling, gain)`` -- samples, samples, linear, linear -- of a request or service that names a limiter
+    (``vispeech_amd.limiter.spec``): ``True`` or a mapping of ``attack_ms``, ``hold_ms``, ``ceiling`` and ``gain_db``.  The
+    ceiling it does not name is its loudness's ``peak_ceiling`` (``loudness``: a ``_loudness_spec``), or 1."""
+    from .. import limiter
+    return limiter.spec(value, fs, default_ceiling=1.0 if loudness is None else loudness[1])
+
+
+def level_rows(eng, reqs, waves, n, fs: int) -> None:
+    """The level control of a batch in which a request names a limiter, on ``waves`` [B, L] in place (row b's first
+    ``n[b]`` samples).  A request with a loudness and no limiter: the peak-cut normalisation it always got
+    (``Engine.loudness_normalize``).  A request with a limiter: its gain -- the loudness gain NOT cut by the peak, or its
+    ``gain_db`` -- and ONE limiter call for all of them (one per distinct attack and hold), the gains staying on the
+    device.  Everybody else is neither read nor written."""
+    from ..engine import Engine
+    nan = float("nan")
+    B = len(reqs)
+    n_host = [max(int(v), 1) for v in n]
+    live = [n[b] >= 1 for b in range(B)]
+    plain = [live[b] and r.loudness is not None and r.limiter is None for b, r in enumerate(reqs)]
+    if any(plain):
+        spec = [r.loudness if plain[b] else (nan, 1.0, 0.0) for b, r in enumerate(reqs)]
+        eng.loudness_normalize(waves, n_host, fs, Engine.loudness_params(B, *zip(*spec)))
+    for A, H in sorted({r.limiter[:2] for b, r in enumerate(reqs) if live[b] and r.limiter is not None}):
+        rows = [live[b] and r.limiter is not None and r.limiter[:2] == (A, H) for b, r in enumerate(reqs)]
+        ceilings = [r.limiter[2] if rows[b] else nan for b, r in enumerate(reqs)]
+        static = [r.limiter[3] if rows[b] and r.loudness is None else 1.0 for b, r in enumerate(reqs)]
+        if any(rows[b] and r.loudness is not None for b, r in enumerate(reqs)):
+            spec = [r.loudness if rows[b] and r.loudness is not None else (nan, 1.0, 0.0) for b, r in enumerate(reqs)]
+            eng.loudness_limit(waves, n_host, fs, Engine.loudness_params(B, *zip(*spec)), attack=A, hold=H, ceilings=ceilings,
+                               static_gains=None if all(g == 1.0 for g in static) else static)
+        else:
+            eng.limit(waves, n_host, ceilings, gains=static, attack=A, hold=H)
+
+
 def _row_formats(eng, reqs, base_rate: int, model_rate: int):
     """Per request the ``(rate, VSP_OUT_*)`` of its row in an ``Engine.output_rows`` call: its own format, or -- for a
     request that names none -- (the service's rate, PCM16), the bytes it gets on the service's own path.  Rates the engine's
@@ -124,8 +159,9 @@ class _Request:
     keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
     ``noise_scale``; a conversion's noise scale is its row's."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None, loudness=None):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None, loudness=None, limiter=None):
         self.row, self.seed, self.scales = row, int(seed), scales
+        self.limiter = limiter        # ``_limiter_spec``: (attack, hold, ceiling, gain) of the limiter behind the request's gain, or None
         self.loudness = loudness      # ``_loudness_spec``: the level the request's waveform is brought to, or None
         self.out_fmt = out_fmt        # ``_output_format``: the request's own output rate and encoding, or None
         self.prosody = prosody        # a ``_Recording``: the row's f0 / energy come from it (``_prosody_controls``), or None
@@ -365,11 +401,17 @@ class BatchingSynthesisService:
     ``loudness``: the level every request of this service is brought to unless it names its own (``submit(loudness=)``;
     False there: none) -- a target in LUFS or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: none.  A batch in
     which a request has one makes ONE ``Engine.loudness_normalize`` call on the generator's output, in place, before the
-    output stage; a batch in which nobody has one makes exactly the calls it always made."""
+    output stage; a batch in which nobody has one makes exactly the calls it always made.
+    ``limiter``: the look-ahead limiter behind every request's gain unless it names its own
+    (``submit(limiter=)``; False there: none) -- True or a mapping of (attack_ms, hold_ms, ceiling, gain_db); None: none.  A
+    request with a loudness and a limiter gets the gain of its target NOT cut by its peak and the limiter at its
+    ``peak_ceiling`` (``normalize_loudness(limiter=)``); one with a limiter only gets ``gain_db`` (0) and the limiter at
+    ``ceiling`` (1).  ONE limiter call per batch, before the output stage; a batch in which nobody names a limiter makes
+    exactly the calls it made before."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
                  spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None,
-                 prosody_align=None, loudness=None):
+                 prosody_align=None, loudness=None, limiter=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -386,6 +428,8 @@ class BatchingSynthesisService:
             prosody_align = Engine._align_params(prosody_align)      # (refused here, not in the worker)
         self.prosody_align = prosody_align or None
         self.loudness = _loudness_spec(loudness)
+        self.limiter = limiter if limiter is not None and limiter is not False else None
+        _limiter_spec(self.limiter, self.loudness, self.sampling_rate)             # (refused here, not in the worker)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -397,7 +441,7 @@ class BatchingSynthesisService:
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
                noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, prosody_audio=None,
                prosody_sample_rate: Optional[int] = None, prosody_encoding=None, prosody_sid=None,
-               loudness=None) -> "concurrent.futures.Future":
+               loudness=None, limiter=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
         The future's result is the request's PCM16 samples (numpy int16, valid part only).
@@ -415,7 +459,9 @@ class BatchingSynthesisService:
         On a service with ``prosody_align`` a row without durations is accepted: the worker aligns its text to the recording
         first (``prosody_sid``: the recording's speaker where it is not the row's).
         ``loudness``: the integrated loudness (BS.1770, LUFS) the request's waveform is brought to before it is encoded -- a
-        target, or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: the service's; False: none."""
+        target, or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: the service's; False: none.
+        ``limiter``: the limiter behind the request's gain -- True or a mapping of (attack_ms, hold_ms, ceiling, gain_db);
+        None: the service's; False: none."""
         prosody = None
         if prosody_sid is not None:
             n_spk = getattr(self.net, "n_speakers", None)
@@ -438,11 +484,11 @@ class BatchingSynthesisService:
         elif prosody_sid is not None:
             raise ValueError("prosody_sid names the speaker of prosody_audio: pass it")
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                      _output_format(output_rate, output_encoding), prosody, self._loudness_of(loudness)))
+                                      _output_format(output_rate, output_encoding), prosody, *self._level_of(loudness, limiter)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None, loudness=None) -> "concurrent.futures.Future":
+                          output_encoding=None, loudness=None, limiter=None) -> "concurrent.futures.Future":
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
         PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
         ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
@@ -450,19 +496,30 @@ class BatchingSynthesisService:
         ``sample_rate`` / ``encoding`` (``vispeech_amd.input_stage``): ``audio`` is raw -- an array of the encoding's dtype or
         ``bytes`` -- at that rate; the batch's raw recordings go through the input stage on the GPU, one call per distinct
         (rate, encoding), before the one ``convert_latent``.  ``output_rate`` / ``output_encoding`` / ``loudness``: as in
-        ``submit`` (the level is that of the converted waveform; the recording is not normalised before conversion)."""
+        ``submit`` (the level is that of the converted waveform; the recording is not normalised before conversion);
+        ``limiter``: as in ``submit``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
-                                      out_fmt=_output_format(output_rate, output_encoding), loudness=self._loudness_of(loudness)))
+                                      out_fmt=_output_format(output_rate, output_encoding),
+                                      **dict(zip(("loudness", "limiter"), self._level_of(loudness, limiter)))))
 
     def _loudness_of(self, loudness):
         return self.loudness if loudness is None else _loudness_spec(loudness)
+
+    def _level_of(self, loudness, limiter):
+        """``(loudness, limiter)`` specs of a request: its own, or the service's."""
+        loud = self._loudness_of(loudness)
+        return loud, _limiter_spec(self.limiter if limiter is None else limiter, loud, self.sampling_rate)
 
     def _normalize(self, reqs, waves, n) -> None:
         """The requests that have a loudness: ONE ``Engine.loudness_normalize`` call over the batch's rows ``waves`` [B, L]
         (the generator's output, row b's first ``n[b]`` samples), in place, at the model's rate.  A row that asks for nothing
         carries a NaN target and is neither read nor written by the apply; a batch in which nobody asks makes no call."""
-        if all(r.loudness is None for r in reqs) or waves.shape[-1] == 0:
+        if waves.shape[-1] == 0:
+            return
+        if any(r.limiter is not None for r in reqs):
+            return level_rows(self.net._engine, reqs, waves, n, self.sampling_rate)
+        if all(r.loudness is None for r in reqs):
             return
         from ..engine import Engine
         nan = float("nan")

@@ -9,9 +9,9 @@ from typing import Optional
 
 import numpy as np
 
-from .. import input_stage, output_stage
+from .. import input_stage, limiter, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
-from .batching import _Conversion, _Request, _collate_from, _input_format, _output_format, _row_formats, latents
+from .batching import _Conversion, _Request, _collate_from, _input_format, _limiter_spec, _output_format, _row_formats, latents
 
 
 class _RowStream:
@@ -58,8 +58,9 @@ class _RowStream:
 class _StreamRequest(_Request):
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None):
-        super().__init__(row, seed, scales, out_fmt)
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, limiter=None):
+        super().__init__(row, seed, scales, out_fmt, limiter=limiter)
+        self.lim = None               # a request with a limiter: its ``limiter.Stream``, from its first tick on
         self.stream = _RowStream()
         self.z = self.g = None
         self.L = self.pos = 0
@@ -119,8 +120,8 @@ class _LiveRequest(_StreamRequest):
     on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
     ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
 
-    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None):
-        super().__init__(None, seed, out_fmt=out_fmt)
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None, limiter=None):
+        super().__init__(None, seed, out_fmt=out_fmt, limiter=limiter)
         self.stream = stream
         self.fmt = stream._fmt        # (rate, encoding) of the feed: its pieces go through ``input`` before they reach ``buf``
         self.input = None             # the session's ``input_stage.Stream``, from its first piece on
@@ -173,7 +174,13 @@ class StreamingBatchService:
     each with its request's rate, encoding and ``output_stage.RowState``, and one device-to-host copy; a request that ends
     gets its filter's tail in the same call; requests that name nothing ride at (the service's rate, PCM16) and get the
     bytes of their own path.  A tick without such a request is the tick described above.  ``fused_output=True`` refuses
-    a request's own format (``ValueError``)."""
+    a request's own format (``ValueError``).
+    They also take ``limiter=`` (True or a mapping of attack_ms, hold_ms, ceiling, gain_db): a fixed gain held under a
+    ceiling by the look-ahead limiter, the level control a stream can have.  A tick in which an
+    active request has one runs on the same ``output_rows`` path, with ONE ``limiter.push_rows`` call for those rows between
+    the generator and ``output_rows``; the request's last chunk flushes its limiter.  Its bytes are those of
+    ``SynthesizerTrn.limit`` on its whole waveform, then the output stage; its delay grows by attack + 12 samples.
+    ``fused_output=True`` refuses the keyword as well."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
@@ -213,33 +220,46 @@ class StreamingBatchService:
                              "output_encoding needs fused_output=False")
         return fmt
 
+    def _limiter(self, limiter):
+        """A request's ``limiter=``: ``(attack, hold, ceiling, gain)`` or None (``batching._limiter_spec``)."""
+        if limiter is None or limiter is False:
+            return None
+        if self.fused_output:
+            raise ValueError("fused_output delivers every row through its one launch: a request's limiter needs fused_output=False")
+        return _limiter_spec(limiter, None, self.sampling_rate)
+
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None) -> _RowStream:
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, limiter=None) -> _RowStream:
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
         1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
         request's PCM16 ``bytes``, one piece per tick the request takes part in.
         ``output_rate`` / ``output_encoding`` ("f32", "s16", "ulaw", "alaw"): the request's own delivery format; its
-        ``bytes`` are then little-endian elements of that encoding at that rate (see the class text)."""
+        ``bytes`` are then little-endian elements of that encoding at that rate (see the class text).
+        ``limiter``: the look-ahead limiter in front of the request's output stage -- True or a
+        mapping of (attack_ms, hold_ms, ceiling, gain_db): the level control a stream can have, a fixed gain held under a
+        ceiling.  The request's bytes are those of ``SynthesizerTrn.limit`` on its whole waveform, then the output stage;
+        its delay grows by attack + 12 samples.  A tick in which a request has one runs as a tick in which a request names
+        a format does, with ONE ``limiter.push_rows`` call for those rows between the generator and ``output_rows``."""
         return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                            self._out_fmt(output_rate, output_encoding)))
+                                            self._out_fmt(output_rate, output_encoding), self._limiter(limiter)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None) -> _RowStream:
+                          output_encoding=None, limiter=None) -> _RowStream:
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
         the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
         frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
         NOT the service's text-to-speech ``noise_scale``).  ``sample_rate`` / ``encoding``: ``audio`` is raw samples in that
         format (an array of the encoding's dtype or ``bytes``); admission runs the group's raw recordings through the
         input stage, one call per distinct (rate, encoding), before its one ``convert_latent``.  ``output_rate`` /
-        ``output_encoding``: as in ``submit``."""
+        ``output_encoding`` / ``limiter``: as in ``submit``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
-                                            out_fmt=self._out_fmt(output_rate, output_encoding)))
+                                            out_fmt=self._out_fmt(output_rate, output_encoding), limiter=self._limiter(limiter)))
 
     def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                         sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                        output_encoding=None) -> LiveConversion:
+                        output_encoding=None, limiter=None) -> LiveConversion:
         """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
         ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
         ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``).
@@ -248,8 +268,9 @@ class StreamingBatchService:
         appends the model-rate samples that are complete to the session's buffer; ``end()`` flushes the filter's tail.
         Readiness is decided on those samples, so the session's delay grows by the filter's half length: ``zeros`` = 32
         input periods (2 ms at 16 kHz).  ``output_rate`` / ``output_encoding``: as in ``submit``; on that path a frame
-        need not be a whole number of output samples."""
+        need not be a whole number of output samples.  ``limiter``: as in ``submit``."""
         out_fmt = self._out_fmt(output_rate, output_encoding)
+        limiter = self._limiter(limiter)
         if self.fused_output:
             # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
             # filter's phase and its history must not see the shift
@@ -269,7 +290,7 @@ class StreamingBatchService:
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         if fmt is not None and fmt[0] not in self.net._engine.input_rates:
             self.net._engine.configure_input(fmt[0], model_rate=self.sampling_rate)      # (allocates: here, not in a tick)
-        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt))
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt, limiter))
 
     def _enqueue(self, req: _StreamRequest) -> _RowStream:
         """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
@@ -490,7 +511,7 @@ class StreamingBatchService:
             counts.append(f1 - r.pos)
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
-        if any(r.out_fmt is not None for r in reqs):
+        if any(r.out_fmt is not None or r.limiter is not None for r in reqs):
             return self._deliver_rows(reqs, rows, counts)
         for r in reqs:
             if r.row_state is not None:        # it shared earlier ticks with requests that name a format
@@ -527,16 +548,32 @@ class StreamingBatchService:
         base = self.sampling_rate if self.output_rate is None else self.output_rate
         fmts = _row_formats(eng, reqs, base, self.sampling_rate)
         out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=False)
-        job = []
+        pieces = [out[b, : n * hop] for b, n in enumerate(counts)]
+        first = [(getattr(r, "e0", 0) + r.pos) * hop for r in reqs]
+        limited = [b for b, r in enumerate(reqs) if r.limiter is not None]
+        for b in limited:
+            r = reqs[b]
+            if r.lim is None:
+                r.lim = limiter.Stream(eng, r.limiter[2], gain=r.limiter[3], attack=r.limiter[0], hold=r.limiter[1])
+            first[b] = r.lim.out_next                                   # the output stage sees the limiter's samples
+        for window in sorted({reqs[b].limiter[:2] for b in limited}):   # (one call: a tick's limiters share attack and hold as a rule)
+            group = [b for b in limited if reqs[b].limiter[:2] == window]
+            done = limiter.push_rows(eng, [(reqs[b].lim, pieces[b], reqs[b].pos + counts[b] >= reqs[b].L) for b in group])
+            for b, y in zip(group, done):
+                pieces[b] = y
+        job, rode = [], []
         for b, (r, n, (rate, enc)) in enumerate(zip(reqs, counts, fmts)):
             if r.row_state is None:
-                self._enter_rows_path(r, rate, (getattr(r, "e0", 0) + r.pos) * hop)
+                self._enter_rows_path(r, rate, first[b])
             r.pos += n
-            job.append((out[b, : n * hop], r.pos >= r.L, rate, enc, r.row_state))
+            if pieces[b].shape[0] or r.pos >= r.L:                      # (a limiter's first short chunk may complete no sample)
+                job.append((pieces[b], r.pos >= r.L, rate, enc, r.row_state))
+                rode.append(b)
         buf, spans = eng.output_rows(job)
         host = _host(buf)                                               # the tick's one device-to-host copy
         _check_numerics(self.net)
-        for r, (off, cnt), (_, enc) in zip(reqs, spans, fmts):
+        for b, (off, cnt) in zip(rode, spans):
+            r, enc = reqs[b], fmts[b][1]
             if cnt:                            # (a short chunk at a low rate may complete no output sample)
                 r.stream._q.put(host[off:off + cnt * output_stage.element_size(enc)].tobytes())
 
