@@ -1172,7 +1172,8 @@ int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, in
  * max_gain_db; a workspace too small is VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload of its rows (20
  * bytes a row: the lengths and the params, pageable host memory as the prosody calls'), allocates nothing and does not
  * synchronise.  n_samples_host, params_host: HOST arrays [B].
- * Not computed: true peak (sample peak only; the meter of the next section has it), stereo and channel weights, momentary and short-term loudness, loudness range. */
+ * Not computed: true peak (sample peak only; the meter of a later section has it), stereo and channel weights, loudness
+ * range.  Momentary, short-term and running loudness: "loudness over time" below. */
 typedef struct vsp_loudness_params {
   float target_lufs, peak_ceiling, max_gain_db;
 } vsp_loudness_params;
@@ -1203,6 +1204,85 @@ int vsp_loudness_apply(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const f
 int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                            float* out, int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_params* params_host,
                            float* lufs, float* peak, float* gains, int32_t* blocks, void* workspace, int64_t workspace_bytes);
+
+/* ---- loudness over time (round 23, ABI 7, additive) ------------------ */
+/* Momentary, short-term and running integrated loudness per 100 ms of a row or of a STREAM, and a causal leveller steered
+ * by the running level.  The specification is this project's own, restated in fp64 in tests/loudness_time_ref.py.  A row
+ * (or stream) is x[0 .. n), mono float32 at fs.  h, the K-weighting, seg[s], the block energy E_j, Z_abs and both gates are
+ * those of "loudness" above, unchanged.  F = n / h in integers: the COMPLETE segments.
+ *   per complete segment s = 0 .. F - 1, float32:
+ *     M[s]     momentary, 400 ms: s >= 3: -0.691 + 10 log10(E_(s-3) / (4 h)); -inf for s < 3 or E = 0.
+ *     S[s]     short-term, 3 s: s >= 29: -0.691 + 10 log10(T_s / (30 h)), T_s = seg[s-29] + ... + seg[s] summed ascending
+ *              from 0 in double; -inf before that or for T = 0.
+ *     I[s]     running integrated: L of "loudness" above over the first (s + 1) h samples (for s < 3 its one-block rule);
+ *              kept[s] (int32) that prefix's kept count.
+ *   per row    M_max, S_max (-inf where there are none); I_end = L of the whole row.
+ *   leveller   per row target_lufs (NaN: the row is neither read nor written), max_gain_db >= 0, max_cut_db >= 0,
+ *              slew_db_per_s > 0, initial_gain_db; d = fl32(slew_db_per_s / 10).  The gain in dB per segment, float32 adds,
+ *              subtracts, mins and maxes only:
+ *                q[s] = c_dB[s-1] if I[s] = -inf, else min(max(fl32(target - I[s]), -max_cut_db), max_gain_db)
+ *                c_dB[s] = c_dB[s-1] + min(max(q[s] - c_dB[s-1], -d), d),  c_dB[-1] = initial_gain_db
+ *                c[s] = fl32(10^(c_dB[s] / 20))  (the only transcendental; c[-1] likewise from initial_gain_db)
+ *   apply      sample i = s h + k, 0 <= k < h, in any segment, the row's partial last one included: c0 = c[s-2], c1 =
+ *              c[s-1] (indices below 0 read c[-1]); w = fl32(fl32(k + 1) rh), rh = fl32(1 / h); a = fl32(c0 + fl32(fl32(c1 -
+ *              c0) w)); out[i] = fl32(a x[i]).  No product is fused with a sum.  A steady level gives a == c0 exactly.
+ * The gain over segment s depends on x[0 .. s h) only: no look-ahead, no added delay, and a sample can leave in the call
+ * it arrives in.  The leveller does not clamp; a limiter behind it runs on its output.
+ * Nothing at or behind n_b is read or written; a row's bits do not depend on its batch; and a stream's table entries and
+ * levelled samples are, bit for bit, those of the one call on the whole row, under ANY split: entry s is computed from
+ * seg[0 .. s] in an order that depends on s alone, and the K-weighting's state crosses calls in double, exactly as it
+ * crosses segments.  The cost of entry s grows with s (both gate passes run over the prefix's blocks).
+ * Rows of time, level_gains and level_apply are described by pointers of their own (streams allocated apart advance in one
+ * call); every table starts at the row's segment 0.  Refused with VSP_ERR_ARG on the host before any launch, naming the
+ * row: a piece that does not start on a segment boundary, first + count above the table, a negative or NaN max_gain_db or
+ * max_cut_db, slew_db_per_s not above 0, a non-finite initial_gain_db, fs out of range; a workspace too small is
+ * VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload, allocates nothing and does not synchronise.
+ * Not computed: loudness range, stereo, steering by the short-term level. */
+typedef struct vsp_loudness_level_params {
+  float target_lufs, max_gain_db, max_cut_db, slew_db_per_s, initial_gain_db;
+} vsp_loudness_level_params;
+typedef struct vsp_loudness_row {
+  const double* seg;            /* time: the row's segment energies, from segment 0 (device, as every pointer here) */
+  float *M, *S, *I;             /* time writes them; level_gains reads I */
+  int32_t* kept;                /* time */
+  float *c_db, *c;              /* level_gains writes them (and reads c_db[first - 1]); level_apply reads c */
+  int64_t first, count;         /* time, level_gains: the entries [first, first + count) */
+  int64_t entries;              /* time, level_gains: the entries the row's tables can hold; level_apply: the entries of c that are valid */
+  const float* in;              /* level_apply: the stream's samples [pos, pos + samples) */
+  float* out;                   /* level_apply: receives them levelled; may be `in` */
+  int64_t pos, samples;
+} vsp_loudness_row;
+/* Workspace of any call of this section for B rows of up to L_max samples (VSP_ERR_ARG as a negative size); monotone in B
+ * and L_max.  time, level_gains and level_apply need that of L_max = 1. */
+int64_t vsp_loudness_time_workspace_bytes(int B, int64_t L_max, int sample_rate);
+/* vsp_loudness_segments carried across calls: row b is the piece audio[b][0 .. n_b) of a stream, starting at the stream's
+ * sample first_host[b] (HOST [B]; NULL: 0), which must be a multiple of h.  state_in [B][4] double (device; NULL: zero):
+ * the K-weighting's state in front of the piece; state_out [B][4] (device; NULL: not wanted; may be state_in): the state
+ * behind the piece's last COMPLETE segment (state_in where it has none).  seg [B][S(L_max)] and peak [B] are those of the
+ * piece.  The same three launches; with both states NULL, vsp_loudness_segments in every bit. */
+int vsp_loudness_segments_from(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                               const int64_t* n_samples_host, const int64_t* first_host, const double* state_in, double* state_out,
+                               double* seg, float* peak, void* workspace, int64_t workspace_bytes);
+/* The table operator alone, on ANY double tables: M, S, I, kept [first, first + count) of every row from its seg[0 .. first +
+ * count).  m_max, s_max: [B] float32 (device), the largest M and S among THIS call's entries (-inf where none), or both
+ * NULL.  One launch, one wave per (row, entry), and one for the maxima.  rows_host: HOST [B]. */
+int vsp_loudness_time(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, float* m_max, float* s_max,
+                      void* workspace, int64_t workspace_bytes);
+/* c_db, c [first, first + count) of every row from ANY table I, continuing from c_db[first - 1] of the row's own table
+ * (initial_gain_db at first = 0): nothing is read back.  One launch, one lane per row. */
+int vsp_loudness_level_gains(vsp_ctx* ctx, void* stream, int B, const vsp_loudness_row* rows_host,
+                             const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes);
+/* The samples [pos, pos + samples) of every row against its c table, which must hold (pos + samples - 1) / h entries.  One
+ * launch; 16-byte accesses where in and out are 16-byte aligned. */
+int vsp_loudness_level_apply(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host,
+                             const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes);
+/* Whole rows audio[b][0 .. n_b) behind one upload: segments, L of the row (i_end), the time tables, and with params_host
+ * (else NULL: a meter; out, c_db and c are not used) gains and apply.  M, S, I, kept, c_db, c: [B][table_stride], table_stride >=
+ * L_max / h, written for s < F_b only; m_max, s_max, i_end, peak: [B] float32.  seg lives in the workspace. */
+int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride, float* out,
+                       int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_level_params* params_host, float* M, float* S,
+                       float* I, int32_t* kept, float* c_db, float* c, int64_t table_stride, float* m_max, float* s_max, float* i_end,
+                       float* peak, void* workspace, int64_t workspace_bytes);
 
 /* ---- true peak and look-ahead limiter (round 22, ABI 7, additive) --- */
 /* A true-peak meter and a look-ahead limiter without a recurrence, per row of a ragged batch of mono float32 rows or of a

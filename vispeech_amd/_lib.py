@@ -167,6 +167,21 @@ class VspLoudnessParams(C.Structure):
     _fields_ = [("target_lufs", C.c_float), ("peak_ceiling", C.c_float), ("max_gain_db", C.c_float)]
 
 
+class VspLoudnessLevelParams(C.Structure):
+    """``vsp_loudness_level_params``: one row's leveller -- target (LUFS; NaN: leave the row alone), largest gain and cut (dB),
+    slew (dB a second) and the gain it starts from (dB)."""
+    _fields_ = [("target_lufs", C.c_float), ("max_gain_db", C.c_float), ("max_cut_db", C.c_float), ("slew_db_per_s", C.c_float),
+                ("initial_gain_db", C.c_float)]
+
+
+class VspLoudnessRow(C.Structure):
+    """``vsp_loudness_row``: one row (or stream) of the loudness-over-time calls, by pointers of its own; every table starts at
+    the row's segment 0."""
+    _fields_ = [("seg", C.c_void_p), ("M", C.c_void_p), ("S", C.c_void_p), ("I", C.c_void_p), ("kept", C.c_void_p),
+                ("c_db", C.c_void_p), ("c", C.c_void_p), ("first", C.c_int64), ("count", C.c_int64), ("entries", C.c_int64),
+                ("inp", C.c_void_p), ("out", C.c_void_p), ("pos", C.c_int64), ("samples", C.c_int64)]
+
+
 class VspLimiterRow(C.Structure):
     """``vsp_limiter_row``: a stream's samples ``[first, first + count)`` at ``in``, the outputs ``[out_first, out_first +
     out_count)`` at ``out``, the stream's length (-1: unknown yet) and the row's ceiling (NaN: leave the row alone)."""
@@ -327,6 +342,13 @@ SIGNATURES = {
     "vsp_loudness_apply": (_I, [_P, _P, _I, _I64, _P, _I64, _P, _I64, C.POINTER(_I64), _P, C.POINTER(VspLoudnessParams), _P, _I64]),
     "vsp_loudness_normalize": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(VspLoudnessParams), _P, _P,
                                     _P, _P, _P, _I64]),
+    "vsp_loudness_time_workspace_bytes": (_I64, [_I, _I64, _I]),
+    "vsp_loudness_segments_from": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), C.POINTER(_I64), _P, _P, _P, _P, _P, _I64]),
+    "vsp_loudness_time": (_I, [_P, _P, _I, _I, C.POINTER(VspLoudnessRow), _P, _P, _P, _I64]),
+    "vsp_loudness_level_gains": (_I, [_P, _P, _I, C.POINTER(VspLoudnessRow), C.POINTER(VspLoudnessLevelParams), _P, _I64]),
+    "vsp_loudness_level_apply": (_I, [_P, _P, _I, _I, C.POINTER(VspLoudnessRow), C.POINTER(VspLoudnessLevelParams), _P, _I64]),
+    "vsp_loudness_level": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(VspLoudnessLevelParams), _P, _P, _P,
+                                _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64]),
     "vsp_true_peak_filter": (_I, [C.POINTER(C.c_float)]),
     "vsp_limiter_history": (_I, [_I, _I, C.POINTER(_I64), C.POINTER(_I64)]),
     "vsp_limiter_workspace_bytes": (_I64, [_I, _I64, _I, _I]),

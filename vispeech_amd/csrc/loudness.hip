@@ -137,6 +137,8 @@ struct SegArgs {
   double* seg;             // [B][S_max]
   unsigned* peak_bits;     // [B]
   int S_max;
+  const double* state_in;  // [B][4] the state every row starts from (NULL: zero)
+  double* state_out;       // [B][4] the state behind every row's last COMPLETE segment (NULL: not wanted); may be state_in
 };
 
 __global__ void __launch_bounds__(64) lk_ends_kernel(const SegArgs g, const KW kw) {
@@ -144,7 +146,8 @@ __global__ void __launch_bounds__(64) lk_ends_kernel(const SegArgs g, const KW k
   const int b = blockIdx.y, s = blockIdx.x, lane = threadIdx.x;
   const int n = g.rows.n[b];
   const int S = (n + kw.h - 1) / kw.h;
-  if (s >= S - 1) return;                          // (uniform) the row's last segment hands its state to nobody
+  // (uniform) the row's last segment hands its state to nobody -- unless the state behind the last complete one is wanted
+  if (s >= (g.state_out ? n / kw.h : S - 1)) return;
   stage_segment(g.audio + (size_t)b * g.stride + (size_t)s * kw.h, kw.h, lk_lds, kw.r, kw.pitch, lane);
   __syncthreads();
   double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -170,12 +173,16 @@ __global__ void __launch_bounds__(64) lk_carry_kernel(const SegArgs g, const KW 
   const int b = blockIdx.x, lane = threadIdx.x;
   const int n = g.rows.n[b];
   const int S = (n + kw.h - 1) / kw.h;
+  const int F = n / kw.h, have = g.state_out ? F : S - 1;      // complete segments; segments whose end state lk_ends left
   if (lane == 0) g.peak_bits[b] = 0u;
   double st[4] = {0.0, 0.0, 0.0, 0.0};
+  if (g.state_in)
+    for (int i = 0; i < 4; ++i) st[i] = g.state_in[4 * (size_t)b + i];
+  double fin[4] = {st[0], st[1], st[2], st[3]};                // the state behind F segments (F = 0: the one it started from)
   for (int s0 = 0; s0 < S; s0 += 64) {
     const int s = s0 + lane;
     double e[4] = {0.0, 0.0, 0.0, 0.0};
-    if (s < S - 1) {
+    if (s < have) {
       const double* p = g.ends + ((size_t)b * g.S_max + s) * 4;
       for (int i = 0; i < 4; ++i) e[i] = p[i];
     }
@@ -189,13 +196,18 @@ __global__ void __launch_bounds__(64) lk_carry_kernel(const SegArgs g, const KW 
         nx[i] = ej[i];
       }
       matvec_add(kw.H, st, nx);
-      for (int i = 0; i < 4; ++i) st[i] = nx[i];
+      for (int i = 0; i < 4; ++i) {
+        st[i] = nx[i];
+        if (s0 + j + 1 == F) fin[i] = nx[i];
+      }
     }
     if (s < S) {
       double* p = g.starts + ((size_t)b * g.S_max + s) * 4;
       for (int i = 0; i < 4; ++i) p[i] = mine[i];
     }
   }
+  if (g.state_out && lane == 0)
+    for (int i = 0; i < 4; ++i) g.state_out[4 * (size_t)b + i] = fin[i];
 }
 
 __global__ void __launch_bounds__(64) lk_energy_kernel(const SegArgs g, const KW kw) {
@@ -246,17 +258,18 @@ struct GateArgs {
   double z_abs;
 };
 
-__global__ void __launch_bounds__(64) lk_gate_kernel(const GateArgs g) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = g.rows.n[b];
-  const double* __restrict__ seg = g.seg + (size_t)b * g.S_max;
-  const bool four = n >= 4 * g.h;
-  const int NB = four ? n / g.h - 3 : 1;
-  const double D = four ? 4.0 * (double)g.h : (double)n;
+struct Gated { float L; int NB, kept; };
+
+// Both gates over the blocks of seg's first n samples, by one wave: the row of lk_gate_kernel, and every prefix of a row in
+// lk_time_kernel -- ONE body, so that the running level of a prefix is the integrated loudness of that prefix in every bit.
+__device__ __forceinline__ Gated gate_wave(const double* __restrict__ seg, int n, int h, double z_abs, int lane) {
+  const bool four = n >= 4 * h;
+  const int NB = four ? n / h - 3 : 1;
+  const double D = four ? 4.0 * (double)h : (double)n;
   auto energy = [&](int j) {
     if (four) return ((seg[j] + seg[j + 1]) + seg[j + 2]) + seg[j + 3];
     double E = 0.0;
-    const int S = (n + g.h - 1) / g.h;
+    const int S = (n + h - 1) / h;
     for (int s = 0; s < S; ++s) E += seg[s];
     return E;
   };
@@ -278,10 +291,19 @@ __global__ void __launch_bounds__(64) lk_gate_kernel(const GateArgs g) {
   };
   double sum_abs, sum_kept;
   int n_abs, n_kept;
-  gated([&](double E) { return E / D > g.z_abs; }, sum_abs, n_abs);
+  gated([&](double E) { return E / D > z_abs; }, sum_abs, n_abs);
   const double mean_abs = n_abs ? sum_abs / (double)n_abs : 0.0;
-  gated([&](double E) { return E / D > g.z_abs && 10.0 * E > mean_abs; }, sum_kept, n_kept);
+  gated([&](double E) { return E / D > z_abs && 10.0 * E > mean_abs; }, sum_kept, n_kept);
   const float L = n_kept ? (float)(-0.691 + 10.0 * log10(sum_kept / (double)n_kept / D)) : -INFINITY;
+  return {L, NB, n_kept};
+}
+
+__global__ void __launch_bounds__(64) lk_gate_kernel(const GateArgs g) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = g.rows.n[b];
+  const Gated r = gate_wave(g.seg + (size_t)b * g.S_max, n, g.h, g.z_abs, lane);
+  const float L = r.L;
+  const int NB = r.NB, n_kept = r.kept;
   if (lane != 0) return;
   g.lufs[b] = L;
   g.blocks[2 * b] = NB;
@@ -332,6 +354,144 @@ __global__ void __launch_bounds__(256) lk_apply_kernel(const ApplyArgs a) {
     for (int k = 0; k < LK_APPLY_SPAN / 256; ++k) {
       const int i = i0 + k * 256 + tid;
       if (i < n) o[i] = g * x[i];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------- loudness over time
+// A row here is a stream or a whole recording, described by pointers of its own (its tables start at segment 0), so that
+// streams that were allocated apart advance in one launch.  Entry s of every table is computed from seg[0 .. s] in an order
+// that depends on s alone: the call, the batch and the split of a stream change no bit.
+//   lk_time_kernel         one wave per (row, segment s of the call): M[s] from four segments, S[s] from thirty, and I[s],
+//                          kept[s] = gate_wave over the prefix of (s + 1) h samples -- the body of lk_gate_kernel, so the cost
+//                          of an entry grows with s (two passes over s - 2 blocks).
+//   lk_time_max_kernel     one wave per row: the largest M and S among the call's entries (a maximum: exact in any order).
+//   lk_level_gains_kernel  one lane per row: the slewed gain in dB, float32 adds, subtracts, mins and maxes only, and its
+//                          linear value; it starts from c_dB[first - 1] in the row's own table (initial_gain_db at first = 0).
+//   lk_level_apply_kernel  out[i] = (c[s-2] + (c[s-1] - c[s-2]) w) x[i], every product and sum rounded on its own (no FMA).
+struct LRow {                            // uploaded with every call of this section
+  const double* seg;
+  float *M, *S, *I;
+  int32_t* kept;
+  float *c_db, *c;
+  const float* in;
+  float* out;
+  int32_t first, count;                  // time, gains: the entries [first, first + count)
+  int32_t pos, samples;                  // apply: the stream's samples [pos, pos + samples); 0 samples for a NaN target
+  float target, max_gain, max_cut, slew, init;
+  int32_t pad;
+};
+
+__device__ __forceinline__ float db_to_linear(float db) { return (float)pow(10.0, (double)db / 20.0); }
+
+__global__ void __launch_bounds__(64) lk_time_kernel(const LRow* __restrict__ rows, int h, double z_abs) {
+  const int b = blockIdx.y, lane = threadIdx.x;
+  const LRow r = rows[b];
+  if ((int)blockIdx.x >= r.count) return;          // (uniform)
+  const int s = r.first + blockIdx.x;
+  const double* __restrict__ seg = r.seg;
+  const Gated g = gate_wave(seg, (s + 1) * h, h, z_abs, lane);
+  if (lane != 0) return;
+  float M = -INFINITY, S = -INFINITY;
+  if (s >= 3) {
+    const double E = ((seg[s - 3] + seg[s - 2]) + seg[s - 1]) + seg[s];
+    if (E > 0.0) M = (float)(-0.691 + 10.0 * log10(E / (4.0 * (double)h)));
+  }
+  if (s >= 29) {
+    double T = 0.0;
+    for (int k = s - 29; k <= s; ++k) T += seg[k];
+    if (T > 0.0) S = (float)(-0.691 + 10.0 * log10(T / (30.0 * (double)h)));
+  }
+  r.M[s] = M;
+  r.S[s] = S;
+  r.I[s] = g.L;
+  r.kept[s] = g.kept;
+}
+
+__global__ void __launch_bounds__(64) lk_time_max_kernel(const LRow* __restrict__ rows, float* m_max, float* s_max) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const LRow r = rows[b];
+  float m = -INFINITY, s = -INFINITY;
+  for (int k = lane; k < r.count; k += 64) {
+    m = fmaxf(m, r.M[r.first + k]);
+    s = fmaxf(s, r.S[r.first + k]);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    m = fmaxf(m, __shfl_xor(m, d));
+    s = fmaxf(s, __shfl_xor(s, d));
+  }
+  if (lane == 0) {
+    m_max[b] = m;
+    s_max[b] = s;
+  }
+}
+
+__global__ void __launch_bounds__(64) lk_level_gains_kernel(const LRow* __restrict__ rows, int B) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const LRow r = rows[b];
+  if (r.target != r.target) return;                // a NaN target: neither read nor written
+  const float d = __fdiv_rn(r.slew, 10.f);
+  float prev = r.first == 0 ? r.init : r.c_db[r.first - 1];
+  for (int s = r.first; s < r.first + r.count; ++s) {
+    const float I = r.I[s];
+    float q = prev;
+    if (I != -INFINITY) q = fminf(fmaxf(__fsub_rn(r.target, I), -r.max_cut), r.max_gain);
+    prev = __fadd_rn(prev, fminf(fmaxf(__fsub_rn(q, prev), -d), d));
+    r.c_db[s] = prev;
+    r.c[s] = db_to_linear(prev);
+  }
+}
+
+__global__ void __launch_bounds__(256) lk_level_apply_kernel(const LRow* __restrict__ rows, int h, float rh) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const LRow r = rows[b];
+  const int n = r.samples;
+  const int i0 = blockIdx.x * LK_APPLY_SPAN;
+  if (i0 >= n) return;                             // (a NaN target has 0 samples: neither read nor written)
+  const float c_init = db_to_linear(r.init);
+  const float* __restrict__ c = r.c;
+  const float* x = r.in;                           // (may be r.out)
+  float* o = r.out;
+  // out = fl32(a x), a = the line from c[s - 2] to c[s - 1] at sample k of segment s.  Every product and sum is rounded on
+  // its own: hipcc contracts a * b + c into an FMA by default, and its __fmul_rn / __fadd_rn are plain operators that it
+  // contracts just the same, so contraction is switched off for this body.
+  auto levelled = [&](int s, int k, float v) {
+#pragma clang fp contract(off)
+    const float c0 = s >= 2 ? c[s - 2] : c_init, c1 = s >= 1 ? c[s - 1] : c_init;
+    const float w = (float)(k + 1) * rh;
+    const float t = (c1 - c0) * w;
+    const float a = c0 + t;
+    return a * v;
+  };
+  if ((((uintptr_t)x | (uintptr_t)o) & 15u) == 0) {
+#pragma unroll
+    for (int q = 0; q < LK_APPLY_SPAN / 1024; ++q) {
+      const int i = i0 + (q * 256 + tid) * 4;
+      if (i >= n) continue;
+      int s = (r.pos + i) / h, k = (r.pos + i) - s * h;
+      auto step = [&](float v) {
+        const float y = levelled(s, k, v);
+        if (++k == h) { k = 0; ++s; }
+        return y;
+      };
+      if (i + 3 < n) {
+        float4 v = *reinterpret_cast<const float4*>(x + i);
+        v.x = step(v.x); v.y = step(v.y); v.z = step(v.z); v.w = step(v.w);
+        *reinterpret_cast<float4*>(o + i) = v;
+      } else {
+        for (int j = i; j < n; ++j) o[j] = step(x[j]);
+      }
+    }
+  } else {
+#pragma unroll 4
+    for (int q = 0; q < LK_APPLY_SPAN / 256; ++q) {
+      const int i = i0 + q * 256 + tid;
+      if (i < n) {
+        const int s = (r.pos + i) / h;
+        o[i] = levelled(s, (r.pos + i) - s * h, x[i]);
+      }
     }
   }
 }
@@ -464,8 +624,9 @@ int upload_rows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, c
 }
 
 int launch_segments(vsp_ctx* ctx, hipStream_t s, int B, int S_max, const KW& kw, const float* audio, int64_t stride, const Rows& rows,
-                    char* ws, const Ws& lay, double* seg, float* peak) {
+                    char* ws, const Ws& lay, double* seg, float* peak, const double* state_in, double* state_out) {
   SegArgs a;
+  a.state_in = state_in; a.state_out = state_out;
   a.audio = audio; a.stride = stride; a.rows = rows;
   a.ends = reinterpret_cast<double*>(ws + lay.ends);
   a.starts = reinterpret_cast<double*>(ws + lay.starts);
@@ -480,7 +641,7 @@ int launch_segments(vsp_ctx* ctx, hipStream_t s, int B, int S_max, const KW& kw,
     if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "loudness (LDS): %s", hipGetErrorString(e));
   }
   const dim3 grid(S_max, B);
-  if (S_max > 1) hipLaunchKernelGGL(lk_ends_kernel, grid, dim3(64), lds, s, a, kw);
+  if (S_max > 1 || state_out) hipLaunchKernelGGL(lk_ends_kernel, grid, dim3(64), lds, s, a, kw);
   hipLaunchKernelGGL(lk_carry_kernel, dim3(B), dim3(64), 0, s, a, kw);
   hipLaunchKernelGGL(lk_energy_kernel, grid, dim3(64), lds, s, a, kw);
   const hipError_t e = hipGetLastError();
@@ -547,7 +708,7 @@ int vsp_loudness_segments(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int 
   char* ws = static_cast<char*>(workspace);
   Rows rows;
   if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
-  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak);
+  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak, nullptr, nullptr);
 }
 
 int vsp_loudness_gate(vsp_ctx* ctx, void* stream, int B, int S_max, int sample_rate, const double* seg, const int64_t* n_samples_host,
@@ -606,8 +767,247 @@ int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int
   if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
   const KW kw = make_kw(sample_rate);
   double* seg = reinterpret_cast<double*>(ws + lay.seg);
-  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws, lay, seg, peak)) return rc;
+  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws, lay, seg, peak, nullptr, nullptr)) return rc;
   if (!blocks) blocks = reinterpret_cast<int32_t*>(ws + lay.blocks);
   if (const int rc = launch_gate(ctx, s, B, S_max, kw.h, seg, rows, true, peak, lufs, blocks, gains)) return rc;
   return launch_apply(ctx, s, B, L_max, audio, audio_stride, out, out_stride, rows, gains);
+}
+
+// ---------------------------------------------------------------------------------- loudness over time: entry points
+namespace {
+
+constexpr int64_t LK_MAX_ENTRIES = LK_MAX_SAMPLES / 800 + 1;      // (h >= 800; every call checks entries h itself)
+
+size_t lrows_bytes(int B) { return align256((size_t)B * sizeof(LRow)); }
+// [rows (as every loudness call)] [LRow [B]] and, for the fused call, [ends] [starts] [seg] [blocks]
+size_t time_head(int B) { return rows_bytes(B) + lrows_bytes(B); }
+
+int check_level(vsp_ctx* ctx, const char* who, int b, const vsp_loudness_level_params& p) {
+  if (!(p.max_gain_db >= 0.f)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: max_gain_db must be at least 0", who, b);
+  if (!(p.max_cut_db >= 0.f)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: max_cut_db must be at least 0", who, b);
+  if (!(p.slew_db_per_s > 0.f)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: slew_db_per_s must be above 0", who, b);
+  if (!std::isfinite(p.initial_gain_db)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: initial_gain_db must be finite", who, b);
+  return VSP_OK;
+}
+
+void set_level(LRow& r, const vsp_loudness_level_params& p) {
+  r.target = p.target_lufs; r.max_gain = p.max_gain_db; r.max_cut = p.max_cut_db; r.slew = p.slew_db_per_s; r.init = p.initial_gain_db;
+}
+
+// The entries [first, first + count) of a row whose tables hold `entries`: refused naming the row.
+int check_entries(vsp_ctx* ctx, const char* who, int b, const vsp_loudness_row& r, int h) {
+  if (r.entries < 0 || r.entries > LK_MAX_ENTRIES || r.entries * h > LK_MAX_SAMPLES + h)
+    return ctx->fail(VSP_ERR_ARG, "%s: row %d: a table of %lld entries: at most 2^30 samples", who, b, (long long)r.entries);
+  if (r.first < 0 || r.count < 0 || r.first + r.count > r.entries)
+    return ctx->fail(VSP_ERR_ARG, "%s: row %d: entries [%lld, %lld + %lld) of a table of %lld", who, b, (long long)r.first,
+                     (long long)r.first, (long long)r.count, (long long)r.entries);
+  return VSP_OK;
+}
+
+int upload_lrows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, const std::vector<LRow>& up, const LRow*& dev) {
+  const hipError_t e = hipMemcpyAsync(ws + rows_bytes(B), up.data(), up.size() * sizeof(LRow), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
+  dev = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
+  return VSP_OK;
+}
+
+int launched(vsp_ctx* ctx, const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  return VSP_OK;
+}
+
+int launch_time(vsp_ctx* ctx, hipStream_t s, int B, int count_max, int h, const LRow* rows, float* m_max, float* s_max) {
+  if (count_max > 0)
+    hipLaunchKernelGGL(lk_time_kernel, dim3(count_max, B), dim3(64), 0, s, rows, h, std::pow(10.0, (-70.0 + 0.691) / 10.0));
+  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, s, rows, m_max, s_max);
+  return launched(ctx, "loudness time");
+}
+
+int launch_level_gains(vsp_ctx* ctx, hipStream_t s, int B, const LRow* rows) {
+  hipLaunchKernelGGL(lk_level_gains_kernel, dim3((B + 63) / 64), dim3(64), 0, s, rows, B);
+  return launched(ctx, "lk_level_gains_kernel");
+}
+
+int launch_level_apply(vsp_ctx* ctx, hipStream_t s, int B, int64_t samples_max, int h, const LRow* rows) {
+  if (samples_max < 1) return VSP_OK;
+  hipLaunchKernelGGL(lk_level_apply_kernel, dim3((unsigned)((samples_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, s, rows, h,
+                     1.f / (float)h);
+  return launched(ctx, "lk_level_apply_kernel");
+}
+
+}  // namespace
+
+int64_t vsp_loudness_time_workspace_bytes(int B, int64_t L_max, int sample_rate) {
+  if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
+  return (int64_t)(lrows_bytes(B) + layout(B, segments_of(L_max, sample_rate)).end);
+}
+
+int vsp_loudness_segments_from(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                               const int64_t* n_samples_host, const int64_t* first_host, const double* state_in, double* state_out,
+                               double* seg, float* peak, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_segments_from";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, and the rows' samples", who, LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
+  const int h = segment_samples(sample_rate);
+  for (int b = 0; first_host && b < B; ++b)
+    if (first_host[b] < 0 || first_host[b] % h || first_host[b] + n_samples_host[b] > LK_MAX_SAMPLES)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: the piece starts at sample %lld: a segment boundary (a multiple of %d), the stream at most 2^30 samples",
+                       who, b, (long long)first_host[b], h);
+  if (!audio || !seg || !peak) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  const Ws lay = layout(B, S_max);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  Rows rows;
+  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
+  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak, state_in, state_out);
+}
+
+int vsp_loudness_time(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, float* m_max, float* s_max,
+                      void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_time";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (B < 1 || B > LK_MAX_B || !rows_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows", who, LK_MAX_B);
+  const int h = segment_samples(sample_rate);
+  std::vector<LRow> up((size_t)B);
+  int64_t count_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const vsp_loudness_row& r = rows_host[b];
+    if (const int rc = check_entries(ctx, who, b, r, h)) return rc;
+    if (r.count && (!r.seg || !r.M || !r.S || !r.I || !r.kept)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    LRow& d = up[b];
+    std::memset(&d, 0, sizeof d);
+    d.seg = r.seg; d.M = r.M; d.S = r.S; d.I = r.I; d.kept = r.kept;
+    d.first = (int32_t)r.first; d.count = (int32_t)r.count;
+    count_max = std::max(count_max, r.count);
+  }
+  if (!m_max != !s_max) return ctx->fail(VSP_ERR_ARG, "%s: m_max and s_max come together", who);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const LRow* dev;
+  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
+  return launch_time(ctx, s, B, (int)count_max, h, dev, m_max, s_max);
+}
+
+int vsp_loudness_level_gains(vsp_ctx* ctx, void* stream, int B, const vsp_loudness_row* rows_host,
+                             const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_level_gains";
+  if (B < 1 || B > LK_MAX_B || !rows_host || !params_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their params", who, LK_MAX_B);
+  std::vector<LRow> up((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const vsp_loudness_row& r = rows_host[b];
+    if (const int rc = check_entries(ctx, who, b, r, LK_FS_MIN / 10)) return rc;
+    if (const int rc = check_level(ctx, who, b, params_host[b])) return rc;
+    const bool alone = params_host[b].target_lufs != params_host[b].target_lufs;
+    if (r.count && !alone && (!r.I || !r.c_db || !r.c)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    LRow& d = up[b];
+    std::memset(&d, 0, sizeof d);
+    d.I = r.I; d.c_db = r.c_db; d.c = r.c;
+    d.first = (int32_t)r.first; d.count = (int32_t)r.count;
+    set_level(d, params_host[b]);
+  }
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const LRow* dev;
+  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
+  return launch_level_gains(ctx, s, B, dev);
+}
+
+int vsp_loudness_level_apply(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host,
+                             const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_level_apply";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (B < 1 || B > LK_MAX_B || !rows_host || !params_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their params", who, LK_MAX_B);
+  const int h = segment_samples(sample_rate);
+  std::vector<LRow> up((size_t)B);
+  int64_t samples_max = 0;
+  for (int b = 0; b < B; ++b) {
+    const vsp_loudness_row& r = rows_host[b];
+    if (r.pos < 0 || r.samples < 0 || r.pos + r.samples > LK_MAX_SAMPLES)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: samples [%lld, %lld + %lld): inside [0, 2^30]", who, b, (long long)r.pos, (long long)r.pos,
+                       (long long)r.samples);
+    if (r.entries < 0 || r.entries > LK_MAX_ENTRIES || (r.samples && (r.pos + r.samples - 1) / h > r.entries))
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: samples up to %lld need %lld entries of c, the table holds %lld", who, b,
+                       (long long)(r.pos + r.samples), (long long)((r.pos + r.samples - 1) / h), (long long)r.entries);
+    if (const int rc = check_level(ctx, who, b, params_host[b])) return rc;
+    const bool alone = params_host[b].target_lufs != params_host[b].target_lufs;
+    if (r.samples && !alone && (!r.in || !r.out || (r.entries && !r.c))) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    LRow& d = up[b];
+    std::memset(&d, 0, sizeof d);
+    d.c = r.c; d.in = r.in; d.out = r.out;
+    d.pos = (int32_t)r.pos; d.samples = alone ? 0 : (int32_t)r.samples;
+    set_level(d, params_host[b]);
+    samples_max = std::max(samples_max, (int64_t)d.samples);
+  }
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const LRow* dev;
+  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
+  return launch_level_apply(ctx, s, B, samples_max, h, dev);
+}
+
+int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride, float* out,
+                       int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_level_params* params_host, float* M, float* S,
+                       float* I, int32_t* kept, float* c_db, float* c, int64_t table_stride, float* m_max, float* s_max, float* i_end,
+                       float* peak, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_level";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const int h = segment_samples(sample_rate);
+  if (!sizes_ok(B, L_max) || audio_stride < L_max || (params_host && out_stride < L_max) || !n_samples_host || table_stride < L_max / h)
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, table_stride >= L_max / h, and the rows' samples", who,
+                     LK_MAX_B);
+  std::vector<int32_t> up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
+  for (int b = 0; params_host && b < B; ++b)
+    if (const int rc = check_level(ctx, who, b, params_host[b])) return rc;
+  if (!audio || !M || !S || !I || !kept || !m_max || !s_max || !i_end || !peak || (params_host && (!out || !c_db || !c)))
+    return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  const Ws lay = layout(B, S_max);                      // (behind the LRows)
+  const size_t shift = lrows_bytes(B);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, shift + lay.end)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  double* seg = reinterpret_cast<double*>(ws + shift + lay.seg);
+  // ONE upload: the rows of the segment kernels, then the rows of this section
+  std::vector<char> both(time_head(B), 0);
+  std::memcpy(both.data(), up.data(), up.size() * sizeof(int32_t));
+  LRow* lr = reinterpret_cast<LRow*>(both.data() + rows_bytes(B));
+  for (int b = 0; b < B; ++b) {
+    LRow& d = lr[b];
+    const size_t t = (size_t)b * table_stride;
+    d.seg = seg + (size_t)b * S_max;
+    d.M = M + t; d.S = S + t; d.I = I + t; d.kept = kept + t;
+    d.first = 0; d.count = (int32_t)(n_samples_host[b] / h);
+    if (!params_host) continue;
+    d.c_db = c_db + t; d.c = c + t;
+    d.in = audio + (size_t)b * audio_stride; d.out = out + (size_t)b * out_stride;
+    d.pos = 0; d.samples = params_host[b].target_lufs != params_host[b].target_lufs ? 0 : (int32_t)n_samples_host[b];
+    set_level(d, params_host[b]);
+  }
+  const hipError_t e = hipMemcpyAsync(ws, both.data(), both.size(), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
+  Rows rows;
+  rows.n = reinterpret_cast<const int32_t*>(ws);
+  rows.n_apply = rows.n + B;
+  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
+  const LRow* dev = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
+  const KW kw = make_kw(sample_rate);
+  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws + shift, lay, seg, peak, nullptr, nullptr)) return rc;
+  int32_t* blocks = reinterpret_cast<int32_t*>(ws + shift + lay.blocks);
+  if (const int rc = launch_gate(ctx, s, B, S_max, h, seg, rows, false, peak, i_end, blocks, nullptr)) return rc;
+  if (const int rc = launch_time(ctx, s, B, (int)(L_max / h), h, dev, m_max, s_max)) return rc;
+  if (!params_host) return VSP_OK;
+  if (const int rc = launch_level_gains(ctx, s, B, dev)) return rc;
+  return launch_level_apply(ctx, s, B, L_max, h, dev);
 }

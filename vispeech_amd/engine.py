@@ -1765,6 +1765,215 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_loudness_normalize")
         return o, gains, lufs, peak, blocks
 
+    # ------------------------------------------------------------------ loudness over time (section 4r)
+    @staticmethod
+    def loudness_level_params(B: int, target_lufs=-23.0, max_gain_db=12.0, max_cut_db=12.0, slew_db_per_s=3.0, initial_gain_db=0.0):
+        """``vsp_loudness_level_params`` [B] from five values, each a scalar or one value per row.  A row's ``target_lufs`` may
+        be None or NaN: the leveller leaves the row alone.  Refused here as the library refuses them, naming the row."""
+        def col(v, name):
+            if v is None or np.ndim(v) == 0:
+                return [float("nan") if v is None else float(v)] * B
+            v = [float("nan") if x is None else float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+            if len(v) != B:
+                raise ValueError(f"loudness: {name} must be a scalar or have {B} entries")
+            return v
+        cols = [col(v, n) for v, n in ((target_lufs, "target_lufs"), (max_gain_db, "max_gain_db"), (max_cut_db, "max_cut_db"),
+                                       (slew_db_per_s, "slew_db_per_s"), (initial_gain_db, "initial_gain_db"))]
+        out = (_lib.VspLoudnessLevelParams * B)()
+        for b in range(B):
+            t, g, c, s, i = (col[b] for col in cols)
+            if not g >= 0.0:
+                raise ValueError(f"loudness: row {b}: max_gain_db must be at least 0")
+            if not c >= 0.0:
+                raise ValueError(f"loudness: row {b}: max_cut_db must be at least 0")
+            if not s > 0.0:
+                raise ValueError(f"loudness: row {b}: slew_db_per_s must be above 0")
+            if not np.isfinite(i):
+                raise ValueError(f"loudness: row {b}: initial_gain_db must be finite")
+            out[b] = _lib.VspLoudnessLevelParams(t, g, c, s, i)
+        return out
+
+    def _own_rows(self, t, dtype, what: str, B=None):
+        """The rows of a table given as ``[B, T]`` or as B 1-D tensors allocated apart: each must already be a ``dtype`` tensor
+        on the device with unit stride (the calls of this section write in place and read what earlier calls left)."""
+        rows = list(t)
+        if B is not None and len(rows) != B:
+            raise ValueError(f"{what} must have {B} rows")
+        for b, r in enumerate(rows):
+            if not (torch.is_tensor(r) and r.dtype == dtype and r.device == self.device and r.dim() == 1 and (r.numel() < 2 or r.stride(0) == 1)):
+                raise ValueError(f"{what}: row {b} must be a 1-D {dtype} tensor on the engine's device")
+        return rows
+
+    @staticmethod
+    def _ints(v, B: int, what: str):
+        v = [int(v)] * B if np.ndim(v) == 0 else [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+        if len(v) != B:
+            raise ValueError(f"{what} must be a scalar or have {B} entries")
+        return v
+
+    def _level_params(self, params, B: int):
+        """``params`` as ``loudness_level_params`` made them, or B mappings of the five fields (a missing one: its default)."""
+        if isinstance(params, C.Array):
+            if len(params) != B:
+                raise ValueError(f"loudness: params must have {B} rows")
+            return params
+        rows = list(params)
+        if len(rows) != B:
+            raise ValueError(f"loudness: params must have {B} rows")
+        names = ("target_lufs", "max_gain_db", "max_cut_db", "slew_db_per_s", "initial_gain_db")
+        defaults = (-23.0, 12.0, 12.0, 3.0, 0.0)
+        return self.loudness_level_params(B, *[[r.get(n, d) for r in rows] for n, d in zip(names, defaults)])
+
+    def loudness_state(self, B: int):
+        """The K-weighting's state of B new streams: ``[B, 4]`` float64 zeros on the device."""
+        return torch.zeros((B, 4), dtype=torch.float64, device=self.device)
+
+    def loudness_table(self, n: int, dtype):
+        """A 1-D table of ``n`` entries of a numpy ``dtype`` on the device (NaN, or -1 for integers, until written)."""
+        dt = {"float64": torch.float64, "float32": torch.float32, "int32": torch.int32}[np.dtype(dtype).name]
+        return torch.full((int(n),), -1 if dt == torch.int32 else float("nan"), dtype=dt, device=self.device)
+
+    def _time_ws(self, B: int):
+        return self._workspace("loudness", self.lib.vsp_loudness_time_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
+
+    def loudness_segments_from(self, audio, n_samples, sample_rate: int, state=None, first=None):
+        """``vsp_loudness_segments_from``: ``loudness_segments`` of the pieces ``audio[b, :n_samples[b]]`` of B streams, each
+        starting on a segment boundary of its stream (``first``: the streams' positions, checked; None: 0) with the
+        K-weighting's ``state`` ``[B, 4]`` float64 on the device (None: zero).  Returns ``(seg, peak, state_out)``:
+        ``state_out`` ``[B, 4]`` is the state behind each piece's last complete segment -- what the next piece starts from."""
+        a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
+        L_max = max(n_host)
+        S_max = int(self.lib.vsp_loudness_segments_count(L_max, fs))
+        st = None
+        if state is not None:
+            st = torch.as_tensor(state).to(device=self.device, dtype=torch.float64).contiguous()
+            if st.shape != (B, 4):
+                raise ValueError(f"state must be [{B}, 4]")
+        f = None if first is None else (C.c_int64 * B)(*self._ints(first, B, "first"))
+        seg = torch.empty((B, S_max), dtype=torch.float64, device=self.device)
+        peak = self._f(B)
+        st_out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_workspace_bytes(B, L_max, fs))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_segments_from(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, (C.c_int64 * B)(*n_host), f,
+                                                     _ptr(st), _ptr(st_out), _ptr(seg), _ptr(peak), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_segments_from")
+        return seg, peak, st_out
+
+    def loudness_time(self, seg, first, count, sample_rate: int, tables=None):
+        """``vsp_loudness_time``: the entries ``[first_b, first_b + count_b)`` of every row's ``M, S, I`` (float32) and ``kept``
+        (int32) from its float64 segment table ``seg`` -- ``[B, T]`` or B 1-D tensors allocated apart, each from the row's
+        segment 0.  ``tables``: ``(M, S, I, kept)`` to write into (likewise), or None: new ``[B, T]`` tensors, NaN (-1 for
+        ``kept``) outside the entries computed.  Returns ``(M, S, I, kept, m_max, s_max)``; the maxima ``[B]`` are those of
+        THIS call's entries."""
+        segs = self._own_rows(seg, torch.float64, "seg")
+        B = len(segs)
+        if B == 0:
+            raise ValueError("loudness_time: at least one row")
+        first, count = self._ints(first, B, "first"), self._ints(count, B, "count")
+        if tables is None:
+            T = max(1, max(f + c for f, c in zip(first, count)))
+            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(3)) + \
+                (torch.full((B, T), -1, dtype=torch.int32, device=self.device),)
+        M, S, I, kept = tables
+        rows = [self._own_rows(t, torch.float32, n, B) for t, n in ((M, "M"), (S, "S"), (I, "I"))] + [self._own_rows(kept, torch.int32, "kept", B)]
+        desc = (_lib.VspLoudnessRow * B)()
+        for b in range(B):
+            entries = min([segs[b].numel()] + [r[b].numel() for r in rows])
+            desc[b] = _lib.VspLoudnessRow(seg=segs[b].data_ptr(), M=rows[0][b].data_ptr(), S=rows[1][b].data_ptr(), I=rows[2][b].data_ptr(),
+                                          kept=rows[3][b].data_ptr(), first=first[b], count=count[b], entries=entries)
+        m_max, s_max = self._f(B), self._f(B)
+        ws = self._time_ws(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_time(self.ctx, self._stream(), B, int(sample_rate), desc, _ptr(m_max), _ptr(s_max), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_time")
+        return M, S, I, kept, m_max, s_max
+
+    def loudness_level_gains(self, I, first, count, params, tables=None):
+        """``vsp_loudness_level_gains``: the leveller's gain in dB and linear, ``c_db`` and ``c``, entries ``[first_b, first_b +
+        count_b)`` of every row from ANY table ``I`` (rows as ``loudness_time``), continuing from ``c_db[first_b - 1]`` of the
+        row's own table (``initial_gain_db`` at 0).  ``tables``: ``(c_db, c)`` to write into, or None: new ``[B, T]`` tensors
+        (NaN outside).  A NaN-target row is neither read nor written.  Returns ``(c_db, c)``."""
+        Is = self._own_rows(I, torch.float32, "I")
+        B = len(Is)
+        if B == 0:
+            raise ValueError("loudness_level_gains: at least one row")
+        params = self._level_params(params, B)
+        first, count = self._ints(first, B, "first"), self._ints(count, B, "count")
+        if tables is None:
+            T = max(1, max(f + c for f, c in zip(first, count)))
+            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(2))
+        c_db, c = tables
+        dbs, cs = self._own_rows(c_db, torch.float32, "c_db", B), self._own_rows(c, torch.float32, "c", B)
+        desc = (_lib.VspLoudnessRow * B)()
+        for b in range(B):
+            desc[b] = _lib.VspLoudnessRow(I=Is[b].data_ptr(), c_db=dbs[b].data_ptr(), c=cs[b].data_ptr(), first=first[b], count=count[b],
+                                          entries=min(Is[b].numel(), dbs[b].numel(), cs[b].numel()))
+        ws = self._time_ws(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_level_gains(self.ctx, self._stream(), B, desc, params, _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_level_gains")
+        return c_db, c
+
+    def loudness_level_apply(self, x, pos, c, entries, sample_rate: int, params, n_samples=None, out=None):
+        """``vsp_loudness_level_apply``: row b's samples ``x[b][:n_b]`` (``n_samples`` None: all of the row) are its stream's
+        ``[pos_b, pos_b + n_b)``; they are levelled against the row's gain table ``c``, of which ``entries[b]`` are valid
+        (at least ``(pos_b + n_b - 1) // h``).  ``x``, ``c``, ``out``: ``[B, .]`` or B 1-D tensors allocated apart.  ``out``
+        may be ``x`` (in place); None: new tensors (of ``n_b`` samples each for rows given apart, a copy of a 2-D ``x``
+        otherwise).  Nothing at or behind ``n_b`` and no NaN-target row is read or written.  Returns ``out``."""
+        xs = self._own_rows(x, torch.float32, "x")
+        B = len(xs)
+        if B == 0:
+            raise ValueError("loudness_level_apply: at least one row")
+        params = self._level_params(params, B)
+        cs = self._own_rows(c, torch.float32, "c", B)
+        pos, entries = self._ints(pos, B, "pos"), self._ints(entries, B, "entries")
+        n = [r.numel() for r in xs] if n_samples is None else self._ints(n_samples, B, "n_samples")
+        if out is None:
+            out = x.clone() if torch.is_tensor(x) else [self._f(max(0, min(k, r.numel()))) for k, r in zip(n, xs)]
+        os_ = self._own_rows(out, torch.float32, "out", B)
+        desc = (_lib.VspLoudnessRow * B)()
+        for b in range(B):
+            if not 0 <= n[b] <= min(xs[b].numel(), os_[b].numel()):
+                raise ValueError(f"loudness: row {b} has {n[b]} samples: its tensors hold {min(xs[b].numel(), os_[b].numel())}")
+            if not 0 <= entries[b] <= cs[b].numel():
+                raise ValueError(f"loudness: row {b}: {entries[b]} entries of a table of {cs[b].numel()}")
+            desc[b] = _lib.VspLoudnessRow(c=cs[b].data_ptr(), entries=entries[b], inp=xs[b].data_ptr(), out=os_[b].data_ptr(), pos=pos[b],
+                                          samples=n[b])
+        ws = self._time_ws(B)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_level_apply(self.ctx, self._stream(), B, int(sample_rate), desc, params, _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_level_apply")
+        return out
+
+    def loudness_level(self, audio, n_samples, sample_rate: int, params=None, out=None):
+        """``vsp_loudness_level``: whole rows in ONE call -- segments, the loudness of the row, the tables over time and, with
+        ``params`` (``loudness_level_params``), the leveller's gains and its output (``out`` None: in place where ``audio`` is a
+        float32 device tensor).  Returns a dict: ``M, S, I`` ``[B, F_max]`` float32 and ``kept`` int32 (row b written for ``s <
+        n_b // h``, NaN / -1 behind), ``m_max, s_max, i_end, peak`` ``[B]``, and with ``params`` ``c_db, c`` and ``out``."""
+        a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
+        o = o_stride = None
+        if params is not None:
+            params = self._level_params(params, B)
+            o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
+            if out is not None and o is not out:
+                raise ValueError("out must be a float32 tensor on the engine's device")
+        L_max = max(n_host)
+        T = max(1, L_max // ((fs + 5) // 10))
+        tab = lambda: torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device)
+        r = dict(M=tab(), S=tab(), I=tab(), kept=torch.full((B, T), -1, dtype=torch.int32, device=self.device), m_max=self._f(B),
+                 s_max=self._f(B), i_end=self._f(B), peak=self._f(B))
+        if params is not None:
+            r.update(c_db=tab(), c=tab(), out=o)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_time_workspace_bytes(B, L_max, fs))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_level(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, _ptr(o), o_stride or 0,
+                                             (C.c_int64 * B)(*n_host), params, _ptr(r["M"]), _ptr(r["S"]), _ptr(r["I"]), _ptr(r["kept"]),
+                                             _ptr(r.get("c_db")), _ptr(r.get("c")), T, _ptr(r["m_max"]), _ptr(r["s_max"]), _ptr(r["i_end"]),
+                                             _ptr(r["peak"]), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_level")
+        return r
+
     # ------------------------------------------------------------------ true peak and limiter (section 4q)
     def limiter_history(self, attack: int, hold: int):
         """``vsp_limiter_history``: ``(behind, ahead)`` -- the samples before an output and after it that reach it."""

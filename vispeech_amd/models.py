@@ -305,6 +305,31 @@ class SynthesizerTrn:
         A, H = _limiter.window(fs, attack_ms, hold_ms)
         return self._engine.limit(audio, n_samples, ceiling, gains=gains, attack=A, hold=H, out=out)
 
+    @torch.no_grad()
+    def loudness_profile(self, audio, n_samples, sample_rate: Optional[int] = None):
+        """Loudness over time (EBU Tech 3341's M, S and I) of every row of a ragged batch, one value per
+        complete 100 ms segment: returns ``(M, S, I, M_max, S_max, I_end)`` -- momentary, short-term and running integrated
+        loudness ``[B, F_max]`` float32 (NaN behind row b's ``n_samples[b] // h`` entries, -inf where a value does not exist
+        yet), the rows' maxima and the integrated loudness of the whole row (``loudness``' value), all on the device."""
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        r = self._engine.loudness_level(audio, n_samples, fs)
+        return r["M"], r["S"], r["I"], r["m_max"], r["s_max"], r["i_end"]
+
+    @torch.no_grad()
+    def level(self, audio, n_samples, target_lufs=-23.0, max_gain_db=12, max_cut_db=12, slew_db_per_s=3, initial_gain_db=0,
+              sample_rate: Optional[int] = None, out=None):
+        """The causal leveller: every row follows its own running integrated loudness towards
+        ``target_lufs``, by at most ``slew_db_per_s``, between ``-max_cut_db`` and ``max_gain_db``, starting from
+        ``initial_gain_db`` -- no look-ahead, no delay; the gain over a 100 ms segment depends on what came before it only.  The
+        five values are scalars or one per row; a row whose target is None or NaN is left alone.  In place where ``audio`` is a
+        float32 tensor on the model's device and ``out`` is None.  It does not clamp: put ``limit`` behind it.  Returns
+        ``(wave, c_dB)``: ``c_dB`` ``[B, F_max]`` is the gain in dB reached at the end of every complete segment."""
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        eng = self._engine
+        params = eng.loudness_level_params(len(n_samples), target_lufs, max_gain_db, max_cut_db, slew_db_per_s, initial_gain_db)
+        r = eng.loudness_level(audio, n_samples, fs, params, out=out)
+        return r["out"], r["c_db"]
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

@@ -9,7 +9,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import input_stage, limiter, output_stage
+from .. import input_stage, limiter, loudness, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
 from .batching import _Conversion, _Request, _collate_from, _input_format, _limiter_spec, _output_format, _row_formats, latents
 
@@ -24,6 +24,7 @@ class _RowStream:
         self._q: "queue.Queue" = queue.Queue()
         self._closed = False
         self._done = False
+        self.loudness = None          # a request that named ``loudness=``, once finished: integrated, maxima, last gain
 
     def __iter__(self):
         return self
@@ -58,9 +59,11 @@ class _RowStream:
 class _StreamRequest(_Request):
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, limiter=None):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, limiter=None, level=None):
         super().__init__(row, seed, scales, out_fmt, limiter=limiter)
         self.lim = None               # a request with a limiter: its ``limiter.Stream``, from its first tick on
+        self.level = level            # ``loudness.spec``: the leveller's five values, {} for a meter only, or None
+        self.loud = None              # a request that names a loudness: its ``loudness.Stream``, from its first tick on
         self.stream = _RowStream()
         self.z = self.g = None
         self.L = self.pos = 0
@@ -120,8 +123,8 @@ class _LiveRequest(_StreamRequest):
     on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
     ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
 
-    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None, limiter=None):
-        super().__init__(None, seed, out_fmt=out_fmt, limiter=limiter)
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None, limiter=None, level=None):
+        super().__init__(None, seed, out_fmt=out_fmt, limiter=limiter, level=level)
         self.stream = stream
         self.fmt = stream._fmt        # (rate, encoding) of the feed: its pieces go through ``input`` before they reach ``buf``
         self.input = None             # the session's ``input_stage.Stream``, from its first piece on
@@ -180,7 +183,14 @@ class StreamingBatchService:
     active request has one runs on the same ``output_rows`` path, with ONE ``limiter.push_rows`` call for those rows between
     the generator and ``output_rows``; the request's last chunk flushes its limiter.  Its bytes are those of
     ``SynthesizerTrn.limit`` on its whole waveform, then the output stage; its delay grows by attack + 12 samples.
-    ``fused_output=True`` refuses the keyword as well."""
+    ``fused_output=True`` refuses the keyword as well.
+    And ``loudness=`` (round 23): a number -- the target in LUFS of the causal leveller, which follows
+    the stream's running integrated loudness with no look-ahead and no delay --, a mapping of (target_lufs, max_gain_db,
+    max_cut_db, slew_db_per_s, initial_gain_db), or True: a meter only.  Such a tick runs on the ``output_rows`` path too,
+    with ONE ``loudness.push_rows`` call for those rows between the generator and the limiter / ``output_rows``; the request's
+    samples are those of ``SynthesizerTrn.level`` on its whole waveform (then ``limit``, then the output stage).  When the
+    request has finished, its stream carries ``.loudness``: ``dict(integrated, momentary_max, short_term_max, gain_db)``.
+    ``fused_output=True`` refuses the keyword; a request that names nothing gets the bytes it always got."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
@@ -228,8 +238,16 @@ class StreamingBatchService:
             raise ValueError("fused_output delivers every row through its one launch: a request's limiter needs fused_output=False")
         return _limiter_spec(limiter, None, self.sampling_rate)
 
+    def _loudness(self, value):
+        """A request's ``loudness=``: ``loudness.spec`` -- the leveller's values, {} for a meter -- or None."""
+        if value is None or value is False:
+            return None
+        if self.fused_output:
+            raise ValueError("fused_output delivers every row through its one launch: a request's loudness needs fused_output=False")
+        return loudness.spec(value)
+
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, limiter=None) -> _RowStream:
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, limiter=None, loudness=None) -> _RowStream:
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
         1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
         request's PCM16 ``bytes``, one piece per tick the request takes part in.
@@ -239,27 +257,30 @@ class StreamingBatchService:
         mapping of (attack_ms, hold_ms, ceiling, gain_db): the level control a stream can have, a fixed gain held under a
         ceiling.  The request's bytes are those of ``SynthesizerTrn.limit`` on its whole waveform, then the output stage;
         its delay grows by attack + 12 samples.  A tick in which a request has one runs as a tick in which a request names
-        a format does, with ONE ``limiter.push_rows`` call for those rows between the generator and ``output_rows``."""
+        a format does, with ONE ``limiter.push_rows`` call for those rows between the generator and ``output_rows``.
+        ``loudness``: the leveller's target (LUFS), a mapping of its five values, or True for a meter only (see the class
+        text); it runs in front of the limiter."""
         return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                            self._out_fmt(output_rate, output_encoding), self._limiter(limiter)))
+                                            self._out_fmt(output_rate, output_encoding), self._limiter(limiter), self._loudness(loudness)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None, limiter=None) -> _RowStream:
+                          output_encoding=None, limiter=None, loudness=None) -> _RowStream:
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
         the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
         frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
         NOT the service's text-to-speech ``noise_scale``).  ``sample_rate`` / ``encoding``: ``audio`` is raw samples in that
         format (an array of the encoding's dtype or ``bytes``); admission runs the group's raw recordings through the
         input stage, one call per distinct (rate, encoding), before its one ``convert_latent``.  ``output_rate`` /
-        ``output_encoding`` / ``limiter``: as in ``submit``."""
+        ``output_encoding`` / ``limiter`` / ``loudness``: as in ``submit``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
-                                            out_fmt=self._out_fmt(output_rate, output_encoding), limiter=self._limiter(limiter)))
+                                            out_fmt=self._out_fmt(output_rate, output_encoding), limiter=self._limiter(limiter),
+                                            level=self._loudness(loudness)))
 
     def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                         sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                        output_encoding=None, limiter=None) -> LiveConversion:
+                        output_encoding=None, limiter=None, loudness=None) -> LiveConversion:
         """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
         ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
         ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``).
@@ -268,9 +289,11 @@ class StreamingBatchService:
         appends the model-rate samples that are complete to the session's buffer; ``end()`` flushes the filter's tail.
         Readiness is decided on those samples, so the session's delay grows by the filter's half length: ``zeros`` = 32
         input periods (2 ms at 16 kHz).  ``output_rate`` / ``output_encoding``: as in ``submit``; on that path a frame
-        need not be a whole number of output samples.  ``limiter``: as in ``submit``."""
+        need not be a whole number of output samples.  ``limiter`` / ``loudness``: as in ``submit`` -- the leveller is what
+        keeps a call that lasts minutes, whose talker moves about the microphone, at its level."""
         out_fmt = self._out_fmt(output_rate, output_encoding)
         limiter = self._limiter(limiter)
+        level = self._loudness(loudness)
         if self.fused_output:
             # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
             # filter's phase and its history must not see the shift
@@ -290,7 +313,7 @@ class StreamingBatchService:
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         if fmt is not None and fmt[0] not in self.net._engine.input_rates:
             self.net._engine.configure_input(fmt[0], model_rate=self.sampling_rate)      # (allocates: here, not in a tick)
-        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt, limiter))
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt, limiter, level))
 
     def _enqueue(self, req: _StreamRequest) -> _RowStream:
         """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
@@ -511,7 +534,7 @@ class StreamingBatchService:
             counts.append(f1 - r.pos)
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
-        if any(r.out_fmt is not None or r.limiter is not None for r in reqs):
+        if any(r.out_fmt is not None or r.limiter is not None or r.level is not None for r in reqs):
             return self._deliver_rows(reqs, rows, counts)
         for r in reqs:
             if r.row_state is not None:        # it shared earlier ticks with requests that name a format
@@ -550,6 +573,18 @@ class StreamingBatchService:
         out = eng.generator_stream_rows(rows, self.chunk_frames, pcm=False)
         pieces = [out[b, : n * hop] for b, n in enumerate(counts)]
         first = [(getattr(r, "e0", 0) + r.pos) * hop for r in reqs]
+        last = [r.pos + n >= r.L for r, n in zip(reqs, counts)]
+        named = [b for b, r in enumerate(reqs) if r.level is not None]
+        if named:                                                       # the leveller (or meter): no delay, so `first` stands
+            for b in named:
+                if reqs[b].loud is None:
+                    reqs[b].loud = loudness.Stream(eng, self.sampling_rate, level=reqs[b].level or True)
+            for b, y in zip(named, loudness.push_rows(eng, [(reqs[b].loud, pieces[b], last[b]) for b in named])):
+                pieces[b] = y
+                if last[b]:
+                    st = reqs[b].loud
+                    reqs[b].stream.loudness = dict(integrated=st.integrated, momentary_max=st.momentary_max,
+                                                   short_term_max=st.short_term_max, gain_db=st.gain_db)
         limited = [b for b, r in enumerate(reqs) if r.limiter is not None]
         for b in limited:
             r = reqs[b]
@@ -558,7 +593,7 @@ class StreamingBatchService:
             first[b] = r.lim.out_next                                   # the output stage sees the limiter's samples
         for window in sorted({reqs[b].limiter[:2] for b in limited}):   # (one call: a tick's limiters share attack and hold as a rule)
             group = [b for b in limited if reqs[b].limiter[:2] == window]
-            done = limiter.push_rows(eng, [(reqs[b].lim, pieces[b], reqs[b].pos + counts[b] >= reqs[b].L) for b in group])
+            done = limiter.push_rows(eng, [(reqs[b].lim, pieces[b], last[b]) for b in group])
             for b, y in zip(group, done):
                 pieces[b] = y
         job, rode = [], []
