@@ -1172,8 +1172,8 @@ int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, in
  * max_gain_db; a workspace too small is VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload of its rows (20
  * bytes a row: the lengths and the params, pageable host memory as the prosody calls'), allocates nothing and does not
  * synchronise.  n_samples_host, params_host: HOST arrays [B].
- * Not computed: true peak (sample peak only; the meter of a later section has it), stereo and channel weights, loudness
- * range.  Momentary, short-term and running loudness: "loudness over time" below. */
+ * Not computed: true peak (sample peak only; the meter of a later section has it), stereo and channel weights.  Momentary,
+ * short-term and running loudness: "loudness over time" below; loudness range: the section behind it. */
 typedef struct vsp_loudness_params {
   float target_lufs, peak_ceiling, max_gain_db;
 } vsp_loudness_params;
@@ -1237,7 +1237,8 @@ int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int
  * row: a piece that does not start on a segment boundary, first + count above the table, a negative or NaN max_gain_db or
  * max_cut_db, slew_db_per_s not above 0, a non-finite initial_gain_db, fs out of range; a workspace too small is
  * VSP_ERR_WORKSPACE.  Each call runs on `stream` behind ONE upload, allocates nothing and does not synchronise.
- * Not computed: loudness range, stereo, steering by the short-term level. */
+ * Not computed: stereo, steering by the short-term level.  Loudness range, and a running level at a constant cost per
+ * entry: "loudness range and the histogram gate" below. */
 typedef struct vsp_loudness_level_params {
   float target_lufs, max_gain_db, max_cut_db, slew_db_per_s, initial_gain_db;
 } vsp_loudness_level_params;
@@ -1283,6 +1284,53 @@ int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sam
                        int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_level_params* params_host, float* M, float* S,
                        float* I, int32_t* kept, float* c_db, float* c, int64_t table_stride, float* m_max, float* s_max, float* i_end,
                        float* peak, void* workspace, int64_t workspace_bytes);
+
+/* ---- loudness range and the histogram gate (round 24, ABI 7, additive) */
+/* Loudness range (EBU Tech 3342) and a running integrated level whose cost per entry does not grow with the stream, both
+ * from histograms of block loudness in 0.1 LU bins over -70 .. +30 LUFS.  The specification is this project's own, restated
+ * in numpy in tests/loudness_hist_ref.py.  h, the K-weighting, seg[s], M[s], S[s] and F are those of "loudness over time"
+ * above, unchanged and in the same bits.  All arithmetic is in double unless stated.
+ *   tables     NB = 1000 bins; edges e_k = pow(10, (k - 693.09) / 100), k = 1 .. 1000, and e_0 = Z_abs by the expression of
+ *              "loudness" above (the formula at k = 0 is the same number with its exponent rounded another way, 2e-15 off:
+ *              both gates share one absolute gate in every bit); bin k covers [-70 + k/10, -70 + (k+1)/10) LUFS; centres
+ *              c_k = pow(10, (k - 692.59) / 100), k = 0 .. 999.  Built on the host; the same bits travel to the device
+ *              with every call.
+ *   binning    a mean square z is not counted where !(z >= e_0) (the absolute gate); else its bin is the largest k <= 999
+ *              with e_k <= z, found by comparisons against the edges only (no logarithm: a bin cannot flip on a
+ *              transcendental's last bit).  Everything at or above e_999 lands in bin 999.
+ *   histograms two per row, int32 [2][1000]: HB counts the 400 ms blocks -- the one ending at segment s >= 3 has z = E /
+ *              (4 h), E as M[s]'s --, HS the 3 s windows -- the one ending at s >= 29 has z = T_s / (30 h).
+ *   I_h[s]     float32, from HB after the entries 0 .. s: n_abs = sum HB[k]; mean_abs = sum HB[k] c_k / n_abs; bin k is kept
+ *              iff 10 c_k > mean_abs (strict); kept[s] = the kept count; I_h[s] = fl32(-0.691 + 10 log10(sum_kept HB[k] c_k /
+ *              kept[s])), -inf with kept[s] = 0 where nothing is kept (always for s < 3: no one-block rule here).  The sums
+ *              run in an order that depends on k alone, so I_h[s] is a function of the counts.
+ *   range      from HS after the row's last entry: mean = sum HS[k] c_k / sum HS[k]; bin k is kept iff 100 c_k > mean (the
+ *              relative gate at -20 LU); N the kept count; in integers lo = (N + 4) / 10, hi = (95 (N - 1) + 50) / 100; k10
+ *              (k95) the smallest kept k whose cumulative kept count exceeds lo (hi); LRA = fl32(k95 - k10) / 10.f; 0 for N = 0.
+ * The state of a stream is integer counts and every value above a function of them, so any split of a stream gives the bits
+ * of the one call; the work of an entry does not depend on s.  Against the exact gate of "loudness over time": where every
+ * prefix's blocks stay a factor 1.05 clear of both gates, kept[s] agrees and |I_h[s] - I[s]| <= 0.05 LU for s >= 3 (half a
+ * bin).  The exact gate is the default everywhere and is unchanged.
+ * Refusals, the ONE upload (here with the tables: 16 KiB), no allocation and no synchronisation: as "loudness over time". */
+#define VSP_LOUDNESS_HIST_BINS 1000
+/* edges[1001], centres[1000].  Host only. */
+int vsp_loudness_hist_tables(double* edges, double* centres);
+/* Workspace of any call of this section for B rows of up to L_max samples (VSP_ERR_ARG as a negative size); monotone in B
+ * and L_max.  vsp_loudness_time_hist needs that of L_max = 1. */
+int64_t vsp_loudness_hist_workspace_bytes(int B, int64_t L_max, int sample_rate);
+/* vsp_loudness_time under the histogram gate: the entries [first, first + count) of M, S (its bits), I = I_h and kept.
+ * hist_host: a HOST array of B device pointers to [2][1000] int32 (HB, then HS), none NULL; a histogram is read as the
+ * state after the entries [0, first) -- at first == 0 it is taken as zero, whatever it holds -- and left as the state after
+ * first + count.  lra [B] float32 (device) or NULL: the range after the call's last entry.  m_max, s_max as there.  One
+ * launch, one wave per row, and one for the maxima. */
+int vsp_loudness_time_hist(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, int32_t* const* hist_host,
+                           float* m_max, float* s_max, float* lra, void* workspace, int64_t workspace_bytes);
+/* Whole rows audio[b][0 .. n_b) behind one upload: the three segment launches, then the histogram launch from zero
+ * histograms, which live in the workspace as seg does.  lra [B]; i_hist [B] or NULL: I_h[F - 1], -inf for F = 0; M, S, I,
+ * kept [B][table_stride], table_stride >= L_max / h, written for s < F_b only: all four or all four NULL. */
+int vsp_loudness_range(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                       const int64_t* n_samples_host, float* lra, float* i_hist, float* M, float* S, float* I, int32_t* kept,
+                       int64_t table_stride, void* workspace, int64_t workspace_bytes);
 
 /* ---- true peak and look-ahead limiter (round 22, ABI 7, additive) --- */
 /* A true-peak meter and a look-ahead limiter without a recurrence, per row of a ragged batch of mono float32 rows or of a

@@ -10,10 +10,20 @@ Every figure stands beside a call of the SAME run:
    position, because both gate passes run over the blocks of the prefix.  The tables are built through the table operator
    on a constructed segment table, and the tick's ``loudness_time`` call is also timed alone at both positions.
 
+``--gate histogram`` measures, in ONE session, the histogram gate beside the exact one:
+
+4. the tick of 16 streams 100 segments in and 36 000 segments in, under both gates, and each tick's table call alone
+   (``loudness_time`` / ``loudness_time_hist``): the histogram gate's work per entry does not depend on the position;
+5. ``Engine.loudness_range`` on 16 rows of 10 s beside ``Engine.loudness_level`` as a meter (``loudness_profile``'s exact call)
+   and the ``Engine.generator`` call that produces 16 such rows;
+6. ``max |I_h - I|`` over those rows' entries from the fourth on, beside the derived 0.05 LU.
+
 Device-event times per call (``torch.cuda.Event``) over a window of ``steps`` calls after a warm-up of the same shape; best /
 median / spread of ``rounds`` rounds that alternate over the calls.  No gate is set on any of them.
 
-usage: tools/loudness_time_measure.py [steps] [rounds] [out.txt]      (default out: profiles/r23_loudness_time.txt)"""
+usage: tools/loudness_time_measure.py [--gate {exact,histogram}] [steps] [rounds] [out.txt]
+       (default out: profiles/r23_loudness_time.txt; with --gate histogram profiles/r24_loudness_hist.txt)"""
+import argparse
 import os
 import sys
 
@@ -29,10 +39,15 @@ from vispeech_amd.models import SynthesizerTrn          # noqa: E402
 from vispeech_amd.schema import dims_from_ctor          # noqa: E402
 from vispeech_amd.synth import synth_state_dict         # noqa: E402
 
-STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r23_loudness_time.txt")
-SECONDS, B, CHUNK, LONG = 10, 16, 64, 36000
+_p = argparse.ArgumentParser(description="loudness over time, measured on the GPU")
+_p.add_argument("--gate", choices=("exact", "histogram"), default="exact")
+_p.add_argument("steps", nargs="?", type=int, default=10)
+_p.add_argument("rounds", nargs="?", type=int, default=3)
+_p.add_argument("out", nargs="?", default=None)
+ARGS = _p.parse_args()
+STEPS, ROUNDS, GATE = ARGS.steps, ARGS.rounds, ARGS.gate
+OUT = ARGS.out or os.path.join(ROOT, "profiles", "r23_loudness_time.txt" if GATE == "exact" else "r24_loudness_hist.txt")
+SECONDS, B, CHUNK, LONG, SHORT = 10, 16, 64, 36000, 100
 
 
 def timed(fn, steps):
@@ -85,6 +100,8 @@ def main():
     # the tick: 16 streams, each fed the next 64 frames of its row (the rows wrap around)
     piece = CHUNK * up
     spec = dict(target_lufs=-23.0)
+    if GATE == "histogram":
+        return histogram_session(eng, dims, audio, n_samples, Z, enc["g"], spec, r)
 
     def streams_at(segments):
         sts = [loudness.Stream(eng, fs, level=spec) for _ in range(B)]
@@ -151,6 +168,114 @@ def main():
               f"{LONG} segments",
               f"   rows before {before.min():.2f} .. {before.max():.2f} LUFS; levelled (target -23 LUFS, 3 dB/s, +-12 dB) "
               f"{after.min():.2f} .. {after.max():.2f} LUFS; gain at the rows' ends {np.nanmin(c_db[:, -1]):+.2f} .. {np.nanmax(c_db[:, -1]):+.2f} dB"]
+    assert eng.status() == 0
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        f.write(text + "\n")
+
+
+def histogram_session(eng, dims, audio, n_samples, Z, g, spec, r):
+    fs, up = dims.sampling_rate, dims.total_upsample
+    h = loudness.segment_samples(fs)
+    n = n_samples[0]
+    piece = CHUNK * up
+    count = piece // h
+    names = ("M", "S", "I", "kept")
+
+    def tables(sts):
+        return tuple([getattr(s, k) for s in sts] for k in names)
+
+    def streams_at(segments, gate):
+        sts = [loudness.Stream(eng, fs, level=spec, gate=gate) for _ in range(B)]
+        table = torch.from_numpy(r.uniform(0.5, 50.0, size=(B, segments))).to("cuda:0")
+        for b, s in enumerate(sts):
+            s._grow(segments + 4096)
+            s.seg[:segments] = table[b]
+        if gate == "exact":
+            eng.loudness_time([s.seg for s in sts], 0, segments, fs, tables=tables(sts))
+        else:
+            eng.loudness_time_hist([s.seg for s in sts], 0, segments, fs, [s.hist for s in sts], tables=tables(sts))
+        eng.loudness_level_gains([s.I for s in sts], 0, segments, [spec] * B, tables=([s.c_db for s in sts], [s.c for s in sts]))
+        for s in sts:
+            s.segments, s.seen = segments, segments * h
+        return sts
+
+    sets = {(gate, at): streams_at(at, gate) for gate in ("exact", "histogram") for at in (SHORT, LONG)}
+    k0 = [0]
+
+    def tick(sts):
+        k = k0[0] % (n // piece)
+        k0[0] += 1
+        return loudness.push_rows(eng, [(s, audio[b, k * piece: (k + 1) * piece], False) for b, s in enumerate(sts)])
+
+    def alone(sts, first, gate):
+        # (into tables and histograms of its own: the streams' must stay what their ticks left)
+        tabs = tuple([torch.empty_like(getattr(s, k)) for s in sts] for k in names)
+        segs = [s.seg for s in sts]
+        if gate == "exact":
+            return lambda: eng.loudness_time(segs, first, count, fs, tables=tabs)
+        hists = [torch.zeros_like(s.hist) for s in sts]
+        return lambda: eng.loudness_time_hist(segs, first, count, fs, hists, tables=tabs)
+
+    frames = Z.shape[2]
+    f0 = [0]
+
+    def generator_tick():
+        k = f0[0] % (frames // CHUNK)
+        f0[0] += 1
+        return eng.generator_stream_rows([(Z[b], g[b].reshape(-1), frames, k * CHUNK, (k + 1) * CHUNK) for b in range(B)], CHUNK, pcm=False)
+
+    jobs = {}
+    for at in (SHORT, LONG):
+        for gate in ("exact", "histogram"):
+            jobs[f"tick: push_rows at {at} segments, {gate}"] = (lambda sts: lambda: tick(sts))(sets[(gate, at)])
+    for at in (SHORT, LONG):
+        jobs[f"loudness_time alone, entries {at - count} .."] = alone(sets[("exact", at)], at - count, "exact")
+        jobs[f"loudness_time_hist alone, entries {at - count} .."] = alone(sets[("histogram", at)], at - count, "histogram")
+    jobs["tick: generator_stream_rows"] = generator_tick
+    jobs["loudness_range, 16 rows of 10 s"] = lambda: eng.loudness_range(audio, n_samples, fs)
+    jobs["loudness_level (meter), 16 rows of 10 s"] = lambda: eng.loudness_level(audio, n_samples, fs)
+    jobs["generator, 16 rows of 10 s"] = lambda: eng.generator(Z, g)
+    ms = {k: [] for k in jobs}
+    for _ in range(ROUNDS):
+        for k, fn in jobs.items():
+            ms[k].append(timed(fn, STEPS))
+    med = lambda k: float(np.median(ms[k]))
+    spread = lambda k: max(ms[k]) - min(ms[k])
+    # the two gates on the rows measured
+    hist, exact = eng.loudness_range(audio, n_samples, fs), eng.loudness_level(audio, n_samples, fs)
+    F = n // h
+    Ih, I = hist["I"][:, 3:F].double().cpu().numpy(), exact["I"][:, 3:F].double().cpu().numpy()
+    both = np.isfinite(Ih) & np.isfinite(I)
+    same_kept = bool((hist["kept"][:, 3:F] == exact["kept"][:, 3:F]).all())
+    lra = hist["lra"].cpu().numpy()
+    props = torch.cuda.get_device_properties(0)
+    keys = list(jobs)
+    lines = [f"loudness range and the histogram gate: a tick of {B} streams with pieces of {CHUNK} frames ({piece} samples, {piece / fs:.2f} s, "
+             f"{count} entries a stream) at {fs} Hz; {B} rows of {SECONDS} s ({n} samples, {F} segments); {ROUNDS} rounds, a window of {STEPS} calls",
+             f"device {torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', 'arch not available')}, "
+             f"{props.multi_processor_count} CUs)",
+             "timer: device events around a window of calls, per call (the Engine calls include their host work and uploads; a tick of",
+             "push_rows includes its per-stream torch copies); the streams advance with every tick, so a window of ticks ends",
+             f"{(2 + STEPS) * ROUNDS * count} segments behind the position named", ""]
+    for k in jobs:
+        lines.append(f"   {k:52s} {fmt(ms[k])}")
+    t = {(gate, at): f"tick: push_rows at {at} segments, {gate}" for gate in ("exact", "histogram") for at in (SHORT, LONG)}
+    gen = med("tick: generator_stream_rows")
+    d = med(t[("histogram", LONG)]) - med(t[("histogram", SHORT)])
+    lines += ["",
+              f"   histogram tick at {LONG} - at {SHORT} segments = {d:+.3f} ms (spreads {spread(t[('histogram', SHORT)]):.3f} / "
+              f"{spread(t[('histogram', LONG)]):.3f} ms); exact tick: {med(t[('exact', LONG)]) - med(t[('exact', SHORT)]):+.3f} ms",
+              f"   histogram / exact tick at {SHORT} segments = {med(t[('histogram', SHORT)]) / med(t[('exact', SHORT)]):.2f}, at {LONG} = "
+              f"{med(t[('histogram', LONG)]) / med(t[('exact', LONG)]):.2f}",
+              f"   tick / the tick's generator call: exact {med(t[('exact', SHORT)]) / gen * 100:.1f} % and {med(t[('exact', LONG)]) / gen * 100:.1f} %; "
+              f"histogram {med(t[('histogram', SHORT)]) / gen * 100:.1f} % and {med(t[('histogram', LONG)]) / gen * 100:.1f} %",
+              f"   loudness_range / loudness_level (meter) = {med(keys[-3]) / med(keys[-2]):.2f}; / the generator call of the rows = "
+              f"{med(keys[-3]) / med(keys[-1]) * 100:.2f} %",
+              f"   max |I_h - I| over {int(both.sum())} entries of the rows = {float(np.abs(Ih - I)[both].max()):.4f} LU (derived: 0.05 where every "
+              f"prefix stays 1.05 clear of both gates); kept equal at every entry: {same_kept}; LRA of the rows {lra.min():.1f} .. {lra.max():.1f} LU"]
     assert eng.status() == 0
     text = "\n".join(lines)
     print(text)

@@ -191,6 +191,7 @@ class VspLimiterRow(C.Structure):
 
 LIMITER_MAX_ATTACK, LIMITER_MAX_HOLD, LIMITER_REACH = 1024, 8192, 12   # samples: A, H and the meter's reach J a side
 LOUDNESS_FS_MIN, LOUDNESS_FS_MAX = 8000, 192000                      # the sample rates the loudness calls take
+LOUDNESS_HIST_BINS = 1000                                            # VSP_LOUDNESS_HIST_BINS
 PROSODY_FS, PROSODY_NFFT = 44100, 1280                             # VSP_PROSODY_*
 PROSODY_MAX_CANDIDATES, PROSODY_SLOTS = 15, 16                       # VSP_PROSODY_MAX_CANDIDATES; floats of a frame in a table
 OUT_F32, OUT_S16, OUT_ULAW, OUT_ALAW = 0, 1, 2, 3                    # VSP_OUT_* (vsp_output_rows)
@@ -349,6 +350,10 @@ SIGNATURES = {
     "vsp_loudness_level_apply": (_I, [_P, _P, _I, _I, C.POINTER(VspLoudnessRow), C.POINTER(VspLoudnessLevelParams), _P, _I64]),
     "vsp_loudness_level": (_I, [_P, _P, _I, _I64, _I, _P, _I64, _P, _I64, C.POINTER(_I64), C.POINTER(VspLoudnessLevelParams), _P, _P, _P,
                                 _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64]),
+    "vsp_loudness_hist_tables": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "vsp_loudness_hist_workspace_bytes": (_I64, [_I, _I64, _I]),
+    "vsp_loudness_time_hist": (_I, [_P, _P, _I, _I, C.POINTER(VspLoudnessRow), C.POINTER(_P), _P, _P, _P, _P, _I64]),
+    "vsp_loudness_range": (_I, [_P, _P, _I, _I64, _I, _P, _I64, C.POINTER(_I64), _P, _P, _P, _P, _P, _P, _I64, _P, _I64]),
     "vsp_true_peak_filter": (_I, [C.POINTER(C.c_float)]),
     "vsp_limiter_history": (_I, [_I, _I, C.POINTER(_I64), C.POINTER(_I64)]),
     "vsp_limiter_workspace_bytes": (_I64, [_I, _I64, _I, _I]),

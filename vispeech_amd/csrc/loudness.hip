@@ -384,6 +384,26 @@ struct LRow {                            // uploaded with every call of this sec
 
 __device__ __forceinline__ float db_to_linear(float db) { return (float)pow(10.0, (double)db / 20.0); }
 
+// M[s] and S[s] of one entry, with the energies they are the logarithms of: E of the 400 ms block and T of the 3 s window
+// that end at segment s (0 where there is none yet).  The one body of lk_time_kernel and lk_hist_kernel.
+struct Levels { float M, S; double E, T; };
+
+__device__ __forceinline__ Levels time_levels(const double* __restrict__ seg, int s, int h) {
+  Levels v = {-INFINITY, -INFINITY, 0.0, 0.0};
+  if (s >= 3) {
+    const double E = ((seg[s - 3] + seg[s - 2]) + seg[s - 1]) + seg[s];
+    if (E > 0.0) v.M = (float)(-0.691 + 10.0 * log10(E / (4.0 * (double)h)));
+    v.E = E;
+  }
+  if (s >= 29) {
+    double T = 0.0;
+    for (int k = s - 29; k <= s; ++k) T += seg[k];
+    if (T > 0.0) v.S = (float)(-0.691 + 10.0 * log10(T / (30.0 * (double)h)));
+    v.T = T;
+  }
+  return v;
+}
+
 __global__ void __launch_bounds__(64) lk_time_kernel(const LRow* __restrict__ rows, int h, double z_abs) {
   const int b = blockIdx.y, lane = threadIdx.x;
   const LRow r = rows[b];
@@ -392,20 +412,165 @@ __global__ void __launch_bounds__(64) lk_time_kernel(const LRow* __restrict__ ro
   const double* __restrict__ seg = r.seg;
   const Gated g = gate_wave(seg, (s + 1) * h, h, z_abs, lane);
   if (lane != 0) return;
-  float M = -INFINITY, S = -INFINITY;
-  if (s >= 3) {
-    const double E = ((seg[s - 3] + seg[s - 2]) + seg[s - 1]) + seg[s];
-    if (E > 0.0) M = (float)(-0.691 + 10.0 * log10(E / (4.0 * (double)h)));
-  }
-  if (s >= 29) {
-    double T = 0.0;
-    for (int k = s - 29; k <= s; ++k) T += seg[k];
-    if (T > 0.0) S = (float)(-0.691 + 10.0 * log10(T / (30.0 * (double)h)));
-  }
-  r.M[s] = M;
-  r.S[s] = S;
+  const Levels v = time_levels(seg, s, h);
+  r.M[s] = v.M;
+  r.S[s] = v.S;
   r.I[s] = g.L;
   r.kept[s] = g.kept;
+}
+
+// ------------------------------------------------------------------- the histogram gate and loudness range
+// lk_hist_kernel: one wave per row, no atomics, and no block waits for another.  The wave keeps the row's two histograms in
+// registers -- bin k in lane k & 63, slot k >> 6: 16 bins a lane -- with the bins' centres beside them, and the 1001 edges
+// in LDS.  64 entries at a time, lane i computes M, S (time_levels) and the two bin indices of entry first + i0 + i (a 10-step
+// binary search over the edges: comparisons only); then the wave walks those entries in order: it bumps the two counts and
+// makes the two gated passes over its 16 bins a lane, each followed by a butterfly, so that every sum runs in an order
+// that depends on k alone and I[s] is a function of the counts.  The quotient of entry i is parked in lane i; its
+// logarithm is taken lane-parallel behind the walk.  The work of an entry does not depend on s: no loop runs over the prefix.
+constexpr int LK_HIST_BINS = VSP_LOUDNESS_HIST_BINS, LK_HIST_SLOTS = 16;
+static_assert(LK_HIST_SLOTS * 64 >= LK_HIST_BINS && LK_HIST_BINS <= 1023, "16 bins a lane; a 10-step search");
+
+struct HistArgs {
+  const LRow* rows;
+  int32_t* const* hist;    // [B] -> [2][1000]
+  const double* edges;     // [1001]
+  const double* centres;   // [1000]
+  float* lra;              // [B] or NULL
+  float* i_last;           // [B] or NULL: I of the call's last entry (-inf where it has none)
+  int h;
+};
+
+// The largest k <= 999 with e[k] <= z, or -1 where !(z >= e[0]).  e holds 1024 doubles, +inf behind the edges.
+__device__ __forceinline__ int hist_bin(const double* e, double z) {
+  if (!(z >= e[0])) return -1;
+  int k = 0;
+#pragma unroll
+  for (int step = 512; step >= 1; step >>= 1) {
+    const int t = k + step;
+    if (t < LK_HIST_BINS && e[t] <= z) k = t;
+  }
+  return k;
+}
+
+// sum = the sum of n[k] c[k] and cnt = the sum of n[k] over the bins with factor c[k] > above: a lane's bins in ascending slot,
+// then a butterfly (the same bits in every lane).
+__device__ __forceinline__ void hist_sum(const int (&n)[LK_HIST_SLOTS], const double (&c)[LK_HIST_SLOTS], double factor, double above,
+                                         double& sum, int& cnt) {
+  sum = 0.0;
+  cnt = 0;
+#pragma unroll
+  for (int j = 0; j < LK_HIST_SLOTS; ++j)
+    if (factor * c[j] > above) {
+      sum += (double)n[j] * c[j];
+      cnt += n[j];
+    }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    sum += __shfl_xor(sum, d);
+    cnt += __shfl_xor(cnt, d);
+  }
+}
+
+__global__ void __launch_bounds__(64) lk_hist_kernel(const HistArgs a) {
+  __shared__ double e[1024];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const LRow r = a.rows[b];
+  int32_t* hist = a.hist[b];
+  for (int k = lane; k < 1024; k += 64) e[k] = k <= LK_HIST_BINS ? a.edges[k] : INFINITY;
+  double c[LK_HIST_SLOTS];
+  int hb[LK_HIST_SLOTS], hs[LK_HIST_SLOTS];
+#pragma unroll
+  for (int j = 0; j < LK_HIST_SLOTS; ++j) {
+    const int k = j * 64 + lane;
+    const bool in = k < LK_HIST_BINS;
+    c[j] = in ? a.centres[k] : 0.0;                // (a bin behind the last: count 0, never kept)
+    hb[j] = in && r.first ? hist[k] : 0;           // at first == 0 the histograms start from zero, whatever they hold
+    hs[j] = in && r.first ? hist[LK_HIST_BINS + k] : 0;
+  }
+  __syncthreads();
+  const double DB = 4.0 * (double)a.h, DS = 30.0 * (double)a.h;
+  if (r.count == 0 && a.i_last && lane == 0) a.i_last[b] = -INFINITY;
+  for (int i0 = 0; i0 < r.count; i0 += 64) {
+    const int s = r.first + i0 + lane;
+    const bool mine = i0 + lane < r.count;
+    Levels v = {-INFINITY, -INFINITY, 0.0, 0.0};
+    int kb = -1, ks = -1;
+    if (mine) {
+      v = time_levels(r.seg, s, a.h);
+      if (s >= 3) kb = hist_bin(e, v.E / DB);
+      if (s >= 29) ks = hist_bin(e, v.T / DS);
+    }
+    double q = 0.0;
+    int kept = 0;
+    const int cnt = min(64, r.count - i0);
+    for (int i = 0; i < cnt; ++i) {                // (every lane walks alike)
+      const int kbi = __shfl(kb, i), ksi = __shfl(ks, i);
+#pragma unroll
+      for (int j = 0; j < LK_HIST_SLOTS; ++j) {
+        hb[j] += kbi == j * 64 + lane ? 1 : 0;
+        hs[j] += ksi == j * 64 + lane ? 1 : 0;
+      }
+      double sum_abs, sum_kept;
+      int n_abs, n_kept;
+      hist_sum(hb, c, 1.0, -1.0, sum_abs, n_abs);
+      const double mean_abs = n_abs ? sum_abs / (double)n_abs : 0.0;
+      hist_sum(hb, c, 10.0, mean_abs, sum_kept, n_kept);
+      if (lane == i) {
+        q = n_kept ? sum_kept / (double)n_kept : 0.0;
+        kept = n_kept;
+      }
+    }
+    if (mine) {
+      const float I = kept ? (float)(-0.691 + 10.0 * log10(q)) : -INFINITY;
+      if (r.M) {
+        r.M[s] = v.M;
+        r.S[s] = v.S;
+        r.I[s] = I;
+        r.kept[s] = kept;
+      }
+      if (a.i_last && i0 + lane == r.count - 1) a.i_last[b] = I;
+    }
+  }
+  if (a.lra) {                                     // the range: percentiles of the kept 3 s windows, by their bins
+    double sum;
+    int n_all;
+    hist_sum(hs, c, 1.0, -1.0, sum, n_all);
+    const double mean = n_all ? sum / (double)n_all : 0.0;
+    int N = 0;
+    int keptj[LK_HIST_SLOTS];
+#pragma unroll
+    for (int j = 0; j < LK_HIST_SLOTS; ++j) {
+      keptj[j] = 100.0 * c[j] > mean ? hs[j] : 0;
+      N += keptj[j];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) N += __shfl_xor(N, d);
+    const int lo = (N + 4) / 10, hi = N ? (int)((95ll * (N - 1) + 50) / 100) : 0;
+    int k10 = -1, k95 = -1, base = 0;
+#pragma unroll
+    for (int j = 0; j < LK_HIST_SLOTS; ++j) {      // cumulative kept counts in ascending k: a scan through the wave per slot
+      int cum = keptj[j];
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(cum, d);
+        if (lane >= d) cum += t;
+      }
+      cum += base;
+      const unsigned long long m10 = __ballot(cum > lo), m95 = __ballot(cum > hi);
+      if (k10 < 0 && m10) k10 = j * 64 + __ffsll((long long)m10) - 1;
+      if (k95 < 0 && m95) k95 = j * 64 + __ffsll((long long)m95) - 1;
+      base = __shfl(cum, 63);
+    }
+    if (lane == 0) a.lra[b] = N ? (float)(k95 - k10) / 10.f : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < LK_HIST_SLOTS; ++j) {
+    const int k = j * 64 + lane;
+    if (k < LK_HIST_BINS) {
+      hist[k] = hb[j];
+      hist[LK_HIST_BINS + k] = hs[j];
+    }
+  }
 }
 
 __global__ void __launch_bounds__(64) lk_time_max_kernel(const LRow* __restrict__ rows, float* m_max, float* s_max) {
@@ -1010,4 +1175,135 @@ int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sam
   if (!params_host) return VSP_OK;
   if (const int rc = launch_level_gains(ctx, s, B, dev)) return rc;
   return launch_level_apply(ctx, s, B, L_max, h, dev);
+}
+
+// --------------------------------------------------------------- loudness range and the histogram gate: entry points
+namespace {
+
+constexpr size_t LK_HIST_TABLE_DOUBLES = 2 * LK_HIST_BINS + 1;      // the edges, then the centres
+
+void hist_tables(double* edges, double* centres) {
+  for (int k = 0; k <= LK_HIST_BINS; ++k) edges[k] = std::pow(10.0, ((double)k - 693.09) / 100.0);
+  edges[0] = std::pow(10.0, (-70.0 + 0.691) / 10.0);     // Z_abs by the exact gate's own expression (the line above is 2e-15 off it)
+  for (int k = 0; k < LK_HIST_BINS; ++k) centres[k] = std::pow(10.0, ((double)k - 692.59) / 100.0);
+}
+
+// [rows (as every loudness call)] [LRow [B]] [histogram pointers [B]] [edges, centres] and, for the fused call,
+// [ends] [starts] [seg] [blocks] [peak [B]] [histograms [B][2][1000]]
+size_t hist_ptrs_bytes(int B) { return align256((size_t)B * sizeof(int32_t*)); }
+size_t hist_head(int B) { return time_head(B) + hist_ptrs_bytes(B) + align256(LK_HIST_TABLE_DOUBLES * sizeof(double)); }
+
+// What a call of this section uploads behind the rows of the segment kernels: the LRows, the histogram pointers, the tables.
+struct HistUpload {
+  std::vector<char> bytes;               // the workspace's first hist_head(B) bytes
+  LRow* rows;
+  int32_t** hist;
+  explicit HistUpload(int B) : bytes(hist_head(B), 0) {
+    rows = reinterpret_cast<LRow*>(bytes.data() + rows_bytes(B));
+    hist = reinterpret_cast<int32_t**>(bytes.data() + time_head(B));
+    double* t = reinterpret_cast<double*>(bytes.data() + time_head(B) + hist_ptrs_bytes(B));
+    hist_tables(t, t + LK_HIST_BINS + 1);
+  }
+  // One copy of [from, the end); the kernel's arguments point into the workspace.
+  int send(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, size_t from, float* lra, float* i_last, int h, HistArgs& a) const {
+    const hipError_t e = hipMemcpyAsync(ws + from, bytes.data() + from, bytes.size() - from, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
+    a.rows = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
+    a.hist = reinterpret_cast<int32_t* const*>(ws + time_head(B));
+    a.edges = reinterpret_cast<const double*>(ws + time_head(B) + hist_ptrs_bytes(B));
+    a.centres = a.edges + LK_HIST_BINS + 1;
+    a.lra = lra; a.i_last = i_last; a.h = h;
+    return VSP_OK;
+  }
+};
+
+int launch_hist(vsp_ctx* ctx, hipStream_t s, int B, const HistArgs& a, float* m_max, float* s_max) {
+  hipLaunchKernelGGL(lk_hist_kernel, dim3(B), dim3(64), 0, s, a);
+  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, s, a.rows, m_max, s_max);
+  return launched(ctx, "loudness histogram");
+}
+
+}  // namespace
+
+int vsp_loudness_hist_tables(double* edges, double* centres) {
+  if (!edges || !centres) return VSP_ERR_ARG;
+  hist_tables(edges, centres);
+  return VSP_OK;
+}
+
+int64_t vsp_loudness_hist_workspace_bytes(int B, int64_t L_max, int sample_rate) {
+  if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
+  return (int64_t)(hist_head(B) + layout(B, segments_of(L_max, sample_rate)).end + align256((size_t)B * sizeof(float)) +
+                   align256((size_t)B * 2 * LK_HIST_BINS * sizeof(int32_t)));
+}
+
+int vsp_loudness_time_hist(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, int32_t* const* hist_host,
+                           float* m_max, float* s_max, float* lra, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_time_hist";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  if (B < 1 || B > LK_MAX_B || !rows_host || !hist_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their histograms", who, LK_MAX_B);
+  const int h = segment_samples(sample_rate);
+  HistUpload up(B);
+  for (int b = 0; b < B; ++b) {
+    const vsp_loudness_row& r = rows_host[b];
+    if (const int rc = check_entries(ctx, who, b, r, h)) return rc;
+    if (r.count && (!r.seg || !r.M || !r.S || !r.I || !r.kept)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    if (!hist_host[b]) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null histogram", who, b);
+    LRow& d = up.rows[b];
+    d.seg = r.seg; d.M = r.M; d.S = r.S; d.I = r.I; d.kept = r.kept;
+    d.first = (int32_t)r.first; d.count = (int32_t)r.count;
+    up.hist[b] = hist_host[b];
+  }
+  if (!m_max != !s_max) return ctx->fail(VSP_ERR_ARG, "%s: m_max and s_max come together", who);
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, hist_head(B))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HistArgs a;
+  if (const int rc = up.send(ctx, who, s, static_cast<char*>(workspace), B, rows_bytes(B), lra, nullptr, h, a)) return rc;
+  return launch_hist(ctx, s, B, a, m_max, s_max);
+}
+
+int vsp_loudness_range(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                       const int64_t* n_samples_host, float* lra, float* i_hist, float* M, float* S, float* I, int32_t* kept,
+                       int64_t table_stride, void* workspace, int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_loudness_range";
+  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const int h = segment_samples(sample_rate);
+  const bool tables = M || S || I || kept;
+  if (tables && (!M || !S || !I || !kept)) return ctx->fail(VSP_ERR_ARG, "%s: M, S, I and kept come together", who);
+  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host || (tables && table_stride < L_max / h))
+    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, table_stride >= L_max / h, and the rows' samples", who,
+                     LK_MAX_B);
+  std::vector<int32_t> rows_up;
+  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, rows_up)) return rc;
+  if (!audio || !lra) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  const Ws lay = layout(B, S_max);                      // (behind the head)
+  const size_t shift = hist_head(B);
+  const size_t peak_at = shift + lay.end, hist_at = peak_at + align256((size_t)B * sizeof(float));
+  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, hist_at + align256((size_t)B * 2 * LK_HIST_BINS * sizeof(int32_t)))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  double* seg = reinterpret_cast<double*>(ws + shift + lay.seg);
+  HistUpload up(B);                                     // ONE upload: the rows of the segment kernels, then the rows of this section
+  std::memcpy(up.bytes.data(), rows_up.data(), rows_up.size() * sizeof(int32_t));
+  for (int b = 0; b < B; ++b) {
+    LRow& d = up.rows[b];
+    const size_t t = (size_t)b * table_stride;
+    d.seg = seg + (size_t)b * S_max;
+    if (tables) { d.M = M + t; d.S = S + t; d.I = I + t; d.kept = kept + t; }
+    d.first = 0; d.count = (int32_t)(n_samples_host[b] / h);
+    up.hist[b] = reinterpret_cast<int32_t*>(ws + hist_at) + (size_t)b * 2 * LK_HIST_BINS;
+  }
+  HistArgs a;
+  if (const int rc = up.send(ctx, who, s, ws, B, 0, lra, i_hist, h, a)) return rc;
+  Rows rows;
+  rows.n = reinterpret_cast<const int32_t*>(ws);
+  rows.n_apply = rows.n + B;
+  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
+  if (const int rc = launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws + shift, lay, seg,
+                                     reinterpret_cast<float*>(ws + peak_at), nullptr, nullptr))
+    return rc;
+  return launch_hist(ctx, s, B, a, nullptr, nullptr);
 }

@@ -1974,6 +1974,71 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_loudness_level")
         return r
 
+    # ------------------------------------------------------------------ loudness range and the histogram gate (section 4s)
+    def loudness_hist_tables(self):
+        """``vsp_loudness_hist_tables``: ``(edges [1001], centres [1000])`` float64 numpy arrays, the bits the device gets."""
+        e, c = np.empty(_lib.LOUDNESS_HIST_BINS + 1, np.float64), np.empty(_lib.LOUDNESS_HIST_BINS, np.float64)
+        rc = self.lib.vsp_loudness_hist_tables(e.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_double)))
+        _lib.check(rc, None, "vsp_loudness_hist_tables")
+        return e, c
+
+    def loudness_hist_state(self, B: int):
+        """The histograms of B new streams: ``[B, 2, 1000]`` int32 zeros on the device (the 400 ms blocks, the 3 s windows)."""
+        return torch.zeros((B, 2, _lib.LOUDNESS_HIST_BINS), dtype=torch.int32, device=self.device)
+
+    def loudness_time_hist(self, seg, first, count, sample_rate: int, hist, tables=None):
+        """``vsp_loudness_time_hist``: ``loudness_time`` under the histogram gate.  ``hist``: ``[B, 2, 1000]`` int32 or B
+        ``[2, 1000]`` tensors allocated apart, on the device: each row's state after its entries ``[0, first_b)`` (taken as
+        zero at ``first_b == 0``), advanced IN PLACE to the state after ``first_b + count_b``.  Returns ``(M, S, I, kept, m_max,
+        s_max, lra)``: ``M`` and ``S`` are ``loudness_time``'s, ``I`` and ``kept`` the histogram gate's, ``lra`` ``[B]`` the
+        loudness range after this call's last entry.  The work of an entry does not depend on where the stream stands."""
+        segs = self._own_rows(seg, torch.float64, "seg")
+        B = len(segs)
+        if B == 0:
+            raise ValueError("loudness_time_hist: at least one row")
+        first, count = self._ints(first, B, "first"), self._ints(count, B, "count")
+        hs = list(hist)
+        if len(hs) != B:
+            raise ValueError(f"hist must have {B} rows")
+        for b, t in enumerate(hs):
+            if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device == self.device and t.is_contiguous()
+                    and tuple(t.shape) == (2, _lib.LOUDNESS_HIST_BINS)):
+                raise ValueError(f"hist: row {b} must be a contiguous [2, {_lib.LOUDNESS_HIST_BINS}] int32 tensor on the engine's device")
+        if tables is None:
+            T = max(1, max(f + c for f, c in zip(first, count)))
+            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(3)) + \
+                (torch.full((B, T), -1, dtype=torch.int32, device=self.device),)
+        M, S, I, kept = tables
+        rows = [self._own_rows(t, torch.float32, n, B) for t, n in ((M, "M"), (S, "S"), (I, "I"))] + [self._own_rows(kept, torch.int32, "kept", B)]
+        desc = (_lib.VspLoudnessRow * B)()
+        for b in range(B):
+            entries = min([segs[b].numel()] + [r[b].numel() for r in rows])
+            desc[b] = _lib.VspLoudnessRow(seg=segs[b].data_ptr(), M=rows[0][b].data_ptr(), S=rows[1][b].data_ptr(), I=rows[2][b].data_ptr(),
+                                          kept=rows[3][b].data_ptr(), first=first[b], count=count[b], entries=entries)
+        m_max, s_max, lra = self._f(B), self._f(B), self._f(B)
+        ws = self._workspace("loudness", self.lib.vsp_loudness_hist_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_time_hist(self.ctx, self._stream(), B, int(sample_rate), desc, (C.c_void_p * B)(*[t.data_ptr() for t in hs]),
+                                                 _ptr(m_max), _ptr(s_max), _ptr(lra), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_time_hist")
+        return M, S, I, kept, m_max, s_max, lra
+
+    def loudness_range(self, audio, n_samples, sample_rate: int):
+        """``vsp_loudness_range``: whole rows in ONE call -- segments, then the histogram gate from zero histograms.  Returns a
+        dict: ``lra`` ``[B]`` float32 (LU), ``i_hist`` ``[B]`` (the running level at the row's last complete segment, -inf
+        where it has none), ``M, S, I`` ``[B, F_max]`` float32 and ``kept`` int32 (NaN / -1 behind a row's entries)."""
+        a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
+        L_max = max(n_host)
+        T = max(1, L_max // ((fs + 5) // 10))
+        tab = lambda: torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device)
+        r = dict(lra=self._f(B), i_hist=self._f(B), M=tab(), S=tab(), I=tab(), kept=torch.full((B, T), -1, dtype=torch.int32, device=self.device))
+        ws = self._workspace("loudness", self.lib.vsp_loudness_hist_workspace_bytes(B, L_max, fs))
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_loudness_range(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, (C.c_int64 * B)(*n_host), _ptr(r["lra"]),
+                                             _ptr(r["i_hist"]), _ptr(r["M"]), _ptr(r["S"]), _ptr(r["I"]), _ptr(r["kept"]), T, _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_loudness_range")
+        return r
+
     # ------------------------------------------------------------------ true peak and limiter (section 4q)
     def limiter_history(self, attack: int, hold: int):
         """``vsp_limiter_history``: ``(behind, ahead)`` -- the samples before an output and after it that reach it."""

@@ -8,6 +8,8 @@ level.  All arithmetic on audio runs in the library; the classes here drive an *
     loudness_time(seg, first, count, fs, tables)    the entries [first, first + count) of (M, S, I, kept), in place
     loudness_level_gains(I, first, count, params, tables)       likewise of (c_db, c)
     loudness_level_apply(x, pos, c, entries, fs, params)        -> the levelled samples, new arrays
+    loudness_hist_state(B)                          [B, 2, 1000] int32 zeros: the histograms of B new streams      } streams with
+    loudness_time_hist(seg, first, count, fs, hist, tables)     -> (M, S, I, kept, m_max, s_max, lra)              } gate="histogram"
 
 -- which is ``vispeech_amd.engine.Engine`` in production and a numpy stand-in in the host tests (tests/loudness_time_ref.py).
 
@@ -15,7 +17,11 @@ A stream keeps, where the engine keeps its arrays (on the device in production):
 h), the 4-double filter state behind its last complete segment, its tables, which grow by doubling, and with them the gain
 reached so far.  Entry s of a table depends on the stream's first (s + 1) h samples and on s alone, and the gain over
 segment s on the samples before it, so ANY split of a stream gives the tables and the samples of the one call on the whole
-row, bit for bit -- and every sample leaves in the push it arrives in: the leveller has no look-ahead and adds no delay."""
+row, bit for bit -- and every sample leaves in the push it arrives in: the leveller has no look-ahead and adds no delay.
+
+``gate="histogram"``: the stream also keeps two histograms of block loudness, integer counts; its
+running level I is read from them at a cost that does not grow with the stream (the exact gate walks the prefix), within
+0.05 LU of the exact one, and it has a loudness range.  Every value is a function of the counts, so the rule above holds."""
 from __future__ import annotations
 
 import math
@@ -25,6 +31,8 @@ import numpy as np
 
 MAX_SAMPLES = 1 << 30                 # of a stream: 6.7 hours at 44.1 kHz, 93 minutes (55 924 segments) at 192 kHz
 FIRST_CAPACITY = 512                  # segments a new stream's tables hold (51 s); doubled when full
+
+GATES = ("exact", "histogram")
 
 LEVEL_FIELDS = dict(target_lufs=-23.0, max_gain_db=12.0, max_cut_db=12.0, slew_db_per_s=3.0, initial_gain_db=0.0)
 
@@ -94,11 +102,17 @@ def _stack(rows, width: Optional[int] = None):
 class Stream:
     """One stream through the meter and, with ``level``, the leveller.  ``push(x)`` takes the next samples (1-D float32, where
     the engine works) and returns ALL of them levelled -- or ``x`` itself when only metering.  ``level``: None / True (meter),
-    a target in LUFS, or a mapping (``spec``).  ``final`` only closes the stream: nothing is held back."""
+    a target in LUFS, or a mapping (``spec``).  ``final`` only closes the stream: nothing is held back.  ``gate``: "exact"
+    (section 4r's running level) or "histogram" (section 4s's, and a ``loudness_range``)."""
 
-    def __init__(self, engine, fs: int, level=None):
+    def __init__(self, engine, fs: int, level=None, gate: str = "exact"):
+        if gate not in GATES:
+            raise ValueError(f"loudness.Stream: gate is one of {GATES}, not {gate!r}")
         self.eng, self.fs, self.h = engine, int(fs), segment_samples(fs)
         self.level = spec(level) or None
+        self.gate = gate
+        self.hist = engine.loudness_hist_state(1)[0] if gate == "histogram" else None
+        self._lra = None
         self.open, self.seen, self.segments, self.ended = None, 0, 0, False
         self.state = engine.loudness_state(1)[0]
         self.capacity = 0
@@ -131,6 +145,13 @@ class Stream:
         if not self.level:
             return None
         return float(self.c_db[self.segments - 1]) if self.segments else self.level["initial_gain_db"]
+
+    @property
+    def loudness_range(self) -> Optional[float]:
+        """The loudness range (LU) of the complete segments so far, from the histogram of 3 s windows; None for an exact stream."""
+        if self.hist is None:
+            return None
+        return 0.0 if self._lra is None else float(self._lra)
 
     # -- one push, in the three steps of ``push_rows``
     def _take(self, x, final: bool):
@@ -167,7 +188,8 @@ class Stream:
 def push_rows(engine, pushes: Sequence[tuple]) -> List:
     """Several streams of one sample rate advance, each at its own position, in ONE set of calls: ``pushes`` is ``[(stream, x,
     final), ...]``.  The streams that complete a segment share one ``loudness_segments_from`` (their complete segments, padded to a
-    batch; the rest stays the stream's open segment) and one ``loudness_time``, the levelled ones among them one
+    batch; the rest stays the stream's open segment) and one ``loudness_time`` -- those with the histogram gate one
+    ``loudness_time_hist`` instead; a call may mix both --, the levelled ones among them one
     ``loudness_level_gains``, and every levelled stream that brought samples one ``loudness_level_apply``.  Returns, per push, its
     samples levelled (``x`` itself for a meter)."""
     if not pushes:
@@ -190,7 +212,16 @@ def push_rows(engine, pushes: Sequence[tuple]) -> List:
         for j, s in enumerate(st):
             s.seg[first[j]: first[j] + ks[j]] = seg[j, : ks[j]]
             s.state = state[j]
-        engine.loudness_time([s.seg for s in st], first, ks, fs, tables=tuple([getattr(s, n) for s in st] for n in ("M", "S", "I", "kept")))
+        exact = [j for j, s in enumerate(st) if s.hist is None]
+        if exact:
+            engine.loudness_time([st[j].seg for j in exact], [first[j] for j in exact], [ks[j] for j in exact], fs,
+                                 tables=tuple([getattr(st[j], n) for j in exact] for n in ("M", "S", "I", "kept")))
+        hg = [j for j, s in enumerate(st) if s.hist is not None]
+        if hg:
+            lra = engine.loudness_time_hist([st[j].seg for j in hg], [first[j] for j in hg], [ks[j] for j in hg], fs, [st[j].hist for j in hg],
+                                            tables=tuple([getattr(st[j], n) for j in hg] for n in ("M", "S", "I", "kept")))[-1]
+            for i, j in enumerate(hg):
+                st[j]._lra = lra[i]
         lv = [j for j, s in enumerate(st) if s.level]
         if lv:
             engine.loudness_level_gains([st[j].I for j in lv], [first[j] for j in lv], [ks[j] for j in lv], [st[j].level for j in lv],

@@ -306,14 +306,38 @@ class SynthesizerTrn:
         return self._engine.limit(audio, n_samples, ceiling, gains=gains, attack=A, hold=H, out=out)
 
     @torch.no_grad()
-    def loudness_profile(self, audio, n_samples, sample_rate: Optional[int] = None):
+    def loudness_profile(self, audio, n_samples, sample_rate: Optional[int] = None, gate: str = "exact"):
         """Loudness over time (EBU Tech 3341's M, S and I) of every row of a ragged batch, one value per
         complete 100 ms segment: returns ``(M, S, I, M_max, S_max, I_end)`` -- momentary, short-term and running integrated
         loudness ``[B, F_max]`` float32 (NaN behind row b's ``n_samples[b] // h`` entries, -inf where a value does not exist
-        yet), the rows' maxima and the integrated loudness of the whole row (``loudness``' value), all on the device."""
+        yet), the rows' maxima and the integrated loudness of the whole row (``loudness``' value), all on the device.
+
+        ``gate="histogram"`` (section 4s): ``I`` is the histogram gate's running level and ``I_end`` its value at the row's last
+        complete segment (-inf where the row has none); ``M`` and ``S`` keep their bits."""
         fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        if gate == "histogram":
+            eng = self._engine
+            seg, _ = eng.loudness_segments(audio, n_samples, fs)
+            F = [int(n) // ((fs + 5) // 10) for n in n_samples]
+            M, S, I, _, m_max, s_max, _ = eng.loudness_time_hist(seg, 0, F, fs, eng.loudness_hist_state(len(F)))
+            i_end = torch.full((len(F),), float("-inf"), dtype=torch.float32, device=I.device)
+            rows = [b for b, f in enumerate(F) if f]
+            if rows:
+                i_end[rows] = I[rows, [F[b] - 1 for b in rows]]
+            return M, S, I, m_max, s_max, i_end
+        if gate != "exact":
+            raise ValueError(f'loudness_profile: gate is "exact" or "histogram", not {gate!r}')
         r = self._engine.loudness_level(audio, n_samples, fs)
         return r["M"], r["S"], r["I"], r["m_max"], r["s_max"], r["i_end"]
+
+    @torch.no_grad()
+    def loudness_range(self, audio, n_samples, sample_rate: Optional[int] = None):
+        """The loudness range (EBU Tech 3342 from a histogram of 3 s windows in 0.1 LU bins) of every
+        row of a ragged batch, in one call: returns ``(lra, I_h)``, both ``[B]`` float32 on the device -- the range in LU (0
+        for a row with fewer than 3 s) and the histogram gate's integrated level over the row's complete 100 ms segments."""
+        fs = int(self.sampling_rate if sample_rate is None else sample_rate)
+        r = self._engine.loudness_range(audio, n_samples, fs)
+        return r["lra"], r["i_hist"]
 
     @torch.no_grad()
     def level(self, audio, n_samples, target_lufs=-23.0, max_gain_db=12, max_cut_db=12, slew_db_per_s=3, initial_gain_db=0,

@@ -190,13 +190,19 @@ class StreamingBatchService:
     with ONE ``loudness.push_rows`` call for those rows between the generator and the limiter / ``output_rows``; the request's
     samples are those of ``SynthesizerTrn.level`` on its whole waveform (then ``limit``, then the output stage).  When the
     request has finished, its stream carries ``.loudness``: ``dict(integrated, momentary_max, short_term_max, gain_db)``.
-    ``fused_output=True`` refuses the keyword; a request that names nothing gets the bytes it always got."""
+    ``fused_output=True`` refuses the keyword; a request that names nothing gets the bytes it always got.
+    ``loudness_gate="histogram"`` (round 24; "exact" is the default) gives those streams the histogram
+    gate: their running level costs the same at every tick, however long a request lasts -- what ``open_conversion`` needs
+    --, stays within 0.05 LU of the exact one, and ``.loudness`` gains ``range_lu``, the loudness range."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
-                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False):
+                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False, loudness_gate: str = "exact"):
         if not 1 <= max_batch <= 64 or chunk_frames < 1:
             raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
+        if loudness_gate not in loudness.GATES:
+            raise ValueError(f"loudness_gate is one of {loudness.GATES}, not {loudness_gate!r}")
+        self.loudness_gate = loudness_gate
         if fused_output and output_rate is None:
             raise ValueError("fused_output needs an output_rate")
         if first_chunk_frames is not None and not 1 <= first_chunk_frames <= chunk_frames:
@@ -578,13 +584,15 @@ class StreamingBatchService:
         if named:                                                       # the leveller (or meter): no delay, so `first` stands
             for b in named:
                 if reqs[b].loud is None:
-                    reqs[b].loud = loudness.Stream(eng, self.sampling_rate, level=reqs[b].level or True)
+                    reqs[b].loud = loudness.Stream(eng, self.sampling_rate, level=reqs[b].level or True, gate=self.loudness_gate)
             for b, y in zip(named, loudness.push_rows(eng, [(reqs[b].loud, pieces[b], last[b]) for b in named])):
                 pieces[b] = y
                 if last[b]:
                     st = reqs[b].loud
                     reqs[b].stream.loudness = dict(integrated=st.integrated, momentary_max=st.momentary_max,
                                                    short_term_max=st.short_term_max, gain_db=st.gain_db)
+                    if st.loudness_range is not None:
+                        reqs[b].stream.loudness["range_lu"] = st.loudness_range
         limited = [b for b, r in enumerate(reqs) if r.limiter is not None]
         for b in limited:
             r = reqs[b]
