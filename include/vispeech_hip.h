@@ -1390,6 +1390,43 @@ int vsp_true_peak(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float*
 int vsp_limiter_rows(vsp_ctx* ctx, void* stream, int B, int A, int H, const vsp_limiter_row* rows_host, const float* gains,
                      float* min_gain, void* workspace, int64_t workspace_bytes);
 
+/* ---- denoiser and inverse STFT (round 25, ABI 7, additive) ----------- */
+/* Subtracts the generator's zero-input spectrum (the "bias" of the denoisers shipped with WaveGlow and HiFi-GAN) from
+ * every STFT frame of a waveform and returns to audio by weighted overlap-add, per row of a ragged batch.  The
+ * specification is this project's own, restated in fp64 in tests/denoiser_ref.py.  Geometry: N = 2 (spec_channels - 1),
+ * hop = the generator's total upsampling, the periodic Hann window of the spectrogram front end, pad = (N - hop) / 2 with
+ * reflection at the row's own two ends, T(n) = vsp_convert_frames(n, hop).
+ *   analysis     X[r][t] = sum_n hann[n] xp[t hop + n] e^{-2 pi i r n / N}, r = 0 .. N / 2: the frames and the convolution
+ *                of vsp_spectrogram_ragged.
+ *   subtraction  m = sqrt(re^2 + im^2); q = max(m - s_b beta_b[r], 0) / m (0 where m = 0); X' = q X.
+ *   synthesis    v_t[n] = hann[n] (1 / N) sum_r w_r Re(X'[r][t] e^{+2 pi i r n / N}), w_0 = w_{N/2} = 1, else 2;
+ *                yp[p] = (sum_t v_t[p - t hop]) / W[p], W[p] = sum_t hann^2[p - t hop] over the row's OWN frames covering
+ *                p, both sums in ascending t; out[b][i] = yp[pad + i], 0 <= i < n_b.
+ * Every call refuses with VSP_ERR_ARG, before any launch, a context without a spectrogram (spec_channels <= 1), one
+ * whose hop does not divide N or whose N exceeds what a block of the overlap-add kernel stages; and, naming the row,
+ * n_b <= pad, n_b > L_max, a negative or infinite strength, a NULL bias with any finite strength.  A row whose strength
+ * is NaN is neither read nor written.  Nothing at or behind n_b is read or written; a row's bits do not depend on its
+ * batch; in == out is allowed (the frames live in the workspace).  n_samples_host and strength_host are HOST arrays [B].
+ * Each call runs on `stream` behind ONE upload of its rows (pageable host memory), allocates nothing and does not
+ * synchronise.  T_max = vsp_convert_frames(L_max, hop). */
+/* Frame operand [B][N][T_max], RI [B][2 spec][T_max], synthesis frames [B][N][T_max] (T_max padded to 64 columns) and the
+ * upload; covers vsp_istft of the same shape.  VSP_ERR_ARG as a negative size. */
+int64_t vsp_denoise_workspace_bytes(const vsp_ctx* ctx, int B, int L_max);
+/* bias[s][r] = |sum_n hann[n] period[s][n mod hop] e^{-2 pi i r n / N}|, [S][spec] float32 on the device: each period
+ * [hop] tiled to one column of the operand, the model.stft convolution, the exact magnitude (no 1e-6).  Workspace:
+ * vsp_denoise_workspace_bytes(ctx, S, N) at least. */
+int vsp_denoise_bias(vsp_ctx* ctx, void* stream, int S, const float* period, float* bias, void* workspace,
+                     int64_t workspace_bytes);
+/* The synthesis half alone: ri [B][2 spec][T_max] dense on the device (rows 0 .. spec - 1 real, then imaginary; columns at
+ * or behind T(n_b) are not used) -> out[b][0 .. n_b).  The model.istft convolution, then the overlap-add kernel. */
+int vsp_istft(vsp_ctx* ctx, void* stream, int B, int L_max, const float* ri, const int64_t* n_samples_host, float* out,
+              int64_t out_stride, void* workspace, int64_t workspace_bytes);
+/* bias: [B][spec] float32 on the device, row b's own.  Five launches: framing, the forward convolution, the subtraction in
+ * place, the inverse convolution, overlap-add. */
+int vsp_denoise(vsp_ctx* ctx, void* stream, int B, int L_max, const float* audio, int64_t audio_stride,
+                const int64_t* n_samples_host, const float* bias, const float* strength_host, float* out, int64_t out_stride,
+                void* workspace, int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""The denoiser and the inverse STFT, measured on the GPU (default configuration, synthetic weights):
+``Engine.denoise`` on 16 rows of 10 s at the model's rate beside the ``Engine.generator_ragged`` call that produces such
+rows, ``Engine.istft`` (the inverse convolution and the overlap-add kernel) and ``Engine.spectrogram_ragged`` (framing, the
+forward convolution on the form launch_conv picks, magnitude) on the same rows, in one session.
+
+Device-event times per call (``torch.cuda.Event``) over a window of ``steps`` calls after a warm-up of the same shape; best /
+median / spread of ``rounds`` rounds that alternate over the calls.  The two convolutions of a ``denoise`` call are then
+read from the library's own per-launch events (``Engine.profile``, class FRAME: one event pair a launch), and so is the
+one of an ``istft`` call; the three small kernels are what is left of the call, and the overlap-add kernel what is left of
+``istft``.  Per kernel: run the tool under ``rocprofv3 --kernel-trace --stats --output-format csv`` (the table under the
+tool's own lines in profiles/r25_denoiser.txt).  No gate is set on any of them.
+
+usage: tools/denoiser_measure.py [steps] [rounds] [out.txt]      (default out: profiles/r25_denoiser.txt)"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from vispeech_amd import _lib                           # noqa: E402
+from vispeech_amd import config as vcfg                 # noqa: E402
+from vispeech_amd.models import SynthesizerTrn          # noqa: E402
+from vispeech_amd.schema import dims_from_ctor          # noqa: E402
+from vispeech_amd.synth import synth_state_dict         # noqa: E402
+
+STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r25_denoiser.txt")
+SECONDS, B = 10, 16
+
+
+def timed(fn, steps):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def fmt(v):
+    return f"best {min(v):8.3f} ms  median {float(np.median(v)):8.3f} ms  spread {max(v) - min(v):6.3f} ms"
+
+
+def convs(eng, fn, calls=5):
+    """(launches per call, ms per call) of the frame-rate convolutions of ``fn``, from the library's per-launch events."""
+    fn()
+    torch.cuda.synchronize()
+    eng.profile(True)
+    eng.profile_read(True, _lib.PROF_FRAME)
+    for _ in range(calls):
+        fn()
+    torch.cuda.synchronize()
+    n, ms = eng.profile_read(True, _lib.PROF_FRAME)[:2]
+    eng.profile(False)
+    return n / calls, ms / calls
+
+
+def main():
+    a, kw0 = vcfg.synthesizer_args(vcfg.default_hparams())
+    dims = dims_from_ctor(*a, **kw0)
+    net = SynthesizerTrn(*a, device="cuda:0", **kw0).eval()
+    net.load_state_dict(synth_state_dict(dims, seed=1234))
+    eng, fs, up = net._engine, dims.sampling_rate, dims.total_upsample
+    spec, N = dims.spec_channels, 2 * (dims.spec_channels - 1)
+    frames = SECONDS * fs // up
+    n = frames * up
+    r = np.random.default_rng(25)
+    sid = [b % dims.n_speakers for b in range(B)]
+    G = torch.from_numpy(net._state["emb_g.weight"][sid]).to("cuda:0")
+    Z = torch.from_numpy(0.5 * r.standard_normal((B, dims.inter_channels, frames)).astype(np.float32)).to("cuda:0")
+    lengths = [frames] * B
+    audio = eng.generator_ragged(Z, G, lengths)[:, 0, :].contiguous()          # the rows measured: the generator's own
+    n_samples = [n] * B
+    bias = net.denoiser_bias(sid)
+    T = eng.convert_frames(n, up)
+    out = torch.empty_like(audio)
+    ri = torch.zeros((B, 2 * spec, T), dtype=torch.float32, device="cuda:0")
+    jobs = {
+        "denoise (strength 0.01)": lambda: eng.denoise(audio, n_samples, bias, 0.01, out=out),
+        "istft": lambda: eng.istft(ri, n_samples),
+        "spectrogram_ragged": lambda: eng.spectrogram_ragged(audio, n_samples),
+        "generator_ragged": lambda: eng.generator_ragged(Z, G, lengths),
+    }
+    ms = {k: [] for k in jobs}
+    for _ in range(ROUNDS):
+        for k, fn in jobs.items():
+            ms[k].append(timed(fn, max(STEPS // 2, 2) if k == "generator_ragged" else STEPS))
+    med = lambda k: float(np.median(ms[k]))
+    n_all, c_all = convs(eng, jobs["denoise (strength 0.01)"])
+    n_inv, c_inv = convs(eng, jobs["istft"])
+    flop = 2.0 * (2 * spec) * N * T * B                                        # one DFT product
+    props = torch.cuda.get_device_properties(0)
+    den, ist = med("denoise (strength 0.01)"), med("istft")
+    lines = [f"denoiser: {B} rows of {SECONDS} s at {fs} Hz ({n} samples, {T} frames); {ROUNDS} rounds, a window of {STEPS} calls "
+             f"({max(STEPS // 2, 2)} for generator_ragged)",
+             f"device {torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', 'arch not available')}, "
+             f"{props.multi_processor_count} CUs)",
+             "timer: device events around a window of calls, per call (the Engine calls include their host work and uploads)", ""]
+    for k in jobs:
+        lines.append(f"   {k:30s} {fmt(ms[k])}")
+    lines += ["",
+              f"   denoise / generator_ragged = {den / med('generator_ragged') * 100:.2f} %",
+              f"   the two DFT products: {2 * flop / 1e9:.1f} GFLOP a call ({flop / 1e9:.1f} each: {2 * spec} x {N} x {T} frames x {B} rows)",
+              "   per launch, from the library's own events (profiling on):",
+              f"      both convolutions of a denoise call ({n_all:.0f} launches)      {c_all:8.3f} ms  ({2 * flop / c_all / 1e9:.1f} TFLOP/s)",
+              f"      framing, subtraction and overlap-add (what is left)  {den - c_all:8.3f} ms",
+              f"      the convolution of an istft call ({n_inv:.0f} launch)           {c_inv:8.3f} ms  ({flop / c_inv / 1e9:.1f} TFLOP/s; its operand is the "
+              f"caller's dense RI, rows of {T} floats: not 16-byte aligned unless T_max is a multiple of 4)",
+              f"      overlap-add (istft less its convolution)             {ist - c_inv:8.3f} ms"]
+    assert eng.status() == 0
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -359,6 +359,10 @@ SIGNATURES = {
     "vsp_limiter_workspace_bytes": (_I64, [_I, _I64, _I, _I]),
     "vsp_true_peak": (_I, [_P, _P, _I, _I64, _P, _I64, C.POINTER(_I64), _P, _P, _I64]),
     "vsp_limiter_rows": (_I, [_P, _P, _I, _I, _I, C.POINTER(VspLimiterRow), _P, _P, _P, _I64]),
+    "vsp_denoise_workspace_bytes": (_I64, [_P, _I, _I]),
+    "vsp_denoise_bias": (_I, [_P, _P, _I, _P, _P, _P, _I64]),
+    "vsp_istft": (_I, [_P, _P, _I, _I, _P, C.POINTER(_I64), _P, _I64, _P, _I64]),
+    "vsp_denoise": (_I, [_P, _P, _I, _I, _P, _I64, C.POINTER(_I64), _P, C.POINTER(C.c_float), _P, _I64, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

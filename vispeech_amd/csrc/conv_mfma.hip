@@ -1759,6 +1759,8 @@ ConvForm conv_form(const ConvArgs& a, int B) {
 #else
   constexpr bool ring = true;
 #endif
+  // (ConvArgs::fixed_form: no grid-size threshold is consulted, so a column's sum never changes its order with B or Nq)
+  if (a.fixed_form) return a.ups_s > 0 ? form_of(VSP_CONV_FORM_NONE) : form_tile(2, 1, 1, 4, a.f16s != 0, ring && a.f16s);
   if (ring && a.f16s) {
     if (a.ups_s > 0) return form_of(VSP_CONV_FORM_NONE);
     // small grids: a 1x1 convolution whose weights have the column-tile image runs every row of a 64-column tile in one

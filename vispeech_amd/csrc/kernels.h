@@ -63,6 +63,9 @@ struct ConvArgs {
   // (conv_cols.hip) of small-grid 1x1 convolutions; NULL = this convolution has no such image
   const uint16_t* wg;
   long wg_min_blocks, wg_max_blocks;   // launch_conv takes the column-tile kernel for this range of 64-column tiles (B * ceil(Nq / 64))
+  // round 25: ONE form whatever B and Nq (the throughput kernel's 64-row x 32-column wave tiles, chunks in ascending order),
+  // for callers that promise a column's bits independent of the batch it is computed in (denoiser.hip); 0: the tree above
+  int fixed_form;
 };
 
 // The kernel launch_conv takes for (a, B): which of the frame-rate kernels, and for the throughput kernel its tile tuple
@@ -558,6 +561,24 @@ hipError_t launch_stft_frames_ragged(const float* audio, long a_bs, const int64_
 hipError_t launch_stft_magnitude_ragged(const float* ri, long r_bs, long r_cs, const int64_t* n_samples, float* spec,
                                         int64_t* frames, int B, int L_max, int n_fft, int hop, int spec_ch, int T_max,
                                         hipStream_t s);
+
+// Denoiser and inverse STFT (denoiser.hip; include/vispeech_hip.h, vsp_denoise): the rows, their lengths and frame counts
+// are those of the ragged spectrogram above; a row with n_samples[b] <= 0 is neither read nor written.
+// ri [B][2 spec_ch][T_max] in place: X' = q X, q = max(m - strength[b] * bias[b][r], 0) / m (0 where m = 0), for t < T_b
+hipError_t launch_denoise_subtract(float* ri, long r_bs, long r_cs, const int64_t* n_samples, const float* bias,
+                                   const float* strength, int B, int L_max, int n_fft, int hop, int spec_ch, int T_max,
+                                   hipStream_t s);
+// frames of an overlap-add tile whose tile * hop outputs fit the LDS budget (0: one hop alone does not fit)
+int istft_ola_tile(int n_fft, int hop);
+// v [B][n_fft][T_max]: the windowed synthesis frames.  out[b][i] = (sum_t v[b][pad + i - t hop][t]) / (sum_t w2[pad + i - t hop])
+// over the row's own frames t < T_b that cover the sample, both sums from 0 in ascending t; w2 [n_fft] = fl32(hann^2).
+// hop divides n_fft, n_fft - hop is even.  Writes out[b][0 .. n_b) and nothing else.
+hipError_t launch_istft_ola(const float* v, long v_bs, long v_cs, const int64_t* n_samples, const float* w2, float* out,
+                            long o_bs, int B, int L_max, int n_fft, int hop, int T_max, hipStream_t s);
+// f [n_fft][S] (row stride f_cs): f[n][s] = period[s][n mod hop]
+hipError_t launch_denoise_bias_frames(const float* period, float* f, long f_cs, int S, int n_fft, int hop, hipStream_t s);
+// bias [S][spec_ch] = sqrt(re^2 + im^2) of ri [2 spec_ch][S] (row stride r_cs)
+hipError_t launch_denoise_bias_magnitude(const float* ri, long r_cs, float* bias, int S, int spec_ch, hipStream_t s);
 
 // Live conversion windows (convert_window.hip; include/vispeech_hip.h, vsp_convert_stream_rows): row b is the window of
 // frames [w0, w0 + Tw) of a recording that may still be arriving.  Descriptors by value, as for the streamed vocoder.

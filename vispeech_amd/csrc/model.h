@@ -88,6 +88,11 @@ struct Model {
   size_t post_w = 0;    // conv_post weight [C][K] (reference layout)
   size_t post_wt = 0;   // the same, tap-major [K][C] for the channels-last kernel
   int post_k = 7, post_c = 32;
+  // round 25, planned BEHIND every tensor above when cfg.spec_channels > 1 (istft.M == 0: none): the synthesis basis of the
+  // inverse STFT, n_fft rows by 2 spec inputs with the window and w_r / n_fft folded in, and fl32(hann^2) [n_fft] for the
+  // overlap-add kernel's normalisation
+  Conv istft;
+  size_t istft_w2 = 0;
   size_t total_floats = 0;
   bool has_cl = false;  // split-f16 channels-last generator weights present
 };

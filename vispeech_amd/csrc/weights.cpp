@@ -381,6 +381,14 @@ int plan_model(vsp_ctx* ctx) {
   m.post_k = 7;
   m.post_w = p.raw((size_t)ch * 7);
   m.post_wt = p.raw((size_t)ch * 7);
+  // inverse STFT (round 25), behind everything above so that no earlier offset moves; packed like the forward basis
+  if (c.spec_channels > 1) {
+    const int n_fft = 2 * (c.spec_channels - 1);
+    p.f16s = ctx->frame_f16s;
+    m.istft = p.conv(n_fft, 2 * c.spec_channels, 1, 1, 0, false);
+    p.f16s = false;
+    m.istft_w2 = p.raw((size_t)n_fft);
+  }
   m.total_floats = p.cur;
   return VSP_OK;
 }
@@ -634,6 +642,17 @@ int fill_model(vsp_ctx* ctx, std::vector<float>& arena) {
       const int k = (int)(((long long)r * n) % N);        // exact angle reduction
       return (float)((row < spec ? cs[k] : -sn[k]) * hann[n]);
     }, [](int) { return 0.f; });
+    // ... and the synthesis basis of the inverse STFT: row n, input r < spec (real part) is hann[n] (w_r / N) cos(2 pi r n / N),
+    // input spec + r (imaginary part) is -hann[n] (w_r / N) sin(...), w_0 = w_{N/2} = 1 and every other w_r = 2
+    if (m.istft.M > 0) {
+      f.conv(m.istft, [&](int n, int col, int) {
+        const int r = col < spec ? col : col - spec;
+        const int k = (int)(((long long)r * n) % N);        // exact angle reduction
+        const double w = (r == 0 || r == N / 2 ? 1.0 : 2.0) / N;
+        return (float)((col < spec ? cs[k] : -sn[k]) * w * hann[n]);
+      }, [](int) { return 0.f; });
+      for (int n = 0; n < N && f.ok; ++n) arena[m.istft_w2 + n] = (float)(hann[n] * hann[n]);
+    }
   }
   // posterior encoder (optional): packed only when every enc_q tensor was supplied
   m.has_vc = false;

@@ -2149,6 +2149,91 @@ class Engine:
         o, mg = self.limit(audio, n_samples, ceilings, gains=gains, attack=attack, hold=hold, out=out)
         return o, gains, lufs, peak, blocks, mg
 
+    # ------------------------------------------------------------------ denoiser and inverse STFT (section 4t)
+    def _denoise_ws(self, B: int, L_max: int, what: str) -> torch.Tensor:
+        if int(self.dims.hop_length) != int(self.dims.total_upsample):
+            raise ValueError(f"{what}: hop_length {self.dims.hop_length} is not the generator's total upsampling "
+                             f"{self.dims.total_upsample}: the bias would not be periodic in a frame")
+        need =int(self.lib.vsp_denoise_workspace_bytes(self.ctx, int(B), int(L_max)))
+        if need < 0:
+            raise ValueError(f"{what}: the context has no denoiser geometry (spec_channels > 1, hop = the generator's total "
+                             f"upsampling dividing n_fft at least four times), or B = {B} / L_max = {L_max} is out of range")
+        return self._workspace("denoise", need)
+
+    def denoise_bias(self, g) -> torch.Tensor:
+        """The denoiser's bias of conditioning vectors ``g`` [S, gin] (any: no row of ``emb_g`` is needed), [S, spec_channels]
+        float32 on the device: the generator on ``back + 1 + fwd`` all-zero latent frames, its output frame ``back`` -- the
+        steady period, without the start-up transient --, then ``vsp_denoise_bias``: the magnitude of the windowed DFT of
+        that period tiled to ``n_fft`` samples."""
+        g = _dev_f32(g, self.device)
+        g = g.reshape(-1, g.shape[-1]) if g.dim() != 2 else g
+        S = g.shape[0]
+        back, fwd = self.generator_frame_dependence()
+        up = self.dims.total_upsample
+        z = torch.zeros((S, self.dims.inter_channels, back + 1 + fwd), dtype=torch.float32, device=self.device)
+        o = self.generator(z, g)
+        period = o[:, 0, back * up:(back + 1) * up].contiguous()
+        return self.denoise_bias_of(period)
+
+    def denoise_bias_of(self, period) -> torch.Tensor:
+        """``vsp_denoise_bias``: ``period`` [S, hop] float32 -> [S, spec_channels] on the device."""
+        p = _dev_f32(period, self.device)
+        if p.dim() != 2 or p.shape[1] != self.dims.total_upsample or p.shape[0] < 1:
+            raise ValueError(f"period must be [S, {self.dims.total_upsample}]")
+        S = p.shape[0]
+        bias = self._f(S, self.dims.spec_channels)
+        ws = self._denoise_ws(S, 2 * (self.dims.spec_channels - 1), "denoise_bias")
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_denoise_bias(self.ctx, self._stream(), S, _ptr(p), _ptr(bias), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_denoise_bias")
+        return bias
+
+    def istft(self, ri, n_samples) -> torch.Tensor:
+        """``vsp_istft``: ``ri`` [B, 2 spec_channels, T_max] (real rows, then imaginary; T_max the frames of the longest row)
+        to audio [B, max(n_samples)] by weighted overlap-add; row b's first ``n_samples[b]`` samples are written, the rest
+        is 0."""
+        x = _dev_f32(ri, self.device)
+        n_host = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        B, L_max = len(n_host), max(n_host)
+        ws = self._denoise_ws(B, L_max, "istft")
+        T = self.convert_frames(L_max, self.dims.total_upsample)
+        if x.dim() != 3 or tuple(x.shape) != (B, 2 * self.dims.spec_channels, T):
+            raise ValueError(f"ri must be [{B}, {2 * self.dims.spec_channels}, {T}]")
+        out = torch.zeros((B, L_max), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_istft(self.ctx, self._stream(), B, L_max, _ptr(x), (C.c_int64 * B)(*n_host), _ptr(out), L_max,
+                                    _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_istft")
+        return out
+
+    def denoise(self, audio, n_samples, bias, strength, out=None) -> torch.Tensor:
+        """``vsp_denoise``: subtract ``strength[b] * bias[b]`` from the magnitude of every STFT frame of ``audio[b,
+        :n_samples[b]]`` and return to audio.  ``bias`` [B, spec_channels] (row b's own); ``strength`` a scalar or one per
+        row, None / NaN: the row is neither read nor written.  ``out`` None: in place where ``audio`` is a float32 device
+        tensor.  Nothing at or behind ``n_samples[b]`` is touched.  Returns ``out``."""
+        a, B, stride, n_host, _ = self._loudness_rows(audio, n_samples, None)
+        o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
+        if out is not None and o is not out:
+            raise ValueError("out must be a float32 tensor on the engine's device")
+        if strength is None or np.ndim(strength) == 0:
+            s = [float("nan") if strength is None else float(strength)] * B
+        else:
+            s = [float("nan") if v is None else float(v) for v in (strength.tolist() if hasattr(strength, "tolist") else strength)]
+            if len(s) != B:
+                raise ValueError(f"denoise: strength must be a scalar or have {B} entries")
+        bp = None
+        if bias is not None:
+            bp = _dev_f32(bias, self.device)
+            if tuple(bp.shape) != (B, self.dims.spec_channels):
+                raise ValueError(f"bias must be [{B}, {self.dims.spec_channels}]")
+        L_max = max(n_host)
+        ws = self._denoise_ws(B, L_max, "denoise")
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_denoise(self.ctx, self._stream(), B, L_max, _ptr(a), stride, (C.c_int64 * B)(*n_host), _ptr(bp),
+                                      (C.c_float * B)(*s), _ptr(o), o_stride, _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_denoise")
+        return o
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

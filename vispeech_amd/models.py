@@ -131,6 +131,7 @@ class SynthesizerTrn:
             raise RuntimeError(f"load_state_dict: {len(missing)} missing keys, e.g. {missing[:3]}")
         _, unexpected = self._engine.set_weights(state_dict, strict=strict)
         self._state = host
+        self.__dict__.pop("_denoiser_bias", None)      # (the denoiser's bias is a function of the weights)
         self._engine.finalize()
         return missing, unexpected
 
@@ -353,6 +354,32 @@ class SynthesizerTrn:
         params = eng.loudness_level_params(len(n_samples), target_lufs, max_gain_db, max_cut_db, slew_db_per_s, initial_gain_db)
         r = eng.loudness_level(audio, n_samples, fs, params, out=out)
         return r["out"], r["c_db"]
+
+    @torch.no_grad()
+    def denoiser_bias(self, sid):
+        """The denoiser's bias of speakers ``sid``, ``[len(sid), spec_channels]`` float32 on the device:
+        the magnitude spectrum of the steady period the generator lays under its output for ``g = emb_g[sid]``.  Built on
+        first use per speaker (one generator call on zeros for the speakers not seen yet), kept until ``load_state_dict``."""
+        ids = [int(s) for s in (sid.tolist() if hasattr(sid, "tolist") else sid)]
+        table = self.__dict__.setdefault("_denoiser_bias", {})
+        new = sorted(set(ids) - set(table))
+        if new:
+            if "emb_g.weight" not in self._state:
+                raise RuntimeError("denoiser_bias: no weights loaded")
+            rows = self._engine.denoise_bias(self._state["emb_g.weight"][new])
+            for i, s in enumerate(new):
+                table[s] = rows[i]
+        return torch.stack([table[s] for s in ids])
+
+    @torch.no_grad()
+    def denoise(self, audio, n_samples, sid, strength=0.01, out=None):
+        """Subtract ``strength`` times the speaker's own bias (``denoiser_bias``) from the magnitude of every STFT frame of
+        ``audio[b, :n_samples[b]]`` and return to audio: the post-filter of the denoisers shipped
+        with WaveGlow and HiFi-GAN, with the steady state as the bias.  ``sid`` per row; ``strength`` a scalar or one per
+        row, None / NaN leaves the row alone.  In place where ``audio`` is a float32 tensor on the model's device and ``out``
+        is None.  Returns the audio."""
+        ids = [int(s) for s in (sid.tolist() if hasattr(sid, "tolist") else sid)]
+        return self._engine.denoise(audio, n_samples, self.denoiser_bias(ids), strength, out=out)
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)

@@ -3,6 +3,7 @@ to their latents, and ``BatchingSynthesisService``."""
 from __future__ import annotations
 
 import concurrent.futures
+import math
 import queue
 import threading
 import time
@@ -57,6 +58,18 @@ def _loudness_spec(loudness):
     if not m >= 0.0:
         raise ValueError("loudness: max_gain_db must be at least 0")
     return (t, c, m)
+
+
+def _denoise_spec(value):
+    """The strength of a request or service that names a denoiser (``SynthesizerTrn.denoise``): a
+    finite number >= 0, ``True`` for 0.01; None / False: none."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return 0.01
+    if isinstance(value, (int, float, np.integer, np.floating)) and math.isfinite(float(value)) and float(value) >= 0.0:
+        return float(value)
+    raise ValueError("denoise: a strength (a finite number, at least 0), or True for 0.01")
 
 
 def _limiter_spec(value, loudness, fs: int):
@@ -159,8 +172,11 @@ class _Request:
     keys its noise, ``scales`` are its own (duration, pitch, energy, noise) scales -- None: 1.0 and the service's
     ``noise_scale``; a conversion's noise scale is its row's."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None, loudness=None, limiter=None):
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, prosody=None, loudness=None, limiter=None,
+                 denoise=None):
         self.row, self.seed, self.scales = row, int(seed), scales
+        self.denoise = denoise        # ``_denoise_spec``: the strength of the denoiser on the request's waveform, or None
+        self.sid = None               # a text request's speaker number, once its batch is collated (the denoiser's bias)
         self.limiter = limiter        # ``_limiter_spec``: (attack, hold, ceiling, gain) of the limiter behind the request's gain, or None
         self.loudness = loudness      # ``_loudness_spec``: the level the request's waveform is brought to, or None
         self.out_fmt = out_fmt        # ``_output_format``: the request's own output rate and encoding, or None
@@ -302,6 +318,8 @@ def _text_latents(eng, collate, reqs, noise_scale: float, model_rate=None, proso
     prosody = any(getattr(r, "prosody", None) is not None for r in reqs)
     batch, ctl, kw = _collated(collate, reqs, noise_scale, *((eng, model_rate, prosody_path, prosody_align) if prosody else ()))
     t = _as_tensor
+    for b, r in enumerate(reqs):
+        r.sid = int(batch["sid"][b])
     enc = eng.encode(t(batch["phonemes"]), t(batch["lengths"]), t(batch["sid"]), t(ctl[0]), t(ctl[1]), t(ctl[2]),
                      isolated=True, **kw)
     frames, tf = eng.frame_lengths_host(enc["frame_lengths"])
@@ -407,11 +425,17 @@ class BatchingSynthesisService:
     request with a loudness and a limiter gets the gain of its target NOT cut by its peak and the limiter at its
     ``peak_ceiling`` (``normalize_loudness(limiter=)``); one with a limiter only gets ``gain_db`` (0) and the limiter at
     ``ceiling`` (1).  ONE limiter call per batch, before the output stage; a batch in which nobody names a limiter makes
-    exactly the calls it made before."""
+    exactly the calls it made before.
+    ``denoise``: the denoiser on every request's waveform unless it names its own
+    (``submit(denoise=)``; False there: none) -- a strength, or True for 0.01; None: none.  A batch in which a request has
+    one makes ONE ``net.denoise`` call on the generator's output, in place, with the speaker's own bias (a conversion's:
+    ``sid_tgt``), BEFORE the loudness call, the limiter and the encoding: what is measured and limited is what is delivered.
+    The other rows carry a NaN strength and are neither read nor written, and so does a row too short for the reflection
+    at its ends (at most (n_fft - hop) / 2 samples); a batch in which nobody has one makes exactly the calls it made before."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
                  spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None,
-                 prosody_align=None, loudness=None, limiter=None):
+                 prosody_align=None, loudness=None, limiter=None, denoise=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -430,6 +454,7 @@ class BatchingSynthesisService:
         self.loudness = _loudness_spec(loudness)
         self.limiter = limiter if limiter is not None and limiter is not False else None
         _limiter_spec(self.limiter, self.loudness, self.sampling_rate)             # (refused here, not in the worker)
+        self.denoise = _denoise_spec(denoise)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -441,7 +466,7 @@ class BatchingSynthesisService:
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
                noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, prosody_audio=None,
                prosody_sample_rate: Optional[int] = None, prosody_encoding=None, prosody_sid=None,
-               loudness=None, limiter=None) -> "concurrent.futures.Future":
+               loudness=None, limiter=None, denoise=None) -> "concurrent.futures.Future":
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it (a ``FilelistRow``).  The four scales are the
         request's own (None: 1.0, and the service's ``noise_scale``); a scale whose control the row carries is not read.
         The future's result is the request's PCM16 samples (numpy int16, valid part only).
@@ -461,7 +486,9 @@ class BatchingSynthesisService:
         ``loudness``: the integrated loudness (BS.1770, LUFS) the request's waveform is brought to before it is encoded -- a
         target, or a mapping of (target_lufs, peak_ceiling, max_gain_db); None: the service's; False: none.
         ``limiter``: the limiter behind the request's gain -- True or a mapping of (attack_ms, hold_ms, ceiling, gain_db);
-        None: the service's; False: none."""
+        None: the service's; False: none.
+        ``denoise``: the strength of the denoiser on the request's waveform, or True for 0.01; None: the service's; False:
+        none."""
         prosody = None
         if prosody_sid is not None:
             n_spk = getattr(self.net, "n_speakers", None)
@@ -484,11 +511,12 @@ class BatchingSynthesisService:
         elif prosody_sid is not None:
             raise ValueError("prosody_sid names the speaker of prosody_audio: pass it")
         return self._enqueue(_Request(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                      _output_format(output_rate, output_encoding), prosody, *self._level_of(loudness, limiter)))
+                                      _output_format(output_rate, output_encoding), prosody, *self._level_of(loudness, limiter),
+                                      denoise=self._denoise_of(denoise)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None, loudness=None, limiter=None) -> "concurrent.futures.Future":
+                          output_encoding=None, loudness=None, limiter=None, denoise=None) -> "concurrent.futures.Future":
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``; the future's result is the
         PCM16 of the recording converted to ``sid_tgt`` (``T(n) * up`` samples at the model's rate, or at ``output_rate``).
         ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference -- NOT the service's text-to-speech
@@ -497,11 +525,29 @@ class BatchingSynthesisService:
         ``bytes`` -- at that rate; the batch's raw recordings go through the input stage on the GPU, one call per distinct
         (rate, encoding), before the one ``convert_latent``.  ``output_rate`` / ``output_encoding`` / ``loudness``: as in
         ``submit`` (the level is that of the converted waveform; the recording is not normalised before conversion);
-        ``limiter``: as in ``submit``."""
+        ``limiter``: as in ``submit``; ``denoise``: as in ``submit``, with the bias of ``sid_tgt``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_Request(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
-                                      out_fmt=_output_format(output_rate, output_encoding),
+                                      out_fmt=_output_format(output_rate, output_encoding), denoise=self._denoise_of(denoise),
                                       **dict(zip(("loudness", "limiter"), self._level_of(loudness, limiter)))))
+
+    def _denoise_of(self, denoise):
+        return self.denoise if denoise is None else _denoise_spec(denoise)
+
+    def _denoise(self, reqs, waves, n, sids) -> None:
+        """The requests that have a denoiser: ONE ``net.denoise`` call over the batch's rows ``waves`` [B, L] (the generator's
+        output, row b's first ``n[b]`` samples), in place, each row with the bias of its speaker ``sids[b]``.  A row that asks
+        for nothing, or is too short for the reflection at its ends, carries a NaN strength and is neither read nor
+        written; a batch in which nobody asks makes no call."""
+        if waves.shape[-1] == 0 or all(r.denoise is None for r in reqs):
+            return
+        d = self.net.dims
+        pad = (2 * (int(d.spec_channels) - 1) - int(d.total_upsample)) // 2
+        nan = float("nan")
+        strength = [nan if r.denoise is None or int(n[b]) <= pad else r.denoise for b, r in enumerate(reqs)]
+        if all(s != s for s in strength):
+            return
+        self.net.denoise(waves, [max(int(v), 1) for v in n], [int(s) for s in sids], strength)
 
     def _loudness_of(self, loudness):
         return self.loudness if loudness is None else _loudness_spec(loudness)
@@ -586,6 +632,7 @@ class BatchingSynthesisService:
                                   duration_control=t(ctl[0]), pitch_control=t(ctl[1]),
                                   energy_control=t(ctl[2]), noise_seed=[r.seed for r in reqs], isolated=True, **kw)
         frames = x_mask.sum(dim=(1, 2)).cpu().tolist()
+        self._denoise(reqs, o[:, 0, :], [int(frames[b]) * hop for b in range(len(reqs))], np.asarray(batch["sid"]).reshape(-1))
         self._normalize(reqs, o[:, 0, :], [int(frames[b]) * hop for b in range(len(reqs))])
         if any(r.out_fmt is not None for r in reqs):
             return self._deliver_rows(reqs, [o[b, 0, : int(frames[b]) * hop] for b in range(len(reqs))])
@@ -628,6 +675,8 @@ class BatchingSynthesisService:
         G = torch.stack([torch.as_tensor(lat[i][1]).reshape(-1) for i in live])
         o = eng.generator_ragged(Z, G, [lat[i][2] for i in live])
         hop = net.dims.total_upsample
+        self._denoise([reqs[i] for i in live], o[:, 0, :], [lat[i][2] * hop for i in live],
+                      [reqs[i].row.sid_tgt if reqs[i].is_conversion else reqs[i].sid for i in live])
         self._normalize([reqs[i] for i in live], o[:, 0, :], [lat[i][2] * hop for i in live])
         if any(r.out_fmt is not None for r in reqs):
             waves = [None] * len(reqs)
