@@ -29,6 +29,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "op_host.h"
 
 namespace {
 
@@ -292,34 +293,27 @@ __global__ void __launch_bounds__(256) align_durations_kernel(const DurArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+using vsp::Call;
+using vsp::Ws;
 
 int path_threads(int K_max) { return std::max(64, ((K_max + AL_SPT - 1) / AL_SPT + 63) / 64 * 64); }
 
-struct RowsWs { size_t rows, end; };                       // frames [B], states [B] (int32)
-RowsWs rows_ws(int B) { return {0, align256((size_t)2 * B * sizeof(int32_t))}; }
+// What each call carves from its workspace (op_host.h); the sizes are the dry passes of these.
+int32_t* carve_rows(Ws& ws, int B) { return static_cast<int32_t*>(ws.bytes((size_t)2 * B * sizeof(int32_t))); }   // frames [B], states [B]
 
-struct PathWs { size_t rows, bp, end; };
-PathWs path_ws(int B, int F_max, int K_max) {
-  PathWs w;
-  w.rows = 0;
-  w.bp = rows_ws(B).end;
-  w.end = w.bp + align256((size_t)B * F_max * path_threads(std::min(K_max, AL_MAX_STATES)));
-  return w;
+struct PathWs { int32_t* rows; uint8_t* bp; };
+PathWs carve_path(Ws& ws, int B, int F_max, int K_max) {   // (a braced list is evaluated in order)
+  return {carve_rows(ws, B), static_cast<uint8_t*>(ws.bytes((size_t)B * F_max * path_threads(std::min(K_max, AL_MAX_STATES))))};
 }
 
-struct DurWs { size_t ints, end; };                        // frames [B], lengths [B], cum [B][Tp]
-DurWs dur_ws(int B, int Tp) { return {0, align256(((size_t)2 * B + (size_t)B * Tp) * sizeof(int32_t))}; }
+int32_t* carve_dur(Ws& ws, int B, int Tp) {                // frames [B], lengths [B], cum [B][Tp]
+  return static_cast<int32_t*>(ws.bytes(((size_t)2 * B + (size_t)B * Tp) * sizeof(int32_t)));
+}
 
 // vsp_align: [the path's (its rows serve the scores too)] [S] [the durations']
-struct AlignWs { size_t path, S, dur, end; };
-AlignWs align_ws(int B, int F_max, int K_max, int Tp) {
-  AlignWs w;
-  w.path = 0;
-  w.S = path_ws(B, F_max, K_max).end;
-  w.dur = w.S + align256((size_t)B * F_max * K_max * sizeof(float));
-  w.end = w.dur + dur_ws(B, Tp).end;
-  return w;
+struct AlignWs { PathWs path; float* S; int32_t* dur; };
+AlignWs carve_align(Ws& ws, int B, int F_max, int K_max, int Tp) {
+  return {carve_path(ws, B, F_max, K_max), ws.f((size_t)B * F_max * K_max), carve_dur(ws, B, Tp)};
 }
 
 bool sizes_ok(int B, int F_max, int K_max) {
@@ -375,63 +369,44 @@ int check_cum(vsp_ctx* ctx, const char* who, int B, int Tp, const int32_t* cum_h
   return VSP_OK;
 }
 
-int upload(vsp_ctx* ctx, const char* who, hipStream_t s, void* dst, const void* src, size_t bytes) {
-  // (pageable host memory: the runtime stages it before hipMemcpyAsync returns, as prosody.hip's uploads rest on)
-  const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-  return VSP_OK;
-}
-
-int launch_scores(vsp_ctx* ctx, hipStream_t s, int B, int C, int F_max, int K_max, const float* x, const float* m, const float* logs,
+int launch_scores(const Call& call, int B, int C, int F_max, int K_max, const float* x, const float* m, const float* logs,
                   const int32_t* rows_dev, float* S) {
   ScoreArgs a;
   a.x = x; a.m = m; a.logs = logs; a.frames = rows_dev; a.states = rows_dev + B; a.S = S;
   a.C = C; a.F_max = F_max; a.K_max = K_max;
   const dim3 grid((K_max + AL_TK - 1) / AL_TK, (F_max + AL_TJ - 1) / AL_TJ, B);
-  hipLaunchKernelGGL(align_scores_kernel, grid, dim3(256), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "align_scores_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(align_scores_kernel, grid, dim3(256), 0, call.s, a);
+  return call.launched("align_scores_kernel");
 }
 
-int launch_path(vsp_ctx* ctx, hipStream_t s, int B, int F_max, int K_max, int K_top, const float* S, const int32_t* rows_dev,
+int launch_path(const Call& call, int B, int F_max, int K_max, int K_top, const float* S, const int32_t* rows_dev,
                 const vsp_align_params& pp, int32_t* states, uint8_t* bp) {
   PathArgs a;
   a.S = S; a.frames = rows_dev; a.states = rows_dev + B; a.bp = bp; a.path = states;
   a.F_max = F_max; a.K_max = K_max; a.RB = path_threads(K_top);
   a.A = pp.max_advance; a.stay_cost = pp.stay_cost; a.skip_cost = pp.skip_cost;
   const size_t lds = (size_t)2 * a.RB * sizeof(double2) + std::max((size_t)AL_CH * a.RB, (size_t)AL_CH * AL_BAND + sizeof(int32_t));
-  hipLaunchKernelGGL(align_path_kernel, dim3(B), dim3(a.RB), lds, s, a);      // (at most 64 KiB: no attribute to raise)
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "align_path_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(align_path_kernel, dim3(B), dim3(a.RB), lds, call.s, a);      // (at most 64 KiB: no attribute to raise)
+  return call.launched("align_path_kernel");
 }
 
-int launch_durations(vsp_ctx* ctx, const char* who, hipStream_t s, int B, int F_max, int Tp, const int32_t* states,
-                     const int64_t* frames_host, const int32_t* cum_host, const int64_t* lengths_host, int32_t* durations, char* ws) {
+int launch_durations(const Call& call, int B, int F_max, int Tp, const int32_t* states, const int64_t* frames_host,
+                     const int32_t* cum_host, const int64_t* lengths_host, int32_t* durations, int32_t* dev) {
   std::vector<int32_t> ints((size_t)2 * B + (size_t)B * Tp, 0);
   for (int b = 0; b < B; ++b) {
     ints[b] = (int32_t)frames_host[b];
     ints[(size_t)B + b] = (int32_t)lengths_host[b];
     std::memcpy(&ints[(size_t)2 * B + (size_t)b * Tp], cum_host + (size_t)b * Tp, (size_t)lengths_host[b] * sizeof(int32_t));
   }
-  if (const int rc = upload(ctx, who, s, ws, ints.data(), ints.size() * sizeof(int32_t))) return rc;
+  if (const int rc = call.upload(dev, ints.data(), ints.size() * sizeof(int32_t))) return rc;
   DurArgs a;
   a.path = states;
-  a.frames = reinterpret_cast<const int32_t*>(ws);
+  a.frames = dev;
   a.lengths = a.frames + B;
   a.cum = a.lengths + B;
   a.dur = durations; a.F_max = F_max; a.Tp = Tp;
-  hipLaunchKernelGGL(align_durations_kernel, dim3((Tp + 255) / 256, B), dim3(256), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "align_durations_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
-}
-
-int need_ws(vsp_ctx* ctx, const char* who, void* workspace, int64_t workspace_bytes, size_t need) {
-  if (!workspace || workspace_bytes < (int64_t)need)
-    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
-  return VSP_OK;
+  hipLaunchKernelGGL(align_durations_kernel, dim3((Tp + 255) / 256, B), dim3(256), 0, call.s, a);
+  return call.launched("align_durations_kernel");
 }
 
 }  // namespace
@@ -440,17 +415,23 @@ int vsp_align_max_states(void) { return AL_MAX_STATES; }
 
 int64_t vsp_align_scores_workspace_bytes(int B, int F_max, int K_max) {
   if (!sizes_ok(B, F_max, K_max)) return VSP_ERR_ARG;
-  return (int64_t)rows_ws(B).end;
+  Ws ws = vsp::dry_ws();
+  carve_rows(ws, B);
+  return (int64_t)ws.cur;
 }
 
 int64_t vsp_align_path_workspace_bytes(int B, int F_max, int K_max) {
   if (!sizes_ok(B, F_max, K_max)) return VSP_ERR_ARG;
-  return (int64_t)path_ws(B, F_max, K_max).end;
+  Ws ws = vsp::dry_ws();
+  carve_path(ws, B, F_max, K_max);
+  return (int64_t)ws.cur;
 }
 
 int64_t vsp_align_workspace_bytes(int B, int F_max, int K_max, int Tp) {
   if (!sizes_ok(B, F_max, K_max) || Tp < 1 || (int64_t)B * Tp > ((int64_t)1 << 28)) return VSP_ERR_ARG;
-  return (int64_t)align_ws(B, F_max, K_max, Tp).end;
+  Ws ws = vsp::dry_ws();
+  carve_align(ws, B, F_max, K_max, Tp);
+  return (int64_t)ws.cur;
 }
 
 int vsp_align_scores(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, const float* x, const float* m, const float* logs,
@@ -463,10 +444,12 @@ int vsp_align_scores(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_
   std::vector<int32_t> fk;
   if (const int rc = check_rows(ctx, who, B, F_max, K_max, frames_host, states_host, nullptr, fk)) return rc;
   if (!x || !m || !logs || !scores) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_ws(B).end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (const int rc = upload(ctx, who, s, workspace, fk.data(), fk.size() * sizeof(int32_t))) return rc;
-  return launch_scores(ctx, s, B, C, F_max, K_max, x, m, logs, static_cast<const int32_t*>(workspace), scores);
+  const Call call{ctx, who, (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  int32_t* rows = carve_rows(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(rows, fk.data(), fk.size() * sizeof(int32_t))) return rc;
+  return launch_scores(call, B, C, F_max, K_max, x, m, logs, rows, scores);
 }
 
 int vsp_align_path(vsp_ctx* ctx, void* stream, int B, int F_max, int K_max, const float* scores, const int64_t* frames_host,
@@ -481,14 +464,13 @@ int vsp_align_path(vsp_ctx* ctx, void* stream, int B, int F_max, int K_max, cons
   std::vector<int32_t> fk;
   if (const int rc = check_rows(ctx, who, B, F_max, K_max, frames_host, states_host, &pp, fk)) return rc;
   if (!scores || !states) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  const PathWs lay = path_ws(B, F_max, K_max);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  if (const int rc = upload(ctx, who, s, ws + lay.rows, fk.data(), fk.size() * sizeof(int32_t))) return rc;
+  const Call call{ctx, who, (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  const PathWs w = carve_path(ws, B, F_max, K_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(w.rows, fk.data(), fk.size() * sizeof(int32_t))) return rc;
   const int K_top = *std::max_element(fk.begin() + B, fk.end());
-  return launch_path(ctx, s, B, F_max, K_max, K_top, scores, reinterpret_cast<const int32_t*>(ws + lay.rows), pp, states,
-                     reinterpret_cast<uint8_t*>(ws + lay.bp));
+  return launch_path(call, B, F_max, K_max, K_top, scores, w.rows, pp, states, w.bp);
 }
 
 int vsp_align_durations(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const int32_t* states, const int64_t* frames_host,
@@ -504,9 +486,11 @@ int vsp_align_durations(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, co
       return ctx->fail(VSP_ERR_ARG, "%s: row %d has %lld frames: 1 <= frames <= F_max = %d", who, b, (long long)frames_host[b], F_max);
   if (const int rc = check_cum(ctx, who, B, Tp, cum_dur_host, lengths_host, nullptr)) return rc;
   if (!states || !durations) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, dur_ws(B, Tp).end)) return rc;
-  return launch_durations(ctx, who, (hipStream_t)stream, B, F_max, Tp, states, frames_host, cum_dur_host, lengths_host, durations,
-                          static_cast<char*>(workspace));
+  const Call call{ctx, who, (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  int32_t* dev = carve_dur(ws, B, Tp);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  return launch_durations(call, B, F_max, Tp, states, frames_host, cum_dur_host, lengths_host, durations, dev);
 }
 
 int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, int Tp, const float* x, const float* m, const float* logs,
@@ -523,17 +507,13 @@ int vsp_align(vsp_ctx* ctx, void* stream, int B, int C, int F_max, int K_max, in
   if (const int rc = check_rows(ctx, who, B, F_max, K_max, frames_host, states_host, &pp, fk)) return rc;
   if (const int rc = check_cum(ctx, who, B, Tp, cum_dur_host, lengths_host, states_host)) return rc;
   if (!x || !m || !logs || !states || !durations) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  const AlignWs lay = align_ws(B, F_max, K_max, Tp);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  const PathWs pl = path_ws(B, F_max, K_max);
-  if (const int rc = upload(ctx, who, s, ws + lay.path + pl.rows, fk.data(), fk.size() * sizeof(int32_t))) return rc;
-  const int32_t* rows_dev = reinterpret_cast<const int32_t*>(ws + lay.path + pl.rows);
-  float* S = reinterpret_cast<float*>(ws + lay.S);
-  if (const int rc = launch_scores(ctx, s, B, C, F_max, K_max, x, m, logs, rows_dev, S)) return rc;
+  const Call call{ctx, who, (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  const AlignWs w = carve_align(ws, B, F_max, K_max, Tp);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(w.path.rows, fk.data(), fk.size() * sizeof(int32_t))) return rc;
+  if (const int rc = launch_scores(call, B, C, F_max, K_max, x, m, logs, w.path.rows, w.S)) return rc;
   const int K_top = *std::max_element(fk.begin() + B, fk.end());
-  if (const int rc = launch_path(ctx, s, B, F_max, K_max, K_top, S, rows_dev, pp, states, reinterpret_cast<uint8_t*>(ws + lay.path + pl.bp)))
-    return rc;
-  return launch_durations(ctx, who, s, B, F_max, Tp, states, frames_host, cum_dur_host, lengths_host, durations, ws + lay.dur);
+  if (const int rc = launch_path(call, B, F_max, K_max, K_top, w.S, w.path.rows, pp, states, w.path.bp)) return rc;
+  return launch_durations(call, B, F_max, Tp, states, frames_host, cum_dur_host, lengths_host, durations, w.dur);
 }

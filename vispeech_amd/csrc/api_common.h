@@ -1,5 +1,5 @@
-// What the launch sequences of the C-ABI (include/vispeech_hip.h) share: the workspace allocator, the tensor view, the Run
-// that carries one call's stream, error state and profiling, and the declarations of the run_* sequences.  The sequences
+// What the launch sequences of the C-ABI (include/vispeech_hip.h) share: the workspace allocator and the tensor view
+// (op_host.h, which the stand-alone operators use too), the Run that carries one call's stream, error state and profiling, and the declarations of the run_* sequences.  The sequences
 // restate SynthesizerTrn.infer (reference models.py:672-722) as HIP kernel launches on the caller's stream; no allocation
 // and no host synchronisation happens on these paths except vsp_frame_lengths_host.
 //   api_context.hip    context, weights, setters, stand-alone operators, profile readers
@@ -14,41 +14,10 @@
 #include <vector>
 
 #include "model.h"
+#include "op_host.h"
 #include "row_controls.h"
 
 namespace vsp {
-
-struct T3 {
-  float* p = nullptr;
-  long bs = 0, cs = 0;
-  T3 chan(int c) const { return T3{p ? p + (size_t)c * cs : nullptr, bs, cs}; }
-};
-
-// Bump allocator over the caller's workspace; in dry mode it only measures.
-struct Ws {
-  char* base;
-  size_t cap;
-  size_t cur = 0;
-  bool dry;
-  bool overflow = false;
-  Ws(void* b, size_t c, bool d) : base((char*)b), cap(c), dry(d) {}
-  void* bytes(size_t n) {
-    const size_t o = cur;
-    cur += (n + 255) / 256 * 256;
-    if (dry) return nullptr;
-    if (cur > cap) { overflow = true; return nullptr; }
-    return base + o;
-  }
-  float* f(size_t n) { return (float*)bytes(n * sizeof(float)); }
-  T3 t3(int B, int C, int T) {
-    const long ts = (T + 63) / 64 * 64;
-    T3 t;
-    t.p = f((size_t)B * C * ts);
-    t.cs = ts;
-    t.bs = (long)C * ts;
-    return t;
-  }
-};
 
 // Stages that run one after another on one stream share scratch: every stage starts at the scope's mark -- next()
 // between two of them --, and the scope leaves `cur` behind the largest.  The only place that moves `cur` back.

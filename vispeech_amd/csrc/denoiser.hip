@@ -254,10 +254,7 @@ int denoise_call(vsp_ctx* ctx, const char* who, void* stream, int B, int L_max, 
                      (long long)need);
   if (const int rc = check_ready(ctx)) return rc;
   if (!any) return VSP_OK;
-  const hipStream_t s = (hipStream_t)stream;
-  // (pageable host memory: the runtime stages it before hipMemcpyAsync returns, as the loudness and prosody uploads rest on)
-  const hipError_t e = hipMemcpyAsync(workspace, up.data(), up.size(), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s: upload: %s", who, hipGetErrorString(e));
+  if (const int rc = vsp::Call{ctx, who, (hipStream_t)stream}.upload(workspace, up.data(), up.size())) return rc;
   io.rows.n = reinterpret_cast<const int64_t*>(workspace);
   io.rows.strength = reinterpret_cast<const float*>(static_cast<char*>(workspace) + (size_t)B * sizeof(int64_t));
   if (!io.bias) io.bias = io.rows.strength;      // (never read: the subtraction does not run without a bias)

@@ -34,6 +34,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "op_host.h"
 #include "resample_common.h"
 
 namespace {
@@ -204,9 +205,12 @@ __global__ void __launch_bounds__(256) lm_apply_kernel(const Row* __restrict__ r
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-size_t rows_bytes(int B) { return align256((size_t)B * sizeof(Row)); }
-int64_t r_words(int64_t out_count, int A, int H) { return (out_count + 2 * (int64_t)A + H + 63) / 64 * 64; }
+using vsp::Call;
+using vsp::Ws;
+
+// The workspace: [Row [B]], then one r buffer per row that has outputs, in row order.
+Row* carve_rows(Ws& ws, int B) { return static_cast<Row*>(ws.bytes((size_t)B * sizeof(Row))); }
+float* carve_r(Ws& ws, int64_t out_count, int A, int H) { return ws.f((size_t)(out_count + 2 * (int64_t)A + H)); }
 
 bool window_ok(int A, int H) { return A >= 0 && A <= LM_MAX_A && H >= 0 && H <= LM_MAX_H; }
 
@@ -223,19 +227,6 @@ Taps make_taps() {
 const Taps& the_taps() {
   static const Taps t = make_taps();
   return t;
-}
-
-int need_ws(vsp_ctx* ctx, const char* who, void* workspace, int64_t workspace_bytes, size_t need) {
-  if (!workspace || workspace_bytes < (int64_t)need)
-    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
-  return VSP_OK;
-}
-
-int upload_rows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, const std::vector<Row>& up) {
-  // (pageable host memory: the runtime stages it before hipMemcpyAsync returns, as the loudness uploads rest on)
-  const hipError_t e = hipMemcpyAsync(ws, up.data(), up.size() * sizeof(Row), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-  return VSP_OK;
 }
 
 }  // namespace
@@ -255,7 +246,10 @@ int vsp_limiter_history(int A, int H, int64_t* behind, int64_t* ahead) {
 
 int64_t vsp_limiter_workspace_bytes(int B, int64_t L_max, int A, int H) {
   if (B < 1 || B > LM_MAX_B || L_max < 1 || L_max > LM_MAX_SAMPLES || !window_ok(A, H)) return VSP_ERR_ARG;
-  return (int64_t)(rows_bytes(B) + (size_t)B * (size_t)r_words(L_max, A, H) * sizeof(float));
+  Ws ws = vsp::dry_ws();                                 // every row at L_max outputs
+  carve_rows(ws, B);
+  for (int b = 0; b < B; ++b) carve_r(ws, L_max, A, H);
+  return (int64_t)ws.cur;
 }
 
 int vsp_true_peak(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float* audio, int64_t audio_stride,
@@ -278,18 +272,17 @@ int vsp_true_peak(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float*
     n_max = std::max(n_max, n);
   }
   if (!audio || !tp) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_bytes(B))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  if (const int rc = upload_rows(ctx, who, s, ws, up)) return rc;
-  hipError_t e = hipMemsetAsync(tp, 0, (size_t)B * sizeof(float), s);
+  const Call call{ctx, who, s};
+  Ws ws = call.open(workspace, workspace_bytes);
+  Row* rows = carve_rows(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(rows, up.data(), up.size() * sizeof(Row))) return rc;
+  const hipError_t e = hipMemsetAsync(tp, 0, (size_t)B * sizeof(float), s);
   if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (tp): %s", who, hipGetErrorString(e));
-  hipLaunchKernelGGL(lm_peak_kernel<true>, dim3((unsigned)((n_max + LM_T1 - 1) / LM_T1), B), dim3(256), 0, s,
-                     reinterpret_cast<const Row*>(ws), (const float*)nullptr, reinterpret_cast<unsigned*>(tp), (unsigned*)nullptr,
-                     the_taps());
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lm_peak_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(lm_peak_kernel<true>, dim3((unsigned)((n_max + LM_T1 - 1) / LM_T1), B), dim3(256), 0, s, rows,
+                     (const float*)nullptr, reinterpret_cast<unsigned*>(tp), (unsigned*)nullptr, the_taps());
+  return call.launched("lm_peak_kernel");
 }
 
 int vsp_limiter_rows(vsp_ctx* ctx, void* stream, int B, int A, int H, const vsp_limiter_row* rows_host, const float* gains,
@@ -300,8 +293,11 @@ int vsp_limiter_rows(vsp_ctx* ctx, void* stream, int B, int A, int H, const vsp_
   if (!window_ok(A, H))
     return ctx->fail(VSP_ERR_ARG, "%s: attack %d, hold %d: 0 <= attack <= %d, 0 <= hold <= %d samples", who, A, H, LM_MAX_A, LM_MAX_H);
   const int64_t behind = (int64_t)A + H + LM_J, ahead = (int64_t)A + LM_J;
+  hipStream_t s = (hipStream_t)stream;
+  const Call call{ctx, who, s};
+  Ws ws = call.open(workspace, workspace_bytes);
+  Row* rows = carve_rows(ws, B);
   std::vector<Row> up((size_t)B);
-  size_t r_off = rows_bytes(B);
   int64_t r_max = 0, out_max = 0;
   for (int b = 0; b < B; ++b) {
     const vsp_limiter_row& h = rows_host[b];
@@ -337,32 +333,25 @@ int vsp_limiter_rows(vsp_ctx* ctx, void* stream, int B, int A, int H, const vsp_
     r.out_count = (int32_t)h.out_count;
     r.r0 = r.out_off - A - H;
     r.r_count = (int32_t)(h.out_count + 2 * (int64_t)A + H);
-    r.r = reinterpret_cast<float*>(static_cast<char*>(workspace) + r_off);
-    r_off += (size_t)r_words(h.out_count, A, H) * sizeof(float);
+    r.r = carve_r(ws, h.out_count, A, H);
     r_max = std::max<int64_t>(r_max, r.r_count);
     out_max = std::max<int64_t>(out_max, h.out_count);
   }
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, r_off)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  if (const int rc = upload_rows(ctx, who, s, ws, up)) return rc;
-  const Row* rows = reinterpret_cast<const Row*>(ws);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(rows, up.data(), up.size() * sizeof(Row))) return rc;
   unsigned* mg = reinterpret_cast<unsigned*>(min_gain);
   // (one tile at least: the launch also sets min_gain to 1)
   hipLaunchKernelGGL(lm_peak_kernel<false>, dim3((unsigned)std::max<int64_t>(1, (r_max + LM_T1 - 1) / LM_T1), B), dim3(256), 0, s, rows,
                      gains, (unsigned*)nullptr, mg, the_taps());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lm_peak_kernel: %s", hipGetErrorString(e));
+  if (const int rc = call.launched("lm_peak_kernel")) return rc;
   if (out_max == 0) return VSP_OK;
   const size_t lds = (size_t)(((LM_T2 + 2 * A + H + 3) & ~3) + LM_T2 + A) * sizeof(float);        // (at most 60 KiB)
   static std::atomic<uint64_t> done{0};
   if (lds > 48 * 1024) {
-    e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(lm_apply_kernel), 64 * 1024, done);
+    const hipError_t e = vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(lm_apply_kernel), 64 * 1024, done);
     if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "limiter (LDS): %s", hipGetErrorString(e));
   }
   const float inv = 1.f / (float)(A + 1);
   hipLaunchKernelGGL(lm_apply_kernel, dim3((unsigned)((out_max + LM_T2 - 1) / LM_T2), B), dim3(256), lds, s, rows, gains, mg, A, H, inv);
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lm_apply_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  return call.launched("lm_apply_kernel");
 }

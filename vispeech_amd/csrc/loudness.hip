@@ -41,6 +41,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "op_host.h"
 
 namespace {
 
@@ -662,7 +663,8 @@ __global__ void __launch_bounds__(256) lk_level_apply_kernel(const LRow* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+using vsp::Call;
+using vsp::Ws;
 
 bool fs_ok(int fs) { return fs >= LK_FS_MIN && fs <= LK_FS_MAX; }
 int segment_samples(int fs) { return (fs + 5) / 10; }
@@ -731,21 +733,27 @@ KW make_kw(int fs) {
   return kw;
 }
 
-// [rows: n, n_apply (int32 [B] each), params (float [B][3])] [ends] [starts] [seg] [blocks]
-struct Ws { size_t rows, ends, starts, seg, blocks, end; };
-size_t rows_bytes(int B) { return align256((size_t)5 * B * sizeof(int32_t)); }
-Ws layout(int B, int64_t S_max) {
-  Ws w;
-  w.rows = 0;
-  w.ends = rows_bytes(B);
-  w.starts = w.ends + align256((size_t)B * S_max * 4 * sizeof(double));
-  w.seg = w.starts + align256((size_t)B * S_max * 4 * sizeof(double));
-  w.blocks = w.seg + align256((size_t)B * S_max * sizeof(double));
-  w.end = w.blocks + align256((size_t)2 * B * sizeof(int32_t));
-  return w;
+// What the calls carve from their workspace (op_host.h); the sizes are the dry passes of these.  Every call's workspace
+// begins with its rows, so a call that needs the rows alone is covered by any of the sizes.
+//   measuring calls:  [rows: n, n_apply (int32 [B] each), params (float [B][3])] [ends] [starts] [seg] [blocks]
+Rows carve_rows(Ws& ws, int B) {
+  const int32_t* n = static_cast<const int32_t*>(ws.bytes((size_t)5 * B * sizeof(int32_t)));
+  return n ? Rows{n, n + B, reinterpret_cast<const float*>(n + (size_t)2 * B)} : Rows{};
 }
 
+struct SegWs { double* ends; double* starts; double* seg; int32_t* blocks; };
+SegWs carve_segments(Ws& ws, int B, int64_t S_max) {      // (a braced list is evaluated in order: so is every carve below)
+  const size_t cells = (size_t)B * S_max;
+  return {static_cast<double*>(ws.bytes(cells * 4 * sizeof(double))), static_cast<double*>(ws.bytes(cells * 4 * sizeof(double))),
+          static_cast<double*>(ws.bytes(cells * sizeof(double))), static_cast<int32_t*>(ws.bytes((size_t)2 * B * sizeof(int32_t)))};
+}
+
+struct MeasureWs { Rows rows; SegWs seg; };
+MeasureWs carve_measure(Ws& ws, int B, int64_t S_max) { return {carve_rows(ws, B), carve_segments(ws, B, S_max)}; }
+
 bool sizes_ok(int B, int64_t L_max) { return B >= 1 && B <= LK_MAX_B && L_max >= 1 && L_max <= LK_MAX_SAMPLES; }
+
+double z_abs() { return std::pow(10.0, (-70.0 + 0.691) / 10.0); }      // the absolute gate, -70 LUFS, as an energy
 
 const vsp_loudness_params kLeaveAlone = {NAN, 1.f, 0.f};
 
@@ -772,29 +780,34 @@ int check_rows(vsp_ctx* ctx, const char* who, int B, int64_t L_max, const int64_
   return VSP_OK;
 }
 
-int need_ws(vsp_ctx* ctx, const char* who, void* workspace, int64_t workspace_bytes, size_t need) {
-  if (!workspace || workspace_bytes < (int64_t)need)
-    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
-  return VSP_OK;
+int check_fs(const Call& call, int fs) {
+  if (fs_ok(fs)) return VSP_OK;
+  return call.ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", call.who, fs, LK_FS_MIN, LK_FS_MAX);
 }
 
-int upload_rows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, const std::vector<int32_t>& up, Rows& rows) {
-  // (pageable host memory: the runtime stages it before hipMemcpyAsync returns, as the prosody and align uploads rest on)
-  const hipError_t e = hipMemcpyAsync(ws, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-  rows.n = reinterpret_cast<const int32_t*>(ws);
-  rows.n_apply = rows.n + B;
-  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
-  return VSP_OK;
+// What every call over a batch of rows begins with: its own conditions on the batch (`ok`; `wants` says them behind the
+// rows' count), then the rows.  The sample rate, where the call has one, is checked before (`ok` may divide by a segment).
+int check_batch(const Call& call, bool ok, const char* wants, int B, int64_t L_max, const int64_t* n_host,
+                const vsp_loudness_params* params, std::vector<int32_t>& up) {
+  if (!ok) return call.ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, %s", call.who, LK_MAX_B, wants);
+  return check_rows(call.ctx, call.who, B, L_max, n_host, params, up);
 }
 
-int launch_segments(vsp_ctx* ctx, hipStream_t s, int B, int S_max, const KW& kw, const float* audio, int64_t stride, const Rows& rows,
-                    char* ws, const Ws& lay, double* seg, float* peak, const double* state_in, double* state_out) {
+int null_pointer(const Call& call) { return call.ctx->fail(VSP_ERR_ARG, "%s: null pointer", call.who); }
+
+int send_rows(const Call& call, const Rows& rows, const std::vector<int32_t>& up) {      // (check_rows' upload to carve_rows' place)
+  return call.upload(const_cast<int32_t*>(rows.n), up.data(), up.size() * sizeof(int32_t));
+}
+
+int launch_segments(const Call& call, int B, int S_max, const KW& kw, const float* audio, int64_t stride, const Rows& rows,
+                    const SegWs& w, double* seg, float* peak, const double* state_in, double* state_out) {
+  vsp_ctx* const ctx = call.ctx;
+  const hipStream_t s = call.s;
   SegArgs a;
   a.state_in = state_in; a.state_out = state_out;
   a.audio = audio; a.stride = stride; a.rows = rows;
-  a.ends = reinterpret_cast<double*>(ws + lay.ends);
-  a.starts = reinterpret_cast<double*>(ws + lay.starts);
+  a.ends = w.ends;
+  a.starts = w.starts;
   a.seg = seg;
   a.peak_bits = reinterpret_cast<unsigned*>(peak);
   a.S_max = S_max;
@@ -809,31 +822,25 @@ int launch_segments(vsp_ctx* ctx, hipStream_t s, int B, int S_max, const KW& kw,
   if (S_max > 1 || state_out) hipLaunchKernelGGL(lk_ends_kernel, grid, dim3(64), lds, s, a, kw);
   hipLaunchKernelGGL(lk_carry_kernel, dim3(B), dim3(64), 0, s, a, kw);
   hipLaunchKernelGGL(lk_energy_kernel, grid, dim3(64), lds, s, a, kw);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "loudness segments: %s", hipGetErrorString(e));
-  return VSP_OK;
+  return call.launched("loudness segments");
 }
 
-int launch_gate(vsp_ctx* ctx, hipStream_t s, int B, int S_max, int h, const double* seg, const Rows& rows, bool with_params,
+int launch_gate(const Call& call, int B, int S_max, int h, const double* seg, const Rows& rows, bool with_params,
                 const float* peak, float* lufs, int32_t* blocks, float* gains) {
   GateArgs a;
   a.seg = seg; a.rows = rows; a.peak = peak; a.lufs = lufs; a.blocks = blocks; a.gains = gains;
   a.S_max = S_max; a.h = h; a.with_params = with_params ? 1 : 0;
-  a.z_abs = std::pow(10.0, (-70.0 + 0.691) / 10.0);
-  hipLaunchKernelGGL(lk_gate_kernel, dim3(B), dim3(64), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lk_gate_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  a.z_abs = z_abs();
+  hipLaunchKernelGGL(lk_gate_kernel, dim3(B), dim3(64), 0, call.s, a);
+  return call.launched("lk_gate_kernel");
 }
 
-int launch_apply(vsp_ctx* ctx, hipStream_t s, int B, int64_t L_max, const float* in, int64_t in_stride, float* out, int64_t out_stride,
+int launch_apply(const Call& call, int B, int64_t L_max, const float* in, int64_t in_stride, float* out, int64_t out_stride,
                  const Rows& rows, const float* gains) {
   ApplyArgs a;
   a.in = in; a.out = out; a.in_stride = in_stride; a.out_stride = out_stride; a.n_apply = rows.n_apply; a.gains = gains;
-  hipLaunchKernelGGL(lk_apply_kernel, dim3((unsigned)((L_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "lk_apply_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(lk_apply_kernel, dim3((unsigned)((L_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, call.s, a);
+  return call.launched("lk_apply_kernel");
 }
 
 }  // namespace
@@ -853,89 +860,100 @@ int64_t vsp_loudness_segments_count(int64_t n_samples, int sample_rate) {
 
 int64_t vsp_loudness_workspace_bytes(int B, int64_t L_max, int sample_rate) {
   if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
-  return (int64_t)layout(B, segments_of(L_max, sample_rate)).end;
+  Ws ws = vsp::dry_ws();
+  carve_measure(ws, B, segments_of(L_max, sample_rate));
+  return (int64_t)ws.cur;
+}
+
+// vsp_loudness_segments, and vsp_loudness_segments_from (a piece of a stream: first_host, state_in, state_out)
+static int segments_call(const Call& call, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
+                         const int64_t* n_samples_host, const int64_t* first_host, const double* state_in, double* state_out, double* seg,
+                         float* peak, void* workspace, int64_t workspace_bytes) {
+  if (const int rc = check_fs(call, sample_rate)) return rc;
+  std::vector<int32_t> up;
+  if (const int rc = check_batch(call, sizes_ok(B, L_max) && audio_stride >= L_max && n_samples_host,
+                                 "1 <= L_max <= 2^30 <= audio_stride, and the rows' samples", B, L_max, n_samples_host, nullptr, up))
+    return rc;
+  const int h = segment_samples(sample_rate);
+  for (int b = 0; first_host && b < B; ++b)
+    if (first_host[b] < 0 || first_host[b] % h || first_host[b] + n_samples_host[b] > LK_MAX_SAMPLES)
+      return call.ctx->fail(VSP_ERR_ARG, "%s: row %d: the piece starts at sample %lld: a segment boundary (a multiple of %d), the stream at most 2^30 samples",
+                            call.who, b, (long long)first_host[b], h);
+  if (!audio || !seg || !peak) return null_pointer(call);
+  const int S_max = (int)segments_of(L_max, sample_rate);
+  Ws ws = call.open(workspace, workspace_bytes);
+  const MeasureWs w = carve_measure(ws, B, S_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = send_rows(call, w.rows, up)) return rc;
+  return launch_segments(call, B, S_max, make_kw(sample_rate), audio, audio_stride, w.rows, w.seg, seg, peak, state_in, state_out);
 }
 
 int vsp_loudness_segments(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                           const int64_t* n_samples_host, double* seg, float* peak, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_segments";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
-  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, and the rows' samples", who, LK_MAX_B);
-  std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
-  if (!audio || !seg || !peak) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  const int S_max = (int)segments_of(L_max, sample_rate);
-  const Ws lay = layout(B, S_max);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  Rows rows;
-  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
-  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak, nullptr, nullptr);
+  return segments_call(Call{ctx, "vsp_loudness_segments", (hipStream_t)stream}, B, L_max, sample_rate, audio, audio_stride, n_samples_host,
+                       nullptr, nullptr, nullptr, seg, peak, workspace, workspace_bytes);
 }
 
 int vsp_loudness_gate(vsp_ctx* ctx, void* stream, int B, int S_max, int sample_rate, const double* seg, const int64_t* n_samples_host,
                       const float* peak, const vsp_loudness_params* params_host, float* lufs, int32_t* blocks, float* gains,
                       void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_gate";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, "vsp_loudness_gate", (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   const int h = segment_samples(sample_rate);
-  if (B < 1 || B > LK_MAX_B || S_max < 1 || (int64_t)S_max * h > LK_MAX_SAMPLES + h || !n_samples_host)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, S_max >= 1 segments (at most 2^30 samples), and the rows' samples", who, LK_MAX_B);
   std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, std::min((int64_t)S_max * h, LK_MAX_SAMPLES), n_samples_host, params_host, up)) return rc;
-  if (!seg || !lufs || !blocks || (params_host && (!peak || !gains))) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_bytes(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Rows rows;
-  if (const int rc = upload_rows(ctx, who, s, static_cast<char*>(workspace), B, up, rows)) return rc;
-  return launch_gate(ctx, s, B, S_max, h, seg, rows, params_host != nullptr, peak, lufs, blocks, gains);
+  if (const int rc = check_batch(call, B >= 1 && B <= LK_MAX_B && S_max >= 1 && (int64_t)S_max * h <= LK_MAX_SAMPLES + h && n_samples_host,
+                                 "S_max >= 1 segments (at most 2^30 samples), and the rows' samples", B,
+                                 std::min((int64_t)S_max * h, LK_MAX_SAMPLES), n_samples_host, params_host, up))
+    return rc;
+  if (!seg || !lufs || !blocks || (params_host && (!peak || !gains))) return null_pointer(call);
+  Ws ws = call.open(workspace, workspace_bytes);
+  const Rows rows = carve_rows(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = send_rows(call, rows, up)) return rc;
+  return launch_gate(call, B, S_max, h, seg, rows, params_host != nullptr, peak, lufs, blocks, gains);
 }
 
 int vsp_loudness_apply(vsp_ctx* ctx, void* stream, int B, int64_t L_max, const float* in, int64_t in_stride, float* out,
                        int64_t out_stride, const int64_t* n_samples_host, const float* gains, const vsp_loudness_params* params_host,
                        void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_apply";
-  if (!sizes_ok(B, L_max) || in_stride < L_max || out_stride < L_max || !n_samples_host)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, and the rows' samples", who, LK_MAX_B);
+  const Call call{ctx, "vsp_loudness_apply", (hipStream_t)stream};
   std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, params_host, up)) return rc;
-  if (!in || !out || !gains) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, rows_bytes(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  Rows rows;
-  if (const int rc = upload_rows(ctx, who, s, static_cast<char*>(workspace), B, up, rows)) return rc;
-  return launch_apply(ctx, s, B, L_max, in, in_stride, out, out_stride, rows, gains);
+  if (const int rc = check_batch(call, sizes_ok(B, L_max) && in_stride >= L_max && out_stride >= L_max && n_samples_host,
+                                 "1 <= L_max <= 2^30 <= both strides, and the rows' samples", B, L_max, n_samples_host, params_host, up))
+    return rc;
+  if (!in || !out || !gains) return null_pointer(call);
+  Ws ws = call.open(workspace, workspace_bytes);
+  const Rows rows = carve_rows(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = send_rows(call, rows, up)) return rc;
+  return launch_apply(call, B, L_max, in, in_stride, out, out_stride, rows, gains);
 }
 
 int vsp_loudness_normalize(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                            float* out, int64_t out_stride, const int64_t* n_samples_host, const vsp_loudness_params* params_host,
                            float* lufs, float* peak, float* gains, int32_t* blocks, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_normalize";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
-  if (!sizes_ok(B, L_max) || audio_stride < L_max || out_stride < L_max || !n_samples_host || !params_host)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, the rows' samples and their params", who, LK_MAX_B);
+  const Call call{ctx, "vsp_loudness_normalize", (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, params_host, up)) return rc;
-  if (!audio || !out || !lufs || !peak || !gains) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  if (const int rc = check_batch(call, sizes_ok(B, L_max) && audio_stride >= L_max && out_stride >= L_max && n_samples_host && params_host,
+                                 "1 <= L_max <= 2^30 <= both strides, the rows' samples and their params", B, L_max, n_samples_host,
+                                 params_host, up))
+    return rc;
+  if (!audio || !out || !lufs || !peak || !gains) return null_pointer(call);
   const int S_max = (int)segments_of(L_max, sample_rate);
-  const Ws lay = layout(B, S_max);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  Rows rows;
-  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
+  Ws ws = call.open(workspace, workspace_bytes);
+  const MeasureWs w = carve_measure(ws, B, S_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = send_rows(call, w.rows, up)) return rc;
   const KW kw = make_kw(sample_rate);
-  double* seg = reinterpret_cast<double*>(ws + lay.seg);
-  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws, lay, seg, peak, nullptr, nullptr)) return rc;
-  if (!blocks) blocks = reinterpret_cast<int32_t*>(ws + lay.blocks);
-  if (const int rc = launch_gate(ctx, s, B, S_max, kw.h, seg, rows, true, peak, lufs, blocks, gains)) return rc;
-  return launch_apply(ctx, s, B, L_max, audio, audio_stride, out, out_stride, rows, gains);
+  if (const int rc = launch_segments(call, B, S_max, kw, audio, audio_stride, w.rows, w.seg, w.seg.seg, peak, nullptr, nullptr)) return rc;
+  if (!blocks) blocks = w.seg.blocks;
+  if (const int rc = launch_gate(call, B, S_max, kw.h, w.seg.seg, w.rows, true, peak, lufs, blocks, gains)) return rc;
+  return launch_apply(call, B, L_max, audio, audio_stride, out, out_stride, w.rows, gains);
 }
 
 // ---------------------------------------------------------------------------------- loudness over time: entry points
@@ -943,9 +961,12 @@ namespace {
 
 constexpr int64_t LK_MAX_ENTRIES = LK_MAX_SAMPLES / 800 + 1;      // (h >= 800; every call checks entries h itself)
 
-size_t lrows_bytes(int B) { return align256((size_t)B * sizeof(LRow)); }
-// [rows (as every loudness call)] [LRow [B]] and, for the fused call, [ends] [starts] [seg] [blocks]
-size_t time_head(int B) { return rows_bytes(B) + lrows_bytes(B); }
+//   calls over time:  [rows (as every loudness call)] [LRow [B]] and, for the fused call, [ends] [starts] [seg] [blocks]
+struct TimeWs { Rows rows; LRow* lrows; };
+TimeWs carve_time(Ws& ws, int B) { return {carve_rows(ws, B), static_cast<LRow*>(ws.bytes((size_t)B * sizeof(LRow)))}; }
+
+struct LevelWs { TimeWs head; SegWs seg; };
+LevelWs carve_level(Ws& ws, int B, int64_t S_max) { return {carve_time(ws, B), carve_segments(ws, B, S_max)}; }
 
 int check_level(vsp_ctx* ctx, const char* who, int b, const vsp_loudness_level_params& p) {
   if (!(p.max_gain_db >= 0.f)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: max_gain_db must be at least 0", who, b);
@@ -969,102 +990,85 @@ int check_entries(vsp_ctx* ctx, const char* who, int b, const vsp_loudness_row& 
   return VSP_OK;
 }
 
-int upload_lrows(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, const std::vector<LRow>& up, const LRow*& dev) {
-  const hipError_t e = hipMemcpyAsync(ws + rows_bytes(B), up.data(), up.size() * sizeof(LRow), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-  dev = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
+// The entries of a row that the time kernels read and write (vsp_loudness_time, vsp_loudness_time_hist).
+int set_entries(const Call& call, int b, const vsp_loudness_row& r, int h, LRow& d) {
+  if (const int rc = check_entries(call.ctx, call.who, b, r, h)) return rc;
+  if (r.count && (!r.seg || !r.M || !r.S || !r.I || !r.kept)) return call.ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", call.who, b);
+  std::memset(&d, 0, sizeof d);
+  d.seg = r.seg; d.M = r.M; d.S = r.S; d.I = r.I; d.kept = r.kept;
+  d.first = (int32_t)r.first; d.count = (int32_t)r.count;
   return VSP_OK;
 }
 
-int launched(vsp_ctx* ctx, const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return VSP_OK;
+// What the three calls over a set of streams end their checks with: the workspace's head, and the LRows into it.
+int send_lrows(const Call& call, int B, const std::vector<LRow>& up, void* workspace, int64_t workspace_bytes, const LRow*& dev) {
+  Ws ws = call.open(workspace, workspace_bytes);
+  const TimeWs w = carve_time(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  dev = w.lrows;
+  return call.upload(w.lrows, up.data(), up.size() * sizeof(LRow));
 }
 
-int launch_time(vsp_ctx* ctx, hipStream_t s, int B, int count_max, int h, const LRow* rows, float* m_max, float* s_max) {
-  if (count_max > 0)
-    hipLaunchKernelGGL(lk_time_kernel, dim3(count_max, B), dim3(64), 0, s, rows, h, std::pow(10.0, (-70.0 + 0.691) / 10.0));
-  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, s, rows, m_max, s_max);
-  return launched(ctx, "loudness time");
+int launch_time(const Call& call, int B, int count_max, int h, const LRow* rows, float* m_max, float* s_max) {
+  if (count_max > 0) hipLaunchKernelGGL(lk_time_kernel, dim3(count_max, B), dim3(64), 0, call.s, rows, h, z_abs());
+  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, call.s, rows, m_max, s_max);
+  return call.launched("loudness time");
 }
 
-int launch_level_gains(vsp_ctx* ctx, hipStream_t s, int B, const LRow* rows) {
-  hipLaunchKernelGGL(lk_level_gains_kernel, dim3((B + 63) / 64), dim3(64), 0, s, rows, B);
-  return launched(ctx, "lk_level_gains_kernel");
+int launch_level_gains(const Call& call, int B, const LRow* rows) {
+  hipLaunchKernelGGL(lk_level_gains_kernel, dim3((B + 63) / 64), dim3(64), 0, call.s, rows, B);
+  return call.launched("lk_level_gains_kernel");
 }
 
-int launch_level_apply(vsp_ctx* ctx, hipStream_t s, int B, int64_t samples_max, int h, const LRow* rows) {
+int launch_level_apply(const Call& call, int B, int64_t samples_max, int h, const LRow* rows) {
   if (samples_max < 1) return VSP_OK;
-  hipLaunchKernelGGL(lk_level_apply_kernel, dim3((unsigned)((samples_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, s, rows, h,
-                     1.f / (float)h);
-  return launched(ctx, "lk_level_apply_kernel");
+  hipLaunchKernelGGL(lk_level_apply_kernel, dim3((unsigned)((samples_max + LK_APPLY_SPAN - 1) / LK_APPLY_SPAN), B), dim3(256), 0, call.s, rows,
+                     h, 1.f / (float)h);
+  return call.launched("lk_level_apply_kernel");
 }
 
 }  // namespace
 
 int64_t vsp_loudness_time_workspace_bytes(int B, int64_t L_max, int sample_rate) {
   if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
-  return (int64_t)(lrows_bytes(B) + layout(B, segments_of(L_max, sample_rate)).end);
+  Ws ws = vsp::dry_ws();
+  carve_level(ws, B, segments_of(L_max, sample_rate));
+  return (int64_t)ws.cur;
 }
 
 int vsp_loudness_segments_from(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                                const int64_t* n_samples_host, const int64_t* first_host, const double* state_in, double* state_out,
                                double* seg, float* peak, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_segments_from";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
-  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, and the rows' samples", who, LK_MAX_B);
-  std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
-  const int h = segment_samples(sample_rate);
-  for (int b = 0; first_host && b < B; ++b)
-    if (first_host[b] < 0 || first_host[b] % h || first_host[b] + n_samples_host[b] > LK_MAX_SAMPLES)
-      return ctx->fail(VSP_ERR_ARG, "%s: row %d: the piece starts at sample %lld: a segment boundary (a multiple of %d), the stream at most 2^30 samples",
-                       who, b, (long long)first_host[b], h);
-  if (!audio || !seg || !peak) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
-  const int S_max = (int)segments_of(L_max, sample_rate);
-  const Ws lay = layout(B, S_max);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  Rows rows;
-  if (const int rc = upload_rows(ctx, who, s, ws, B, up, rows)) return rc;
-  return launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws, lay, seg, peak, state_in, state_out);
+  return segments_call(Call{ctx, "vsp_loudness_segments_from", (hipStream_t)stream}, B, L_max, sample_rate, audio, audio_stride,
+                       n_samples_host, first_host, state_in, state_out, seg, peak, workspace, workspace_bytes);
 }
 
 int vsp_loudness_time(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, float* m_max, float* s_max,
                       void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
   const char* who = "vsp_loudness_time";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, who, (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   if (B < 1 || B > LK_MAX_B || !rows_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows", who, LK_MAX_B);
   const int h = segment_samples(sample_rate);
   std::vector<LRow> up((size_t)B);
   int64_t count_max = 0;
   for (int b = 0; b < B; ++b) {
-    const vsp_loudness_row& r = rows_host[b];
-    if (const int rc = check_entries(ctx, who, b, r, h)) return rc;
-    if (r.count && (!r.seg || !r.M || !r.S || !r.I || !r.kept)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
-    LRow& d = up[b];
-    std::memset(&d, 0, sizeof d);
-    d.seg = r.seg; d.M = r.M; d.S = r.S; d.I = r.I; d.kept = r.kept;
-    d.first = (int32_t)r.first; d.count = (int32_t)r.count;
-    count_max = std::max(count_max, r.count);
+    if (const int rc = set_entries(call, b, rows_host[b], h, up[b])) return rc;
+    count_max = std::max(count_max, rows_host[b].count);
   }
   if (!m_max != !s_max) return ctx->fail(VSP_ERR_ARG, "%s: m_max and s_max come together", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
   const LRow* dev;
-  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
-  return launch_time(ctx, s, B, (int)count_max, h, dev, m_max, s_max);
+  if (const int rc = send_lrows(call, B, up, workspace, workspace_bytes, dev)) return rc;
+  return launch_time(call, B, (int)count_max, h, dev, m_max, s_max);
 }
 
 int vsp_loudness_level_gains(vsp_ctx* ctx, void* stream, int B, const vsp_loudness_row* rows_host,
                              const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
   const char* who = "vsp_loudness_level_gains";
+  const Call call{ctx, who, (hipStream_t)stream};
   if (B < 1 || B > LK_MAX_B || !rows_host || !params_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their params", who, LK_MAX_B);
   std::vector<LRow> up((size_t)B);
   for (int b = 0; b < B; ++b) {
@@ -1079,18 +1083,17 @@ int vsp_loudness_level_gains(vsp_ctx* ctx, void* stream, int B, const vsp_loudne
     d.first = (int32_t)r.first; d.count = (int32_t)r.count;
     set_level(d, params_host[b]);
   }
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
   const LRow* dev;
-  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
-  return launch_level_gains(ctx, s, B, dev);
+  if (const int rc = send_lrows(call, B, up, workspace, workspace_bytes, dev)) return rc;
+  return launch_level_gains(call, B, dev);
 }
 
 int vsp_loudness_level_apply(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host,
                              const vsp_loudness_level_params* params_host, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
   const char* who = "vsp_loudness_level_apply";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, who, (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   if (B < 1 || B > LK_MAX_B || !rows_host || !params_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their params", who, LK_MAX_B);
   const int h = segment_samples(sample_rate);
   std::vector<LRow> up((size_t)B);
@@ -1113,11 +1116,9 @@ int vsp_loudness_level_apply(vsp_ctx* ctx, void* stream, int B, int sample_rate,
     set_level(d, params_host[b]);
     samples_max = std::max(samples_max, (int64_t)d.samples);
   }
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, time_head(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
   const LRow* dev;
-  if (const int rc = upload_lrows(ctx, who, s, static_cast<char*>(workspace), B, up, dev)) return rc;
-  return launch_level_apply(ctx, s, B, samples_max, h, dev);
+  if (const int rc = send_lrows(call, B, up, workspace, workspace_bytes, dev)) return rc;
+  return launch_level_apply(call, B, samples_max, h, dev);
 }
 
 int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride, float* out,
@@ -1125,33 +1126,33 @@ int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sam
                        float* I, int32_t* kept, float* c_db, float* c, int64_t table_stride, float* m_max, float* s_max, float* i_end,
                        float* peak, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_level";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, "vsp_loudness_level", (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   const int h = segment_samples(sample_rate);
-  if (!sizes_ok(B, L_max) || audio_stride < L_max || (params_host && out_stride < L_max) || !n_samples_host || table_stride < L_max / h)
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= both strides, table_stride >= L_max / h, and the rows' samples", who,
-                     LK_MAX_B);
   std::vector<int32_t> up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, up)) return rc;
+  if (const int rc = check_batch(call, sizes_ok(B, L_max) && audio_stride >= L_max && !(params_host && out_stride < L_max) && n_samples_host &&
+                                           table_stride >= L_max / h,
+                                 "1 <= L_max <= 2^30 <= both strides, table_stride >= L_max / h, and the rows' samples", B, L_max, n_samples_host,
+                                 nullptr, up))
+    return rc;
   for (int b = 0; params_host && b < B; ++b)
-    if (const int rc = check_level(ctx, who, b, params_host[b])) return rc;
-  if (!audio || !M || !S || !I || !kept || !m_max || !s_max || !i_end || !peak || (params_host && (!out || !c_db || !c)))
-    return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+    if (const int rc = check_level(ctx, call.who, b, params_host[b])) return rc;
+  if (!audio || !M || !S || !I || !kept || !m_max || !s_max || !i_end || !peak || (params_host && (!out || !c_db || !c))) return null_pointer(call);
   const int S_max = (int)segments_of(L_max, sample_rate);
-  const Ws lay = layout(B, S_max);                      // (behind the LRows)
-  const size_t shift = lrows_bytes(B);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, shift + lay.end)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  double* seg = reinterpret_cast<double*>(ws + shift + lay.seg);
-  // ONE upload: the rows of the segment kernels, then the rows of this section
-  std::vector<char> both(time_head(B), 0);
-  std::memcpy(both.data(), up.data(), up.size() * sizeof(int32_t));
-  LRow* lr = reinterpret_cast<LRow*>(both.data() + rows_bytes(B));
+  Ws ws = call.open(workspace, workspace_bytes);
+  const LevelWs w = carve_level(ws, B, S_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  // ONE upload: the rows of the segment kernels, then the rows of this section -- a host copy of the head, carved as the head is
+  Ws head = vsp::dry_ws();
+  carve_time(head, B);
+  std::vector<char> both(head.cur, 0);
+  Ws mirror(both.data(), both.size(), false);
+  const TimeWs host = carve_time(mirror, B);
+  std::memcpy(const_cast<int32_t*>(host.rows.n), up.data(), up.size() * sizeof(int32_t));
   for (int b = 0; b < B; ++b) {
-    LRow& d = lr[b];
+    LRow& d = host.lrows[b];
     const size_t t = (size_t)b * table_stride;
-    d.seg = seg + (size_t)b * S_max;
+    d.seg = w.seg.seg + (size_t)b * S_max;
     d.M = M + t; d.S = S + t; d.I = I + t; d.kept = kept + t;
     d.first = 0; d.count = (int32_t)(n_samples_host[b] / h);
     if (!params_host) continue;
@@ -1160,21 +1161,16 @@ int vsp_loudness_level(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sam
     d.pos = 0; d.samples = params_host[b].target_lufs != params_host[b].target_lufs ? 0 : (int32_t)n_samples_host[b];
     set_level(d, params_host[b]);
   }
-  const hipError_t e = hipMemcpyAsync(ws, both.data(), both.size(), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-  Rows rows;
-  rows.n = reinterpret_cast<const int32_t*>(ws);
-  rows.n_apply = rows.n + B;
-  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
-  const LRow* dev = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
+  if (const int rc = call.upload(workspace, both.data(), both.size())) return rc;
+  const Rows& rows = w.head.rows;
+  const LRow* dev = w.head.lrows;
   const KW kw = make_kw(sample_rate);
-  if (const int rc = launch_segments(ctx, s, B, S_max, kw, audio, audio_stride, rows, ws + shift, lay, seg, peak, nullptr, nullptr)) return rc;
-  int32_t* blocks = reinterpret_cast<int32_t*>(ws + shift + lay.blocks);
-  if (const int rc = launch_gate(ctx, s, B, S_max, h, seg, rows, false, peak, i_end, blocks, nullptr)) return rc;
-  if (const int rc = launch_time(ctx, s, B, (int)(L_max / h), h, dev, m_max, s_max)) return rc;
+  if (const int rc = launch_segments(call, B, S_max, kw, audio, audio_stride, rows, w.seg, w.seg.seg, peak, nullptr, nullptr)) return rc;
+  if (const int rc = launch_gate(call, B, S_max, h, w.seg.seg, rows, false, peak, i_end, w.seg.blocks, nullptr)) return rc;
+  if (const int rc = launch_time(call, B, (int)(L_max / h), h, dev, m_max, s_max)) return rc;
   if (!params_host) return VSP_OK;
-  if (const int rc = launch_level_gains(ctx, s, B, dev)) return rc;
-  return launch_level_apply(ctx, s, B, L_max, h, dev);
+  if (const int rc = launch_level_gains(call, B, dev)) return rc;
+  return launch_level_apply(call, B, L_max, h, dev);
 }
 
 // --------------------------------------------------------------- loudness range and the histogram gate: entry points
@@ -1184,43 +1180,58 @@ constexpr size_t LK_HIST_TABLE_DOUBLES = 2 * LK_HIST_BINS + 1;      // the edges
 
 void hist_tables(double* edges, double* centres) {
   for (int k = 0; k <= LK_HIST_BINS; ++k) edges[k] = std::pow(10.0, ((double)k - 693.09) / 100.0);
-  edges[0] = std::pow(10.0, (-70.0 + 0.691) / 10.0);     // Z_abs by the exact gate's own expression (the line above is 2e-15 off it)
+  edges[0] = z_abs();                                    // by the exact gate's own expression (the line above is 2e-15 off it)
   for (int k = 0; k < LK_HIST_BINS; ++k) centres[k] = std::pow(10.0, ((double)k - 692.59) / 100.0);
 }
 
-// [rows (as every loudness call)] [LRow [B]] [histogram pointers [B]] [edges, centres] and, for the fused call,
-// [ends] [starts] [seg] [blocks] [peak [B]] [histograms [B][2][1000]]
-size_t hist_ptrs_bytes(int B) { return align256((size_t)B * sizeof(int32_t*)); }
-size_t hist_head(int B) { return time_head(B) + hist_ptrs_bytes(B) + align256(LK_HIST_TABLE_DOUBLES * sizeof(double)); }
+//   histogram calls:  [rows (as every loudness call)] [LRow [B]] [histogram pointers [B]] [edges, centres] and, for the fused
+//                     call, [a measuring call's: rows (not used: the head's serve), ends, starts, seg, blocks] [peak [B]]
+//                     [histograms [B][2][1000]]
+struct HistWs { TimeWs head; int32_t** hist; double* tables; };
+HistWs carve_hist(Ws& ws, int B) {
+  return {carve_time(ws, B), static_cast<int32_t**>(ws.bytes((size_t)B * sizeof(int32_t*))),
+          static_cast<double*>(ws.bytes(LK_HIST_TABLE_DOUBLES * sizeof(double)))};
+}
 
-// What a call of this section uploads behind the rows of the segment kernels: the LRows, the histogram pointers, the tables.
+struct RangeWs { HistWs head; SegWs seg; float* peak; int32_t* hists; };
+RangeWs carve_range(Ws& ws, int B, int64_t S_max) {
+  return {carve_hist(ws, B), carve_measure(ws, B, S_max).seg, ws.f((size_t)B),
+          static_cast<int32_t*>(ws.bytes((size_t)B * 2 * LK_HIST_BINS * sizeof(int32_t)))};
+}
+
+size_t hist_head_bytes(int B) {
+  Ws ws = vsp::dry_ws();
+  carve_hist(ws, B);
+  return ws.cur;
+}
+
+// What a call of this section uploads: a host copy of the workspace's head, carved as the head is -- behind the rows of the
+// segment kernels the LRows, the histogram pointers, the tables.
 struct HistUpload {
-  std::vector<char> bytes;               // the workspace's first hist_head(B) bytes
-  LRow* rows;
-  int32_t** hist;
-  explicit HistUpload(int B) : bytes(hist_head(B), 0) {
-    rows = reinterpret_cast<LRow*>(bytes.data() + rows_bytes(B));
-    hist = reinterpret_cast<int32_t**>(bytes.data() + time_head(B));
-    double* t = reinterpret_cast<double*>(bytes.data() + time_head(B) + hist_ptrs_bytes(B));
-    hist_tables(t, t + LK_HIST_BINS + 1);
+  std::vector<char> bytes;
+  Ws mirror;
+  const HistWs host;
+  explicit HistUpload(int B) : bytes(hist_head_bytes(B), 0), mirror(bytes.data(), bytes.size(), false), host(carve_hist(mirror, B)) {
+    hist_tables(host.tables, host.tables + LK_HIST_BINS + 1);
   }
-  // One copy of [from, the end); the kernel's arguments point into the workspace.
-  int send(vsp_ctx* ctx, const char* who, hipStream_t s, char* ws, int B, size_t from, float* lra, float* i_last, int h, HistArgs& a) const {
-    const hipError_t e = hipMemcpyAsync(ws + from, bytes.data() + from, bytes.size() - from, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (rows): %s", who, hipGetErrorString(e));
-    a.rows = reinterpret_cast<const LRow*>(ws + rows_bytes(B));
-    a.hist = reinterpret_cast<int32_t* const*>(ws + time_head(B));
-    a.edges = reinterpret_cast<const double*>(ws + time_head(B) + hist_ptrs_bytes(B));
+  // One copy, of the whole head or of what lies behind its first rows; the kernel's arguments point into the workspace.
+  int send(const Call& call, const HistWs& dev, bool with_rows, float* lra, float* i_last, int h, HistArgs& a) const {
+    const char* from = with_rows ? bytes.data() : reinterpret_cast<const char*>(host.head.lrows);
+    void* to = with_rows ? (void*)dev.head.rows.n : (void*)dev.head.lrows;
+    if (const int rc = call.upload(to, from, (size_t)(bytes.data() + bytes.size() - from))) return rc;
+    a.rows = dev.head.lrows;
+    a.hist = dev.hist;
+    a.edges = dev.tables;
     a.centres = a.edges + LK_HIST_BINS + 1;
     a.lra = lra; a.i_last = i_last; a.h = h;
     return VSP_OK;
   }
 };
 
-int launch_hist(vsp_ctx* ctx, hipStream_t s, int B, const HistArgs& a, float* m_max, float* s_max) {
-  hipLaunchKernelGGL(lk_hist_kernel, dim3(B), dim3(64), 0, s, a);
-  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, s, a.rows, m_max, s_max);
-  return launched(ctx, "loudness histogram");
+int launch_hist(const Call& call, int B, const HistArgs& a, float* m_max, float* s_max) {
+  hipLaunchKernelGGL(lk_hist_kernel, dim3(B), dim3(64), 0, call.s, a);
+  if (m_max) hipLaunchKernelGGL(lk_time_max_kernel, dim3(B), dim3(64), 0, call.s, a.rows, m_max, s_max);
+  return call.launched("loudness histogram");
 }
 
 }  // namespace
@@ -1233,77 +1244,67 @@ int vsp_loudness_hist_tables(double* edges, double* centres) {
 
 int64_t vsp_loudness_hist_workspace_bytes(int B, int64_t L_max, int sample_rate) {
   if (!sizes_ok(B, L_max) || !fs_ok(sample_rate)) return VSP_ERR_ARG;
-  return (int64_t)(hist_head(B) + layout(B, segments_of(L_max, sample_rate)).end + align256((size_t)B * sizeof(float)) +
-                   align256((size_t)B * 2 * LK_HIST_BINS * sizeof(int32_t)));
+  Ws ws = vsp::dry_ws();
+  carve_range(ws, B, segments_of(L_max, sample_rate));
+  return (int64_t)ws.cur;
 }
 
 int vsp_loudness_time_hist(vsp_ctx* ctx, void* stream, int B, int sample_rate, const vsp_loudness_row* rows_host, int32_t* const* hist_host,
                            float* m_max, float* s_max, float* lra, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
   const char* who = "vsp_loudness_time_hist";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, who, (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   if (B < 1 || B > LK_MAX_B || !rows_host || !hist_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows and their histograms", who, LK_MAX_B);
   const int h = segment_samples(sample_rate);
   HistUpload up(B);
   for (int b = 0; b < B; ++b) {
-    const vsp_loudness_row& r = rows_host[b];
-    if (const int rc = check_entries(ctx, who, b, r, h)) return rc;
-    if (r.count && (!r.seg || !r.M || !r.S || !r.I || !r.kept)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    if (const int rc = set_entries(call, b, rows_host[b], h, up.host.head.lrows[b])) return rc;
     if (!hist_host[b]) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null histogram", who, b);
-    LRow& d = up.rows[b];
-    d.seg = r.seg; d.M = r.M; d.S = r.S; d.I = r.I; d.kept = r.kept;
-    d.first = (int32_t)r.first; d.count = (int32_t)r.count;
-    up.hist[b] = hist_host[b];
+    up.host.hist[b] = hist_host[b];
   }
   if (!m_max != !s_max) return ctx->fail(VSP_ERR_ARG, "%s: m_max and s_max come together", who);
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, hist_head(B))) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  Ws ws = call.open(workspace, workspace_bytes);
+  const HistWs w = carve_hist(ws, B);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
   HistArgs a;
-  if (const int rc = up.send(ctx, who, s, static_cast<char*>(workspace), B, rows_bytes(B), lra, nullptr, h, a)) return rc;
-  return launch_hist(ctx, s, B, a, m_max, s_max);
+  if (const int rc = up.send(call, w, false, lra, nullptr, h, a)) return rc;
+  return launch_hist(call, B, a, m_max, s_max);
 }
 
 int vsp_loudness_range(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int sample_rate, const float* audio, int64_t audio_stride,
                        const int64_t* n_samples_host, float* lra, float* i_hist, float* M, float* S, float* I, int32_t* kept,
                        int64_t table_stride, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  const char* who = "vsp_loudness_range";
-  if (!fs_ok(sample_rate)) return ctx->fail(VSP_ERR_ARG, "%s: sample_rate %d: %d <= sample_rate <= %d", who, sample_rate, LK_FS_MIN, LK_FS_MAX);
+  const Call call{ctx, "vsp_loudness_range", (hipStream_t)stream};
+  if (const int rc = check_fs(call, sample_rate)) return rc;
   const int h = segment_samples(sample_rate);
   const bool tables = M || S || I || kept;
-  if (tables && (!M || !S || !I || !kept)) return ctx->fail(VSP_ERR_ARG, "%s: M, S, I and kept come together", who);
-  if (!sizes_ok(B, L_max) || audio_stride < L_max || !n_samples_host || (tables && table_stride < L_max / h))
-    return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows, 1 <= L_max <= 2^30 <= audio_stride, table_stride >= L_max / h, and the rows' samples", who,
-                     LK_MAX_B);
+  if (tables && (!M || !S || !I || !kept)) return ctx->fail(VSP_ERR_ARG, "%s: M, S, I and kept come together", call.who);
   std::vector<int32_t> rows_up;
-  if (const int rc = check_rows(ctx, who, B, L_max, n_samples_host, nullptr, rows_up)) return rc;
-  if (!audio || !lra) return ctx->fail(VSP_ERR_ARG, "%s: null pointer", who);
+  if (const int rc = check_batch(call, sizes_ok(B, L_max) && audio_stride >= L_max && n_samples_host && !(tables && table_stride < L_max / h),
+                                 "1 <= L_max <= 2^30 <= audio_stride, table_stride >= L_max / h, and the rows' samples", B, L_max,
+                                 n_samples_host, nullptr, rows_up))
+    return rc;
+  if (!audio || !lra) return null_pointer(call);
   const int S_max = (int)segments_of(L_max, sample_rate);
-  const Ws lay = layout(B, S_max);                      // (behind the head)
-  const size_t shift = hist_head(B);
-  const size_t peak_at = shift + lay.end, hist_at = peak_at + align256((size_t)B * sizeof(float));
-  if (const int rc = need_ws(ctx, who, workspace, workspace_bytes, hist_at + align256((size_t)B * 2 * LK_HIST_BINS * sizeof(int32_t)))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  double* seg = reinterpret_cast<double*>(ws + shift + lay.seg);
+  Ws ws = call.open(workspace, workspace_bytes);
+  const RangeWs w = carve_range(ws, B, S_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
   HistUpload up(B);                                     // ONE upload: the rows of the segment kernels, then the rows of this section
-  std::memcpy(up.bytes.data(), rows_up.data(), rows_up.size() * sizeof(int32_t));
+  std::memcpy(const_cast<int32_t*>(up.host.head.rows.n), rows_up.data(), rows_up.size() * sizeof(int32_t));
   for (int b = 0; b < B; ++b) {
-    LRow& d = up.rows[b];
+    LRow& d = up.host.head.lrows[b];
     const size_t t = (size_t)b * table_stride;
-    d.seg = seg + (size_t)b * S_max;
+    d.seg = w.seg.seg + (size_t)b * S_max;
     if (tables) { d.M = M + t; d.S = S + t; d.I = I + t; d.kept = kept + t; }
     d.first = 0; d.count = (int32_t)(n_samples_host[b] / h);
-    up.hist[b] = reinterpret_cast<int32_t*>(ws + hist_at) + (size_t)b * 2 * LK_HIST_BINS;
+    up.host.hist[b] = w.hists + (size_t)b * 2 * LK_HIST_BINS;
   }
   HistArgs a;
-  if (const int rc = up.send(ctx, who, s, ws, B, 0, lra, i_hist, h, a)) return rc;
-  Rows rows;
-  rows.n = reinterpret_cast<const int32_t*>(ws);
-  rows.n_apply = rows.n + B;
-  rows.params = reinterpret_cast<const float*>(rows.n + (size_t)2 * B);
-  if (const int rc = launch_segments(ctx, s, B, S_max, make_kw(sample_rate), audio, audio_stride, rows, ws + shift, lay, seg,
-                                     reinterpret_cast<float*>(ws + peak_at), nullptr, nullptr))
+  if (const int rc = up.send(call, w.head, true, lra, i_hist, h, a)) return rc;
+  if (const int rc = launch_segments(call, B, S_max, make_kw(sample_rate), audio, audio_stride, w.head.head.rows, w.seg, w.seg.seg, w.peak,
+                                     nullptr, nullptr))
     return rc;
-  return launch_hist(ctx, s, B, a, nullptr, nullptr);
+  return launch_hist(call, B, a, nullptr, nullptr);
 }

@@ -36,6 +36,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "op_host.h"
 
 namespace {
 
@@ -617,28 +618,20 @@ void build_tables(const Plan& pl, Tables& t) {
   }
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+using vsp::Call;
+using vsp::Ws;
 
-struct ContourWs { size_t n_samples, stat, tables, end; };
-ContourWs contour_ws(int B, const Plan& pl) {
-  ContourWs w;
-  size_t cur = 0;
-  w.n_samples = cur; cur += align256((size_t)B * sizeof(int64_t));
-  w.stat = cur; cur += align256((size_t)B * sizeof(RowStat));
-  w.tables = cur; cur += align256(((size_t)PR_NFFT + pl.W4 + (size_t)PR_LAGS_PER_WAVE * pl.LB) * sizeof(float));
-  w.end = cur;
-  return w;
+// What each call carves from its workspace (op_host.h); the sizes are the dry passes of these.
+struct ContourWs { int64_t* n_samples; RowStat* stat; float* tables; };
+ContourWs carve_contour(Ws& ws, int B, const Plan& pl) {      // (a braced list is evaluated in order: so is every carve below)
+  return {static_cast<int64_t*>(ws.bytes((size_t)B * sizeof(int64_t))), static_cast<RowStat*>(ws.bytes((size_t)B * sizeof(RowStat))),
+          ws.f((size_t)PR_NFFT + pl.W4 + (size_t)PR_LAGS_PER_WAVE * pl.LB)};
 }
 
-struct PhonemeWs { size_t ints, interp, prev, end; };
-PhonemeWs phoneme_ws(int B, int64_t F_max, int Tp) {
-  PhonemeWs w;
-  size_t cur = 0;
-  w.ints = cur; cur += align256(((size_t)2 * B * Tp + 2 * (size_t)B) * sizeof(int32_t));     // start, dur, frames, lengths
-  w.interp = cur; cur += align256((size_t)B * F_max * sizeof(float));
-  w.prev = cur; cur += align256((size_t)B * F_max * sizeof(int32_t));
-  w.end = cur;
-  return w;
+struct PhonemeWs { int32_t* ints; float* interp; int32_t* prev; };
+PhonemeWs carve_phoneme(Ws& ws, int B, int64_t F_max, int Tp) {      // ints: start, dur, frames, lengths
+  return {static_cast<int32_t*>(ws.bytes(((size_t)2 * B * Tp + 2 * (size_t)B) * sizeof(int32_t))), ws.f((size_t)B * F_max),
+          static_cast<int32_t*>(ws.bytes((size_t)B * F_max * sizeof(int32_t)))};
 }
 
 std::atomic<uint64_t> g_contour_lds_done{0}, g_candidate_lds_done{0};
@@ -661,47 +654,32 @@ int refuse_path(vsp_ctx* ctx, const char* who, int bad) {
                    VSP_PROSODY_MAX_CANDIDATES);
 }
 
-struct PathWs { size_t frames, bp, end; };
-PathWs path_ws(int B, int64_t F_max) {
-  PathWs w;
-  size_t cur = 0;
-  w.frames = cur; cur += align256((size_t)B * sizeof(int32_t));
-  w.bp = cur; cur += align256((size_t)B * F_max * PR_SLOTS);
-  w.end = cur;
-  return w;
+struct PathWs { int32_t* frames; uint8_t* bp; };
+PathWs carve_path(Ws& ws, int B, int64_t F_max) {
+  return {static_cast<int32_t*>(ws.bytes((size_t)B * sizeof(int32_t))), static_cast<uint8_t*>(ws.bytes((size_t)B * F_max * PR_SLOTS))};
 }
 
 // vsp_prosody_contours_path: [the contour call's] [cand_f] [cand_s] [the path's]
-struct ContourPathWs { size_t cand_f, cand_s, path, end; };
-ContourPathWs contour_path_ws(int B, int64_t F_max, const Plan& pl) {
-  ContourPathWs w;
-  size_t cur = contour_ws(B, pl).end;
-  w.cand_f = cur; cur += align256((size_t)B * F_max * PR_SLOTS * sizeof(float));
-  w.cand_s = cur; cur += align256((size_t)B * F_max * PR_SLOTS * sizeof(float));
-  w.path = cur; cur += path_ws(B, F_max).end;
-  w.end = cur;
-  return w;
+struct ContourPathWs { ContourWs contour; float* cand_f; float* cand_s; PathWs path; };
+ContourPathWs carve_contour_path(Ws& ws, int B, int64_t F_max, const Plan& pl) {
+  return {carve_contour(ws, B, pl), ws.f((size_t)B * F_max * PR_SLOTS), ws.f((size_t)B * F_max * PR_SLOTS), carve_path(ws, B, F_max)};
 }
 
 // The launch of the path kernel behind the upload of the rows' frame counts (already checked).
-int launch_path(vsp_ctx* ctx, const char* who, hipStream_t s, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
-                const std::vector<int32_t>& frames, const vsp_prosody_path_params& pp, float* f0_frames, char* ws) {
-  const PathWs lay = path_ws(B, F_max);
-  hipError_t e = hipMemcpyAsync(ws + lay.frames, frames.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (frames): %s", who, hipGetErrorString(e));
+int launch_path(const Call& call, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
+                const std::vector<int32_t>& frames, const vsp_prosody_path_params& pp, float* f0_frames, const PathWs& w) {
+  if (const int rc = call.upload(w.frames, frames.data(), (size_t)B * sizeof(int32_t), "frames")) return rc;
   // kappa = 0.01 fs / hop, Praat's time-step correction, written so that it is exactly 1 where fs = 100 hop
   const double kappa = (double)PR_FS / (100.0 * (double)hop);
   PathArgs a;
   a.cand_f = cand_f; a.cand_s = cand_s;
-  a.frames = reinterpret_cast<const int32_t*>(ws + lay.frames);
-  a.bp = reinterpret_cast<uint8_t*>(ws + lay.bp);
+  a.frames = w.frames;
+  a.bp = w.bp;
   a.f0 = f0_frames; a.F_max = F_max;
   a.c_oct = (float)((double)pp.octave_jump_cost * kappa);
   a.c_vuv = (float)((double)pp.voiced_unvoiced_cost * kappa);
-  hipLaunchKernelGGL(path_kernel, dim3(B), dim3(64), 0, s, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "path_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(path_kernel, dim3(B), dim3(64), 0, call.s, a);
+  return call.launched("path_kernel");
 }
 
 }  // namespace
@@ -716,18 +694,23 @@ int64_t vsp_prosody_workspace_bytes(int B, int64_t L_max, int hop, int Tp, const
   if (B < 1 || B > PR_MAX_B || Tp < 0 || make_plan(params, pl)) return VSP_ERR_ARG;
   const int F_max = vsp_prosody_frames(L_max, hop);
   if (F_max < 0) return VSP_ERR_ARG;
-  return (int64_t)std::max(contour_ws(B, pl).end, phoneme_ws(B, F_max, std::max(Tp, 1)).end);
+  Ws contour = vsp::dry_ws(), phoneme = vsp::dry_ws();
+  carve_contour(contour, B, pl);
+  carve_phoneme(phoneme, B, F_max, std::max(Tp, 1));
+  return (int64_t)std::max(contour.cur, phoneme.cur);
 }
 
 // The contour call of all three entry points; `who` names the one in every message.  n_voiced = 0: the per-frame decision
 // into f0_frames (vsp_prosody_contours).  n_voiced >= 1: the candidate tables instead -- the caller's (cand_f, cand_s), or,
-// where both are NULL, the workspace's, for the path that follows (vsp_prosody_contours_path: f0_frames is the path's
-// output and is not touched here; the workspace must then hold that call's whole layout).
-static int contours_impl(const char* who, vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio,
-                         int64_t audio_stride, const int64_t* n_samples_host, const vsp_prosody_params* params, int n_voiced,
-                         float* f0_frames, float* cand_f, float* cand_s, float* energy_frames, int64_t* frames, void* workspace,
-                         int64_t workspace_bytes) {
-  const bool own_tables = n_voiced > 0 && !cand_f && !cand_s;
+// with `fused`, the workspace's, for the path that follows (vsp_prosody_contours_path: f0_frames is the path's output and
+// is not touched here; the workspace must then hold that call's whole layout, which comes back in *fused).
+static int contours_impl(const Call& call, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
+                         const int64_t* n_samples_host, const vsp_prosody_params* params, int n_voiced, float* f0_frames, float* cand_f,
+                         float* cand_s, float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes,
+                         ContourPathWs* fused = nullptr) {
+  vsp_ctx* const ctx = call.ctx;
+  const char* const who = call.who;
+  const bool own_tables = fused != nullptr;
   Plan pl;
   if (const int bad = make_plan(params, pl)) {
     if (bad == 1) return ctx->fail(VSP_ERR_ARG, "%s: the pitch floor must be at least 40 Hz (the analysis window must fit in LDS)", who);
@@ -745,10 +728,10 @@ static int contours_impl(const char* who, vsp_ctx* ctx, void* stream, int B, int
   if (!audio || (!f0_frames && (n_voiced == 0 || own_tables)) || (n_voiced > 0 && !own_tables && (!cand_f || !cand_s)) ||
       !energy_frames || !frames || audio_stride < L_max)
     return ctx->fail(VSP_ERR_ARG, "%s: null pointer, or audio_stride < L_max", who);
-  const ContourWs lay = contour_ws(B, pl);
-  const size_t need = own_tables ? contour_path_ws(B, F_max, pl).end : lay.end;
-  if (!workspace || workspace_bytes < (int64_t)need)
-    return ctx->fail(VSP_ERR_WORKSPACE, "%s: the workspace needs %lld bytes", who, (long long)need);
+  Ws ws = call.open(workspace, workspace_bytes);
+  if (own_tables) *fused = carve_contour_path(ws, B, F_max, pl);
+  const ContourWs w = own_tables ? fused->contour : carve_contour(ws, B, pl);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
   const int span4 = (pl.W + (PR_FPB - 1) * hop + 3) & ~3;
   // the lag buffers share the raw span's floats where they fit (48 KiB per block at the defaults: three blocks per CU)
   const int rbuf_floats = PR_FPB * (PR_LAGS_PER_WAVE * pl.LB + 4);
@@ -757,35 +740,27 @@ static int contours_impl(const char* who, vsp_ctx* ctx, void* stream, int B, int
   const size_t lds = ((size_t)span4 + (size_t)PR_FPB * pl.NA + (rbuf_over_span ? 0 : (size_t)rbuf_floats)) * sizeof(float);
   if (lds > 160 * 1024) return ctx->fail(VSP_ERR_UNSUPPORTED, "%s: %zu bytes of LDS", who, lds);
 
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  // The uploads here and in vsp_prosody_phonemes read PAGEABLE host memory -- the caller's array, the process-wide table
-  // whose lock is dropped right after the call, a local vector -- and rest on the runtime reading such memory into its own
-  // staging buffer before hipMemcpyAsync returns (as api_frame.hip does for the noise seeds and the row controls).  That
-  // blocks the host for the copy, and it is why these calls cannot be captured into a graph.
-  hipError_t e = hipMemcpyAsync(ws + lay.n_samples, n_samples_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    std::lock_guard<std::mutex> lock(g_tables_mu);
+  const hipStream_t s = call.s;
+  if (const int rc = call.upload(w.n_samples, n_samples_host, (size_t)B * sizeof(int64_t), "tables")) return rc;
+  {
+    std::lock_guard<std::mutex> lock(g_tables_mu);      // (dropped right after the call: the runtime has staged the table by then)
     Tables& t = g_tables;
     if (t.W != pl.W || t.t0 != pl.t0 || t.LB != pl.LB || t.tmin != pl.tmin || t.tmax != pl.tmax) build_tables(pl, t);
-    e = hipMemcpyAsync(ws + lay.tables, t.host.data(), t.host.size() * sizeof(float), hipMemcpyHostToDevice, s);
+    if (const int rc = call.upload(w.tables, t.host.data(), t.host.size() * sizeof(float), "tables")) return rc;
   }
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "%s (tables): %s", who, hipGetErrorString(e));
-  const int64_t* n_dev = reinterpret_cast<const int64_t*>(ws + lay.n_samples);
-  RowStat* stat = reinterpret_cast<RowStat*>(ws + lay.stat);
-  const float* tab = reinterpret_cast<const float*>(ws + lay.tables);
-  hipLaunchKernelGGL(row_peak_kernel, dim3(B), dim3(1024), 0, s, audio, audio_stride, n_dev, stat);
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "row_peak_kernel: %s", hipGetErrorString(e));
+  const float* tab = w.tables;
+  hipLaunchKernelGGL(row_peak_kernel, dim3(B), dim3(1024), 0, s, audio, audio_stride, w.n_samples, w.stat);
+  if (const int rc = call.launched("row_peak_kernel")) return rc;
   if (lds > 64 * 1024) {
     // (the size follows the caller's floor and hop; the attribute is set ONCE per device and instantiation, so it is the cap
     // checked above, the largest request the kernel can get -- a later call with a lower floor must not find a smaller one)
-    e = n_voiced > 0 ? vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel<true>), 160 * 1024, g_candidate_lds_done)
+    const hipError_t e =
+        n_voiced > 0 ? vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel<true>), 160 * 1024, g_candidate_lds_done)
                      : vsp::set_max_dynamic_lds(reinterpret_cast<const void*>(contour_kernel<false>), 160 * 1024, g_contour_lds_done);
     if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel (LDS): %s", hipGetErrorString(e));
   }
   ContourArgs a;
-  a.audio = audio; a.a_bs = audio_stride; a.n_samples = n_dev; a.stat = stat;
+  a.audio = audio; a.a_bs = audio_stride; a.n_samples = w.n_samples; a.stat = w.stat;
   a.hann = tab; a.win = tab + PR_NFFT; a.inv_rw = tab + PR_NFFT + pl.W4;
   a.f0 = f0_frames; a.energy = energy_frames; a.frames = frames;
   a.F_max = F_max; a.hop = hop;
@@ -793,25 +768,19 @@ static int contours_impl(const char* who, vsp_ctx* ctx, void* stream, int B, int
   a.fs = (float)PR_FS; a.floor_hz = pl.p.floor_hz; a.vt = pl.p.voicing_threshold;
   a.st_scale = pl.p.silence_threshold / (1.f + pl.p.voicing_threshold); a.oc = pl.p.octave_cost;
   a.cand_f = cand_f; a.cand_s = cand_s; a.n_voiced = n_voiced;
-  if (own_tables) {
-    const ContourPathWs cp = contour_path_ws(B, F_max, pl);
-    a.cand_f = reinterpret_cast<float*>(ws + cp.cand_f);
-    a.cand_s = reinterpret_cast<float*>(ws + cp.cand_s);
-  }
+  if (own_tables) { a.cand_f = fused->cand_f; a.cand_s = fused->cand_s; }
   const dim3 grid((F_max + PR_FPB - 1) / PR_FPB, B), block(64 * PR_FPB);
   if (n_voiced > 0) hipLaunchKernelGGL(contour_kernel<true>, grid, block, lds, s, a);
   else hipLaunchKernelGGL(contour_kernel<false>, grid, block, lds, s, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "contour_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  return call.launched("contour_kernel");
 }
 
 int vsp_prosody_contours(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
                          const int64_t* n_samples_host, const vsp_prosody_params* params, float* f0_frames,
                          float* energy_frames, int64_t* frames, void* workspace, int64_t workspace_bytes) {
   if (!ctx) return VSP_ERR_ARG;
-  return contours_impl("vsp_prosody_contours", ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params, 0, f0_frames,
-                       nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes);
+  return contours_impl(Call{ctx, "vsp_prosody_contours", (hipStream_t)stream}, B, L_max, hop, audio, audio_stride, n_samples_host, params,
+                       0, f0_frames, nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes);
 }
 
 int64_t vsp_prosody_path_workspace_bytes(int B, int64_t L_max, int hop, const vsp_prosody_params* params,
@@ -821,7 +790,9 @@ int64_t vsp_prosody_path_workspace_bytes(int B, int64_t L_max, int hop, const vs
   if (B < 1 || B > PR_MAX_B || make_plan(params, pl) || check_path(path, pp)) return VSP_ERR_ARG;
   const int F_max = vsp_prosody_frames(L_max, hop);
   if (F_max < 0) return VSP_ERR_ARG;
-  return (int64_t)contour_path_ws(B, F_max, pl).end;      // (the candidate call and the path alone each need a part of it)
+  Ws ws = vsp::dry_ws();
+  carve_contour_path(ws, B, F_max, pl);                   // (the candidate call and the path alone each need a part of it)
+  return (int64_t)ws.cur;
 }
 
 int vsp_prosody_candidates(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
@@ -830,8 +801,8 @@ int vsp_prosody_candidates(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int
   if (!ctx) return VSP_ERR_ARG;
   if (max_candidates < 2 || max_candidates > VSP_PROSODY_MAX_CANDIDATES) return refuse_path(ctx, "vsp_prosody_candidates", 2);
   if (!cand_f || !cand_s) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_candidates: null pointer, or audio_stride < L_max");
-  return contours_impl("vsp_prosody_candidates", ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params,
-                       max_candidates - 1, nullptr, cand_f, cand_s, energy_frames, frames, workspace, workspace_bytes);
+  return contours_impl(Call{ctx, "vsp_prosody_candidates", (hipStream_t)stream}, B, L_max, hop, audio, audio_stride, n_samples_host,
+                       params, max_candidates - 1, nullptr, cand_f, cand_s, energy_frames, frames, workspace, workspace_bytes);
 }
 
 int vsp_prosody_path(vsp_ctx* ctx, void* stream, int B, int F_max, int hop, const float* cand_f, const float* cand_s,
@@ -850,11 +821,11 @@ int vsp_prosody_path(vsp_ctx* ctx, void* stream, int B, int F_max, int hop, cons
     fr[b] = (int32_t)frames_host[b];
   }
   if (!cand_f || !cand_s || !f0_frames) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_path: null pointer");
-  const PathWs lay = path_ws(B, F_max);
-  if (!workspace || workspace_bytes < (int64_t)lay.end)
-    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_path: the workspace needs %lld bytes", (long long)lay.end);
-  return launch_path(ctx, "vsp_prosody_path", (hipStream_t)stream, B, F_max, hop, cand_f, cand_s, fr, pp, f0_frames,
-                     static_cast<char*>(workspace));
+  const Call call{ctx, "vsp_prosody_path", (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  const PathWs w = carve_path(ws, B, F_max);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  return launch_path(call, B, F_max, hop, cand_f, cand_s, fr, pp, f0_frames, w);
 }
 
 int vsp_prosody_contours_path(vsp_ctx* ctx, void* stream, int B, int64_t L_max, int hop, const float* audio, int64_t audio_stride,
@@ -865,18 +836,14 @@ int vsp_prosody_contours_path(vsp_ctx* ctx, void* stream, int B, int64_t L_max, 
   vsp_prosody_path_params pp;
   if (const int bad = check_path(path, pp)) return refuse_path(ctx, who, bad);
   // (everything else is refused in there, before its first launch: the rows, the pointers, the whole layout's size)
-  const int rc = contours_impl(who, ctx, stream, B, L_max, hop, audio, audio_stride, n_samples_host, params, pp.max_candidates - 1,
-                               f0_frames, nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes);
+  const Call call{ctx, who, (hipStream_t)stream};
+  ContourPathWs w;
+  const int rc = contours_impl(call, B, L_max, hop, audio, audio_stride, n_samples_host, params, pp.max_candidates - 1, f0_frames,
+                               nullptr, nullptr, energy_frames, frames, workspace, workspace_bytes, &w);
   if (rc != VSP_OK) return rc;
-  Plan pl;
-  make_plan(params, pl);
-  const int F_max = vsp_prosody_frames(L_max, hop);
-  const ContourPathWs cp = contour_path_ws(B, F_max, pl);
   std::vector<int32_t> fr(B);
   for (int b = 0; b < B; ++b) fr[b] = (int32_t)(n_samples_host[b] / hop) + 1;
-  char* ws = static_cast<char*>(workspace);
-  return launch_path(ctx, who, (hipStream_t)stream, B, F_max, hop, reinterpret_cast<const float*>(ws + cp.cand_f),
-                     reinterpret_cast<const float*>(ws + cp.cand_s), fr, pp, f0_frames, ws + cp.path);
+  return launch_path(call, B, vsp_prosody_frames(L_max, hop), hop, w.cand_f, w.cand_s, fr, pp, f0_frames, w.path);
 }
 
 int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, const float* f0_frames, const float* energy_frames,
@@ -908,24 +875,20 @@ int vsp_prosody_phonemes(vsp_ctx* ctx, void* stream, int B, int F_max, int Tp, c
     len[b] = (int32_t)lengths_host[b];
   }
   if (!f0_frames || !energy_frames || !f0 || !energy) return ctx->fail(VSP_ERR_ARG, "vsp_prosody_phonemes: null pointer");
-  const PhonemeWs lay = phoneme_ws(B, F_max, Tp);
-  if (!workspace || workspace_bytes < (int64_t)lay.end)
-    return ctx->fail(VSP_ERR_WORKSPACE, "vsp_prosody_phonemes: the workspace needs %lld bytes", (long long)lay.end);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  hipError_t e = hipMemcpyAsync(ws + lay.ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "vsp_prosody_phonemes (durations): %s", hipGetErrorString(e));
+  const Call call{ctx, "vsp_prosody_phonemes", (hipStream_t)stream};
+  Ws ws = call.open(workspace, workspace_bytes);
+  const PhonemeWs w = carve_phoneme(ws, B, F_max, Tp);
+  if (const int rc = call.need_ws(workspace, workspace_bytes, ws.cur)) return rc;
+  if (const int rc = call.upload(w.ints, ints.data(), ints.size() * sizeof(int32_t), "durations")) return rc;
   PhonemeArgs a;
   a.f0_frames = f0_frames; a.energy_frames = energy_frames;
-  a.start = reinterpret_cast<const int32_t*>(ws + lay.ints);
+  a.start = w.ints;
   a.dur = a.start + (size_t)B * Tp;
   a.frames = a.dur + (size_t)B * Tp;
   a.lengths = a.frames + B;
-  a.interp = reinterpret_cast<float*>(ws + lay.interp);
-  a.prev = reinterpret_cast<int32_t*>(ws + lay.prev);
+  a.interp = w.interp;
+  a.prev = w.prev;
   a.f0 = f0; a.energy = energy; a.F_max = F_max; a.Tp = Tp;
-  hipLaunchKernelGGL(phoneme_kernel, dim3(B), dim3(64), 0, s, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return ctx->fail(VSP_ERR_HIP, "phoneme_kernel: %s", hipGetErrorString(e));
-  return VSP_OK;
+  hipLaunchKernelGGL(phoneme_kernel, dim3(B), dim3(64), 0, call.s, a);
+  return call.launched("phoneme_kernel");
 }

@@ -26,6 +26,26 @@ def _dev_i64(t, device) -> torch.Tensor:
     return torch.as_tensor(t).to(device=device, dtype=torch.int64).contiguous()
 
 
+def _host_list(v, conv=int, n=None, name=None):
+    """``v`` (a tensor, an array or any sequence) as a list on the host, every entry through ``conv``; with ``n`` a
+    ``ValueError`` naming ``name`` unless it has ``n`` entries."""
+    out = [conv(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+    if n is not None and len(out) != n:
+        raise ValueError(f"{name} must be a scalar or have {n} entries")
+    return out
+
+
+def _nan_float(x) -> float:
+    return float("nan") if x is None else float(x)
+
+
+def _column(v, B: int, name: str, conv=_nan_float):
+    """One value per row: a scalar (or None) for every row, or ``B`` values."""
+    if v is None or np.ndim(v) == 0:
+        return [conv(v)] * B
+    return _host_list(v, conv, B, name)
+
+
 class OutputHistory:
     """What a streamed request keeps between two ``Engine.generator_stream_rows_output`` calls: a [2, K] float32 device
     tensor -- the input samples the next outputs still need, K = ``vsp_output_history_samples`` -- and which side is
@@ -606,7 +626,7 @@ class Engine:
         if a.dim() != 2:
             raise ValueError("audio must be [B, L] (rows padded to a common length)")
         B, stride = a.shape
-        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         if len(n_host) != B:
             raise ValueError(f"n_samples must have {B} entries")
         if any(x < 0 or x > stride for x in n_host):
@@ -1109,7 +1129,7 @@ class Engine:
             raise ValueError("o must be a float32 [B, 1, n] or [B, n] tensor with contiguous rows")
         B, n = x.shape
         lens = [n] * B if sample_lengths is None else \
-            [int(v) for v in (sample_lengths.tolist() if hasattr(sample_lengths, "tolist") else sample_lengths)]
+            _host_list(sample_lengths)
         formats = list(formats)
         if len(lens) != B or len(formats) != B or any(v < 0 or v > n for v in lens):
             raise ValueError(f"sample_lengths and formats must have {B} entries, 0 <= sample_lengths[b] <= {n}")
@@ -1220,7 +1240,7 @@ class Engine:
         if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
             raise ValueError("raw must be [B, stride] with contiguous rows")
         B, stride = a.shape
-        n_host = [int(x) for x in (n_in.tolist() if hasattr(n_in, "tolist") else n_in)]
+        n_host = _host_list(n_in)
         if len(n_host) != B or any(x < 0 or x > stride for x in n_host):
             raise ValueError(f"n_in must have {B} entries with 0 <= n_in[b] <= raw.shape[1]")
         n_out = [input_stage.out_len(x, L, M) for x in n_host]
@@ -1292,7 +1312,7 @@ class Engine:
         if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
             raise ValueError("audio must be [B, L] (rows padded to a common length, contiguous)")
         B, stride = a.shape[0], (a.stride(0) if a.shape[0] > 1 else a.shape[1])
-        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         if len(n_host) != B or B == 0:
             raise ValueError(f"n_samples must have {B} entries (at least one row)")
         hop = self._hop(hop_length)
@@ -1382,7 +1402,7 @@ class Engine:
         if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
             raise ValueError("audio must be [B, L] (rows padded to a common length, contiguous)")
         B, stride = a.shape[0], (a.stride(0) if a.shape[0] > 1 else a.shape[1])
-        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         if len(n_host) != B or B == 0:
             raise ValueError(f"n_samples must have {B} entries (at least one row)")
         hop = self._hop(hop_length)
@@ -1425,7 +1445,7 @@ class Engine:
         if not np.array_equal(di, d):
             raise ValueError("durations must be whole numbers of frames")
         Tp = di.shape[1]
-        ln = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        ln = _host_list(lengths)
         fh = [int(x) for x in frames_host]
         if len(ln) != B or len(fh) != B or Tp < 1:
             raise ValueError(f"lengths and frames_host must have {B} entries, durations at least one column")
@@ -1502,7 +1522,7 @@ class Engine:
         """``cum_dur`` [B, Tp] and ``lengths`` [B] on the HOST (a device tensor is copied back)."""
         c = cum_dur.detach().cpu().numpy() if torch.is_tensor(cum_dur) else np.asarray(cum_dur)
         c = np.ascontiguousarray(c.reshape(B, -1), dtype=np.int32)
-        ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        ln = _host_list(lengths)
         if len(ln) != B or c.shape[1] < 1:
             raise ValueError(f"lengths must have {B} entries, cum_dur at least one column")
         return c, ln
@@ -1598,7 +1618,7 @@ class Engine:
         ``durations`` [B, Tp] int64 on the device."""
         from types import SimpleNamespace
         pp = self._align_params(params)
-        n_host = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         frames = [self.convert_frames(n) for n in n_host]
         for b, T in enumerate(frames):
             if T < 1:
@@ -1629,14 +1649,8 @@ class Engine:
     def loudness_params(B: int, target_lufs=-23.0, peak_ceiling=1.0, max_gain_db=30.0):
         """``vsp_loudness_params`` [B] from three values, each a scalar or one value per row.  A row's ``target_lufs`` may be
         None or NaN: the row is left alone.  Refused here as the library refuses them (a ``ValueError`` naming the row)."""
-        def col(v, name):
-            if v is None or np.ndim(v) == 0:
-                return [float("nan") if v is None else float(v)] * B
-            v = [float("nan") if x is None else float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
-            if len(v) != B:
-                raise ValueError(f"loudness: {name} must be a scalar or have {B} entries")
-            return v
-        t, c, m = col(target_lufs, "target_lufs"), col(peak_ceiling, "peak_ceiling"), col(max_gain_db, "max_gain_db")
+        t, c, m = (_column(v, B, f"loudness: {n}") for v, n in ((target_lufs, "target_lufs"), (peak_ceiling, "peak_ceiling"),
+                                                                 (max_gain_db, "max_gain_db")))
         out = (_lib.VspLoudnessParams * B)()
         for b in range(B):
             if not c[b] > 0.0:
@@ -1655,7 +1669,7 @@ class Engine:
             raise ValueError(f"{what} must be [B, L] (rows padded to a common length, each contiguous)")
         B = a.shape[0]
         stride = a.stride(0) if B > 1 else a.shape[1]
-        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         if len(n_host) != B or B == 0:
             raise ValueError(f"n_samples must have {B} entries (at least one row)")
         if stride < a.shape[1]:
@@ -1694,7 +1708,7 @@ class Engine:
         if t.dim() != 2 or t.shape[1] < 1:
             raise ValueError("seg must be [B, S_max]")
         B, S_max = t.shape
-        n_host = [int(x) for x in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         fs = int(sample_rate)
         if len(n_host) != B or B == 0:
             raise ValueError(f"n_samples must have {B} entries (at least one row)")
@@ -1770,14 +1784,7 @@ class Engine:
     def loudness_level_params(B: int, target_lufs=-23.0, max_gain_db=12.0, max_cut_db=12.0, slew_db_per_s=3.0, initial_gain_db=0.0):
         """``vsp_loudness_level_params`` [B] from five values, each a scalar or one value per row.  A row's ``target_lufs`` may
         be None or NaN: the leveller leaves the row alone.  Refused here as the library refuses them, naming the row."""
-        def col(v, name):
-            if v is None or np.ndim(v) == 0:
-                return [float("nan") if v is None else float(v)] * B
-            v = [float("nan") if x is None else float(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
-            if len(v) != B:
-                raise ValueError(f"loudness: {name} must be a scalar or have {B} entries")
-            return v
-        cols = [col(v, n) for v, n in ((target_lufs, "target_lufs"), (max_gain_db, "max_gain_db"), (max_cut_db, "max_cut_db"),
+        cols = [_column(v, B, f"loudness: {n}") for v, n in ((target_lufs, "target_lufs"), (max_gain_db, "max_gain_db"), (max_cut_db, "max_cut_db"),
                                        (slew_db_per_s, "slew_db_per_s"), (initial_gain_db, "initial_gain_db"))]
         out = (_lib.VspLoudnessLevelParams * B)()
         for b in range(B):
@@ -1806,10 +1813,7 @@ class Engine:
 
     @staticmethod
     def _ints(v, B: int, what: str):
-        v = [int(v)] * B if np.ndim(v) == 0 else [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
-        if len(v) != B:
-            raise ValueError(f"{what} must be a scalar or have {B} entries")
-        return v
+        return [int(v)] * B if np.ndim(v) == 0 else _host_list(v, int, B, what)
 
     def _level_params(self, params, B: int):
         """``params`` as ``loudness_level_params`` made them, or B mappings of the five fields (a missing one: its default)."""
@@ -1833,8 +1837,28 @@ class Engine:
         dt = {"float64": torch.float64, "float32": torch.float32, "int32": torch.int32}[np.dtype(dtype).name]
         return torch.full((int(n),), -1 if dt == torch.int32 else float("nan"), dtype=dt, device=self.device)
 
+    def _tables(self, B: int, T: int, floats: int, ints: int = 0):
+        """New ``[B, T]`` tables on the device: ``floats`` float32 ones of NaN, then ``ints`` int32 ones of -1."""
+        return tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(floats)) + \
+            tuple(torch.full((B, T), -1, dtype=torch.int32, device=self.device) for _ in range(ints))
+
     def _time_ws(self, B: int):
         return self._workspace("loudness", self.lib.vsp_loudness_time_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
+
+    def _time_rows(self, segs, first, count, tables):
+        """What ``loudness_time`` and ``loudness_time_hist`` hand the library: ``(desc, M, S, I, kept)`` -- the rows'
+        ``VspLoudnessRow`` over their segment tables ``segs`` and ``tables`` (None: new ones, to the last entry asked for)."""
+        B = len(segs)
+        if tables is None:
+            tables = self._tables(B, max(1, max(f + c for f, c in zip(first, count))), 3, 1)
+        M, S, I, kept = tables
+        rows = [self._own_rows(t, torch.float32, n, B) for t, n in ((M, "M"), (S, "S"), (I, "I"))] + [self._own_rows(kept, torch.int32, "kept", B)]
+        desc = (_lib.VspLoudnessRow * B)()
+        for b in range(B):
+            entries = min([segs[b].numel()] + [r[b].numel() for r in rows])
+            desc[b] = _lib.VspLoudnessRow(seg=segs[b].data_ptr(), M=rows[0][b].data_ptr(), S=rows[1][b].data_ptr(), I=rows[2][b].data_ptr(),
+                                          kept=rows[3][b].data_ptr(), first=first[b], count=count[b], entries=entries)
+        return desc, M, S, I, kept
 
     def loudness_segments_from(self, audio, n_samples, sample_rate: int, state=None, first=None):
         """``vsp_loudness_segments_from``: ``loudness_segments`` of the pieces ``audio[b, :n_samples[b]]`` of B streams, each
@@ -1871,17 +1895,7 @@ class Engine:
         if B == 0:
             raise ValueError("loudness_time: at least one row")
         first, count = self._ints(first, B, "first"), self._ints(count, B, "count")
-        if tables is None:
-            T = max(1, max(f + c for f, c in zip(first, count)))
-            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(3)) + \
-                (torch.full((B, T), -1, dtype=torch.int32, device=self.device),)
-        M, S, I, kept = tables
-        rows = [self._own_rows(t, torch.float32, n, B) for t, n in ((M, "M"), (S, "S"), (I, "I"))] + [self._own_rows(kept, torch.int32, "kept", B)]
-        desc = (_lib.VspLoudnessRow * B)()
-        for b in range(B):
-            entries = min([segs[b].numel()] + [r[b].numel() for r in rows])
-            desc[b] = _lib.VspLoudnessRow(seg=segs[b].data_ptr(), M=rows[0][b].data_ptr(), S=rows[1][b].data_ptr(), I=rows[2][b].data_ptr(),
-                                          kept=rows[3][b].data_ptr(), first=first[b], count=count[b], entries=entries)
+        desc, M, S, I, kept = self._time_rows(segs, first, count, tables)
         m_max, s_max = self._f(B), self._f(B)
         ws = self._time_ws(B)
         with torch.cuda.device(self.device):
@@ -1901,8 +1915,7 @@ class Engine:
         params = self._level_params(params, B)
         first, count = self._ints(first, B, "first"), self._ints(count, B, "count")
         if tables is None:
-            T = max(1, max(f + c for f, c in zip(first, count)))
-            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(2))
+            tables = self._tables(B, max(1, max(f + c for f, c in zip(first, count))), 2)
         c_db, c = tables
         dbs, cs = self._own_rows(c_db, torch.float32, "c_db", B), self._own_rows(c, torch.float32, "c", B)
         desc = (_lib.VspLoudnessRow * B)()
@@ -1960,11 +1973,9 @@ class Engine:
                 raise ValueError("out must be a float32 tensor on the engine's device")
         L_max = max(n_host)
         T = max(1, L_max // ((fs + 5) // 10))
-        tab = lambda: torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device)
-        r = dict(M=tab(), S=tab(), I=tab(), kept=torch.full((B, T), -1, dtype=torch.int32, device=self.device), m_max=self._f(B),
-                 s_max=self._f(B), i_end=self._f(B), peak=self._f(B))
+        r = dict(zip(("M", "S", "I", "kept"), self._tables(B, T, 3, 1)), m_max=self._f(B), s_max=self._f(B), i_end=self._f(B), peak=self._f(B))
         if params is not None:
-            r.update(c_db=tab(), c=tab(), out=o)
+            r.update(zip(("c_db", "c"), self._tables(B, T, 2)), out=o)
         ws = self._workspace("loudness", self.lib.vsp_loudness_time_workspace_bytes(B, L_max, fs))
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_loudness_level(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, _ptr(o), o_stride or 0,
@@ -2004,17 +2015,7 @@ class Engine:
             if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device == self.device and t.is_contiguous()
                     and tuple(t.shape) == (2, _lib.LOUDNESS_HIST_BINS)):
                 raise ValueError(f"hist: row {b} must be a contiguous [2, {_lib.LOUDNESS_HIST_BINS}] int32 tensor on the engine's device")
-        if tables is None:
-            T = max(1, max(f + c for f, c in zip(first, count)))
-            tables = tuple(torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device) for _ in range(3)) + \
-                (torch.full((B, T), -1, dtype=torch.int32, device=self.device),)
-        M, S, I, kept = tables
-        rows = [self._own_rows(t, torch.float32, n, B) for t, n in ((M, "M"), (S, "S"), (I, "I"))] + [self._own_rows(kept, torch.int32, "kept", B)]
-        desc = (_lib.VspLoudnessRow * B)()
-        for b in range(B):
-            entries = min([segs[b].numel()] + [r[b].numel() for r in rows])
-            desc[b] = _lib.VspLoudnessRow(seg=segs[b].data_ptr(), M=rows[0][b].data_ptr(), S=rows[1][b].data_ptr(), I=rows[2][b].data_ptr(),
-                                          kept=rows[3][b].data_ptr(), first=first[b], count=count[b], entries=entries)
+        desc, M, S, I, kept = self._time_rows(segs, first, count, tables)
         m_max, s_max, lra = self._f(B), self._f(B), self._f(B)
         ws = self._workspace("loudness", self.lib.vsp_loudness_hist_workspace_bytes(B, 1, _lib.LOUDNESS_FS_MIN))
         with torch.cuda.device(self.device):
@@ -2030,8 +2031,7 @@ class Engine:
         a, B, stride, n_host, fs = self._loudness_rows(audio, n_samples, sample_rate)
         L_max = max(n_host)
         T = max(1, L_max // ((fs + 5) // 10))
-        tab = lambda: torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device)
-        r = dict(lra=self._f(B), i_hist=self._f(B), M=tab(), S=tab(), I=tab(), kept=torch.full((B, T), -1, dtype=torch.int32, device=self.device))
+        r = dict(lra=self._f(B), i_hist=self._f(B), **dict(zip(("M", "S", "I", "kept"), self._tables(B, T, 3, 1))))
         ws = self._workspace("loudness", self.lib.vsp_loudness_hist_workspace_bytes(B, L_max, fs))
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_loudness_range(self.ctx, self._stream(), B, L_max, fs, _ptr(a), stride, (C.c_int64 * B)(*n_host), _ptr(r["lra"]),
@@ -2106,12 +2106,7 @@ class Engine:
         o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
         if out is not None and o is not out:
             raise ValueError("out must be a float32 tensor on the engine's device")
-        if ceiling is None or np.ndim(ceiling) == 0:
-            c = [float("nan") if ceiling is None else float(ceiling)] * B
-        else:
-            c = [float("nan") if v is None else float(v) for v in (ceiling.tolist() if hasattr(ceiling, "tolist") else ceiling)]
-            if len(c) != B:
-                raise ValueError(f"limiter: ceiling must be a scalar or have {B} entries")
+        c = _column(ceiling, B, "limiter: ceiling")
         A, H = int(attack), int(hold)
         desc = (_lib.VspLimiterRow * B)()
         for b, n in enumerate(n_host):
@@ -2193,7 +2188,7 @@ class Engine:
         to audio [B, max(n_samples)] by weighted overlap-add; row b's first ``n_samples[b]`` samples are written, the rest
         is 0."""
         x = _dev_f32(ri, self.device)
-        n_host = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        n_host = _host_list(n_samples)
         B, L_max = len(n_host), max(n_host)
         ws = self._denoise_ws(B, L_max, "istft")
         T = self.convert_frames(L_max, self.dims.total_upsample)
@@ -2215,12 +2210,7 @@ class Engine:
         o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
         if out is not None and o is not out:
             raise ValueError("out must be a float32 tensor on the engine's device")
-        if strength is None or np.ndim(strength) == 0:
-            s = [float("nan") if strength is None else float(strength)] * B
-        else:
-            s = [float("nan") if v is None else float(v) for v in (strength.tolist() if hasattr(strength, "tolist") else strength)]
-            if len(s) != B:
-                raise ValueError(f"denoise: strength must be a scalar or have {B} entries")
+        s = _column(strength, B, "denoise: strength")
         bp = None
         if bias is not None:
             bp = _dev_f32(bias, self.device)
