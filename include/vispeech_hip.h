@@ -1427,6 +1427,54 @@ int vsp_denoise(vsp_ctx* ctx, void* stream, int B, int L_max, const float* audio
                 const int64_t* n_samples_host, const float* bias, const float* strength_host, float* out, int64_t out_stride,
                 void* workspace, int64_t workspace_bytes);
 
+/* ---- denoiser for streams (round 26, ABI 7, additive) ---------------- */
+/* The denoiser above over rows that are each a piece of a stream at its own position: a stream cut anywhere gives the bits
+ * of vsp_denoise on the finished recording.  The operator has no recurrence.  With R = N / hop:
+ *   frame t reads the samples [t hop - pad, t hop - pad + N), reflected at sample 0 always and at the stream's end `total`
+ *   only once that end is known and reached;
+ *   output j sits at padded position p = j + pad and sums the frames floor(p / hop) - (R - 1) .. floor(p / hop), clipped to
+ *   [0, T(total)): it depends on the samples j - (N - 1) .. j + N - 1 and on nothing else;
+ *   with n samples of an open stream, the frames t with t hop - pad + N <= n -- Tc(n) of them -- are frames of the finished
+ *   recording whatever its length, and the outputs [0, E(n)), E(n) = max(0, Tc(n) hop - pad), are final: a delay n - E(n)
+ *   between N - hop and N - 1 samples (1536 .. 2047 for the default model: 35 .. 46 ms at 44.1 kHz);
+ *   to go on from output E(n) a stream keeps its samples from E(n) - (N - hop) on.
+ * The call is stateless: it frames, transforms, subtracts and overlap-adds the window of frames its outputs need -- up to
+ * R - 1 frames a row that an earlier call computed too -- and carries nothing between calls.  The two DFT products run on
+ * the form vsp_denoise uses, whose column does not depend on where in the operand it sits; each output's sum is one chain
+ * from 0 in ascending t, as there. */
+typedef struct vsp_denoise_row {
+  const float* in;      /* device: the stream's samples [first, first + count) */
+  int64_t first, count;
+  float* out;           /* device: receives the outputs [out_first, out_first + out_count); may alias `in` at the same positions */
+  int64_t out_first, out_count;
+  int64_t total;        /* the stream's length, or -1 while its end is unknown */
+  float strength;       /* >= 0; NaN: the row is neither read nor written */
+} vsp_denoise_row;
+/* *behind = N - hop, *ahead = N - 1: the samples before an output and after it that can reach it.  Host only; VSP_ERR_ARG for
+ * a context without the denoiser's geometry. */
+int vsp_denoise_history(const vsp_ctx* ctx, int64_t* behind, int64_t* ahead);
+/* E(n_seen) above, or n_seen for a closed stream: the outputs that are final.  Host arithmetic only -- the ONE rule that
+ * callers in any language share; VSP_ERR_ARG (negative) for n_seen < 0 or a context without the geometry. */
+int64_t vsp_denoise_complete(const vsp_ctx* ctx, int64_t n_seen, int closed);
+/* Workspace of vsp_denoise_rows for B rows of up to L_max OUTPUTS each: three int64 per row, then the frame operand, RI and
+ * the synthesis frames for windows of ceil((L_max - 1) / hop) + R columns (the dry pass of the call's own sequence).
+ * Monotone in both arguments; VSP_ERR_ARG as a negative size (1 <= B <= 64, 1 <= L_max <= 2^30). */
+int64_t vsp_denoise_rows_workspace_bytes(const vsp_ctx* ctx, int B, int64_t L_max);
+/* rows_host: HOST array [B], 1 <= B <= 64; bias: [B][spec] float32 on the device, row b's own.  Five launches -- the window
+ * framing of vsp_convert_stream_rows, the forward convolution, the subtraction, the inverse convolution, overlap-add -- whose
+ * row descriptors travel as kernel arguments: no upload, no allocation, no synchronisation.  The workspace must hold
+ * vsp_denoise_rows_workspace_bytes(ctx, B, the largest out_count).  Exactly out[0 .. out_count) of every live row is
+ * written; a row with out_count = 0 is not read.  VSP_ERR_ARG before any launch, naming the row, when
+ *   total is known and not above pad;
+ *   the row's samples start behind the first sample its frames read: at most `behind` before out_first (history is missing);
+ *   its frames read past first + count while the samples do not reach a known end (look-ahead is missing);
+ *   samples or outputs lie behind `total`, a position or count is negative or above 2^30, a pointer of a row that has
+ *   samples (outputs) is NULL, the strength is negative or infinite, bias is NULL with any finite strength;
+ * and for the geometries vsp_denoise refuses.  A whole utterance of n samples is first = out_first = 0, count = out_count =
+ * total = n, and has the bits of vsp_denoise. */
+int vsp_denoise_rows(vsp_ctx* ctx, void* stream, int B, const vsp_denoise_row* rows_host, const float* bias, void* workspace,
+                     int64_t workspace_bytes);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

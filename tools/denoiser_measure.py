@@ -11,7 +11,13 @@ one of an ``istft`` call; the three small kernels are what is left of the call, 
 ``istft``.  Per kernel: run the tool under ``rocprofv3 --kernel-trace --stats --output-format csv`` (the table under the
 tool's own lines in profiles/r25_denoiser.txt).  No gate is set on any of them.
 
-usage: tools/denoiser_measure.py [steps] [rounds] [out.txt]      (default out: profiles/r25_denoiser.txt)"""
+``--stream`` measures the denoiser for streams instead: one tick of 16 streams, each pushing a piece of
+64 frames through ``denoiser.push_rows`` (ONE ``vsp_denoise_rows`` call: 67 frames a row, 3 of them the overlap an earlier
+tick computed too), beside that tick's ``Engine.generator_stream_rows`` call and beside ``Engine.denoise`` on the same 16
+pieces as whole rows.  The streams run on (their pieces cycle over the 10 s rows), so every timed tick is a steady-state one.
+
+usage: tools/denoiser_measure.py [--stream] [steps] [rounds] [out.txt]
+       (default out: profiles/r25_denoiser.txt, with --stream profiles/r26_denoiser_stream.txt)"""
 import os
 import sys
 
@@ -27,10 +33,13 @@ from vispeech_amd.models import SynthesizerTrn          # noqa: E402
 from vispeech_amd.schema import dims_from_ctor          # noqa: E402
 from vispeech_amd.synth import synth_state_dict         # noqa: E402
 
-STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-OUT = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r25_denoiser.txt")
+STREAM = "--stream" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--stream"]
+STEPS = int(ARGS[0]) if len(ARGS) > 0 else 10
+ROUNDS = int(ARGS[1]) if len(ARGS) > 1 else 3
+OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "r26_denoiser_stream.txt" if STREAM else "r25_denoiser.txt")
 SECONDS, B = 10, 16
+CHUNK = 64                                             # frames of a piece: the streaming service's default chunk
 
 
 def timed(fn, steps):
@@ -81,6 +90,8 @@ def main():
     audio = eng.generator_ragged(Z, G, lengths)[:, 0, :].contiguous()          # the rows measured: the generator's own
     n_samples = [n] * B
     bias = net.denoiser_bias(sid)
+    if STREAM:
+        return stream_main(net, dims, audio, Z, G, bias, frames)
     T = eng.convert_frames(n, up)
     out = torch.empty_like(audio)
     ri = torch.zeros((B, 2 * spec, T), dtype=torch.float32, device="cuda:0")
@@ -116,6 +127,60 @@ def main():
               f"      the convolution of an istft call ({n_inv:.0f} launch)           {c_inv:8.3f} ms  ({flop / c_inv / 1e9:.1f} TFLOP/s; its operand is the "
               f"caller's dense RI, rows of {T} floats: not 16-byte aligned unless T_max is a multiple of 4)",
               f"      overlap-add (istft less its convolution)             {ist - c_inv:8.3f} ms"]
+    assert eng.status() == 0
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        f.write(text + "\n")
+
+
+def stream_main(net, dims, audio, Z, G, bias, frames):
+    from vispeech_amd import denoiser
+    eng, fs, up = net._engine, dims.sampling_rate, dims.total_upsample
+    N = 2 * (dims.spec_channels - 1)
+    piece = CHUNK * up
+    per_row = frames // CHUNK                              # whole pieces in a 10 s row
+    streams = [denoiser.Stream(eng, bias[b], 0.01) for b in range(B)]
+    state = {"k": 0, "out": 0}
+
+    def tick():
+        k = state["k"] % per_row
+        state["k"] += 1
+        outs = denoiser.push_rows(eng, [(streams[b], audio[b, k * piece:(k + 1) * piece], False) for b in range(B)])
+        state["out"] = sum(int(o.shape[0]) for o in outs)
+
+    f0 = frames // 2                                       # the generator's tick: every row mid-utterance
+    rows = [(Z[b], G[b], frames, f0, f0 + CHUNK) for b in range(B)]
+    whole = audio[:, :piece].contiguous()
+    out = torch.empty_like(whole)
+    jobs = {
+        "denoiser.push_rows (a tick)": tick,
+        "denoise (the pieces, whole)": lambda: eng.denoise(whole, [piece] * B, bias, 0.01, out=out),
+        "generator_stream_rows (a tick)": lambda: eng.generator_stream_rows(rows, CHUNK, pcm=False),
+    }
+    ms = {k: [] for k in jobs}
+    for _ in range(ROUNDS):
+        for k, fn in jobs.items():
+            ms[k].append(timed(fn, STEPS))
+    med = lambda k: float(np.median(ms[k]))
+    assert state["out"] == B * piece                       # steady state: a tick puts out what it takes in
+    T = CHUNK + N // up - 1
+    props = torch.cuda.get_device_properties(0)
+    lines = [f"denoiser for streams: a tick of {B} streams, each a piece of {CHUNK} frames ({piece} samples, {piece / fs * 1e3:.0f} ms at {fs} Hz); "
+             f"{ROUNDS} rounds, a window of {STEPS} calls",
+             f"device {torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', 'arch not available')}, "
+             f"{props.multi_processor_count} CUs)",
+             "timer: device events around a window of calls, per call (the calls include their host work: a tick's also the",
+             "       streams' buffers -- one torch.cat and one slice a stream)", ""]
+    for k in jobs:
+        lines.append(f"   {k:32s} {fmt(ms[k])}")
+    push, one, gen = med("denoiser.push_rows (a tick)"), med("denoise (the pieces, whole)"), med("generator_stream_rows (a tick)")
+    lines += ["",
+              f"   a tick's windows hold {T} frames a row, {T - CHUNK} of them computed by the tick before too ({(T - CHUNK) / T * 100:.1f} %)",
+              f"   push_rows / denoise of the same pieces whole = {push / one:.2f}",
+              f"   push_rows / generator_stream_rows            = {push / gen * 100:.2f} %",
+              f"   algorithmic delay of the stream: {N - up} .. {N - 1} samples ({(N - up) / fs * 1e3:.1f} .. {(N - 1) / fs * 1e3:.1f} ms)"]
     assert eng.status() == 0
     text = "\n".join(lines)
     print(text)

@@ -189,6 +189,13 @@ class VspLimiterRow(C.Structure):
                 ("out_count", C.c_int64), ("total", C.c_int64), ("ceiling", C.c_float)]
 
 
+class VspDenoiseRow(C.Structure):
+    """``vsp_denoise_row``: a stream's samples ``[first, first + count)`` at ``in``, the outputs ``[out_first, out_first +
+    out_count)`` at ``out``, the stream's length (-1: unknown yet) and the row's strength (NaN: leave the row alone)."""
+    _fields_ = [("inp", C.c_void_p), ("first", C.c_int64), ("count", C.c_int64), ("out", C.c_void_p), ("out_first", C.c_int64),
+                ("out_count", C.c_int64), ("total", C.c_int64), ("strength", C.c_float)]
+
+
 LIMITER_MAX_ATTACK, LIMITER_MAX_HOLD, LIMITER_REACH = 1024, 8192, 12   # samples: A, H and the meter's reach J a side
 LOUDNESS_FS_MIN, LOUDNESS_FS_MAX = 8000, 192000                      # the sample rates the loudness calls take
 LOUDNESS_HIST_BINS = 1000                                            # VSP_LOUDNESS_HIST_BINS
@@ -363,6 +370,10 @@ SIGNATURES = {
     "vsp_denoise_bias": (_I, [_P, _P, _I, _P, _P, _P, _I64]),
     "vsp_istft": (_I, [_P, _P, _I, _I, _P, C.POINTER(_I64), _P, _I64, _P, _I64]),
     "vsp_denoise": (_I, [_P, _P, _I, _I, _P, _I64, C.POINTER(_I64), _P, C.POINTER(C.c_float), _P, _I64, _P, _I64]),
+    "vsp_denoise_history": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "vsp_denoise_complete": (_I64, [_P, _I64, _I]),
+    "vsp_denoise_rows_workspace_bytes": (_I64, [_P, _I, _I64]),
+    "vsp_denoise_rows": (_I, [_P, _P, _I, C.POINTER(VspDenoiseRow), _P, _P, _I64]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

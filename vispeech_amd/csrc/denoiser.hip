@@ -2,6 +2,8 @@
 // zero-input spectrum subtracted from every STFT frame of a ragged batch, and the way back to audio by weighted
 // overlap-add.  Framing and both DFT products are the launchers of the spectrogram front end (spectrogram_ragged.hip,
 // conv_mfma.hip); the kernels here are the subtraction, the overlap-add and the two small ones of the bias.
+// For streams ("denoiser for streams") every row is a window of frames of its own stream: the window
+// framing of the live conversion (convert_window.hip), the same two products, and the rows forms of the two kernels.
 #include "api_common.h"
 #include "stft_framing.h"   // (the LDS budget and the bank skew of the framing kernels: overlap-add is framing run backwards)
 
@@ -30,6 +32,35 @@ __global__ void __launch_bounds__(256) denoise_subtract_kernel(float* __restrict
   const float q = m > 0.f ? fmaxf(m - strength[b] * bias[(size_t)b * spec_ch + r], 0.f) / m : 0.f;
   *re_p = q * re;
   *im_p = q * im;
+}
+
+// The rows form: the same expressions on the same operands, so a bin has the bits denoise_subtract_kernel gives it.
+__global__ void __launch_bounds__(256) denoise_subtract_rows_kernel(float* __restrict__ ri, long r_bs, long r_cs,
+                                                                    const DenoiseSubRows rows, int spec_ch, int T_max) {
+  const int b = blockIdx.y;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;      // r * T_max + t
+  if (e >= (long)spec_ch * T_max) return;
+  const DenoiseSubRow row = rows.r[b];
+  const int r = (int)(e / T_max), t = (int)(e - (long)r * T_max);
+  if (t >= row.Tw) return;
+  float* re_p = ri + (size_t)b * r_bs + (size_t)r * r_cs + t;
+  float* im_p = ri + (size_t)b * r_bs + (size_t)(spec_ch + r) * r_cs + t;
+  const float re = *re_p, im = *im_p;
+  const float m = sqrtf(re * re + im * im);
+  const float q = m > 0.f ? fmaxf(m - row.strength * row.bias[r], 0.f) / m : 0.f;
+  *re_p = q * re;
+  *im_p = q * im;
+}
+
+hipError_t launch_denoise_subtract_rows(float* ri, long r_bs, long r_cs, const DenoiseSubRows& rows, int B, int spec_ch,
+                                        int T_max, hipStream_t s) {
+  if (!ri || B <= 0 || B > STREAM_ROWS_MAX || T_max <= 0 || spec_ch <= 0 || r_cs < T_max) return hipErrorInvalidValue;
+  for (int b = 0; b < B; ++b)
+    if (!rows.r[b].bias || rows.r[b].Tw <= 0 || rows.r[b].Tw > T_max) return hipErrorInvalidValue;
+  const long blocks = ((long)spec_ch * T_max + 255) / 256;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(denoise_subtract_rows_kernel, dim3((unsigned)blocks, B), dim3(256), 0, s, ri, r_bs, r_cs, rows, spec_ch, T_max);
+  return hipGetLastError();
 }
 
 hipError_t launch_denoise_subtract(float* ri, long r_bs, long r_cs, const int64_t* n_samples, const float* bias,
@@ -107,6 +138,63 @@ hipError_t launch_istft_ola(const float* v, long v_bs, long v_cs, const int64_t*
   const size_t lds = (size_t)(fr_slot(tile * hop) + 1) * sizeof(float);
   hipLaunchKernelGGL(istft_ola_kernel, dim3(tiles, B), dim3(FR_THREADS), lds, s, v, v_bs, v_cs, n_samples, w2, out, o_bs, L_max,
                      n_fft, hop, tile);
+  return hipGetLastError();
+}
+
+// The rows form.  One block = the `tile * hop` padded positions [(w0 + c0) hop, (w0 + c0 + tile) hop) of one row, c0 =
+// blockIdx.x * tile a column of the row's window: the walk starts at the window's first position, so the tiles are not
+// those of istft_ola_kernel -- and need not be, because a thread's chain is the sample's own: the frames floor(p / hop) -
+// (R - 1) .. floor(p / hop), ascending, from 0, those outside [0, T_b) skipped.  Frame t is column t - w0; a column
+// outside the window is skipped for memory's sake only (the host's windows hold every frame of every REQUESTED output, and
+// the quotient of any other position is not stored).  The same two loops and the same skewed slots as above.
+__global__ void __launch_bounds__(FR_THREADS) istft_ola_rows_kernel(const float* __restrict__ v, long v_bs, long v_cs,
+                                                                    const DenoiseOlaRows rows, const float* __restrict__ w2,
+                                                                    int n_fft, int hop, int tile) {
+  extern __shared__ float span[];
+  const int b = blockIdx.y, c0 = blockIdx.x * tile;
+  const DenoiseOlaRow r = rows.r[b];
+  const int pad = (n_fft - hop) / 2, R = n_fft / hop;
+  const long p0 = ((long)r.w0 + c0) * hop;
+  const int total = tile * hop;
+  const long j0 = r.out_first + pad, j1 = j0 + r.out_count;       // the requested outputs as padded positions
+  // (uniform over the block) none of the row's outputs falls into this span
+  if (p0 >= j1 || p0 + total <= j0) return;
+  const float* row = v + (size_t)b * v_bs;
+  for (int e = threadIdx.x; e < total; e += FR_THREADS) {
+    const int tl = e % tile, kk = e / tile;      // (tile is a power of two)
+    float sum = 0.f, w = 0.f;
+    for (int q = 0; q < R; ++q) {
+      const int c = c0 + tl - (R - 1) + q;
+      const int k = kk + (R - 1 - q) * hop;
+      if (c < 0 || c >= r.Tw || (long)r.w0 + c >= r.T_b) continue;
+      sum += row[(size_t)k * v_cs + c];
+      w += w2[k];
+    }
+    span[fr_slot(tl * hop + kk)] = w > 0.f ? sum / w : 0.f;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < total; i += FR_THREADS) {
+    const long p = p0 + i;
+    if (p >= j0 && p < j1) r.out[p - j0] = span[fr_slot(i)];
+  }
+}
+
+hipError_t launch_istft_ola_rows(const float* v, long v_bs, long v_cs, const DenoiseOlaRows& rows, const float* w2, int B,
+                                 int n_fft, int hop, int T_max, hipStream_t s) {
+  const int tile = istft_ola_tile(n_fft, hop);
+  if (!v || !w2 || B <= 0 || B > STREAM_ROWS_MAX || T_max <= 0 || tile <= 0 || n_fft % hop || (n_fft - hop) % 2 || v_cs < T_max)
+    return hipErrorInvalidValue;
+  const int R = n_fft / hop, pad = (n_fft - hop) / 2;
+  for (int b = 0; b < B; ++b) {
+    const DenoiseOlaRow& r = rows.r[b];
+    // every output lies under the window: [w0 hop, (w0 + Tw + R - 1) hop) in padded positions
+    if (!r.out || r.out_count <= 0 || r.out_first < 0 || r.w0 < 0 || r.Tw <= 0 || r.Tw > T_max || r.T_b <= r.w0 ||
+        r.out_first + pad < (long)r.w0 * hop || r.out_first + pad + r.out_count > ((long)r.w0 + r.Tw + R - 1) * hop)
+      return hipErrorInvalidValue;
+  }
+  const int tiles = (T_max + R - 1 + tile - 1) / tile;
+  const size_t lds = (size_t)(fr_slot(tile * hop) + 1) * sizeof(float);
+  hipLaunchKernelGGL(istft_ola_rows_kernel, dim3(tiles, B), dim3(FR_THREADS), lds, s, v, v_bs, v_cs, rows, w2, n_fft, hop, tile);
   return hipGetLastError();
 }
 
@@ -262,9 +350,127 @@ int denoise_call(vsp_ctx* ctx, const char* who, void* stream, int B, int L_max, 
                    [&](Run& r) { denoise_impl(r, g, B, L_max, T, io, synthesis_only); }, (int64_t)rows_bytes(B));
 }
 
+// ---- rows: every row a window of frames of its own stream ------------------------------------
+constexpr int64_t DN_MAX_SAMPLES = (int64_t)1 << 30;
+constexpr long DN_NO_BOUND = 1L << 40;      // T_b of a stream whose end is unknown
+
+// The largest window a row of L outputs has: its first output's frame, R - 1 before it, and one per hop started behind it.
+int rows_window_max(const Geometry& g, int64_t L) { return (int)((L - 1 + g.hop - 1) / g.hop) + g.n_fft / g.hop; }
+
+struct RowsIO { ConvWinFrameRows frame; DenoiseSubRows sub; DenoiseOlaRows ola; };
+
+// launch_window_frames -> DFT -> subtraction in place -> inverse DFT -> overlap-add over the windows; B live rows
+void denoise_rows_impl(Run& r, const Geometry& g, int B, int T, const RowsIO* io) {
+  vsp_ctx* const ctx = r.ctx;
+  Ws& ws = r.ws;
+  int64_t* scal = static_cast<int64_t*>(ws.bytes((size_t)3 * B * sizeof(int64_t)));      // what the framing kernel leaves for others
+  T3 F = ws.t3(B, g.n_fft, T), RI = ws.t3(B, 2 * g.spec, T), V = ws.t3(B, g.n_fft, T);
+  if (ws.dry || ws.overflow) return;
+  r.chk(launch_window_frames(io->frame, F.p, F.bs, F.cs, scal, scal + B, scal + 2 * B, B, g.n_fft, g.hop, T, r.s), "window frames");
+  ConvArgs a = r.args(ctx->model.stft, F, RI, T, T);
+  a.fixed_form = 1;        // (as denoise_impl: the form of the product is the one-shot call's whatever B and T)
+  r.conv(a, B);
+  if (r.ok()) r.chk(launch_denoise_subtract_rows(RI.p, RI.bs, RI.cs, io->sub, B, g.spec, T, r.s), "denoise subtract rows");
+  a = r.args(ctx->model.istft, RI, V, T, T);
+  a.fixed_form = 1;
+  r.conv(a, B);
+  if (r.ok())
+    r.chk(launch_istft_ola_rows(V.p, V.bs, V.cs, io->ola, r.A(ctx->model.istft_w2), B, g.n_fft, g.hop, T, r.s), "istft overlap-add rows");
+}
+
 }  // namespace
 
 extern "C" {
+
+int vsp_denoise_history(const vsp_ctx* ctx, int64_t* behind, int64_t* ahead) {
+  Geometry g;
+  if (!ctx || !behind || !ahead || denoise_geometry(ctx, &g)) return VSP_ERR_ARG;
+  *behind = g.n_fft - g.hop;
+  *ahead = g.n_fft - 1;
+  return VSP_OK;
+}
+
+int64_t vsp_denoise_complete(const vsp_ctx* ctx, int64_t n_seen, int closed) {
+  Geometry g;
+  if (!ctx || n_seen < 0 || denoise_geometry(ctx, &g)) return VSP_ERR_ARG;
+  if (closed) return n_seen;
+  const int64_t pad = (g.n_fft - g.hop) / 2, room = n_seen + pad - g.n_fft;
+  const int64_t Tc = room < 0 ? 0 : room / g.hop + 1;      // frames t with t hop - pad + n_fft <= n_seen
+  return std::max<int64_t>(0, Tc * g.hop - pad);
+}
+
+int64_t vsp_denoise_rows_workspace_bytes(const vsp_ctx* ctx, int B, int64_t L_max) {
+  Geometry g;
+  if (!ctx || denoise_geometry(ctx, &g) || B < 1 || B > STREAM_ROWS_MAX || L_max < 1 || L_max > DN_MAX_SAMPLES) return VSP_ERR_ARG;
+  const int T = rows_window_max(g, L_max);
+  return dry_bytes(ctx, [&](Run& r) { denoise_rows_impl(r, g, B, T, nullptr); });
+}
+
+int vsp_denoise_rows(vsp_ctx* ctx, void* stream, int B, const vsp_denoise_row* rows_host, const float* bias, void* workspace,
+                     int64_t workspace_bytes) {
+  if (!ctx) return VSP_ERR_ARG;
+  const char* who = "vsp_denoise_rows";
+  Geometry g;
+  if (const char* why = denoise_geometry(ctx, &g)) return ctx->fail(VSP_ERR_ARG, "%s: %s", who, why);
+  if (B < 1 || B > STREAM_ROWS_MAX || !rows_host) return ctx->fail(VSP_ERR_ARG, "%s: 1 <= B <= %d rows", who, STREAM_ROWS_MAX);
+  const int64_t pad = (g.n_fft - g.hop) / 2, R = g.n_fft / g.hop;
+  RowsIO io;
+  std::memset(&io, 0, sizeof io);
+  int live = 0, T = 0;
+  int64_t out_max = 1;
+  for (int b = 0; b < B; ++b) {
+    const vsp_denoise_row& h = rows_host[b];
+    if (std::isnan(h.strength)) continue;                  // left alone, whatever else it holds
+    if (h.strength < 0.f || std::isinf(h.strength))
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: the strength %g is negative or infinite", who, b, (double)h.strength);
+    if (!bias) return ctx->fail(VSP_ERR_ARG, "%s: row %d: a finite strength and no bias", who, b);
+    if (h.first < 0 || h.count < 0 || h.out_first < 0 || h.out_count < 0 || h.total < -1 || h.first > DN_MAX_SAMPLES ||
+        h.count > DN_MAX_SAMPLES || h.out_first > DN_MAX_SAMPLES || h.out_count > DN_MAX_SAMPLES || h.total > DN_MAX_SAMPLES)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: negative position or count, or more than 2^30 samples", who, b);
+    const int64_t end = h.first + h.count, out_end = h.out_first + h.out_count;
+    if (h.total >= 0 && h.total <= pad)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: a stream of %lld samples is not above (n_fft - hop) / 2 = %lld: the reflection at its ends "
+                                    "is undefined", who, b, (long long)h.total, (long long)pad);
+    if (h.total >= 0 && (end > h.total || out_end > h.total))
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: samples [%lld, %lld) or outputs [%lld, %lld) lie behind the stream's end %lld", who, b,
+                       (long long)h.first, (long long)end, (long long)h.out_first, (long long)out_end, (long long)h.total);
+    if ((h.count > 0 && !h.in) || (h.out_count > 0 && !h.out)) return ctx->fail(VSP_ERR_ARG, "%s: row %d: null pointer", who, b);
+    out_max = std::max(out_max, h.out_count);
+    if (h.out_count == 0) continue;                        // nothing to put out: nothing is read either
+    // the frames that cover the outputs, and the samples those frames read (convert_window_plan without a halo)
+    const bool closed = h.total >= 0 && end == h.total;
+    const long T_b = h.total >= 0 ? stft_ragged_frames((long)h.total, g.n_fft, g.hop) : DN_NO_BOUND;
+    const int64_t w0 = std::max<int64_t>(0, (h.out_first + pad) / g.hop - (R - 1));
+    const int64_t w1 = std::min<int64_t>(T_b, (out_end - 1 + pad) / g.hop + 1);
+    long lo = 0, hi = 0;
+    // (an open row's frames must end inside its samples; a closed one's reflect at `total`)
+    if (w1 <= w0 || convert_window_plan(g.n_fft, g.hop, 0, (long)end, closed ? 1 : 0, (int)w0, (int)w1, nullptr, nullptr, &lo, &hi) < 0)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: no frame covers the outputs [%lld, %lld)", who, b, (long long)h.out_first,
+                       (long long)out_end);
+    if (hi > end)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: outputs up to %lld need the samples up to %lld (look-ahead n_fft - 1 at most), the row ends "
+                                    "at %lld before the stream does", who, b, (long long)out_end, (long long)hi, (long long)end);
+    if (lo < h.first)
+      return ctx->fail(VSP_ERR_ARG, "%s: row %d: output %lld needs the samples from %lld on (history n_fft - hop at most), the row starts at %lld",
+                       who, b, (long long)h.out_first, (long long)lo, (long long)h.first);
+    const int Tw = (int)(w1 - w0);
+    ConvWinFrameRow& f = io.frame.r[live];
+    f.audio = h.in; f.first = (long)h.first; f.n = (long)end; f.w0 = (int)w0; f.Tw = Tw; f.closed = closed ? 1 : 0;
+    io.sub.r[live] = DenoiseSubRow{bias + (size_t)b * g.spec, h.strength, Tw};
+    io.ola.r[live] = DenoiseOlaRow{h.out, (long)h.out_first, T_b, (int)h.out_count, (int)w0, Tw, 0};
+    T = std::max(T, Tw);
+    ++live;
+  }
+  const int64_t need = vsp_denoise_rows_workspace_bytes(ctx, B, out_max);
+  if (need < 0) return ctx->fail(VSP_ERR_ARG, "%s: bad argument", who);
+  if (!workspace || workspace_bytes < need)
+    return ctx->fail(VSP_ERR_WORKSPACE, "%s workspace too small: %lld < %lld bytes", who, (long long)(workspace ? workspace_bytes : 0),
+                     (long long)need);
+  if (const int rc = check_ready(ctx)) return rc;
+  if (!live) return VSP_OK;
+  // (live <= B and T <= the window of out_max outputs: the run fits what `need` measured)
+  return run_sized(ctx, stream, who, need, workspace, workspace_bytes, [&](Run& r) { denoise_rows_impl(r, g, live, T, &io); });
+}
 
 int64_t vsp_denoise_workspace_bytes(const vsp_ctx* ctx, int B, int L_max) {
   Geometry g;

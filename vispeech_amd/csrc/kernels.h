@@ -607,6 +607,25 @@ hipError_t launch_window_noise(const ConvWinNoiseRows& rows, int B, int C, int T
 hipError_t launch_window_cut(const float* z, const StreamCollectRows& rows, int B, int C, int T_max, float* out, int span,
                              hipStream_t s);
 
+// Denoiser rows (denoiser.hip; include/vispeech_hip.h, vsp_denoise_rows): row b is the window of frames [w0, w0 + Tw) of a
+// stream, framed by launch_window_frames above; frame t of the stream sits at column t - w0 of the three operands.
+// Descriptors by value, as for the live conversion windows.
+struct DenoiseSubRow { const float* bias; float strength; int Tw; };      // 16 B: the row's own bias [spec_ch]
+struct DenoiseSubRows { DenoiseSubRow r[STREAM_ROWS_MAX]; };
+// 40 B: the outputs [out_first, out_first + out_count) of the stream go to out[0 .. out_count); frames at or behind T_b
+// do not exist (T(total) of a stream whose end is known, else no bound)
+struct DenoiseOlaRow { float* out; long out_first, T_b; int out_count, w0, Tw, pad; };
+struct DenoiseOlaRows { DenoiseOlaRow r[STREAM_ROWS_MAX]; };
+// launch_denoise_subtract with the row's live columns, strength and bias in its descriptor: columns at or behind Tw_b stay 0
+hipError_t launch_denoise_subtract_rows(float* ri, long r_bs, long r_cs, const DenoiseSubRows& rows, int B, int spec_ch,
+                                        int T_max, hipStream_t s);
+// launch_istft_ola over windows: sample j of the stream sits at padded position p = j + pad and sums the frames
+// floor(p / hop) - (R - 1) .. floor(p / hop) that lie in [0, T_b), from 0 in ascending t -- the chain of launch_istft_ola
+// whatever w0 --, and W likewise.  The caller's windows hold every such frame of every requested output.  Writes
+// out_b[0 .. out_count_b) and nothing else.
+hipError_t launch_istft_ola_rows(const float* v, long v_bs, long v_cs, const DenoiseOlaRows& rows, const float* w2, int B,
+                                 int n_fft, int hop, int T_max, hipStream_t s);
+
 }  // namespace vsp
 
 #include "cl_args.h"   // (builders of the Cl*Args above)

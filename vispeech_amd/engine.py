@@ -2224,6 +2224,62 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_denoise")
         return o
 
+    def denoise_history(self):
+        """``vsp_denoise_history``: ``(behind, ahead)`` = ``(n_fft - hop, n_fft - 1)`` -- the samples before an output and
+        after it that can reach it."""
+        behind, ahead = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.vsp_denoise_history(self.ctx, C.byref(behind), C.byref(ahead)), None,
+                   "vsp_denoise_history (the context has no denoiser geometry)")
+        return behind.value, ahead.value
+
+    def denoise_complete(self, n_seen: int, closed: bool = False) -> int:
+        """``vsp_denoise_complete``: the outputs of a stream that are final once ``n_seen`` samples are in (host arithmetic)."""
+        e = int(self.lib.vsp_denoise_complete(self.ctx, int(n_seen), int(bool(closed))))
+        if e < 0:
+            raise ValueError(f"denoise_complete({n_seen}): negative, or the context has no denoiser geometry")
+        return e
+
+    def denoise_rows(self, rows, bias):
+        """``vsp_denoise_rows``: ONE call over rows ``(x, first, out_first, out_count, total, strength)`` -- ``x`` a 1-D
+        float32 device tensor holding the stream's samples ``[first, first + len(x))``, ``total`` the stream's length or -1 /
+        None, ``strength`` None / NaN for a row left alone -- each at its own position.  ``bias`` [B, spec_channels] (row
+        b's own), or None when every row is left alone.  Returns the rows' denoised samples ``[out_first, out_first +
+        out_count)`` as new 1-D tensors."""
+        B = len(rows)
+        if B == 0:
+            raise ValueError("denoise_rows: at least one row")
+        if int(self.dims.hop_length) != int(self.dims.total_upsample):
+            raise ValueError(f"denoise_rows: hop_length {self.dims.hop_length} is not the generator's total upsampling "
+                             f"{self.dims.total_upsample}: the bias would not be periodic in a frame")
+        bp = None
+        if bias is not None:
+            bp = _dev_f32(bias, self.device)
+            if tuple(bp.shape) != (B, self.dims.spec_channels):
+                raise ValueError(f"bias must be [{B}, {self.dims.spec_channels}]")
+        desc = (_lib.VspDenoiseRow * B)()
+        keep, outs = [], []
+        for b, (x, first, out_first, out_count, total, strength) in enumerate(rows):
+            x = x if (torch.is_tensor(x) and x.dtype == torch.float32 and x.device == self.device and x.is_contiguous()) \
+                else _dev_f32(x, self.device)
+            if x.dim() != 1:
+                raise ValueError(f"denoise_rows: row {b}: samples must be 1-D")
+            o = self._f(max(int(out_count), 0))
+            keep.append(x)
+            outs.append(o)
+            desc[b] = _lib.VspDenoiseRow(x.data_ptr() if x.numel() else None, int(first), x.numel(),
+                                         o.data_ptr() if o.numel() else None, int(out_first), int(out_count),
+                                         -1 if total is None else int(total), float("nan") if strength is None else float(strength))
+        L_max = max(1, max(int(r[3]) for r in rows))
+        need = int(self.lib.vsp_denoise_rows_workspace_bytes(self.ctx, B, L_max))
+        if need < 0:
+            raise ValueError(f"denoise_rows: the context has no denoiser geometry (spec_channels > 1, hop = the generator's total "
+                             f"upsampling dividing n_fft at least four times), or B = {B} / {L_max} outputs is out of range")
+        ws = self._workspace("denoise", need)
+        with torch.cuda.device(self.device):
+            rc = self.lib.vsp_denoise_rows(self.ctx, self._stream(), B, desc, _ptr(bp), _ptr(ws), ws.numel())
+        _lib.check(rc, self.ctx, "vsp_denoise_rows")
+        return outs
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.vsp_profile_enable(self.ctx, int(on)), self.ctx, "vsp_profile_enable")
 

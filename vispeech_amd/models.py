@@ -381,6 +381,15 @@ class SynthesizerTrn:
         ids = [int(s) for s in (sid.tolist() if hasattr(sid, "tolist") else sid)]
         return self._engine.denoise(audio, n_samples, self.denoiser_bias(ids), strength, out=out)
 
+    @torch.no_grad()
+    def denoise_stream(self, sid, strength=0.01):
+        """``denoise`` for audio that is still arriving: a ``vispeech_amd.denoiser.Stream`` with
+        speaker ``sid``'s bias.  ``push(x)`` returns the denoised samples the pushes so far complete, ``push(x, final=True)``
+        the rest; the pieces joined are the bits of ``denoise`` on the whole, at a delay of ``n_fft - hop`` to ``n_fft - 1``
+        samples.  Several streams advance in one call through ``denoiser.push_rows``."""
+        from . import denoiser
+        return denoiser.Stream(self._engine, self.denoiser_bias([int(sid)])[0], strength)
+
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
 

@@ -9,9 +9,10 @@ from typing import Optional
 
 import numpy as np
 
-from .. import input_stage, limiter, loudness, output_stage
+from .. import denoiser, input_stage, limiter, loudness, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
-from .batching import _Conversion, _Request, _collate_from, _input_format, _limiter_spec, _output_format, _row_formats, latents
+from .batching import (_Conversion, _Request, _collate_from, _denoise_spec, _input_format, _limiter_spec, _output_format, _row_formats,
+                       latents)
 
 
 class _RowStream:
@@ -59,8 +60,9 @@ class _RowStream:
 class _StreamRequest(_Request):
     """One request of a ``StreamingBatchService``: queued (``z`` None), then active at frame ``pos`` of its ``L``."""
 
-    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, limiter=None, level=None):
-        super().__init__(row, seed, scales, out_fmt, limiter=limiter)
+    def __init__(self, row, seed: int, scales=(None, None, None, None), out_fmt=None, limiter=None, level=None, denoise=None):
+        super().__init__(row, seed, scales, out_fmt, limiter=limiter, denoise=denoise)
+        self.den = None               # a request with a denoiser: its ``denoiser.Stream``, from its first tick on
         self.lim = None               # a request with a limiter: its ``limiter.Stream``, from its first tick on
         self.level = level            # ``loudness.spec``: the leveller's five values, {} for a meter only, or None
         self.loud = None              # a request that names a loudness: its ``loudness.Stream``, from its first tick on
@@ -123,8 +125,9 @@ class _LiveRequest(_StreamRequest):
     on, ``done`` frames are delivered.  For the tick it takes part in, the request is an ordinary row of the vocoder call:
     ``z`` is its window of ``z_hat`` -- frames ``[e0, e0 + L)`` of the recording -- and ``pos`` counts from ``e0``."""
 
-    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None, limiter=None, level=None):
-        super().__init__(None, seed, out_fmt=out_fmt, limiter=limiter, level=level)
+    def __init__(self, stream: LiveConversion, sid_src: int, sid_tgt: int, seed: int, noise_scale, out_fmt=None, limiter=None, level=None,
+                 denoise=None):
+        super().__init__(None, seed, out_fmt=out_fmt, limiter=limiter, level=level, denoise=denoise)
         self.stream = stream
         self.fmt = stream._fmt        # (rate, encoding) of the feed: its pieces go through ``input`` before they reach ``buf``
         self.input = None             # the session's ``input_stage.Stream``, from its first piece on
@@ -193,13 +196,27 @@ class StreamingBatchService:
     ``fused_output=True`` refuses the keyword; a request that names nothing gets the bytes it always got.
     ``loudness_gate="histogram"`` (round 24; "exact" is the default) gives those streams the histogram
     gate: their running level costs the same at every tick, however long a request lasts -- what ``open_conversion`` needs
-    --, stays within 0.05 LU of the exact one, and ``.loudness`` gains ``range_lu``, the loudness range."""
+    --, stays within 0.05 LU of the exact one, and ``.loudness`` gains ``range_lu``, the loudness range.
+    ``denoise=`` (round 26), on the service for every request or on ``submit`` / ``submit_conversion`` /
+    ``open_conversion`` for one (None there: the service's; False: none): a strength, or True for 0.01 -- the denoiser of
+    ``SynthesizerTrn.denoise`` with the speaker's own bias (a conversion's: ``sid_tgt``), on the generator's chunks as they
+    come.  Such a tick runs on the ``output_rows`` path with ONE ``denoiser.push_rows`` call for those rows, in front of the
+    loudness call and the limiter -- the order of ``BatchingSynthesisService`` --; the request's last chunk flushes its
+    denoiser, and the stages behind are handed the positions of the denoiser's output.  Its samples are those of
+    ``SynthesizerTrn.denoise`` on its whole waveform; its delay grows by ``n_fft - hop`` to ``n_fft - 1`` samples, and a tick
+    in which its denoiser completes no sample delivers nothing for it.  ``fused_output=True`` refuses the keyword; a
+    request that names nothing gets the bytes it always got, and a service in which nobody does makes the calls it always
+    made."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
-                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False, loudness_gate: str = "exact"):
+                 sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False, loudness_gate: str = "exact",
+                 denoise=None):
         if not 1 <= max_batch <= 64 or chunk_frames < 1:
             raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
+        self.denoise = _denoise_spec(denoise)
+        if self.denoise is not None and fused_output:
+            raise ValueError("fused_output delivers every row through its one launch: a denoiser needs fused_output=False")
         if loudness_gate not in loudness.GATES:
             raise ValueError(f"loudness_gate is one of {loudness.GATES}, not {loudness_gate!r}")
         self.loudness_gate = loudness_gate
@@ -252,8 +269,16 @@ class StreamingBatchService:
             raise ValueError("fused_output delivers every row through its one launch: a request's loudness needs fused_output=False")
         return loudness.spec(value)
 
+    def _denoise(self, value):
+        """A request's ``denoise=``: its strength (``batching._denoise_spec``), the service's for None, or None."""
+        strength = self.denoise if value is None else _denoise_spec(value)
+        if strength is not None and self.fused_output:
+            raise ValueError("fused_output delivers every row through its one launch: a request's denoiser needs fused_output=False")
+        return strength
+
     def submit(self, row, noise_seed: int, *, duration_scale=None, pitch_scale=None, energy_scale=None,
-               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, limiter=None, loudness=None) -> _RowStream:
+               noise_scale=None, output_rate: Optional[int] = None, output_encoding=None, limiter=None, loudness=None,
+               denoise=None) -> _RowStream:
         """``row``: one row as ``vispeech_amd.text.collate_rows`` takes it; the four scales are the request's own (None:
         1.0, and the service's ``noise_scale``), as in ``BatchingSynthesisService.submit``.  Returns the iterator of the
         request's PCM16 ``bytes``, one piece per tick the request takes part in.
@@ -265,28 +290,32 @@ class StreamingBatchService:
         its delay grows by attack + 12 samples.  A tick in which a request has one runs as a tick in which a request names
         a format does, with ONE ``limiter.push_rows`` call for those rows between the generator and ``output_rows``.
         ``loudness``: the leveller's target (LUFS), a mapping of its five values, or True for a meter only (see the class
-        text); it runs in front of the limiter."""
+        text); it runs in front of the limiter.
+        ``denoise``: the strength of the denoiser on the request's waveform, or True for 0.01; None: the service's; False:
+        none (see the class text); it runs in front of both."""
         return self._enqueue(_StreamRequest(row, noise_seed, (duration_scale, pitch_scale, energy_scale, noise_scale),
-                                            self._out_fmt(output_rate, output_encoding), self._limiter(limiter), self._loudness(loudness)))
+                                            self._out_fmt(output_rate, output_encoding), self._limiter(limiter), self._loudness(loudness),
+                                            self._denoise(denoise)))
 
     def submit_conversion(self, audio, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                           sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                          output_encoding=None, limiter=None, loudness=None) -> _RowStream:
+                          output_encoding=None, limiter=None, loudness=None, denoise=None) -> _RowStream:
         """``audio``: a 1-D float32 recording at the model's rate, spoken by speaker ``sid_src``.  Returns the iterator of
         the PCM16 ``bytes`` of the recording converted to ``sid_tgt``, one piece per tick; a recording too short for one
         frame ends at once with no bytes.  ``noise_scale`` multiplies the posterior's noise (None: 1.0, the reference --
         NOT the service's text-to-speech ``noise_scale``).  ``sample_rate`` / ``encoding``: ``audio`` is raw samples in that
         format (an array of the encoding's dtype or ``bytes``); admission runs the group's raw recordings through the
         input stage, one call per distinct (rate, encoding), before its one ``convert_latent``.  ``output_rate`` /
-        ``output_encoding`` / ``limiter`` / ``loudness``: as in ``submit``."""
+        ``output_encoding`` / ``limiter`` / ``loudness``: as in ``submit``; ``denoise``: as in ``submit``, with the bias of
+        ``sid_tgt``."""
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         return self._enqueue(_StreamRequest(_Conversion(audio, sid_src, sid_tgt, noise_scale, fmt), noise_seed,
                                             out_fmt=self._out_fmt(output_rate, output_encoding), limiter=self._limiter(limiter),
-                                            level=self._loudness(loudness)))
+                                            level=self._loudness(loudness), denoise=self._denoise(denoise)))
 
     def open_conversion(self, sid_src: int, sid_tgt: int, noise_seed: int, *, noise_scale=None,
                         sample_rate: Optional[int] = None, encoding=None, output_rate: Optional[int] = None,
-                        output_encoding=None, limiter=None, loudness=None) -> LiveConversion:
+                        output_encoding=None, limiter=None, loudness=None, denoise=None) -> LiveConversion:
         """Opens a live conversion from speaker ``sid_src`` to ``sid_tgt``: ``feed`` the recording to the returned
         ``LiveConversion`` as it arrives, ``end()`` it, and iterate over it for the PCM16 ``bytes``.  ``noise_scale`` as in
         ``submit_conversion`` (None: 1.0); ``noise_seed`` keys the noise, frame-major (``vsp_convert_stream_rows``).
@@ -296,10 +325,12 @@ class StreamingBatchService:
         Readiness is decided on those samples, so the session's delay grows by the filter's half length: ``zeros`` = 32
         input periods (2 ms at 16 kHz).  ``output_rate`` / ``output_encoding``: as in ``submit``; on that path a frame
         need not be a whole number of output samples.  ``limiter`` / ``loudness``: as in ``submit`` -- the leveller is what
-        keeps a call that lasts minutes, whose talker moves about the microphone, at its level."""
+        keeps a call that lasts minutes, whose talker moves about the microphone, at its level.  ``denoise``: as in
+        ``submit_conversion`` -- a call that lasts minutes is where the vocoder's steady buzz is heard longest."""
         out_fmt = self._out_fmt(output_rate, output_encoding)
         limiter = self._limiter(limiter)
         level = self._loudness(loudness)
+        denoise = self._denoise(denoise)
         if self.fused_output:
             # the tick hands a live row to the fused output stage at a position counted from its window's first frame: the
             # filter's phase and its history must not see the shift
@@ -319,7 +350,8 @@ class StreamingBatchService:
         fmt = _input_format(sample_rate, encoding, self.sampling_rate)
         if fmt is not None and fmt[0] not in self.net._engine.input_rates:
             self.net._engine.configure_input(fmt[0], model_rate=self.sampling_rate)      # (allocates: here, not in a tick)
-        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt, limiter, level))
+        return self._enqueue(_LiveRequest(LiveConversion(self._cv, fmt), sid_src, sid_tgt, noise_seed, noise_scale, out_fmt, limiter, level,
+                                          denoise))
 
     def _enqueue(self, req: _StreamRequest) -> _RowStream:
         """A text request or a conversion joins the queue, a live session the open sessions; the worker is woken."""
@@ -540,7 +572,7 @@ class StreamingBatchService:
             counts.append(f1 - r.pos)
         self.stats["ticks"] += 1
         self.stats["rows_per_tick"].append(len(rows))
-        if any(r.out_fmt is not None or r.limiter is not None or r.level is not None for r in reqs):
+        if any(r.out_fmt is not None or r.limiter is not None or r.level is not None or r.denoise is not None for r in reqs):
             return self._deliver_rows(reqs, rows, counts)
         for r in reqs:
             if r.row_state is not None:        # it shared earlier ticks with requests that name a format
@@ -580,6 +612,16 @@ class StreamingBatchService:
         pieces = [out[b, : n * hop] for b, n in enumerate(counts)]
         first = [(getattr(r, "e0", 0) + r.pos) * hop for r in reqs]
         last = [r.pos + n >= r.L for r, n in zip(reqs, counts)]
+        denoised = [b for b, r in enumerate(reqs) if r.denoise is not None]
+        if denoised:                                                    # in front of everything: the one-shot service's order
+            for b in denoised:
+                r = reqs[b]
+                if r.den is None:
+                    sid = r.sid_tgt if isinstance(r, _LiveRequest) else r.row.sid_tgt if r.is_conversion else r.sid
+                    r.den = denoiser.Stream(eng, self.net.denoiser_bias([sid])[0], r.denoise)
+                first[b] = r.den.out_next                               # the stages behind see the denoiser's samples
+            for b, y in zip(denoised, denoiser.push_rows(eng, [(reqs[b].den, pieces[b], last[b]) for b in denoised])):
+                pieces[b] = y
         named = [b for b, r in enumerate(reqs) if r.level is not None]
         if named:                                                       # the leveller (or meter): no delay, so `first` stands
             for b in named:
