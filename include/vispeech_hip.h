@@ -1475,6 +1475,29 @@ int64_t vsp_denoise_rows_workspace_bytes(const vsp_ctx* ctx, int B, int64_t L_ma
 int vsp_denoise_rows(vsp_ctx* ctx, void* stream, int B, const vsp_denoise_row* rows_host, const float* bias, void* workspace,
                      int64_t workspace_bytes);
 
+/* ---- the denoiser's transform (round 27, ABI 7, additive) ------------ */
+/* Which transform vsp_denoise, vsp_denoise_rows, vsp_denoise_bias and vsp_istft -- and their workspace-size functions, by
+ * the same dry pass -- run between framing and overlap-add:
+ *   VSP_STFT_DFT (the default)  the two products with the windowed DFT bases and the subtraction between them: the
+ *                               launches and the bits of rounds 25 and 26.
+ *   VSP_STFT_FFT                a real FFT of N points per frame in LDS (N / 2 complex points in five radix-4 passes and a
+ *                               split step; twiddles and windows from fp64 tables in the arena): vsp_denoise and
+ *                               vsp_denoise_rows run framing, ONE fused launch (window, forward, subtraction, inverse, window;
+ *                               the spectrum never reaches memory) and overlap-add, vsp_istft the inverse launch and
+ *                               overlap-add, vsp_denoise_bias the forward launch between its two kernels.  The sums are
+ *                               those of the specification; their bits are an FFT's, not the product's.  Every frame is
+ *                               transformed on its own, so the contracts of the product path hold unchanged: a row's bits do
+ *                               not depend on its batch, a stream cut anywhere gives the bits of vsp_denoise under the
+ *                               same transform.  The workspace is smaller (one frame tensor), never larger.
+ * The switch belongs to the context and is read by each call; a bias should be made under the transform that subtracts it.
+ * The spectrogram front end of voice conversion (vsp_spectrogram*, vsp_convert_*) ignores it.
+ * vsp_set_stft_transform: VSP_ERR_ARG, with a message and before any launch, for an unknown kind, and for VSP_STFT_FFT on a
+ * context without the denoiser's geometry or with N != 2048.  vsp_stft_transform: the kind in force. */
+#define VSP_STFT_DFT 0
+#define VSP_STFT_FFT 1
+int vsp_set_stft_transform(vsp_ctx* ctx, int kind);
+int vsp_stft_transform(const vsp_ctx* ctx);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* When enabled, every launch of a profiled class is bracketed by a HIP event pair on the launch
  * stream.  vsp_profile_read_class synchronises those events and returns, since the last reset, for

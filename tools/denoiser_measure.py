@@ -16,8 +16,14 @@ tool's own lines in profiles/r25_denoiser.txt).  No gate is set on any of them.
 tick computed too), beside that tick's ``Engine.generator_stream_rows`` call and beside ``Engine.denoise`` on the same 16
 pieces as whole rows.  The streams run on (their pieces cycle over the 10 s rows), so every timed tick is a steady-state one.
 
-usage: tools/denoiser_measure.py [--stream] [steps] [rounds] [out.txt]
-       (default out: profiles/r25_denoiser.txt, with --stream profiles/r26_denoiser_stream.txt)"""
+``--transform fft``, alone or with ``--stream``: the same rows under both transforms, ``dft`` and
+``fft`` alternating call by call's window in one session, each with the bias of its own transform; per launch, the two
+products of the one and the fused launch of the other from the library's events.  The frames a block of the FFT kernels owns
+is the process's (``VSP_FFT_TILE`` = 4 / 8 / 16, default 8): one run per tile size.
+
+usage: tools/denoiser_measure.py [--stream] [--transform fft] [steps] [rounds] [out.txt]
+       (default out: profiles/r25_denoiser.txt, with --stream profiles/r26_denoiser_stream.txt, with --transform fft
+       profiles/r27_denoiser_fft.txt)"""
 import os
 import sys
 
@@ -35,9 +41,19 @@ from vispeech_amd.synth import synth_state_dict         # noqa: E402
 
 STREAM = "--stream" in sys.argv[1:]
 ARGS = [a for a in sys.argv[1:] if a != "--stream"]
+TRANSFORM = "dft"
+if "--transform" in ARGS:
+    i = ARGS.index("--transform")
+    TRANSFORM = ARGS[i + 1] if i + 1 < len(ARGS) else ""
+    if TRANSFORM not in ("dft", "fft"):
+        sys.exit("--transform dft | fft")
+    del ARGS[i:i + 2]
+FFT = TRANSFORM == "fft"
+TILE = os.environ.get("VSP_FFT_TILE", "8")
 STEPS = int(ARGS[0]) if len(ARGS) > 0 else 10
 ROUNDS = int(ARGS[1]) if len(ARGS) > 1 else 3
-OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(ROOT, "profiles", "r26_denoiser_stream.txt" if STREAM else "r25_denoiser.txt")
+OUT = ARGS[2] if len(ARGS) > 2 else os.path.join(
+    ROOT, "profiles", "r27_denoiser_fft.txt" if FFT else "r26_denoiser_stream.txt" if STREAM else "r25_denoiser.txt")
 SECONDS, B = 10, 16
 CHUNK = 64                                             # frames of a piece: the streaming service's default chunk
 
@@ -91,8 +107,10 @@ def main():
     n_samples = [n] * B
     bias = net.denoiser_bias(sid)
     if STREAM:
-        return stream_main(net, dims, audio, Z, G, bias, frames)
+        return stream_main(net, dims, audio, Z, G, bias, frames, net.denoiser_bias(sid, "fft") if FFT else None)
     T = eng.convert_frames(n, up)
+    if FFT:
+        return fft_main(net, dims, audio, n_samples, Z, G, lengths, bias, net.denoiser_bias(sid, "fft"), T)
     out = torch.empty_like(audio)
     ri = torch.zeros((B, 2 * spec, T), dtype=torch.float32, device="cuda:0")
     jobs = {
@@ -135,7 +153,54 @@ def main():
         f.write(text + "\n")
 
 
-def stream_main(net, dims, audio, Z, G, bias, frames):
+def fft_main(net, dims, audio, n_samples, Z, G, lengths, bias, bias_fft, T):
+    """``denoise`` and ``istft`` under both transforms, alternating, and the per-launch split of each."""
+    eng, fs = net._engine, dims.sampling_rate
+    spec, N = dims.spec_channels, 2 * (dims.spec_channels - 1)
+    out = torch.empty_like(audio)
+    ri = torch.zeros((B, 2 * spec, T), dtype=torch.float32, device="cuda:0")
+    jobs = {
+        "denoise dft (strength 0.01)": lambda: eng.denoise(audio, n_samples, bias, 0.01, out=out),
+        "denoise fft (strength 0.01)": lambda: eng.denoise(audio, n_samples, bias_fft, 0.01, out=out, transform="fft"),
+        "istft dft": lambda: eng.istft(ri, n_samples),
+        "istft fft": lambda: eng.istft(ri, n_samples, transform="fft"),
+        "generator_ragged": lambda: eng.generator_ragged(Z, G, lengths),
+    }
+    ms = {k: [] for k in jobs}
+    for _ in range(ROUNDS):
+        for k, fn in jobs.items():
+            ms[k].append(timed(fn, max(STEPS // 2, 2) if k == "generator_ragged" else STEPS))
+    med = lambda k: float(np.median(ms[k]))
+    split = {k: convs(eng, jobs[k]) for k in jobs if k != "generator_ragged"}
+    d_dft, d_fft = med("denoise dft (strength 0.01)"), med("denoise fft (strength 0.01)")
+    moved = 2.0 * 4.0 * B * N * T                                              # the frame tensor in, the synthesis frames out
+    props = torch.cuda.get_device_properties(0)
+    lines = [f"denoiser on the in-LDS FFT: {B} rows of {SECONDS} s at {fs} Hz ({n_samples[0]} samples, {T} frames); {ROUNDS} rounds that "
+             f"alternate over the calls, a window of {STEPS} calls ({max(STEPS // 2, 2)} for generator_ragged)",
+             f"device {torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', 'arch not available')}, "
+             f"{props.multi_processor_count} CUs); frames a block of the FFT kernels: {TILE}",
+             "timer: device events around a window of calls, per call (the Engine calls include their host work and uploads)", ""]
+    for k in jobs:
+        lines.append(f"   {k:30s} {fmt(ms[k])}")
+    lines += ["",
+              f"   denoise fft / denoise dft = {d_fft / d_dft:.3f};  of generator_ragged: dft {d_dft / med('generator_ragged') * 100:.2f} %, "
+              f"fft {d_fft / med('generator_ragged') * 100:.2f} %",
+              "   per launch, from the library's own events (profiling on):"]
+    for k, (n_l, c) in split.items():
+        what = "fused launch" if k.startswith("denoise fft") else "inverse launch" if k == "istft fft" else "product(s)"
+        lines.append(f"      {k:30s} {n_l:.0f} {what:15s} {c:8.3f} ms   the rest of the call (framing, subtraction, overlap-add) {med(k) - c:8.3f} ms")
+    c_fused, c_prod = split["denoise fft (strength 0.01)"][1], split["denoise dft (strength 0.01)"][1]
+    lines += [f"   the fused launch moves {moved / 1e6:.0f} MB (frames in, synthesis frames out, in place): {moved / c_fused / 1e9:.2f} TB/s; "
+              f"fused launch / the two products = {c_fused / c_prod:.3f}"]
+    assert eng.status() == 0
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(OUT) or ".", exist_ok=True)
+    with open(OUT, "w") as f:
+        f.write(text + "\n")
+
+
+def stream_main(net, dims, audio, Z, G, bias, frames, bias_fft=None):
     from vispeech_amd import denoiser
     eng, fs, up = net._engine, dims.sampling_rate, dims.total_upsample
     N = 2 * (dims.spec_channels - 1)
@@ -144,7 +209,7 @@ def stream_main(net, dims, audio, Z, G, bias, frames):
     streams = [denoiser.Stream(eng, bias[b], 0.01) for b in range(B)]
     state = {"k": 0, "out": 0}
 
-    def tick():
+    def tick(streams=streams, state=state):
         k = state["k"] % per_row
         state["k"] += 1
         outs = denoiser.push_rows(eng, [(streams[b], audio[b, k * piece:(k + 1) * piece], False) for b in range(B)])
@@ -159,6 +224,11 @@ def stream_main(net, dims, audio, Z, G, bias, frames):
         "denoise (the pieces, whole)": lambda: eng.denoise(whole, [piece] * B, bias, 0.01, out=out),
         "generator_stream_rows (a tick)": lambda: eng.generator_stream_rows(rows, CHUNK, pcm=False),
     }
+    if bias_fft is not None:                               # the same tick and the same pieces on the FFT, alternating with the above
+        streams_fft = [denoiser.Stream(eng, bias_fft[b], 0.01, transform="fft") for b in range(B)]
+        state_fft = {"k": 0, "out": 0}
+        jobs["denoiser.push_rows fft (a tick)"] = lambda: tick(streams_fft, state_fft)
+        jobs["denoise fft (the pieces, whole)"] = lambda: eng.denoise(whole, [piece] * B, bias_fft, 0.01, out=out, transform="fft")
     ms = {k: [] for k in jobs}
     for _ in range(ROUNDS):
         for k, fn in jobs.items():
@@ -181,6 +251,13 @@ def stream_main(net, dims, audio, Z, G, bias, frames):
               f"   push_rows / denoise of the same pieces whole = {push / one:.2f}",
               f"   push_rows / generator_stream_rows            = {push / gen * 100:.2f} %",
               f"   algorithmic delay of the stream: {N - up} .. {N - 1} samples ({(N - up) / fs * 1e3:.1f} .. {(N - 1) / fs * 1e3:.1f} ms)"]
+    if bias_fft is not None:
+        assert state_fft["out"] == B * piece
+        push_fft = med("denoiser.push_rows fft (a tick)")
+        lines += [f"   frames a block of the FFT kernels: {TILE}",
+                  f"   push_rows fft / push_rows dft                = {push_fft / push:.3f}",
+                  f"   push_rows fft / generator_stream_rows        = {push_fft / gen * 100:.2f} %",
+                  f"   denoise fft / denoise dft (the pieces whole) = {med('denoise fft (the pieces, whole)') / one:.3f}"]
     assert eng.status() == 0
     text = "\n".join(lines)
     print(text)

@@ -215,6 +215,8 @@ _F = C.c_float
 _U64 = C.c_uint64
 
 # name -> (restype, argtypes); every symbol include/vispeech_hip.h declares
+STFT_TRANSFORMS = {"dft": 0, "fft": 1}      # VSP_STFT_DFT, VSP_STFT_FFT (vsp_set_stft_transform)
+
 SIGNATURES = {
     "vsp_abi_version": (_I, []),
     "vsp_create": (_I, [C.POINTER(VspConfig), _I, C.POINTER(_P)]),
@@ -374,6 +376,8 @@ SIGNATURES = {
     "vsp_denoise_complete": (_I64, [_P, _I64, _I]),
     "vsp_denoise_rows_workspace_bytes": (_I64, [_P, _I, _I64]),
     "vsp_denoise_rows": (_I, [_P, _P, _I, C.POINTER(VspDenoiseRow), _P, _P, _I64]),
+    "vsp_set_stft_transform": (_I, [_P, _I]),
+    "vsp_stft_transform": (_I, [_P]),
     "vsp_profile_enable": (_I, [_P, _I]),
     "vsp_profile_read": (_I, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),
     "vsp_profile_read_class": (_I, [_P, _I, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(C.c_double),

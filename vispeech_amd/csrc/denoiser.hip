@@ -5,6 +5,7 @@
 // For streams ("denoiser for streams") every row is a window of frames of its own stream: the window
 // framing of the live conversion (convert_window.hip), the same two products, and the rows forms of the two kernels.
 #include "api_common.h"
+#include "fft_plan.h"       // (the n_fft the in-LDS FFT transforms, the layout of its tables)
 #include "stft_framing.h"   // (the LDS budget and the bank skew of the framing kernels: overlap-add is framing run backwards)
 
 using namespace vsp;
@@ -257,6 +258,22 @@ const char* denoise_geometry(const vsp_ctx* ctx, Geometry* g) {
   return nullptr;
 }
 
+// The transform the context's switch asks for (vsp_set_stft_transform refuses VSP_STFT_FFT where it cannot run).
+bool use_fft(const vsp_ctx* ctx) { return ctx->stft_transform == VSP_STFT_FFT && ctx->model.has_fft; }
+
+// One launch of fft.hip under the library's per-launch events (class FRAME, as the products it stands in for): `passes`
+// transforms of B x T frames -- 5 N log2 N flops each, the textbook count --, the frame tensor read and written once.
+template <class Launch>
+void fft_launch(Run& r, const Geometry& g, int B, int T, int passes, const char* what, Launch launch) {
+  if (!r.ok()) return;
+  const bool prof = r.prof_begin(VSP_PROF_FRAME);
+  r.chk(launch(), what);
+  if (prof) {
+    const double frames = (double)B * T, bytes = 2.0 * 4.0 * frames * g.n_fft;
+    r.prof_end(VSP_PROF_FRAME, passes * 5.0 * g.n_fft * std::log2((double)g.n_fft) * frames, bytes, bytes, bytes);
+  }
+}
+
 struct Rows { const int64_t* n; const float* strength; };      // the upload: the head of the workspace
 size_t rows_bytes(int B) { return ((size_t)B * (sizeof(int64_t) + sizeof(float)) + 255) / 256 * 256; }
 
@@ -268,6 +285,30 @@ struct DenoiseIO {
 void denoise_impl(Run& r, const Geometry& g, int B, int L_max, int T, const DenoiseIO& io, bool synthesis_only) {
   vsp_ctx* const ctx = r.ctx;
   Ws& ws = r.ws;
+  if (use_fft(ctx)) {
+    // framing -> ONE launch, frames to synthesis frames in place (RI stays in LDS) -> overlap-add; the synthesis half
+    // alone: the inverse transform of io.ri into the same tensor
+    T3 F = ws.t3(B, g.n_fft, T);
+    if (ws.dry || ws.overflow) return;
+    const float* tab = r.A(ctx->model.fft_tab);
+    if (synthesis_only) {
+      fft_launch(r, g, B, T, 1, "fft inverse", [&] {
+        return launch_fft_inverse(io.ri, (long)2 * g.spec * T, T, F.p, F.bs, F.cs, tab, io.rows.n, B, L_max, g.n_fft, g.hop, T, r.s);
+      });
+    } else {
+      r.chk(launch_stft_frames_ragged(io.audio, (long)io.audio_stride, io.rows.n, F.p, F.bs, F.cs, B, L_max, g.n_fft, g.hop, T, r.s),
+            "stft frames ragged");
+      fft_launch(r, g, B, T, 2, "fft denoise", [&] {
+        return launch_fft_denoise(F.p, F.bs, F.cs, F.p, F.bs, F.cs, tab, io.rows.n, io.bias, io.rows.strength, B, L_max, g.n_fft, g.hop,
+                                  g.spec, T, r.s);
+      });
+    }
+    if (r.ok())
+      r.chk(launch_istft_ola(F.p, F.bs, F.cs, io.rows.n, r.A(ctx->model.istft_w2), io.out, (long)io.out_stride, B, L_max, g.n_fft, g.hop,
+                             T, r.s),
+            "istft overlap-add");
+    return;
+  }
   T3 F = ws.t3(B, g.n_fft, T), RI = ws.t3(B, 2 * g.spec, T), V = ws.t3(B, g.n_fft, T);
   if (ws.dry || ws.overflow) return;
   if (synthesis_only) {
@@ -296,6 +337,13 @@ void bias_impl(Run& r, const Geometry& g, int S, const float* period, float* bia
   T3 F = ws.t3(1, g.n_fft, S), RI = ws.t3(1, 2 * g.spec, S);
   if (ws.dry || ws.overflow) return;
   r.chk(launch_denoise_bias_frames(period, F.p, F.cs, S, g.n_fft, g.hop, r.s), "denoise bias frames");
+  if (use_fft(r.ctx)) {      // (every column a speaker: all S of them live)
+    fft_launch(r, g, 1, S, 1, "fft forward", [&] {
+      return launch_fft_forward(F.p, F.bs, F.cs, RI.p, RI.bs, RI.cs, r.A(r.ctx->model.fft_tab), nullptr, 1, 0, g.n_fft, g.hop, S, r.s);
+    });
+    if (r.ok()) r.chk(launch_denoise_bias_magnitude(RI.p, RI.cs, bias, S, g.spec, r.s), "denoise bias magnitude");
+    return;
+  }
   ConvArgs a = r.args(r.ctx->model.stft, F, RI, S, S);
   a.fixed_form = 1;        // (a speaker's bias does not depend on the speakers it is computed with)
   r.conv(a, 1);
@@ -364,6 +412,17 @@ void denoise_rows_impl(Run& r, const Geometry& g, int B, int T, const RowsIO* io
   vsp_ctx* const ctx = r.ctx;
   Ws& ws = r.ws;
   int64_t* scal = static_cast<int64_t*>(ws.bytes((size_t)3 * B * sizeof(int64_t)));      // what the framing kernel leaves for others
+  if (use_fft(ctx)) {        // (as denoise_impl: the same template of the fused kernel, so a frame has the one-shot call's bits)
+    T3 F = ws.t3(B, g.n_fft, T);
+    if (ws.dry || ws.overflow) return;
+    r.chk(launch_window_frames(io->frame, F.p, F.bs, F.cs, scal, scal + B, scal + 2 * B, B, g.n_fft, g.hop, T, r.s), "window frames");
+    fft_launch(r, g, B, T, 2, "fft denoise rows", [&] {
+      return launch_fft_denoise_rows(F.p, F.bs, F.cs, F.p, F.bs, F.cs, r.A(ctx->model.fft_tab), io->sub, B, g.n_fft, g.spec, T, r.s);
+    });
+    if (r.ok())
+      r.chk(launch_istft_ola_rows(F.p, F.bs, F.cs, io->ola, r.A(ctx->model.istft_w2), B, g.n_fft, g.hop, T, r.s), "istft overlap-add rows");
+    return;
+  }
   T3 F = ws.t3(B, g.n_fft, T), RI = ws.t3(B, 2 * g.spec, T), V = ws.t3(B, g.n_fft, T);
   if (ws.dry || ws.overflow) return;
   r.chk(launch_window_frames(io->frame, F.p, F.bs, F.cs, scal, scal + B, scal + 2 * B, B, g.n_fft, g.hop, T, r.s), "window frames");
@@ -381,6 +440,22 @@ void denoise_rows_impl(Run& r, const Geometry& g, int B, int T, const RowsIO* io
 }  // namespace
 
 extern "C" {
+
+int vsp_set_stft_transform(vsp_ctx* ctx, int kind) {
+  if (!ctx) return VSP_ERR_ARG;
+  if (kind != VSP_STFT_DFT && kind != VSP_STFT_FFT)
+    return ctx->fail(VSP_ERR_ARG, "vsp_set_stft_transform: unknown kind %d (VSP_STFT_DFT = 0, VSP_STFT_FFT = 1)", kind);
+  if (kind == VSP_STFT_FFT) {
+    Geometry g;
+    if (const char* why = denoise_geometry(ctx, &g)) return ctx->fail(VSP_ERR_ARG, "vsp_set_stft_transform: %s", why);
+    if (g.n_fft != FFT_N || !ctx->model.has_fft)
+      return ctx->fail(VSP_ERR_ARG, "vsp_set_stft_transform: the FFT transforms n_fft = %d only, the context has n_fft = %d", FFT_N, g.n_fft);
+  }
+  ctx->stft_transform = kind;
+  return VSP_OK;
+}
+
+int vsp_stft_transform(const vsp_ctx* ctx) { return ctx ? ctx->stft_transform : VSP_ERR_ARG; }
 
 int vsp_denoise_history(const vsp_ctx* ctx, int64_t* behind, int64_t* ahead) {
   Geometry g;

@@ -626,6 +626,22 @@ hipError_t launch_denoise_subtract_rows(float* ri, long r_bs, long r_cs, const D
 hipError_t launch_istft_ola_rows(const float* v, long v_bs, long v_cs, const DenoiseOlaRows& rows, const float* w2, int B,
                                  int n_fft, int hop, int T_max, hipStream_t s);
 
+// The STFT of the denoiser as an in-LDS real FFT (fft.hip, fft_plan.h) on the operands above:
+// f [B][n_fft][T_max] frames, ri [B][2 spec][T_max], v [B][n_fft][T_max] windowed synthesis frames; tab = the arena's FFT
+// tables (Model::fft_tab).  Columns at or behind a row's live count -- T(n_b), or Tw_b of a rows descriptor -- are neither
+// read nor written.  hipErrorInvalidValue for any n_fft but FFT_N.
+// f -> v with the subtraction of launch_denoise_subtract between the transforms; f == v is allowed
+hipError_t launch_fft_denoise(const float* f, long f_bs, long f_cs, float* v, long v_bs, long v_cs, const float* tab,
+                              const int64_t* n_samples, const float* bias, const float* strength, int B, int L_max, int n_fft,
+                              int hop, int spec_ch, int T_max, hipStream_t s);
+hipError_t launch_fft_denoise_rows(const float* f, long f_bs, long f_cs, float* v, long v_bs, long v_cs, const float* tab,
+                                   const DenoiseSubRows& rows, int B, int n_fft, int spec_ch, int T_max, hipStream_t s);
+// f -> ri and ri -> v; n_samples NULL: every row has T_max live columns
+hipError_t launch_fft_forward(const float* f, long f_bs, long f_cs, float* ri, long r_bs, long r_cs, const float* tab,
+                              const int64_t* n_samples, int B, int L_max, int n_fft, int hop, int T_max, hipStream_t s);
+hipError_t launch_fft_inverse(const float* ri, long r_bs, long r_cs, float* v, long v_bs, long v_cs, const float* tab,
+                              const int64_t* n_samples, int B, int L_max, int n_fft, int hop, int T_max, hipStream_t s);
+
 }  // namespace vsp
 
 #include "cl_args.h"   // (builders of the Cl*Args above)

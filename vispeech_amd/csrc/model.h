@@ -93,6 +93,10 @@ struct Model {
   // overlap-add kernel's normalisation
   Conv istft;
   size_t istft_w2 = 0;
+  // round 27, behind those again when n_fft is the one the in-LDS FFT transforms (has_fft): its twiddles, split-step factors
+  // and the two windows (fft_plan.h, FFT_TAB_*)
+  bool has_fft = false;
+  size_t fft_tab = 0;
   size_t total_floats = 0;
   bool has_cl = false;  // split-f16 channels-last generator weights present
 };
@@ -187,6 +191,9 @@ struct vsp_ctx {
   // computes it -- masks where the reference applies none, the generator's tensors ending at the utterance's own length,
   // and per-utterance noise keys (vsp_set_noise_seeds; noise_first is then ignored).  Off: the reference's padded batch.
   bool isolated = false;
+  // vsp_set_stft_transform (round 27): the transform of vsp_denoise, vsp_denoise_rows, vsp_denoise_bias and vsp_istft --
+  // VSP_STFT_DFT, the two products, or VSP_STFT_FFT, the kernels of fft.hip
+  int stft_transform = 0;
   std::vector<uint64_t> noise_seeds;
   // Per-row controls (vsp_set_row_controls, round 13): utterance b's own scales and which of its controls are given --
   // the arguments of the B = 1 call isolated mode reproduces.  Empty: the scalar arguments of the call hold for every row.

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <functional>
 
+#include "fft_plan.h"
 #include "model.h"
 
 namespace vsp {
@@ -388,6 +389,9 @@ int plan_model(vsp_ctx* ctx) {
     m.istft = p.conv(n_fft, 2 * c.spec_channels, 1, 1, 0, false);
     p.f16s = false;
     m.istft_w2 = p.raw((size_t)n_fft);
+    // ... and behind it the tables of the in-LDS FFT (round 27)
+    m.has_fft = n_fft == FFT_N;
+    if (m.has_fft) m.fft_tab = p.raw((size_t)FFT_TAB_FLOATS);
   }
   m.total_floats = p.cur;
   return VSP_OK;
@@ -652,6 +656,7 @@ int fill_model(vsp_ctx* ctx, std::vector<float>& arena) {
         return (float)((col < spec ? cs[k] : -sn[k]) * w * hann[n]);
       }, [](int) { return 0.f; });
       for (int n = 0; n < N && f.ok; ++n) arena[m.istft_w2 + n] = (float)(hann[n] * hann[n]);
+      if (m.has_fft && f.ok) fft_fill_tables(arena.data() + m.fft_tab);
     }
   }
   // posterior encoder (optional): packed only when every enc_q tensor was supplied

@@ -5,7 +5,9 @@ runs in ``vsp_denoise_rows``; the classes here drive an *engine* -- any object w
     denoise_history()                 (behind, ahead) = (n_fft - hop, n_fft - 1)
     denoise_complete(n_seen)          (optional) the outputs that are final once n_seen samples of an open stream are in
     denoise_rows(rows, bias)          rows of (x, first, out_first, out_count, total or -1, strength), x holding the
-                                      stream's samples [first, first + len(x)); bias [B, spec] -> the rows' outputs
+                                      stream's samples [first, first + len(x)); bias [B, spec] -> the rows' outputs;
+                                      called with transform="fft" for streams that carry it, and
+                                      with no keyword otherwise
 
 -- which is ``vispeech_amd.engine.Engine`` in production and a numpy stand-in in the host tests.
 
@@ -39,10 +41,14 @@ class Stream:
     ``push(x, final=True)`` returns the rest up to the stream's end (x may be empty), reflected there as the one-shot call
     reflects.  Between pushes the stream keeps the ``behind`` samples before ``out_next`` and those after it (``buf``, which
     starts at sample ``first``; on the device for device input).  A stream that ends at ``pad`` samples or fewer, for which
-    the reflection is undefined, returns its own samples."""
+    the reflection is undefined, returns its own samples.  ``transform``: ``"dft"`` or ``"fft"``, the transform of every call
+    the stream makes (``bias_row`` should come from the same one)."""
 
-    def __init__(self, engine, bias_row, strength: float = 0.01):
+    def __init__(self, engine, bias_row, strength: float = 0.01, transform: str = "dft"):
         self.eng, self.bias, self.strength = engine, bias_row, float(strength)
+        if transform not in ("dft", "fft"):
+            raise ValueError(f"denoiser.Stream: transform must be 'dft' or 'fft', not {transform!r}")
+        self.transform = transform
         if not (self.strength >= 0.0 and np.isfinite(self.strength)):
             raise ValueError("denoiser.Stream: the strength is a finite number, at least 0")
         self.behind, self.ahead = engine.denoise_history()
@@ -90,18 +96,23 @@ class Stream:
 def push_rows(engine, pushes: Sequence[tuple]) -> List:
     """Several streams advance in ONE ``denoise_rows`` call: ``pushes`` is ``[(stream, x, final), ...]``, each stream at its
     own position with its own bias and strength.  Returns, per push, the samples it completes (an empty array where it
-    completes none).  No call is made when no push completes a sample."""
+    completes none).  No call is made when no push completes a sample.  The call runs under the streams' transform; streams
+    that disagree are refused."""
     if not pushes:
         return []
     if len({id(s) for s, _, _ in pushes}) != len(pushes):
         raise ValueError("denoiser.push_rows: a stream advances once per call")
     if any(s.ended for s, _, _ in pushes):
         raise ValueError("denoiser.Stream: pushed after its final push")
+    transforms = {s.transform for s, _, _ in pushes}
+    if len(transforms) != 1:
+        raise ValueError("denoiser.push_rows: the streams of one call share one transform, not " + " and ".join(sorted(transforms)))
+    kw = {} if transforms == {"dft"} else {"transform": transforms.pop()}      # (the default makes the call it always made)
     rows = [s._take(x, final) for s, x, final in pushes]
     live = [i for i, r in enumerate(rows) if r is not None]
     outs = [None] * len(pushes)
     if live:
-        done = engine.denoise_rows([rows[i] for i in live], _stack([pushes[i][0].bias for i in live]))
+        done = engine.denoise_rows([rows[i] for i in live], _stack([pushes[i][0].bias for i in live]), **kw)
         for j, i in enumerate(live):
             outs[i] = done[j]
     return [s._advance(r, o) for (s, _, _), r, o in zip(pushes, rows, outs)]

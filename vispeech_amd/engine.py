@@ -2145,6 +2145,13 @@ class Engine:
         return o, gains, lufs, peak, blocks, mg
 
     # ------------------------------------------------------------------ denoiser and inverse STFT (section 4t)
+    def _set_transform(self, transform: str, what: str) -> None:
+        """``vsp_set_stft_transform`` right before a call: ``"dft"``, the two products, or ``"fft"``.
+        The workspace of the call is sized behind it, by the same switch."""
+        if transform not in _lib.STFT_TRANSFORMS:
+            raise ValueError(f"{what}: transform must be 'dft' or 'fft', not {transform!r}")
+        _lib.check(self.lib.vsp_set_stft_transform(self.ctx, _lib.STFT_TRANSFORMS[transform]), self.ctx, "vsp_set_stft_transform")
+
     def _denoise_ws(self, B: int, L_max: int, what: str) -> torch.Tensor:
         if int(self.dims.hop_length) != int(self.dims.total_upsample):
             raise ValueError(f"{what}: hop_length {self.dims.hop_length} is not the generator's total upsampling "
@@ -2155,7 +2162,7 @@ class Engine:
                              f"upsampling dividing n_fft at least four times), or B = {B} / L_max = {L_max} is out of range")
         return self._workspace("denoise", need)
 
-    def denoise_bias(self, g) -> torch.Tensor:
+    def denoise_bias(self, g, transform: str = "dft") -> torch.Tensor:
         """The denoiser's bias of conditioning vectors ``g`` [S, gin] (any: no row of ``emb_g`` is needed), [S, spec_channels]
         float32 on the device: the generator on ``back + 1 + fwd`` all-zero latent frames, its output frame ``back`` -- the
         steady period, without the start-up transient --, then ``vsp_denoise_bias``: the magnitude of the windowed DFT of
@@ -2168,10 +2175,11 @@ class Engine:
         z = torch.zeros((S, self.dims.inter_channels, back + 1 + fwd), dtype=torch.float32, device=self.device)
         o = self.generator(z, g)
         period = o[:, 0, back * up:(back + 1) * up].contiguous()
-        return self.denoise_bias_of(period)
+        return self.denoise_bias_of(period, transform=transform)
 
-    def denoise_bias_of(self, period) -> torch.Tensor:
+    def denoise_bias_of(self, period, transform: str = "dft") -> torch.Tensor:
         """``vsp_denoise_bias``: ``period`` [S, hop] float32 -> [S, spec_channels] on the device."""
+        self._set_transform(transform, "denoise_bias")
         p = _dev_f32(period, self.device)
         if p.dim() != 2 or p.shape[1] != self.dims.total_upsample or p.shape[0] < 1:
             raise ValueError(f"period must be [S, {self.dims.total_upsample}]")
@@ -2183,13 +2191,14 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_denoise_bias")
         return bias
 
-    def istft(self, ri, n_samples) -> torch.Tensor:
+    def istft(self, ri, n_samples, transform: str = "dft") -> torch.Tensor:
         """``vsp_istft``: ``ri`` [B, 2 spec_channels, T_max] (real rows, then imaginary; T_max the frames of the longest row)
         to audio [B, max(n_samples)] by weighted overlap-add; row b's first ``n_samples[b]`` samples are written, the rest
         is 0."""
         x = _dev_f32(ri, self.device)
         n_host = _host_list(n_samples)
         B, L_max = len(n_host), max(n_host)
+        self._set_transform(transform, "istft")
         ws = self._denoise_ws(B, L_max, "istft")
         T = self.convert_frames(L_max, self.dims.total_upsample)
         if x.dim() != 3 or tuple(x.shape) != (B, 2 * self.dims.spec_channels, T):
@@ -2201,11 +2210,13 @@ class Engine:
         _lib.check(rc, self.ctx, "vsp_istft")
         return out
 
-    def denoise(self, audio, n_samples, bias, strength, out=None) -> torch.Tensor:
+    def denoise(self, audio, n_samples, bias, strength, out=None, transform: str = "dft") -> torch.Tensor:
         """``vsp_denoise``: subtract ``strength[b] * bias[b]`` from the magnitude of every STFT frame of ``audio[b,
         :n_samples[b]]`` and return to audio.  ``bias`` [B, spec_channels] (row b's own); ``strength`` a scalar or one per
         row, None / NaN: the row is neither read nor written.  ``out`` None: in place where ``audio`` is a float32 device
-        tensor.  Nothing at or behind ``n_samples[b]`` is touched.  Returns ``out``."""
+        tensor.  Nothing at or behind ``n_samples[b]`` is touched.  Returns ``out``.  ``transform``: ``"dft"``, the two
+        products, or ``"fft"``, the in-LDS FFT (``bias`` should come from the same transform) -- as in
+        ``istft``, ``denoise_bias``, ``denoise_bias_of`` and ``denoise_rows``."""
         a, B, stride, n_host, _ = self._loudness_rows(audio, n_samples, None)
         o, _, o_stride, _, _ = self._loudness_rows(a if out is None else out, n_samples, None, "out")
         if out is not None and o is not out:
@@ -2217,6 +2228,7 @@ class Engine:
             if tuple(bp.shape) != (B, self.dims.spec_channels):
                 raise ValueError(f"bias must be [{B}, {self.dims.spec_channels}]")
         L_max = max(n_host)
+        self._set_transform(transform, "denoise")
         ws = self._denoise_ws(B, L_max, "denoise")
         with torch.cuda.device(self.device):
             rc = self.lib.vsp_denoise(self.ctx, self._stream(), B, L_max, _ptr(a), stride, (C.c_int64 * B)(*n_host), _ptr(bp),
@@ -2239,7 +2251,7 @@ class Engine:
             raise ValueError(f"denoise_complete({n_seen}): negative, or the context has no denoiser geometry")
         return e
 
-    def denoise_rows(self, rows, bias):
+    def denoise_rows(self, rows, bias, transform: str = "dft"):
         """``vsp_denoise_rows``: ONE call over rows ``(x, first, out_first, out_count, total, strength)`` -- ``x`` a 1-D
         float32 device tensor holding the stream's samples ``[first, first + len(x))``, ``total`` the stream's length or -1 /
         None, ``strength`` None / NaN for a row left alone -- each at its own position.  ``bias`` [B, spec_channels] (row
@@ -2270,6 +2282,7 @@ class Engine:
                                          o.data_ptr() if o.numel() else None, int(out_first), int(out_count),
                                          -1 if total is None else int(total), float("nan") if strength is None else float(strength))
         L_max = max(1, max(int(r[3]) for r in rows))
+        self._set_transform(transform, "denoise_rows")
         need = int(self.lib.vsp_denoise_rows_workspace_bytes(self.ctx, B, L_max))
         if need < 0:
             raise ValueError(f"denoise_rows: the context has no denoiser geometry (spec_channels > 1, hop = the generator's total "

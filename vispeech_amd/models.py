@@ -356,39 +356,48 @@ class SynthesizerTrn:
         return r["out"], r["c_db"]
 
     @torch.no_grad()
-    def denoiser_bias(self, sid):
+    def denoiser_bias(self, sid, transform="dft"):
         """The denoiser's bias of speakers ``sid``, ``[len(sid), spec_channels]`` float32 on the device:
         the magnitude spectrum of the steady period the generator lays under its output for ``g = emb_g[sid]``.  Built on
-        first use per speaker (one generator call on zeros for the speakers not seen yet), kept until ``load_state_dict``."""
+        first use per speaker (one generator call on zeros for the speakers not seen yet), kept until ``load_state_dict``.
+        ``transform``: ``"dft"`` or ``"fft"`` -- the table is keyed by ``(speaker, transform)``, so each
+        path subtracts a bias made by its own transform."""
+        if transform not in ("dft", "fft"):
+            raise ValueError(f"denoiser_bias: transform must be 'dft' or 'fft', not {transform!r}")
         ids = [int(s) for s in (sid.tolist() if hasattr(sid, "tolist") else sid)]
         table = self.__dict__.setdefault("_denoiser_bias", {})
-        new = sorted(set(ids) - set(table))
+        new = sorted(s for s in set(ids) if (s, transform) not in table)
+        kw = {} if transform == "dft" else {"transform": transform}      # (the default makes the call it always made)
         if new:
             if "emb_g.weight" not in self._state:
                 raise RuntimeError("denoiser_bias: no weights loaded")
-            rows = self._engine.denoise_bias(self._state["emb_g.weight"][new])
+            rows = self._engine.denoise_bias(self._state["emb_g.weight"][new], **kw)
             for i, s in enumerate(new):
-                table[s] = rows[i]
-        return torch.stack([table[s] for s in ids])
+                table[(s, transform)] = rows[i]
+        return torch.stack([table[(s, transform)] for s in ids])
 
     @torch.no_grad()
-    def denoise(self, audio, n_samples, sid, strength=0.01, out=None):
+    def denoise(self, audio, n_samples, sid, strength=0.01, out=None, transform="dft"):
         """Subtract ``strength`` times the speaker's own bias (``denoiser_bias``) from the magnitude of every STFT frame of
         ``audio[b, :n_samples[b]]`` and return to audio: the post-filter of the denoisers shipped
         with WaveGlow and HiFi-GAN, with the steady state as the bias.  ``sid`` per row; ``strength`` a scalar or one per
         row, None / NaN leaves the row alone.  In place where ``audio`` is a float32 tensor on the model's device and ``out``
-        is None.  Returns the audio."""
+        is None.  Returns the audio.  ``transform="fft"``: both the call and the bias on the in-LDS FFT
+        instead of the DFT products -- the same sums, other bits."""
         ids = [int(s) for s in (sid.tolist() if hasattr(sid, "tolist") else sid)]
-        return self._engine.denoise(audio, n_samples, self.denoiser_bias(ids), strength, out=out)
+        if transform == "dft":
+            return self._engine.denoise(audio, n_samples, self.denoiser_bias(ids), strength, out=out)
+        return self._engine.denoise(audio, n_samples, self.denoiser_bias(ids, transform), strength, out=out, transform=transform)
 
     @torch.no_grad()
-    def denoise_stream(self, sid, strength=0.01):
+    def denoise_stream(self, sid, strength=0.01, transform="dft"):
         """``denoise`` for audio that is still arriving: a ``vispeech_amd.denoiser.Stream`` with
         speaker ``sid``'s bias.  ``push(x)`` returns the denoised samples the pushes so far complete, ``push(x, final=True)``
         the rest; the pieces joined are the bits of ``denoise`` on the whole, at a delay of ``n_fft - hop`` to ``n_fft - 1``
-        samples.  Several streams advance in one call through ``denoiser.push_rows``."""
+        samples.  Several streams advance in one call through ``denoiser.push_rows``.  ``transform``: as in ``denoise``; the
+        stream carries it and its bias is that transform's."""
         from . import denoiser
-        return denoiser.Stream(self._engine, self.denoiser_bias([int(sid)])[0], strength)
+        return denoiser.Stream(self._engine, self.denoiser_bias([int(sid)], transform)[0], strength, transform=transform)
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)

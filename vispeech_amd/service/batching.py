@@ -60,6 +60,16 @@ def _loudness_spec(loudness):
     return (t, c, m)
 
 
+def _denoise_transform(value) -> str:
+    """A service's ``denoise_transform=``: None or ``"dft"`` -- the calls the service always made -- or ``"fft"`` (DESIGN.md
+    section 4v)."""
+    if value is None:
+        return "dft"
+    if value not in ("dft", "fft"):
+        raise ValueError(f"denoise_transform is 'dft' or 'fft', not {value!r}")
+    return value
+
+
 def _denoise_spec(value):
     """The strength of a request or service that names a denoiser (``SynthesizerTrn.denoise``): a
     finite number >= 0, ``True`` for 0.01; None / False: none."""
@@ -431,11 +441,13 @@ class BatchingSynthesisService:
     one makes ONE ``net.denoise`` call on the generator's output, in place, with the speaker's own bias (a conversion's:
     ``sid_tgt``), BEFORE the loudness call, the limiter and the encoding: what is measured and limited is what is delivered.
     The other rows carry a NaN strength and are neither read nor written, and so does a row too short for the reflection
-    at its ends (at most (n_fft - hop) / 2 samples); a batch in which nobody has one makes exactly the calls it made before."""
+    at its ends (at most (n_fft - hop) / 2 samples); a batch in which nobody has one makes exactly the calls it made before.
+    ``denoise_transform="fft"`` hands ``transform="fft"`` to that one call; a service that names none
+    makes the call, and delivers the bytes, it always did."""
 
     def __init__(self, net, max_batch: int = 16, max_wait_s: float = 0.005, noise_scale: float = 0.667, *, table=None,
                  spk2id=None, collate=None, output_rate: Optional[int] = None, sampling_rate: int = 44100, prosody_path=None,
-                 prosody_align=None, loudness=None, limiter=None, denoise=None):
+                 prosody_align=None, loudness=None, limiter=None, denoise=None, denoise_transform=None):
         if max_batch < 1 or max_wait_s < 0:
             raise ValueError("max_batch >= 1 and max_wait_s >= 0")
         self._collate = _collate_from(table, spk2id, collate)
@@ -455,6 +467,7 @@ class BatchingSynthesisService:
         self.limiter = limiter if limiter is not None and limiter is not False else None
         _limiter_spec(self.limiter, self.loudness, self.sampling_rate)             # (refused here, not in the worker)
         self.denoise = _denoise_spec(denoise)
+        self.denoise_transform = _denoise_transform(denoise_transform)
         if self.output_rate is not None:
             net._engine.configure_output(self.output_rate, in_rate=int(sampling_rate))
         self._q: "queue.Queue" = queue.Queue()
@@ -547,7 +560,8 @@ class BatchingSynthesisService:
         strength = [nan if r.denoise is None or int(n[b]) <= pad else r.denoise for b, r in enumerate(reqs)]
         if all(s != s for s in strength):
             return
-        self.net.denoise(waves, [max(int(v), 1) for v in n], [int(s) for s in sids], strength)
+        kw = {} if self.denoise_transform == "dft" else {"transform": self.denoise_transform}
+        self.net.denoise(waves, [max(int(v), 1) for v in n], [int(s) for s in sids], strength, **kw)
 
     def _loudness_of(self, loudness):
         return self.loudness if loudness is None else _loudness_spec(loudness)

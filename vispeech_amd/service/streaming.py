@@ -11,7 +11,7 @@ import numpy as np
 
 from .. import denoiser, input_stage, limiter, loudness, output_stage
 from ._pcm import Busy, _check_numerics, _host_i16
-from .batching import (_Conversion, _Request, _collate_from, _denoise_spec, _input_format, _limiter_spec, _output_format, _row_formats,
+from .batching import (_Conversion, _Request, _collate_from, _denoise_spec, _denoise_transform, _input_format, _limiter_spec, _output_format, _row_formats,
                        latents)
 
 
@@ -206,15 +206,17 @@ class StreamingBatchService:
     ``SynthesizerTrn.denoise`` on its whole waveform; its delay grows by ``n_fft - hop`` to ``n_fft - 1`` samples, and a tick
     in which its denoiser completes no sample delivers nothing for it.  ``fused_output=True`` refuses the keyword; a
     request that names nothing gets the bytes it always got, and a service in which nobody does makes the calls it always
-    made."""
+    made.  ``denoise_transform="fft"`` (round 27): the requests' streams, their biases and so the one
+    ``push_rows`` call per tick run on the in-LDS FFT; a service that names none makes the calls it always made."""
 
     def __init__(self, net, max_batch: int = 16, chunk_frames: int = 64, first_chunk_frames: Optional[int] = None,
                  noise_scale: float = 0.667, *, table=None, spk2id=None, collate=None, output_rate: Optional[int] = None,
                  sampling_rate: int = 44100, autostart: bool = True, fused_output: bool = False, loudness_gate: str = "exact",
-                 denoise=None):
+                 denoise=None, denoise_transform=None):
         if not 1 <= max_batch <= 64 or chunk_frames < 1:
             raise ValueError("1 <= max_batch <= 64 and chunk_frames >= 1")
         self.denoise = _denoise_spec(denoise)
+        self.denoise_transform = _denoise_transform(denoise_transform)
         if self.denoise is not None and fused_output:
             raise ValueError("fused_output delivers every row through its one launch: a denoiser needs fused_output=False")
         if loudness_gate not in loudness.GATES:
@@ -618,7 +620,11 @@ class StreamingBatchService:
                 r = reqs[b]
                 if r.den is None:
                     sid = r.sid_tgt if isinstance(r, _LiveRequest) else r.row.sid_tgt if r.is_conversion else r.sid
-                    r.den = denoiser.Stream(eng, self.net.denoiser_bias([sid])[0], r.denoise)
+                    if self.denoise_transform == "dft":
+                        r.den = denoiser.Stream(eng, self.net.denoiser_bias([sid])[0], r.denoise)
+                    else:
+                        r.den = denoiser.Stream(eng, self.net.denoiser_bias([sid], self.denoise_transform)[0], r.denoise,
+                                                transform=self.denoise_transform)
                 first[b] = r.den.out_next                               # the stages behind see the denoiser's samples
             for b, y in zip(denoised, denoiser.push_rows(eng, [(reqs[b].den, pieces[b], last[b]) for b in denoised])):
                 pieces[b] = y
